@@ -18,6 +18,9 @@ configs[2] (4096 x 10, interfrl and nofrl at replay capacity 100000) and configs
 with its own prewarm, warm-up and timed region of the same --steps (capped at 300), under also_measured.{config3_interfrl,
 config3_nofrl, config5}; `value` stays configs[1] interfrl (--no-extra-configs skips them).
 
+--dump-outputs DIR writes what the last timed step of the primary workload computed (dump_outputs()); its timed steps then start
+from a state fixed by the arguments, so two runs or two builds can be compared output for output.
+
 Without --mode the line carries BOTH workloads of the 4096 x 5 shape, measured one after the other in the same run:
 the primary one (PRIMARY_MODE) as `value`, the other under `also_measured`:
   * nofrl    -- the reference's default `fed_method` (src/config.py:25): 20480 independent agents, HBM-bound, no
@@ -99,6 +102,12 @@ def parse():
                          "a chip coming out of idle (trainer construction, ring fill) runs its first ~0.5 s 3-5 %% slow (clocks and power "
                          "state), so a short run -- --steps 20 --warmup 5 is 55 ms -- would time the ramp, not the workload; the line "
                          "records what was added (prewarm)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed for the primary workload (actions, next states, "
+                         "rewards, losses, gradients, weights, target weights) as DIR/<name>.npy in float32, at most 64 MB in all (an "
+                         "array over its share is a fixed, seeded sample of its elements). The primary workload's trainer is then built "
+                         "anew after the prewarm, so that its --warmup and --steps steps start from the state the arguments fix: the same "
+                         "arguments give the same inputs in every run, and two builds can be compared output for output")
     ap.add_argument("--weighted", action="store_true",
                     help="interfrl: weighted federated averaging (weighted_average_enabled, the Config default src/config.py:28; "
                          "workers/trainer.py:385-398) with the weights computed on the device from a ring of closed-episode rewards "
@@ -114,7 +123,10 @@ def parse():
                     help="run although AVD_* / AVDDPG_HIP_LIB environment overrides are set or the loaded library is a diagnostic "
                          "build (the line then lists them under env_overrides / diagnostic_library); without it bench.py refuses")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def cpu_baseline(seconds, pl_size, mode="nofrl"):
@@ -288,6 +300,37 @@ def spawn_ranks(args):
     return rc
 
 
+DUMP_BYTES = 60 << 20  # --dump-outputs: float32 payload of all arrays together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(vt, out_dir):
+    """--dump-outputs: what the last step left for a caller of VecTrainer.step() -- the actions taken, the states and rewards the
+    platoons moved to, the learn call's losses and gradients, the weights and target weights after the update -- as float32
+    out_dir/<name>.npy. An array over its share of DUMP_BYTES is cut to a fixed, seeded sample of its flattened elements (in index
+    order, the same elements in every run). Returns {name: {"shape": full shape, "elements": elements written}}."""
+    import numpy as np
+    import torch
+
+    if getattr(vt, "set_grads", None) is not None:  # the shared-set learners: one [M, theta] slab for the M sets
+        grads, losses = vt.set_grads, vt.set_losses
+    else:  # (the fused nofrl update keeps only a workspace in vt.grads: avd_learn_update_f32)
+        grads, losses = (None if vt.fused_update else vt.grads), vt.losses
+    arrays = {"actions": vt.actions, "states": vt.env.x, "rewards": vt.env.reward, "losses": losses, "grads": grads,
+              "theta": vt.agents.theta, "theta_target": vt.agents.theta_t}
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    share = DUMP_BYTES // (4 * len(arrays))
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().float()
+        if a.numel() > share:
+            idx = np.unique(np.random.RandomState(0).randint(0, a.numel(), size=share))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
+        written[name] = {"shape": list(t.shape), "elements": a.numel()}
+    return written
+
+
 def build_trainer(args, mode, engine, rank, group, ring=None):
     from avddpg_amd import config, trainer
 
@@ -306,23 +349,34 @@ def build_trainer(args, mode, engine, rank, group, ring=None):
                               overlap_allreduce=True if (args.overlap and mode == "interfrl" and group is not None and engine == "fused3") else None)
 
 
-def run_workload(args, mode, engine, rank, world, group, vt=None):
-    """Time args.steps steps of one workload (trainer `vt`, built here when not given); return the fields of the JSON line."""
+def run_workload(args, mode, engine, rank, world, group, built=None, dump=None):
+    """Time args.steps steps of one workload; return the fields of the JSON line. built: {mode: trainer} made beforehand, from which
+    this workload's trainer is TAKEN (popped here, not passed: an argument stays referenced by the caller for the whole call, and a
+    dump replaces the trainer after the prewarm; a 4096 x 10 nofrl trainer has no room for a second one); built here when absent.
+    dump: a directory for dump_outputs() of the last timed step."""
+    import gc
+
     import torch
 
     P, L = args.platoons, args.pl_size
+    vt = built.pop(mode, None) if built else None
     if vt is None:
         vt = build_trainer(args, mode, engine, rank, group)
     batched = vt.shared and vt.shared_engine in ("batched", "fused", "fused3")
     fset = vt.shared and vt.shared_engine in ("fused", "fused3")
     split3 = vt.shared and vt.shared_engine == "fused3"
-    # synthetic steady state: replay rings full of random-init-platoon-like rows
-    ring = vt.replay.ring
-    chunk = max(1, (1 << 28) // (ring.shape[1] * ring.shape[2]))
-    for a0 in range(0, ring.shape[0], chunk):
-        ring[a0:a0 + chunk].normal_(0.0, 1.0)
-    vt.replay.buffer_counter = args.buffer_size
-    vt.reset_episode()
+
+    def steady_state():
+        """synthetic steady state: replay rings full of random-init-platoon-like rows from a seeded stream, a new episode"""
+        ring = vt.replay.ring
+        gen = torch.Generator(device=ring.device).manual_seed(1 + rank)
+        chunk = max(1, (1 << 28) // (ring.shape[1] * ring.shape[2]))
+        for a0 in range(0, ring.shape[0], chunk):
+            ring[a0:a0 + chunk].normal_(0.0, 1.0, generator=gen)
+        vt.replay.buffer_counter = args.buffer_size
+        vt.reset_episode()
+
+    steady_state()
 
     # per-stage / per-kernel HIP events, each recorded on the stream its kernels are launched on
     names = ("act+env", "replay", "learn", "update", "learn+update", "allreduce")  # (allreduce: inside "learn"; its own events, on its stream)
@@ -375,7 +429,17 @@ def run_workload(args, mode, engine, rank, world, group, vt=None):
             one_step(False)
         torch.cuda.synchronize()
         prewarm_steps += 16
+    if prewarm_steps and dump:
+        # how far the prewarm moved the trainer depends on the wall clock: for a dump, the warm-up and timed steps run on a new trainer,
+        # in the state the arguments fix. The old one is freed first, so the new one gets the same blocks back from the caching
+        # allocator. (Not in plain runs: with the rebuild the 4096 x 5 interfrl step measured ~1 % slower.)
+        ring = vt.replay.ring
+        vt = None
+        gc.collect()
+        vt = build_trainer(args, mode, engine, rank, group, ring=ring)
+        steady_state()
     elapsed, stage_ms = timed_run(args.warmup, args.steps)
+    dumped = dump_outputs(vt, dump) if dump and rank == 0 else None
     # N > 1, split engine: time the OTHER collective form too (same trainer, same state), so that one multi-GPU run shows what the
     # overlap hides: forms.single = one all-reduce of the whole slab between learn and Adam; forms.overlapped = critic block on a side
     # stream under the actor phase + actor block on the main stream. `value` is the form the trainer runs: the single collective
@@ -626,6 +690,8 @@ def run_workload(args, mode, engine, rank, world, group, vt=None):
     }
     if plan:
         out["update_plan"] = plan
+    if dumped:
+        out["dump_outputs"] = {"dir": os.path.abspath(dump), "arrays": dumped}
     if rccl:
         out["rccl_ranks"] = world if args.backend == "nccl" else 0
         out["collective_backend"] = args.backend
@@ -728,6 +794,7 @@ def main():
                                   ["interfrl" if PRIMARY_MODE == "nofrl" else "nofrl"])
     # interfrl without --engine: the f32-class fused set learner where it exists (reference widths, decentralized)
     engine = args.engine or ("fused3" if (not args.hidden and args.framework == "decentralized") else None)
+    primary = modes[0]
     if os.environ.get("AVD_BENCH_ORDER") == "rev":  # diagnostics: measure the secondary workload first
         modes = modes[::-1]
     # Two workloads: BOTH trainers are built before anything is timed -- the one with per-agent slabs (nofrl: 25 GB of
@@ -743,7 +810,8 @@ def main():
     for i, m in enumerate(modes):
         if i:
             time.sleep(float(os.environ.get("AVD_BENCH_PAUSE", "1.0")))  # idle gap, outside both timed regions
-        results.append(run_workload(args, m, engine, rank, world, group, vt=trainers.pop(m, None)))
+        results.append(run_workload(args, m, engine, rank, world, group, built=trainers,
+                                    dump=args.dump_outputs if m == primary else None))
     if os.environ.get("AVD_BENCH_ORDER") == "rev":
         results = results[::-1]
 
@@ -763,12 +831,10 @@ def main():
         torch.cuda.empty_cache()
         sub = lambda **kw: argparse.Namespace(**{**vars(args), "steps": min(args.steps, 300), "warmup": min(args.warmup, 50), **kw})
         a3 = sub(pl_size=10)
-        t_nofrl = build_trainer(a3, "nofrl", None, rank, None)  # (per-agent slabs + the 164 GB ring first, on a clean heap)
-        t_inter = build_trainer(a3, "interfrl", "fused3", rank, None, ring=t_nofrl.replay.ring)
-        extras["config3_interfrl"] = run_workload(a3, "interfrl", "fused3", rank, world, None, vt=t_inter)
-        del t_inter
-        extras["config3_nofrl"] = run_workload(a3, "nofrl", None, rank, world, None, vt=t_nofrl)
-        del t_nofrl
+        t3 = {"nofrl": build_trainer(a3, "nofrl", None, rank, None)}  # (per-agent slabs + the 164 GB ring first, on a clean heap)
+        t3["interfrl"] = build_trainer(a3, "interfrl", "fused3", rank, None, ring=t3["nofrl"].replay.ring)
+        extras["config3_interfrl"] = run_workload(a3, "interfrl", "fused3", rank, world, None, built=t3)
+        extras["config3_nofrl"] = run_workload(a3, "nofrl", None, rank, world, None, built=t3)
         gc.collect()
         torch.cuda.empty_cache()
         a5 = sub(hidden=1024)

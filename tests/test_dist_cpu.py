@@ -149,14 +149,15 @@ def test_bench_self_spawns_its_ranks_as_children_without_a_launcher():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["AVD_BENCH_SPAWN_PROBE"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4"], env=env, capture_output=True, text=True,
-                       timeout=120)
-    assert p.returncode == 0, p.stderr
-    lines = [l for l in p.stdout.splitlines() if l.strip()]
-    assert len(lines) == 1  # rank 0 only
-    got = json.loads(lines[0])
-    assert got["RANK"] == "0" and got["LOCAL_RANK"] == "0" and got["WORLD_SIZE"] == "4" and got["MASTER_ADDR"] == "127.0.0.1"
-    assert int(got["MASTER_PORT"]) > 0
+    for n in (4, 8):  # 8: BASELINE configs[3]'s rank count
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n)], env=env, capture_output=True, text=True,
+                           timeout=120)
+        assert p.returncode == 0, p.stderr
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1  # rank 0 only
+        got = json.loads(lines[0])
+        assert got["RANK"] == "0" and got["LOCAL_RANK"] == "0" and got["WORLD_SIZE"] == str(n) and got["MASTER_ADDR"] == "127.0.0.1"
+        assert int(got["MASTER_PORT"]) > 0
     env["AVD_BENCH_SPAWN_PROBE"] = "fail1"
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2"], env=env, capture_output=True, text=True,
                        timeout=120)
