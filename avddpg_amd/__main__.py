@@ -48,6 +48,10 @@ def get_cmdl_args(argv, conf):
                          "episodes' rewards| from a device-side history, from step fed_weight_window x steps_per_episode on; conf.json "
                          "records the rule (episodes_mode, episode_clock)")
     tr.add_argument("--report_every", type=int, default=10000, help="--episodes platoon: steps per curve point")
+    tr.add_argument("--eval_platoons", type=str, default=None, metavar="N|all",
+                    help="--episodes platoon: also score the actors of the first N platoons (or all) at every curve point with one "
+                         "launch of the evaluator rollout kernel; adds the columns evaluator_mean,evaluator_min,evaluator_max to "
+                         "curve.csv (not in the reference CLI)")
     tr.add_argument("--save_platoons", type=int, default=None,
                     help="checkpoint the agents of the first N platoons only (default: all with --episodes reference, 4 with platoon)")
     tr.add_argument("--out", type=str, default=".outputs")
@@ -57,6 +61,12 @@ def get_cmdl_args(argv, conf):
     args = ap.parse_args(argv)
     if getattr(args, "save_platoons", None) is not None and args.save_platoons < 1:
         ap.error("--save_platoons must be >= 1 (esim reloads platoon 1's actors)")
+    ev = getattr(args, "eval_platoons", None)
+    if ev is not None:
+        if args.episodes != "platoon":
+            ap.error("--eval_platoons needs --episodes platoon")
+        if ev != "all" and not (ev.isdigit() and int(ev) >= 1):
+            ap.error("--eval_platoons takes a platoon count >= 1 or 'all'")
     return args, set_args_to_config(args, conf)
 
 
@@ -108,14 +118,23 @@ def main(argv=None, conf=None):
                 np.random.set_state(rng_state)
                 return float(r)
 
+            n_eval = None if args.eval_platoons is None else (vt.P if args.eval_platoons == "all" else min(vt.P, int(args.eval_platoons)))
+
+            def many():  # the first n_eval platoons' scores from one rollout launch: mean, min, max (evaluator.run_many)
+                if n_eval is None:
+                    return ""
+                sc = vt.evaluator_scores(range(n_eval))
+                return f",{float(np.mean(sc)):.3f},{float(np.min(sc)):.3f},{float(np.max(sc)):.3f}"
+
             with open(os.path.join(base, "curve.csv"), "w") as f:
-                f.write("step,episodes_closed,mean_episodic_reward,mean_episode_length,evaluator_score\n")
-                f.write(f"0,0,,,{score():.3f}\n")
+                extra = "" if n_eval is None else ",evaluator_mean,evaluator_min,evaluator_max"
+                f.write(f"step,episodes_closed,mean_episodic_reward,mean_episode_length,evaluator_score{extra}\n")
+                f.write(f"0,0,,,{score():.3f}{many()}\n")
                 for k in range(1, conf.total_time_steps + 1):
                     vt.step()
                     if k % args.report_every == 0 or k == conf.total_time_steps:
                         r, ln, n = vt.env.pop_episode_stats()
-                        f.write(f"{k},{n},{r:.5f},{ln:.2f},{score():.3f}\n")
+                        f.write(f"{k},{n},{r:.5f},{ln:.2f},{score():.3f}{many()}\n")
                         f.flush()
             if vt.nonfinite_updates():
                 print(f"warning: {vt.nonfinite_updates()} weight-set updates were skipped for non-finite gradients", file=sys.stderr)
@@ -123,6 +142,10 @@ def main(argv=None, conf=None):
             vt = trainer.VecTrainer(conf, rng=args.rng, auto_reset=False, shared_engine=args.engine)
             ep, avg = vt.run()
             artifacts.generate_csvs(base, conf, ep, avg)
+        # Trainer.run / run_simulations (workers/trainer.py:277-280, 537-550): every platoon's evaluator score / re_scalar and their
+        # average, written into conf.json (the evaluator reseeds the global legacy RNG; run_many puts it back)
+        conf.pl_rews_for_simulations = vt.run_simulations()
+        conf.pl_rew_for_simulation = float(np.average(conf.pl_rews_for_simulations))
         n_save = vt.P if args.save_platoons is None and args.episodes == "reference" else min(vt.P, 4 if args.save_platoons is None else args.save_platoons)
         artifacts.save_agents(base, vt.agents, n_save, vt.M, shared=vt.shared)
         # what ran, beside the reference's fields: how many platoons' agents the directory holds (esim loops over exactly these),

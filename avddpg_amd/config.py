@@ -57,6 +57,9 @@ class Config:
         self.tau = 0.001
         self.batch_size = 64
         self.buffer_size = 100000
+        # end-of-training simulation rewards (config.py:151-152), written by `tr` (workers/trainer.py:277-280)
+        self.pl_rew_for_simulation = 0
+        self.pl_rews_for_simulations = []
         # models (config.py:112-117)
         self.actor_layer1_size, self.actor_layer2_size = 256, 128
         self.critic_layer1_size, self.critic_act_layer_size, self.critic_layer2_size = 256, 48, 128

@@ -12,23 +12,31 @@ def get_number_of_timesteps_for_plot(conf, manual_timestep_override=None):
     return conf.steps_per_episode if manual_timestep_override is None else manual_timestep_override
 
 
-def run(conf=None, actors=None, pl_idx=None, seed=True, manual_timestep_override=None, set_mod=None, **_ignored):
-    """actors: an ``AgentGroup`` whose first ``pl_size`` weight sets are the platoon's vehicle actors (or whose
-    sets are addressed with ``set_mod``). Host-RNG parity mode: the global legacy RNG is seeded with
-    ``conf.evaluation_seed`` and consumed in the reference's order. Returns (pl_rew, traces)."""
+def _start(conf, seed=True, manual_timestep_override=None, evaluation_seed=None):
+    """The rollout's prelude (:44-60): seed the global legacy RNG with ``conf.evaluation_seed`` (or ``evaluation_seed``), the
+    evaluator platoon's constructor draws, the T leader-input draws, then reset(). Returns (env, float32 inputs [T], T);
+    env.x / env.prev_a hold the start state."""
     if seed:
-        np.random.seed(conf.evaluation_seed)  # rand.set_global_seed (src/rand.py:10)
-    L = conf.pl_size
-    env = vec.VecPlatoon(1, L, conf, evaluator_states_enabled=True, rng="host", track_aux=True)  # evaluator.py:47
+        np.random.seed(conf.evaluation_seed if evaluation_seed is None else evaluation_seed)  # rand.set_global_seed (src/rand.py:10)
+    env = vec.VecPlatoon(1, conf.pl_size, conf, evaluator_states_enabled=True, rng="host", track_aux=True)  # evaluator.py:47
     steps = get_number_of_timesteps_for_plot(conf, manual_timestep_override)
     rand = (lambda: np.random.uniform(-conf.reset_max_u, conf.reset_max_u)) if conf.rand_gen == conf.uniform else \
         (lambda: np.random.normal(0, conf.reset_max_u))
     inputs = np.array([rand() for _ in range(steps)], dtype=np.float32)  # :55-56
+    env.reset()
+    return env, inputs, steps
+
+
+def run(conf=None, actors=None, pl_idx=None, seed=True, manual_timestep_override=None, set_mod=None, **_ignored):
+    """actors: an ``AgentGroup`` whose first ``pl_size`` weight sets are the platoon's vehicle actors (or whose
+    sets are addressed with ``set_mod``). Host-RNG parity mode: the global legacy RNG is seeded with
+    ``conf.evaluation_seed`` and consumed in the reference's order. Returns (pl_rew, traces)."""
+    env, inputs, steps = _start(conf, seed, manual_timestep_override)
+    L = conf.pl_size
     d_inputs = torch.from_numpy(inputs).to(env.device)
     M, A = env.num_models, env.num_actions  # centralized: one model with L actions and a 4L-wide observation (:48, :58)
     xs = 4 * L // M
     counters = torch.zeros(M, dtype=torch.float32, device=env.device)  # float32 counters (:67)
-    env.reset()
     act = torch.zeros(1, L, dtype=torch.float32, device=env.device)
     raw = torch.zeros(M * A, dtype=torch.float32, device=env.device)
     sm = M if set_mod is None else set_mod
@@ -47,3 +55,101 @@ def run(conf=None, actors=None, pl_idx=None, seed=True, manual_timestep_override
     pl_rew = round(np.average(counters.cpu().numpy()), 3)  # np.float32 rounded in float32, as the reference (:145)
     return pl_rew, dict(states=states.cpu().numpy(), inputs=ctrl.cpu().numpy(), jerks=jerks.cpu().numpy(),
                         counters=counters.cpu().numpy(), leader=inputs)
+
+
+class RolloutBatch:
+    """The device inputs of one avd_eval_rollout_f32 launch (prepare_many); ``launch()`` enqueues it on the current stream,
+    ``results()`` reads the counters and traces back. run_many = prepare_many + launch + results."""
+
+    def __init__(self, conf, actors, platoons, set_mod, seeds, manual_timestep_override, trace):
+        platoons = [int(p) for p in platoons]
+        seeds = [int(conf.evaluation_seed)] if seeds is None else [int(s) for s in seeds]
+        if not platoons or not seeds:
+            raise ValueError("run_many needs at least one platoon and one seed")
+        NP, NS = len(platoons), len(seeds)
+        saved = np.random.get_state()
+        try:
+            starts = [_start(conf, True, manual_timestep_override, evaluation_seed=sd) for sd in seeds]
+        finally:
+            np.random.set_state(saved)
+        env, _, T = starts[0]
+        L, M = conf.pl_size, env.num_models
+        lay = actors.lay
+        if (lay.S, lay.A) != (env.num_states, env.num_actions):
+            raise ValueError(f"actors have S={lay.S} A={lay.A}, the platoon needs S={env.num_states} A={env.num_actions}")
+        shared = set_mod is not None and set_mod != 0
+        if shared and set_mod != M:
+            raise ValueError(f"set_mod={set_mod}: run_many addresses per-agent sets (None / 0) or shared sets (set_mod = M = {M})")
+        if not shared and min(platoons) < 0:
+            raise ValueError("negative platoon index")
+        need = M if shared else (max(platoons) + 1) * M
+        if need > actors.n_sets:
+            raise ValueError(f"platoons {platoons} need {need} weight sets, the group holds {actors.n_sets}")
+        # rollouts: shared sets one per seed (every platoon's result is the same), per-agent sets one per (platoon, seed)
+        self.roll = (lambda i, k: k) if shared else (lambda i, k: i * NS + k)
+        self.n_roll = NS if shared else NP * NS
+        want = []
+        for t in trace:
+            i, k = (int(t), 0) if np.isscalar(t) else (int(t[0]), int(t[1]))
+            if not (0 <= i < NP and 0 <= k < NS):
+                raise IndexError(f"trace entry {t} outside the [{NP}, {NS}] result")
+            want.append((i, k))
+        self.want, self.tr_roll = want, sorted({self.roll(i, k) for i, k in want})
+        dev, nt = env.device, len(self.tr_roll)
+        i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+        self.conf, self.actors, self.env, self.T, self.L, self.M, self.NP, self.NS = conf, actors, env, T, L, M, NP, NS
+        self.leader_h = [inp for _, inp, _ in starts]
+        self.x0 = torch.stack([e.x.reshape(L, 4) for e, _, _ in starts]).contiguous()
+        self.pa0 = torch.stack([e.prev_a.reshape(L) for e, _, _ in starts]).contiguous()
+        self.leader = torch.from_numpy(np.stack(self.leader_h)).to(dev)
+        self.set_base = torch.tensor([0] * NS if shared else [p * M for p in platoons for _ in seeds], **i32)
+        self.start_idx = torch.tensor(list(range(NS)) * (1 if shared else NP), **i32)
+        self.counters = torch.empty(self.n_roll, M, **f32)
+        self.tr_idx = torch.tensor(self.tr_roll, **i32) if nt else None
+        self.tr_s = torch.empty(nt, T, L, env.obs_width, **f32) if nt else None
+        self.tr_a = torch.empty(nt, T, L, **f32) if nt else None
+        self.tr_j = torch.empty(nt, T, L, **f32) if nt else None
+
+    def launch(self):
+        a, c = self.actors, self.conf
+        call("avd_eval_rollout_f32", a._layp, ptr(self.env.d_consts), self.n_roll, self.L, self.M, self.T, ptr(a.theta), ptr(a.stats),
+             a.n_sets, ptr(self.set_base), ptr(self.x0), ptr(self.pa0), ptr(self.leader), self.NS, ptr(self.start_idx), a.high,
+             c.action_low, c.action_high, c.sample_rate, ptr(self.counters), len(self.tr_roll), ptr(self.tr_idx), ptr(self.tr_s),
+             ptr(self.tr_a), ptr(self.tr_j), stream_handle())
+
+    def results(self):
+        c = self.counters.cpu().numpy()
+        rows = np.array([round(np.average(c[j]), 3) for j in range(self.n_roll)], dtype=np.float32)  # row by row, as run (:145)
+        sel = np.array([[self.roll(i, k) for k in range(self.NS)] for i in range(self.NP)])
+        scores, cnt = rows[sel], c[sel]
+        traces = {}
+        if self.tr_roll:
+            hs, ha, hj = self.tr_s.cpu().numpy(), self.tr_a.cpu().numpy(), self.tr_j.cpu().numpy()
+            for i, k in self.want:
+                j = self.tr_roll.index(self.roll(i, k))
+                traces[(i, k)] = dict(states=hs[j], inputs=ha[j], jerks=hj[j], counters=cnt[i, k].copy(), leader=self.leader_h[k])
+        return scores, cnt, traces
+
+
+def prepare_many(conf, actors, platoons, set_mod=None, seeds=None, manual_timestep_override=None, trace=()):
+    """run_many's host part (start states and leader inputs drawn, device inputs uploaded) as a RolloutBatch."""
+    return RolloutBatch(conf, actors, platoons, set_mod, seeds, manual_timestep_override, trace)
+
+
+def run_many(conf, actors, platoons, set_mod=None, seeds=None, manual_timestep_override=None, trace=()):
+    """The rollout of ``run`` for many platoons' actors and evaluation seeds at once: ONE launch of the evaluator rollout
+    kernel (avd_eval_rollout_f32, csrc/eval.hip), one workgroup per (platoon, seed). What Trainer.run_simulations
+    (workers/trainer.py:537-550) and esim (run.py:60-70) do platoon by platoon.
+
+    actors: an ``AgentGroup``. set_mod None (or 0): per-agent sets -- platoon p's M models are sets p*M .. p*M+M-1;
+    set_mod = M: shared sets -- every platoon uses sets 0 .. M-1 (its rollouts are then computed once per seed).
+    seeds: evaluation seeds (default ``(conf.evaluation_seed,)``); each one's start state and leader inputs are drawn on the
+    host exactly as ``run`` draws them, and the caller's global ``np.random`` state is restored on return.
+    trace: (i, k) index pairs into the result (or plain i for k = 0) whose per-step traces are returned.
+
+    Returns (scores, counters, traces): scores float32 [len(platoons), len(seeds)] (round(mean(counters), 3), :145),
+    counters float32 [len(platoons), len(seeds), M], traces {(i, k): dict like run's}. Entry [i, k] is bit-identical to
+    ``run`` with ``evaluation_seed = seeds[k]`` on platoon ``platoons[i]``'s sets."""
+    b = prepare_many(conf, actors, platoons, set_mod, seeds, manual_timestep_override, trace)
+    b.launch()
+    return b.results()

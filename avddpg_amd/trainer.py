@@ -598,6 +598,23 @@ class VecTrainer:
             self.update_reward_list(ep)
         return self.all_ep_reward_lists, self.all_avg_reward_lists
 
+    def evaluator_scores(self, platoons=None):
+        """workers/evaluator.py:145 score of the CURRENT actors of each of this rank's ``platoons`` (default: all), from one
+        launch of the evaluator rollout kernel (evaluator.run_many); float32 [len(platoons)]. Shared sets: one rollout."""
+        from . import evaluator
+
+        platoons = list(range(self.P)) if platoons is None else list(platoons)
+        if self.shared:
+            sc = evaluator.run_many(self.conf, self.agents, [0], set_mod=self.M)[0]
+            return np.repeat(sc[:, 0], len(platoons))
+        return evaluator.run_many(self.conf, self.agents, platoons)[0][:, 0]
+
+    def run_simulations(self):
+        """Trainer.run_simulations (workers/trainer.py:537-550): every local platoon's evaluator score over steps_per_episode
+        steps divided by re_scalar -- the values the reference appends to conf.pl_rews_for_simulations (:549). Plots and the
+        second, manual_timestep_override rollout are out of scope; a multi-rank run scores its own platoons."""
+        return [float(r / self.conf.re_scalar) for r in self.evaluator_scores()]
+
 
 class Trainer:
     """Reference-shaped facade (workers/trainer.py:18-61, 223): ``Trainer(base_dir, timestamp, debug_enabled,

@@ -418,6 +418,25 @@ int avd_actor_forward_shared_bf16(const avd_mlp_layout* lay, int n_agents, int n
                                   const float* stats, const float* state, float high, float* out, void* workspace,
                                   size_t workspace_bytes, void* stream);
 
+/* ---- evaluator rollout (workers/evaluator.py:40-95, 145; run once per platoon by Trainer.run_simulations,
+ *      workers/trainer.py:277-280, 537-550, and by esim, run.py:60-70) --------------------------------------------
+ * R noise-free, deterministic-start episodes of T steps in ONE launch (one workgroup per rollout, no communication
+ * between workgroups). Rollout r: models m = 0..M-1 use weight set set_base[r] + m (< n_sets); start state
+ * x0[start_idx[r]] [L][4], prev_a0[start_idx[r]] [L] and leader inputs leader[start_idx[r]] [T] (start_idx < n_start).
+ * Per step: actor forward of each model on its observation (4L / M floats apart, the first S read), action =
+ * clip(out, lo, hi), Platoon.step (= avd_env_step_f32), counters[r][m] += reward (M == L) or += the platoon-mean reward
+ * (M == 1, centralized). counters [R][M] are written, not accumulated. Bit-identical to the evaluator's per-step launches
+ * (avd_actor_forward_f32 -> avd_policy_f32 -> avd_env_step_f32, float32 counters).
+ * Traces for the n_trace rollouts trace_idx[j] (or n_trace = 0 and NULLs): tr_states [n_trace][T][L][min(4, S)] post-step
+ * observations, tr_actions [n_trace][T][L] clipped actions, tr_jerks [n_trace][T][L] = (x_before[2] - prev_a_before) *
+ * (1 / sample_rate) (Vehicle.get_jerk, environment.py:477). A set_base / start_idx out of range makes that rollout's
+ * counters NaN and reads nothing. M must be L or 1, lay->A * M == L. */
+int avd_eval_rollout_f32(const avd_mlp_layout* lay, const avd_env_consts* d_consts, int R, int L, int M, int T, const float* theta,
+                         const float* stats, int n_sets, const int32_t* set_base, const float* x0, const float* prev_a0,
+                         const float* leader, int n_start, const int32_t* start_idx, float high, float lo, float hi,
+                         float sample_rate, float* counters, int n_trace, const int32_t* trace_idx, float* tr_states,
+                         float* tr_actions, float* tr_jerks, void* stream);
+
 /* D[M][Nc] (f32, ldd) = A[M][K] . B[Nc][K]^T with bf16 operands (K contiguous, K % 64 == 0) and f32 accumulation: the
  * GEMM under avd_learn_shared_bf16, exposed for parity tests. A and B must be readable up to the next multiple of 256
  * rows. */
