@@ -10,6 +10,27 @@ import sys
 from .config import Config
 
 
+def parse_seeds(text):
+    """``--seeds`` value -> list of seeds: comma-separated non-negative integers and inclusive ranges ``a-b`` (``1,2,5-8`` ->
+    [1, 2, 5, 6, 7, 8]), in the order given; an empty item, a reversed range or a seed listed twice is a ValueError."""
+    out = []
+    for item in str(text).split(","):
+        item = item.strip()
+        lo, sep, hi = item.partition("-")
+        if not lo.isdigit() or (sep and not hi.isdigit()):
+            raise ValueError(f"--seeds: {item!r} is neither a seed nor a range a-b of non-negative integers")
+        a, b = int(lo), int(hi) if sep else int(lo)
+        if b < a:
+            raise ValueError(f"--seeds: the range {item!r} runs backwards")
+        out.extend(range(a, b + 1))
+    dup = sorted({k for k in out if out.count(k) > 1})
+    if dup:
+        raise ValueError(f"--seeds: seed(s) {dup} listed more than once")
+    if any(k >= 2 ** 32 for k in out):
+        raise ValueError("--seeds: seeds must be below 2**32 (the global np.random seed and the initial weights' RandomState take them)")
+    return out
+
+
 def get_cmdl_args(argv, conf):
     ap = argparse.ArgumentParser(prog="python -m avddpg_amd", description="avddpg hot path on MI355X")
     sub = ap.add_subparsers(dest="mode")
@@ -54,6 +75,12 @@ def get_cmdl_args(argv, conf):
                          "curve.csv (not in the reference CLI)")
     tr.add_argument("--save_platoons", type=int, default=None,
                     help="checkpoint the agents of the first N platoons only (default: all with --episodes reference, 4 with platoon)")
+    tr.add_argument("--seeds", type=str, default=None, metavar="LIST",
+                    help="--rng device --episodes platoon: train one independent experiment per seed (e.g. 1,2,5-8) in ONE process and "
+                         "launch chain; experiment k is bit-for-bit what `tr --seed k` trains alone wherever no set learner reduces over "
+                         "platoons (nofrl; interfrl --engine per_agent). Writes <out>/<timestamp>/seed<k>/ per seed (curve.csv, the "
+                         "actors, conf.json). Not with --seed, intrafrl, weights aggregation or the centralized framework (not in the "
+                         "reference CLI)")
     tr.add_argument("--out", type=str, default=".outputs")
     es = sub.add_parser("esim", help="run in evaluation/simulator mode")
     es.add_argument("exp_path", type=str)
@@ -61,6 +88,15 @@ def get_cmdl_args(argv, conf):
     args = ap.parse_args(argv)
     if getattr(args, "save_platoons", None) is not None and args.save_platoons < 1:
         ap.error("--save_platoons must be >= 1 (esim reloads platoon 1's actors)")
+    if getattr(args, "seeds", None) is not None:
+        if args.rng != "device" or args.episodes != "platoon":
+            ap.error("--seeds needs --rng device --episodes platoon")
+        if any(a == "--seed" or a.startswith("--seed=") for a in argv):
+            ap.error("--seeds and --seed are mutually exclusive")
+        try:
+            args.seeds = parse_seeds(args.seeds)
+        except ValueError as e:
+            ap.error(str(e))
     ev = getattr(args, "eval_platoons", None)
     if ev is not None:
         if args.episodes != "platoon":
@@ -99,6 +135,10 @@ def main(argv=None, conf=None):
         np.random.seed(conf.random_seed)  # rand.set_global_seed (src/rand.py:6-15)
         base = os.path.join(args.out, datetime.datetime.now().strftime("%y%m%d_%H%M%S"))
         os.makedirs(base, exist_ok=True)
+        if args.seeds is not None:
+            train_seed_batch(args, conf, base)
+            print(base)
+            return
         if args.episodes == "platoon":
             if args.rng != "device":
                 raise SystemExit("--episodes platoon needs --rng device")
@@ -178,6 +218,76 @@ def main(argv=None, conf=None):
             print(f"platoon {p}: cumulative platoon reward {rew}")
     else:
         raise SystemExit("modes: tr, esim")
+
+
+def train_seed_batch(args, conf, base):
+    """`tr --seeds`: the experiments of one VecTrainer(seeds=...) batch, each written to <base>/seed<k>/ exactly as `tr --seed k
+    --episodes platoon` writes its own directory (curve.csv, the saved agents, conf.json), plus conf.json's `seed_batch`. The curve
+    points' evaluator scores of all experiments come from ONE evaluator rollout launch (VecTrainer.evaluator_scores)."""
+    import copy
+
+    import numpy as np
+
+    from . import artifacts, trainer
+
+    seeds = list(args.seeds)
+    E = len(seeds)
+    try:
+        vt = trainer.VecTrainer(conf, rng="device", auto_reset="platoon", shared_engine=args.engine,
+                                fused_update=conf.fed_method == conf.nofrl, seeds=seeds)
+    except ValueError as e:
+        raise SystemExit(f"--seeds: {e}")
+    vt.reset_episode()
+    P = vt.P_exp
+    n_eval = None if args.eval_platoons is None else (P if args.eval_platoons == "all" else min(P, int(args.eval_platoons)))
+    dirs = [os.path.join(base, f"seed{k}") for k in seeds]
+    for d in dirs:
+        os.makedirs(d, exist_ok=True)
+
+    def points():  # per experiment: ",<platoon 1's score>[,mean,min,max of the first n_eval platoons]" from one rollout launch
+        sc = vt.evaluator_scores(range(max(1, n_eval or 1)))
+        out = []
+        for e in range(E):
+            line = f"{float(sc[e, 0]):.3f}"
+            if n_eval is not None:
+                row = sc[e, :n_eval]
+                line += f",{float(np.mean(row)):.3f},{float(np.min(row)):.3f},{float(np.max(row)):.3f}"
+            out.append(line)
+        return out
+
+    files = [open(os.path.join(d, "curve.csv"), "w") for d in dirs]
+    try:
+        extra = "" if n_eval is None else ",evaluator_mean,evaluator_min,evaluator_max"
+        for f, pt in zip(files, points()):
+            f.write(f"step,episodes_closed,mean_episodic_reward,mean_episode_length,evaluator_score{extra}\n")
+            f.write(f"0,0,,,{pt}\n")
+        for k in range(1, conf.total_time_steps + 1):
+            vt.step()
+            if k % args.report_every == 0 or k == conf.total_time_steps:
+                r, ln, n = vt.env.pop_episode_stats(per_experiment=True)
+                for e, (f, pt) in enumerate(zip(files, points())):
+                    f.write(f"{k},{int(n[e])},{float(r[e]):.5f},{float(ln[e]):.2f},{pt}\n")
+                    f.flush()
+    finally:
+        for f in files:
+            f.close()
+    if vt.nonfinite_updates():
+        print(f"warning: {vt.nonfinite_updates()} weight-set updates were skipped for non-finite gradients", file=sys.stderr)
+    sims = vt.run_simulations()  # [E][P], one rollout launch
+    n_save = min(P, 4 if args.save_platoons is None else args.save_platoons)
+    for e, (k, d) in enumerate(zip(seeds, dirs)):
+        artifacts.save_agents(d, vt.experiment_agents(e), n_save, vt.M, shared=vt.shared)
+        ce = copy.copy(conf)
+        ce.random_seed = k
+        ce.pl_rews_for_simulations = sims[e]
+        ce.pl_rew_for_simulation = float(np.average(sims[e]))
+        ce.saved_platoons = int(n_save)
+        ce.episodes_mode = "platoon"
+        ce.episode_clock = ("per-platoon episodes on the device; schedule predicates on step // steps_per_episode; weighted averaging "
+                            "(if enabled) from step weighted_window x steps_per_episode on, weights from each agent's last "
+                            "weighted_window closed episodes")
+        ce.seed_batch = seeds
+        artifacts.config_writer(os.path.join(d, "conf.json"), ce)
 
 
 if __name__ == "__main__":

@@ -11,6 +11,21 @@ namespace avd {
 
 constexpr int ENV_THREADS = 256;
 
+// Seed keys. G = false: one experiment, the scalar `seed` (the original entry points). G = true: a batch of E experiments whose
+// platoons are interleaved -- experiment e's platoon p is global platoon g = p*E + e -- and every draw of platoon g is made with
+// (seeds[g % E], the same call counter, the index the solo run of that experiment uses: platoon g / E). The choice is made at
+// compile time: the G = false kernels carry no extra branch, load or division.
+template <bool G>
+__device__ __forceinline__ int seed_key(uint64_t seed, const uint64_t* __restrict__ seeds, int E, int g, uint64_t& key) {
+    if constexpr (G) {
+        key = seeds[g % E];
+        return g / E;
+    } else {
+        key = seed;
+        return g;
+    }
+}
+
 struct EnvLds {
     float A[AVD_MAX_L][16];
     float B[AVD_MAX_L][4];
@@ -109,10 +124,11 @@ __global__ __launch_bounds__(ENV_THREADS) void env_step_kernel(const avd_env_con
 }
 
 // Fresh state of vehicle (p, i) (Vehicle.reset, environment.py:520-559; Platoon.reset :284-301) -- the draws only; the caller
-// chains a_lead = predecessor's fresh x[2] (:291-294).
+// chains a_lead = predecessor's fresh x[2] (:291-294). rv: the Philox index of the vehicle (v; in an experiment batch its index in
+// the solo run).
 __device__ __forceinline__ void reset_draws(const avd_env_consts* cst, int mode, const float* draws, const float* front_accel,
-                                            uint64_t seed, uint64_t counter, int p, int i, long v, float& d0, float& d1,
-                                            float& d2, float& fa) {
+                                            uint64_t seed, uint64_t counter, int p, int i, long v, uint32_t rv, float& d0,
+                                            float& d1, float& d2, float& fa) {
 #pragma clang fp contract(off)
     if (mode == 1) {  // evaluator constants (environment.py:534-539)
         d0 = cst->reset_ep_eval, d1 = cst->reset_ev_eval, d2 = cst->reset_a_eval;
@@ -121,8 +137,8 @@ __device__ __forceinline__ void reset_draws(const avd_env_consts* cst, int mode,
     } else if (draws) {  // host-RNG parity mode
         d0 = draws[v * 3 + 0], d1 = draws[v * 3 + 1], d2 = draws[v * 3 + 2];
     } else {  // device Philox (:547-549; util.py:67-70)
-        const u32x4 ra = philox_at(seed, counter, (uint32_t)v, STREAM_RESET_A);
-        const u32x4 rb = philox_at(seed, counter, (uint32_t)v, STREAM_RESET_B);
+        const u32x4 ra = philox_at(seed, counter, rv, STREAM_RESET_A);
+        const u32x4 rb = philox_at(seed, counter, rv, STREAM_RESET_B);
         if (cst->uniform_reset) {
             d0 = uniform_pm1(ra.x) * cst->reset_ep_max;
             d1 = uniform_pm1(ra.y) * cst->reset_max_ev;
@@ -139,19 +155,21 @@ __device__ __forceinline__ void reset_draws(const avd_env_consts* cst, int mode,
         if (front_accel) {
             fa = front_accel[p];
         } else {
-            const u32x4 rb = philox_at(seed, counter, (uint32_t)v, STREAM_RESET_B);
+            const u32x4 rb = philox_at(seed, counter, rv, STREAM_RESET_B);
             fa = (cst->uniform_reset ? uniform_pm1(rb.z) : box_muller(rb.z, rb.w, nullptr)) * cst->leader_reset_a;
         }
     }
 }
 
+template <bool G>
 __global__ __launch_bounds__(ENV_THREADS) void env_reset_kernel(const avd_env_consts* __restrict__ cst, int P, int L,
                                                                 float4* __restrict__ x, float* __restrict__ prev_a,
                                                                 float* __restrict__ cum_accel,
                                                                 const float* __restrict__ draws,
                                                                 const float* __restrict__ front_accel, int mode,
                                                                 uint64_t seed, uint64_t counter,
-                                                                const int32_t* __restrict__ cond) {
+                                                                const int32_t* __restrict__ cond,
+                                                                const uint64_t* __restrict__ seeds, int E) {
 #pragma clang fp contract(off)
     __shared__ float x2s[ENV_THREADS];
     if (cond && *cond == 0) return;  // uniform across the grid
@@ -163,7 +181,11 @@ __global__ __launch_bounds__(ENV_THREADS) void env_reset_kernel(const avd_env_co
     const bool active = (lp < pb) && (p < P);
     const long v = (long)p * L + i;
     float d0 = 0.f, d1 = 0.f, d2 = 0.f, fa = 0.f;
-    if (active) reset_draws(cst, mode, draws, front_accel, seed, counter, p, i, v, d0, d1, d2, fa);
+    if (active) {
+        uint64_t key;
+        const int pl = seed_key<G>(seed, seeds, E, p, key);
+        reset_draws(cst, mode, draws, front_accel, key, counter, p, i, v, G ? (uint32_t)((long)pl * L + i) : (uint32_t)v, d0, d1, d2, fa);
+    }
     x2s[tid] = d2;
     __syncthreads();
     if (active) {
@@ -183,6 +205,7 @@ __global__ __launch_bounds__(ENV_THREADS) void env_reset_kernel(const avd_env_co
 // device per step), the counters restart from 0 and the platoon gets fresh reset states (Platoon.reset, same draws as
 // env_reset_kernel at (seed, counter, vehicle)). *any_reset is set to 1 when any platoon was reset (the caller's "states changed
 // under the actor outputs" flag). One thread per vehicle, whole platoons per block.
+template <bool G>
 __global__ __launch_bounds__(ENV_THREADS) void episode_end_kernel(const avd_env_consts* __restrict__ cst, int P, int L, int M,
                                                                   float4* __restrict__ x, float* __restrict__ prev_a,
                                                                   float* __restrict__ cum_accel,
@@ -190,7 +213,8 @@ __global__ __launch_bounds__(ENV_THREADS) void episode_end_kernel(const avd_env_
                                                                   float* __restrict__ ep_reward, int limit,
                                                                   float* __restrict__ ret_sum, float* __restrict__ len_sum,
                                                                   int32_t* __restrict__ ep_cnt, int32_t* __restrict__ any_reset,
-                                                                  int mode, uint64_t seed, uint64_t counter) {
+                                                                  int mode, uint64_t seed, uint64_t counter,
+                                                                  const uint64_t* __restrict__ seeds, int E) {
 #pragma clang fp contract(off)
     __shared__ float x2s[ENV_THREADS];
     __shared__ float rs[ENV_THREADS];
@@ -208,7 +232,10 @@ __global__ __launch_bounds__(ENV_THREADS) void episode_end_kernel(const avd_env_
         len = ep_len[p] + 1;
         end = (done[p] != 0) || (len >= limit);
         if (end) {
-            reset_draws(cst, mode, nullptr, nullptr, seed, counter, p, i, v, d0, d1, d2, fa);
+            uint64_t key;
+            const int pl = seed_key<G>(seed, seeds, E, p, key);
+            reset_draws(cst, mode, nullptr, nullptr, key, counter, p, i, v, G ? (uint32_t)((long)pl * L + i) : (uint32_t)v, d0, d1, d2,
+                        fa);
             if (i < M) er = ep_reward[(long)p * M + i];
         }
     }
@@ -260,8 +287,11 @@ struct StepArgs {
     float* ring;  // [P*L][cap][2S+2] or NULL (no replay add)
     int cap, slot;
     float* ep_reward;  // [P*L] += reward, or NULL
+    const uint64_t* seeds;  // experiment batch (step_fused_kernel<true>): E seeds, platoon g draws with seeds[g % E]
+    int n_groups;
 };
 
+template <bool G>
 __global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs a) {
 #pragma clang fp contract(off)
     __shared__ float sA[AVD_MAX_L][16], sB[AVD_MAX_L][4], sC[AVD_MAX_L][4];
@@ -281,7 +311,9 @@ __global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs 
         xv = a.x_in[v];
         pa = a.prev_a[v];
         // OUActionNoise.__call__ (src/noise.py:15-19) and policy (agent/ddpgagent.py:22-27)
-        const u32x4 rn = philox_at(a.seed, a.ou_counter, (uint32_t)v, STREAM_OU);
+        uint64_t key;
+        const int pl = seed_key<G>(a.seed, a.seeds, a.n_groups, p, key);  // (the solo run's platoon index)
+        const u32x4 rn = philox_at(key, a.ou_counter, G ? (uint32_t)((long)pl * L + i) : (uint32_t)v, STREAM_OU);
         const float nrm = box_muller(rn.x, rn.y, nullptr);
         const float st = a.ou_state[v];
         const float noise = (st + (a.theta * (a.mean - st)) * a.dt) + a.scale * nrm;
@@ -289,7 +321,7 @@ __global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs 
         uu = fminf(fmaxf(a.actor_out[v] + noise, a.lo), a.hi);
         a.action[v] = uu;
         if (i == 0) {  // leader exog, redrawn every step (workers/trainer.py:291-295; util.get_random_val)
-            const u32x4 re = philox_at(a.seed, a.exog_counter, (uint32_t)p, STREAM_NORMAL);
+            const u32x4 re = philox_at(key, a.exog_counter, (uint32_t)pl, STREAM_NORMAL);
             exog_own = (a.exog_uniform ? uniform_pm1(re.x) : box_muller(re.x, re.y, nullptr)) * a.exog_scale;
             a.leader_exog[p] = exog_own;
         }
@@ -413,8 +445,8 @@ extern "C" int avd_env_reset_f32(const avd_env_consts* d_consts, int P, int L, f
     AVD_REQUIRE(mode >= 0 && mode <= 2, "avd_env_reset_f32: mode %d", mode);
     const int pb = ENV_THREADS / L;
     const int grid = (P + pb - 1) / pb;
-    hipLaunchKernelGGL(env_reset_kernel, dim3(grid), dim3(ENV_THREADS), 0, (hipStream_t)stream, d_consts, P, L,
-                       (float4*)x, prev_a, cum_accel, draws, front_accel, mode, seed, counter, cond);
+    hipLaunchKernelGGL(env_reset_kernel<false>, dim3(grid), dim3(ENV_THREADS), 0, (hipStream_t)stream, d_consts, P, L,
+                       (float4*)x, prev_a, cum_accel, draws, front_accel, mode, seed, counter, cond, nullptr, 1);
     return check_launch("avd_env_reset_f32");
 }
 
@@ -427,9 +459,9 @@ extern "C" int avd_episode_end_f32(const avd_env_consts* d_consts, int P, int L,
                 "avd_episode_end_f32: null pointer");
     AVD_REQUIRE(limit >= 1 && mode >= 0 && mode <= 2, "avd_episode_end_f32: limit=%d mode=%d", limit, mode);
     const int pb = ENV_THREADS / L;
-    hipLaunchKernelGGL(episode_end_kernel, dim3((P + pb - 1) / pb), dim3(ENV_THREADS), 0, (hipStream_t)stream, d_consts, P, L, M,
-                       (float4*)x, prev_a, cum_accel, done, ep_len, ep_reward, limit, ret_sum, len_sum, ep_cnt, any_reset, mode,
-                       seed, counter);
+    hipLaunchKernelGGL(episode_end_kernel<false>, dim3((P + pb - 1) / pb), dim3(ENV_THREADS), 0, (hipStream_t)stream, d_consts, P, L,
+                       M, (float4*)x, prev_a, cum_accel, done, ep_len, ep_reward, limit, ret_sum, len_sum, ep_cnt, any_reset, mode,
+                       seed, counter, nullptr, 1);
     return check_launch("avd_episode_end_f32");
 }
 
@@ -464,6 +496,32 @@ extern "C" int avd_uniform_f32(int n, float* out, float half_width, uint64_t see
     return check_launch("avd_uniform_f32");
 }
 
+// the two step_fused entry points: arguments checked, StepArgs filled, step_fused_kernel<G> launched
+template <bool G>
+static int step_fused_launch(const char* who, const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
+                             float* prev_a, float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done,
+                             int32_t* any_done_other, const float* actor_out, float* ou_state, float* action, float* leader_exog,
+                             float ou_theta, float ou_mean, float ou_dt, float ou_std_dev, float action_low, float action_high,
+                             float exog_scale, int exog_uniform, uint64_t seed, const uint64_t* d_seeds, int n_groups,
+                             uint64_t ou_counter, uint64_t exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward,
+                             void* stream) {
+    AVD_REQUIRE(P > 0 && L > 0 && L <= AVD_MAX_L && (S == 3 || S == 4), "%s: P=%d L=%d S=%d", who, P, L, S);
+    AVD_REQUIRE(d_consts && x_in && x_out && prev_a && reward && done && actor_out && ou_state && action && leader_exog,
+                "%s: null pointer", who);
+    AVD_REQUIRE(!ring || (cap > 0 && replay_counter >= 0), "%s: cap=%d counter=%ld", who, cap, (long)replay_counter);
+    StepArgs a;
+    a.cst = d_consts, a.P = P, a.L = L, a.S = S, a.x_in = (const float4*)x_in, a.x_out = (float4*)x_out, a.prev_a = prev_a;
+    a.cum_accel = cum_accel, a.reward = reward, a.term = term, a.done = done, a.any_done = any_done, a.any_done_other = any_done_other;
+    a.actor_out = actor_out, a.ou_state = ou_state, a.action = action, a.leader_exog = leader_exog;
+    a.theta = ou_theta, a.mean = ou_mean, a.dt = ou_dt, a.scale = ou_std_dev * (float)sqrt((double)ou_dt);  // as avd_ou_step_f32
+    a.lo = action_low, a.hi = action_high, a.exog_scale = exog_scale, a.exog_uniform = exog_uniform;
+    a.seed = seed, a.ou_counter = ou_counter, a.exog_counter = exog_counter, a.seeds = d_seeds, a.n_groups = n_groups;
+    a.ring = ring, a.cap = cap, a.slot = ring ? (int)(replay_counter % cap) : 0, a.ep_reward = ep_reward;
+    const int per_block = (ENV_THREADS / 64) * (64 / L);
+    hipLaunchKernelGGL(step_fused_kernel<G>, dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS), 0, (hipStream_t)stream, a);
+    return check_launch(who);
+}
+
 extern "C" int avd_step_fused_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
                                   float* prev_a, float* cum_accel, float* reward, uint8_t* term, uint8_t* done,
                                   int32_t* any_done, int32_t* any_done_other, const float* actor_out, float* ou_state,
@@ -471,19 +529,57 @@ extern "C" int avd_step_fused_f32(const avd_env_consts* d_consts, int P, int L, 
                                   float action_low, float action_high, float exog_scale, int exog_uniform, uint64_t seed,
                                   uint64_t ou_counter, uint64_t exog_counter, float* ring, int cap, int64_t replay_counter,
                                   float* ep_reward, void* stream) {
-    AVD_REQUIRE(P > 0 && L > 0 && L <= AVD_MAX_L && (S == 3 || S == 4), "avd_step_fused_f32: P=%d L=%d S=%d", P, L, S);
-    AVD_REQUIRE(d_consts && x_in && x_out && prev_a && reward && done && actor_out && ou_state && action && leader_exog,
-                "avd_step_fused_f32: null pointer");
-    AVD_REQUIRE(!ring || (cap > 0 && replay_counter >= 0), "avd_step_fused_f32: cap=%d counter=%ld", cap, (long)replay_counter);
-    StepArgs a;
-    a.cst = d_consts, a.P = P, a.L = L, a.S = S, a.x_in = (const float4*)x_in, a.x_out = (float4*)x_out, a.prev_a = prev_a;
-    a.cum_accel = cum_accel, a.reward = reward, a.term = term, a.done = done, a.any_done = any_done, a.any_done_other = any_done_other;
-    a.actor_out = actor_out, a.ou_state = ou_state, a.action = action, a.leader_exog = leader_exog;
-    a.theta = ou_theta, a.mean = ou_mean, a.dt = ou_dt, a.scale = ou_std_dev * (float)sqrt((double)ou_dt);  // as avd_ou_step_f32
-    a.lo = action_low, a.hi = action_high, a.exog_scale = exog_scale, a.exog_uniform = exog_uniform;
-    a.seed = seed, a.ou_counter = ou_counter, a.exog_counter = exog_counter;
-    a.ring = ring, a.cap = cap, a.slot = ring ? (int)(replay_counter % cap) : 0, a.ep_reward = ep_reward;
-    const int per_block = (ENV_THREADS / 64) * (64 / L);
-    hipLaunchKernelGGL(step_fused_kernel, dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS), 0, (hipStream_t)stream, a);
-    return check_launch("avd_step_fused_f32");
+    return step_fused_launch<false>("avd_step_fused_f32", d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done,
+                                    any_done, any_done_other, actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt,
+                                    ou_std_dev, action_low, action_high, exog_scale, exog_uniform, seed, nullptr, 1, ou_counter,
+                                    exog_counter, ring, cap, replay_counter, ep_reward, stream);
+}
+
+// ---- experiment batches: the draw kernels keyed by a device seed table (G = true) ----------------------------------------
+// P is the batch's platoon count (n_groups experiments x P / n_groups platoons each, interleaved: g = p*n_groups + e).
+#define AVD_REQUIRE_GROUPS(who, P)                                                                                            \
+    AVD_REQUIRE(d_seeds && n_groups >= 1 && (P) > 0 && (P) % n_groups == 0, "%s: d_seeds=%p n_groups=%d P=%d (P must be a " \
+                "multiple of n_groups)", who, (const void*)d_seeds, n_groups, (int)(P))
+
+extern "C" int avd_step_fused_seeds_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
+                                        float* prev_a, float* cum_accel, float* reward, uint8_t* term, uint8_t* done,
+                                        int32_t* any_done, int32_t* any_done_other, const float* actor_out, float* ou_state,
+                                        float* action, float* leader_exog, float ou_theta, float ou_mean, float ou_dt,
+                                        float ou_std_dev, float action_low, float action_high, float exog_scale, int exog_uniform,
+                                        const uint64_t* d_seeds, int n_groups, uint64_t ou_counter, uint64_t exog_counter,
+                                        float* ring, int cap, int64_t replay_counter, float* ep_reward, void* stream) {
+    AVD_REQUIRE_GROUPS("avd_step_fused_seeds_f32", P);
+    return step_fused_launch<true>("avd_step_fused_seeds_f32", d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done,
+                                   any_done, any_done_other, actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt,
+                                   ou_std_dev, action_low, action_high, exog_scale, exog_uniform, 0, d_seeds, n_groups, ou_counter,
+                                   exog_counter, ring, cap, replay_counter, ep_reward, stream);
+}
+
+extern "C" int avd_env_reset_seeds_f32(const avd_env_consts* d_consts, int P, int L, float* x, float* prev_a, float* cum_accel,
+                                       int mode, const uint64_t* d_seeds, int n_groups, uint64_t counter, const int32_t* cond,
+                                       void* stream) {
+    AVD_REQUIRE(P > 0 && L > 0 && L <= AVD_MAX_L, "avd_env_reset_seeds_f32: P=%d L=%d", P, L);
+    AVD_REQUIRE(d_consts && x && prev_a, "avd_env_reset_seeds_f32: null pointer");
+    AVD_REQUIRE(mode >= 0 && mode <= 2, "avd_env_reset_seeds_f32: mode %d", mode);
+    AVD_REQUIRE_GROUPS("avd_env_reset_seeds_f32", P);
+    const int pb = ENV_THREADS / L;
+    hipLaunchKernelGGL(env_reset_kernel<true>, dim3((P + pb - 1) / pb), dim3(ENV_THREADS), 0, (hipStream_t)stream, d_consts, P, L,
+                       (float4*)x, prev_a, cum_accel, nullptr, nullptr, mode, 0, counter, cond, d_seeds, n_groups);
+    return check_launch("avd_env_reset_seeds_f32");
+}
+
+extern "C" int avd_episode_end_seeds_f32(const avd_env_consts* d_consts, int P, int L, int M, float* x, float* prev_a,
+                                         float* cum_accel, const uint8_t* done, int32_t* ep_len, float* ep_reward, int limit,
+                                         float* ret_sum, float* len_sum, int32_t* ep_cnt, int32_t* any_reset, int mode,
+                                         const uint64_t* d_seeds, int n_groups, uint64_t counter, void* stream) {
+    AVD_REQUIRE(P > 0 && L > 0 && L <= AVD_MAX_L && M >= 1 && M <= L, "avd_episode_end_seeds_f32: P=%d L=%d M=%d", P, L, M);
+    AVD_REQUIRE(d_consts && x && prev_a && done && ep_len && ep_reward && ret_sum && len_sum && ep_cnt,
+                "avd_episode_end_seeds_f32: null pointer");
+    AVD_REQUIRE(limit >= 1 && mode >= 0 && mode <= 2, "avd_episode_end_seeds_f32: limit=%d mode=%d", limit, mode);
+    AVD_REQUIRE_GROUPS("avd_episode_end_seeds_f32", P);
+    const int pb = ENV_THREADS / L;
+    hipLaunchKernelGGL(episode_end_kernel<true>, dim3((P + pb - 1) / pb), dim3(ENV_THREADS), 0, (hipStream_t)stream, d_consts, P, L,
+                       M, (float4*)x, prev_a, cum_accel, done, ep_len, ep_reward, limit, ret_sum, len_sum, ep_cnt, any_reset, mode, 0,
+                       counter, d_seeds, n_groups);
+    return check_launch("avd_episode_end_seeds_f32");
 }

@@ -65,19 +65,30 @@ __global__ void replay_gather_kernel(int n_agents, int cap, int S, int A, int B,
 // ReplayBuffer.sample (src/replaybuffer.py:49-63) in one launch: a thread draws FOUR batch indices of an agent with one Philox
 // call -- the draws of replay_indices_kernel, bit for bit -- and moves their rows whole (8-byte pieces of the 40-byte rows,
 // 16-byte pieces out), instead of one thread per float behind a separate index kernel.
-template <int S>
+// G = true: an experiment batch (E experiments of M agents per platoon, platoons interleaved: agent v = (p*E + e)*M + m). The thread
+// of agent v's rows 4q..4q+3 draws with (seeds[e], counter, the thread index of the solo run: (p*M + m)*(B/4) + q). G = false: the
+// scalar seed, thread index t (no extra work).
+template <int S, bool G>
 __global__ __launch_bounds__(256) void replay_sample_kernel(int n_agents, int cap, int B, const float* __restrict__ ring,
                                                             uint32_t range, uint64_t seed, uint64_t counter,
                                                             int32_t* __restrict__ idx, float* __restrict__ s,
                                                             float* __restrict__ a, float* __restrict__ r,
-                                                            float* __restrict__ s2) {
+                                                            float* __restrict__ s2, const uint64_t* __restrict__ seeds, int E,
+                                                            int M) {
     constexpr int row = 2 * S + 2;
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long total = (long)n_agents * B, base = t * 4;
     if (base >= total) return;
-    const u32x4 rr = philox_at(seed, counter, (uint32_t)t, STREAM_REPLAY);
-    const uint32_t w[4] = {rr.x, rr.y, rr.z, rr.w};
     const int ag = (int)(base / B);  // B is a multiple of 4: the four rows belong to one agent
+    uint64_t key = seed;
+    uint32_t ti = (uint32_t)t;
+    if constexpr (G) {
+        const int g = ag / M, e = g % E;
+        key = seeds[e];
+        ti = (uint32_t)(((long)(g / E) * M + (ag - g * M)) * (B / 4) + (base - (long)ag * B) / 4);
+    }
+    const u32x4 rr = philox_at(key, counter, ti, STREAM_REPLAY);
+    const uint32_t w[4] = {rr.x, rr.y, rr.z, rr.w};
     int ix[4];
     float v[4][row];
 #pragma unroll
@@ -109,21 +120,39 @@ __global__ __launch_bounds__(256) void replay_sample_kernel(int n_agents, int ca
 
 using namespace avd;
 
-extern "C" int avd_replay_sample_f32(int n_agents, int cap, int S, int A, int B, const float* ring, int range, uint64_t seed,
-                                     uint64_t counter, int32_t* idx, float* s, float* a, float* r, float* s2, void* stream) {
+template <bool G>
+static int replay_sample_launch(const char* who, int n_agents, int cap, int S, int A, int B, const float* ring, int range, uint64_t seed,
+                                const uint64_t* d_seeds, int n_groups, int M, uint64_t counter, int32_t* idx, float* s, float* a,
+                                float* r, float* s2, void* stream) {
     AVD_REQUIRE(n_agents > 0 && cap > 0 && (S == 3 || S == 4) && A == 1 && B > 0 && B % 4 == 0 && range > 0 && range <= cap,
-                "avd_replay_sample_f32: n=%d cap=%d S=%d A=%d B=%d range=%d (S in {3, 4}, A = 1, B a multiple of 4)", n_agents, cap, S,
-                A, B, range);
-    AVD_REQUIRE(ring && idx && s && a && r && s2, "avd_replay_sample_f32: null pointer");
+                "%s: n=%d cap=%d S=%d A=%d B=%d range=%d (S in {3, 4}, A = 1, B a multiple of 4)", who, n_agents, cap, S, A, B, range);
+    AVD_REQUIRE(ring && idx && s && a && r && s2, "%s: null pointer", who);
     const long calls = (long)n_agents * B / 4;
     const dim3 grid((unsigned)((calls + 255) / 256));
     if (S == 4)
-        hipLaunchKernelGGL(replay_sample_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, n_agents, cap, B, ring, (uint32_t)range,
-                           seed, counter, idx, s, a, r, s2);
+        hipLaunchKernelGGL((replay_sample_kernel<4, G>), grid, dim3(256), 0, (hipStream_t)stream, n_agents, cap, B, ring, (uint32_t)range,
+                           seed, counter, idx, s, a, r, s2, d_seeds, n_groups, M);
     else
-        hipLaunchKernelGGL(replay_sample_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, n_agents, cap, B, ring, (uint32_t)range,
-                           seed, counter, idx, s, a, r, s2);
-    return check_launch("avd_replay_sample_f32");
+        hipLaunchKernelGGL((replay_sample_kernel<3, G>), grid, dim3(256), 0, (hipStream_t)stream, n_agents, cap, B, ring, (uint32_t)range,
+                           seed, counter, idx, s, a, r, s2, d_seeds, n_groups, M);
+    return check_launch(who);
+}
+
+extern "C" int avd_replay_sample_f32(int n_agents, int cap, int S, int A, int B, const float* ring, int range, uint64_t seed,
+                                     uint64_t counter, int32_t* idx, float* s, float* a, float* r, float* s2, void* stream) {
+    return replay_sample_launch<false>("avd_replay_sample_f32", n_agents, cap, S, A, B, ring, range, seed, nullptr, 1, 1, counter, idx, s,
+                                       a, r, s2, stream);
+}
+
+extern "C" int avd_replay_sample_seeds_f32(int n_agents, int cap, int S, int A, int B, const float* ring, int range,
+                                           const uint64_t* d_seeds, int n_groups, int agents_per_platoon, uint64_t counter, int32_t* idx,
+                                           float* s, float* a, float* r, float* s2, void* stream) {
+    AVD_REQUIRE(d_seeds && n_groups >= 1 && agents_per_platoon >= 1 && n_agents > 0 &&
+                    n_agents % ((long)n_groups * agents_per_platoon) == 0,
+                "avd_replay_sample_seeds_f32: d_seeds=%p n_groups=%d agents_per_platoon=%d n=%d (n must be a multiple of "
+                "n_groups x agents_per_platoon)", (const void*)d_seeds, n_groups, agents_per_platoon, n_agents);
+    return replay_sample_launch<true>("avd_replay_sample_seeds_f32", n_agents, cap, S, A, B, ring, range, 0, d_seeds, n_groups,
+                                      agents_per_platoon, counter, idx, s, a, r, s2, stream);
 }
 
 extern "C" int avd_replay_add_f32(int n_agents, int cap, int S, int A, float* ring, int64_t counter,

@@ -61,7 +61,7 @@ class RolloutBatch:
     """The device inputs of one avd_eval_rollout_f32 launch (prepare_many); ``launch()`` enqueues it on the current stream,
     ``results()`` reads the counters and traces back. run_many = prepare_many + launch + results."""
 
-    def __init__(self, conf, actors, platoons, set_mod, seeds, manual_timestep_override, trace):
+    def __init__(self, conf, actors, platoons, set_mod, seeds, manual_timestep_override, trace, set_bases=None):
         platoons = [int(p) for p in platoons]
         seeds = [int(conf.evaluation_seed)] if seeds is None else [int(s) for s in seeds]
         if not platoons or not seeds:
@@ -82,12 +82,18 @@ class RolloutBatch:
             raise ValueError(f"set_mod={set_mod}: run_many addresses per-agent sets (None / 0) or shared sets (set_mod = M = {M})")
         if not shared and min(platoons) < 0:
             raise ValueError("negative platoon index")
-        need = M if shared else (max(platoons) + 1) * M
+        if set_bases is not None:
+            set_bases = [int(b) for b in set_bases]
+            if not shared or len(set_bases) != NP or min(set_bases) < 0:
+                raise ValueError(f"set_bases={set_bases}: shared sets only (set_mod = M), one non-negative base per platoon entry")
+        need = (M + (max(set_bases) if set_bases else 0)) if shared else (max(platoons) + 1) * M
         if need > actors.n_sets:
             raise ValueError(f"platoons {platoons} need {need} weight sets, the group holds {actors.n_sets}")
-        # rollouts: shared sets one per seed (every platoon's result is the same), per-agent sets one per (platoon, seed)
-        self.roll = (lambda i, k: k) if shared else (lambda i, k: i * NS + k)
-        self.n_roll = NS if shared else NP * NS
+        # rollouts: shared sets one per seed (every platoon's result is the same) -- or, with set_bases, one per (entry, seed); per-agent
+        # sets one per (platoon, seed)
+        per_entry = not shared or set_bases is not None
+        self.roll = (lambda i, k: i * NS + k) if per_entry else (lambda i, k: k)
+        self.n_roll = NP * NS if per_entry else NS
         want = []
         for t in trace:
             i, k = (int(t), 0) if np.isscalar(t) else (int(t[0]), int(t[1]))
@@ -102,8 +108,11 @@ class RolloutBatch:
         self.x0 = torch.stack([e.x.reshape(L, 4) for e, _, _ in starts]).contiguous()
         self.pa0 = torch.stack([e.prev_a.reshape(L) for e, _, _ in starts]).contiguous()
         self.leader = torch.from_numpy(np.stack(self.leader_h)).to(dev)
-        self.set_base = torch.tensor([0] * NS if shared else [p * M for p in platoons for _ in seeds], **i32)
-        self.start_idx = torch.tensor(list(range(NS)) * (1 if shared else NP), **i32)
+        bases = [0] * NS if not per_entry else ([b for b in set_bases for _ in seeds] if shared else [p * M for p in platoons for _ in seeds])
+        self.set_base = torch.tensor(bases, **i32)
+        self.start_idx = torch.tensor(list(range(NS)) * (NP if per_entry else 1), **i32)
+        if self.set_base.numel() != self.n_roll or self.start_idx.numel() != self.n_roll:  # (the kernel reads both per rollout)
+            raise AssertionError(f"rollout tables of {self.set_base.numel()} / {self.start_idx.numel()} entries for {self.n_roll} rollouts")
         self.counters = torch.empty(self.n_roll, M, **f32)
         self.tr_idx = torch.tensor(self.tr_roll, **i32) if nt else None
         self.tr_s = torch.empty(nt, T, L, env.obs_width, **f32) if nt else None
@@ -131,18 +140,20 @@ class RolloutBatch:
         return scores, cnt, traces
 
 
-def prepare_many(conf, actors, platoons, set_mod=None, seeds=None, manual_timestep_override=None, trace=()):
+def prepare_many(conf, actors, platoons, set_mod=None, seeds=None, manual_timestep_override=None, trace=(), set_bases=None):
     """run_many's host part (start states and leader inputs drawn, device inputs uploaded) as a RolloutBatch."""
-    return RolloutBatch(conf, actors, platoons, set_mod, seeds, manual_timestep_override, trace)
+    return RolloutBatch(conf, actors, platoons, set_mod, seeds, manual_timestep_override, trace, set_bases)
 
 
-def run_many(conf, actors, platoons, set_mod=None, seeds=None, manual_timestep_override=None, trace=()):
+def run_many(conf, actors, platoons, set_mod=None, seeds=None, manual_timestep_override=None, trace=(), set_bases=None):
     """The rollout of ``run`` for many platoons' actors and evaluation seeds at once: ONE launch of the evaluator rollout
     kernel (avd_eval_rollout_f32, csrc/eval.hip), one workgroup per (platoon, seed). What Trainer.run_simulations
     (workers/trainer.py:537-550) and esim (run.py:60-70) do platoon by platoon.
 
     actors: an ``AgentGroup``. set_mod None (or 0): per-agent sets -- platoon p's M models are sets p*M .. p*M+M-1;
-    set_mod = M: shared sets -- every platoon uses sets 0 .. M-1 (its rollouts are then computed once per seed).
+    set_mod = M: shared sets -- every platoon uses sets 0 .. M-1 (its rollouts are then computed once per seed); with
+    set_bases (one per entry of ``platoons``) entry i uses sets set_bases[i] .. set_bases[i]+M-1 instead -- e.g. experiment e's sets
+    e*M .. of a seed batch (trainer.VecTrainer(seeds=...)).
     seeds: evaluation seeds (default ``(conf.evaluation_seed,)``); each one's start state and leader inputs are drawn on the
     host exactly as ``run`` draws them, and the caller's global ``np.random`` state is restored on return.
     trace: (i, k) index pairs into the result (or plain i for k = 0) whose per-step traces are returned.
@@ -150,6 +161,6 @@ def run_many(conf, actors, platoons, set_mod=None, seeds=None, manual_timestep_o
     Returns (scores, counters, traces): scores float32 [len(platoons), len(seeds)] (round(mean(counters), 3), :145),
     counters float32 [len(platoons), len(seeds), M], traces {(i, k): dict like run's}. Entry [i, k] is bit-identical to
     ``run`` with ``evaluation_seed = seeds[k]`` on platoon ``platoons[i]``'s sets."""
-    b = prepare_many(conf, actors, platoons, set_mod, seeds, manual_timestep_override, trace)
+    b = prepare_many(conf, actors, platoons, set_mod, seeds, manual_timestep_override, trace, set_bases)
     b.launch()
     return b.results()

@@ -62,10 +62,36 @@ def is_valid_step_for_federated_training_with_weights(conf, training_episode, tr
         is_valid_update_step(conf, training_step) and is_model_weight_updates_enabled(conf)
 
 
+def check_seed_batch(conf, rng, auto_reset, group, fused_step=None):
+    """Why a batch of experiments (VecTrainer(seeds=...)) cannot run with these settings, raised as a ValueError -- or None. Called
+    before anything is allocated or launched. A batch needs every draw keyed per experiment and nothing that couples experiments."""
+    if rng != "device":
+        raise ValueError("a seed batch needs rng='device': the host-RNG parity mode consumes one global np.random stream")
+    if auto_reset != "platoon":
+        raise ValueError("a seed batch needs per-platoon episodes (auto_reset='platoon', --episodes platoon): the reference rule "
+                         "(any terminal platoon ends the episode of all) would couple the experiments")
+    if conf.framework == conf.cntrl:
+        raise ValueError("a seed batch needs the decentralized framework: the centralized one has no fused step and its draw "
+                         "kernels have no seed table")
+    if conf.fed_method == conf.intrafrl:
+        raise ValueError("a seed batch covers nofrl and interfrl; intrafrl is not supported")
+    if is_fed_enabled(conf) and is_model_weight_updates_enabled(conf):
+        raise ValueError("a seed batch covers gradient aggregation only: weights aggregation writes one group's average into every "
+                         "agent (workers/trainer.py:442-446)")
+    if group is not None:
+        raise ValueError("a seed batch runs on one GPU: no process group")
+    if fused_step is not None and not fused_step:
+        raise ValueError("a seed batch needs the fused step (its draws are keyed per experiment; the separate draw kernels are not)")
+
+
+# The set learners' largest weight-set count (the shape checks of csrc/fset.hip and csrc/fsplit.hip); the others take any count.
+SET_ENGINE_MAX_SETS = {"fused": 64, "fused3": 64}
+
+
 class VecTrainer:
     def __init__(self, conf, device=None, rng="device", group=None, shared_sets=None, seed=None, auto_reset=False,
                  pipeline_chunks=1, fused_update=False, shared_engine=None, init_seed=None, fused_step=None,
-                 replay_ring=None, overlap_allreduce=None):
+                 replay_ring=None, overlap_allreduce=None, seeds=None):
         """group: torch.distributed process group whose ranks each hold ``conf.num_platoons`` platoons
         (interfrl gradients are all-reduced over it). auto_reset: end episodes on the device (no host
         sync per step); needs rng='device'. True: the reference's rule -- any terminal platoon (or the step limit) ends
@@ -75,13 +101,28 @@ class VecTrainer:
         the any-terminal rule cuts every episode to the first terminal among them.
         seed: this rank's env / noise / replay stream seed (give every rank its own). init_seed: seed of the initial
         weights, ``conf.random_seed`` by default -- rank-INVARIANT: every agent on every rank starts from the same
-        weights (workers/trainer.py:121-131); with a group they are broadcast from rank 0 as well."""
+        weights (workers/trainer.py:121-131); with a group they are broadcast from rank 0 as well.
+        seeds: a BATCH of len(seeds) = E independent experiments in one launch chain (exclusive with seed / init_seed): experiment e is
+        what VecTrainer(seed=seeds[e], init_seed=seeds[e]) computes alone (``python -m avddpg_amd tr --seed seeds[e]``), bit for bit
+        wherever no set learner reduces over platoons (nofrl, interfrl per_agent). Its conf.num_platoons platoons are interleaved with
+        the others': experiment e's platoon p is platoon p * E + e of the batch (self.P = E * conf.num_platoons), agent
+        (e, p, m) = (p * E + e) * M + m; shared weight sets: experiment e owns sets e*M .. e*M+M-1. check_seed_batch says what a batch
+        needs (device RNG, per-platoon episodes, decentralized nofrl / interfrl with gradients, one GPU)."""
         conf.refresh()
         self.conf, self.rng, self.group = conf, rng, group
         self.device = torch.device(device if device is not None else "cuda")
-        self.P, self.L = conf.num_platoons, conf.pl_size
-        seed = conf.random_seed if seed is None else seed
-        self.env = vec.VecPlatoon(self.P, self.L, conf, self.device, rand_states=conf.rand_states, rng=rng, seed=seed)
+        self.seeds = None
+        if seeds is not None:
+            if seed is not None or init_seed is not None:
+                raise ValueError("seeds= is mutually exclusive with seed= / init_seed=")
+            self.seeds = vec.seed_table(seeds, "cpu")[0]
+            check_seed_batch(conf, rng, auto_reset, group, fused_step)
+        self.E = 1 if self.seeds is None else len(self.seeds)
+        self.P, self.L = conf.num_platoons * self.E, conf.pl_size
+        self.P_exp = conf.num_platoons  # platoons per experiment
+        seed = (conf.random_seed if seed is None else seed) if self.seeds is None else None
+        self.env = vec.VecPlatoon(self.P, self.L, conf, self.device, rand_states=conf.rand_states, rng=rng, seed=seed or 0,
+                                  seeds=self.seeds)
         # models per platoon: L decentralized, 1 centralized (environment.py:35-42). The reference trainer iterates
         # conf.pl_size models (trainer.py:45) and therefore only completes a centralized step when pl_size == 1; for
         # pl_size > 1 this follows the loop shape of its evaluator (workers/evaluator.py:48-91: env.num_models).
@@ -96,7 +137,7 @@ class VecTrainer:
         self.x_stride = 4 * self.L // self.M  # floats between consecutive agents' observations in env.x
         n_agents = self.P * self.M
         self.n_agents = n_agents
-        self.ou = vec.VecOUNoise(n_agents, conf, self.device, rng=rng, seed=seed)
+        self.ou = vec.VecOUNoise(n_agents, conf, self.device, rng=rng, seed=seed or 0, seeds=self.seeds)
         fed = is_fed_enabled(conf)
         can_share = (fed and conf.fed_method == conf.interfrl and is_gradient_updates_enabled(conf)
                      and conf.fed_update_delay_steps == 1 and conf.fed_update_count == 1
@@ -104,16 +145,19 @@ class VecTrainer:
         self.shared = can_share if shared_sets is None else bool(shared_sets)
         if self.shared and not can_share:
             raise ValueError("shared weight sets are only exact for interfrl+gradients with every step federated")
-        self.set_mod = self.M if self.shared else 0
-        self.agents = vec.AgentGroup(self.M if self.shared else n_agents, self.S, self.A, conf, self.device,
-                                     seed=conf.random_seed if init_seed is None else init_seed,
-                                     hidd_mult=self.env.hidden_multiplier)
+        # the federated view [Pf, Mf]: (platoons, weight-set slots) of the per-set means -- with a seed batch the E experiments' M
+        # slots side by side (agent (e, p, m) is row p, slot e*M + m), so every mean runs over one experiment's platoons only
+        self.Pf, self.Mf = self.P_exp, self.E * self.M
+        self.set_mod = self.Mf if self.shared else 0
+        self.agents = vec.AgentGroup(self.Mf if self.shared else n_agents, self.S, self.A, conf, self.device,
+                                     seed=None if self.seeds else (conf.random_seed if init_seed is None else init_seed),
+                                     hidd_mult=self.env.hidden_multiplier, seeds=self.seeds, seed_block=self.M)
         from . import dist as _dist
         _dist.broadcast_agents(self.agents, group)
         # platoons over all ranks: a constant, reduced once here (the federated mean's divisor)
         self.total_platoons = _dist.total_platoons(self.P, group, self.device)
         self.replay = vec.VecReplay(n_agents, conf.buffer_size, conf.batch_size, self.S, self.A, self.device, rng=rng,
-                                    seed=seed, ring=replay_ring)
+                                    seed=seed or 0, ring=replay_ring, seeds=self.seeds, agents_per_platoon=self.M)
         f32 = dict(dtype=torch.float32, device=self.device)
         # Shared weight sets: "per_agent" = the f32 LDS-resident kernel per agent + fed_sum (exact f32, widths up to
         # 256); "batched" = one learn over each set's P x 64 rows as bf16 MFMA GEMMs (csrc/wide.hip; any width multiple
@@ -131,6 +175,9 @@ class VecTrainer:
         if self.shared_engine in ("fused", "fused3") and (lay.H1, lay.H2, lay.Ha, lay.A, lay.B) != (256, 128, 48, 1, 64):
             raise ValueError("shared_engine='fused' / 'fused3' (csrc/fset.hip, fsplit.hip) serve the reference widths 256/128/48, A = 1, batch 64 only; "
                              f"got {lay.H1}/{lay.H2}/{lay.Ha}, A = {lay.A}, batch {lay.B}: use shared_engine='batched'")
+        if self.seeds is not None and self.shared and self.Mf > SET_ENGINE_MAX_SETS.get(self.shared_engine, self.Mf):
+            raise ValueError(f"a seed batch of {self.E} experiments x {self.M} weight sets needs {self.Mf} sets; shared_engine="
+                             f"{self.shared_engine!r} takes at most {SET_ENGINE_MAX_SETS[self.shared_engine]}")
         self.actor_out = torch.zeros(n_agents, self.A, **f32)
         self.actions = torch.zeros(self.P, self.M, self.A, **f32)  # self.actions[p][m] (trainer.py:179)
         self.leader_exog = torch.zeros(self.P, **f32)
@@ -161,7 +208,7 @@ class VecTrainer:
             self._hist_ring = torch.zeros(n_agents, W, **f32)
             self._hist_cnt = torch.zeros(self.P, dtype=torch.int32, device=self.device)
             self._w_raw, self._aw = torch.ones(n_agents, **f32), torch.ones(n_agents, **f32)
-            self._wsum = torch.full((self.M,), float(self.P), **f32)
+            self._wsum = torch.full((self.Mf,), float(self.Pf), **f32)
         self.steps_total = 0  # training steps since construction (per-platoon episodes: the schedule's episode-equivalent clock)
         # fused_step: OU noise, policy clip, leader exog, platoon step, replay add and the reward counters in ONE launch
         # (avd_step_fused_f32; bit-identical to the separate kernels). Device-RNG mode, decentralized agents. Default: on
@@ -236,7 +283,7 @@ class VecTrainer:
         if self.shared and self.shared_engine == "batched" and self.agents.lay.H2 > 256:
             # wide shared sets: every agent re-reading its set's megabytes of weights is the wrong shape; one GEMM
             # chain per set instead (bf16 operands, like this engine's learner)
-            sm = self.env.x.view(P, M, 4)[..., :self.S].transpose(0, 1).contiguous()  # set-major [M, P, S]
+            sm = self.env.x.view(self.Pf, self.Mf, 4)[..., :self.S].transpose(0, 1).contiguous()  # set-major [M, P, S]
             o = self.agents.actor_shared(sm, P * M)
             self.actor_out.copy_(o.transpose(0, 1).reshape(P * M, 1))
         elif self._act_ready:
@@ -251,6 +298,8 @@ class VecTrainer:
         if self.fused_step:
             self._step_fused()
             return
+        if self.seeds is not None:
+            vec._no_scalar_draw("VecTrainer._act (separate draw kernels)")
         if self.rng == "host":
             # reference draw order per platoon: M OU normals, then the leader exog (trainer.py:286-295)
             normals = np.empty((P, M))
@@ -284,11 +333,13 @@ class VecTrainer:
         env.any_done = env._any_flags[k:k + 1]  # this step's flag (cleared by the previous step's launch, zero at start)
         other = env._any_flags[1 - k:2 - k]
         env.x, env.x_prev = env.x_prev, env.x
-        call("avd_step_fused_f32", ptr(env.d_consts), self.P, self.L, self.S, ptr(env.x_prev), ptr(env.x), ptr(env.prev_a),
+        # the seed argument: the scalar seed, or (a batch) the seed table and its length (avd_step_fused_seeds_f32)
+        fn, key = ("avd_step_fused_f32", (self.seed,)) if self.seeds is None else ("avd_step_fused_seeds_f32", (ptr(env.d_seeds), self.E))
+        call(fn, ptr(env.d_consts), self.P, self.L, self.S, ptr(env.x_prev), ptr(env.x), ptr(env.prev_a),
              ptr(env.cum_accel), ptr(env.reward), ptr(env.term), ptr(env.done), ptr(env.any_done), ptr(other),
              ptr(self.actor_out), ptr(ou.state), ptr(self.actions), ptr(self.leader_exog), conf.theta, ou.mean, conf.ou_dt,
              conf.std_dev, conf.action_low, conf.action_high, conf.reset_max_u, 1 if conf.rand_gen == conf.uniform else 0,
-             self.seed, ou.calls, self.exog_calls, ptr(rp.ring), rp.cap, rp.buffer_counter, ptr(self.ep_reward), stream_handle())
+             *key, ou.calls, self.exog_calls, ptr(rp.ring), rp.cap, rp.buffer_counter, ptr(self.ep_reward), stream_handle())
         ou.calls += 1
         self.exog_calls += 1
         env.step_count += 1
@@ -380,8 +431,9 @@ class VecTrainer:
     def _learn_batched(self, s, a, r, s2, weights=None):
         """interfrl with every step federated, shared sets: Trainer.learn + federated mean (trainer.py:400-431) as ONE
         learn over each set's P x B rows. The sampled batch is agent-major (agent v = p*M + m); the learner wants it
-        set-major. Across ranks the per-set means are combined like the per-agent path's sums (dist.exchange_fed_sums)."""
-        P, M, B = self.P, self.M, self.conf.batch_size
+        set-major. Across ranks the per-set means are combined like the per-agent path's sums (dist.exchange_fed_sums).
+        (P, M) is the federated view (Pf, Mf): a seed batch's experiments are E x M sets of P_exp platoons each.)"""
+        P, M, B = self.Pf, self.Mf, self.conf.batch_size
         sm = lambda x: x.view(P, M, *x.shape[1:]).transpose(0, 1).reshape(M, P * B, *x.shape[2:]).contiguous()
         if getattr(self, "set_grads", None) is None:
             from .dist import set_exchange_buffer
@@ -443,7 +495,7 @@ class VecTrainer:
                            lambda: learn("actor"), timers=self.timers, flag=flag)
 
     def _update(self, ep, i, fed):
-        conf, P, M = self.conf, self.P, self.M
+        conf, P, M = self.conf, self.Pf, self.Mf  # (the federated view: = P, M without a seed batch)
         if not fed or not is_valid_update_step(conf, i):
             # local update (:345-356); note the gate tests the step only, not the episode (SURVEY 8a FRL quirk)
             if self.shared:
@@ -567,7 +619,9 @@ class VecTrainer:
 
     def _refresh_weights(self, host_enabled):
         """trainer.py:385-398 on the device: w, the per-set sums and the learners' per-agent factors for the NEXT step's update."""
-        call("avd_fed_weights_f32", self.P, self.M, int(self.conf.weighted_window), ptr(self._hist_ring), ptr(self._hist_cnt),
+        # the federated view [Pf, Mf] (a seed batch: each per-set sum over one experiment's platoons; hist_cnt is read only by the
+        # all-platoons episode rule, host_enabled < 0, which a batch does not run)
+        call("avd_fed_weights_f32", self.Pf, self.Mf, int(self.conf.weighted_window), ptr(self._hist_ring), ptr(self._hist_cnt),
              int(host_enabled), ptr(self._w_raw), ptr(self._aw), ptr(self._wsum), stream_handle())
 
     def nonfinite_updates(self):
@@ -600,9 +654,18 @@ class VecTrainer:
 
     def evaluator_scores(self, platoons=None):
         """workers/evaluator.py:145 score of the CURRENT actors of each of this rank's ``platoons`` (default: all), from one
-        launch of the evaluator rollout kernel (evaluator.run_many); float32 [len(platoons)]. Shared sets: one rollout."""
+        launch of the evaluator rollout kernel (evaluator.run_many); float32 [len(platoons)]. Shared sets: one rollout.
+        A seed batch: ``platoons`` index each experiment's own platoons; float32 [E, len(platoons)], still one launch."""
         from . import evaluator
 
+        if self.seeds is not None:
+            E, M = self.E, self.M
+            platoons = list(range(self.P_exp)) if platoons is None else list(platoons)
+            if self.shared:  # one rollout per experiment, on its sets e*M .. e*M+M-1
+                sc = evaluator.run_many(self.conf, self.agents, list(range(E)), set_mod=M, set_bases=[e * M for e in range(E)])[0]
+                return np.repeat(sc[:, :1], len(platoons), axis=1)
+            glob = [vec.batch_platoon(e, p, E) for e in range(E) for p in platoons]
+            return evaluator.run_many(self.conf, self.agents, glob)[0][:, 0].reshape(E, len(platoons))
         platoons = list(range(self.P)) if platoons is None else list(platoons)
         if self.shared:
             sc = evaluator.run_many(self.conf, self.agents, [0], set_mod=self.M)[0]
@@ -612,8 +675,18 @@ class VecTrainer:
     def run_simulations(self):
         """Trainer.run_simulations (workers/trainer.py:537-550): every local platoon's evaluator score over steps_per_episode
         steps divided by re_scalar -- the values the reference appends to conf.pl_rews_for_simulations (:549). Plots and the
-        second, manual_timestep_override rollout are out of scope; a multi-rank run scores its own platoons."""
+        second, manual_timestep_override rollout are out of scope; a multi-rank run scores its own platoons.
+        A seed batch: one such list per experiment ([E][P_exp]), from one rollout launch."""
+        if self.seeds is not None:
+            return [[float(r / self.conf.re_scalar) for r in row] for row in self.evaluator_scores()]
         return [float(r / self.conf.re_scalar) for r in self.evaluator_scores()]
+
+    def experiment_agents(self, e):
+        """Experiment e's actors / critics (a seed batch) as an AgentGroup laid out like its solo run's (vec.AgentGroup.experiment_view):
+        what artifacts.save_agents and the evaluator take."""
+        if self.seeds is None:
+            raise ValueError("experiment_agents needs a seed batch (VecTrainer(seeds=...))")
+        return self.agents.experiment_view(e, self.E, self.M, self.shared)
 
 
 class Trainer:

@@ -23,15 +23,54 @@ def _dev(device):
     return torch.device(device if device is not None else "cuda")
 
 
+def seed_table(seeds, device):
+    """An experiment batch's seeds -> (tuple of ints, int64 device tensor with the uint64 bit patterns the *_seeds_* kernels read)."""
+    seeds = tuple(int(k) for k in seeds)
+    if not seeds:
+        raise ValueError("an experiment batch needs at least one seed")
+    if len(set(seeds)) != len(seeds):
+        raise ValueError(f"duplicate seeds in {list(seeds)}: the experiments would be identical")
+    if any(k < 0 or k >= 2 ** 64 for k in seeds):
+        raise ValueError(f"seeds must lie in [0, 2**64): {list(seeds)}")
+    bits = np.array(seeds, dtype=np.uint64).view(np.int64)
+    return seeds, torch.from_numpy(bits.copy()).to(device)
+
+
+def lane_of(g, E):
+    """Platoon g of a batch of E interleaved experiments -> (experiment, its platoon index in that experiment's solo run)."""
+    return g % E, g // E
+
+
+def batch_platoon(e, p, E):
+    """Experiment e's platoon p -> its platoon index in the batch (the inverse of lane_of)."""
+    return p * E + e
+
+
+def _no_scalar_draw(what):
+    raise _hip.AvdError(f"{what}: an experiment batch (seeds=...) draws only through the *_seeds_* kernels; this path would "
+                        "draw with one scalar seed for every experiment")
+
+
 class VecPlatoon:
     """P platoons of L vehicles. Batched ``Platoon`` (reference src/environment.py:8-301)."""
 
     def __init__(self, num_platoons, length, config, device=None, rand_states=True, evaluator_states_enabled=False,
-                 rng="host", seed=1, track_aux=False):
+                 rng="host", seed=1, track_aux=False, seeds=None):
+        """seeds: an experiment batch -- len(seeds) experiments of num_platoons / len(seeds) platoons each, interleaved (experiment e's
+        platoon p is platoon p * E + e), each drawing exactly what a solo VecPlatoon with seed=seeds[e] draws (device RNG only)."""
         self.P, self.L, self.config = int(num_platoons), int(length), config
         self.length = self.L
         self.device = _dev(device)
         self.rng, self.seed = rng, int(seed)
+        self.seeds = self.d_seeds = None
+        self.n_groups = 1
+        if seeds is not None:
+            if rng != "device":
+                raise ValueError("an experiment batch (seeds=...) needs rng='device'")
+            self.seeds, self.d_seeds = seed_table(seeds, self.device)
+            self.n_groups = len(self.seeds)
+            if self.P % self.n_groups:
+                raise ValueError(f"num_platoons={self.P} is not a multiple of the {self.n_groups} experiments")
         self.rand_states, self.evaluator_states_enabled = rand_states, evaluator_states_enabled
         centralized = config.framework == config.cntrl
         # attributes read by callers (environment.py:35-54)
@@ -100,6 +139,10 @@ class VecPlatoon:
         self._upload_reset(draws, self.front_accel)
 
     def _upload_reset(self, draws, fa, cond=None):
+        if self.seeds is not None:
+            call("avd_env_reset_seeds_f32", ptr(self.d_consts), self.P, self.L, ptr(self.x), ptr(self.prev_a), ptr(self.cum_accel),
+                 self._mode(), ptr(self.d_seeds), self.n_groups, self.reset_count, ptr(cond), stream_handle())
+            return
         d = torch.from_numpy(draws.astype(np.float32)).to(self.device) if draws is not None else None
         f = torch.from_numpy(np.asarray(fa, dtype=np.float32)).to(self.device) if fa is not None else None
         call("avd_env_reset_f32", ptr(self.d_consts), self.P, self.L, ptr(self.x), ptr(self.prev_a),
@@ -149,9 +192,14 @@ class VecPlatoon:
             raise ValueError("per-platoon episode ends need rng='device'")
         self.ensure_episode_state()
         st = self.ep_stats
-        call("avd_episode_end_f32", ptr(self.d_consts), self.P, self.L, M, ptr(self.x), ptr(self.prev_a), ptr(self.cum_accel),
-             ptr(self.done), ptr(self.ep_len), ptr(ep_reward), int(limit), ptr(st["ret_sum"]), ptr(st["len_sum"]),
-             ptr(st["count"]), ptr(any_reset), self._mode(), self.seed, self.reset_count, stream_handle())
+        if self.seeds is not None:
+            call("avd_episode_end_seeds_f32", ptr(self.d_consts), self.P, self.L, M, ptr(self.x), ptr(self.prev_a), ptr(self.cum_accel),
+                 ptr(self.done), ptr(self.ep_len), ptr(ep_reward), int(limit), ptr(st["ret_sum"]), ptr(st["len_sum"]),
+                 ptr(st["count"]), ptr(any_reset), self._mode(), ptr(self.d_seeds), self.n_groups, self.reset_count, stream_handle())
+        else:
+            call("avd_episode_end_f32", ptr(self.d_consts), self.P, self.L, M, ptr(self.x), ptr(self.prev_a), ptr(self.cum_accel),
+                 ptr(self.done), ptr(self.ep_len), ptr(ep_reward), int(limit), ptr(st["ret_sum"]), ptr(st["len_sum"]),
+                 ptr(st["count"]), ptr(any_reset), self._mode(), self.seed, self.reset_count, stream_handle())
         self.reset_count += 1
 
     def ensure_episode_state(self):
@@ -161,10 +209,22 @@ class VecPlatoon:
             self.ep_len = z(torch.int32)
             self.ep_stats = dict(ret_sum=z(torch.float32), len_sum=z(torch.float32), count=z(torch.int32))
 
-    def pop_episode_stats(self):
+    def pop_episode_stats(self, per_experiment=False):
         """(mean platoon-mean episodic reward, mean episode length, episodes closed) since the last call; clears the sums.
-        Host synchronisation: call it at reporting points, not per step."""
+        Host synchronisation: call it at reporting points, not per step.
+        per_experiment (experiment batch): the three as float64 / float64 / int64 arrays [E], entry e computed from experiment e's
+        platoons with the same reductions as a solo run's call (so bit-identical to it)."""
         st = self.ep_stats
+        if per_experiment:
+            E = self.n_groups
+            parts = [{k: t.view(-1, E)[:, e].contiguous() for k, t in st.items()} for e in range(E)]
+            n = np.array([int(q["count"].sum()) for q in parts], dtype=np.int64)
+            ret = np.array([float(q["ret_sum"].double().sum()) for q in parts])
+            ln = np.array([float(q["len_sum"].double().sum()) for q in parts])
+            for t in st.values():
+                t.zero_()
+            with np.errstate(invalid="ignore", divide="ignore"):
+                return np.where(n > 0, ret / np.maximum(n, 1), np.nan), np.where(n > 0, ln / np.maximum(n, 1), np.nan), n
         n = int(st["count"].sum())
         ret, ln = float(st["ret_sum"].double().sum()), float(st["len_sum"].double().sum())
         for t in st.values():
@@ -189,9 +249,14 @@ class VecPlatoon:
 class VecOUNoise:
     """n independent scalar OU processes (reference src/noise.py)."""
 
-    def __init__(self, n, config, device=None, rng="host", seed=1, mean=0.0):
+    def __init__(self, n, config, device=None, rng="host", seed=1, mean=0.0, seeds=None):
+        """seeds: an experiment batch's seed table (its draws happen inside avd_step_fused_seeds_f32, which advances ``calls``;
+        calling this object then raises)."""
         self.n, self.config, self.device = int(n), config, _dev(device)
         self.rng, self.seed, self.calls = rng, int(seed), 0
+        self.seeds = None if seeds is None else seed_table(seeds, "cpu")[0]
+        if self.seeds is not None and rng != "device":
+            raise ValueError("an experiment batch (seeds=...) needs rng='device'")
         self.mean = float(mean)  # the level every process reverts to (src/noise.py:7, 17; the reference trainer passes zeros)
         self.state = torch.zeros(self.n, dtype=torch.float32, device=self.device)  # x_prev = 0 (noise.py:29)
 
@@ -200,6 +265,8 @@ class VecOUNoise:
 
     def __call__(self, normals=None):
         """Advance all processes; ``normals`` [n] host array of N(0,1) draws (host-RNG mode)."""
+        if self.seeds is not None:
+            _no_scalar_draw("VecOUNoise()")
         c = self.config
         d_n = None
         if self.rng == "host":
@@ -216,13 +283,23 @@ class VecReplay:
     """One ring buffer per agent: ring[n_agents][cap][2S+A+1] float32 (reference src/replaybuffer.py)."""
 
     def __init__(self, n_agents, buffer_capacity, batch_size, num_states, num_actions, device=None, rng="host",
-                 seed=1, ring=None):
+                 seed=1, ring=None, seeds=None, agents_per_platoon=1):
         """ring: an existing [n_agents, capacity, 2S+A+1] float32 device tensor to use instead of allocating one (two trainers
-        of the same shape measured in one process share the 82 GB ring of BASELINE configs[1])."""
+        of the same shape measured in one process share the 82 GB ring of BASELINE configs[1]).
+        seeds: an experiment batch (agent v = (p*E + e) * agents_per_platoon + m belongs to experiment e): sample() draws through
+        avd_replay_sample_seeds_f32, each experiment's indices those of a solo VecReplay with seed=seeds[e]."""
         self.n, self.cap, self.B = int(n_agents), int(buffer_capacity), int(batch_size)
         self.S, self.A = int(num_states), int(num_actions)
         self.row = 2 * self.S + self.A + 1
         self.device, self.rng, self.seed = _dev(device), rng, int(seed)
+        self.seeds = self.d_seeds = None
+        self.agents_per_platoon = int(agents_per_platoon)
+        if seeds is not None:
+            if rng != "device":
+                raise ValueError("an experiment batch (seeds=...) needs rng='device'")
+            self.seeds, self.d_seeds = seed_table(seeds, self.device)
+            if self.n % (len(self.seeds) * self.agents_per_platoon):
+                raise ValueError(f"n_agents={self.n} is not a multiple of {len(self.seeds)} experiments x {self.agents_per_platoon} agents")
         if ring is not None:
             if tuple(ring.shape) != (self.n, self.cap, self.row) or ring.dtype != torch.float32 or not ring.is_contiguous():
                 raise _hip.AvdError(f"replay ring must be contiguous float32 {(self.n, self.cap, self.row)}, got {tuple(ring.shape)}")
@@ -249,6 +326,8 @@ class VecReplay:
 
     def draw_indices(self, host_idx=None):
         """host mode: np.random.choice(range, B) per agent in agent order (replaybuffer.py:54)."""
+        if self.seeds is not None:
+            _no_scalar_draw("VecReplay.draw_indices")
         if self.rng == "host":
             if host_idx is None:
                 rr = self.sample_range()
@@ -268,6 +347,14 @@ class VecReplay:
     def sample(self, host_idx=None):
         """ReplayBuffer.sample (src/replaybuffer.py:49-63). Device-RNG mode: index draw + row gather in ONE launch
         (avd_replay_sample_f32: the same Philox draws as draw_indices(), bit for bit, rows moved whole)."""
+        if self.seeds is not None:
+            if host_idx is not None or not (self.A == 1 and self.S in (3, 4) and self.B % 4 == 0):
+                _no_scalar_draw("VecReplay.sample (host indices, or a shape avd_replay_sample_seeds_f32 does not serve)")
+            call("avd_replay_sample_seeds_f32", self.n, self.cap, self.S, self.A, self.B, ptr(self.ring), self.sample_range(),
+                 ptr(self.d_seeds), len(self.seeds), self.agents_per_platoon, self.samples, ptr(self.idx), ptr(self.s), ptr(self.a),
+                 ptr(self.r), ptr(self.s2), stream_handle())
+            self.samples += 1
+            return self.s, self.a, self.r, self.s2
         if self.rng != "host" and host_idx is None and self.A == 1 and self.S in (3, 4) and self.B % 4 == 0:
             call("avd_replay_sample_f32", self.n, self.cap, self.S, self.A, self.B, ptr(self.ring), self.sample_range(), self.seed,
                  self.samples, ptr(self.idx), ptr(self.s), ptr(self.a), ptr(self.r), ptr(self.s2), stream_handle())
@@ -282,7 +369,11 @@ class AgentGroup:
     workers/trainer.py:100-139).  ``set_mod`` maps agent v to its weight set: 0 -> set v
     (one per agent, reference nofrl), M -> set v % M (shared per vehicle index)."""
 
-    def __init__(self, n_sets, num_states, num_actions, config, device=None, hidd_mult=1, seed=None, high_bound=None):
+    def __init__(self, n_sets, num_states, num_actions, config, device=None, hidd_mult=1, seed=None, high_bound=None, seeds=None,
+                 seed_block=1):
+        """seeds (an experiment batch; exclusive with seed): set j belongs to experiment (j // seed_block) % len(seeds) and starts from
+        the weights a group built with seed=seeds[e] starts from (seed_block = M: the interleaved layout of VecPlatoon(seeds=...) for
+        per-agent sets and for shared sets alike)."""
         c = config
         self.config, self.device, self.n_sets = c, _dev(device), int(n_sets)
         if (c.critic_layer1_size, c.critic_layer2_size) != (c.actor_layer1_size, c.actor_layer2_size):
@@ -303,11 +394,23 @@ class AgentGroup:
         self.v = torch.zeros(n, T, **f32)
         self.step = torch.zeros(n, dtype=torch.int32, device=self.device)
         self._layp = C.byref(self.lay)
-        rs = np.random.RandomState(c.random_seed if seed is None else seed)
-        th, st = params.init_weights(self.lay, rs, nominal=(c.actor_layer1_size, c.actor_layer2_size), dims=self.dims)
-        # every agent starts from agent (0,0)'s weights; targets copy their online nets (trainer.py:121-131)
-        self.theta.copy_(torch.from_numpy(th).to(self.device).expand(n, T))
-        self.stats.copy_(torch.from_numpy(st).to(self.device).expand(n, S))
+        if seeds is not None and seed is not None:
+            raise ValueError("AgentGroup: seed and seeds are mutually exclusive")
+        init = lambda k: params.init_weights(self.lay, np.random.RandomState(k), nominal=(c.actor_layer1_size, c.actor_layer2_size),
+                                             dims=self.dims)
+        if seeds is None:
+            th, st = init(c.random_seed if seed is None else seed)
+            # every agent starts from agent (0,0)'s weights; targets copy their online nets (trainer.py:121-131)
+            self.theta.copy_(torch.from_numpy(th).to(self.device).expand(n, T))
+            self.stats.copy_(torch.from_numpy(st).to(self.device).expand(n, S))
+        else:
+            E, blk = len(seeds), int(seed_block)
+            if n % (E * blk):
+                raise ValueError(f"AgentGroup: {n} sets are not a multiple of {E} experiments x {blk}")
+            for e, k in enumerate(seeds):  # each experiment's sets from its own seed, as its solo run
+                th, st = init(int(k))
+                self.theta.view(-1, E, blk, T)[:, e].copy_(torch.from_numpy(th).to(self.device).expand(n // (E * blk), blk, T))
+                self.stats.view(-1, E, blk, S)[:, e].copy_(torch.from_numpy(st).to(self.device).expand(n // (E * blk), blk, S))
         self.theta_t.copy_(self.theta)
         self.stats_t.copy_(self.stats)
 
@@ -603,6 +706,21 @@ class AgentGroup:
         done = torch.cuda.Event()
         done.record(side)
         main.wait_event(done)
+
+    def experiment_view(self, e, E, M, shared):
+        """Experiment e's weight sets of a batch of E interleaved experiments as an AgentGroup laid out like its solo run's: per-agent
+        sets -> the sets of its platoons in solo order (platoon p = sets p*M .. p*M+M-1; copied, they are strided in the batch), shared
+        sets -> its M sets (a view). For saving and the evaluator; the optimiser state is not carried over."""
+        import copy
+        g = copy.copy(self)
+        T, S = self.lay.theta_size, self.lay.stats_size
+        pick = (lambda x, w: x.view(E, M, w)[e]) if shared else (lambda x, w: x.view(-1, E, M, w)[:, e].reshape(-1, w).contiguous())
+        for name, w in (("theta", T), ("stats", S), ("theta_t", T), ("stats_t", S)):
+            setattr(g, name, pick(getattr(self, name), w))
+        g.n_sets = g.theta.shape[0]
+        for name in ("m", "v", "step", "theta_alt"):  # optimiser state stays with the batch
+            setattr(g, name, None)
+        return g
 
     # -- Keras-style weight access (host copies) ---------------------------------------------------
     def get_weights(self, set_idx, which, target=False, trainable_only=False):

@@ -328,6 +328,35 @@ int avd_step_fused_f32(const avd_env_consts* d_consts, int P, int L, int S, cons
 int avd_replay_sample_f32(int n_agents, int cap, int S, int A, int B, const float* ring, int range, uint64_t seed, uint64_t counter,
                           int32_t* idx, float* s, float* a, float* r, float* s2, void* stream);
 
+/* ---- experiment batches: many seeds in one launch chain (the reference runs one seed per process, src/config.py:136-137) ----
+ * E = n_groups independent experiments of P / E platoons each, their platoons INTERLEAVED: experiment e's platoon p is platoon
+ * g = p*E + e of the batch (agent (e, p, m) is v = g*M + m). d_seeds: E uint64 seeds in device memory. Every draw the solo run
+ * of experiment e makes with (seed, counter, index) is made here with (d_seeds[e], the same counter, the same index of that solo
+ * run): platoon g / E, vehicle (g / E)*L + i, replay thread ((g / E)*M + m)*(B/4) + q. So each experiment's slice of every
+ * output is bit-identical to the scalar entry point called with its own seed on its own P / E platoons, and with n_groups = 1 the
+ * result equals the scalar entry point's. Device-RNG mode only (no host draws). P (n_agents for the replay) must be a multiple of
+ * n_groups (of n_groups x agents_per_platoon). */
+/* avd_step_fused_f32 with a seed table: workers/trainer.py:282-322 (src/noise.py:15-19, src/environment.py:209-241,
+ * src/replaybuffer.py:36-47) for E experiments at once. */
+int avd_step_fused_seeds_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out, float* prev_a,
+                             float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done, int32_t* any_done_other,
+                             const float* actor_out, float* ou_state, float* action, float* leader_exog, float ou_theta,
+                             float ou_mean, float ou_dt, float ou_std_dev, float action_low, float action_high, float exog_scale,
+                             int exog_uniform, const uint64_t* d_seeds, int n_groups, uint64_t ou_counter, uint64_t exog_counter,
+                             float* ring, int cap, int64_t replay_counter, float* ep_reward, void* stream);
+/* avd_env_reset_f32 with a seed table (Platoon.reset, src/environment.py:284-301, 520-559; device draws only). */
+int avd_env_reset_seeds_f32(const avd_env_consts* d_consts, int P, int L, float* x, float* prev_a, float* cum_accel, int mode,
+                            const uint64_t* d_seeds, int n_groups, uint64_t counter, const int32_t* cond, void* stream);
+/* avd_episode_end_f32 with a seed table (workers/trainer.py:232-273 per platoon; the fresh states of src/environment.py:284-301). */
+int avd_episode_end_seeds_f32(const avd_env_consts* d_consts, int P, int L, int M, float* x, float* prev_a, float* cum_accel,
+                              const uint8_t* done, int32_t* ep_len, float* ep_reward, int limit, float* ret_sum, float* len_sum,
+                              int32_t* ep_cnt, int32_t* any_reset, int mode, const uint64_t* d_seeds, int n_groups, uint64_t counter,
+                              void* stream);
+/* avd_replay_sample_f32 with a seed table (ReplayBuffer.sample, src/replaybuffer.py:49-63); agents_per_platoon = M. */
+int avd_replay_sample_seeds_f32(int n_agents, int cap, int S, int A, int B, const float* ring, int range, const uint64_t* d_seeds,
+                                int n_groups, int agents_per_platoon, uint64_t counter, int32_t* idx, float* s, float* a, float* r,
+                                float* s2, void* stream);
+
 /* actor(state) for agents that SHARE n_sets weight sets (agent v uses set v % n_sets), reference widths, on the f32 matrix
  * cores (csrc/act.hip: v_mfma_f32_32x32x2_f32, exact f32 products -- agent/model.py:26-36 in the reference's arithmetic
  * class). Same values as avd_actor_forward_f32 with set_mod = n_sets up to the f32 summation order (1e-7 relative).
