@@ -14,8 +14,9 @@
 // Three structural facts keep this from costing 3x fset.hip:
 //   * the output layers are one unit wide, so the second-layer gradient is rank one times a mask:
 //         dZ2[row][n] = g3[row] * c3[n] * [z2[row][n] > 0]
-//     The mask (with the sign of g3) is EXACT in fp16: it is what the heads write (as fp16 +-1 / 0, "sm"), c3[n] is folded
-//     into the other operand (dx: W2c[f][n] = c3[n] W2[f][n], split once per call) or applied at the end (dw: finalize), and
+//     The mask (with the sign of g3) is EXACT in fp16. The heads write it as one bit per element ("sm", 16 B per row:
+//     HeadArgs::sm), and dw / dx / dxa expand it on staging to fp16 +-1 / 0, the sign taken from g3 (mask_chunk16, mask_pair);
+//     c3[n] is folded into the other operand (dx: W2c[f][n] = c3[n] W2[f][n], split once per call) or applied at the end (dw: finalize), and
 //     |g3[row]| is folded into the first-layer input (dw: relu(W1 (|g| x) + |g| b1) = |g| P1, one MFMA with split operands
 //     like every first layer here) or multiplied onto the f32 result (dx). dw and dx then need TWO MFMAs per product, and the
 //     heads split nothing on their way out.
@@ -408,7 +409,10 @@ struct HeadArgs {
     const float* yin;  // HEAD_BOTH: TD targets
     const float* aw;   // per-agent factor on the loss seeds (weighted federated mean) or NULL
     float* out;        // OUT_*: per-row result
-    f16* sm;           // HEAD_BOTH: sign(g3) * [z2 > 0] as fp16 +-1 / 0 (EXACT); OUT_TANH_SAVE: [z2 > 0] as 1 / 0; [n_agents][64][128]
+    unsigned* sm;      // HEAD_BOTH, OUT_TANH_SAVE: the relu mask [z2 > 0], one bit per element, [n_agents][64][4 words] (16 B per row;
+                       // no sign: the readers take sign(g3) from g3). Word t of a row covers features [32 t, 32 t + 32), pair-interleaved:
+                       // bit j = feature 32 t + 2 j, bit 16 + j = feature 32 t + 2 j + 1 (j = 0..15) -- so that fp16 pair j of a
+                       // 16-feature chunk is one AND and one v_mul_u32_u24 away (mask_pair)
     float* g3;         // HEAD_BOTH: the row factor of dZ2 [n_agents][64]
     float* dmu;        // HEAD_BOTH: dLa/dmu per row [n_agents][64]
     float* part_s;     // HEAD_*: [grid][8 waves][2] sums of the seeds and of the loss terms
@@ -565,24 +569,24 @@ __global__ __launch_bounds__(NT) void head_kernel(const HeadArgs p) {
             }
             return zp;
         };
-        // the relu mask of tile t as fp16 (a = z2 or relu(z2)): s16 = 0x3c00 (+1: unsigned, OUT_TANH_SAVE) or the seed's sign, 0x3c00 / 0xbc00
-        auto mask_t = [&](const f32x16& a, int t, unsigned s16, f16* dst) {
-            unsigned pk[4][2];
+        // the relu mask of tile t (a = z2 or relu(z2)) as this lane's half of the tile's packed word (HeadArgs::sm): the lane holds
+        // columns c = 8 g + 4 h + j, i.e. bits 4 g + 2 h + (j >> 1) + 16 (j & 1); built here as for h = 0 (mask_store shifts by 2 h)
+        auto mask_t = [&](const f32x16& a) {
+            unsigned b = 0;
 #pragma unroll
             for (int g = 0; g < 4; ++g)
 #pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const int i = 4 * g + 2 * e;
-                    pk[g][e] = (a[i] > 0.f ? s16 : 0u) | (a[i + 1] > 0.f ? s16 << 16 : 0u);
-                }
-#pragma unroll
-            for (int gg = 0; gg < 2; ++gg) {  // 16-byte row-major pieces: the row's two lanes cover 32 contiguous bytes
-                const auto s0 = __builtin_amdgcn_permlane32_swap(pk[2 * gg][0], pk[2 * gg + 1][0], false, false);
-                const auto s1 = __builtin_amdgcn_permlane32_swap(pk[2 * gg][1], pk[2 * gg + 1][1], false, false);
-                uint4 o;
-                o.x = s0[0], o.y = s1[0], o.z = s0[1], o.w = s1[1];
-                *(uint4*)(dst + 32 * t + 16 * gg) = o;
-            }
+                for (int j = 0; j < 4; ++j) b |= a[4 * g + j] > 0.f ? 1u << (4 * g + (j >> 1) + 16 * (j & 1)) : 0u;
+            return b;
+        };
+        // the row's four words (16 B) from the two lanes' halves: swapping (t, t + 2) across the lane halves leaves lane half h with
+        // the h = 0 half and the h = 1 half of word 2 h + (t & 1) -- as (own, partner's) in half 0, (partner's, own) in half 1
+        auto mask_store = [&](const unsigned (&b)[4], unsigned* dst) {
+            const auto s0 = __builtin_amdgcn_permlane32_swap(b[0], b[2], false, false);
+            const auto s1 = __builtin_amdgcn_permlane32_swap(b[1], b[3], false, false);
+            uint2 o;
+            o.x = s0[0] | (s0[1] << 2), o.y = s1[0] | (s1[1] << 2);
+            *(uint2*)(dst + 2 * h) = o;
         };
         auto out_z = [&](f32x16 (&ac)[4]) {  // relu in place, output layer: z = d3 + sum_n c3[n] relu(z2[n])
             float zp = 0.f;
@@ -700,10 +704,10 @@ __global__ __launch_bounds__(NT) void head_kernel(const HeadArgs p) {
                 const float diff = d3 + zp - ty, g3a = 2.f * diff * p.inv_n * tw;
                 if (h == 0) p.g3[ri] = g3a, Dacc += g3a, Lacc += diff * diff;
                 gmax = fmaxf(gmax, fabsf(g3a));
+                unsigned mb[4];
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    mask_t(acc[t], t, g3a < 0.f ? 0xbc00u : 0x3c00u, p.sm + ri * H2 + 8 * h);
-                }
+                for (int t = 0; t < 4; ++t) mb[t] = mask_t(acc[t]);
+                mask_store(mb, p.sm + ri * 4);
             }
             __builtin_amdgcn_sched_barrier(0);
             // ---- branch B: critic(s, mu) -> the actor loss -mean(q) and its gradient w.r.t. the action (:501-504)
@@ -767,13 +771,15 @@ __global__ __launch_bounds__(NT) void head_kernel(const HeadArgs p) {
             const float o = tanhf(z) * p.high;
             if (h == 0) p.out[ri] = o;
         } else if (MODE == OUT_TANH_SAVE) {
-            // mu = actor(s) AND what the actor's backward pass needs from this forward pass: the relu mask of z2 (fp16 1 / 0,
-            // UNSIGNED: the seed's sign is not known yet -- it rides on the row factor in dw / dx) and tanh(z). With them
+            // mu = actor(s) AND what the actor's backward pass needs from this forward pass: the relu mask of z2 (one bit per
+            // element; the seed's sign is not known yet -- it rides on the row factor in dw / dx) and tanh(z). With them
             // r03's HEAD_ACTOR launch -- the same 200 MFMAs per 32 rows once more, 239 us -- is not needed at all (r04).
             const float t = tanhf(z);
             if (h == 0) p.out[ri] = t * p.high, p.tz[ri] = t;
+            unsigned mb[4];
 #pragma unroll
-            for (int tt = 0; tt < 4; ++tt) mask_t(acc[tt], tt, 0x3c00u, p.sm + ri * H2 + 8 * h);
+            for (int tt = 0; tt < 4; ++tt) mb[tt] = mask_t(acc[tt]);
+            mask_store(mb, p.sm + ri * 4);
         } else {  // OUT_TD
             if (h == 0) p.out[ri] = ty + p.gamma * z;
         }
@@ -855,6 +861,19 @@ __device__ __forceinline__ float set_gscale(const float* part_m, int set, int n_
     return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(ldexpf(1.f, k))));  // (uniform: keep it in an SGPR)
 }
 
+// ---- the packed relu mask (HeadArgs::sm) back to fp16 -----------------------------------------------------------------------
+// fp16 pair j of a chunk whose word is already shifted so that its features' bits sit at j and 16 + j: low half = bit j, high half
+// = bit 16 + j, each m or 0, with mj = m >> j and m = 0x3c00 (+1) or 0xbc00 (-1). Exact: m has its low 10 bits clear (m >> j for
+// j <= 7 loses nothing), and both operands stay below 2^24 -- one v_and_b32 and one v_mul_u32_u24.
+__device__ __forceinline__ unsigned mask_pair(unsigned d, int j, unsigned mj) { return __umul24(d & (0x10001u << j), mj); }
+// the 16 features [16 c, 16 c + 16) of a row as 32 bytes of fp16 (the heads' old image, byte for byte): w = word c >> 1 of the row
+__device__ __forceinline__ void mask_chunk16(unsigned w, int c, unsigned m, uint4& lo, uint4& hi) {
+    const unsigned d = w >> (8 * (c & 1));
+    lo.x = mask_pair(d, 0, m), lo.y = mask_pair(d, 1, m >> 1), lo.z = mask_pair(d, 2, m >> 2), lo.w = mask_pair(d, 3, m >> 3);
+    hi.x = mask_pair(d, 4, m >> 4), hi.y = mask_pair(d, 5, m >> 5), hi.z = mask_pair(d, 6, m >> 6), hi.w = mask_pair(d, 7, m >> 7);
+}
+__device__ __forceinline__ unsigned mask_one(float g3, bool signed_) { return signed_ && g3 < 0.f ? 0xbc00u : 0x3c00u; }
+
 // ---- dw: G[f][n] += sum_rows (|g3| P1)[row][f] * sm[row][n] over all tiles of the workgroup -------------------------------
 struct DwArgs {
     NetP net;
@@ -863,8 +882,9 @@ struct DwArgs {
     const float* act;  // the critic's action input [n_agents][64]
     const float* g3;   // [n_agents][64]
     const float* part_m;  // [grid][8] max |g3| per wave of the kernel that wrote g3 (set_gscale)
-    const f16* sm;     // [n_agents][64][128] fp16 +-1 / 0 (critic: sign(g3) inside, HEAD_BOTH) or 1 / 0 (actor: OUT_TANH_SAVE; the sign of
-                       // g3 then goes onto the A operand: one v_xor per packed pair, from a per-row sign table in LDS)
+    const unsigned* sm;  // the packed relu mask of the head (HeadArgs::sm), expanded on staging to fp16 +-1 / 0 (critic: sign(g3) applied
+                       // there) or 1 / 0 (actor: the sign of g3 then goes onto the A operand: one v_xor per packed pair, from a per-row
+                       // sign table in LDS)
     float* partG;      // [grid][KG][128] (row K: the constant-one feature = sum over rows of g3 * mask -> db2 / c3)
     int abl;           // diagnostic build only (AVD_FSPLIT_ABL; 0 in the product): timing ablations with WRONG results -- 1: every tile
                        // fetch reads the workgroup's first tile (no HBM traffic), 2: no workgroup barrier in the tile loop
@@ -903,15 +923,21 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
 #pragma unroll
     for (int c = 0; c < XC; ++c) G1[c] = zero16;
 
-    // Staging. sm (335 MB per pass, from HBM): 64 rows x 8 chunks of 32 bytes, one chunk per thread, TWO tiles ahead in two
-    // register sets used alternately -- one tile of lookahead (~2.5 us) does not cover the tail of the HBM latency over 512
-    // threads and a barrier: measured, a third of the kernel was the wait for it (tools/fsplit_ablate.sh @ tag r06-pre-prune). The inputs
+    // Staging. sm (21 MB per pass, from HBM; 335 MB as fp16 before the one-bit image): 64 rows x 8 chunks of 16 features, one chunk
+    // per thread (a 32-bit word of the row, shared by two threads; critic: with its row's g3 for the sign), TWO tiles ahead in two
+    // register sets used alternately, expanded to 32 bytes of fp16 on the way into LDS (mask_chunk16: two VALU per fp16 pair; the
+    // critic's per-row sign adds the seven shifts of m). (fp16 image: one tile of lookahead did not cover the tail of the HBM latency over 512 threads and a barrier -- a
+    // third of the kernel was the wait for it, tools/fsplit_ablate.sh @ tag r06-pre-prune.) The inputs
     // (states, g3, actions: 31 MB, L2 / Infinity-Cache resident): one tile ahead, threads 0..127 build the |g3|-scaled fragment
     // of (row, lane half) = (tid >> 1, tid & 1) once per tile.
     const int srow = tid >> 3, sch = tid & 7, frow = tid >> 1, fh = tid & 1;
-    uint4 a0 = {}, a1 = {}, b0 = {}, b1 = {};
-    float sx[4] = {0.f, 0.f, 0.f, 0.f}, sg = 0.f, sa = 0.f;
-    auto smsrc = [&](int pl) { return (const uint4*)(p.sm + ((long)(((FSPLIT_ABL(p.abl) & 1) ? j0 : pl) * p.n_sets + set) * TILE + srow) * H2 + 16 * sch); };
+    unsigned ma = 0, mb = 0;
+    float sx[4] = {0.f, 0.f, 0.f, 0.f}, sg = 0.f, sa = 0.f, ga = 0.f, gb = 0.f;
+    auto fetch_m = [&](int pl, unsigned& m, float& g) {
+        const long ri = (long)(((FSPLIT_ABL(p.abl) & 1) ? j0 : pl) * p.n_sets + set) * TILE + srow;
+        m = p.sm[ri * 4 + (sch >> 1)];
+        if (NET::critic) g = p.g3[ri];
+    };
     auto fetch_x = [&](int pl) {
         if (pl >= P || tid >= 2 * TILE) return;
         const long ri = (long)(pl * p.n_sets + set) * TILE + frow;
@@ -919,10 +945,10 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
         sg = p.g3[ri];
         if (NET::critic) sa = p.act[ri];
     };
-    auto stage = [&](int pl, int buf, const uint4& d0, const uint4& d1) {
+    auto stage = [&](int pl, int buf, unsigned m, float g) {
         if (pl >= P) return;
         uint4* dst = (uint4*)(smimg[buf] + srow * LDZ + 16 * sch);
-        dst[0] = d0, dst[1] = d1;
+        mask_chunk16(m, sch, mask_one(g, NET::critic), dst[0], dst[1]);
         if (tid < 2 * TILE) {
             const float g = fabsf(sg) * gsc;  // in [0, 1)
             fq[buf][tid] = make_xg(g * sx[0], g * sx[1], g * sx[2], g * sx[3], g, fh);
@@ -1044,10 +1070,10 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
             }
         }
     };
-    if (j0 < P) a0 = smsrc(j0)[0], a1 = smsrc(j0)[1];
+    if (j0 < P) fetch_m(j0, ma, ga);
     fetch_x(j0);
-    if (j0 + J < P) b0 = smsrc(j0 + J)[0], b1 = smsrc(j0 + J)[1];
-    stage(j0, 0, a0, a1);
+    if (j0 + J < P) fetch_m(j0 + J, mb, gb);
+    stage(j0, 0, ma, ga);
     __syncthreads();
 #ifdef AVD_STAMP
     unsigned long long tacc[4] = {0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
@@ -1058,22 +1084,22 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
     for (int pi = j0; pi < P; pi += 2 * J) {
         // tile pi from buffer 0; set a takes tile pi + 2J; set b (tile pi + J) goes to buffer 1
         fetch_x(pi + J);
-        if (pi + 2 * J < P) a0 = smsrc(pi + 2 * J)[0], a1 = smsrc(pi + 2 * J)[1];
+        if (pi + 2 * J < P) fetch_m(pi + 2 * J, ma, ga);
         STAMP(0);
         compute(0);
         STAMP(1);
-        stage(pi + J, 1, b0, b1);
+        stage(pi + J, 1, mb, gb);
         STAMP(2);
         if (!(FSPLIT_ABL(p.abl) & 2)) __syncthreads();
         STAMP(3);
         if (pi + J < P) {
             // tile pi + J from buffer 1; set b takes tile pi + 3J; set a (tile pi + 2J) goes to buffer 0
             fetch_x(pi + 2 * J);
-            if (pi + 3 * J < P) b0 = smsrc(pi + 3 * J)[0], b1 = smsrc(pi + 3 * J)[1];
+            if (pi + 3 * J < P) fetch_m(pi + 3 * J, mb, gb);
             STAMP(0);
             compute(1);
             STAMP(1);
-            stage(pi + 2 * J, 0, a0, a1);
+            stage(pi + 2 * J, 0, ma, ga);
             STAMP(2);
             if (!(FSPLIT_ABL(p.abl) & 2)) __syncthreads();
             STAMP(3);
@@ -1122,8 +1148,8 @@ struct DxArgs {
     int L_cWa, L_cba;  // dxa_kernel: offsets of the critic's action-layer weights / bias inside net.th
     const float* g3;
     const float* part_m;  // [grid][8] max |g3| per wave of the kernel that wrote g3 (set_gscale)
-    const f16* sm;
-    int unsigned_mask;  // actor: sm holds 1 / 0 (OUT_TANH_SAVE), the row factor keeps the sign of g3; critic: sm holds sign(g3) inside
+    const unsigned* sm;  // the packed relu mask of the head (HeadArgs::sm)
+    int unsigned_mask;  // actor: the mask is staged as 1 / 0, the row factor keeps the sign of g3; critic: staged as sign(g3) * mask
     float* partV;      // [grid][KP][16]       sum_rows (dC * mask) * [x_hi | x_lo | 1] per feature
     int abl;           // diagnostic build only (see DwArgs)
     unsigned long long* stamp;  // diagnostic build (-DAVD_STAMP) only
@@ -1170,18 +1196,20 @@ __global__ __launch_bounds__(NT) void dx_kernel(const DxArgs p) {
         const int k = (i >> 5) & 31;
         (&xt[0][0][0])[i] = (f16)(k == 8 ? 1.f : 0.f);
     }
+    // sm: thread (srow, sch) expands features [16 sch, +16) of row srow (mask_chunk16; critic: signed by its row's g3, gs) into the
+    // fp16 image, one tile ahead like the rest
     const int srow = tid >> 3, sch = tid & 7;
-    uint4 d0 = {}, d1 = {};
-    float gn = 0.f;
+    unsigned dm = 0;
+    float gn = 0.f, gs = 0.f;
     auto fetch = [&](int agent) {
         if (FSPLIT_ABL(p.abl) & 1) agent = j0 * p.n_sets + set;
-        const uint4* src = (const uint4*)(p.sm + ((long)agent * TILE + srow) * H2 + 16 * sch);
-        d0 = src[0], d1 = src[1];
+        dm = p.sm[((long)agent * TILE + srow) * 4 + (sch >> 1)];
+        if (NET::critic) gs = p.g3[(long)agent * TILE + srow];
         if (tid < TILE) gn = p.g3[(long)agent * TILE + tid];
     };
     auto stage = [&](int buf) {
         uint4* dst = (uint4*)(smimg[buf] + srow * LDZ + 16 * sch);
-        dst[0] = d0, dst[1] = d1;
+        mask_chunk16(dm, sch, mask_one(gs, NET::critic), dst[0], dst[1]);
         if (tid < TILE) g3s[buf][tid] = (p.unsigned_mask ? gn : fabsf(gn)) * gv;
     };
     f16x8 xfn0 = {}, xfn1 = {};  // the rows' input fragments [x_hi | x_lo] (h = 0) / [x_hi | 1 1 0 0] (h = 1), both row halves (two
@@ -1316,12 +1344,13 @@ __global__ __launch_bounds__(NT) void dx_kernel(const DxArgs p) {
 
 // ---- dxa: the critic's ACTION feature tiles (48 features = tiles 8, 9) of dC and their parameter sums ----------------------
 // A quarter of dx_kernel's matrix work per tile. Every wave is on its own: wave w = (rh, ft, par) takes row half rh of feature tile
-// 8 + ft of every second tile (parity par) of the workgroup and fetches its 32 sm rows (8 KB, contiguous) itself, TWO of its
-// tiles ahead, as eight COALESCED 1-KiB pieces (16 lanes per 256-byte row) that go through a wave-private LDS image (272-byte
-// rows) into the A-fragment layout -- no workgroup barrier anywhere in the loop. (r03 / early r04: the fragments straight from
-// global memory, i.e. one 16-byte piece of 32 different rows per load instruction: 91-93 us whatever the prefetch depth. Also
-// tried in r04: the tiles in pairs through a shared image, one barrier per pair like dx_kernel -- 118 us: with one pair of
-// lookahead every barrier interval pays the HBM latency; and as extra units INSIDE dx_kernel -- 409 us against 229 + 91.)
+// 8 + ft of every second tile (parity par) of the workgroup and fetches its 32 packed mask rows (512 B, contiguous: lane (r, h)
+// loads row r's 16 bytes) itself, TWO of its tiles ahead -- no workgroup barrier anywhere in the loop. Each lane expands its own
+// A fragments from those words in registers (k-step s: word s >> 1 shifted by 8 (s & 1) + 4 h, four mask_pair; signed by its
+// row's g3): the same fp16 operands that r04..r06 staged through a wave-private LDS image from an 8-KB fp16 fetch (then 66 us,
+// bound by that read; r03 / early r04 read the fp16 fragments straight from global memory, 16 bytes of 32 different rows per
+// load: 91-93 us. Also tried in r04: the tiles in pairs through a shared image, one barrier per pair like dx_kernel -- 118 us;
+// and as extra units INSIDE dx_kernel -- 409 us against 229 + 91.)
 // The action layer has ONE input (agent/model.py:68-71), so everything behind dC is f32 VALU work, no second product (r03: a
 // first-layer MFMA, a [k][row] LDS image per wave, four more MFMAs and their operand splits per unit): p1 = relu(a wa + ba) as
 // one fma + max -- the relu mask from an exact f32 pre-activation --, dWa = sum (dC mask) a, dba = sum (dC mask). The two
@@ -1331,8 +1360,6 @@ __global__ __launch_bounds__(NT) void dxa_kernel(const DxArgs p) {
     typedef CriticS NET;
     constexpr int KP = NET::KP;
     constexpr float VSH = 1.f / 32.f;
-    constexpr int LDZ = 136;
-    __shared__ __attribute__((aligned(16))) f16 simg[8][32 * LDZ];     // per wave: its unit's 32 sm rows
     __shared__ __attribute__((aligned(16))) float ga[8][2][2][32];  // per wave, per buffer: |g3| gv and a of its 32 rows
     __shared__ float comb[8][64][2];
     __shared__ float gred[8];
@@ -1354,32 +1381,31 @@ __global__ __launch_bounds__(NT) void dxa_kernel(const DxArgs p) {
     const float wa = f < HA ? th[p.L_cWa + f] : 0.f, ba = f < HA ? th[p.L_cba + f] : 0.f;
     float Sa = 0.f, Sb = 0.f;
     const int ntile = j0 < P ? (P - j0 + J - 1) / J : 0;
-    // two register sets of prefetched operands, used alternately (k = par, par + 2, ..). (Plain variables through macros: as arrays
-    // handed to lambdas by reference the two sets ended up in scratch memory and -- promoted by the compiler -- in 64 KB of LDS.)
-    uint4 A0 = {}, A1 = {}, A2 = {}, A3 = {}, A4 = {}, A5 = {}, A6 = {}, A7 = {}, B0 = {}, B1 = {}, B2 = {}, B3 = {}, B4 = {}, B5 = {}, B6 = {}, B7 = {};
+    // two register sets of prefetched operands, used alternately (k = par, par + 2, ..): the lane's row of the packed mask, its g3
+    // and action. (Plain variables through macros: as arrays handed to lambdas by reference, r04's two sets ended up in scratch.)
+    uint4 mA = {}, mB = {};
     float gA = 0.f, aA = 0.f, gB = 0.f, aB = 0.f;
-#define DXA_FETCH(k_, X, g_, a_)                                                                                    \
+#define DXA_FETCH(k_, m_, g_, a_)                                                                                   \
     {                                                                                                               \
         const long r0_ = (long)((j0 + (k_) * J) * p.n_sets + set) * TILE + 32 * rh;                                 \
-        const uint4* src_ = (const uint4*)(p.sm + r0_ * H2) + lane; /* piece i = rows 4 i .. 4 i + 3: lane = 16 (row & 3) + chunk */ \
-        X##0 = src_[0], X##1 = src_[64], X##2 = src_[128], X##3 = src_[192], X##4 = src_[256], X##5 = src_[320], X##6 = src_[384], X##7 = src_[448]; \
+        m_ = *(const uint4*)(p.sm + (r0_ + r) * 4);                                                                 \
         g_ = p.g3[r0_ + r], a_ = p.act[r0_ + r];                                                                    \
     }
-#define DXA_PUT(buf_, X, g_, a_)                                                                                    \
+#define DXA_PUT(buf_, g_, a_)                                                                                       \
     {                                                                                                               \
         if (h == 0) ga[w][buf_][0][r] = fabsf(g_) * gv, ga[w][buf_][1][r] = a_;                                     \
-        f16* dst_ = simg[w] + (lane >> 4) * LDZ + 8 * (lane & 15);                                                   \
-        *(uint4*)(dst_) = X##0, *(uint4*)(dst_ + 4 * LDZ) = X##1, *(uint4*)(dst_ + 8 * LDZ) = X##2, *(uint4*)(dst_ + 12 * LDZ) = X##3; \
-        *(uint4*)(dst_ + 16 * LDZ) = X##4, *(uint4*)(dst_ + 20 * LDZ) = X##5, *(uint4*)(dst_ + 24 * LDZ) = X##6, *(uint4*)(dst_ + 28 * LDZ) = X##7; \
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                                      \
         __builtin_amdgcn_wave_barrier();                                                                            \
     }
-    auto unit = [&](int buf) {
+    auto unit = [&](int buf, const uint4 mw, float g) {
         f32x16 dc = zero16;  // [row][feature]: feature on the lane
-        const f16* arow = simg[w] + r * LDZ + 8 * h;
+        const unsigned m = mask_one(g, true);
+        const unsigned mwt[4] = {mw.x >> (4 * h), mw.y >> (4 * h), mw.z >> (4 * h), mw.w >> (4 * h)};
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
-            const f16x8 af = *(const f16x8*)(arow + 16 * s);
+            // A fragment: features 16 s + 8 h + 0..7 of the lane's row, pairs 4 h + 0..3 of chunk s (the fp16 image's row, 16 bytes)
+            const unsigned d = mwt[s >> 1] >> (8 * (s & 1));
+            const f16x8 af = fragh(mask_pair(d, 0, m), mask_pair(d, 1, m >> 1), mask_pair(d, 2, m >> 2), mask_pair(d, 3, m >> 3));
             dc = mfmah(af, wch[s], dc), dc = mfmah(af, wcl[s], dc);
         }
         float sa = 0.f, sb = 0.f;
@@ -1395,19 +1421,25 @@ __global__ __launch_bounds__(NT) void dxa_kernel(const DxArgs p) {
             }
         }
         Sa += sa, Sb += sb;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the image is rewritten by this wave's next unit)
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (ga[w][buf] is rewritten by this wave's next unit)
         __builtin_amdgcn_wave_barrier();
     };
-    if (par < ntile) DXA_FETCH(par, A, gA, aA);
-    if (par + 2 < ntile) DXA_FETCH(par + 2, B, gB, aB);
+    if (par < ntile) DXA_FETCH(par, mA, gA, aA);
+    if (par + 2 < ntile) DXA_FETCH(par + 2, mB, gB, aB);
     for (int k = par; k < ntile; k += 4) {
-        DXA_PUT(0, A, gA, aA);  // (the set's registers are free again: its next fetch goes out before the unit's arithmetic)
-        if (k + 4 < ntile) DXA_FETCH(k + 4, A, gA, aA);
-        unit(0);
+        DXA_PUT(0, gA, aA);
+        {
+            const uint4 mc = mA;  // (the set's registers are free again: its next fetch goes out before the unit's arithmetic)
+            const float gc = gA;
+            if (k + 4 < ntile) DXA_FETCH(k + 4, mA, gA, aA);
+            unit(0, mc, gc);
+        }
         if (k + 2 < ntile) {
-            DXA_PUT(1, B, gB, aB);
-            if (k + 6 < ntile) DXA_FETCH(k + 6, B, gB, aB);
-            unit(1);
+            DXA_PUT(1, gB, aB);
+            const uint4 mc = mB;
+            const float gc = gB;
+            if (k + 6 < ntile) DXA_FETCH(k + 6, mB, gB, aB);
+            unit(1, mc, gc);
         }
     }
 #undef DXA_FETCH
@@ -1459,8 +1491,8 @@ static Plan make_plan(int n_agents, int n_sets) {
     pl.wap = take(4 * (size_t)n_sets * 48);
     const size_t rows = (size_t)n_agents * TILE;
     pl.a2 = take(4 * rows), pl.y = take(4 * rows), pl.mu = take(4 * rows), pl.dmu = take(4 * rows), pl.g3 = take(4 * rows);
-    pl.sm = take(sizeof(f16) * rows * H2);   // the critic's signed masks (HEAD_BOTH)
-    pl.sma = take(sizeof(f16) * rows * H2);  // the actor's unsigned masks (OUT_TANH_SAVE: written before the critic's are used)
+    pl.sm = take(16 * rows);   // the critic's relu masks, one bit per element (HEAD_BOTH)
+    pl.sma = take(16 * rows);  // the actor's (OUT_TANH_SAVE: written before the critic's are used)
     pl.tz = take(4 * rows);
     pl.t1p = take(2 * 4 * (size_t)n_sets * CriticS::K * H2), pl.s2raw = take(2 * 4 * (size_t)n_sets * H2);  // (per net)
     pl.xfs = take(32 * rows), pl.xfs2 = take(32 * rows);
@@ -1519,7 +1551,7 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
     int* bad = (int*)(ws + pl.bad);
     float *a2 = (float*)(ws + pl.a2), *y = (float*)(ws + pl.y), *mu = (float*)(ws + pl.mu), *dmu = (float*)(ws + pl.dmu);
     float* g3 = (float*)(ws + pl.g3);
-    f16 *sm = (f16*)(ws + pl.sm), *sma = (f16*)(ws + pl.sma);
+    unsigned *sm = (unsigned*)(ws + pl.sm), *sma = (unsigned*)(ws + pl.sma);
     auto F = [&](size_t off) { return (float*)(ws + off); };
     const dim3 grid(pl.grid), block(NT);
     HeadArgs h;
