@@ -882,9 +882,8 @@ struct DwArgs {
     const float* act;  // the critic's action input [n_agents][64]
     const float* g3;   // [n_agents][64]
     const float* part_m;  // [grid][8] max |g3| per wave of the kernel that wrote g3 (set_gscale)
-    const unsigned* sm;  // the packed relu mask of the head (HeadArgs::sm), expanded on staging to fp16 +-1 / 0 (critic: sign(g3) applied
-                       // there) or 1 / 0 (actor: the sign of g3 then goes onto the A operand: one v_xor per packed pair, from a per-row
-                       // sign table in LDS)
+    const unsigned* sm;  // the packed relu mask of the head (HeadArgs::sm), expanded on staging to fp16 sign(g3) / 0 (both nets; r07's actor
+                       // staged 1 / 0 and put the sign onto the A operand: 48 v_xor per wave and tile against 8 VALU per thread here)
     float* partG;      // [grid][KG][128] (row K: the constant-one feature = sum over rows of g3 * mask -> db2 / c3)
     int abl;           // diagnostic build only (AVD_FSPLIT_ABL; 0 in the product): timing ablations with WRONG results -- 1: every tile
                        // fetch reads the workgroup's first tile (no HBM traffic), 2: no workgroup barrier in the tile loop
@@ -903,8 +902,6 @@ template <int S, class NET>
 __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
     constexpr int KG = NET::KG, LDZ = 160;
     constexpr int XC = NET::critic ? 2 : 1;  // column tiles of a wave's extra piece
-    constexpr bool SGN = !NET::critic;       // unsigned masks: the sign of g3 rides on the A operand
-    __shared__ __attribute__((aligned(16))) unsigned short sgn16[2][TILE];  // 0x8000 where g3[row] < 0: two rows = one packed-pair sign word
     __shared__ __attribute__((aligned(16))) f16 smimg[2][TILE * LDZ];  // (40 KB: reused for the extra pieces' partial sums)
     __shared__ __attribute__((aligned(16))) f16x8 fq[2][TILE * 2];      // scaled input fragments [row][lane half] of the states
     __shared__ __attribute__((aligned(16))) f16x8 fa[2][TILE * 2];      // ... of the action (critic)
@@ -936,7 +933,7 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
     auto fetch_m = [&](int pl, unsigned& m, float& g) {
         const long ri = (long)(((FSPLIT_ABL(p.abl) & 1) ? j0 : pl) * p.n_sets + set) * TILE + srow;
         m = p.sm[ri * 4 + (sch >> 1)];
-        if (NET::critic) g = p.g3[ri];
+        g = p.g3[ri];
     };
     auto fetch_x = [&](int pl) {
         if (pl >= P || tid >= 2 * TILE) return;
@@ -945,15 +942,18 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
         sg = p.g3[ri];
         if (NET::critic) sa = p.act[ri];
     };
-    auto stage = [&](int pl, int buf, unsigned m, float g) {
-        if (pl >= P) return;
+    // (the mask expansion has no branch: past the last tile it writes stale words into a buffer nobody reads, so that compute()
+    // can issue it between its last MFMAs)
+    auto stage_m = [&](int buf, unsigned m, float g) {
         uint4* dst = (uint4*)(smimg[buf] + srow * LDZ + 16 * sch);
-        mask_chunk16(m, sch, mask_one(g, NET::critic), dst[0], dst[1]);
+        mask_chunk16(m, sch, mask_one(g, true), dst[0], dst[1]);
+    };
+    auto stage_x = [&](int pl, int buf) {
+        if (pl >= P) return;
         if (tid < 2 * TILE) {
             const float g = fabsf(sg) * gsc;  // in [0, 1)
             fq[buf][tid] = make_xg(g * sx[0], g * sx[1], g * sx[2], g * sx[3], g, fh);
             if (NET::critic) fa[buf][tid] = make_xg(g * sa, 0.f, 0.f, 0.f, g, fh);
-            if (SGN && fh == 0) sgn16[buf][frow] = sg < 0.f ? 0x8000 : 0;
         }
     };
     const int g4 = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
@@ -976,8 +976,7 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
                 for (int j = 0; j < 4; ++j) bfr[c][4 * hf + j] = t[j];
             }
     };
-    // pair m of a unit's 16 rows = registers 2m, 2m + 1 = rows acc_row(2m, h), + 1 of row half e: sign word 16 e + 4 (m >> 1) + 2 h + (m & 1)
-    auto split16e = [&](const f32x16& p1, unsigned (&qh)[8], unsigned (&ql)[8], int buf, int e) {
+    auto split16e = [&](const f32x16& p1, unsigned (&qh)[8], unsigned (&ql)[8]) {
         if (FSPLIT_ABL(p.abl) & 4) {  // (timing ablation, diagnostic build: no relu / split VALU: WRONG results)
 #pragma unroll
             for (int m = 0; m < 8; ++m) qh[m] = __float_as_uint(p1[2 * m]), ql[m] = __float_as_uint(p1[2 * m + 1]);
@@ -985,18 +984,11 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
         }
 #pragma unroll
         for (int m = 0; m < 8; ++m) split2h(relu(p1[2 * m]), relu(p1[2 * m + 1]), qh[m], ql[m]);
-        if (SGN) {
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-                const uint2 sw = *(const uint2*)((const unsigned*)sgn16[buf] + 16 * e + 4 * qd + 2 * h);
-                qh[2 * qd] ^= sw.x, ql[2 * qd] ^= sw.x, qh[2 * qd + 1] ^= sw.y, ql[2 * qd + 1] ^= sw.y;
-            }
-        }
     };
-    auto compute = [&](int buf) {
+    auto compute = [&](int buf, unsigned m, float g) {  // (m, g: the mask word of the tile after it, staged into buffer buf ^ 1)
         unsigned ah[8], al[8], bh[8], bl[8];
         // stage 0: first layer + split of row half 0 (exposed)
-        split16e(mfmah(fq[buf][r * 2 + h], wf0, zero16), ah, al, buf, 0);
+        split16e(mfmah(fq[buf][r * 2 + h], wf0, zero16), ah, al);
         __builtin_amdgcn_sched_barrier(0);
         // stage 1: MFMAs of row half 0 | first layer + split of row half 1
         {
@@ -1010,7 +1002,7 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) G0[c] = mfmah(hi, bfr[c], G0[c]), G0[c] = mfmah(lo, bfr[c], G0[c]);
             }
-            split16e(p1, bh, bl, buf, 1);
+            split16e(p1, bh, bl);
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
@@ -1018,7 +1010,7 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, SGN ? 4 : 3, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -1036,7 +1028,7 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) G0[c] = mfmah(hi, bfr[c], G0[c]), G0[c] = mfmah(lo, bfr[c], G0[c]);
             }
-            split16e(px, ah, al, buf, xrh);
+            split16e(px, ah, al);
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
@@ -1044,13 +1036,14 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, SGN ? 4 : 3, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
         }
         // stage 3: MFMAs of the extra piece: column tile(s) xc0.. of row half xrh (runtime: the fragments are read at their
-        // address, not selected from registers)
+        // address, not selected from registers) | the mask expansion of the next tile (r07: after them, with no MFMA beside it)
+        stage_m(buf ^ 1, m, g);
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             const f16x8 hi = fragh(ah[4 * s], ah[4 * s + 1], ah[4 * s + 2], ah[4 * s + 3]);
@@ -1069,11 +1062,19 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
                 G1[c] = mfmah(lo, bx, G1[c]);
             }
         }
+        __builtin_amdgcn_sched_group_barrier(0x100, 4 * XC, 0);
+#pragma unroll
+        for (int i = 0; i < 4 * XC; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);
+        __builtin_amdgcn_sched_barrier(0);
     };
     if (j0 < P) fetch_m(j0, ma, ga);
     fetch_x(j0);
     if (j0 + J < P) fetch_m(j0 + J, mb, gb);
-    stage(j0, 0, ma, ga);
+    stage_m(0, ma, ga), stage_x(j0, 0);
     __syncthreads();
 #ifdef AVD_STAMP
     unsigned long long tacc[4] = {0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
@@ -1086,9 +1087,9 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
         fetch_x(pi + J);
         if (pi + 2 * J < P) fetch_m(pi + 2 * J, ma, ga);
         STAMP(0);
-        compute(0);
+        compute(0, mb, gb);
         STAMP(1);
-        stage(pi + J, 1, mb, gb);
+        stage_x(pi + J, 1);
         STAMP(2);
         if (!(FSPLIT_ABL(p.abl) & 2)) __syncthreads();
         STAMP(3);
@@ -1097,9 +1098,9 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
             fetch_x(pi + 2 * J);
             if (pi + 3 * J < P) fetch_m(pi + 3 * J, mb, gb);
             STAMP(0);
-            compute(1);
+            compute(1, ma, ga);
             STAMP(1);
-            stage(pi + 2 * J, 0, ma, ga);
+            stage_x(pi + 2 * J, 0);
             STAMP(2);
             if (!(FSPLIT_ABL(p.abl) & 2)) __syncthreads();
             STAMP(3);
@@ -1149,7 +1150,6 @@ struct DxArgs {
     const float* g3;
     const float* part_m;  // [grid][8] max |g3| per wave of the kernel that wrote g3 (set_gscale)
     const unsigned* sm;  // the packed relu mask of the head (HeadArgs::sm)
-    int unsigned_mask;  // actor: the mask is staged as 1 / 0, the row factor keeps the sign of g3; critic: staged as sign(g3) * mask
     float* partV;      // [grid][KP][16]       sum_rows (dC * mask) * [x_hi | x_lo | 1] per feature
     int abl;           // diagnostic build only (see DwArgs)
     unsigned long long* stamp;  // diagnostic build (-DAVD_STAMP) only
@@ -1171,9 +1171,11 @@ template <int S, class NET>
 __global__ __launch_bounds__(NT) void dx_kernel(const DxArgs p) {
     constexpr int KP = NET::KP, LDZ = 136;  // 272-byte rows: conflict-free b128 row reads
     constexpr float VSH = 1.f / 32.f;
+    // sm images: two buffers (read by the dC products only, all before the barrier that ends their tile); input images and row
+    // factors: three (the previous tile's row half 1 is still read after the barrier that publishes the next one: see the loop)
     __shared__ __attribute__((aligned(16))) f16 smimg[2][TILE * LDZ];
-    __shared__ __attribute__((aligned(16))) f16 xt[2][2][32 * 32];  // per buffer, per row half: [k column][row]
-    __shared__ __attribute__((aligned(16))) float g3s[2][TILE];
+    __shared__ __attribute__((aligned(16))) f16 xt[3][2][32 * 32];  // per slot, per row half: [k column][row]
+    __shared__ __attribute__((aligned(16))) float g3s[3][TILE];
     __shared__ float gred[8];
     const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, r = lane & 31, h = lane >> 5, ft = w;
     const int set = blockIdx.x % p.n_sets, j0 = blockIdx.x / p.n_sets, J = gridDim.x / p.n_sets, P = p.n_agents / p.n_sets;
@@ -1192,143 +1194,189 @@ __global__ __launch_bounds__(NT) void dx_kernel(const DxArgs p) {
     const float gv = gsc * VSH, vs = gsc * swc * VSH;
     const f16x8 wf = p.net.wf1h[((long)set * NGT_MAX + ft) * 64 + lane];  // (scaled by S1: p1 = S1 z1, U1 rescaled at the end)
     f32x16 V = zero16;
-    for (int i = tid; i < 2 * 2 * 32 * 32; i += NT) {  // columns 9.. stay zero, column 8 is the ones column (bias)
+    for (int i = tid; i < 3 * 2 * 32 * 32; i += NT) {  // columns 9.. stay zero, column 8 is the ones column (bias)
         const int k = (i >> 5) & 31;
         (&xt[0][0][0])[i] = (f16)(k == 8 ? 1.f : 0.f);
     }
-    // sm: thread (srow, sch) expands features [16 sch, +16) of row srow (mask_chunk16; critic: signed by its row's g3, gs) into the
-    // fp16 image, one tile ahead like the rest
+    // sm: thread (srow, sch) expands features [16 sch, +16) of row srow (mask_chunk16) into the fp16 image. Actor: as 1 / 0, the sign
+    // of g3 rides in the row factor g3s; critic: signed by its row's g3 (gs), row factor |g3|. (The actor's form would save the
+    // critic a load and eight VALU per thread and tile, but it is not bit-identical: an MFMA sum of negated products is not always
+    // the negated sum -- measured, every dumped array of the bench differed.)
     const int srow = tid >> 3, sch = tid & 7;
     unsigned dm = 0;
     float gn = 0.f, gs = 0.f;
-    auto fetch = [&](int agent) {
-        if (FSPLIT_ABL(p.abl) & 1) agent = j0 * p.n_sets + set;
-        dm = p.sm[((long)agent * TILE + srow) * 4 + (sch >> 1)];
-        if (NET::critic) gs = p.g3[(long)agent * TILE + srow];
-        if (tid < TILE) gn = p.g3[(long)agent * TILE + tid];
+    // Every fetch reads a valid tile (past the last one: the last one again, staged into a buffer nobody reads), so the tile loop
+    // has no branch but its own: the staging is scheduled into the MFMA phases below.
+    auto fetch = [&](int pl) {
+        if (FSPLIT_ABL(p.abl) & 1) pl = j0;
+        const long agent = (long)pl * p.n_sets + set;
+        dm = p.sm[(agent * TILE + srow) * 4 + (sch >> 1)];
+        if (NET::critic) gs = p.g3[agent * TILE + srow];
+        if (tid < TILE) gn = p.g3[agent * TILE + tid];
     };
-    auto stage = [&](int buf) {
+    auto stage = [&](int buf, int slot) {
         uint4* dst = (uint4*)(smimg[buf] + srow * LDZ + 16 * sch);
         mask_chunk16(dm, sch, mask_one(gs, NET::critic), dst[0], dst[1]);
-        if (tid < TILE) g3s[buf][tid] = (p.unsigned_mask ? gn : fabsf(gn)) * gv;
+        if (tid < TILE) g3s[slot][tid] = (NET::critic ? fabsf(gn) : gn) * gv;
     };
     f16x8 xfn0 = {}, xfn1 = {};  // the rows' input fragments [x_hi | x_lo] (h = 0) / [x_hi | 1 1 0 0] (h = 1), both row halves (two
                                  // variables, not an array: LLVM merges the two image copies below into one indexed by the wave number
                                  // and then keeps the array in scratch memory)
-    auto fetch_x = [&](int agent) {
-        xfn0 = p.xfh[((long)agent * TILE + r) * 2 + h];
-        xfn1 = p.xfh[((long)agent * TILE + 32 + r) * 2 + h];
+    auto fetch_x = [&](int pl) {
+        const long agent = (long)pl * p.n_sets + set;
+        xfn0 = p.xfh[(agent * TILE + r) * 2 + h];
+        xfn1 = p.xfh[(agent * TILE + 32 + r) * 2 + h];
     };
-    auto stage_x = [&](int buf) {  // [k][row] image of [x_hi | x_lo]: the h = 0 fragments, transposed (waves 0, 1: one row half each)
+    auto stage_x = [&](int slot) {  // [k][row] image of [x_hi | x_lo]: the h = 0 fragments, transposed (waves 0, 1: one row half each)
         if (w < 2 && h == 0) {
             f16x8 src = xfn0;
             if (w == 1) src = xfn1;
             asm volatile("" : "+v"(src));  // (a register copy selected by the scalar wave number, not a memory index)
 #pragma unroll
-            for (int k = 0; k < 8; ++k) xt[buf][w][k * 32 + r] = src[k];
+            for (int k = 0; k < 8; ++k) xt[slot][w][k * 32 + r] = src[k];
         }
     };
-    __syncthreads();  // the zero / ones fill above before the first stage_x
-    if (j0 < P) fetch(j0 * p.n_sets + set), fetch_x(j0 * p.n_sets + set), stage(0), stage_x(0);
-    __syncthreads();
 #ifdef AVD_STAMP
     unsigned long long dacc[4] = {0, 0, 0, 0}, dlast = __builtin_amdgcn_s_memtime();
 #define DXSTAMP(i) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); dacc[i] += t_ - dlast; dlast = t_; }
 #else
 #define DXSTAMP(i)
 #endif
-    int buf = 0;
-    for (int pi = j0; pi < P; pi += J, buf ^= 1) {
-        const bool more = pi + J < P;
-        const f16x8 xf[2] = {xfn0, xfn1};
-        if (more) fetch((pi + J) * p.n_sets + set), fetch_x((pi + J) * p.n_sets + set);
+    auto read_a = [&](int buf, int e, f16x8 (&smf)[8]) {
+        const f16* arow = smimg[buf] + (32 * e + r) * LDZ + 8 * h;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) smf[s] = *(const f16x8*)(arow + 16 * s);
+    };
+    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+    auto read_img = [&](const f16* img, f16x8 (&xb)[2]) {  // B operand of V from a [k][row] image
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const f16x4 lo = *(const f16x4*)(img + r * 32 + 16 * s + 4 * h);
+            const f16x4 hi = *(const f16x4*)(img + r * 32 + 16 * s + 8 + 4 * h);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) xb[s][j] = lo[j], xb[s][4 + j] = hi[j];
+        }
+    };
+    auto dc_product = [&](const f16x8 (&smf)[8]) {  // dC of one row half: 16 MFMAs on one accumulator, k-steps in order
+        f32x16 dc = zero16;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) dc = mfmah(smf[s], wch[s], dc), dc = mfmah(smf[s], wcl[s], dc);
+        return dc;
+    };
+    // BN/ReLU backward of the first layer: only the MASKED gradient is needed per element. The two unmasked per-feature sums of
+    // r03 -- sum_rows dC (-> d beta1) and sum_rows dC relu(z1) (-> d gamma1): 3 of this kernel's ~8 VALU per element, and the
+    // kernel is VALU-bound at 40 % of the matrix pipe -- are linear images of sums that exist anyway (r04, finalize_feat_kernel):
+    //     sum_rows dC[row][f]           = sum_n W2[f][n] db2[n]                         (backprop of the row sum through the layer)
+    //     sum_rows dC[row][f] relu(z1)  = sum_k W1[k][f] V[f][k] + b1[f] V[f][8]        (relu(z1) = mask z1, z1 = x . W1 + b1)
+    auto backward = [&](int slot, int e, const f32x16& dc, const f32x16& p1, unsigned (&vh)[8], unsigned (&vl)[8]) {
+        if (FSPLIT_ABL(p.abl) & 4) {  // (timing ablation, diagnostic build: the BN / ReLU backward + split VALU skipped, raw bits as operands: WRONG results)
+#pragma unroll
+            for (int m = 0; m < 8; ++m) vh[m] = __float_as_uint(dc[2 * m]) ^ __float_as_uint(p1[2 * m]), vl[m] = __float_as_uint(dc[2 * m + 1]);
+            return;
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 gq = *(const float4*)(&g3s[slot][32 * e + 8 * g + 4 * h]);
+            const float gg[4] = {gq.x, gq.y, gq.z, gq.w};
+            float dm[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int k = 4 * g + j;
+                dm[j] = p1[k] > 0.f ? dc[k] * gg[j] : 0.f;
+            }
+            split2h(dm[0], dm[1], vh[2 * g], vl[2 * g]);
+            split2h(dm[2], dm[3], vh[2 * g + 1], vl[2 * g + 1]);
+        }
+    };
+    auto v_product = [&](const unsigned (&vh)[8], const unsigned (&vl)[8], const f16x8 (&xb)[2]) {  // V += one row half: 4 MFMAs
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            V = mfmah(fragh(vh[4 * s], vh[4 * s + 1], vh[4 * s + 2], vh[4 * s + 3]), xb[s], V);
+            V = mfmah(fragh(vl[4 * s], vl[4 * s + 1], vl[4 * s + 2], vl[4 * s + 3]), xb[s], V);
+        }
+    };
+    // The tile loop is a software pipeline over row halves AND tiles. Tile t sits in sm buffer t & 1 and slot t % 3; each
+    // iteration is three phases and one barrier:
+    //   1: dC of row half 0 of tile t                    | backward + split VALU of row half 1 of tile t - 1
+    //   2: V of row half 1 of tile t - 1, dC of half 1   | backward + split VALU of row half 0 of tile t, staging of tile t + 1
+    //   3: V of row half 0 of tile t;  barrier
+    // r07 issued the halves of one tile in turn: the dC of half 0 had no VALU beside it, half 1's VALU had only the 8 V MFMAs, and
+    // the staging of the next tile came after all of them -- the two waves of a SIMD share the barrier, so they were always in the
+    // same phase and the matrix and vector pipes hardly overlapped (5.9 k cycles per tile and SIMD for 2.7 k of MFMA). Each
+    // accumulator still sees its MFMAs in the same order (V: half 0 of tile t, half 1 of tile t, half 0 of tile t + 1, ...), so the
+    // results are bit-identical. The slot of tile t - 1 is read in phase 1 of iteration t, after the barrier that publishes tile
+    // t; tile t + 1 is written in phase 2: a third slot keeps them apart. The sm buffers need no third: both dC of a tile come
+    // before the barrier that ends its iteration.
+    f16x8 xf0, xf1;  // tile t's input fragments (xfn*: tile t + 1)
+    f32x16 dc1 = zero16, p11 = zero16;  // row half 1 of the previous tile, carried over the barrier
+    auto iteration = [&](auto has_prev_c, int pi, int buf, int slot) {
+        constexpr bool has_prev = decltype(has_prev_c)::value;
+        const int pslot = slot == 0 ? 2 : slot - 1, nslot = slot == 2 ? 0 : slot + 1;
+        const int nn = pi + 2 * J < P ? pi + 2 * J : (pi + J < P ? pi + J : pi);  // tile t + 2 (or the last valid one)
         DXSTAMP(0);
-        // The two row halves as a software pipeline: [dC of half 0] [dC of half 1 | BN/ReLU backward + split VALU of half 0]
-        // [V of half 0 | VALU of half 1] [V of half 1]. One half after the other, the two waves of a SIMD run their MFMA phases
-        // together and their VALU phases together (one barrier per tile) and the pipes never overlap (dw_kernel, measured).
-        auto read_a = [&](int e, f16x8 (&smf)[8]) {
-            const f16* arow = smimg[buf] + (32 * e + r) * LDZ + 8 * h;
-#pragma unroll
-            for (int s = 0; s < 8; ++s) smf[s] = *(const f16x8*)(arow + 16 * s);
-        };
-        typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-        auto read_img = [&](const f16* img, f16x8 (&xb)[2]) {  // B operand of V from a [k][row] image
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const f16x4 lo = *(const f16x4*)(img + r * 32 + 16 * s + 4 * h);
-                const f16x4 hi = *(const f16x4*)(img + r * 32 + 16 * s + 8 + 4 * h);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) xb[s][j] = lo[j], xb[s][4 + j] = hi[j];
-            }
-        };
-        // BN/ReLU backward of the first layer: only the MASKED gradient is needed per element. The two unmasked per-feature sums of
-        // r03 -- sum_rows dC (-> d beta1) and sum_rows dC relu(z1) (-> d gamma1): 3 of this kernel's ~8 VALU per element, and the
-        // kernel is VALU-bound at 40 % of the matrix pipe -- are linear images of sums that exist anyway (r04, finalize_feat_kernel):
-        //     sum_rows dC[row][f]           = sum_n W2[f][n] db2[n]                         (backprop of the row sum through the layer)
-        //     sum_rows dC[row][f] relu(z1)  = sum_k W1[k][f] V[f][k] + b1[f] V[f][8]        (relu(z1) = mask z1, z1 = x . W1 + b1)
-        auto backward = [&](int e, const f32x16& dc, const f32x16& p1, unsigned (&vh)[8], unsigned (&vl)[8]) {
-            if (FSPLIT_ABL(p.abl) & 4) {  // (timing ablation, diagnostic build: the BN / ReLU backward + split VALU skipped, raw bits as operands: WRONG results)
-#pragma unroll
-                for (int m = 0; m < 8; ++m) vh[m] = __float_as_uint(dc[2 * m]) ^ __float_as_uint(p1[2 * m]), vl[m] = __float_as_uint(dc[2 * m + 1]);
-                return;
-            }
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float4 gq = *(const float4*)(&g3s[buf][32 * e + 8 * g + 4 * h]);
-                const float gg[4] = {gq.x, gq.y, gq.z, gq.w};
-                float dm[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int k = 4 * g + j;
-                    dm[j] = p1[k] > 0.f ? dc[k] * gg[j] : 0.f;
-                }
-                split2h(dm[0], dm[1], vh[2 * g], vl[2 * g]);
-                split2h(dm[2], dm[3], vh[2 * g + 1], vl[2 * g + 1]);
-            }
-        };
+        // phase 1
         f16x8 smf[8], xb0[2], xb1[2];
         unsigned vh0[8], vl0[8], vh1[8], vl1[8];
-        // stage 0: dC of row half 0
-        read_a(0, smf);
-        f32x16 dc0 = zero16;
+        read_a(buf, 0, smf);
+        const f32x16 dc0 = dc_product(smf);
+        const f32x16 p10 = mfmah(xf0, wf, zero16);
+        if constexpr (has_prev) {
+            read_img(xt[pslot][1], xb1);
+            backward(pslot, 1, dc1, p11, vh1, vl1);
+            __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);
 #pragma unroll
-        for (int s = 0; s < 8; ++s) dc0 = mfmah(smf[s], wch[s], dc0), dc0 = mfmah(smf[s], wcl[s], dc0);
-        const f32x16 p10 = mfmah(xf[0], wf, zero16);
-        __builtin_amdgcn_sched_barrier(0);
-        // stage 1: dC of row half 1 | backward VALU of row half 0
-        read_a(1, smf);
-        read_img(xt[buf][0], xb0);
-        f32x16 dc1 = zero16;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) dc1 = mfmah(smf[s], wch[s], dc1), dc1 = mfmah(smf[s], wcl[s], dc1);
-        const f32x16 p11 = mfmah(xf[1], wf, zero16);
-        backward(0, dc0, p10, vh0, vl0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 12, 0);
-#pragma unroll
-        for (int i = 0; i < 17; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            for (int i = 0; i < 17; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            }
         }
         __builtin_amdgcn_sched_barrier(0);
-        // stage 2: V of row half 0 | backward VALU of row half 1; then V of row half 1
-        read_img(xt[buf][1], xb1);
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            V = mfmah(fragh(vh0[4 * s], vh0[4 * s + 1], vh0[4 * s + 2], vh0[4 * s + 3]), xb0[s], V);
-            V = mfmah(fragh(vl0[4 * s], vl0[4 * s + 1], vl0[4 * s + 2], vl0[4 * s + 3]), xb0[s], V);
-        }
-        backward(1, dc1, p11, vh1, vl1);
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            V = mfmah(fragh(vh1[4 * s], vh1[4 * s + 1], vh1[4 * s + 2], vh1[4 * s + 3]), xb1[s], V);
-            V = mfmah(fragh(vl1[4 * s], vl1[4 * s + 1], vl1[4 * s + 2], vl1[4 * s + 3]), xb1[s], V);
-        }
         DXSTAMP(1);
-        if (more) stage(buf ^ 1), stage_x(buf ^ 1);
+        // phase 2
+        if constexpr (has_prev) v_product(vh1, vl1, xb1);
+        read_a(buf, 1, smf);
+        read_img(xt[slot][0], xb0);
+        dc1 = dc_product(smf);
+        p11 = mfmah(xf1, wf, zero16);
+        backward(slot, 0, dc0, p10, vh0, vl0);
+        stage(buf ^ 1, nslot);
+        stage_x(nslot);
+        xf0 = xfn0, xf1 = xfn1;
+        fetch(nn), fetch_x(nn);
+        __builtin_amdgcn_sched_group_barrier(0x100, 16, 0);
+#pragma unroll
+        for (int i = 0; i < (has_prev ? 21 : 17); ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
+            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // phase 3
+        v_product(vh0, vl0, xb0);
         DXSTAMP(2);
         if (!(FSPLIT_ABL(p.abl) & 2)) __syncthreads();
         DXSTAMP(3);
+    };
+    __syncthreads();  // the zero / ones fill above before the first stage_x
+    if (j0 < P) {
+        fetch(j0), fetch_x(j0), stage(0, 0), stage_x(0);
+        xf0 = xfn0, xf1 = xfn1;
+        const int n1 = j0 + J < P ? j0 + J : j0;
+        fetch(n1), fetch_x(n1);
+    }
+    __syncthreads();
+    if (j0 < P) {
+        iteration(std::false_type{}, j0, 0, 0);
+        int buf = 1, slot = 1, pi = j0 + J;
+        for (; pi < P; pi += J, buf ^= 1, slot = slot == 2 ? 0 : slot + 1) iteration(std::true_type{}, pi, buf, slot);
+        // the last tile's row half 1
+        const int pslot = slot == 0 ? 2 : slot - 1;
+        f16x8 xb1[2];
+        unsigned vh1[8], vl1[8];
+        read_img(xt[pslot][1], xb1);
+        backward(pslot, 1, dc1, p11, vh1, vl1);
+        v_product(vh1, vl1, xb1);
     }
 #ifdef AVD_STAMP
     if (p.stamp && blockIdx.x == 16 && lane == 0)
@@ -1571,7 +1619,7 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
     dw.stamp = d_stamp;
 #endif
     DxArgs dx;
-    dx.n_agents = n_agents, dx.n_sets = n_sets, dx.sm = sm, dx.g3 = g3, dx.xfh = xfs, dx.stamp = nullptr, dx.L_cWa = dx.L_cba = 0, dx.unsigned_mask = 0;
+    dx.n_agents = n_agents, dx.n_sets = n_sets, dx.sm = sm, dx.g3 = g3, dx.xfh = xfs, dx.stamp = nullptr, dx.L_cWa = dx.L_cba = 0;
     dx.abl = dw.abl;
 #ifdef AVD_STAMP
     dx.stamp = d_stamp;
@@ -1624,7 +1672,7 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
         dw.sm = sma, dx.sm = sma;
         dw.net = net[0], dw.act = nullptr, dw.partG = F(pl.partG[0]), dw.part_m = F(pl.partM[0]);
         hipLaunchKernelGGL((dw_kernel<S, ActorS>), grid, block, 0, st, dw);
-        dx.net = net[0], dx.partV = F(pl.partV[0]), dx.act = nullptr, dx.part_m = F(pl.partM[0]), dx.L_cWa = dx.L_cba = 0, dx.unsigned_mask = 1;
+        dx.net = net[0], dx.partV = F(pl.partV[0]), dx.act = nullptr, dx.part_m = F(pl.partM[0]), dx.L_cWa = dx.L_cba = 0;
         hipLaunchKernelGGL((dx_kernel<S, ActorS>), grid, block, 0, st, dx);
         // 12: the actor block of the slab (the single call: both blocks)
         if (phases == PH_ACTOR) launch_finalize(fa, st, 0, 1);
