@@ -13,16 +13,22 @@ Launch: python bench.py --gpus N --steps K --warmup W. N > 1: one rank per GPU, 
 (RANK / LOCAL_RANK / WORLD_SIZE in the environment) or, when WORLD_SIZE is not set, started BY this script as N child
 processes before anything touches the GPU (the parent only waits and never imports torch). Rank 0 prints ONE JSON line.
 
-On one GPU, without flags that select a workload, the same run then also times the other single-GPU BASELINE configs --
-configs[2] (4096 x 10, interfrl and nofrl at replay capacity 100000) and configs[4] (hidden 1024, bf16 batched engine) -- each
-with its own prewarm, warm-up and timed region of the same --steps (capped at 300), under also_measured.{config3_interfrl,
-config3_nofrl, config5}; `value` stays configs[1] interfrl (--no-extra-configs skips them).
+A plain run does only what its headline figure needs: it builds the primary workload's trainer, prewarms and warms it up, times
+the --steps steps, writes --dump-outputs if given and prints the line. Everything else the benchmark measures takes runs of its
+own and needs --full:
+  * without --mode, the other workload of the same shape (under also_measured, below);
+  * on one GPU, without flags that select a workload, the other single-GPU BASELINE configs -- configs[2] (4096 x 10, interfrl
+    and nofrl at replay capacity 100000) and configs[4] (hidden 1024, bf16 batched engine) -- each with its own prewarm, warm-up
+    and timed region of the same --steps (capped at 300), under also_measured.{config3_interfrl, config3_nofrl, config5};
+    `value` stays configs[1] interfrl (--no-extra-configs skips them);
+  * on one GPU, the reference-shaped CPU loop (cpu_baseline; --no-cpu-baseline skips it);
+  * interfrl over a process group, the other collective form (collective.forms; --no-collective-ab skips it).
 
 --dump-outputs DIR writes what the last timed step of the primary workload computed (dump_outputs()); its timed steps then start
 from a state fixed by the arguments, so two runs or two builds can be compared output for output.
 
-Without --mode the line carries BOTH workloads of the 4096 x 5 shape, measured one after the other in the same run:
-the primary one (PRIMARY_MODE) as `value`, the other under `also_measured`:
+With --full and without --mode the line carries BOTH workloads of the 4096 x 5 shape, measured one after the other in the same
+run: the primary one (PRIMARY_MODE) as `value`, the other under `also_measured`:
   * nofrl    -- the reference's default `fed_method` (src/config.py:25): 20480 independent agents, HBM-bound, no
                 data-path collective (replicas only across GPUs);
   * interfrl -- BASELINE configs[3]'s per-GPU shape (workers/trainer.py:400-431): gradients averaged over the platoons
@@ -57,9 +63,14 @@ def parse():
     ap.add_argument("--platoons", type=int, default=4096, help="platoons per GPU")
     ap.add_argument("--pl-size", type=int, default=5)
     ap.add_argument("--buffer-size", type=int, default=100000)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, each in runs of its own: the other workload of the shape "
+                         "(without --mode), BASELINE configs[2] and configs[4] (plain 1-GPU shape), the CPU baseline (one GPU) and the "
+                         "other collective form (interfrl over a process group). Without it the run times the primary workload only")
     ap.add_argument("--mode", choices=["nofrl", "interfrl", "intrafrl"], default=None,
-                    help="measure this workload only (default: both, PRIMARY_MODE as `value`, the other under `also_measured`)")
-    ap.add_argument("--no-secondary", action="store_true", help="default run: skip the non-primary workload")
+                    help="measure this workload only (default: PRIMARY_MODE as `value`; with --full also the other one, under "
+                         "`also_measured`)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full run: skip the non-primary workload")
     ap.add_argument("--engine", choices=["per_agent", "batched", "fused", "fused3"], default=None,
                     help="interfrl: per_agent = f32 LDS-resident learn kernel per agent + federated sum; batched = one "
                          "bf16 MFMA GEMM chain per weight set over all its rows (default where per_agent does not exist); "
@@ -88,8 +99,8 @@ def parse():
                          "default: on a one-rank RCCL communicator the overlapped form measured slower, DESIGN.md section 6)")
     ap.add_argument("--no-overlap", action="store_true", help="(the default since r05; accepted for older command lines)")
     ap.add_argument("--no-collective-ab", action="store_true",
-                    help="interfrl, N > 1: do not also time the OTHER collective form (by default the line carries both under "
-                         "collective.forms so that one multi-GPU run attributes its own communication cost)")
+                    help="interfrl, N > 1, --full: do not also time the OTHER collective form (by default a --full line carries both "
+                         "under collective.forms so that one multi-GPU run attributes its own communication cost)")
     ap.add_argument("--init-timeout", type=float, default=600.0,
                     help="N > 1: seconds the process-group rendezvous + first collective may take before the rank gives up (non-zero exit). "
                          "Generous on purpose: on a fresh box the ranks' first `import torch` / HIP initialisation can finish minutes apart, "
@@ -113,11 +124,11 @@ def parse():
                          "workers/trainer.py:385-398) with the weights computed on the device from a ring of closed-episode rewards "
                          "(avd_fed_history_push_f32 + avd_fed_weights_f32: two small launches per step)")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="default 1-GPU run: do not also time BASELINE configs[2] (4096 x 10) and configs[4] (hidden 1024) after the two "
+                    help="--full 1-GPU run: do not also time BASELINE configs[2] (4096 x 10) and configs[4] (hidden 1024) after the two "
                          "4096 x 5 workloads")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full 1-GPU run: do not time the reference-shaped CPU loop")
     ap.add_argument("--cpu-all-cores", action="store_true",
-                    help="also time N independent single-thread copies of the CPU loop on all host cores (side figure, opt-in)")
+                    help="--full: also time N independent single-thread copies of the CPU loop on all host cores (side figure, opt-in)")
     ap.add_argument("--master-port", type=int, default=0, help="self-spawned ranks: rendezvous port (0 = pick a free one)")
     ap.add_argument("--allow-diagnostics", action="store_true",
                     help="run although AVD_* / AVDDPG_HIP_LIB environment overrides are set or the loaded library is a diagnostic "
@@ -440,12 +451,12 @@ def run_workload(args, mode, engine, rank, world, group, built=None, dump=None):
         steady_state()
     elapsed, stage_ms = timed_run(args.warmup, args.steps)
     dumped = dump_outputs(vt, dump) if dump and rank == 0 else None
-    # N > 1, split engine: time the OTHER collective form too (same trainer, same state), so that one multi-GPU run shows what the
+    # --full, N > 1, split engine: time the OTHER collective form too (same trainer, same state), so that one multi-GPU run shows what the
     # overlap hides: forms.single = one all-reduce of the whole slab between learn and Adam; forms.overlapped = critic block on a side
     # stream under the actor phase + actor block on the main stream. `value` is the form the trainer runs: the single collective
     # unless --overlap (on a one-rank RCCL communicator the overlapped form measured slower).
     forms = None
-    if (world > 1 or group is not None) and mode == "interfrl" and split3 and not args.no_collective_ab:
+    if args.full and (world > 1 or group is not None) and mode == "interfrl" and split3 and not args.no_collective_ab:
         chosen = "overlapped" if vt.overlap_allreduce else "single"
         forms = {chosen: {"ms_per_step": 1e3 * elapsed / args.steps, "stages_ms": stage_ms}}
         vt.overlap_allreduce = not vt.overlap_allreduce
@@ -790,7 +801,7 @@ def main():
         # per platoon, the fused learn + Adam + Polyak kernel
         modes = ["nofrl"]
     else:
-        modes = [PRIMARY_MODE] + ([] if args.no_secondary or args.hidden or args.framework != "decentralized" else
+        modes = [PRIMARY_MODE] + ([] if not args.full or args.no_secondary or args.hidden or args.framework != "decentralized" else
                                   ["interfrl" if PRIMARY_MODE == "nofrl" else "nofrl"])
     # interfrl without --engine: the f32-class fused set learner where it exists (reference widths, decentralized)
     engine = args.engine or ("fused3" if (not args.hidden and args.framework == "decentralized") else None)
@@ -817,10 +828,10 @@ def main():
 
     # The other single-GPU BASELINE configs under the same clock: configs[2] = 4096 x 10 (interfrl with the split
     # engine + the reference's default nofrl, replay capacity 100000) and configs[4] = hidden 1024 (bf16 batched engine), each with its
-    # own trainer, prewarm, warm-up and timed region; only in the plain default run on one GPU (no --mode / --hidden / --engine /
-    # shape flags), after the two 4096 x 5 workloads have been freed.
+    # own trainer, prewarm, warm-up and timed region; only in the --full run on one GPU without --mode / --hidden / --engine / shape
+    # flags, after the two 4096 x 5 workloads have been freed.
     extras = {}
-    default_run = (world == 1 and group is None and not args.mode and not args.hidden and not args.engine and not args.no_secondary
+    default_run = (args.full and world == 1 and group is None and not args.mode and not args.hidden and not args.engine and not args.no_secondary
                    and not args.weighted
                    and args.framework == "decentralized" and args.platoons == 4096 and args.pl_size == 5 and args.chunks == 1
                    and not args.no_fused and not args.no_extra_configs)
@@ -863,7 +874,7 @@ def main():
             out.setdefault("also_measured", {}).update(
                 {k: {f: r[f] for f in ("value", "unit", "updates_per_s", "ms_per_step", "steps", "warmup", "dtype", "config", "roofline",
                                        "stages_ms", "prewarm", "pipeline")} for k, r in extras.items()})
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, args.pl_size, first["config"]["mode"])
             if args.cpu_all_cores:  # the whole host beside the reference's own 1-thread setting (opt-in side figure)
                 try:

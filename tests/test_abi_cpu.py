@@ -230,9 +230,10 @@ def test_learn_update_plan_describes_the_centralized_pipeline_and_single_launch_
 
 
 def test_bench_default_run_declares_every_single_gpu_baseline_config():
-    """bench.py's plain 1-GPU run must carry BASELINE configs[2] (both federated modes) and configs[4] beside the two configs[1]
+    """bench.py's --full 1-GPU run must carry BASELINE configs[2] (both federated modes) and configs[4] beside the two configs[1]
     workloads: the keys of also_measured are a module constant, each naming the BASELINE.json entry it measures,
-    and the run that emits them is the flag-less one (tests/test_gpu_bench_ranks.py runs it on the GPU). No GPU, no torch here."""
+    and the run that emits them is the one with --full and no other flag (tests/test_gpu_bench_ranks.py runs it on the GPU). No GPU,
+    no torch here."""
     import importlib.util
     import json
     import os
@@ -249,3 +250,28 @@ def test_bench_default_run_declares_every_single_gpu_baseline_config():
     src = open(os.path.join(root, "bench.py")).read()
     assert "default_run" in src and "--no-extra-configs" in src and 'out.setdefault("also_measured", {}).update(' in src
     assert bench.PRIMARY_MODE == "interfrl"
+
+
+def test_bench_plain_run_leaves_everything_but_the_headline_to_full(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times the primary workload only: the second workload, the other BASELINE
+    configs, the CPU baseline and the other collective form are measured only with --full, which is off by default. No GPU here."""
+    import importlib.util
+    import os
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    args = bench.parse()
+    assert args.full is False and (args.steps, args.warmup, args.gpus) == (20, 5, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse().full is True
+    src = open(os.path.join(root, "bench.py")).read()
+    main_src = src[src.index("def main():"):]
+    # each extra measurement is gated on --full
+    assert "not args.full or args.no_secondary" in main_src
+    assert "default_run = (args.full and" in main_src
+    assert "if args.full and world == 1 and not args.no_cpu_baseline:" in main_src
+    assert "if args.full and (world > 1 or group is not None)" in src

@@ -47,14 +47,14 @@ def test_two_ranks_on_one_gpu_over_gloo():
 def test_two_ranks_over_rccl_when_two_gpus_are_visible():
     """The same command over RCCL. With two or more GPUs visible: two ranks, one per GPU. With one GPU, where RCCL refuses two ranks per
     device ("Duplicate GPU detected"), its one rank runs through a real RCCL communicator (--one-rank-rccl): every collective of the
-    N > 1 interfrl path goes through RCCL on the device, timed in both of its forms (the two-rank data path: over gloo above and in
-    tests/test_dist_cpu.py)."""
+    N > 1 interfrl path goes through RCCL on the device, timed in both of its forms with --full (the two-rank data path: over gloo
+    above and in tests/test_dist_cpu.py)."""
     need_gpu()
     if torch.cuda.device_count() >= 2:
         out = _bench(["--backend", "nccl"])
         assert out["n_gpus"] == 2 and out["value"] > 0 and out["rccl_ranks"] == 2 and out["collective_backend"] == "nccl"
         return
-    out = _bench(["--one-rank-rccl", "--master-port", str(_free_port())], gpus=1)
+    out = _bench(["--full", "--one-rank-rccl", "--master-port", str(_free_port())], gpus=1)
     assert out["n_gpus"] == 1 and out["value"] > 0 and out["rccl_ranks"] == 1 and out["collective_backend"] == "nccl"
     col = out["collective"]
     assert col["per_step_ms"] > 0 and out["stages_ms"]["allreduce"] == col["per_step_ms"] and col["overlapped"] is False
@@ -97,8 +97,28 @@ def test_dumped_outputs_of_the_last_timed_step_repeat_bit_for_bit(tmp_path, mode
     assert all(np.array_equal(outs[0][f], outs[1][f]) for f in outs[0]), [f for f in outs[0] if not np.array_equal(outs[0][f], outs[1][f])]
 
 
+def test_plain_one_gpu_run_times_the_primary_workload_only():
+    """A plain run (`python bench.py --gpus 1 --steps K --warmup W`, no --full) does only what its headline figure needs: the primary
+    workload, no second workload, no CPU baseline, no other configs -- and its line still says what the headline is."""
+    need_gpu()
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--platoons", "256", "--buffer-size", "4096", "--steps", "4",
+           "--warmup", "2", "--prewarm-seconds", "0.2"]
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["primary_mode"] == "interfrl" and out["n_gpus"] == 1 and out["steps"] == 4 and out["warmup"] == 2
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["higher_is_better"] is True and out["unit"] == "env-steps/s"
+    assert abs(out["value"] - 256 * 1e3 / out["ms_per_step"]) < 1e-6 * out["value"]
+    assert "also_measured" not in out and "cpu_baseline" not in out
+
+
 def test_default_one_gpu_run_carries_every_single_gpu_baseline_config():
-    """The driver's command (`python bench.py --gpus 1 --steps K --warmup W`) times configs[1] in both federated modes AND
+    """The driver's command with --full (`python bench.py --gpus 1 --steps K --warmup W --full`) times configs[1] in both federated modes AND
     configs[2] (4096 x 10, both modes, replay capacity 100000) AND configs[4] (hidden 1024) in ONE line: `value` stays
     configs[1] interfrl, the others sit under also_measured with their own roofline. Full sizes (82 + 164 GB rings): about a minute."""
     need_gpu()
@@ -108,7 +128,7 @@ def test_default_one_gpu_run_carries_every_single_gpu_baseline_config():
     import bench
 
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--prewarm-seconds", "0.2",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)

@@ -150,7 +150,7 @@ def test_bench_gpus4_plumbing_on_one_device():
     share the one GPU over gloo (RCCL refuses several ranks per device), 64 platoons each. Four, not BASELINE configs[3]'s eight: at
     most six processes may hold one GPU, and this test's own process is one of them (the launcher itself starts eight ranks in
     tests/test_dist_cpu.py's probe mode). One JSON line, n_gpus = 4,
-    the collective timed on its own (`collective.per_step_ms`, `stages_ms.allreduce`) in BOTH of its forms (`collective.forms`:
+    the collective timed on its own (`collective.per_step_ms`, `stages_ms.allreduce`) in BOTH of its forms with --full (`collective.forms`:
     single = one all-reduce of the slab; overlapped = critic block on a side stream under the actor phase), so that a first 8-GPU
     run attributes its own communication cost. Over gloo the trainer picks the single form (host-staged: the overlap is not real,
     ADVICE r04) and says so."""
@@ -164,7 +164,7 @@ def test_bench_gpus4_plumbing_on_one_device():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     n = 4
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--backend", "gloo", "--single-device", "--platoons", "64",
-           "--buffer-size", "256", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--mode", "interfrl"]
+           "--buffer-size", "256", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--mode", "interfrl", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -183,7 +183,7 @@ def test_bench_gpus4_plumbing_on_one_device():
 
 
 def test_bench_gpus2_self_spawned_ranks_run_both_workloads_and_print_one_line():
-    """`python bench.py --gpus 2` with no launcher: the script starts its two ranks itself (children, before any GPU call),
+    """`python bench.py --gpus 2 --full` with no launcher: the script starts its two ranks itself (children, before any GPU call),
     runs nofrl (replicas) and interfrl (one all-reduce of the gradient slab per step) and rank 0 prints ONE JSON line.
     On a 1-GPU box: --single-device + gloo (RCCL refuses two ranks per device); on an N-GPU node the same command
     without those two flags runs over RCCL."""
@@ -196,7 +196,7 @@ def test_bench_gpus2_self_spawned_ranks_run_both_workloads_and_print_one_line():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--single-device", "--platoons", "96",
-           "--buffer-size", "512", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"]
+           "--buffer-size", "512", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -2,13 +2,13 @@
 # Regenerates the round-5 artefacts of profiles/ in one gpurun call (outputs under gpurun_out/profiles_r05/; copy what is to be judged
 # into profiles/). usage: /usr/local/graft/bin/gpurun --timeout 3600 -- 'bash tools/make_profiles_r05.sh'
 R=${GRAFT_REPO_ROOT:-/root/repo}; T=r05; OUT=$R/gpurun_out/profiles_$T; rm -rf $OUT; mkdir -p $OUT; cd $R
-python bench.py > $OUT/${T}_bench_default.json 2>$OUT/err.txt
-python bench.py --pl-size 10 --buffer-size 100000 --no-cpu-baseline --steps 400 --warmup 50 > $OUT/${T}_bench_config3_4096x10.json 2>>$OUT/err.txt
+python bench.py --full > $OUT/${T}_bench_default.json 2>$OUT/err.txt
+python bench.py --full --pl-size 10 --buffer-size 100000 --no-cpu-baseline --steps 400 --warmup 50 > $OUT/${T}_bench_config3_4096x10.json 2>>$OUT/err.txt
 python bench.py --framework centralized --no-cpu-baseline --steps 300 --warmup 30 > $OUT/${T}_bench_centralized_4096x5.json 2>>$OUT/err.txt
 python bench.py --mode interfrl --hidden 1024 --steps 60 --warmup 10 --no-cpu-baseline > $OUT/${T}_bench_config5_hidden1024.json 2>>$OUT/err.txt
 python bench.py --mode interfrl --engine per_agent --no-cpu-baseline --steps 300 --warmup 30 > $OUT/${T}_bench_interfrl_per_agent.json 2>>$OUT/err.txt
-python bench.py --gpus 2 --backend gloo --single-device --platoons 256 --buffer-size 4096 --steps 50 --warmup 10 --no-cpu-baseline --mode interfrl > $OUT/${T}_bench_2ranks_one_gpu_gloo.json 2>>$OUT/err.txt
-python bench.py --one-rank-rccl --mode interfrl --no-cpu-baseline --steps 1000 --warmup 200 > $OUT/${T}_bench_one_rank_rccl.json 2>>$OUT/err.txt
+python bench.py --full --gpus 2 --backend gloo --single-device --platoons 256 --buffer-size 4096 --steps 50 --warmup 10 --no-cpu-baseline --mode interfrl > $OUT/${T}_bench_2ranks_one_gpu_gloo.json 2>>$OUT/err.txt
+python bench.py --full --one-rank-rccl --mode interfrl --no-cpu-baseline --steps 1000 --warmup 200 > $OUT/${T}_bench_one_rank_rccl.json 2>>$OUT/err.txt
 cd /tmp && export TMPDIR=/tmp
 B="python3 $R/bench.py --steps 60 --warmup 20 --no-cpu-baseline"
 pmc_pair() {  # tag, then the arguments of tools/pmc_workload.py

@@ -6,9 +6,9 @@
 # ONLY="driver config5" (environment) restricts the run to those groups: driver, config5, intrafrl, weighted, rccl, env, headline
 R=${GRAFT_REPO_ROOT:-/root/repo}; T=r06; OUT=$R/gpurun_out/profiles_$T; rm -rf $OUT; mkdir -p $OUT; cd $R
 want() { [ -z "$ONLY" ] || [[ " $ONLY " == *" $1 "* ]]; }
-# the driver's own command (all five lines in one JSON) and the 2000-step default
-want driver && python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${T}_bench_driver_command.json 2>$OUT/err.txt
-want driver && python bench.py > $OUT/${T}_bench_default.json 2>>$OUT/err.txt
+# the driver's own command with --full (all five lines in one JSON) and the 2000-step --full run
+want driver && python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/${T}_bench_driver_command.json 2>$OUT/err.txt
+want driver && python bench.py --full > $OUT/${T}_bench_default.json 2>>$OUT/err.txt
 # BASELINE configs[4] on its own, longer; intrafrl; weighted vs unweighted on the same box; the one-rank RCCL communicator
 want config5 && python bench.py --mode interfrl --hidden 1024 --steps 60 --warmup 10 --no-cpu-baseline > $OUT/${T}_bench_config5_hidden1024.json 2>>$OUT/err.txt
 want intrafrl && python bench.py --mode intrafrl --no-cpu-baseline --steps 300 --warmup 30 > $OUT/${T}_bench_intrafrl.json 2>>$OUT/err.txt
@@ -16,7 +16,7 @@ want intrafrl && python bench.py --mode intrafrl --intra-chunks 1 --no-cpu-basel
 want intrafrl && python bench.py --mode intrafrl --directional --no-cpu-baseline --steps 300 --warmup 30 > $OUT/${T}_bench_intrafrl_directional.json 2>>$OUT/err.txt
 want weighted && python bench.py --mode interfrl --no-cpu-baseline --steps 2000 --warmup 200 > $OUT/${T}_bench_interfrl_unweighted.json 2>>$OUT/err.txt
 want weighted && python bench.py --mode interfrl --weighted --no-cpu-baseline --steps 2000 --warmup 200 > $OUT/${T}_bench_interfrl_weighted.json 2>>$OUT/err.txt
-want rccl && python bench.py --one-rank-rccl --mode interfrl --no-cpu-baseline --steps 1000 --warmup 200 > $OUT/${T}_bench_one_rank_rccl.json 2>>$OUT/err.txt
+want rccl && python bench.py --one-rank-rccl --mode interfrl --no-cpu-baseline --full --steps 1000 --warmup 200 > $OUT/${T}_bench_one_rank_rccl.json 2>>$OUT/err.txt
 want env && python tools/env_bandwidth_fused.py $OUT/${T}_env_bandwidth_step_fused.json > $OUT/${T}_env_bandwidth_step_fused.txt 2>>$OUT/err.txt
 cd /tmp && export TMPDIR=/tmp
 pmc_pair() {  # tag, then the arguments of tools/pmc_workload.py
