@@ -31,6 +31,48 @@ def parse_seeds(text):
     return out
 
 
+SWEEP_NAMES = ("actor_lr", "critic_lr", "tau", "gamma", "std_dev", "theta")  # (vec.HP_KEYS)
+
+
+def parse_sweep(items):
+    """``--sweep NAME=V1,V2,...`` values (in flag order) -> [(name, [values])]; an unknown or repeated name, an empty list, a value
+    listed twice or one that is not a number is a ValueError."""
+    out, seen = [], set()
+    for item in items:
+        name, sep, vals = str(item).partition("=")
+        name = name.strip()
+        if not sep or name not in SWEEP_NAMES:
+            raise ValueError(f"--sweep: {item!r} is not NAME=V1,V2,... with NAME one of {', '.join(SWEEP_NAMES)}")
+        if name in seen:
+            raise ValueError(f"--sweep: {name} is swept twice")
+        seen.add(name)
+        parts = [v.strip() for v in vals.split(",")]
+        if not vals.strip() or any(not v for v in parts):
+            raise ValueError(f"--sweep {name}: empty value list or item")
+        try:
+            nums = [float(v) for v in parts]
+        except ValueError:
+            raise ValueError(f"--sweep {name}: {vals!r} holds a value that is not a number") from None
+        if len(set(nums)) != len(nums):
+            raise ValueError(f"--sweep {name}: a value is listed twice in {vals!r}")
+        out.append((name, nums))
+    return out
+
+
+def sweep_experiments(sweep, seeds):
+    """The experiments of a sweep: the product of its value lists in flag order (the last flag varying fastest), times the seeds
+    (innermost) -> [(label, {name: value}, seed)]. The label names every swept value: ``actor_lr=0.0001_gamma=0.95``."""
+    import itertools
+
+    names = [n for n, _ in sweep]
+    out = []
+    for combo in itertools.product(*[v for _, v in sweep]):
+        h = dict(zip(names, combo))
+        label = "_".join(f"{n}={v!r}" for n, v in h.items())
+        out.extend((label, h, int(k)) for k in seeds)
+    return out
+
+
 def get_cmdl_args(argv, conf):
     ap = argparse.ArgumentParser(prog="python -m avddpg_amd", description="avddpg hot path on MI355X")
     sub = ap.add_subparsers(dest="mode")
@@ -81,6 +123,12 @@ def get_cmdl_args(argv, conf):
                          "platoons (nofrl; interfrl --engine per_agent). Writes <out>/<timestamp>/seed<k>/ per seed (curve.csv, the "
                          "actors, conf.json). Not with --seed, intrafrl, weights aggregation or the centralized framework (not in the "
                          "reference CLI)")
+    tr.add_argument("--sweep", action="append", default=None, metavar="NAME=V1,V2,...",
+                    help="--rng device --episodes platoon: a hyperparameter sweep in ONE process and launch chain over actor_lr, critic_lr, "
+                         "tau, gamma, std_dev or theta (repeat the flag for a grid; the last flag varies fastest), times --seeds (or "
+                         "--seed). Experiment (values, k) is bit-for-bit what `tr --seed k` with those values trains alone (nofrl; "
+                         "interfrl --engine per_agent; --engine fused3: what `tr --seeds` with those values trains). Writes <out>/<timestamp>/<label>/seed<k>/ per experiment and sweep.csv (not in "
+                         "the reference CLI)")
     tr.add_argument("--out", type=str, default=".outputs")
     es = sub.add_parser("esim", help="run in evaluation/simulator mode")
     es.add_argument("exp_path", type=str)
@@ -97,6 +145,16 @@ def get_cmdl_args(argv, conf):
             args.seeds = parse_seeds(args.seeds)
         except ValueError as e:
             ap.error(str(e))
+    if getattr(args, "sweep", None) is not None:
+        if args.rng != "device" or args.episodes != "platoon":
+            ap.error("--sweep needs --rng device --episodes platoon")
+        try:
+            args.sweep = parse_sweep(args.sweep)
+        except ValueError as e:
+            ap.error(str(e))
+        for name, _ in args.sweep:  # (the parsed values: argparse also takes abbreviations such as --actor)
+            if getattr(args, name, None) is not None:
+                ap.error(f"--sweep {name} and --{name} are mutually exclusive")
     ev = getattr(args, "eval_platoons", None)
     if ev is not None:
         if args.episodes != "platoon":
@@ -135,6 +193,10 @@ def main(argv=None, conf=None):
         np.random.seed(conf.random_seed)  # rand.set_global_seed (src/rand.py:6-15)
         base = os.path.join(args.out, datetime.datetime.now().strftime("%y%m%d_%H%M%S"))
         os.makedirs(base, exist_ok=True)
+        if args.sweep is not None:
+            train_sweep(args, conf, base)
+            print(base)
+            return
         if args.seeds is not None:
             train_seed_batch(args, conf, base)
             print(base)
@@ -220,27 +282,49 @@ def main(argv=None, conf=None):
         raise SystemExit("modes: tr, esim")
 
 
-def train_seed_batch(args, conf, base):
+def train_sweep(args, conf, base):
+    """`tr --sweep`: one VecTrainer(seeds=..., hparams=...) over the grid x seeds (sweep_experiments), experiment (label, k) written to
+    <base>/<label>/seed<k>/ as `tr --seed k` with those values writes its own directory (conf.json holds the values in the reference's
+    fields, the grid as `sweep`), and <base>/sweep.csv: one row per experiment with its values, seed, pl_rew_for_simulation and the
+    last curve point's evaluator score."""
+    seeds = list(args.seeds) if args.seeds is not None else [int(conf.random_seed)]
+    exps = sweep_experiments(args.sweep, seeds)
+    rows = train_seed_batch(args, conf, base, experiments=exps)
+    import csv
+
+    with open(os.path.join(base, "sweep.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["label", *SWEEP_NAMES, "seed", "pl_rew_for_simulation", "final_evaluator_score"])
+        for (label, _, k), (ce, last) in zip(exps, rows):
+            w.writerow([label, *[repr(float(getattr(ce, n))) for n in SWEEP_NAMES], k, repr(ce.pl_rew_for_simulation), last])
+
+
+def train_seed_batch(args, conf, base, experiments=None):
     """`tr --seeds`: the experiments of one VecTrainer(seeds=...) batch, each written to <base>/seed<k>/ exactly as `tr --seed k
     --episodes platoon` writes its own directory (curve.csv, the saved agents, conf.json), plus conf.json's `seed_batch`. The curve
-    points' evaluator scores of all experiments come from ONE evaluator rollout launch (VecTrainer.evaluator_scores)."""
-    import copy
-
+    points' evaluator scores of all experiments come from ONE evaluator rollout launch (VecTrainer.evaluator_scores).
+    experiments (`tr --sweep`): [(label, hparams dict, seed)] -> <base>/<label>/seed<k>/, conf.json with the experiment's values and
+    `sweep`; returns [(experiment Config, last curve point's evaluator score)]."""
     import numpy as np
 
     from . import artifacts, trainer
 
-    seeds = list(args.seeds)
+    if experiments is None:
+        seeds, hps, flag = list(args.seeds), None, "--seeds"
+        dirs = [os.path.join(base, f"seed{k}") for k in seeds]
+    else:
+        seeds, hps, flag = [k for _, _, k in experiments], [h for _, h, _ in experiments], "--sweep"
+        dirs = [os.path.join(base, label, f"seed{k}") for label, _, k in experiments]
     E = len(seeds)
     try:
         vt = trainer.VecTrainer(conf, rng="device", auto_reset="platoon", shared_engine=args.engine,
-                                fused_update=conf.fed_method == conf.nofrl, seeds=seeds)
+                                fused_update=conf.fed_method == conf.nofrl, seeds=seeds, hparams=hps)
     except ValueError as e:
-        raise SystemExit(f"--seeds: {e}")
+        raise SystemExit(f"{flag}: {e}")
     vt.reset_episode()
     P = vt.P_exp
     n_eval = None if args.eval_platoons is None else (P if args.eval_platoons == "all" else min(P, int(args.eval_platoons)))
-    dirs = [os.path.join(base, f"seed{k}") for k in seeds]
+    last = [None] * E
     for d in dirs:
         os.makedirs(d, exist_ok=True)
 
@@ -248,7 +332,7 @@ def train_seed_batch(args, conf, base):
         sc = vt.evaluator_scores(range(max(1, n_eval or 1)))
         out = []
         for e in range(E):
-            line = f"{float(sc[e, 0]):.3f}"
+            line = last[e] = f"{float(sc[e, 0]):.3f}"
             if n_eval is not None:
                 row = sc[e, :n_eval]
                 line += f",{float(np.mean(row)):.3f},{float(np.min(row)):.3f},{float(np.max(row)):.3f}"
@@ -275,10 +359,10 @@ def train_seed_batch(args, conf, base):
         print(f"warning: {vt.nonfinite_updates()} weight-set updates were skipped for non-finite gradients", file=sys.stderr)
     sims = vt.run_simulations()  # [E][P], one rollout launch
     n_save = min(P, 4 if args.save_platoons is None else args.save_platoons)
+    done = []
     for e, (k, d) in enumerate(zip(seeds, dirs)):
         artifacts.save_agents(d, vt.experiment_agents(e), n_save, vt.M, shared=vt.shared)
-        ce = copy.copy(conf)
-        ce.random_seed = k
+        ce = vt.experiment_conf(e)  # (its seed; in a sweep also its values, in the reference's fields)
         ce.pl_rews_for_simulations = sims[e]
         ce.pl_rew_for_simulation = float(np.average(sims[e]))
         ce.saved_platoons = int(n_save)
@@ -286,8 +370,14 @@ def train_seed_batch(args, conf, base):
         ce.episode_clock = ("per-platoon episodes on the device; schedule predicates on step // steps_per_episode; weighted averaging "
                             "(if enabled) from step weighted_window x steps_per_episode on, weights from each agent's last "
                             "weighted_window closed episodes")
-        ce.seed_batch = seeds
+        if experiments is None:
+            ce.seed_batch = seeds
+        else:
+            ce.seed_batch = list(dict.fromkeys(seeds))
+            ce.sweep = [[n, list(v)] for n, v in args.sweep]  # the grid in flag order (a list: conf.json keeps lists, not dicts)
         artifacts.config_writer(os.path.join(d, "conf.json"), ce)
+        done.append((ce, last[e]))
+    return done
 
 
 if __name__ == "__main__":

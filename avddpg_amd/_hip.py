@@ -34,6 +34,12 @@ class EnvConsts(C.Structure):
                 ("C", (C.c_float * 4) * AVD_MAX_L)]
 
 
+class HParams(C.Structure):
+    """avd_hparams: one experiment's row of a hyperparameter sweep's device table (32 bytes)"""
+    _fields_ = [("actor_lr", C.c_float), ("critic_lr", C.c_float), ("tau", C.c_float), ("one_minus_tau", C.c_float),
+                ("gamma", C.c_float), ("ou_theta", C.c_float), ("ou_scale", C.c_float), ("reserved", C.c_float)]
+
+
 _LAYOUT_FIELDS = ["S", "A", "H1", "H2", "Ha", "B",
                   "aW1", "ab1", "ag1", "abe1", "aW2", "ab2", "ag2", "abe2", "aW3", "ab3", "actor_size",
                   "cWs", "cbs", "cgs", "cbes", "cWa", "cba", "cga", "cbea", "cW2", "cb2", "cg3", "cbe3", "cW3", "cb3",
@@ -68,6 +74,14 @@ _PROTOS = {
     "avd_env_reset_seeds_f32": [_P, _i, _i, _P, _P, _P, _i, _P, _i, _u64, _P, _P],
     "avd_episode_end_seeds_f32": [_P, _i, _i, _i, _P, _P, _P, _P, _P, _P, _i, _P, _P, _P, _P, _i, _P, _i, _u64, _P],
     "avd_replay_sample_seeds_f32": [_i, _i, _i, _i, _i, _P, _i, _P, _i, _i, _u64, _P, _P, _P, _P, _P, _P],
+    "avd_step_fused_hp_f32": [_P, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _f, _f, _f, _i, _P, _P, _i,
+                              _u64, _u64, _P, _i, _i64, _P, _P],
+    "avd_learn_hp_f32": [_LP, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _f, _P, _P, _P, _i, _i, _P],
+    "avd_learn_update_hp_f32": [_LP, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _P, _P, _P, _i, _i, _P],
+    "avd_learn_update_act_hp_f32": [_LP, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _P, _P, _P, _i, _P, _P, _i, _i, _P],
+    "avd_adam_polyak_hp_f32": [_LP, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P],
+    "avd_adam_polyak_guarded_hp_f32": [_LP, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P],
+    "avd_learn_set_split_hp_f16x3": [_LP, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _P, _P, _P, C.c_size_t, _P, _i, _i, _P],
     "avd_actor_forward_set_f32": [_LP, _i, _i, _P, _P, _P, _i, _f, _P, _P, _P],
     "avd_replay_add_f32": [_i, _i, _i, _i, _P, _i64, _P, _P, _i, _P, _P, _P],
     "avd_replay_indices": [_i, _i, _i, _u64, _u64, _P, _P],

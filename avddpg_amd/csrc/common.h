@@ -39,6 +39,25 @@ inline int check_launch(const char* what) {
         }                             \
     } while (0)
 
+// ---- hyperparameter sweeps (the *_hp_* entry points) --------------------------------------
+// The per-experiment table of a sweep: weight set / agent j belongs to experiment (j / block) % n_groups. The HP twins of a kernel
+// take one HpRef as a trailing variadic argument (`HpRef... hp`, empty in the scalar instantiation, whose parameter list and code
+// stay those of the original kernel) and read their values from it where the kernel already knows which experiment it serves.
+struct HpRef {
+    const avd_hparams* hp;
+    int n_groups, block;
+};
+template <class... H>
+__device__ __forceinline__ const avd_hparams& hp_of(int j, const H&... h) {
+    const HpRef r{h...};
+    return r.hp[(j / r.block) % r.n_groups];
+}
+
+#define AVD_REQUIRE_HP(who, d_hp, n_groups, set_block, count)                                                                  \
+    AVD_REQUIRE((d_hp) && (n_groups) >= 1 && (set_block) >= 1 && (count) > 0 && (count) % ((n_groups) * (set_block)) == 0,    \
+                "%s: d_hp=%p n_groups=%d set_block=%d count=%d (the count must be a multiple of n_groups x set_block)", who,     \
+                (const void*)(d_hp), (int)(n_groups), (int)(set_block), (int)(count))
+
 // ---- Philox4x32-10 (Salmon et al. 2011), counter-based: no state in HBM -------------------
 struct u32x4 {
     uint32_t x, y, z, w;

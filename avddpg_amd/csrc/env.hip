@@ -291,8 +291,9 @@ struct StepArgs {
     int n_groups;
 };
 
-template <bool G>
-__global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs a) {
+// HP (avd_step_fused_hp_f32, with G): platoon g's ou_theta / ou_scale from the sweep table, row g % n_groups (its experiment)
+template <bool G, bool HP = false, class... H>
+__global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs a, H... hp) {
 #pragma clang fp contract(off)
     __shared__ float sA[AVD_MAX_L][16], sB[AVD_MAX_L][4], sC[AVD_MAX_L][4];
     const avd_env_consts* cst = a.cst;
@@ -316,7 +317,12 @@ __global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs 
         const u32x4 rn = philox_at(key, a.ou_counter, G ? (uint32_t)((long)pl * L + i) : (uint32_t)v, STREAM_OU);
         const float nrm = box_muller(rn.x, rn.y, nullptr);
         const float st = a.ou_state[v];
-        const float noise = (st + (a.theta * (a.mean - st)) * a.dt) + a.scale * nrm;
+        float theta = a.theta, scale = a.scale;
+        if constexpr (HP) {
+            const avd_hparams& h = hp_of(p, hp...);  // (block 1: row p % n_groups)
+            theta = h.ou_theta, scale = h.ou_scale;
+        }
+        const float noise = (st + (theta * (a.mean - st)) * a.dt) + scale * nrm;
         a.ou_state[v] = noise;
         uu = fminf(fmaxf(a.actor_out[v] + noise, a.lo), a.hi);
         a.action[v] = uu;
@@ -497,14 +503,14 @@ extern "C" int avd_uniform_f32(int n, float* out, float half_width, uint64_t see
 }
 
 // the two step_fused entry points: arguments checked, StepArgs filled, step_fused_kernel<G> launched
-template <bool G>
+template <bool G, bool HP = false>
 static int step_fused_launch(const char* who, const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
                              float* prev_a, float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done,
                              int32_t* any_done_other, const float* actor_out, float* ou_state, float* action, float* leader_exog,
                              float ou_theta, float ou_mean, float ou_dt, float ou_std_dev, float action_low, float action_high,
                              float exog_scale, int exog_uniform, uint64_t seed, const uint64_t* d_seeds, int n_groups,
                              uint64_t ou_counter, uint64_t exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward,
-                             void* stream) {
+                             void* stream, const avd_hparams* d_hp = nullptr) {
     AVD_REQUIRE(P > 0 && L > 0 && L <= AVD_MAX_L && (S == 3 || S == 4), "%s: P=%d L=%d S=%d", who, P, L, S);
     AVD_REQUIRE(d_consts && x_in && x_out && prev_a && reward && done && actor_out && ou_state && action && leader_exog,
                 "%s: null pointer", who);
@@ -518,7 +524,11 @@ static int step_fused_launch(const char* who, const avd_env_consts* d_consts, in
     a.seed = seed, a.ou_counter = ou_counter, a.exog_counter = exog_counter, a.seeds = d_seeds, a.n_groups = n_groups;
     a.ring = ring, a.cap = cap, a.slot = ring ? (int)(replay_counter % cap) : 0, a.ep_reward = ep_reward;
     const int per_block = (ENV_THREADS / 64) * (64 / L);
-    hipLaunchKernelGGL(step_fused_kernel<G>, dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS), 0, (hipStream_t)stream, a);
+    if constexpr (HP)
+        hipLaunchKernelGGL((step_fused_kernel<G, true, HpRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS), 0,
+                           (hipStream_t)stream, a, HpRef{d_hp, n_groups, 1});
+    else
+        hipLaunchKernelGGL(step_fused_kernel<G>, dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS), 0, (hipStream_t)stream, a);
     return check_launch(who);
 }
 
@@ -553,6 +563,21 @@ extern "C" int avd_step_fused_seeds_f32(const avd_env_consts* d_consts, int P, i
                                    any_done, any_done_other, actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt,
                                    ou_std_dev, action_low, action_high, exog_scale, exog_uniform, 0, d_seeds, n_groups, ou_counter,
                                    exog_counter, ring, cap, replay_counter, ep_reward, stream);
+}
+
+extern "C" int avd_step_fused_hp_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
+                                     float* prev_a, float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done,
+                                     int32_t* any_done_other, const float* actor_out, float* ou_state, float* action, float* leader_exog,
+                                     float ou_mean, float ou_dt, float action_low, float action_high, float exog_scale, int exog_uniform,
+                                     const uint64_t* d_seeds, const avd_hparams* d_hp, int n_groups, uint64_t ou_counter,
+                                     uint64_t exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward, void* stream) {
+    AVD_REQUIRE_GROUPS("avd_step_fused_hp_f32", P);
+    AVD_REQUIRE_HP("avd_step_fused_hp_f32", d_hp, n_groups, 1, P);
+    // (the scalar theta / scale the kernel would read are replaced per platoon; zeros here keep them out of the arithmetic)
+    return step_fused_launch<true, true>("avd_step_fused_hp_f32", d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done,
+                                         any_done, any_done_other, actor_out, ou_state, action, leader_exog, 0.f, ou_mean, ou_dt, 0.f,
+                                         action_low, action_high, exog_scale, exog_uniform, 0, d_seeds, n_groups, ou_counter,
+                                         exog_counter, ring, cap, replay_counter, ep_reward, stream, d_hp);
 }
 
 extern "C" int avd_env_reset_seeds_f32(const avd_env_consts* d_consts, int P, int L, float* x, float* prev_a, float* cum_accel,

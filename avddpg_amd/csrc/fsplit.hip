@@ -442,8 +442,10 @@ struct HeadArgs {
 #define HEAD_SLOW 3
 #endif
 
-template <int S, class NET, int MODE>
-__global__ __launch_bounds__(NT) void head_kernel(const HeadArgs p) {
+// HP (OUT_TD of avd_learn_set_split_hp_f16x3): the TD epilogue's gamma is the workgroup's weight set's, row (set / block) % n_groups of
+// the sweep table; nothing else differs from the scalar instantiation.
+template <int S, class NET, int MODE, bool HP = false, class... H>
+__global__ __launch_bounds__(NT) void head_kernel(const HeadArgs p, H... hp) {
     constexpr int K = NET::K, NKS = NET::NKS, NFT = NET::NFT, LD = NET::LD;  // LD/2 = 4 (mod 8) dwords: conflict-free b128
     constexpr int NTH = NT;  // 8 waves: two per SIMD at <= 256 registers
     constexpr bool BOTH = (MODE == HEAD_BOTH);
@@ -781,7 +783,11 @@ __global__ __launch_bounds__(NT) void head_kernel(const HeadArgs p) {
             for (int tt = 0; tt < 4; ++tt) mb[tt] = mask_t(acc[tt]);
             mask_store(mb, p.sm + ri * 4);
         } else {  // OUT_TD
-            if (h == 0) p.out[ri] = ty + p.gamma * z;
+            if constexpr (HP) {
+                if (h == 0) p.out[ri] = ty + hp_of(set, hp...).gamma * z;
+            } else {
+                if (h == 0) p.out[ri] = ty + p.gamma * z;
+            }
         }
         HSTAMP(2);  // epilogue
 #ifdef AVD_STAMP
@@ -1574,10 +1580,10 @@ static int check_shape(const avd_mlp_layout* L, int n_agents, int n_sets, const 
 // so that a multi-GPU caller can put the critic block's all-reduce on a side stream while the actor phase still runs
 // (avddpg_amd/trainer.py; workers/trainer.py:400-431 averages the two gradient lists independently).
 enum Phase { PH_CRITIC = 1, PH_ACTOR = 2, PH_BOTH = 3 };
-template <int S>
+template <int S, class... H>
 static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, const float* theta, const float* stats, const float* theta_t,
                const float* stats_t, const float* s, const float* a, const float* r, const float* s2, const float* aw, float gamma,
-               float high, float* grads, float* losses, unsigned char* ws, const Plan& pl, hipStream_t st) {
+               float high, float* grads, float* losses, unsigned char* ws, const Plan& pl, hipStream_t st, H... hp) {
     PrepArgs pa;
     pa.L = L, pa.S = S, pa.theta = theta, pa.stats = stats, pa.theta_t = theta_t, pa.stats_t = stats_t;
     pa.wap = (unsigned*)(ws + pl.wap), pa.bad = (int*)(ws + pl.bad), pa.smax = (unsigned*)(ws + pl.bad + sizeof(int));
@@ -1606,9 +1612,10 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
     h.n_agents = n_agents, h.n_sets = n_sets, h.gamma = gamma, h.high = high, h.inv_n = inv_n, h.aw = aw, h.sm = sm, h.g3 = g3, h.dmu = dmu;
     h.act2 = nullptr, h.part_s2 = nullptr, h.stamp = nullptr, h.bad = bad, h.part_m = nullptr, h.tz = F(pl.tz), h.abl = 0;
     if (const char* e = AVD_DIAG_ENV("FSPLIT_ABL")) h.abl = atoi(e);
-    auto head = [&](auto kern, int ni, const f16x8* x, const float* act, const float* rr, const float* yin, float* out, float* part_s) {
+    auto head = [&](auto kern, int ni, const f16x8* x, const float* act, const float* rr, const float* yin, float* out, float* part_s,
+                    auto... extra) {
         h.net = net[ni], h.xf = x, h.act = act, h.r = rr, h.yin = yin, h.out = out, h.part_s = part_s;
-        hipLaunchKernelGGL(kern, grid, block, 0, st, h);
+        hipLaunchKernelGGL(kern, grid, block, 0, st, h, extra...);
     };
     DwArgs dw;
     dw.n_agents = n_agents, dw.n_sets = n_sets, dw.sm = sm, dw.g3 = g3, dw.x = s, dw.stamp = nullptr, dw.abl = 0;
@@ -1645,7 +1652,10 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
         hipLaunchKernelGGL(pack_x_kernel<S>, dim3((unsigned)((2 * nrows + 255) / 256), 2), dim3(256), 0, st, pk);
         // 1-2: targets
         head(head_kernel<S, ActorS, OUT_TANH>, 2, xfs2, nullptr, nullptr, nullptr, a2, nullptr);
-        head(head_kernel<S, CriticS, OUT_TD>, 3, xfs2, a2, r, nullptr, y, nullptr);
+        if constexpr (sizeof...(H) > 0)  // a sweep: each set's gamma (avd_learn_set_split_hp_f16x3)
+            head(head_kernel<S, CriticS, OUT_TD, true, H...>, 3, xfs2, a2, r, nullptr, y, nullptr, hp...);
+        else
+            head(head_kernel<S, CriticS, OUT_TD>, 3, xfs2, a2, r, nullptr, y, nullptr);
         // 3: mu -- and the actor's relu masks + tanh(z) for its backward pass (no second actor forward: r03's HEAD_ACTOR)
         h.sm = sma;
         head(head_kernel<S, ActorS, OUT_TANH_SAVE>, 0, xfs, nullptr, nullptr, nullptr, mu, nullptr);
@@ -1718,10 +1728,11 @@ extern "C" int avd_learn_set_split_workspace(const avd_mlp_layout* lay, int n_ag
     return AVD_OK;
 }
 
+template <class... H>
 static int split_entry(int phases, const char* who, const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
                        const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r, const float* s2,
                        const float* agent_weight, float gamma, float high, float* grads, float* losses, void* workspace,
-                       size_t workspace_bytes, void* stream) {
+                       size_t workspace_bytes, void* stream, H... hp) {
     int rc = fsplit::check_shape(lay, n_agents, n_sets, who);
     if (rc) return rc;
     const bool cr = phases & fsplit::PH_CRITIC;
@@ -1733,9 +1744,9 @@ static int split_entry(int phases, const char* who, const avd_mlp_layout* lay, i
         return check_launch("avd_learn_set_split: hipMemsetAsync(grads)");
     if (lay->S == 4)
         return fsplit::run<4>(phases, *lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2, agent_weight, gamma, high, grads,
-                              losses, (unsigned char*)workspace, pl, (hipStream_t)stream);
+                              losses, (unsigned char*)workspace, pl, (hipStream_t)stream, hp...);
     return fsplit::run<3>(phases, *lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2, agent_weight, gamma, high, grads, losses,
-                          (unsigned char*)workspace, pl, (hipStream_t)stream);
+                          (unsigned char*)workspace, pl, (hipStream_t)stream, hp...);
 }
 
 extern "C" int avd_learn_set_split_f16x3(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
@@ -1744,6 +1755,17 @@ extern "C" int avd_learn_set_split_f16x3(const avd_mlp_layout* lay, int n_agents
                                           float* losses, void* workspace, size_t workspace_bytes, void* stream) {
     return split_entry(fsplit::PH_BOTH, "avd_learn_set_split_f16x3", lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2,
                        agent_weight, gamma, high, grads, losses, workspace, workspace_bytes, stream);
+}
+
+// a hyperparameter sweep: the whole call with each weight set's gamma from d_hp (set j: row (j / set_block) % n_groups) in the TD epilogue
+extern "C" int avd_learn_set_split_hp_f16x3(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
+                                            const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
+                                            const float* s2, const float* agent_weight, float high, float* grads, float* losses,
+                                            void* workspace, size_t workspace_bytes, const avd_hparams* d_hp, int n_groups, int set_block,
+                                            void* stream) {
+    AVD_REQUIRE_HP("avd_learn_set_split_hp_f16x3", d_hp, n_groups, set_block, n_sets);
+    return split_entry(fsplit::PH_BOTH, "avd_learn_set_split_hp_f16x3", lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2,
+                       agent_weight, 0.f, high, grads, losses, workspace, workspace_bytes, stream, HpRef{d_hp, n_groups, set_block});
 }
 
 // deprecated alias (r03's name: the operand pairs were bf16 then; every pair has been fp16 since r04)

@@ -598,14 +598,16 @@ __device__ __forceinline__ void l2_coefs(const L2Raw& r, Lds& l, unsigned H2, un
     }
 }
 
-template <int S, int H1, int H2, int HA, bool FUSED>
+// HP (the avd_learn*_hp_f32 entries): gamma, the step sizes and tau / 1 - tau of the agent's experiment from the sweep table, each
+// read where the pass that uses it starts (scalar loads: the agent is the workgroup), not held from the kernel's start.
+template <int S, int H1, int H2, int HA, bool FUSED, bool HP = false, class... H>
 __global__ __launch_bounds__(FT, 2) void learn_kernel_l(avd_mlp_layout L_arg, int set_mod, const float* __restrict__ theta,
                                                          const float* __restrict__ stats, float* __restrict__ theta_t,
                                                          float* __restrict__ stats_t, const float* __restrict__ s,
                                                          const float* __restrict__ a, const float* __restrict__ r,
                                                          const float* __restrict__ s2, float gamma, float high,
                                                          float* __restrict__ grads, float* __restrict__ losses,
-                                                         UpdArgs upd) {
+                                                         UpdArgs upd, H... hp) {
     static_assert(H1 <= FT && HA <= FT && 2 * H2 == FT && S <= 4, "widths");
     constexpr int KC = H1 + HA, LDB = ld_of(H2);
     // The layout (43 offsets) is the kernel's FIRST argument, i.e. the first bytes of the kernarg segment. It is read
@@ -738,10 +740,15 @@ __global__ __launch_bounds__(FT, 2) void learn_kernel_l(avd_mlp_layout L_arg, in
             PH(6);
         }
         if (it == 0) {  // TD target, no done mask (trainer.py:494)
+            if constexpr (HP) gamma = hp_of(agent, hp...).gamma;
             if (tid < TILE) l.sY[tid] = fmaf(gamma, l.sQ[tid], l.sR[tid]);
             if constexpr (FUSED) {  // the frozen BN statistics take part in the soft update too (ddpgagent.py:44-53)
 #pragma clang fp contract(off)
                 float* stt = stats_t + (long)set * L.stats_size;
+                if constexpr (HP) {
+                    const avd_hparams& h = hp_of(agent, hp...);
+                    upd.tau = h.tau, upd.omt = h.one_minus_tau;
+                }
                 for (int i = tid; i < L.stats_size; i += FT) stt[i] = net.st[i] * upd.tau + stt[i] * upd.omt;
             }
             lds_barrier();
@@ -787,6 +794,11 @@ __global__ __launch_bounds__(FT, 2) void learn_kernel_l(avd_mlp_layout L_arg, in
                 const int t = upd.step[agent];
                 const float b1p = (float)pow((double)0.9f, (double)t), b2p = (float)pow((double)0.999f, (double)t);
                 const float root = sqrtf(1.0f - b2p);
+                if constexpr (HP) {  // (tau / 1 - tau as well: the W2 epilogues of this pass and the small tensors' update read them)
+                    const avd_hparams& h = hp_of(agent, hp...);
+                    upd.actor_lr = h.actor_lr, upd.critic_lr = h.critic_lr;
+                    bulk.tau = h.tau, bulk.omt = h.one_minus_tau;
+                }
                 // wave-uniform values computed on the vector unit: moved to SGPRs so that they cost no vector register for
                 // the rest of the kernel
                 bulk.alpha_a = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(
@@ -877,10 +889,11 @@ __global__ __launch_bounds__(FT, 2) void learn_kernel_l(avd_mlp_layout L_arg, in
     PH_CLK_END();
 }
 
-template <int S, bool FUSED>
+template <int S, bool FUSED, class... H>
 static int launch(const avd_mlp_layout* lay, int n_agents, int set_mod, const float* theta, const float* stats,
                   float* theta_t, float* stats_t, const float* s, const float* a, const float* r, const float* s2,
-                  float gamma, float high, float* grads, float* losses, UpdArgs upd, void* stream) {
+                  float gamma, float high, float* grads, float* losses, UpdArgs upd, void* stream, H... hp) {
+    constexpr bool HP = sizeof...(H) > 0;
     constexpr int H1 = 256, H2 = 128, HA = 48;
     size_t lds = sizeof(float) * lds_floats(H1 + HA, H2);
     if (const char* kb = AVD_DIAG_ENV("LEAN_LDS_KB")) {  // diagnostics: force 1 workgroup per CU; never below what the kernel needs
@@ -888,14 +901,15 @@ static int launch(const avd_mlp_layout* lay, int n_agents, int set_mod, const fl
         if (want > lds && want <= 160 * 1024) lds = want;
     }
     static_assert(sizeof(float) * lds_floats(H1 + HA, H2) <= 80 * 1024, "two workgroups per CU");
-    hipError_t e = hipFuncSetAttribute((const void*)learn_kernel_l<S, H1, H2, HA, FUSED>,
+    hipError_t e = hipFuncSetAttribute((const void*)learn_kernel_l<S, H1, H2, HA, FUSED, HP, H...>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) {
         set_error("lean_launch: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
         return AVD_E_LAUNCH;
     }
-    hipLaunchKernelGGL((learn_kernel_l<S, H1, H2, HA, FUSED>), dim3(n_agents), dim3(FT), lds, (hipStream_t)stream, *lay,
-                       set_mod, theta, stats, theta_t, stats_t, s, a, r, s2, gamma, high, grads, losses, upd);
+    hipLaunchKernelGGL((learn_kernel_l<S, H1, H2, HA, FUSED, HP, H...>), dim3(n_agents), dim3(FT), lds, (hipStream_t)stream, *lay,
+                       set_mod, theta, stats, theta_t, stats_t, s, a, r, s2, gamma, high, grads, losses, upd, hp...);
+    if constexpr (HP) return check_launch(FUSED ? "avd_learn_update_hp_f32 (lean)" : "avd_learn_hp_f32 (lean)");
     return check_launch(FUSED ? "avd_learn_update_f32 (lean)" : "avd_learn_f32 (lean)");
 }
 
@@ -925,6 +939,30 @@ int lean_launch(const avd_mlp_layout* lay, bool fused, int n_agents, int set_mod
 #define AVD_LEAN(SS, FF)                                                                                              \
     return lean::launch<SS, FF>(lay, n_agents, set_mod, theta, stats, theta_t, stats_t, s, a, r, s2, gamma, high, grads, \
                                 losses, upd, stream)
+    if (lay->S == 4) {
+        if (fused) AVD_LEAN(4, true);
+        AVD_LEAN(4, false);
+    }
+    if (fused) AVD_LEAN(3, true);
+    AVD_LEAN(3, false);
+#undef AVD_LEAN
+}
+
+// the HP twins (avd_learn_hp_f32, avd_learn_update[_act]_hp_f32): reference widths only, arguments checked by the caller
+int lean_launch_hp(const avd_mlp_layout* lay, bool fused, int n_agents, int set_mod, const float* theta, const float* stats,
+                   float* theta_t, float* stats_t, const float* s, const float* a, const float* r, const float* s2, float high,
+                   float* grads, float* losses, UpdArgs upd, const avd_hparams* d_hp, int n_groups, int set_block, void* stream) {
+    if (!(lay->A == 1 && lay->H1 == 256 && lay->H2 == 128 && lay->Ha == 48 && (lay->S == 3 || lay->S == 4) &&
+          lay->B == TILE)) {
+        set_error("%s: a hyperparameter sweep runs the reference widths 256/128/48, A=1, B=64, S in {3,4} only (got %d/%d/%d, A=%d, "
+                  "B=%d, S=%d)", fused ? "avd_learn_update_hp_f32" : "avd_learn_hp_f32", lay->H1, lay->H2, lay->Ha, lay->A, lay->B,
+                  lay->S);
+        return AVD_E_UNSUPPORTED;
+    }
+    const HpRef hr{d_hp, n_groups, set_block};
+#define AVD_LEAN(SS, FF)                                                                                                       \
+    return lean::launch<SS, FF>(lay, n_agents, set_mod, theta, stats, theta_t, stats_t, s, a, r, s2, 0.f, high, grads, losses, \
+                                upd, stream, hr)
     if (lay->S == 4) {
         if (fused) AVD_LEAN(4, true);
         AVD_LEAN(4, false);

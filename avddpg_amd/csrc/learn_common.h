@@ -696,5 +696,9 @@ int cen_launch_update(const avd_mlp_layout* lay, int n_agents, const float* thet
 int lean_launch(const avd_mlp_layout* lay, bool fused, int n_agents, int set_mod, const float* theta, const float* stats,
                 float* theta_t, float* stats_t, const float* s, const float* a, const float* r, const float* s2,
                 float gamma, float high, float* grads, float* losses, UpdArgs upd, void* stream);
+// its HP twins: gamma, the step sizes and tau per agent from d_hp (agent j: row (j / set_block) % n_groups); upd's scalars unused
+int lean_launch_hp(const avd_mlp_layout* lay, bool fused, int n_agents, int set_mod, const float* theta, const float* stats,
+                   float* theta_t, float* stats_t, const float* s, const float* a, const float* r, const float* s2, float high,
+                   float* grads, float* losses, UpdArgs upd, const avd_hparams* d_hp, int n_groups, int set_block, void* stream);
 
 }  // namespace avd

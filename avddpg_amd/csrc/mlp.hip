@@ -1676,6 +1676,65 @@ extern "C" int avd_learn_update_f32(const avd_mlp_layout* lay, int n_agents, con
                              actor_lr, critic_lr, tau, grads_scratch, losses, nullptr, 0, nullptr, stream);
 }
 
+// ---- hyperparameter sweeps: the lean learner's HP twins (reference widths only; the general / centralized kernels have none) ----
+extern "C" int avd_learn_hp_f32(const avd_mlp_layout* lay, int n_agents, int set_mod, const float* theta, const float* stats,
+                                const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
+                                const float* s2, float high, float* grads, float* losses, const avd_hparams* d_hp, int n_groups,
+                                int set_block, void* stream) {
+    int rc = check_mlp_dims(lay, "avd_learn_hp_f32");
+    if (rc) return rc;
+    AVD_REQUIRE(n_agents > 0 && set_mod >= 0, "avd_learn_hp_f32: n_agents=%d set_mod=%d", n_agents, set_mod);
+    AVD_REQUIRE(theta && stats && theta_t && stats_t && s && a && r && s2 && grads, "avd_learn_hp_f32: null pointer");
+    AVD_REQUIRE_HP("avd_learn_hp_f32", d_hp, n_groups, set_block, n_agents);
+    if (!use_lean_kernel() || AVD_DIAG_ENV("LEARN_GENERAL")) {  // (diagnostic build: the scalar entry would run another kernel)
+        set_error("avd_learn_hp_f32: the HP twins exist for learn_kernel_l only; the diagnostic LEARN_KERNEL / LEARN_GENERAL switches select another kernel");
+        return AVD_E_UNSUPPORTED;
+    }
+    return lean_launch_hp(lay, false, n_agents, set_mod, theta, stats, (float*)theta_t, (float*)stats_t, s, a, r, s2, high, grads,
+                          losses, UpdArgs{}, d_hp, n_groups, set_block, stream);
+}
+
+static int learn_update_hp_impl(const char* who, const avd_mlp_layout* lay, int n_agents, const float* theta, const float* stats,
+                                float* theta_out, float* theta_t, float* stats_t, float* m, float* v, const int32_t* step, const float* s,
+                                const float* a, const float* r, const float* s2, float high, float* grads_scratch, float* losses,
+                                const float* next_state, int x_stride, float* next_action, const avd_hparams* d_hp, int n_groups,
+                                int set_block, void* stream) {
+    int rc = check_mlp_dims(lay, who);
+    if (rc) return rc;
+    AVD_REQUIRE(n_agents > 0, "%s: n_agents=%d", who, n_agents);
+    AVD_REQUIRE(theta && stats && theta_out && theta_t && stats_t && m && v && step && s && a && r && s2 && grads_scratch,
+                "%s: null pointer", who);
+    AVD_REQUIRE(theta_out != theta, "%s: theta_out must not alias theta (every pass reads pre-update weights)", who);
+    AVD_REQUIRE_HP(who, d_hp, n_groups, set_block, n_agents);
+    if (!use_lean_kernel() || AVD_DIAG_ENV("LEARN_GENERAL")) {  // (diagnostic build: the scalar entry would run another kernel)
+        set_error("%s: the HP twins exist for learn_kernel_l only; the diagnostic LEARN_KERNEL / LEARN_GENERAL switches select another kernel", who);
+        return AVD_E_UNSUPPORTED;
+    }
+    // the step sizes and tau of UpdArgs come from the table inside the kernel
+    UpdArgs upd = {theta_out, m, v, step, 0.f, 0.f, 0.f, 0.f, next_state, x_stride, next_action};
+    return lean_launch_hp(lay, true, n_agents, 0, theta, stats, theta_t, stats_t, s, a, r, s2, high, grads_scratch, losses, upd, d_hp,
+                          n_groups, set_block, stream);
+}
+
+extern "C" int avd_learn_update_hp_f32(const avd_mlp_layout* lay, int n_agents, const float* theta, const float* stats, float* theta_out,
+                                       float* theta_t, float* stats_t, float* m, float* v, const int32_t* step, const float* s,
+                                       const float* a, const float* r, const float* s2, float high, float* grads_scratch, float* losses,
+                                       const avd_hparams* d_hp, int n_groups, int set_block, void* stream) {
+    return learn_update_hp_impl("avd_learn_update_hp_f32", lay, n_agents, theta, stats, theta_out, theta_t, stats_t, m, v, step, s, a, r,
+                                s2, high, grads_scratch, losses, nullptr, 0, nullptr, d_hp, n_groups, set_block, stream);
+}
+
+extern "C" int avd_learn_update_act_hp_f32(const avd_mlp_layout* lay, int n_agents, const float* theta, const float* stats,
+                                           float* theta_out, float* theta_t, float* stats_t, float* m, float* v, const int32_t* step,
+                                           const float* s, const float* a, const float* r, const float* s2, float high,
+                                           float* grads_scratch, float* losses, const float* next_state, int x_stride,
+                                           float* next_action, const avd_hparams* d_hp, int n_groups, int set_block, void* stream) {
+    AVD_REQUIRE(next_state && next_action && lay && x_stride >= lay->S, "avd_learn_update_act_hp_f32: next_state / x_stride");
+    return learn_update_hp_impl("avd_learn_update_act_hp_f32", lay, n_agents, theta, stats, theta_out, theta_t, stats_t, m, v, step, s,
+                                a, r, s2, high, grads_scratch, losses, next_state, x_stride, next_action, d_hp, n_groups, set_block,
+                                stream);
+}
+
 extern "C" int avd_learn_update_plan(const avd_mlp_layout* lay, int n_agents, int* chunk_agents, int* n_chunks, int* update_groups) {
     AVD_REQUIRE(lay && n_agents > 0 && chunk_agents && n_chunks && update_groups, "avd_learn_update_plan: null / n_agents=%d", n_agents);
     if (cen_supports(lay) && !AVD_DIAG_ENV("LEARN_GENERAL")) {

@@ -24,14 +24,20 @@ __device__ __forceinline__ bool slab_is_nan(const float* g, int actor_size) {
 
 // grid: (blocks over theta_size/4, n_sets). GUARD: avd_adam_polyak_guarded_f32 -- a set with a NaN gradient slab takes no step at all
 // (weights, moments, targets untouched), its Adam iteration count (already advanced by the caller) is put back and *skipped counts it.
-template <bool GUARD>
+// HP (avd_adam_polyak_hp_f32 / _guarded_hp_f32): the set's step sizes and tau / 1 - tau from the sweep table (one row per workgroup).
+template <bool GUARD, bool HP = false, class... H>
 __global__ __launch_bounds__(256) void adam_polyak_kernel(int theta_size, int actor_size, float4* __restrict__ theta,
                                                           float4* __restrict__ theta_t, float4* __restrict__ m,
                                                           float4* __restrict__ v, const float4* __restrict__ grads,
                                                           int32_t* __restrict__ step, float actor_lr,
-                                                          float critic_lr, float tau, float omt, int32_t* __restrict__ skipped) {
+                                                          float critic_lr, float tau, float omt, int32_t* __restrict__ skipped,
+                                                          H... hp) {
 #pragma clang fp contract(off)
     const int set = blockIdx.y;
+    if constexpr (HP) {
+        const avd_hparams& h = hp_of(set, hp...);
+        actor_lr = h.actor_lr, critic_lr = h.critic_lr, tau = h.tau, omt = h.one_minus_tau;
+    }
     const int t = step[set];
     if (GUARD && slab_is_nan((const float*)grads + (long)set * theta_size, actor_size)) {
         if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -269,11 +275,17 @@ __global__ void polyak_kernel(long n, const float* __restrict__ w, float* __rest
         t[i] = w[i] * tau + t[i] * omt;
 }
 // the BN statistics' soft update of the guarded form: set by set, skipping the sets adam_polyak_kernel<true> skips
+// (HP: the HP forms', guarded or not (GUARD), with the set's tau / 1 - tau from the sweep table)
+template <bool GUARD = true, bool HP = false, class... H>
 __global__ void polyak_guarded_kernel(int stats_size, const float* __restrict__ w, float* __restrict__ t, float tau, float omt,
-                                      const float* __restrict__ grads, int theta_size, int actor_size) {
+                                      const float* __restrict__ grads, int theta_size, int actor_size, H... hp) {
 #pragma clang fp contract(off)
     const int set = blockIdx.y;
-    if (slab_is_nan(grads + (long)set * theta_size, actor_size)) return;
+    if (GUARD && slab_is_nan(grads + (long)set * theta_size, actor_size)) return;
+    if constexpr (HP) {
+        const avd_hparams& h = hp_of(set, hp...);
+        tau = h.tau, omt = h.one_minus_tau;
+    }
     const long base = (long)set * stats_size;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < stats_size; i += gridDim.x * blockDim.x)
         t[base + i] = w[base + i] * tau + t[base + i] * omt;
@@ -373,7 +385,7 @@ static int adam_polyak_launch(const char* who, bool guard, const avd_mlp_layout*
     if (rc) return rc;
     // BN moving stats take part in the soft update too (ddpgagent.py:44-53 iterates .weights)
     if (guard) {
-        hipLaunchKernelGGL(polyak_guarded_kernel, dim3((unsigned)((lay->stats_size + 255) / 256), n_sets), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(polyak_guarded_kernel<>, dim3((unsigned)((lay->stats_size + 255) / 256), n_sets), dim3(256), 0, (hipStream_t)stream,
                            lay->stats_size, stats, stats_t, tauf, omt, grads, lay->theta_size, lay->actor_size);
         return check_launch(who);
     }
@@ -382,6 +394,31 @@ static int adam_polyak_launch(const char* who, bool guard, const avd_mlp_layout*
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(polyak_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ns, stats, stats_t,
                        tauf, omt);
+    return check_launch(who);
+}
+
+// The HP forms of adam_polyak_launch: the same kernels' HP twins, each set's values from row (set / set_block) % n_groups of d_hp.
+template <bool GUARD>
+static int adam_polyak_hp_launch(const char* who, const avd_mlp_layout* lay, int n_sets, float* theta, float* stats, float* theta_t,
+                                 float* stats_t, float* m, float* v, const float* grads, int32_t* step, int32_t* skipped,
+                                 const avd_hparams* d_hp, int n_groups, int set_block, void* stream) {
+    AVD_REQUIRE(lay && n_sets > 0, "%s: n_sets=%d", who, n_sets);
+    AVD_REQUIRE(theta && stats && theta_t && stats_t && m && v && grads && step, "%s: null pointer", who);
+    AVD_REQUIRE(lay->theta_size % 4 == 0 && lay->actor_size % 4 == 0 && lay->stats_size % 4 == 0, "%s: layout not 4-float aligned", who);
+    AVD_REQUIRE_HP(who, d_hp, n_groups, set_block, n_sets);
+    const HpRef hr{d_hp, n_groups, set_block};
+    const int n4 = lay->theta_size / 4;
+    int gx = (n4 + 255) / 256;
+    if (n_sets >= 256 && gx > 8) gx = 8;
+    if (const char* e = AVD_DIAG_ENV("ADAM_GX")) gx = atoi(e);
+    hipLaunchKernelGGL((adam_polyak_kernel<GUARD, true, HpRef>), dim3(gx, n_sets), dim3(256), 0, (hipStream_t)stream, lay->theta_size,
+                       lay->actor_size, (float4*)theta, (float4*)theta_t, (float4*)m, (float4*)v, (const float4*)grads, step, 0.f, 0.f,
+                       0.f, 0.f, GUARD ? skipped : (int32_t*)nullptr, hr);
+    int rc = check_launch(who);
+    if (rc) return rc;
+    // BN moving stats take part in the soft update too (ddpgagent.py:44-53), set by set with the set's tau
+    hipLaunchKernelGGL((polyak_guarded_kernel<GUARD, true, HpRef>), dim3((unsigned)((lay->stats_size + 255) / 256), n_sets), dim3(256),
+                       0, (hipStream_t)stream, lay->stats_size, stats, stats_t, 0.f, 0.f, grads, lay->theta_size, lay->actor_size, hr);
     return check_launch(who);
 }
 
@@ -465,6 +502,20 @@ extern "C" int avd_adam_polyak_f32(const avd_mlp_layout* lay, int n_sets, float*
                                    float actor_lr, float critic_lr, double tau, void* stream) {
     return adam_polyak_launch("avd_adam_polyak_f32", false, lay, n_sets, theta, stats, theta_t, stats_t, m, v, grads, (int32_t*)step, actor_lr,
                               critic_lr, tau, nullptr, stream);
+}
+
+extern "C" int avd_adam_polyak_hp_f32(const avd_mlp_layout* lay, int n_sets, float* theta, float* stats, float* theta_t, float* stats_t,
+                                      float* m, float* v, const float* grads, const int32_t* step, const avd_hparams* d_hp, int n_groups,
+                                      int set_block, void* stream) {
+    return adam_polyak_hp_launch<false>("avd_adam_polyak_hp_f32", lay, n_sets, theta, stats, theta_t, stats_t, m, v, grads, (int32_t*)step,
+                                        nullptr, d_hp, n_groups, set_block, stream);
+}
+
+extern "C" int avd_adam_polyak_guarded_hp_f32(const avd_mlp_layout* lay, int n_sets, float* theta, float* stats, float* theta_t,
+                                              float* stats_t, float* m, float* v, const float* grads, int32_t* step, int32_t* skipped,
+                                              const avd_hparams* d_hp, int n_groups, int set_block, void* stream) {
+    return adam_polyak_hp_launch<true>("avd_adam_polyak_guarded_hp_f32", lay, n_sets, theta, stats, theta_t, stats_t, m, v, grads, step,
+                                       skipped, d_hp, n_groups, set_block, stream);
 }
 
 extern "C" int avd_adam_polyak_guarded_f32(const avd_mlp_layout* lay, int n_sets, float* theta, float* stats, float* theta_t,

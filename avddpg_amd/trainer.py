@@ -84,6 +84,33 @@ def check_seed_batch(conf, rng, auto_reset, group, fused_step=None):
         raise ValueError("a seed batch needs the fused step (its draws are keyed per experiment; the separate draw kernels are not)")
 
 
+def check_sweep(conf, seeds, hparams, shared_engine=None, pipeline_chunks=1):
+    """Why a hyperparameter sweep (VecTrainer(seeds=..., hparams=...)) cannot run, raised as a ValueError -- or its full rows (one dict of
+    vec.HP_KEYS per experiment). Called before anything is allocated or launched; a sweep is a seed batch (check_seed_batch) whose
+    learners take their scalars from a per-experiment table: the exact-f32 kernels or the split-operand set learner (fused3) at the
+    reference widths."""
+    from .vec import hparams_rows
+
+    hparams = list(hparams)
+    if len(hparams) != len(seeds):
+        raise ValueError(f"hparams has {len(hparams)} rows for {len(seeds)} seeds: one dict per experiment")
+    rows = hparams_rows(conf, hparams)
+    pairs = [(int(k), tuple(r[n] for n in sorted(r))) for k, r in zip(seeds, rows)]
+    if len(set(pairs)) != len(pairs):
+        raise ValueError("a hyperparameter sweep lists the same (seed, hparams) experiment twice: the experiments would be identical")
+    if shared_engine not in (None, "per_agent", "fused3"):
+        raise ValueError(f"a hyperparameter sweep runs the per_agent and fused3 engines only; shared_engine={shared_engine!r} has no "
+                         "per-experiment table")
+    widths = (conf.actor_layer1_size, conf.actor_layer2_size, conf.critic_layer1_size, conf.critic_layer2_size,
+              conf.critic_act_layer_size, conf.batch_size)
+    if widths != (256, 128, 256, 128, 48, 64):
+        raise ValueError(f"a hyperparameter sweep runs the reference widths 256/128/48 with batch 64 only, got layers {widths[:5]} and "
+                         f"batch {widths[5]}")
+    if int(pipeline_chunks) > 1:
+        raise ValueError("a hyperparameter sweep does not run the chunked learn || update pipeline (pipeline_chunks > 1)")
+    return rows
+
+
 # The set learners' largest weight-set count (the shape checks of csrc/fset.hip and csrc/fsplit.hip); the others take any count.
 SET_ENGINE_MAX_SETS = {"fused": 64, "fused3": 64}
 
@@ -91,7 +118,7 @@ SET_ENGINE_MAX_SETS = {"fused": 64, "fused3": 64}
 class VecTrainer:
     def __init__(self, conf, device=None, rng="device", group=None, shared_sets=None, seed=None, auto_reset=False,
                  pipeline_chunks=1, fused_update=False, shared_engine=None, init_seed=None, fused_step=None,
-                 replay_ring=None, overlap_allreduce=None, seeds=None):
+                 replay_ring=None, overlap_allreduce=None, seeds=None, hparams=None):
         """group: torch.distributed process group whose ranks each hold ``conf.num_platoons`` platoons
         (interfrl gradients are all-reduced over it). auto_reset: end episodes on the device (no host
         sync per step); needs rng='device'. True: the reference's rule -- any terminal platoon (or the step limit) ends
@@ -107,22 +134,33 @@ class VecTrainer:
         wherever no set learner reduces over platoons (nofrl, interfrl per_agent). Its conf.num_platoons platoons are interleaved with
         the others': experiment e's platoon p is platoon p * E + e of the batch (self.P = E * conf.num_platoons), agent
         (e, p, m) = (p * E + e) * M + m; shared weight sets: experiment e owns sets e*M .. e*M+M-1. check_seed_batch says what a batch
-        needs (device RNG, per-platoon episodes, decentralized nofrl / interfrl with gradients, one GPU)."""
+        needs (device RNG, per-platoon episodes, decentralized nofrl / interfrl with gradients, one GPU).
+        hparams: a hyperparameter SWEEP (needs seeds): one dict per experiment, keys a subset of vec.HP_KEYS (actor_lr, critic_lr,
+        tau, gamma, std_dev, theta; a missing key takes conf's value). Experiment e is then what VecTrainer(Config(**hparams[e]),
+        seed=seeds[e], init_seed=seeds[e]) computes alone, bit for bit, wherever a seed batch is; a seed may repeat when its rows
+        differ (fused3: experiment e equals a seed batch of the same seeds whose conf holds row e's values -- its reduction tree depends on
+        the set count). check_sweep says what else a sweep needs (the per_agent or fused3 engine, the reference widths, no
+        pipeline_chunks)."""
         conf.refresh()
         self.conf, self.rng, self.group = conf, rng, group
         self.device = torch.device(device if device is not None else "cuda")
-        self.seeds = None
+        self.seeds = self.hp_rows = None
+        if hparams is not None and seeds is None:
+            raise ValueError("hparams= needs seeds= (one seed per experiment of the sweep)")
         if seeds is not None:
             if seed is not None or init_seed is not None:
                 raise ValueError("seeds= is mutually exclusive with seed= / init_seed=")
-            self.seeds = vec.seed_table(seeds, "cpu")[0]
+            self.seeds = vec.seed_table(seeds, "cpu", distinct=hparams is None)[0]
             check_seed_batch(conf, rng, auto_reset, group, fused_step)
+            if hparams is not None:
+                self.hp_rows = check_sweep(conf, self.seeds, hparams, shared_engine, pipeline_chunks)
+        distinct = self.hp_rows is None
         self.E = 1 if self.seeds is None else len(self.seeds)
         self.P, self.L = conf.num_platoons * self.E, conf.pl_size
         self.P_exp = conf.num_platoons  # platoons per experiment
         seed = (conf.random_seed if seed is None else seed) if self.seeds is None else None
         self.env = vec.VecPlatoon(self.P, self.L, conf, self.device, rand_states=conf.rand_states, rng=rng, seed=seed or 0,
-                                  seeds=self.seeds)
+                                  seeds=self.seeds, distinct_seeds=distinct)
         # models per platoon: L decentralized, 1 centralized (environment.py:35-42). The reference trainer iterates
         # conf.pl_size models (trainer.py:45) and therefore only completes a centralized step when pl_size == 1; for
         # pl_size > 1 this follows the loop shape of its evaluator (workers/evaluator.py:48-91: env.num_models).
@@ -137,7 +175,7 @@ class VecTrainer:
         self.x_stride = 4 * self.L // self.M  # floats between consecutive agents' observations in env.x
         n_agents = self.P * self.M
         self.n_agents = n_agents
-        self.ou = vec.VecOUNoise(n_agents, conf, self.device, rng=rng, seed=seed or 0, seeds=self.seeds)
+        self.ou = vec.VecOUNoise(n_agents, conf, self.device, rng=rng, seed=seed or 0, seeds=self.seeds, distinct_seeds=distinct)
         fed = is_fed_enabled(conf)
         can_share = (fed and conf.fed_method == conf.interfrl and is_gradient_updates_enabled(conf)
                      and conf.fed_update_delay_steps == 1 and conf.fed_update_count == 1
@@ -152,12 +190,17 @@ class VecTrainer:
         self.agents = vec.AgentGroup(self.Mf if self.shared else n_agents, self.S, self.A, conf, self.device,
                                      seed=None if self.seeds else (conf.random_seed if init_seed is None else init_seed),
                                      hidd_mult=self.env.hidden_multiplier, seeds=self.seeds, seed_block=self.M)
+        self.d_hp = None
+        if self.hp_rows is not None:  # the sweep's table: agent / set j of the batch is experiment (j // M) % E
+            self.d_hp = vec.hparams_table(self.hp_rows, conf.ou_dt, self.device)
+            self.agents.set_hparams(self.d_hp, self.E, self.M)
         from . import dist as _dist
         _dist.broadcast_agents(self.agents, group)
         # platoons over all ranks: a constant, reduced once here (the federated mean's divisor)
         self.total_platoons = _dist.total_platoons(self.P, group, self.device)
         self.replay = vec.VecReplay(n_agents, conf.buffer_size, conf.batch_size, self.S, self.A, self.device, rng=rng,
-                                    seed=seed or 0, ring=replay_ring, seeds=self.seeds, agents_per_platoon=self.M)
+                                    seed=seed or 0, ring=replay_ring, seeds=self.seeds, agents_per_platoon=self.M,
+                                    distinct_seeds=distinct)
         f32 = dict(dtype=torch.float32, device=self.device)
         # Shared weight sets: "per_agent" = the f32 LDS-resident kernel per agent + fed_sum (exact f32, widths up to
         # 256); "batched" = one learn over each set's P x 64 rows as bf16 MFMA GEMMs (csrc/wide.hip; any width multiple
@@ -333,6 +376,18 @@ class VecTrainer:
         env.any_done = env._any_flags[k:k + 1]  # this step's flag (cleared by the previous step's launch, zero at start)
         other = env._any_flags[1 - k:2 - k]
         env.x, env.x_prev = env.x_prev, env.x
+        if self.d_hp is not None:  # a sweep: each platoon's OU theta and scale from its experiment's row (avd_step_fused_hp_f32)
+            call("avd_step_fused_hp_f32", ptr(env.d_consts), self.P, self.L, self.S, ptr(env.x_prev), ptr(env.x), ptr(env.prev_a),
+                 ptr(env.cum_accel), ptr(env.reward), ptr(env.term), ptr(env.done), ptr(env.any_done), ptr(other), ptr(self.actor_out),
+                 ptr(ou.state), ptr(self.actions), ptr(self.leader_exog), ou.mean, conf.ou_dt, conf.action_low, conf.action_high,
+                 conf.reset_max_u, 1 if conf.rand_gen == conf.uniform else 0, ptr(env.d_seeds), ptr(self.d_hp), self.E, ou.calls,
+                 self.exog_calls, ptr(rp.ring), rp.cap, rp.buffer_counter, ptr(self.ep_reward), stream_handle())
+            ou.calls += 1
+            self.exog_calls += 1
+            env.step_count += 1
+            rp.buffer_counter += 1
+            self._added = True
+            return
         # the seed argument: the scalar seed, or (a batch) the seed table and its length (avd_step_fused_seeds_f32)
         fn, key = ("avd_step_fused_f32", (self.seed,)) if self.seeds is None else ("avd_step_fused_seeds_f32", (ptr(env.d_seeds), self.E))
         call(fn, ptr(env.d_consts), self.P, self.L, self.S, ptr(env.x_prev), ptr(env.x), ptr(env.prev_a),
@@ -687,6 +742,20 @@ class VecTrainer:
         if self.seeds is None:
             raise ValueError("experiment_agents needs a seed batch (VecTrainer(seeds=...))")
         return self.agents.experiment_view(e, self.E, self.M, self.shared)
+
+    def experiment_conf(self, e):
+        """Experiment e's Config (a seed batch or sweep): a copy of conf with its seed as random_seed and, in a sweep, its
+        hyperparameters in the reference's own fields (actor_lr, critic_lr, tau, gamma, std_dev, theta) -- what its writers record."""
+        import copy
+
+        if self.seeds is None:
+            raise ValueError("experiment_conf needs a seed batch (VecTrainer(seeds=...))")
+        c = copy.copy(self.conf)
+        c.random_seed = self.seeds[e]
+        if self.hp_rows is not None:
+            for k, v in self.hp_rows[e].items():
+                setattr(c, k, v)
+        return c
 
 
 class Trainer:

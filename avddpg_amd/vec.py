@@ -23,17 +23,75 @@ def _dev(device):
     return torch.device(device if device is not None else "cuda")
 
 
-def seed_table(seeds, device):
-    """An experiment batch's seeds -> (tuple of ints, int64 device tensor with the uint64 bit patterns the *_seeds_* kernels read)."""
+def seed_table(seeds, device, distinct=True):
+    """An experiment batch's seeds -> (tuple of ints, int64 device tensor with the uint64 bit patterns the *_seeds_* kernels read).
+    distinct=False: a seed may repeat (a hyperparameter sweep, whose experiments also differ in their hparams rows)."""
     seeds = tuple(int(k) for k in seeds)
     if not seeds:
         raise ValueError("an experiment batch needs at least one seed")
-    if len(set(seeds)) != len(seeds):
+    if distinct and len(set(seeds)) != len(seeds):
         raise ValueError(f"duplicate seeds in {list(seeds)}: the experiments would be identical")
     if any(k < 0 or k >= 2 ** 64 for k in seeds):
         raise ValueError(f"seeds must lie in [0, 2**64): {list(seeds)}")
     bits = np.array(seeds, dtype=np.uint64).view(np.int64)
     return seeds, torch.from_numpy(bits.copy()).to(device)
+
+
+# the Config fields a hyperparameter sweep may set per experiment (every one reaches the kernels as a scalar only)
+HP_KEYS = ("actor_lr", "critic_lr", "tau", "gamma", "std_dev", "theta")
+
+
+def hparams_rows(conf, hparams):
+    """One dict per experiment (keys a subset of HP_KEYS) -> the full rows, conf's value for every missing key. Raises ValueError
+    for an unknown key or a value outside what the update rules take (lr > 0, tau in (0, 1], gamma in [0, 1], std_dev, theta >= 0)."""
+    import math
+
+    rows = []
+    for e, h in enumerate(hparams):
+        if not isinstance(h, dict):
+            raise ValueError(f"hparams[{e}] must be a dict, got {type(h).__name__}")
+        bad = sorted(set(h) - set(HP_KEYS))
+        if bad:
+            raise ValueError(f"hparams[{e}]: unknown key(s) {bad}; a sweep sets {list(HP_KEYS)}")
+        row = {k: float(h[k]) if k in h else float(getattr(conf, k)) for k in HP_KEYS}
+        for k, v in row.items():
+            if not math.isfinite(v):
+                raise ValueError(f"hparams[{e}]: {k}={v} is not finite")
+        for k in ("actor_lr", "critic_lr"):
+            if row[k] <= 0:
+                raise ValueError(f"hparams[{e}]: {k}={row[k]} must be > 0")
+        if not 0 < row["tau"] <= 1:
+            raise ValueError(f"hparams[{e}]: tau={row['tau']} must lie in (0, 1]")
+        if not 0 <= row["gamma"] <= 1:
+            raise ValueError(f"hparams[{e}]: gamma={row['gamma']} must lie in [0, 1]")
+        for k in ("std_dev", "theta"):
+            if row[k] < 0:
+                raise ValueError(f"hparams[{e}]: {k}={row[k]} must be >= 0")
+        rows.append(row)
+    return rows
+
+
+def hparams_struct(row, ou_dt):
+    """One full row -> _hip.HParams with every value rounded as the scalar entry points round it: the float arguments (ctypes
+    double -> float), tau / 1 - tau of the double tau (avd_adam_polyak_f32), ou_scale = f32(std_dev) * f32(sqrt(double(f32(ou_dt))))
+    as a float product (avd_step_fused_f32 takes ou_dt as a float)."""
+    import math
+
+    f32 = np.float32
+    h = _hip.HParams()
+    h.actor_lr, h.critic_lr = f32(row["actor_lr"]), f32(row["critic_lr"])
+    h.tau, h.one_minus_tau = f32(row["tau"]), f32(1.0 - row["tau"])
+    h.gamma, h.ou_theta = f32(row["gamma"]), f32(row["theta"])
+    h.ou_scale = f32(f32(row["std_dev"]) * f32(math.sqrt(float(f32(ou_dt)))))
+    h.reserved = 0.0
+    return h
+
+
+def hparams_table(rows, ou_dt, device):
+    """Full rows -> the avd_hparams device table (uint8 tensor, 32 bytes per experiment) the *_hp_* entry points read."""
+    arr = (_hip.HParams * len(rows))(*[hparams_struct(r, ou_dt) for r in rows])
+    raw = np.frombuffer(bytes(arr), dtype=np.uint8).copy()
+    return torch.from_numpy(raw).to(device)
 
 
 def lane_of(g, E):
@@ -55,7 +113,7 @@ class VecPlatoon:
     """P platoons of L vehicles. Batched ``Platoon`` (reference src/environment.py:8-301)."""
 
     def __init__(self, num_platoons, length, config, device=None, rand_states=True, evaluator_states_enabled=False,
-                 rng="host", seed=1, track_aux=False, seeds=None):
+                 rng="host", seed=1, track_aux=False, seeds=None, distinct_seeds=True):
         """seeds: an experiment batch -- len(seeds) experiments of num_platoons / len(seeds) platoons each, interleaved (experiment e's
         platoon p is platoon p * E + e), each drawing exactly what a solo VecPlatoon with seed=seeds[e] draws (device RNG only)."""
         self.P, self.L, self.config = int(num_platoons), int(length), config
@@ -67,7 +125,7 @@ class VecPlatoon:
         if seeds is not None:
             if rng != "device":
                 raise ValueError("an experiment batch (seeds=...) needs rng='device'")
-            self.seeds, self.d_seeds = seed_table(seeds, self.device)
+            self.seeds, self.d_seeds = seed_table(seeds, self.device, distinct_seeds)
             self.n_groups = len(self.seeds)
             if self.P % self.n_groups:
                 raise ValueError(f"num_platoons={self.P} is not a multiple of the {self.n_groups} experiments")
@@ -249,12 +307,12 @@ class VecPlatoon:
 class VecOUNoise:
     """n independent scalar OU processes (reference src/noise.py)."""
 
-    def __init__(self, n, config, device=None, rng="host", seed=1, mean=0.0, seeds=None):
+    def __init__(self, n, config, device=None, rng="host", seed=1, mean=0.0, seeds=None, distinct_seeds=True):
         """seeds: an experiment batch's seed table (its draws happen inside avd_step_fused_seeds_f32, which advances ``calls``;
         calling this object then raises)."""
         self.n, self.config, self.device = int(n), config, _dev(device)
         self.rng, self.seed, self.calls = rng, int(seed), 0
-        self.seeds = None if seeds is None else seed_table(seeds, "cpu")[0]
+        self.seeds = None if seeds is None else seed_table(seeds, "cpu", distinct_seeds)[0]
         if self.seeds is not None and rng != "device":
             raise ValueError("an experiment batch (seeds=...) needs rng='device'")
         self.mean = float(mean)  # the level every process reverts to (src/noise.py:7, 17; the reference trainer passes zeros)
@@ -283,7 +341,7 @@ class VecReplay:
     """One ring buffer per agent: ring[n_agents][cap][2S+A+1] float32 (reference src/replaybuffer.py)."""
 
     def __init__(self, n_agents, buffer_capacity, batch_size, num_states, num_actions, device=None, rng="host",
-                 seed=1, ring=None, seeds=None, agents_per_platoon=1):
+                 seed=1, ring=None, seeds=None, agents_per_platoon=1, distinct_seeds=True):
         """ring: an existing [n_agents, capacity, 2S+A+1] float32 device tensor to use instead of allocating one (two trainers
         of the same shape measured in one process share the 82 GB ring of BASELINE configs[1]).
         seeds: an experiment batch (agent v = (p*E + e) * agents_per_platoon + m belongs to experiment e): sample() draws through
@@ -297,7 +355,7 @@ class VecReplay:
         if seeds is not None:
             if rng != "device":
                 raise ValueError("an experiment batch (seeds=...) needs rng='device'")
-            self.seeds, self.d_seeds = seed_table(seeds, self.device)
+            self.seeds, self.d_seeds = seed_table(seeds, self.device, distinct_seeds)
             if self.n % (len(self.seeds) * self.agents_per_platoon):
                 raise ValueError(f"n_agents={self.n} is not a multiple of {len(self.seeds)} experiments x {self.agents_per_platoon} agents")
         if ring is not None:
@@ -413,6 +471,19 @@ class AgentGroup:
                 self.stats.view(-1, E, blk, S)[:, e].copy_(torch.from_numpy(st).to(self.device).expand(n // (E * blk), blk, S))
         self.theta_t.copy_(self.theta)
         self.stats_t.copy_(self.stats)
+        # a hyperparameter sweep: (avd_hparams device table, n_groups, set_block) -- set / agent j takes row (j // set_block) % n_groups;
+        # learn / apply / learn_update then go through the *_hp_* entry points (set_hparams)
+        self.hp = None
+
+    def set_hparams(self, table, n_groups, set_block):
+        """Route learn / apply / learn_update through the *_hp_* entry points with this avd_hparams table (vec.hparams_table)."""
+        if self.n_sets % (int(n_groups) * int(set_block)):
+            raise ValueError(f"AgentGroup: {self.n_sets} sets are not a multiple of {n_groups} experiments x {set_block}")
+        self.hp = (table, int(n_groups), int(set_block))
+
+    def _no_hp(self, what):
+        if self.hp is not None:
+            raise _hip.AvdError(f"{what}: a hyperparameter sweep (set_hparams) has no per-experiment form of this path")
 
     # -- forward ----------------------------------------------------------------------------------
     def actor(self, states, set_mod, x_stride=None, out=None, target=False, run_if_nonzero=None):
@@ -458,6 +529,12 @@ class AgentGroup:
         n_agents = s.shape[0]
         if grads is None:
             grads = torch.empty(n_agents, self.lay.theta_size, dtype=torch.float32, device=self.device)
+        if self.hp is not None:  # each agent's gamma from the sweep table
+            tbl, E, blk = self.hp
+            call("avd_learn_hp_f32", self._layp, n_agents, set_mod, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
+                 ptr(self.stats_t), ptr(s), ptr(a), ptr(r), ptr(s2), self.high, ptr(grads), ptr(losses), ptr(tbl), E, blk,
+                 stream_handle())
+            return grads
         call("avd_learn_f32", self._layp, n_agents, set_mod, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
              ptr(self.stats_t), ptr(s), ptr(a), ptr(r), ptr(s2), self.config.gamma, self.high, ptr(grads),
              ptr(losses), stream_handle())
@@ -495,6 +572,8 @@ class AgentGroup:
         all-reduce between them on a side stream).
         Returns the mean gradient per set [n_sets, theta_size]."""
         import ctypes
+        if self.hp is not None and not (split and phase is None):
+            self._no_hp("learn_set_fused (bf16 operands, or a phase of the split call)")
         self._check_agent_major(s, a, r, s2, n_agents, agent_weight)
         if grads is None:
             grads = torch.empty(self.n_sets, self.lay.theta_size, dtype=torch.float32, device=self.device)
@@ -514,6 +593,12 @@ class AgentGroup:
             return grads
         if phase not in (None, "critic"):
             raise _hip.AvdError(f"phase={phase!r}")
+        if self.hp is not None:  # a sweep: each set's gamma from the table (avd_learn_set_split_hp_f16x3)
+            tbl, E, blk = self.hp
+            call("avd_learn_set_split_hp_f16x3", self._layp, n_agents, self.n_sets, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
+                 ptr(self.stats_t), ptr(s), ptr(a), ptr(r), ptr(s2), ptr(agent_weight), self.high, ptr(grads), ptr(losses), ptr(ws),
+                 ws.numel(), ptr(tbl), E, blk, stream_handle())
+            return grads
         call("avd_learn_set_split_critic" if phase == "critic" else fn, self._layp, n_agents, self.n_sets, ptr(self.theta), ptr(self.stats),
              ptr(self.theta_t), ptr(self.stats_t), ptr(s), ptr(a), ptr(r), ptr(s2), ptr(agent_weight), self.config.gamma, self.high,
              ptr(grads), ptr(losses), ptr(ws), ws.numel(), stream_handle())
@@ -562,6 +647,18 @@ class AgentGroup:
         counted in ``self.nonfinite_skipped`` (device int32; no host synchronisation) -- avd_adam_polyak_guarded_f32."""
         c = self.config
         self.step += 1
+        if self.hp is not None:  # each set's step sizes and tau from the sweep table
+            tbl, E, blk = self.hp
+            if guarded:
+                if getattr(self, "nonfinite_skipped", None) is None:
+                    self.nonfinite_skipped = torch.zeros(1, dtype=torch.int32, device=self.device)
+                call("avd_adam_polyak_guarded_hp_f32", self._layp, self.n_sets, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
+                     ptr(self.stats_t), ptr(self.m), ptr(self.v), ptr(grads), ptr(self.step), ptr(self.nonfinite_skipped), ptr(tbl), E,
+                     blk, stream_handle())
+            else:
+                call("avd_adam_polyak_hp_f32", self._layp, self.n_sets, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
+                     ptr(self.stats_t), ptr(self.m), ptr(self.v), ptr(grads), ptr(self.step), ptr(tbl), E, blk, stream_handle())
+            return
         if guarded:
             if getattr(self, "nonfinite_skipped", None) is None:
                 self.nonfinite_skipped = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -578,6 +675,7 @@ class AgentGroup:
         mean of the platoon's M gradient rows, averaged where it is consumed (avd_adam_polyak_intra_f32: one pass over the slab;
         same values as fed_mean + fed_scatter + apply). lead_skip: intra_directional_averaging -- vehicle 0 of every platoon takes
         no step at all (:417-418). weights [P, M] or None."""
+        self._no_hp("apply_intra")
         c = self.config
         hi = P if hi is None else hi
         if self.n_sets != P * M:
@@ -648,6 +746,19 @@ class AgentGroup:
             self.theta_alt = self.theta.clone()  # alignment padding stays zero in both slabs
         c = self.config
         self.step += 1
+        if self.hp is not None:  # each agent's gamma, step sizes and tau from the sweep table
+            tbl, E, blk = self.hp
+            args = (self._layp, n, ptr(self.theta), ptr(self.stats), ptr(self.theta_alt), ptr(self.theta_t), ptr(self.stats_t),
+                    ptr(self.m), ptr(self.v), ptr(self.step), ptr(s), ptr(a), ptr(r), ptr(s2), self.high, ptr(grads), ptr(losses))
+            if next_actions is not None:
+                if self.lay.A != 1:
+                    raise _hip.AvdError("next-action epilogue: A == 1 only")
+                xs = next_states.shape[-1] if x_stride is None else x_stride
+                call("avd_learn_update_act_hp_f32", *args, ptr(next_states), xs, ptr(next_actions), ptr(tbl), E, blk, stream_handle())
+            else:
+                call("avd_learn_update_hp_f32", *args, ptr(tbl), E, blk, stream_handle())
+            self.theta, self.theta_alt = self.theta_alt, self.theta
+            return
         args = (self._layp, n, ptr(self.theta), ptr(self.stats), ptr(self.theta_alt), ptr(self.theta_t), ptr(self.stats_t),
                 ptr(self.m), ptr(self.v), ptr(self.step), ptr(s), ptr(a), ptr(r), ptr(s2), c.gamma, self.high, c.actor_lr,
                 c.critic_lr, float(c.tau), ptr(grads), ptr(losses))
@@ -667,6 +778,7 @@ class AgentGroup:
         (an HBM stream) runs on a side HIP stream underneath the learn kernel of slice c+1 (matrix-core
         bound, ~1/5 of HBM bandwidth). Results are identical to learn() followed by apply().
         timers: optional dict of lists collecting (start, end) event pairs per kernel ("learn", "update")."""
+        self._no_hp("learn_apply")
         n = self.n_sets
         if s.shape[0] != n:
             raise _hip.AvdError("learn_apply needs one weight set per agent (set_mod == 0)")
@@ -718,7 +830,7 @@ class AgentGroup:
         for name, w in (("theta", T), ("stats", S), ("theta_t", T), ("stats_t", S)):
             setattr(g, name, pick(getattr(self, name), w))
         g.n_sets = g.theta.shape[0]
-        for name in ("m", "v", "step", "theta_alt"):  # optimiser state stays with the batch
+        for name in ("m", "v", "step", "theta_alt", "hp"):  # optimiser state (and a sweep's table) stays with the batch
             setattr(g, name, None)
         return g
 

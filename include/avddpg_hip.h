@@ -357,6 +357,58 @@ int avd_replay_sample_seeds_f32(int n_agents, int cap, int S, int A, int B, cons
                                 int n_groups, int agents_per_platoon, uint64_t counter, int32_t* idx, float* s, float* a, float* r,
                                 float* s2, void* stream);
 
+/* ---- hyperparameter sweeps: per-experiment scalars in one launch chain (src/config.py:97-105 per process in the reference) ----
+ * An experiment batch (above) whose experiments also differ in the scalars the kernels take: d_hp is a table of n_groups
+ * avd_hparams in device memory, one per experiment. Every derived value is formed on the host exactly as the scalar entry points
+ * form it, so experiment e's slice of every output is bit-identical to the scalar entry point called with row e's values.
+ * The learner / optimiser entries take (d_hp, n_groups, set_block): weight set or agent j belongs to experiment
+ * (j / set_block) % n_groups (per-agent sets: agent (p*E + e)*M + m; shared sets: set e*M + m; set_block = M). The count of sets
+ * or agents must be a multiple of n_groups * set_block. */
+typedef struct avd_hparams {
+    float actor_lr, critic_lr; /* Adam step sizes */
+    float tau, one_minus_tau;  /* (float)tau, (float)(1.0 - tau) of the double tau */
+    float gamma;               /* TD discount */
+    float ou_theta, ou_scale;  /* OU mean reversion; (float)std_dev * (float)sqrt((double)ou_dt) */
+    float reserved;
+} avd_hparams;
+
+/* avd_step_fused_seeds_f32 with experiment g % n_groups's ou_theta / ou_scale from d_hp (in place of ou_theta / ou_std_dev). */
+int avd_step_fused_hp_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out, float* prev_a,
+                          float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done, int32_t* any_done_other,
+                          const float* actor_out, float* ou_state, float* action, float* leader_exog, float ou_mean, float ou_dt,
+                          float action_low, float action_high, float exog_scale, int exog_uniform, const uint64_t* d_seeds,
+                          const avd_hparams* d_hp, int n_groups, uint64_t ou_counter, uint64_t exog_counter, float* ring, int cap,
+                          int64_t replay_counter, float* ep_reward, void* stream);
+/* avd_learn_f32 with each agent's gamma from d_hp. Reference widths only (256/128/48, A = 1, B = 64, S in {3, 4}). */
+int avd_learn_hp_f32(const avd_mlp_layout* lay, int n_agents, int set_mod, const float* theta, const float* stats,
+                     const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r, const float* s2,
+                     float high, float* grads, float* losses, const avd_hparams* d_hp, int n_groups, int set_block, void* stream);
+/* avd_learn_update_f32 / avd_learn_update_act_f32 with each agent's gamma, step sizes and tau from d_hp. Reference widths only. */
+int avd_learn_update_hp_f32(const avd_mlp_layout* lay, int n_agents, const float* theta, const float* stats, float* theta_out,
+                            float* theta_t, float* stats_t, float* m, float* v, const int32_t* step, const float* s, const float* a,
+                            const float* r, const float* s2, float high, float* grads_scratch, float* losses, const avd_hparams* d_hp,
+                            int n_groups, int set_block, void* stream);
+int avd_learn_update_act_hp_f32(const avd_mlp_layout* lay, int n_agents, const float* theta, const float* stats, float* theta_out,
+                                float* theta_t, float* stats_t, float* m, float* v, const int32_t* step, const float* s,
+                                const float* a, const float* r, const float* s2, float high, float* grads_scratch, float* losses,
+                                const float* next_state, int x_stride, float* next_action, const avd_hparams* d_hp, int n_groups,
+                                int set_block, void* stream);
+/* avd_adam_polyak_f32 / avd_adam_polyak_guarded_f32 with each set's step sizes and tau from d_hp (the BN statistics' soft
+ * update included). */
+int avd_adam_polyak_hp_f32(const avd_mlp_layout* lay, int n_sets, float* theta, float* stats, float* theta_t, float* stats_t,
+                           float* m, float* v, const float* grads, const int32_t* step, const avd_hparams* d_hp, int n_groups,
+                           int set_block, void* stream);
+int avd_adam_polyak_guarded_hp_f32(const avd_mlp_layout* lay, int n_sets, float* theta, float* stats, float* theta_t,
+                                   float* stats_t, float* m, float* v, const float* grads, int32_t* step, int32_t* skipped,
+                                   const avd_hparams* d_hp, int n_groups, int set_block, void* stream);
+
+/* avd_learn_set_split_f16x3 (the whole call) with each weight set's gamma from d_hp in the target critic's TD epilogue (set j: row
+ * (j / set_block) % n_groups; n_sets a multiple of n_groups x set_block). Everything else as avd_learn_set_split_f16x3. */
+int avd_learn_set_split_hp_f16x3(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
+                                 const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r, const float* s2,
+                                 const float* agent_weight, float high, float* grads, float* losses, void* workspace, size_t workspace_bytes,
+                                 const avd_hparams* d_hp, int n_groups, int set_block, void* stream);
+
 /* actor(state) for agents that SHARE n_sets weight sets (agent v uses set v % n_sets), reference widths, on the f32 matrix
  * cores (csrc/act.hip: v_mfma_f32_32x32x2_f32, exact f32 products -- agent/model.py:26-36 in the reference's arithmetic
  * class). Same values as avd_actor_forward_f32 with set_mod = n_sets up to the f32 summation order (1e-7 relative).
