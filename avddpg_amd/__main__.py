@@ -129,6 +129,16 @@ def get_cmdl_args(argv, conf):
                          "--seed). Experiment (values, k) is bit-for-bit what `tr --seed k` with those values trains alone (nofrl; "
                          "interfrl --engine per_agent; --engine fused3: what `tr --seeds` with those values trains). Writes <out>/<timestamp>/<label>/seed<k>/ per experiment and sweep.csv (not in "
                          "the reference CLI)")
+    tr.add_argument("--pbt", type=int, default=None, metavar="STEPS",
+                    help="with --sweep: population-based training -- every STEPS steps (not at the last) rank the experiments by the mean "
+                         "evaluator score of their platoons, copy the learners (weights, targets, BN statistics, Adam state) of members of "
+                         "the top fraction onto the bottom fraction and give those their parent's values times factors drawn from "
+                         "--pbt_perturb; environments, OU noise, replay and seeds stay. Writes <out>/<timestamp>/pbt.csv (not in the "
+                         "reference CLI)")
+    tr.add_argument("--pbt_fraction", type=float, default=None, help="--pbt: the share of experiments replaced per generation, in (0, 0.5] "
+                                                                        "(default 0.25)")
+    tr.add_argument("--pbt_perturb", type=str, default=None, metavar="F1,F2,...",
+                    help="--pbt: the factors a replaced experiment's swept values are multiplied by, one drawn per value (default 0.8,1.2)")
     tr.add_argument("--out", type=str, default=".outputs")
     es = sub.add_parser("esim", help="run in evaluation/simulator mode")
     es.add_argument("exp_path", type=str)
@@ -155,6 +165,22 @@ def get_cmdl_args(argv, conf):
         for name, _ in args.sweep:  # (the parsed values: argparse also takes abbreviations such as --actor)
             if getattr(args, name, None) is not None:
                 ap.error(f"--sweep {name} and --{name} are mutually exclusive")
+    if getattr(args, "pbt", None) is not None or getattr(args, "pbt_fraction", None) is not None or getattr(args, "pbt_perturb", None) is not None:
+        if args.pbt is None:
+            ap.error("--pbt_fraction / --pbt_perturb need --pbt")
+        from .pbt import check_pbt
+
+        try:
+            perturb = [float(f) for f in (args.pbt_perturb if args.pbt_perturb is not None else "0.8,1.2").split(",")]
+        except ValueError:
+            ap.error(f"--pbt_perturb: {args.pbt_perturb!r} is not a comma-separated list of numbers")
+        fraction = 0.25 if args.pbt_fraction is None else args.pbt_fraction
+        swept = [n for n, _ in args.sweep] if args.sweep is not None else None
+        n_exp = len(sweep_experiments(args.sweep, args.seeds if args.seeds is not None else [args.seed])) if swept else 0
+        try:
+            args.pbt, args.pbt_fraction, args.pbt_perturb, _ = check_pbt(args.pbt, fraction, perturb, n_exp, swept)
+        except ValueError as e:
+            ap.error(f"--pbt: {e}")
     ev = getattr(args, "eval_platoons", None)
     if ev is not None:
         if args.episodes != "platoon":
@@ -286,7 +312,7 @@ def train_sweep(args, conf, base):
     """`tr --sweep`: one VecTrainer(seeds=..., hparams=...) over the grid x seeds (sweep_experiments), experiment (label, k) written to
     <base>/<label>/seed<k>/ as `tr --seed k` with those values writes its own directory (conf.json holds the values in the reference's
     fields, the grid as `sweep`), and <base>/sweep.csv: one row per experiment with its values, seed, pl_rew_for_simulation and the
-    last curve point's evaluator score."""
+    last curve point's evaluator score. With --pbt the values are the final ones and <base>/pbt.csv holds every generation."""
     seeds = list(args.seeds) if args.seeds is not None else [int(conf.random_seed)]
     exps = sweep_experiments(args.sweep, seeds)
     rows = train_seed_batch(args, conf, base, experiments=exps)
@@ -305,9 +331,13 @@ def train_seed_batch(args, conf, base, experiments=None):
     points' evaluator scores of all experiments come from ONE evaluator rollout launch (VecTrainer.evaluator_scores).
     experiments (`tr --sweep`): [(label, hparams dict, seed)] -> <base>/<label>/seed<k>/, conf.json with the experiment's values and
     `sweep`; returns [(experiment Config, last curve point's evaluator score)]."""
+    import csv
+
     import numpy as np
 
     from . import artifacts, trainer
+    from . import pbt as _pbt
+    from .vec import HP_KEYS
 
     if experiments is None:
         seeds, hps, flag = list(args.seeds), None, "--seeds"
@@ -339,6 +369,27 @@ def train_seed_batch(args, conf, base, experiments=None):
             out.append(line)
         return out
 
+    use_pbt = experiments is not None and getattr(args, "pbt", None) is not None
+    lineage = [[] for _ in range(E)]
+    pbt_file = open(os.path.join(base, "pbt.csv"), "w", newline="") if use_pbt else None
+    if use_pbt:
+        pbt_csv = csv.writer(pbt_file)
+        pbt_csv.writerow(["generation", "step", "experiment", "label", "seed", "fitness", "rank", "parent", *HP_KEYS])
+    swept = [n for n, _ in args.sweep] if experiments is not None else []
+
+    def generation(g, step):  # score (one rollout launch), plan, exploit, set the new values; one pbt.csv row per experiment
+        fit = np.mean(vt.evaluator_scores().astype(np.float64), axis=1)
+        pairs, new_rows = _pbt.plan(fit, vt.hp_rows, swept, g, vt.seeds, args.pbt_fraction, args.pbt_perturb)
+        vt.exploit(pairs)
+        vt.set_hparams(new_rows)
+        rank = {e: r + 1 for r, e in enumerate(_pbt.ranking(fit))}
+        parent = {dst: src for src, dst in pairs}
+        for e, (label, _, k) in enumerate(experiments):
+            vals = [vt.hp_rows[e][n] for n in HP_KEYS]
+            pbt_csv.writerow([g, step, e, label, k, repr(float(fit[e])), rank[e], parent.get(e, ""), *[repr(float(x)) for x in vals]])
+            lineage[e].append(dict(generation=g, step=step, parent=parent.get(e), values=dict(zip(HP_KEYS, map(float, vals)))))
+        pbt_file.flush()
+
     files = [open(os.path.join(d, "curve.csv"), "w") for d in dirs]
     try:
         extra = "" if n_eval is None else ",evaluator_mean,evaluator_min,evaluator_max"
@@ -352,9 +403,13 @@ def train_seed_batch(args, conf, base, experiments=None):
                 for e, (f, pt) in enumerate(zip(files, points())):
                     f.write(f"{k},{int(n[e])},{float(r[e]):.5f},{float(ln[e]):.2f},{pt}\n")
                     f.flush()
+            if use_pbt and k % args.pbt == 0 and k != conf.total_time_steps:
+                generation(k // args.pbt, k)
     finally:
         for f in files:
             f.close()
+        if pbt_file is not None:
+            pbt_file.close()
     if vt.nonfinite_updates():
         print(f"warning: {vt.nonfinite_updates()} weight-set updates were skipped for non-finite gradients", file=sys.stderr)
     sims = vt.run_simulations()  # [E][P], one rollout launch
@@ -375,6 +430,9 @@ def train_seed_batch(args, conf, base, experiments=None):
         else:
             ce.seed_batch = list(dict.fromkeys(seeds))
             ce.sweep = [[n, list(v)] for n, v in args.sweep]  # the grid in flag order (a list: conf.json keeps lists, not dicts)
+            if use_pbt:  # (lists of pairs, as `sweep`: conf.json keeps lists, not dicts, at the top level)
+                ce.pbt = [["interval", args.pbt], ["fraction", args.pbt_fraction], ["perturb", list(args.pbt_perturb)],
+                          ["lineage", lineage[e]]]
         artifacts.config_writer(os.path.join(d, "conf.json"), ce)
         done.append((ce, last[e]))
     return done

@@ -83,6 +83,7 @@ _PROTOS = {
     "avd_adam_polyak_guarded_hp_f32": [_LP, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _P],
     "avd_learn_set_split_hp_f16x3": [_LP, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _P, _P, _P, C.c_size_t, _P, _i, _i, _P],
     "avd_actor_forward_set_f32": [_LP, _i, _i, _P, _P, _P, _i, _f, _P, _P, _P],
+    "avd_copy_experiment_sets_f32": [_LP, _i, _i, _i, _P, _i, _P, _P, _P, _P, _P, _P, _P, _P],
     "avd_replay_add_f32": [_i, _i, _i, _i, _P, _i64, _P, _P, _i, _P, _P, _P],
     "avd_replay_indices": [_i, _i, _i, _u64, _u64, _P, _P],
     "avd_replay_gather_f32": [_i, _i, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P],

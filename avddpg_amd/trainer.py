@@ -743,6 +743,30 @@ class VecTrainer:
             raise ValueError("experiment_agents needs a seed batch (VecTrainer(seeds=...))")
         return self.agents.experiment_view(e, self.E, self.M, self.shared)
 
+    def exploit(self, pairs):
+        """Population-based training (a seed batch): experiment dst's learner -- every weight set's online and target weights, BN
+        statistics, Adam moments and step counter -- becomes a bitwise copy of experiment src's, for every (src, dst) pair
+        (AgentGroup.copy_experiments; destinations distinct and never a source). Its environment, OU state, replay ring and seed stay its
+        own. The actor outputs a fused update left for the next step came from the old weights: the next step recomputes them on the
+        plain actor path, which is bit-identical to that prefetch for the experiments that were not replaced."""
+        if self.seeds is None:
+            raise ValueError("exploit needs a seed batch (VecTrainer(seeds=...))")
+        self.agents.copy_experiments(pairs, self.E, self.M)
+        self._act_ready = False
+
+    def set_hparams(self, hparams):
+        """A sweep's values mid-run: one dict per experiment (keys a subset of vec.HP_KEYS, a missing key takes conf's value), validated
+        by vec.hparams_rows (a repeated (seed, values) experiment is allowed here). The avd_hparams table is rewritten in place by a copy
+        on the current stream, so every later launch reads the new values; experiment_conf records them."""
+        if self.hp_rows is None:
+            raise ValueError("set_hparams needs a hyperparameter sweep (VecTrainer(seeds=..., hparams=...))")
+        hparams = list(hparams)
+        if len(hparams) != self.E:
+            raise ValueError(f"hparams has {len(hparams)} rows for {self.E} experiments: one dict per experiment")
+        rows = vec.hparams_rows(self.conf, hparams)
+        self.d_hp.copy_(vec.hparams_table(rows, self.conf.ou_dt, self.device))
+        self.hp_rows = rows
+
     def experiment_conf(self, e):
         """Experiment e's Config (a seed batch or sweep): a copy of conf with its seed as random_seed and, in a sweep, its
         hyperparameters in the reference's own fields (actor_lr, critic_lr, tau, gamma, std_dev, theta) -- what its writers record."""

@@ -481,6 +481,18 @@ class AgentGroup:
             raise ValueError(f"AgentGroup: {self.n_sets} sets are not a multiple of {n_groups} experiments x {set_block}")
         self.hp = (table, int(n_groups), int(set_block))
 
+    def copy_experiments(self, pairs, n_groups, set_block):
+        """Population-based training: for every (src, dst) experiment pair, the k-th weight set of dst becomes a bitwise copy of the k-th
+        set of src -- theta, theta_t, m, v, stats, stats_t and step; set j belongs to experiment (j // set_block) % n_groups
+        (avd_copy_experiment_sets_f32: destinations distinct and never a source, or nothing is written). One launch on the current
+        stream, no host synchronisation. theta_alt (learn_update's ping-pong slab) is rewritten whole by the next step and is not copied."""
+        flat = [int(x) for pr in pairs for x in pr]
+        if len(flat) != 2 * len(pairs):
+            raise ValueError(f"pairs must be (src, dst) experiment pairs, got {pairs!r}")
+        arr = (C.c_int32 * max(1, len(flat)))(*flat)
+        call("avd_copy_experiment_sets_f32", self._layp, self.n_sets, int(n_groups), int(set_block), arr, len(pairs), ptr(self.theta),
+             ptr(self.stats), ptr(self.theta_t), ptr(self.stats_t), ptr(self.m), ptr(self.v), ptr(self.step), stream_handle())
+
     def _no_hp(self, what):
         if self.hp is not None:
             raise _hip.AvdError(f"{what}: a hyperparameter sweep (set_hparams) has no per-experiment form of this path")

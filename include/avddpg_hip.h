@@ -409,6 +409,18 @@ int avd_learn_set_split_hp_f16x3(const avd_mlp_layout* lay, int n_agents, int n_
                                  const float* agent_weight, float high, float* grads, float* losses, void* workspace, size_t workspace_bytes,
                                  const avd_hparams* d_hp, int n_groups, int set_block, void* stream);
 
+/* ---- population-based training: move learner state from one experiment to another (csrc/pbt.hip) ----
+ * Weight set j belongs to experiment (j / set_block) % n_groups, as in the *_hp_* entry points (per-agent sets: set_block = M;
+ * shared sets: E*M sets, set_block = M). For each of the n_pairs pairs[i] = (src, dst) of experiment indices (host memory), the k-th
+ * set of dst receives the k-th set of src: its theta, theta_t, m and v rows, its stats and stats_t rows and its step counter, bit for
+ * bit; nothing else is written. Refused (AVD_E_INVALID, before any launch, every slab unchanged): n_sets not a multiple of
+ * n_groups x set_block, an index out of range, src == dst, a destination listed twice, a destination that is also a source, a null
+ * or misaligned (16 B) slab pointer, a theta_size / stats_size that is not a multiple of 4. No copy between host and device and no
+ * synchronisation: the call may be captured in a graph. */
+int avd_copy_experiment_sets_f32(const avd_mlp_layout* lay, int n_sets, int n_groups, int set_block, const int32_t* pairs, int n_pairs,
+                                 float* theta, float* stats, float* theta_t, float* stats_t, float* m, float* v, int32_t* step,
+                                 void* stream);
+
 /* actor(state) for agents that SHARE n_sets weight sets (agent v uses set v % n_sets), reference widths, on the f32 matrix
  * cores (csrc/act.hip: v_mfma_f32_32x32x2_f32, exact f32 products -- agent/model.py:26-36 in the reference's arithmetic
  * class). Same values as avd_actor_forward_f32 with set_mod = n_sets up to the f32 summation order (1e-7 relative).
