@@ -1555,6 +1555,27 @@ static int check_mlp_dims(const avd_mlp_layout* L, const char* who, bool rows_on
     return AVD_OK;
 }
 
+// Everything avd_learn_f32 / avd_learn_update_f32 refuse about a SHAPE, on the host and before any launch: the widths' domain, the
+// batch size, and the general kernel's 64-row tile against the 160 KiB of LDS (the reference and centralized shapes, which have
+// kernels of their own, lie below that bound as well: 30184 and at most 40488 of the 40960 floats).
+static int check_learn_shape(const avd_mlp_layout* L, const char* who) {
+    int rc = check_mlp_dims(L, who);
+    if (rc) return rc;
+    if (L->B != TILE) {
+        set_error("%s: batch_size=%d; the tile kernels implement B == %d", who, L->B, TILE);
+        return AVD_E_UNSUPPORTED;
+    }
+    const size_t lds = sizeof(float) * gen::lds_floats(*L);
+    if (lds > 160 * 1024) {
+        set_error("%s: S=%d A=%d H1=%d H2=%d Ha=%d need %zu B of LDS per 64-row tile (> 160 KiB)", who, L->S, L->A, L->H1, L->H2,
+                  L->Ha, lds);
+        return AVD_E_UNSUPPORTED;
+    }
+    return AVD_OK;
+}
+
+extern "C" int avd_learn_check_shape(const avd_mlp_layout* lay) { return check_learn_shape(lay, "avd_learn_f32"); }
+
 static int launch_rows(const avd_mlp_layout* lay, int mode, int n_agents, int set_mod, const float* theta,
                        const float* stats, const float* state, int x_stride, const float* action, float high,
                        float* out, void* stream, const char* who, const int32_t* run_if_nonzero = nullptr) {
@@ -1612,12 +1633,8 @@ extern "C" int avd_learn_f32(const avd_mlp_layout* lay, int n_agents, int set_mo
                              const float* stats, const float* theta_t, const float* stats_t, const float* s,
                              const float* a, const float* r, const float* s2, float gamma, float high, float* grads,
                              float* losses, void* stream) {
-    int rc = check_mlp_dims(lay, "avd_learn_f32");
+    int rc = check_learn_shape(lay, "avd_learn_f32");
     if (rc) return rc;
-    if (lay->B != TILE) {
-        set_error("avd_learn_f32: batch_size=%d; the tile kernel implements B == %d", lay->B, TILE);
-        return AVD_E_UNSUPPORTED;
-    }
     AVD_REQUIRE(n_agents > 0 && set_mod >= 0, "avd_learn_f32: n_agents=%d set_mod=%d", n_agents, set_mod);
     AVD_REQUIRE(theta && stats && theta_t && stats_t && s && a && r && s2 && grads, "avd_learn_f32: null pointer");
     // reference widths (src/config.py:112-117) take the dimension-specialised kernel; anything else the general one
@@ -1638,12 +1655,7 @@ extern "C" int avd_learn_f32(const avd_mlp_layout* lay, int n_agents, int set_mo
     // the centralized framework's shapes (S = 4 L, A = L, widths x 1.2) at L = 3 / 5: their own eight-wave kernel (cen.hip)
     if (cen_supports(lay) && !AVD_DIAG_ENV("LEARN_GENERAL"))
         return cen_launch(lay, n_agents, set_mod, theta, stats, theta_t, stats_t, s, a, r, s2, gamma, high, grads, losses, stream);
-    const size_t lds = sizeof(float) * gen::lds_floats(*lay);
-    if (lds > 160 * 1024) {
-        set_error("avd_learn_f32: S=%d A=%d H1=%d H2=%d Ha=%d need %zu B of LDS per 64-row tile (> 160 KiB)", lay->S,
-                  lay->A, lay->H1, lay->H2, lay->Ha, lds);
-        return AVD_E_UNSUPPORTED;
-    }
+    const size_t lds = sizeof(float) * gen::lds_floats(*lay);  // (<= 160 KiB: check_learn_shape)
     hipError_t e = hipFuncSetAttribute((const void*)gen::learn_kernel_g<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)lds);
     if (e != hipSuccess) {
@@ -1762,7 +1774,7 @@ static int learn_update_impl(const avd_mlp_layout* lay, int n_agents, const floa
                              const float* s, const float* a, const float* r, const float* s2, float gamma, float high,
                              float actor_lr, float critic_lr, double tau, float* grads_scratch, float* losses,
                              const float* next_state, int x_stride, float* next_action, void* stream) {
-    int rc = check_mlp_dims(lay, "avd_learn_update_f32");
+    int rc = check_learn_shape(lay, "avd_learn_update_f32");
     if (rc) return rc;
     AVD_REQUIRE(n_agents > 0, "avd_learn_update_f32: n_agents=%d", n_agents);
     AVD_REQUIRE(theta && stats && theta_out && theta_t && stats_t && m && v && step && s && a && r && s2 && grads_scratch,
@@ -1770,19 +1782,10 @@ static int learn_update_impl(const avd_mlp_layout* lay, int n_agents, const floa
     AVD_REQUIRE(theta_out != theta, "avd_learn_update_f32: theta_out must not alias theta (every pass reads pre-update weights)");
     const int a0 = lay->aW2, a1 = lay->aW2 + lay->H1 * lay->H2;  // the two W2 matrices: updated inside the learn kernels
     const int c0 = lay->actor_size + lay->cW2, c1 = c0 + (lay->H1 + lay->Ha) * lay->H2;
-    if (lay->B != TILE) {
-        set_error("avd_learn_update_f32: batch_size=%d; the tile kernels implement B == %d", lay->B, TILE);
-        return AVD_E_UNSUPPORTED;
-    }
     if (!(lay->A == 1 && lay->H1 == 256 && lay->H2 == 128 && lay->Ha == 48 && (lay->S == 3 || lay->S == 4)) ||
         AVD_DIAG_ENV("LEARN_GENERAL")) {
         // any other shape the general kernel serves (centralized framework, non-default widths): its fused form
-        const size_t lds = sizeof(float) * gen::lds_floats(*lay);
-        if (lds > 160 * 1024) {
-            set_error("avd_learn_update_f32: S=%d A=%d H1=%d H2=%d Ha=%d need %zu B of LDS per 64-row tile (> 160 KiB)", lay->S,
-                      lay->A, lay->H1, lay->H2, lay->Ha, lds);
-            return AVD_E_UNSUPPORTED;
-        }
+        const size_t lds = sizeof(float) * gen::lds_floats(*lay);  // (<= 160 KiB: check_learn_shape)
         hipError_t e = hipFuncSetAttribute((const void*)gen::learn_kernel_g<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)lds);
         if (e != hipSuccess) {

@@ -221,6 +221,10 @@ class VecTrainer:
         if self.seeds is not None and self.shared and self.Mf > SET_ENGINE_MAX_SETS.get(self.shared_engine, self.Mf):
             raise ValueError(f"a seed batch of {self.E} experiments x {self.M} weight sets needs {self.Mf} sets; shared_engine="
                              f"{self.shared_engine!r} takes at most {SET_ENGINE_MAX_SETS[self.shared_engine]}")
+        if self.shared_engine == "per_agent":
+            # avd_learn_f32 / avd_learn_update_f32 train these networks: a shape they do not serve (centralized pl_size >= 6: the
+            # 64-row tile no longer fits the LDS; H2 > 256) is refused here with their message, not at the first learn step
+            call("avd_learn_check_shape", self.agents._layp)
         self.actor_out = torch.zeros(n_agents, self.A, **f32)
         self.actions = torch.zeros(self.P, self.M, self.A, **f32)  # self.actions[p][m] (trainer.py:179)
         self.leader_exog = torch.zeros(self.P, **f32)

@@ -200,6 +200,11 @@ int avd_learn_f32(const avd_mlp_layout* lay, int n_agents, int set_mod, const fl
                   const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
                   const float* s2, float gamma, float high, float* grads, float* losses, void* stream);
 
+/* Whether avd_learn_f32 / avd_learn_update_f32 serve this shape, without launching anything: AVD_OK, or the status and
+ * avd_last_error() message those calls would give for it (widths outside the domain above, B != 64, or a 64-row tile of the
+ * general kernel that does not fit the 160 KiB of LDS). For callers that want to refuse a configuration when it is built. */
+int avd_learn_check_shape(const avd_mlp_layout* lay);
+
 /* Adam x2 (critic then actor; tf.keras.optimizers.Adam defaults, workers/trainer.py:138-139, 348-349)
  * followed by ddpgagent.update_target over ALL weights incl. BN stats (agent/ddpgagent.py:31-55;
  * workers/trainer.py:352-356), fused per element, for n_sets weight sets.

@@ -77,6 +77,21 @@ def test_error_reporting_without_gpu():
         _hip.call("avd_learn_f32", ctypes.byref(lay), 1, 0, *([None] * 8), 0.99, 2.5, None, None, None)
 
 
+def test_learn_shape_check_draws_the_lds_boundary_without_a_launch():
+    """avd_learn_check_shape: what avd_learn_f32 / avd_learn_update_f32 would say about a shape, on the host. At 320/160/64 the general
+    kernel's tile takes 36968 + 64 S + 448 A floats of the 40960: centralized pl_size 5 fits with 472 to spare, pl_size 6 does not."""
+    ok = [(4, 1, 256, 128, 48), (3, 1, 256, 128, 48), (20, 5, 320, 160, 64), (64, 16, 128, 64, 32), (21, 3, 128, 256, 32), (1, 1, 16, 32, 16)]
+    for dims in ok:
+        lay = _hip.make_layout(*dims, 64)
+        _hip.call("avd_learn_check_shape", ctypes.byref(lay))
+    for dims, B, msg in (((24, 6, 320, 160, 64), 64, r"need 164768 B of LDS per 64-row tile \(> 160 KiB\)"),
+                         ((4, 1, 256, 288, 48), 64, "H2 a multiple of 32 and <= 256"), ((65, 1, 256, 128, 48), 64, "S <= 64"),
+                         ((4, 17, 256, 128, 48), 64, "A <= 16"), ((4, 1, 256, 128, 48), 32, "B == 64")):
+        lay = _hip.make_layout(*dims, B)
+        with pytest.raises(_hip.AvdError, match=msg):
+            _hip.call("avd_learn_check_shape", ctypes.byref(lay))
+
+
 def test_layout_matches_reference_parameter_counts():
     lay = _hip.make_layout(4, 1, 256, 128, 48, 64)
     # SURVEY a-9/a-10: 35 073 actor + 41 409 critic trainables, 768 + 864 moving stats

@@ -46,10 +46,10 @@ def _batch(seed, B=64, S=4, A=1):
     return rs.normal(size=(B, S)), rs.uniform(-2.5, 2.5, (B, A)), rs.normal(size=(B, 1)), rs.normal(size=(B, S))
 
 
-@pytest.mark.parametrize("seed", [0, 1])
-def test_learn_matches_torch_autograd_f64(seed):
-    actor, critic, t_actor, t_critic = _rand_nets(seed)
-    s, a, r, s2 = _batch(seed)
+def _check_learn_against_torch_autograd(seed, **shape):
+    """r is [B, 1] and broadcasts over the critic's A outputs in the TD target; both losses are torch.mean over B x A."""
+    actor, critic, t_actor, t_critic = _rand_nets(seed, **shape)
+    s, a, r, s2 = _batch(seed, S=shape.get("S", 4), A=shape.get("A", 1))
     cg, ag, aux = mlp.learn((s, a, r, s2), actor, critic, t_actor, t_critic, 0.99, 2.5)
     def T(ws, trainable):
         return [torch.tensor(x, dtype=torch.float64, requires_grad=(i in trainable)) for i, x in enumerate(ws)]
@@ -66,12 +66,47 @@ def test_learn_matches_torch_autograd_f64(seed):
         assert np.allclose(mine, ref.numpy(), rtol=1e-9, atol=1e-13)
     for mine, ref in zip(ag, ga):
         assert np.allclose(mine, ref.numpy(), rtol=1e-9, atol=1e-13)
+    return cg, ag, gc, ga
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+def test_learn_matches_torch_autograd_f64(seed):
+    _check_learn_against_torch_autograd(seed)
+
+
+# the shapes at which the GPU tests lean on the oracle (tests/test_gpu_mlp.py, tests/test_gpu_general_shapes.py): the centralized
+# framework's multi-action rules, both documented maxima, every minimum, ragged S / A, H2 at its maximum, A > S
+ORACLE_SHAPES = [(20, 5, 307, 153, 57), (64, 16, 320, 160, 64), (1, 1, 16, 32, 16), (7, 2, 48, 32, 16), (21, 3, 128, 256, 32),
+                 (40, 10, 307, 153, 57), (5, 16, 16, 32, 16)]
+
+
+@pytest.mark.parametrize("S,A,H1,H2,Ha", ORACLE_SHAPES)
+def test_learn_matches_torch_autograd_f64_at_the_gpu_tests_shapes(S, A, H1, H2, Ha):
+    """The assertions of test_learn_matches_torch_autograd_f64 at multi-action and padded-width shapes, every gradient tensor
+    non-trivial (a comparison of zeros would pin nothing), and the float32 oracle -- the GPU tests' yardstick for their
+    "4 x the float32 oracle's own error" escape -- within 2e-5 of the float64 one, as test_f32_learn_close_to_f64 asks."""
+    cg, ag, gc, ga = _check_learn_against_torch_autograd(11, S=S, A=A, H1=H1, H2=H2, Ha=Ha)
+    assert [tuple(x.shape) for x in cg + ag] == [tuple(x.shape) for x in list(gc) + list(ga)]
+    assert cg[12].shape == (H2, A) and cg[2].shape == (A, Ha) and ag[8].shape == (H2, A)
+    for x in cg + ag:
+        assert np.max(np.abs(x)) > 1e-8
+    n64 = _rand_nets(11, S=S, A=A, H1=H1, H2=H2, Ha=Ha)
+    b = _batch(11, S=S, A=A)
+    c32, a32, _ = mlp.learn(b, *[[x.astype(np.float32) for x in net] for net in n64])
+    for x, y in zip(cg + ag, c32 + a32):
+        assert y.dtype == np.float32 and np.max(np.abs(x - y)) <= 2e-5 * max(1e-3, np.max(np.abs(x)))
 
 
 def test_learn_finite_differences():
-    actor, critic, t_actor, t_critic = _rand_nets(3, H1=8, H2=8, Ha=8)
-    batch = _batch(3, B=16)
+    for A in (1, 3):  # A = 3: r broadcast over the three critic outputs, both losses averaged over B x A
+        _check_finite_differences(A)
+
+
+def _check_finite_differences(A):
+    actor, critic, t_actor, t_critic = _rand_nets(3, A=A, H1=8, H2=8, Ha=8)
+    batch = _batch(3, B=16, A=A)
     cg, ag, aux = mlp.learn(batch, actor, critic, t_actor, t_critic)
+    assert aux["q"].shape == (16, A) and aux["y"].shape == (16, A)
     rs = np.random.RandomState(0)
     for which, net, grads, tr_idx, key in (("c", critic, cg, mlp.CRITIC_TRAINABLE, "critic_loss"),
                                            ("a", actor, ag, mlp.ACTOR_TRAINABLE, "actor_loss")):
@@ -86,7 +121,7 @@ def test_learn_finite_differences():
             lm = mlp.learn(batch, actor, critic, t_actor, t_critic)[2][key]
             flat[j] = old
             fd = (lp - lm) / (2 * h)
-            assert abs(fd - grads[gi].reshape(-1)[j]) < 1e-6 * max(1.0, abs(fd)), (which, gi)
+            assert abs(fd - grads[gi].reshape(-1)[j]) < 1e-6 * max(1.0, abs(fd)), (A, which, gi)
 
 
 def test_f32_learn_close_to_f64():
