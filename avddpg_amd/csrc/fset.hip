@@ -797,9 +797,7 @@ __global__ __launch_bounds__(NT) void dxa_kernel(const DxArgs p) {
 // ---- finalize: sum the workgroups' partials of a set (fixed order), apply the BN folds, write the gradient slab -------
 // One item per 32 lanes: output column n (items 0..127: output layer, BN2, b2) or first-layer feature f (items 128..):
 // lane jl sums the partials of workgroups jl, jl + 32, .. of the set, then a fixed shuffle tree combines the 32 lanes.
-__global__ __launch_bounds__(512) void finalize_small_kernel(const FinArgs a) {
-    const int set = blockIdx.x, net = a.net_lo + blockIdx.y, tid = threadIdx.x, jl = tid & 31;
-    const int item = a.item_base + blockIdx.z * 16 + (tid >> 5);
+__device__ __forceinline__ void finalize_small_item(const FinArgs& a, int set, int net, int item, int jl) {
     const bool critic = net;
     const avd_mlp_layout& L = a.L;
     const float* th = a.theta + (long)set * L.theta_size + (critic ? L.actor_size : 0);
@@ -897,9 +895,11 @@ __global__ __launch_bounds__(512) void finalize_small_kernel(const FinArgs a) {
         for (int k = 0; k < sin; ++k) g[oW + k * ld + ff] = inv1 * (V[k] + V[4 + k]);
     }
 }
+__global__ __launch_bounds__(512) void finalize_small_kernel(const FinArgs a) {
+    finalize_small_item(a, blockIdx.x, a.net_lo + blockIdx.y, a.item_base + blockIdx.z * 16 + (threadIdx.x >> 5), threadIdx.x & 31);
+}
 // W2 gradients: dW2[f][n] = inv1[f] * G[f][n] + sh1[f] * db2[n] (db2 read back from the slab finalize_small wrote)
-__global__ __launch_bounds__(128) void finalize_w2_kernel(const FinArgs a) {
-    const int f = blockIdx.x, set = blockIdx.y, net = a.net_lo + blockIdx.z, n = threadIdx.x;
+__device__ __forceinline__ void finalize_w2_row(const FinArgs& a, int f, int set, int net, int n) {
     const bool critic = net;
     const int K = critic ? Critic::K : Actor::K, KG = critic ? Critic::KG : Actor::KG;
     if (f >= K) return;
@@ -931,6 +931,18 @@ __global__ __launch_bounds__(128) void finalize_w2_kernel(const FinArgs a) {
     if (a.c3[net]) G *= a.c3[net][(long)set * VEC + H2 + n];
     if (a.bad && *a.bad) G = __uint_as_float(0x7fc00000u);
     g[oW2 + (long)f * H2 + n] = inv1 * G + sh1 * g[ob2 + n];
+}
+__global__ __launch_bounds__(128) void finalize_w2_kernel(const FinArgs a) {
+    finalize_w2_row(a, blockIdx.x, blockIdx.y, a.net_lo + blockIdx.z, threadIdx.x);
+}
+// The W2 rows and the feature items of finalize_small in ONE launch (r09; fsplit.hip's chain, where the feature items need the db2
+// of the column items): both read the db2 that the column items' launch wrote and nothing of each other -- the feature items write
+// the first-layer tensors, the W2 rows dW2 and t1p. Blocks [0, n_w2) of x: four W2 rows each; the rest: sixteen feature items each;
+// a block is one role throughout (no barrier in either; the feature items' shuffles stay inside 32 lanes).
+__global__ __launch_bounds__(512) void finalize_w2_feat_kernel(const FinArgs a, int n_w2) {
+    const int set = blockIdx.y, net = a.net_lo + blockIdx.z, tid = threadIdx.x;
+    if ((int)blockIdx.x < n_w2) finalize_w2_row(a, 4 * blockIdx.x + (tid >> 7), set, net, tid & 127);
+    else finalize_small_item(a, set, net, H2 + ((int)blockIdx.x - n_w2) * 16 + (tid >> 5), tid & 31);
 }
 // T1-dependent outputs of a net whose T1 comes from the weight-gradient partials (FinArgs::t1_from_g): one block per set, one
 // thread per output column, the K products in index order with eight loads in flight
@@ -973,12 +985,14 @@ void launch_finalize(const FinArgs& fa0, hipStream_t st, int net_lo, int n_nets)
     const int K = (net_lo + n_nets > 1) ? Critic::K : Actor::K;
     if (fa.partU[net_lo]) {
         hipLaunchKernelGGL(finalize_small_kernel, dim3(fa.n_sets, n_nets, (H2 + K + 15) / 16), dim3(512), 0, st, fa);
-    } else {  // the feature items read the db2 the column items write: two launches
+        hipLaunchKernelGGL(finalize_w2_kernel, dim3(K, fa.n_sets, n_nets), dim3(H2), 0, st, fa);
+    } else {
+        // the feature items AND the W2 rows read the db2 the column items write (finalize_w2_row: sh1 * g[ob2 + n]): the column
+        // items are a launch of their own, the two readers share the next one -- three launches where r08 had four
         hipLaunchKernelGGL(finalize_small_kernel, dim3(fa.n_sets, n_nets, H2 / 16), dim3(512), 0, st, fa);
-        fa.item_base = H2;
-        hipLaunchKernelGGL(finalize_small_kernel, dim3(fa.n_sets, n_nets, (K + 15) / 16), dim3(512), 0, st, fa);
+        const int n_w2 = (K + 3) / 4;
+        hipLaunchKernelGGL(finalize_w2_feat_kernel, dim3(n_w2 + (K + 15) / 16, fa.n_sets, n_nets), dim3(512), 0, st, fa, n_w2);
     }
-    hipLaunchKernelGGL(finalize_w2_kernel, dim3(K, fa.n_sets, n_nets), dim3(H2), 0, st, fa);
     bool any = false;
     for (int net = net_lo; net < net_lo + n_nets; ++net) any = any || fa.t1_from_g[net];
     if (any) hipLaunchKernelGGL(finalize_t1_kernel, dim3(fa.n_sets, n_nets), dim3(H2), 0, st, fa);

@@ -66,7 +66,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 // their lo parts stay normal numbers). An activation S1 P1 >= 65520 (P1 >= 1023.75) would round to fp16 inf -- and, the file being
 // built with -fno-honor-nans (relu = one v_max_f32, which returns its non-NaN operand), the resulting NaN accumulators would
 // silently become zeros. Every conversion to fp16 that can overflow is therefore TESTED: the scaled static operands in the prep
-// kernels, the inputs in pack_x_kernel, and the running maximum of every first-layer accumulator tile in the forward heads
+// kernels, the inputs in the pack role of front_kernel, and the running maximum of every first-layer accumulator tile in the forward heads
 // (8 v_max3_f32 per tile); a hit sets *bad and finalize writes NaN into the whole gradient slab, like a non-finite input.
 typedef _Float16 f16;
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
@@ -192,26 +192,32 @@ struct PackArgs {
     const float* extra[2];
     f16x8* outh[2];
     long rows;
-    int* bad;
 };
+// A role of front_kernel (below): block bx of input `which`. Nothing in that launch may set *bad -- one of its blocks clears it with
+// a plain store -- so a hit is reported through the wave's own word of the front flags (front_flag), which prep_kernel ORs into *bad.
+__device__ __forceinline__ void front_flag(unsigned* wave_flags, bool hit) {
+    const bool any = __ballot(hit) != 0;
+    if ((threadIdx.x & 63) == 0) wave_flags[threadIdx.x >> 6] = any;  // written by every wave, hit or not: no stale word survives a call
+}
 template <int S>
-__global__ __launch_bounds__(256) void pack_x_kernel(const PackArgs a) {
-    const int which = blockIdx.y;
+__device__ __forceinline__ void pack_x_role(const PackArgs& a, int which, long bx, unsigned* wave_flags) {
     const float* x = a.x[which];
     const float* extra = a.extra[which];
     const bool extra_is_action = which == 0;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= 2 * a.rows) return;
-    float v[4];
-    load_x<S>(x, i >> 1, v);
-    bool nf = not_finite(v[0]) || not_finite(v[1]) || not_finite(v[2]) || not_finite(v[3]);
-    nf = nf || fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))) >= F16_OVERFLOW;  // (fp16 input fragments)
-    if (!(i & 1)) {
-        const float e = extra[i >> 1];  // a (an fp16 input fragment of the critic too) or r
-        nf = nf || not_finite(e) || (extra_is_action && fabsf(e) >= F16_OVERFLOW);
+    const long i = bx * 256 + threadIdx.x;
+    bool nf = false;
+    if (i < 2 * a.rows) {
+        float v[4];
+        load_x<S>(x, i >> 1, v);
+        nf = not_finite(v[0]) || not_finite(v[1]) || not_finite(v[2]) || not_finite(v[3]);
+        nf = nf || fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))) >= F16_OVERFLOW;  // (fp16 input fragments)
+        if (!(i & 1)) {
+            const float e = extra[i >> 1];  // a (an fp16 input fragment of the critic too) or r
+            nf = nf || not_finite(e) || (extra_is_action && fabsf(e) >= F16_OVERFLOW);
+        }
+        a.outh[which][i] = make_xh(v[0], v[1], v[2], v[3], (int)(i & 1));
     }
-    if (nf) atomicOr(a.bad, 1);
-    a.outh[which][i] = make_xh(v[0], v[1], v[2], v[3], (int)(i & 1));
+    front_flag(wave_flags, nf);
 }
 
 // ---- operand preparation ---------------------------------------------------------------------------------------------
@@ -224,14 +230,17 @@ struct PrepArgs {
     f16x8* wf1h[4];
     float* vec[4];
     unsigned* wap;
-    unsigned* smax;  // [4 nets][sets][2] maxima of scale_kernel (zeroed with *bad)
-    int* bad;
+    unsigned* smax;  // [4 nets][sets][SCALE_SLICES][2] maxima of the scale role, one pair per slice block (plain stores)
+    int* bad;        // cleared by the front launch, set from prep_kernel on
+    unsigned* fflag; // [n_fflag] front flags: one word per wave of the prep1 and pack roles, non-zero = what used to set *bad there
+    int n_fflag;
 };
 // SW per (net, set): the power of two that puts max |inv1[f] W2[f][n]| into [2^12, 2^13) -> vec[2 H2 + 1]; online nets also
-// SWC, the same for dx_kernel's operand c3[n] W2[f][n] -> vec[2 H2 + 2]. Two steps: scale_kernel leaves the two maxima per (net,
-// set) in smax (atomicMax on the bits of non-negative floats: order-independent, so deterministic; 16 blocks per matrix, coalesced
-// -- r03's one block per matrix walked 304 rows of 512 bytes with one thread each: 11 us, 33 with the second maximum), every
-// thread of prep_kernel turns them into the powers of two, block n = 0 writes them for the later kernels.
+// SWC, the same for dx_kernel's operand c3[n] W2[f][n] -> vec[2 H2 + 2]. Two steps: the scale role of front_kernel leaves the two
+// maxima of each of 16 slices per (net, set) in smax (16 blocks per matrix, coalesced -- r03's one block per matrix walked 304 rows
+// of 512 bytes with one thread each: 11 us, 33 with the second maximum; plain stores, r09: until then atomicMax into words that a
+// memset had to zero first), every thread of prep_kernel takes the maximum of the 16 (on the bits of non-negative floats: order-
+// independent, so deterministic) and turns it into the powers of two, block n = 0 writes them for the later kernels.
 constexpr int SCALE_SLICES = 16;
 __device__ __forceinline__ float pow2_for(float mx) {  // the power of two that puts mx into [2^12, 2^13)
     int e = 0;
@@ -240,9 +249,9 @@ __device__ __forceinline__ float pow2_for(float mx) {  // the power of two that 
     k = k < -14 ? -14 : (k > 30 ? 30 : k);
     return ldexpf(1.f, k);
 }
-__global__ __launch_bounds__(256) void scale_kernel(const PrepArgs a) {
+__device__ __forceinline__ void scale_role(const PrepArgs& a, int net, int set, int slice, int n_sets) {
     __shared__ float red[256], red2[256], c3a[H2], inva[CriticS::K];
-    const int net = blockIdx.x, set = blockIdx.y, slice = blockIdx.z, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     const bool critic = net & 1, target = net >= 2;
     const avd_mlp_layout& L = a.L;
     const float* th = (target ? a.theta_t : a.theta) + (long)set * L.theta_size + (critic ? L.actor_size : 0);
@@ -272,9 +281,9 @@ __global__ __launch_bounds__(256) void scale_kernel(const PrepArgs a) {
         __syncthreads();
     }
     if (tid == 0) {
-        unsigned* dst = a.smax + ((long)net * gridDim.y + set) * 2;
-        atomicMax(dst, __float_as_uint(red[0]));  // (non-negative floats order like their bits; a NaN / inf input lands on top and is
-        atomicMax(dst + 1, __float_as_uint(red2[0]));  //  caught by the finiteness tests of prep_kernel)
+        unsigned* dst = a.smax + (((long)net * n_sets + set) * SCALE_SLICES + slice) * 2;
+        dst[0] = __float_as_uint(red[0]);  // (non-negative floats order like their bits; a NaN / inf input lands on top and is
+        dst[1] = __float_as_uint(red2[0]);  //  caught by the finiteness tests of prep_kernel)
     }
 }
 // one block per (output column n, net, set), one thread per feature f
@@ -289,8 +298,16 @@ __global__ __launch_bounds__(320) void prep_kernel(const PrepArgs a) {
     const int oW2 = critic ? L.cW2 : L.aW2, ob2 = critic ? L.cb2 : L.ab2, oW3 = critic ? L.cW3 : L.aW3, ob3 = critic ? L.cb3 : L.ab3;
     const int og2 = critic ? L.cg3 : L.ag2, obe2 = critic ? L.cbe3 : L.abe2, omm2 = critic ? L.cmm3 : L.amm2, omv2 = critic ? L.cmv3 : L.amv2;
     const float inv2n = (1.0f / sqrtf(st[omv2 + n] + BN_EPS)) * th[og2 + n], c3n = inv2n * th[oW3 + n];
-    const unsigned* smax = a.smax + ((long)net * gridDim.z + set) * 2;
-    const float SW = pow2_for(__uint_as_float(smax[0])), SWC = pow2_for(__uint_as_float(smax[1]));
+    const unsigned* smax = a.smax + ((long)net * gridDim.z + set) * SCALE_SLICES * 2;
+    unsigned mx = 0, mxc = 0;
+#pragma unroll
+    for (int sl = 0; sl < SCALE_SLICES; ++sl) mx = max(mx, smax[2 * sl]), mxc = max(mxc, smax[2 * sl + 1]);
+    const float SW = pow2_for(__uint_as_float(mx)), SWC = pow2_for(__uint_as_float(mxc));
+    // what the prep1 and pack roles of the front launch found (they cannot set *bad themselves: that launch clears it): the blocks of
+    // net 0, set 0 share the words between them
+    if (net == 0 && set == 0)
+        for (int w = n * 320 + f; w < a.n_fflag; w += H2 * 320)
+            if (a.fflag[w]) atomicOr(a.bad, 1);
     float shw = 0.f;
     if (f < KP) {
         float w = 0.f, inv = 0.f;
@@ -353,10 +370,12 @@ __global__ __launch_bounds__(320) void prep_kernel(const PrepArgs a) {
         if (f == 0) vec[2 * H2] = th[ob3] + red[0];
     }
 }
-// first-layer weight fragments: one block per (feature tile, net, set), one thread per lane of the fragment; tiles >= 8 of a
-// critic are its action layer; feature K of every net is the constant one relu(0 x + 1) (dw_kernel: its row of G is db2)
-__global__ __launch_bounds__(64) void prep1_kernel(const PrepArgs a) {
-    const int ft = blockIdx.x, net = blockIdx.y, set = blockIdx.z, lane = threadIdx.x, r = lane & 31, h = lane >> 5;
+// first-layer weight fragments: one wave per (feature tile, net, set), one thread per lane of the fragment; tiles >= 8 of a
+// critic are its action layer; feature K of every net is the constant one relu(0 x + 1) (dw_kernel: its row of G is db2).
+// A role of front_kernel, four to a block; returns whether an operand was non-finite or would overflow fp16 (-> the wave's front flag).
+__device__ __forceinline__ bool prep1_role(const PrepArgs& a, int ft, int net, int set, int lane) {
+    const int r = lane & 31, h = lane >> 5;
+    bool hit = false;
     const bool critic = net & 1, target = net >= 2;
     const avd_mlp_layout& L = a.L;
     const float* th = (target ? a.theta_t : a.theta) + (long)set * L.theta_size + (critic ? L.actor_size : 0);
@@ -374,9 +393,9 @@ __global__ __launch_bounds__(64) void prep1_kernel(const PrepArgs a) {
             for (int k = 0; k < 4; ++k) w[k] = k < a.S ? W[k * H1 + f] : 0.f;
             b = th[(critic ? L.cbs : L.ab1) + f];
         }
-        if (not_finite(w[0]) || not_finite(w[1]) || not_finite(w[2]) || not_finite(w[3]) || not_finite(b)) atomicOr(a.bad, 1);
+        if (not_finite(w[0]) || not_finite(w[1]) || not_finite(w[2]) || not_finite(w[3]) || not_finite(b)) hit = true;
         // the heads' and dx's fragments carry S1 w, S1 b as fp16 pairs
-        if (S1 * fmaxf(fmaxf(fabsf(w[0]), fabsf(w[1])), fmaxf(fmaxf(fabsf(w[2]), fabsf(w[3])), fabsf(b))) >= F16_OVERFLOW) atomicOr(a.bad, 1);
+        if (S1 * fmaxf(fmaxf(fabsf(w[0]), fabsf(w[1])), fmaxf(fmaxf(fabsf(w[2]), fabsf(w[3])), fabsf(b))) >= F16_OVERFLOW) hit = true;
     }
     a.wf1h[net][((long)set * NGT_MAX + ft) * 64 + lane] = make_wh(w[0], w[1], w[2], w[3], b, S1, h);
     if (net == 1 && ft == 0 && lane < 48) {
@@ -393,6 +412,59 @@ __global__ __launch_bounds__(64) void prep1_kernel(const PrepArgs a) {
         }
         a.wap[(long)set * 48 + lane] = v;
     }
+    return hit;
+}
+
+// ---- the front launch (r09): everything of a learn call that depends on nothing but the call's inputs, in ONE launch ---------------
+// scale, prep1 and pack_x have no dependence on one another, and the two memsets in front of them (the gradient slab; *bad and the
+// maxima) were stream operations of their own: five dependent-looking operations, none of which fills the GPU for its whole
+// duration. The block index selects the role; a block is one role from its first instruction to its last (the scale role's
+// barriers are met by whole blocks). Workgroups are dispatched in index order, so the latency-bound roles come FIRST -- scale's
+// 64 blocks per set walk a dependent chain of reductions, ~10 us however empty the GPU is -- and the streaming role (pack: 2 x
+// ceil(rows / 128) blocks) fills every slot they leave and runs beside them; the other way round the small blocks would only start
+// when the last pack blocks retire, and their latency would be a tail.
+//   [0, n_scale)               scale: block -> (net, set, slice); two maxima per slice, plain stores (no zeroed word needed)
+//   [.., + n_prep1)            prep1: wave -> (feature tile, net, set)
+//   [.., + n_zero)             the gradient slab, 4096 floats per block: finalize never writes the padding between its tensors, and
+//                              nothing reads or writes the slab between here and finalize; the first of them also clears *bad --
+//                              safe because no role of this launch sets it (front flags: front_flag, prep_kernel)
+//   [.., + 2 n_pack)           pack_x: (s, a) then (s2, r)
+// prep_kernel needs the maxima and follows as the second launch.
+struct FrontArgs {
+    PrepArgs pa;
+    PackArgs pk;
+    float* grads;
+    long n_grads;  // floats of the slab
+    int n_sets, n_scale, n_prep1, n_zero, n_pack;
+};
+constexpr int ZERO_PER_BLOCK = 4096;
+template <int S>
+__global__ __launch_bounds__(256) void front_kernel(const FrontArgs a) {
+    int b = blockIdx.x;
+    if (b < a.n_scale) {
+        scale_role(a.pa, b & 3, (b >> 2) % a.n_sets, (b >> 2) / a.n_sets, a.n_sets);
+        return;
+    }
+    b -= a.n_scale;
+    if (b < a.n_prep1) {
+        const int q = 4 * b + (threadIdx.x >> 6);  // (feature tile, net, set), feature tile fastest
+        bool hit = false;
+        if (q < NGT_MAX * 4 * a.n_sets) hit = prep1_role(a.pa, q % NGT_MAX, (q / NGT_MAX) & 3, q / (NGT_MAX * 4), threadIdx.x & 63);
+        front_flag(a.pa.fflag + 4 * (long)b, hit);
+        return;
+    }
+    b -= a.n_prep1;
+    if (b < a.n_zero) {
+        if (b == 0 && threadIdx.x == 0) *a.pa.bad = 0;
+        const long base = (long)b * ZERO_PER_BLOCK + threadIdx.x;
+#pragma unroll
+        for (int k = 0; k < ZERO_PER_BLOCK / 256; ++k)
+            if (base + 256 * k < a.n_grads) a.grads[base + 256 * k] = 0.f;
+        return;
+    }
+    b -= a.n_zero;
+    const int which = b >= a.n_pack;
+    pack_x_role<S>(a.pk, which, b - which * a.n_pack, a.pa.fflag + 4 * ((long)a.n_prep1 + b));
 }
 
 // ---- head: first layer -> second-layer GEMM (three MFMAs per product) -> output layer [-> its backward] -------------------
@@ -402,7 +474,7 @@ struct HeadArgs {
     unsigned long long* stamp;  // diagnostic build (-DAVD_STAMP) only: [8 waves][8] accumulated s_memtime deltas of workgroup 16
     NetP net;
     int n_agents, n_sets;
-    const f16x8* xf;   // [n_agents][64][2] packed first-layer input fragments of the states, fp16 pairs (pack_x_kernel)
+    const f16x8* xf;   // [n_agents][64][2] packed first-layer input fragments of the states, fp16 pairs (front_kernel: pack_x_role)
     const float* act;  // [n_agents][64] the critic's action input (a, a' or mu)
     const float* act2; // HEAD_BOTH: mu (act = a)
     const float* r;    // OUT_TD: rewards [n_agents][64]
@@ -1147,7 +1219,7 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
 struct DxArgs {
     NetP net;
     int n_agents, n_sets;
-    const f16x8* xfh;  // packed state fragments, fp16 pairs (pack_x_kernel): the rows' first-layer input AND (lane half 0: [x_hi | x_lo])
+    const f16x8* xfh;  // packed state fragments, fp16 pairs (front_kernel: pack_x_role): the rows' first-layer input AND (lane half 0: [x_hi | x_lo])
                        // the [k][row] image of V's B operand. The first layer's SIGN is the relu mask: as bf16 pairs (2^-16) about
                        // 1e-5 of the pre-activations landed on the wrong side of zero, and one flipped row moves an entry of dW1 / db1
                        // by ~1e-3 of the tensor's max (r03, measured); fp16 pairs put z1 at the f32 level
@@ -1519,7 +1591,8 @@ __global__ __launch_bounds__(NT) void dxa_kernel(const DxArgs p) {
 struct Plan {
     int grid, J;
     size_t Whi[4], Wlo[4], Wchi[2], Wclo[2], wf1h[4], vec[4], wap, a2, y, mu, dmu, g3, sm, sma, tz, t1p, s2raw, xfs, xfs2, partHs[3], partM[2],
-        partV[2], partG[2], bad, total;
+        partV[2], partG[2], bad, smax, fflag, total;
+    int n_prep1, n_pack, n_fflag;  // front_kernel: blocks of the prep1 role, of the pack role per input; front flag words
 };
 static Plan make_plan(int n_agents, int n_sets) {
     Plan pl;
@@ -1557,7 +1630,12 @@ static Plan make_plan(int n_agents, int n_sets) {
         pl.partG[i] = take(4 * (size_t)pl.grid * KG * H2);
     }
     for (int i = 0; i < 3; ++i) pl.partHs[i] = take(4 * (size_t)pl.grid * 8 * 2);
-    pl.bad = take(sizeof(int) + sizeof(unsigned) * 4 * (size_t)n_sets * 2);  // the flag, then scale_kernel's maxima: one memset
+    // nothing below is ever zeroed from the host: the front launch writes every word of it that a later kernel reads
+    pl.n_prep1 = (NGT_MAX * 4 * n_sets + 3) / 4, pl.n_pack = (int)((2 * rows + 255) / 256);
+    pl.n_fflag = 4 * (pl.n_prep1 + 2 * pl.n_pack);
+    pl.bad = take(sizeof(int));
+    pl.smax = take(sizeof(unsigned) * 4 * (size_t)n_sets * SCALE_SLICES * 2);
+    pl.fflag = take(sizeof(unsigned) * (size_t)pl.n_fflag);
     pl.total = o;
     return pl;
 }
@@ -1579,6 +1657,14 @@ static int check_shape(const avd_mlp_layout* L, int n_agents, int n_sets, const 
 //   ACTOR : actor gradients from the d mu the critic phase left in the workspace, finalize of the actor block
 // so that a multi-GPU caller can put the critic block's all-reduce on a side stream while the actor phase still runs
 // (avddpg_amd/trainer.py; workers/trainer.py:400-431 averages the two gradient lists independently).
+// Fifteen launches and no other stream operation in the single call (r09; r08 issued 21: two memsets -- three fills -- and 18 launches):
+//   front_kernel (scale | prep1 | slab and *bad zeroing | pack_x, roles by block range: ~30 us where the five operations it replaces
+//   took 54), prep_kernel, the four heads, dw / dx / dxa of the critic, actor_seed, dw / dx of the actor, then finalize in three
+//   (fset.hip launch_finalize: column items; W2 rows | feature items; t1 -- 41 us where four launches took 48). Every cross-block
+//   dependence is a launch boundary; the workspace and the slab may hold anything when a call begins (tests/test_gpu_fsplit_glue.py).
+//   Same box, 400-learn rounds alternated: 1785.5-1786.5 -> 1754.6-1757.0 us per learn (profiles/r09_glue_ab_learn_time.txt).
+//   Not done: finalize in TWO launches -- finalize_w2 is not independent of the column items (it adds sh1 * db2 read back from the
+//   slab), so the column items keep a launch of their own; the actor seed folded into HEAD_BOTH (7 us and a boundary: not tried).
 enum Phase { PH_CRITIC = 1, PH_ACTOR = 2, PH_BOTH = 3 };
 template <int S, class... H>
 static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, const float* theta, const float* stats, const float* theta_t,
@@ -1586,7 +1672,8 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
                float high, float* grads, float* losses, unsigned char* ws, const Plan& pl, hipStream_t st, H... hp) {
     PrepArgs pa;
     pa.L = L, pa.S = S, pa.theta = theta, pa.stats = stats, pa.theta_t = theta_t, pa.stats_t = stats_t;
-    pa.wap = (unsigned*)(ws + pl.wap), pa.bad = (int*)(ws + pl.bad), pa.smax = (unsigned*)(ws + pl.bad + sizeof(int));
+    pa.wap = (unsigned*)(ws + pl.wap), pa.bad = (int*)(ws + pl.bad), pa.smax = (unsigned*)(ws + pl.smax);
+    pa.fflag = (unsigned*)(ws + pl.fflag), pa.n_fflag = pl.n_fflag;
     NetP net[4];
     for (int i = 0; i < 4; ++i) {
         const bool critic = i & 1, target = i >= 2;
@@ -1639,17 +1726,17 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
         fa.partG[i] = F(pl.partG[i]), fa.c3[i] = F(pl.vec[i]);
     fa.t1_from_g[0] = fa.t1_from_g[1] = 1, fa.t1p = F(pl.t1p), fa.s2raw = F(pl.s2raw);  // T1 of both nets: from the weight-gradient partials
     if (phases & PH_CRITIC) {
-        if (hipMemsetAsync(ws + pl.bad, 0, sizeof(int) + sizeof(unsigned) * 4 * (size_t)n_sets * 2, st) != hipSuccess)
-            return check_launch("avd_learn_set_split: memset");
         // (r05, measured and not kept: the preparation chain -- three small dependent launches over 1.5 MB of weights, ~30 us -- on a side
         //  stream beside the input packing, forked and joined by events: 1969-1978 us per learn against 1957-1961 serial on the same
-        //  box; the fork / join costs more than the overlap of two sub-30-us stages returns)
-        hipLaunchKernelGGL(scale_kernel, dim3(4, n_sets, SCALE_SLICES), dim3(256), 0, st, pa);
+        //  box; the fork / join costs more than the overlap of two sub-30-us stages returns. r09: the same overlap without a fork --
+        //  the independent pieces are roles of ONE launch, front_kernel, which also does what two memsets did)
+        FrontArgs fr;
+        fr.pa = pa, fr.grads = grads, fr.n_grads = (long)n_sets * L.theta_size, fr.n_sets = n_sets;
+        fr.pk.x[0] = s, fr.pk.extra[0] = a, fr.pk.outh[0] = xfs, fr.pk.x[1] = s2, fr.pk.extra[1] = r, fr.pk.outh[1] = xfs2, fr.pk.rows = nrows;
+        fr.n_scale = 4 * n_sets * SCALE_SLICES, fr.n_prep1 = pl.n_prep1, fr.n_pack = pl.n_pack;
+        fr.n_zero = (int)((fr.n_grads + ZERO_PER_BLOCK - 1) / ZERO_PER_BLOCK);
+        hipLaunchKernelGGL(front_kernel<S>, dim3((unsigned)(fr.n_scale + fr.n_prep1 + fr.n_zero + 2 * fr.n_pack)), dim3(256), 0, st, fr);
         hipLaunchKernelGGL(prep_kernel, dim3(H2, 4, n_sets), dim3(320), 0, st, pa);
-        hipLaunchKernelGGL(prep1_kernel, dim3(NGT_MAX, 4, n_sets), dim3(64), 0, st, pa);
-        PackArgs pk;
-        pk.x[0] = s, pk.extra[0] = a, pk.outh[0] = xfs, pk.x[1] = s2, pk.extra[1] = r, pk.outh[1] = xfs2, pk.rows = nrows, pk.bad = bad;
-        hipLaunchKernelGGL(pack_x_kernel<S>, dim3((unsigned)((2 * nrows + 255) / 256), 2), dim3(256), 0, st, pk);
         // 1-2: targets
         head(head_kernel<S, ActorS, OUT_TANH>, 2, xfs2, nullptr, nullptr, nullptr, a2, nullptr);
         if constexpr (sizeof...(H) > 0)  // a sweep: each set's gamma (avd_learn_set_split_hp_f16x3)
@@ -1739,9 +1826,8 @@ static int split_entry(int phases, const char* who, const avd_mlp_layout* lay, i
     AVD_REQUIRE(theta && stats && s && grads && workspace && (!cr || (theta_t && stats_t && a && r && s2)), "%s: null pointer", who);
     const fsplit::Plan pl = fsplit::make_plan(n_agents, n_sets);
     AVD_REQUIRE(workspace_bytes >= pl.total, "%s: workspace %zu B < %zu B", who, workspace_bytes, pl.total);
-    // (padding floats of the slab are never written by finalize: keep them zero like every other gradient producer)
-    if (cr && hipMemsetAsync(grads, 0, sizeof(float) * (size_t)n_sets * lay->theta_size, (hipStream_t)stream) != hipSuccess)
-        return check_launch("avd_learn_set_split: hipMemsetAsync(grads)");
+    // (padding floats of the slab are never written by finalize: the critic phase's front launch zeroes the slab, like every other
+    //  gradient producer keeps them zero)
     if (lay->S == 4)
         return fsplit::run<4>(phases, *lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2, agent_weight, gamma, high, grads,
                               losses, (unsigned char*)workspace, pl, (hipStream_t)stream, hp...);
