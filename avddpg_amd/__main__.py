@@ -73,6 +73,70 @@ def sweep_experiments(sweep, seeds):
     return out
 
 
+def _scenario_flags(p, where):
+    p.add_argument("--scenarios", type=str, default=None, metavar="LIST",
+                   help=f"{where} evaluate every platoon's actors over these leader scenarios (comma-separated, of zero, step, ramp, brake, "
+                        "sine, gaussian) x --eval_seeds in ONE launch of the scenario evaluator and write scenarios.csv: one row per "
+                        "(platoon, scenario, seed, vehicle) with the control metrics (peak errors, control effort, jerk, terminal steps, "
+                        "string-stability ratio) and the case's score (not in the reference CLI)")
+    p.add_argument("--eval_seeds", type=str, default=None, metavar="LIST",
+                   help="--scenarios: the evaluation seeds (e.g. 6,7-9; default: the configuration's evaluation_seed); a seed fixes the "
+                        "start state and the gaussian scenario's leader inputs")
+    p.add_argument("--scenario_amp", type=float, default=None,
+                   help="--scenarios: the amplitude of step, ramp, brake and sine (default: reset_max_u, the scale of leader input the "
+                        "actors are trained on)")
+    p.add_argument("--scenario_period", type=float, default=None, help="--scenarios: the sine's period in seconds (default 10)")
+
+
+def _check_scenario_flags(ap, args):
+    """The scenario flags of a parsed namespace, validated in place (scenarios -> list of names, eval_seeds -> list of seeds or None)."""
+    import math
+
+    from .scenarios import check_names
+
+    if args.scenarios is None:
+        for flag in ("eval_seeds", "scenario_amp", "scenario_period"):
+            if getattr(args, flag) is not None:
+                ap.error(f"--{flag} needs --scenarios")
+        return
+    try:
+        args.scenarios = check_names([n.strip() for n in args.scenarios.split(",")])
+    except ValueError as e:
+        ap.error(f"--scenarios: {e}")
+    if args.eval_seeds is not None:
+        try:
+            args.eval_seeds = parse_seeds(args.eval_seeds)
+        except ValueError as e:
+            ap.error(str(e).replace("--seeds", "--eval_seeds"))
+    if args.scenario_amp is not None and not math.isfinite(args.scenario_amp):
+        ap.error("--scenario_amp must be finite")
+    if args.scenario_period is not None and not (math.isfinite(args.scenario_period) and args.scenario_period > 0):
+        ap.error("--scenario_period must be finite and > 0")
+    if args.mode == "tr" and int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+        # (one of the two choices: refused, rather than every rank writing a scenarios.csv of its own platoons)
+        ap.error("--scenarios is not available under a process group of more than one rank (scenarios.csv is not gathered across ranks)")
+
+
+def _suite(args):
+    """run_cases' keyword arguments from the scenario flags."""
+    return dict(scenarios=args.scenarios, seeds=args.eval_seeds, amp=args.scenario_amp,
+                period_s=10.0 if args.scenario_period is None else args.scenario_period)
+
+
+def _record_suite(conf, res, args):
+    """conf.json's scenario_suite: names, seeds, amp, period (a list of pairs: conf.json keeps lists, not dicts)."""
+    conf.scenario_suite = [["names", list(res.scenarios)], ["seeds", list(res.seeds)],
+                           ["amp", float(conf.reset_max_u if args.scenario_amp is None else args.scenario_amp)],
+                           ["period_s", 10.0 if args.scenario_period is None else float(args.scenario_period)]]
+
+
+def _slice(res, e):
+    """Experiment e's CaseResults of a batch's ([E, P, ...] arrays)."""
+    from .evaluator import CaseResults
+
+    return CaseResults(res.scenarios, res.seeds, res.T, res.scores[e], res.counters[e], {k: v[e] for k, v in res.metrics.items()})
+
+
 def get_cmdl_args(argv, conf):
     ap = argparse.ArgumentParser(prog="python -m avddpg_amd", description="avddpg hot path on MI355X")
     sub = ap.add_subparsers(dest="mode")
@@ -139,11 +203,15 @@ def get_cmdl_args(argv, conf):
                                                                         "(default 0.25)")
     tr.add_argument("--pbt_perturb", type=str, default=None, metavar="F1,F2,...",
                     help="--pbt: the factors a replaced experiment's swept values are multiplied by, one drawn per value (default 0.8,1.2)")
+    _scenario_flags(tr, "after training, beside the simulation rewards:")
     tr.add_argument("--out", type=str, default=".outputs")
     es = sub.add_parser("esim", help="run in evaluation/simulator mode")
     es.add_argument("exp_path", type=str)
     es.add_argument("--n_timesteps", type=int, default=100)
+    _scenario_flags(es, "instead of the per-platoon rollouts of --n_timesteps steps (the scenarios run the full episode length):")
     args = ap.parse_args(argv)
+    if args.mode in ("tr", "esim"):
+        _check_scenario_flags(ap, args)
     if getattr(args, "save_platoons", None) is not None and args.save_platoons < 1:
         ap.error("--save_platoons must be >= 1 (esim reloads platoon 1's actors)")
     if getattr(args, "seeds", None) is not None:
@@ -274,6 +342,11 @@ def main(argv=None, conf=None):
         # average, written into conf.json (the evaluator reseeds the global legacy RNG; run_many puts it back)
         conf.pl_rews_for_simulations = vt.run_simulations()
         conf.pl_rew_for_simulation = float(np.average(conf.pl_rews_for_simulations))
+        if args.scenarios is not None:  # every local platoon over scenarios x seeds, one launch
+            from . import scenarios as _sc
+            res = vt.evaluate_scenarios(**_suite(args))
+            _sc.write_csv(os.path.join(base, "scenarios.csv"), res, range(1, vt.P + 1))
+            _record_suite(conf, res, args)
         n_save = vt.P if args.save_platoons is None and args.episodes == "reference" else min(vt.P, 4 if args.save_platoons is None else args.save_platoons)
         artifacts.save_agents(base, vt.agents, n_save, vt.M, shared=vt.shared)
         # what ran, beside the reference's fields: how many platoons' agents the directory holds (esim loops over exactly these),
@@ -296,6 +369,19 @@ def main(argv=None, conf=None):
         # a run saved with --save_platoons N holds the first N platoons' agents: conf.json says how many (older directories: all)
         import json
         saved = json.load(open(os.path.join(args.exp_path, "conf.json"))).get("saved_platoons", conf.num_platoons)
+        if args.scenarios is not None:  # ALL saved platoons' actors in one group, one launch
+            from . import scenarios as _sc
+            saved = int(saved)
+            grp = vec.AgentGroup(saved * M, shape.num_states, shape.num_actions, conf, hidd_mult=shape.hidden_multiplier)
+            for p in range(1, saved + 1):
+                if not os.path.exists(os.path.join(args.exp_path, artifacts.FNAME["actor"] % (p, 1) + ".npz")):
+                    raise FileNotFoundError(f"{args.exp_path}: no checkpoint of platoon {p}'s actors (conf.json records {saved} saved platoons)")
+                for m in range(M):
+                    grp.set_weights((p - 1) * M + m, "actor", artifacts.load_actor_weights(args.exp_path, p, m + 1))
+            res = evaluator.run_cases(conf, grp, range(saved), **_suite(args))
+            _sc.write_csv(os.path.join(args.exp_path, "scenarios.csv"), res, range(1, saved + 1))
+            print("\n".join(_sc.report_lines(res, range(1, saved + 1))))
+            return
         for p in range(1, int(saved) + 1):
             if not os.path.exists(os.path.join(args.exp_path, artifacts.FNAME["actor"] % (p, 1) + ".npz")):
                 raise FileNotFoundError(f"{args.exp_path}: no checkpoint of platoon {p}'s actors (conf.json records {saved} saved platoons)")
@@ -413,6 +499,7 @@ def train_seed_batch(args, conf, base, experiments=None):
     if vt.nonfinite_updates():
         print(f"warning: {vt.nonfinite_updates()} weight-set updates were skipped for non-finite gradients", file=sys.stderr)
     sims = vt.run_simulations()  # [E][P], one rollout launch
+    suite = vt.evaluate_scenarios(**_suite(args)) if args.scenarios is not None else None  # [E, P, scen, seed, ...], one launch
     n_save = min(P, 4 if args.save_platoons is None else args.save_platoons)
     done = []
     for e, (k, d) in enumerate(zip(seeds, dirs)):
@@ -433,6 +520,10 @@ def train_seed_batch(args, conf, base, experiments=None):
             if use_pbt:  # (lists of pairs, as `sweep`: conf.json keeps lists, not dicts, at the top level)
                 ce.pbt = [["interval", args.pbt], ["fraction", args.pbt_fraction], ["perturb", list(args.pbt_perturb)],
                           ["lineage", lineage[e]]]
+        if suite is not None:
+            from . import scenarios as _sc
+            _sc.write_csv(os.path.join(d, "scenarios.csv"), _slice(suite, e), range(1, P + 1))
+            _record_suite(ce, suite, args)
         artifacts.config_writer(os.path.join(d, "conf.json"), ce)
         done.append((ce, last[e]))
     return done

@@ -13,6 +13,7 @@ if os.environ.get("AVDDPG_HIP_LIB"):  # diagnostics: A/B another build of the sa
     LIB_PATH = os.path.abspath(os.environ["AVDDPG_HIP_LIB"])
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "avddpg_hip.h")
 AVD_MAX_L = 16
+AVD_EVAL_NMETRIC = 8
 
 
 class AvdError(RuntimeError):
@@ -118,6 +119,8 @@ _PROTOS = {
     "avd_actor_forward_shared_bf16": [_LP, _i, _i, _P, _P, _P, _f, _P, _P, C.c_size_t, _P],
     "avd_eval_rollout_f32": [_LP, _P, _i, _i, _i, _i, _P, _P, _i, _P, _P, _P, _P, _i, _P, _f, _f, _f, _f, _P, _i, _P, _P, _P, _P,
                              _P],
+    "avd_eval_cases_f32": [_LP, _P, _i, _i, _i, _i, _i, _P, _P, _i, _P, _P, _P, _P, _f, _f, _f, _f, _P, _P, _P],
+    "avd_eval_cases_block": [_i, _i],  # returns the block size itself (>= 1), or AVD_E_INVALID: not for call()
     "avd_gemm_bt_bf16": [_i, _i, _i, _P, C.c_long, _P, C.c_long, _P, C.c_long, _P],
 }
 

@@ -1,0 +1,313 @@
+// Scenario evaluator for gfx950: G groups (one platoon's weight sets each) x K cases (a start state and a leader-input row each) of the
+// evaluator rollout (eval.hip) in ONE launch, with per-vehicle control metrics reduced on the device.
+//
+// One 256-thread workgroup per (group, block of RB cases): grid G x ceil(K / RB), no communication between workgroups, no spin-wait.
+// Every case of a group reads the SAME weights, so per step and model each thread loads each weight element it owns once and applies
+// it to all RB rows of its block: acc[r] = fmaf(x[r][k], w, acc[r]). Per row the k split, the fmaf order and the reduction tree are
+// those of gemv_relu / bn_apply / block_dot (learn_common.h), so row r's actor outputs -- and with the shared platoon step
+// (eval_common.h) its counters -- are bit-identical to eval_rollout_kernel's, while the weight bytes streamed drop RB-fold.
+//
+// Activations live in LDS transposed, [k][RB]: a thread's RB operands of one k are RB consecutive floats (ds_read_b128 for RB % 4 == 0),
+// read as a broadcast by every lane of a wave that works on the same k range.
+//
+// Rows >= K of the tail block are computed on a zero state in LDS only: they read no start state or leader input and write nothing.
+#include "eval_common.h"
+
+namespace avd {
+
+constexpr int CASES_LDS_SHARED = 24 * AVD_MAX_L;                  // sA, sB, sC (floats), one copy per workgroup
+constexpr int CASES_LDS_ROW = 11 * AVD_MAX_L + NTHREADS;          // per row: xin, xs, raw, chain, negr, part (floats); + H1 + H2
+
+struct CasesArgs {
+    avd_mlp_layout lay;
+    const avd_env_consts* cst;
+    int G, K, L, M, T, x_stride, n_sets;
+    const float* theta;
+    const float* stats;
+    const int32_t* set_base;  // [G]
+    const float* x0;          // [K][L][4]
+    const float* prev_a0;     // [K][L]
+    const float* leader;      // [K][T]
+    float high, lo, hi, inv_dt;
+    float* counters;          // [G][K][M]
+    float* metrics;           // [G][K][L][AVD_EVAL_NMETRIC] or null
+};
+
+// the RB row operands of one k: xT[k][0..RB)
+template <int RB>
+__device__ __forceinline__ void load_rows(const float* p, float (&x)[RB]) {
+    if constexpr (RB % 4 == 0) {
+#pragma unroll
+        for (int r = 0; r < RB; r += 4) {
+            const float4 v = *(const float4*)(p + r);
+            x[r] = v.x, x[r + 1] = v.y, x[r + 2] = v.z, x[r + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < RB; ++r) x[r] = p[r];
+    }
+}
+
+// gemv_relu (learn_common.h) for RB rows: yT[n][r] = relu(sum_k xT[k][r] * W[k][n] + b[n]); part is [RB][NTHREADS]
+template <int RB>
+__device__ __forceinline__ void gemv_relu_rows(const float* xT, int K, const float* __restrict__ W, const float* __restrict__ b, int N,
+                                               float* part, float* yT) {
+    const int cols = N < NTHREADS ? N : NTHREADS;
+    const int ksplit = NTHREADS / cols;
+    for (int n0 = 0; n0 < N; n0 += cols) {
+        const int n = n0 + (threadIdx.x % cols);
+        const int kh = threadIdx.x / cols;
+        constexpr int UNROLL_K = RB >= 16 ? 2 : 4;  // 16 rows: two k in flight keep the kernel at 146 VGPRs (3 waves per SIMD)
+        float acc[RB];
+#pragma unroll
+        for (int r = 0; r < RB; ++r) acc[r] = 0.f;
+        if (kh < ksplit && n < N) {
+            const int kb = (K * kh) / ksplit, ke = (K * (kh + 1)) / ksplit;
+#pragma unroll UNROLL_K
+            for (int k = kb; k < ke; ++k) {
+                const float w = W[(long)k * N + n];
+                float x[RB];
+                load_rows<RB>(xT + k * RB, x);
+#pragma unroll
+                for (int r = 0; r < RB; ++r) acc[r] = fmaf(x[r], w, acc[r]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < RB; ++r) part[r * NTHREADS + threadIdx.x] = acc[r];
+        __syncthreads();
+        if (threadIdx.x < cols && n < N) {
+            const float bn = b[n];
+#pragma unroll
+            for (int r = 0; r < RB; ++r) {
+                float sum = bn;
+                for (int h = 0; h < ksplit; ++h) sum += part[r * NTHREADS + h * cols + threadIdx.x];
+                yT[n * RB + r] = fmaxf(sum, 0.f);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// bn_apply (learn_common.h) for RB rows: the coefficients are formed once per k
+template <int RB>
+__device__ __forceinline__ void bn_apply_rows(float* yT, int n, const float* __restrict__ g, const float* __restrict__ be,
+                                              const float* __restrict__ mm, const float* __restrict__ mv) {
+    for (int k = threadIdx.x; k < n; k += NTHREADS) {
+        const float iv = (1.0f / sqrtf(mv[k] + BN_EPS)) * g[k];
+#pragma unroll
+        for (int r = 0; r < RB; ++r) yT[k * RB + r] = fmaf(yT[k * RB + r], iv, be[k] - mm[k] * iv);
+    }
+}
+
+// block_dot (learn_common.h) for RB rows: out[r] = sum_k xT[k][r] * w[k * wstride] in part[r * NTHREADS + 0..3] (the four waves'
+// partial sums, to be added in wave order); one barrier, the caller adds and synchronizes
+template <int RB>
+__device__ __forceinline__ void block_dot_rows(const float* xT, const float* __restrict__ w, int wstride, int n, float* part) {
+    float acc[RB];
+#pragma unroll
+    for (int r = 0; r < RB; ++r) acc[r] = 0.f;
+    for (int k = threadIdx.x; k < n; k += NTHREADS) {
+        const float wk = w[(long)k * wstride];
+        float x[RB];
+        load_rows<RB>(xT + k * RB, x);
+#pragma unroll
+        for (int r = 0; r < RB; ++r) acc[r] = fmaf(x[r], wk, acc[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < RB; ++r) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc[r] += __shfl_xor(acc[r], o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int r = 0; r < RB; ++r) part[r * NTHREADS + (threadIdx.x >> 6)] = acc[r];
+    }
+    __syncthreads();
+}
+
+template <int RB>
+__global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const avd_mlp_layout& L = a.lay;
+    const int tid = threadIdx.x, nv = a.L, g = blockIdx.x, k0 = blockIdx.y * RB;
+    const int nrows = (a.K - k0) < RB ? (a.K - k0) : RB;  // rows of this block that are cases (>= 1 by the grid)
+    float* sA = smem;                               // [L][16]
+    float* sB = sA + 16 * AVD_MAX_L;                // [L][4]
+    float* sC = sB + 4 * AVD_MAX_L;                 // [L][4]
+    float* xs = sC + 4 * AVD_MAX_L;                 // [RB][4 * AVD_MAX_L] platoon states (the actors' input)
+    float* xinT = xs + RB * 4 * AVD_MAX_L;          // [S][RB] one model's observation, transposed
+    float* raw = xinT + RB * 4 * AVD_MAX_L;         // [RB][AVD_MAX_L] actor outputs, vehicle order (m * A + a)
+    float* chain = raw + RB * AVD_MAX_L;            // [RB][AVD_MAX_L]
+    float* negr = chain + RB * AVD_MAX_L;           // [RB][AVD_MAX_L]
+    float* part = negr + RB * AVD_MAX_L;            // [RB][NTHREADS]
+    float* h1T = part + RB * NTHREADS;              // [H1][RB]
+    float* h2T = h1T + RB * L.H1;                   // [H2][RB]
+    const int row = tid / nv, v = tid - row * nv;   // vehicle threads: RB * L <= NTHREADS (host check)
+    const bool veh = tid < RB * nv;
+    const bool live = veh && row < nrows;           // a vehicle of a real case: the only threads that touch x0 / leader / the outputs
+    const long cas = (long)g * a.K + k0 + row;      // (group, case) index of this thread's row
+    const int base = a.set_base[g];
+    if (base < 0 || base + a.M > a.n_sets) {  // uniform per workgroup: nothing read
+        if (live) {
+            if (v < a.M) a.counters[cas * a.M + v] = __builtin_nanf("");
+            if (a.metrics)
+                for (int i = 0; i < AVD_EVAL_NMETRIC; ++i) a.metrics[(cas * nv + v) * AVD_EVAL_NMETRIC + i] = __builtin_nanf("");
+        }
+        return;
+    }
+    const avd_env_consts* cst = a.cst;
+    for (int i = tid; i < nv * 16; i += NTHREADS) sA[i] = cst->A[i >> 4][i & 15];
+    for (int i = tid; i < nv * 4; i += NTHREADS) sB[i] = cst->B[i >> 2][i & 3], sC[i] = cst->C[i >> 2][i & 3];
+    for (int i = tid; i < RB * 4 * AVD_MAX_L; i += NTHREADS) xs[i] = 0.f;
+    __syncthreads();
+    float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
+    float pa = 0.f, cnt = 0.f;
+    float mx_ep = 0.f, mx_ev = 0.f, mx_a = 0.f, su2 = 0.f, sj2 = 0.f, nterm = 0.f, first = -1.0f;
+    const float* leader = a.leader + (long)(k0 + (live ? row : 0)) * a.T;
+    if (live) {
+        const float* x0 = a.x0 + ((long)(k0 + row) * nv + v) * 4;
+        xv = make_float4(x0[0], x0[1], x0[2], x0[3]);
+        pa = a.prev_a0[(long)(k0 + row) * nv + v];
+    }
+    if (veh) ((float4*)(xs + row * 4 * AVD_MAX_L))[v] = xv;
+    __syncthreads();
+    const int S = L.S, A = L.A, M = a.M;
+    for (int t = 0; t < a.T; ++t) {
+        // ---- actor forward of each model, RB rows at once ----
+        for (int m = 0; m < M; ++m) {
+            const float* th = a.theta + (long)(base + m) * L.theta_size;
+            const float* st = a.stats + (long)(base + m) * L.stats_size;
+            for (int i = tid; i < RB * S; i += NTHREADS) {
+                const int r = i / S, s = i - r * S;
+                xinT[s * RB + r] = xs[r * 4 * AVD_MAX_L + m * a.x_stride + s];
+            }
+            __syncthreads();
+            gemv_relu_rows<RB>(xinT, S, th + L.aW1, th + L.ab1, L.H1, part, h1T);
+            bn_apply_rows<RB>(h1T, L.H1, th + L.ag1, th + L.abe1, st + L.amm1, st + L.amv1);
+            __syncthreads();
+            gemv_relu_rows<RB>(h1T, L.H1, th + L.aW2, th + L.ab2, L.H2, part, h2T);
+            bn_apply_rows<RB>(h2T, L.H2, th + L.ag2, th + L.abe2, st + L.amm2, st + L.amv2);
+            __syncthreads();
+            for (int k = 0; k < A; ++k) {
+                block_dot_rows<RB>(h2T, th + L.aW3 + k, A, L.H2, part);
+                if (tid < RB) {
+                    const float* p = part + tid * NTHREADS;
+                    const float z = (p[0] + p[1] + p[2] + p[3]) + th[L.ab3 + k];
+                    raw[tid * AVD_MAX_L + m * A + k] = tanhf(z) * a.high;
+                }
+                __syncthreads();
+            }
+        }
+        // ---- noise-free policy, platoon step ----
+        float uu = 0.f;
+        VehStep vs = {};
+        if (veh) {
+            uu = fminf(fmaxf(raw[row * AVD_MAX_L + v], a.lo), a.hi);  // np.clip (ddpgagent.py:27)
+            vs = veh_step_pre(cst, sA + v * 16, sB + v * 4, xv, uu);
+            chain[row * AVD_MAX_L + v] = vs.chain;
+        }
+        __syncthreads();
+        if (veh) {
+            const float exog = (v == 0) ? (live ? leader[t] : 0.f) : chain[row * AVD_MAX_L + v - 1];
+            float4 xn;
+            const float nr = veh_step_post(cst, vs, sB + v * 4, sC + v * 4, xv, pa, uu, exog, xn);
+            if (M == nv) cnt = cnt + nr;  // counters += env.reward[0]
+            else negr[row * AVD_MAX_L + v] = nr;
+            // ---- metrics (scenarios.metrics_from_traces: sequential float32 sums in step order, no contraction) ----
+            const bool is_term = ((fabsf(xv.x) > cst->max_ep) || (fabsf(xv.y) > cst->max_ev)) && (cst->can_terminate != 0);  // veh_step_post's test
+            if (is_term) {
+                nterm = nterm + 1.0f;
+                if (first < 0.f) first = (float)t;
+            }
+            const float jerk = (xv.z - pa) * a.inv_dt;
+            su2 = su2 + uu * uu;
+            sj2 = sj2 + jerk * jerk;
+            mx_ep = fmaxf(mx_ep, fabsf(xn.x)), mx_ev = fmaxf(mx_ev, fabsf(xn.y)), mx_a = fmaxf(mx_a, fabsf(xn.z));
+            pa = xv.z;  // prev_x <- x
+            xv = xn;
+            ((float4*)(xs + row * 4 * AVD_MAX_L))[v] = xn;
+        }
+        __syncthreads();
+        if (M != nv && veh && v == 0) {  // centralized: counters += reward_mean = (1/L) * sum in vehicle order (env.hip)
+            float s = 0.f;
+            for (int k = 0; k < nv; ++k) s = s + negr[row * AVD_MAX_L + k];
+            cnt = cnt + (1.0f / (float)nv) * s;
+        }
+    }
+    if (live) {
+        if (v < M) a.counters[cas * M + v] = cnt;
+        if (a.metrics) {
+            float* o = a.metrics + (cas * nv + v) * AVD_EVAL_NMETRIC;
+            o[0] = mx_ep, o[1] = mx_ev, o[2] = mx_a, o[3] = su2, o[4] = sj2, o[5] = nterm, o[6] = first, o[7] = fabsf(xv.x);
+        }
+    }
+}
+
+// the block sizes instantiated, largest first
+constexpr int CASES_RB[] = {16, 8, 4, 1};
+
+int cases_block(int K, int L) {
+    int rb = CASES_RB[0];
+    for (int c : CASES_RB)  // the smallest block that holds all K cases (no idle rows beyond the tail), else the largest
+        if (c >= K && c * L <= NTHREADS) rb = c;
+    return rb;
+}
+
+template <int RB>
+int launch_cases(const CasesArgs& a, size_t lds, hipStream_t stream) {
+    if (lds > 48 * 1024)
+        (void)hipFuncSetAttribute((const void*)eval_cases_kernel<RB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(eval_cases_kernel<RB>, dim3(a.G, (a.K + RB - 1) / RB), dim3(NTHREADS), lds, stream, a);
+    return check_launch("avd_eval_cases_f32");
+}
+
+}  // namespace avd
+
+using namespace avd;
+
+extern "C" int avd_eval_cases_block(int K, int L) {
+    AVD_REQUIRE(K >= 1, "avd_eval_cases_block: K=%d (K must be >= 1)", K);
+    AVD_REQUIRE(L >= 1 && L <= AVD_MAX_L, "avd_eval_cases_block: L=%d (L must be 1..%d)", L, AVD_MAX_L);
+    return cases_block(K, L);
+}
+
+extern "C" int avd_eval_cases_f32(const avd_mlp_layout* lay, const avd_env_consts* d_consts, int G, int K, int L, int M, int T,
+                                  const float* theta, const float* stats, int n_sets, const int32_t* set_base, const float* x0,
+                                  const float* prev_a0, const float* leader, float high, float lo, float hi, float sample_rate,
+                                  float* counters, float* metrics, void* stream) {
+    AVD_REQUIRE(lay && d_consts, "avd_eval_cases_f32: null layout or constants");
+    AVD_REQUIRE(L >= 1 && L <= AVD_MAX_L, "avd_eval_cases_f32: L=%d (L must be 1..%d)", L, AVD_MAX_L);
+    AVD_REQUIRE(M == L || M == 1, "avd_eval_cases_f32: M=%d (M must be L=%d, decentralized, or 1, centralized)", M, L);
+    AVD_REQUIRE(G >= 1 && K >= 1 && T >= 1, "avd_eval_cases_f32: G=%d K=%d T=%d (all must be >= 1)", G, K, T);
+    AVD_REQUIRE(n_sets >= M, "avd_eval_cases_f32: n_sets=%d (need n_sets >= M=%d)", n_sets, M);
+    AVD_REQUIRE(theta && stats && set_base && x0 && prev_a0 && leader && counters, "avd_eval_cases_f32: null pointer");
+    AVD_REQUIRE(sample_rate > 0.f, "avd_eval_cases_f32: sample_rate=%g", (double)sample_rate);
+    // the model shape the platoon implies: M * A = L actions, observations of 4L / M floats (the first S read)
+    const int x_stride = 4 * L / M;
+    AVD_REQUIRE(lay->A * M == L && lay->S <= x_stride && lay->S >= 1,
+                "avd_eval_cases_f32: layout S=%d A=%d does not fit L=%d M=%d (need A * M == L, S <= %d)", lay->S, lay->A, L, M, x_stride);
+    AVD_REQUIRE(lay->H1 > 0 && lay->H2 > 0, "avd_eval_cases_f32: layout H1=%d H2=%d", lay->H1, lay->H2);
+    const int rb = cases_block(K, L);
+    const size_t lds = sizeof(float) * ((size_t)CASES_LDS_SHARED + (size_t)rb * ((size_t)CASES_LDS_ROW + lay->H1 + lay->H2));
+    if (lds > 160 * 1024) {
+        set_error("avd_eval_cases_f32: hidden sizes need %zu B of LDS for blocks of %d cases (> 160 KiB)", lds, rb);
+        return AVD_E_UNSUPPORTED;
+    }
+    if ((long)((K + rb - 1) / rb) > 65535) {
+        set_error("avd_eval_cases_f32: K=%d cases in blocks of %d exceed the grid's second dimension", K, rb);
+        return AVD_E_UNSUPPORTED;
+    }
+    CasesArgs a;
+    a.lay = *lay, a.cst = d_consts, a.G = G, a.K = K, a.L = L, a.M = M, a.T = T, a.x_stride = x_stride, a.n_sets = n_sets;
+    a.theta = theta, a.stats = stats, a.set_base = set_base, a.x0 = x0, a.prev_a0 = prev_a0, a.leader = leader;
+    a.high = high, a.lo = lo, a.hi = hi;
+    a.inv_dt = 1.0f / sample_rate;  // host float32 division, as avd_eval_rollout_f32 forms it
+    a.counters = counters, a.metrics = metrics;
+    switch (rb) {
+        case 16: return launch_cases<16>(a, lds, (hipStream_t)stream);
+        case 8: return launch_cases<8>(a, lds, (hipStream_t)stream);
+        case 4: return launch_cases<4>(a, lds, (hipStream_t)stream);
+        default: return launch_cases<1>(a, lds, (hipStream_t)stream);
+    }
+}

@@ -164,3 +164,124 @@ def run_many(conf, actors, platoons, set_mod=None, seeds=None, manual_timestep_o
     b = prepare_many(conf, actors, platoons, set_mod, seeds, manual_timestep_override, trace, set_bases)
     b.launch()
     return b.results()
+
+
+class CaseResults:
+    """What run_cases returns: ``scores`` float32 [NP, n_scen, n_seed] (round(mean(counters), 3), :145), ``counters`` float32
+    [NP, n_scen, n_seed, M], ``metrics`` {name: float32 [NP, n_scen, n_seed, L]} (scenarios.METRICS), ``summary()`` the derived
+    values (scenarios.summarise); ``scenarios`` / ``seeds`` name the two case axes, ``T`` is the rollout length."""
+
+    def __init__(self, scenarios, seeds, T, scores, counters, metrics):
+        self.scenarios, self.seeds, self.T = list(scenarios), list(seeds), int(T)
+        self.scores, self.counters, self.metrics = scores, counters, metrics
+
+    def summary(self):
+        from . import scenarios as _sc
+
+        return _sc.summarise(self.metrics, self.T)
+
+
+class CaseBatch:
+    """The device inputs of one avd_eval_cases_f32 launch (prepare_cases); ``launch()`` enqueues it on the current stream,
+    ``results()`` reads counters and metrics back. run_cases = prepare_cases + launch + results. ``block`` is the number of cases per
+    workgroup the kernel uses for this batch (avd_eval_cases_block)."""
+
+    def __init__(self, conf, actors, platoons, scenarios, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override):
+        from . import _hip
+        from . import scenarios as _sc
+
+        platoons = [int(p) for p in platoons]
+        names = _sc.check_names(scenarios)
+        seeds = [int(conf.evaluation_seed)] if seeds is None else [int(s) for s in seeds]
+        if not platoons or not seeds:
+            raise ValueError("run_cases needs at least one platoon and one seed")
+        if len(set(seeds)) != len(seeds):
+            raise ValueError(f"seeds {seeds}: a seed is listed more than once")
+        T = get_number_of_timesteps_for_plot(conf, manual_timestep_override)
+        amp, period_s = _sc.check_knobs(T, amp, period_s)
+        NP, NS, NC = len(platoons), len(seeds), len(names)
+        saved = np.random.get_state()
+        try:
+            starts = [_start(conf, True, manual_timestep_override, evaluation_seed=sd) for sd in seeds]
+        finally:
+            np.random.set_state(saved)
+        env = starts[0][0]
+        L, M = conf.pl_size, env.num_models
+        lay = actors.lay
+        if (lay.S, lay.A) != (env.num_states, env.num_actions):
+            raise ValueError(f"actors have S={lay.S} A={lay.A}, the platoon needs S={env.num_states} A={env.num_actions}")
+        shared = set_mod is not None and set_mod != 0
+        if shared and set_mod != M:
+            raise ValueError(f"set_mod={set_mod}: run_cases addresses per-agent sets (None / 0) or shared sets (set_mod = M = {M})")
+        if not shared and min(platoons) < 0:
+            raise ValueError("negative platoon index")
+        if set_bases is not None:
+            set_bases = [int(b) for b in set_bases]
+            if not shared or len(set_bases) != NP or min(set_bases) < 0:
+                raise ValueError(f"set_bases={set_bases}: shared sets only (set_mod = M), one non-negative base per platoon entry")
+        need = (M + (max(set_bases) if set_bases else 0)) if shared else (max(platoons) + 1) * M
+        if need > actors.n_sets:
+            raise ValueError(f"platoons {platoons} need {need} weight sets, the group holds {actors.n_sets}")
+        # groups: shared sets ONE (every platoon's result is the same) -- or, with set_bases, one per entry; per-agent sets one per platoon
+        per_entry = not shared or set_bases is not None
+        bases = [0] if not per_entry else (set_bases if shared else [p * M for p in platoons])
+        self.group = (lambda i: i) if per_entry else (lambda i: 0)
+        self.G, self.K = len(bases), NC * NS
+        dev = env.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.conf, self.actors, self.env, self.T, self.L, self.M, self.NP, self.NS, self.NC = conf, actors, env, T, L, M, NP, NS, NC
+        self.scenarios, self.seeds = names, seeds
+        # cases: scenarios x seeds, seeds innermost; a case's start state is its seed's, its leader row its scenario's (gaussian: its seed's)
+        prof = {n: _sc.leader_profile(n, T, conf, amp, period_s) for n in names if n != "gaussian"}
+        self.leader_h = np.stack([starts[k][1] if n == "gaussian" else prof[n] for n in names for k in range(NS)])
+        self.x0 = torch.stack([e.x.reshape(L, 4) for e, _, _ in starts]).repeat(NC, 1, 1).contiguous()
+        self.pa0 = torch.stack([e.prev_a.reshape(L) for e, _, _ in starts]).repeat(NC, 1).contiguous()
+        self.leader = torch.from_numpy(self.leader_h).to(dev)
+        self.set_base = torch.tensor(bases, dtype=torch.int32, device=dev)
+        self.counters = torch.empty(self.G, self.K, M, **f32)
+        self.metrics = torch.empty(self.G, self.K, L, _hip.AVD_EVAL_NMETRIC, **f32)
+        self.block = int(_hip.lib().avd_eval_cases_block(self.K, L))
+
+    def launch(self):
+        a, c = self.actors, self.conf
+        call("avd_eval_cases_f32", a._layp, ptr(self.env.d_consts), self.G, self.K, self.L, self.M, self.T, ptr(a.theta), ptr(a.stats),
+             a.n_sets, ptr(self.set_base), ptr(self.x0), ptr(self.pa0), ptr(self.leader), a.high, c.action_low, c.action_high,
+             c.sample_rate, ptr(self.counters), ptr(self.metrics), stream_handle())
+
+    def results(self):
+        from . import scenarios as _sc
+
+        c = self.counters.cpu().numpy().reshape(self.G * self.K, self.M)
+        rows = np.array([round(np.average(r), 3) for r in c], dtype=np.float32)  # row by row, as run (:145)
+        sel = [self.group(i) for i in range(self.NP)]
+        scores = rows.reshape(self.G, self.NC, self.NS)[sel]
+        cnt = c.reshape(self.G, self.NC, self.NS, self.M)[sel]
+        m = self.metrics.cpu().numpy().reshape(self.G, self.NC, self.NS, self.L, -1)[sel]
+        metrics = {n: np.ascontiguousarray(m[..., j]) for j, n in enumerate(_sc.METRICS)}
+        return CaseResults(self.scenarios, self.seeds, self.T, scores, cnt, metrics)
+
+
+def prepare_cases(conf, actors, platoons, scenarios=("gaussian",), seeds=None, amp=None, period_s=10.0, set_mod=None, set_bases=None,
+                  manual_timestep_override=None):
+    """run_cases' host part (start states drawn, leader profiles made, device inputs uploaded) as a CaseBatch."""
+    return CaseBatch(conf, actors, platoons, scenarios, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override)
+
+
+def run_cases(conf, actors, platoons, scenarios=("gaussian",), seeds=None, amp=None, period_s=10.0, set_mod=None, set_bases=None,
+              manual_timestep_override=None):
+    """Every platoon's actors over a library of leader scenarios x evaluation seeds in ONE launch of the scenario evaluator
+    (avd_eval_cases_f32, csrc/evalx.hip): one workgroup per (platoon, block of cases), each weight element read once per block, the
+    per-vehicle control metrics reduced on the device. The reference's evaluator names these input responses and fills in only the
+    Gaussian one (workers/evaluator.py:55-70).
+
+    scenarios: names of scenarios.SCENARIOS (leader_profile; amp defaults to conf.reset_max_u, period_s is the sine's period).
+    seeds: evaluation seeds (default ``(conf.evaluation_seed,)``). Cases are scenarios x seeds, seeds innermost; a case's start state
+    is drawn as ``run`` draws it for its seed, and only the gaussian scenario's leader inputs depend on the seed. The caller's global
+    ``np.random`` state is restored on return. actors / platoons / set_mod / set_bases address weight sets as in ``run_many``.
+
+    Returns a CaseResults. Entry [i, s, k] of its counters is bit-identical to the rollout kernel's (run_many) on the same start state
+    and leader row -- for the gaussian scenario, to ``run_many(seeds=seeds)[1][i, k]`` -- and its metrics to
+    scenarios.metrics_from_traces on that rollout's traces."""
+    b = prepare_cases(conf, actors, platoons, scenarios, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override)
+    b.launch()
+    return b.results()

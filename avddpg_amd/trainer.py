@@ -731,6 +731,33 @@ class VecTrainer:
             return np.repeat(sc[:, 0], len(platoons))
         return evaluator.run_many(self.conf, self.agents, platoons)[0][:, 0]
 
+    def evaluate_scenarios(self, scenarios, seeds=None, platoons=None, amp=None, period_s=10.0):
+        """The CURRENT actors of each of this rank's ``platoons`` (default: all) over leader scenarios x evaluation seeds, from one
+        launch of the scenario evaluator (evaluator.run_cases): a CaseResults with scores [P, scen, seed], counters [P, scen, seed, M]
+        and metrics {name: [P, scen, seed, L]}. Shared sets: one group of rollouts, repeated per platoon.
+        A seed batch or sweep: ``platoons`` index each experiment's own platoons and every array gains a leading experiment axis
+        ([E, P, scen, seed, ...]), still from one launch; experiment e's slice equals run_cases on experiment_agents(e)."""
+        from . import evaluator
+
+        kw = dict(scenarios=scenarios, seeds=seeds, amp=amp, period_s=period_s)
+        if self.seeds is not None:
+            E, M = self.E, self.M
+            platoons = list(range(self.P_exp)) if platoons is None else list(platoons)
+            n = len(platoons)
+            if self.shared:  # one group per experiment, on its sets e*M .. e*M+M-1
+                r = evaluator.run_cases(self.conf, self.agents, list(range(E)), set_mod=M, set_bases=[e * M for e in range(E)], **kw)
+                lift = lambda x: np.repeat(x[:, None], n, axis=1)
+            else:
+                r = evaluator.run_cases(self.conf, self.agents, [vec.batch_platoon(e, p, E) for e in range(E) for p in platoons], **kw)
+                lift = lambda x: x.reshape(E, n, *x.shape[1:])
+            return evaluator.CaseResults(r.scenarios, r.seeds, r.T, lift(r.scores), lift(r.counters), {k: lift(v) for k, v in r.metrics.items()})
+        platoons = list(range(self.P)) if platoons is None else list(platoons)
+        if self.shared:
+            r = evaluator.run_cases(self.conf, self.agents, [0], set_mod=self.M, **kw)
+            rep = lambda x: np.repeat(x, len(platoons), axis=0)
+            return evaluator.CaseResults(r.scenarios, r.seeds, r.T, rep(r.scores), rep(r.counters), {k: rep(v) for k, v in r.metrics.items()})
+        return evaluator.run_cases(self.conf, self.agents, platoons, **kw)
+
     def run_simulations(self):
         """Trainer.run_simulations (workers/trainer.py:537-550): every local platoon's evaluator score over steps_per_episode
         steps divided by re_scalar -- the values the reference appends to conf.pl_rews_for_simulations (:549). Plots and the

@@ -535,6 +535,33 @@ int avd_eval_rollout_f32(const avd_mlp_layout* lay, const avd_env_consts* d_cons
                          float sample_rate, float* counters, int n_trace, const int32_t* trace_idx, float* tr_states,
                          float* tr_actions, float* tr_jerks, void* stream);
 
+/* ---- scenario evaluator: the evaluator rollout above for G groups x K cases in ONE launch, with control metrics reduced on the
+ *      device. The reference's evaluator loops over an `input_opts` dict "for a variety of input responses" of which only the
+ *      Gaussian one was filled in (workers/evaluator.py:55-70; config.py names zerofig_name / stepfig_name / rampfig_name beside
+ *      guasfig_name) ------------------------------------------------------------------------------------------------------------
+ * Group g is one platoon's weight sets set_base[g] .. set_base[g] + M - 1 (< n_sets); case k is the start state x0[k] [L][4],
+ * prev_a0[k] [L] and the leader-input row leader[k] [T]. Every group runs every case. counters[g][k] [M] is bit-identical to what
+ * avd_eval_rollout_f32 writes for a rollout with set_base = set_base[g], start_idx = k. metrics[g][k] [L][AVD_EVAL_NMETRIC] (or
+ * NULL), per vehicle, float32, sums as sequential float32 adds in step order without contraction:
+ *   0 max_abs_ep, 1 max_abs_ev, 2 max_abs_a  max over steps of |post-step state[0 / 1 / 2]|
+ *   3 sum_u2                                 sum of the clipped action squared
+ *   4 sum_jerk2                              sum of the jerk squared, jerk = (x_before[2] - prev_a_before) * (1 / sample_rate)
+ *   5 term_steps, 6 first_term               steps on which the terminal test (pre-step state, environment.py:505-510) fired and the
+ *                                            first of them (-1: none); the evaluator does not stop on it
+ *   7 final_abs_ep                           |state[0]| after the last step
+ * One workgroup per (group, block of avd_eval_cases_block(K, L) cases): each weight element is read once per block and applied to
+ * all of its rows, with the per-row summation order of the rollout kernel. A set_base out of range makes that group's counters
+ * and metrics NaN and reads nothing. M must be L or 1, lay->A * M == L. */
+#define AVD_EVAL_NMETRIC 8
+int avd_eval_cases_f32(const avd_mlp_layout* lay, const avd_env_consts* d_consts, int G, int K, int L, int M, int T,
+                       const float* theta, const float* stats, int n_sets, const int32_t* set_base, const float* x0,
+                       const float* prev_a0, const float* leader, float high, float lo, float hi, float sample_rate,
+                       float* counters, float* metrics, void* stream);
+
+/* The number of cases per workgroup avd_eval_cases_f32 uses for K cases of L vehicles (host only, no HIP call): the value itself
+ * (>= 1), or AVD_E_INVALID for K < 1 or L outside 1..AVD_MAX_L. */
+int avd_eval_cases_block(int K, int L);
+
 /* D[M][Nc] (f32, ldd) = A[M][K] . B[Nc][K]^T with bf16 operands (K contiguous, K % 64 == 0) and f32 accumulation: the
  * GEMM under avd_learn_shared_bf16, exposed for parity tests. A and B must be readable up to the next multiple of 256
  * rows. */
