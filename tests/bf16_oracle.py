@@ -1,0 +1,331 @@
+"""A bf16-operand restatement of oracle/mlp.py's learn(), the tile-mask cases of the shared-set learner (csrc/wide.hip) and the
+acceptance rule that tests/test_gpu_wide_tiles.py holds the kernels to (TEST INFRASTRUCTURE, CPU only, no GPU and no library call
+beyond the layout).
+
+learn() below is oracle/mlp.py's learn() with one change: every matrix product goes through ``mm(x, w) = rnd(x) @ rnd(w)``. With
+``rnd = round_bf16`` both operands of every product are rounded to bf16 (round to nearest even) and everything else -- the
+accumulation, the biases, the BN tables, relu, tanh, the column sums -- stays float64: what a correct implementation on bf16 matrix
+cores with ideal accumulation computes, up to WHERE it places its roundings. With ``rnd = identity`` it is oracle/mlp.py bit for
+bit (tests/test_bf16_oracle_cpu.py). ``dq_scale`` / ``da_scale`` multiply the critic's loss seed / the action gradient row by row:
+the handle the self-checks use to build a wrong result (a tile whose gradient is missing).
+
+The acceptance rule (tolerances()): for tensor X over the masks of one case and tile size,
+    scale  = max over the masks of max |ref_X|                       (free of one tile's cancellation: cb3, ab3 are one element)
+    e_bf16 = max over the masks of max |bf16oracle_X - ref_X| / scale
+    pass  <=>  max |got_X - ref_X| / scale <= max(FLOOR, FACTOR * e_bf16)   on every mask
+FLOOR = 1e-4 is the f32 accumulation-order floor (tests/test_gpu_mlp.py GRAD_TOL), FACTOR = 4 the margin for "the error a correct
+lower-precision implementation makes" (tests/test_gpu_mlp.py:112) -- a different placement of the roundings, another summation
+order. Nothing measured from a kernel enters it. CAP: a tolerance above 0.5 would pass a wholly wrong tile (error O(1)); the CPU
+suite asserts that no compared tensor of any case reaches it."""
+import functools
+from collections import namedtuple
+
+import numpy as np
+
+from oracle import mlp as omlp
+
+NAMES = ["cWs", "cbs", "cWa", "cba", "cgs", "cbes", "cga", "cbea", "cW2", "cb2", "cg3", "cbe3", "cW3", "cb3",
+         "aW1", "ab1", "ag1", "abe1", "aW2", "ab2", "ag2", "abe2", "aW3", "ab3"]
+HEADS = ("aW3", "ab3", "ag2", "abe2", "cW3", "cb3", "cg3", "cbe3")
+FLOOR, FACTOR, CAP = 1e-4, 4.0, 0.5
+
+
+def identity(x):
+    return x
+
+
+def round_bf16(x):
+    """x -> float32 -> bf16 (round to nearest, ties to even; subnormals kept, inf/nan kept), returned in x's dtype."""
+    x = np.asarray(x)
+    f = np.ascontiguousarray(x, dtype=np.float32)
+    b = f.view(np.uint32)
+    r = ((b + (np.uint32(0x7FFF) + ((b >> np.uint32(16)) & np.uint32(1)))) & np.uint32(0xFFFF0000)).view(np.float32)
+    r = np.where(np.isfinite(f), r, f)
+    return r.astype(x.dtype if x.dtype.kind == "f" else np.float32)
+
+
+# ---- oracle/mlp.py's forward / backward / learn with the product as a parameter -------------------------------------------------
+def _layer2(p, inv, sh, W2, b2, mm, fold):
+    """Second layer on the first layer's BN output p * inv + sh. fold: as csrc/wide.hip places it (prep_w2_kernel, bias2_kernel) --
+    inv folded into W2 BEFORE the rounding, the relu'd p as the other operand, sh . W2 in the (unrounded) bias."""
+    if fold:
+        return mm(p, inv[:, None] * W2) + (b2 + sh @ W2)
+    return mm(p * inv + sh, W2) + b2
+
+
+def actor_forward(w, s, high, mm, fold=False):
+    W1, b1, g1, be1, mm1, mv1, W2, b2, g2, be2, mm2, mv2, W3, b3 = w
+    dt = W1.dtype.type
+    s = np.asarray(s, dtype=W1.dtype)
+    p1 = np.maximum(mm(s, W1) + b1, 0)
+    i1, sh1 = omlp._bn_coeffs(g1, be1, mm1, mv1)
+    y1 = p1 * i1 + sh1
+    p2 = np.maximum(_layer2(p1, i1, sh1, W2, b2, mm, fold), 0)
+    i2, sh2 = omlp._bn_coeffs(g2, be2, mm2, mv2)
+    y2 = p2 * i2 + sh2
+    t = np.tanh(mm(y2, W3) + b3)
+    return t * dt(high), (s, p1, y1, p2, y2, t)
+
+
+def critic_forward(w, s, a, mm, fold=False):
+    Ws, bs, Wa, ba, gs, bes, mms, mvs, ga, bea, mma, mva, W2, b2, g3, be3, mm3, mv3, W3, b3 = w
+    s = np.asarray(s, dtype=Ws.dtype)
+    a = np.asarray(a, dtype=Ws.dtype)
+    ps = np.maximum(mm(s, Ws) + bs, 0)
+    is_, shs = omlp._bn_coeffs(gs, bes, mms, mvs)
+    ys = ps * is_ + shs
+    pa = np.maximum(mm(a, Wa) + ba, 0)
+    ia, sha = omlp._bn_coeffs(ga, bea, mma, mva)
+    ya = pa * ia + sha
+    c = np.concatenate([ys, ya], axis=1)
+    p2 = np.maximum(_layer2(np.concatenate([ps, pa], axis=1), np.concatenate([is_, ia]), np.concatenate([shs, sha]), W2, b2, mm, fold)
+                    if fold else mm(c, W2) + b2, 0)
+    i3, sh3 = omlp._bn_coeffs(g3, be3, mm3, mv3)
+    y2 = p2 * i3 + sh3
+    return mm(y2, W3) + b3, (s, a, ps, pa, c, p2, y2)
+
+
+def critic_backward(w, cache, dq, mm, need_params=True):
+    Ws, bs, Wa, ba, gs, bes, mms, mvs, ga, bea, mma, mva, W2, b2, g3, be3, mm3, mv3, W3, b3 = w
+    s, a, ps, pa, c, p2, y2 = cache
+    h1 = Ws.shape[1]
+    dW3 = mm(y2.T, dq)
+    db3 = dq.sum(axis=0)
+    dy2 = mm(dq, W3.T)
+    dg3, dbe3, dz2 = omlp._bn_backward(dy2, p2, g3, mm3, mv3)
+    dW2 = mm(c.T, dz2)
+    db2 = dz2.sum(axis=0)
+    dc = mm(dz2, W2.T)
+    dga, dbea, dza = omlp._bn_backward(dc[:, h1:], pa, ga, mma, mva)
+    dWa = mm(a.T, dza)
+    dba = dza.sum(axis=0)
+    da = mm(dza, Wa.T)
+    if not need_params:
+        return None, da
+    dgs, dbes, dzs = omlp._bn_backward(dc[:, :h1], ps, gs, mms, mvs)
+    dWs = mm(s.T, dzs)
+    dbs = dzs.sum(axis=0)
+    return [dWs, dbs, dWa, dba, dgs, dbes, dga, dbea, dW2, db2, dg3, dbe3, dW3, db3], da
+
+
+def actor_backward(w, cache, dout, high, mm):
+    W1, b1, g1, be1, mm1, mv1, W2, b2, g2, be2, mm2, mv2, W3, b3 = w
+    dt = W1.dtype.type
+    s, p1, y1, p2, y2, t = cache
+    dz3 = dout * dt(high) * (dt(1) - t * t)
+    dW3 = mm(y2.T, dz3)
+    db3 = dz3.sum(axis=0)
+    dy2 = mm(dz3, W3.T)
+    dg2, dbe2, dz2 = omlp._bn_backward(dy2, p2, g2, mm2, mv2)
+    dW2 = mm(y1.T, dz2)
+    db2 = dz2.sum(axis=0)
+    dy1 = mm(dz2, W2.T)
+    dg1, dbe1, dz1 = omlp._bn_backward(dy1, p1, g1, mm1, mv1)
+    dW1 = mm(s.T, dz1)
+    db1 = dz1.sum(axis=0)
+    return [dW1, db1, dg1, dbe1, dW2, db2, dg2, dbe2, dW3, db3]
+
+
+def _action_gradient(critic, cache, dq1, rnd, placement):
+    """d q(s, mu) / d mu as csrc/wide.hip's forward kernels form it (one action, tools/dual_emul.py): from the EXACT relu mask of the
+    second layer and cf = inv3 W3, never through a rounded gradient matrix --
+      dual  (fw::fwd_gen_kernel<true, 4>): E = (mask . bf16(cf)) @ bf16(inv_a W2[action rows])^T, da = d sum_f pos Wa E
+      delta (fw::fwd_delta_kernel):        E = mask @ bf16(cf W2[action rows])^T,                 da = d sum_f pos (inv_a Wa) E"""
+    Ws, bs, Wa, ba, gs, bes, mms, mvs, ga, bea, mma, mva, W2, b2, g3, be3, mm3, mv3, W3, b3 = critic
+    s, a, ps, pa, c, p2, y2 = cache
+    ia, _ = omlp._bn_coeffs(ga, bea, mma, mva)
+    i3, _ = omlp._bn_coeffs(g3, be3, mm3, mv3)
+    assert W3.shape[1] == 1 and Wa.shape[0] == 1
+    cf, mask, pos, W2a = i3 * W3[:, 0], (p2 > 0).astype(p2.dtype), (pa > 0).astype(pa.dtype), W2[Ws.shape[1]:]
+    if placement == "dual":
+        E = (mask * rnd(cf)[None, :]) @ rnd(ia[:, None] * W2a).T
+        return dq1 * (pos * Wa[0][None, :] * E).sum(axis=1, keepdims=True)
+    E = mask @ rnd(cf[None, :] * W2a).T
+    return dq1 * (pos * (ia * Wa[0])[None, :] * E).sum(axis=1, keepdims=True)
+
+
+def learn(batch, actor, critic, t_actor, t_critic, gamma=0.99, high=2.5, rnd=round_bf16, dq_scale=None, da_scale=None,
+          placement="generic"):
+    """oracle/mlp.py learn() with mm(x, w) = rnd(x) @ rnd(w). dq_scale / da_scale [rows, 1]: factors on the critic's loss seed /
+    on the action gradient the actor's backward pass starts from (None: untouched).
+    placement: "generic" -- both operands of every ``@`` of oracle/mlp.py as written; "dual" / "delta" -- two roundings moved to where
+    csrc/wide.hip documents them: the BN scale folded into W2 before rounding in every forward pass (_layer2), and the critic's
+    action gradient in the named kernel's form (_action_gradient). Everything else stays generic."""
+    assert placement in ("generic", "dual", "delta")
+    fold = placement != "generic"
+    mm = lambda x, w: np.matmul(rnd(x), rnd(w))
+    s, a, r, s2 = batch
+    dtype = actor[0].dtype
+    dt = dtype.type
+    s, a, s2 = (np.asarray(v, dtype=dtype) for v in (s, a, s2))
+    r = np.asarray(r, dtype=dtype).reshape(len(s), -1)
+    ta, _ = actor_forward(t_actor, s2, high, mm, fold)
+    y = r + dt(gamma) * critic_forward(t_critic, s2, ta, mm, fold)[0]
+    q, cc = critic_forward(critic, s, a, mm, fold)
+    n = dt(q.size)
+    critic_loss = np.mean(np.square(y - q))
+    dq = (dt(2) * (q - y) / n).astype(dtype)
+    if dq_scale is not None:
+        dq = dq * dq_scale
+    critic_grad, _ = critic_backward(critic, cc, dq, mm)
+    a1, ac = actor_forward(actor, s, high, mm, fold)
+    q1, cc1 = critic_forward(critic, s, a1, mm, fold)
+    actor_loss = -np.mean(q1)
+    dq1 = np.full_like(q1, dt(-1) / dt(q1.size))
+    if fold:
+        da = _action_gradient(critic, cc1, dq1, rnd, placement)
+    else:
+        _, da = critic_backward(critic, cc1, dq1, mm, need_params=False)
+    if da_scale is not None:
+        da = da * da_scale
+    actor_grad = actor_backward(actor, ac, da, high, mm)
+    return critic_grad, actor_grad, dict(critic_loss=critic_loss, actor_loss=actor_loss, y=y, q=q, q1=q1, a1=a1)
+
+
+# ---- the acceptance rule --------------------------------------------------------------------------------------------------------
+def tolerances(refs, emus):
+    """refs, emus: one {name: array} per mask of ONE case and tile size -> {name: (scale, e_bf16, tol)}."""
+    out = {}
+    for name in NAMES:
+        scale = max(max(np.max(np.abs(r[name])) for r in refs), 1e-300)
+        e = max(np.max(np.abs(m[name] - r[name])) for r, m in zip(refs, emus)) / scale
+        out[name] = (scale, e, max(FLOOR, FACTOR * e))
+    return out
+
+
+def violations(got, ref, tol, skip=()):
+    """[(name, error / scale, tolerance)] of the tensors of one mask's result that miss the rule."""
+    bad = []
+    for name in NAMES:
+        if name in skip:
+            continue
+        scale, _, limit = tol[name]
+        err = np.max(np.abs(np.asarray(got[name], np.float64) - ref[name])) / scale
+        if not err <= limit:
+            bad.append((name, float(err), float(limit)))
+    return bad
+
+
+# ---- the cases: shapes from the path conditions of avd_learn_shared_bf16 (csrc/wide.hip, "fused_fwd" ... "act_in_dx") -----------
+Case = namedtuple("Case", "name widths S rows seed path drop32 placement")
+N_SETS, CHECK_SET = 2, 1  # two weight sets (the set stride is exercised); the oracles are computed for the second
+CASES = [
+    # fused forward, rank-one backward, critic(s, a) and critic(s, mu) in one pass (dual), fw::dx_gen_kernel<true> (H1 / 256 == 4)
+    Case("h1024", (1024, 1024, 48), 4, 4096, 12, "fused fwd + rank-one bwd + dual + dx_gen<true>", (), "dual"),
+    # rank-one backward with fw::dx_gen_kernel<false>, two state feature blocks (H1 = 512) ...
+    Case("h512", (512, 512, 48), 4, 1024, 12, "fused fwd + rank-one bwd + dual + dx_gen<false>, 2 feature blocks", (), "dual"),
+    # ... and one (H1 = 256)
+    Case("h256x512", (256, 512, 48), 4, 1024, 13, "fused fwd + rank-one bwd + dual + dx_gen<false>, 1 feature block", (), "dual"),
+    # H1 = 128 is no multiple of 256: no rank-one chain -- fused forward (stored activations), fw::fwd_delta_kernel, backward layer-wise
+    Case("h128x512", (128, 512, 32), 4, 1024, 14, "fused fwd + fwd_delta, layer-wise bwd", (), "delta"),
+    # H2 = 128 is no multiple of fw::FC and S = 3: nothing fused
+    Case("h256x128_S3", (256, 128, 48), 3, 1024, 15, "everything layer-wise", (), "generic"),
+    # 960 rows pad to 1024: the padding rows add nothing
+    Case("h1024_pad", (1024, 1024, 48), 4, 960, 20, "as h1024, Ns = 960 < Np = 1024", (), "dual"),
+]
+CASE = {c.name: c for c in CASES}
+
+
+def masks(case):
+    """[(label, tile size t, lo, hi)]: rows [lo, hi) carry weight 1, all others 0; hi is clipped to the set's rows."""
+    rows, out = case.rows, []
+    n256 = (rows + 255) // 256
+    for i in range(n256):
+        out.append((f"t256[{i}]", 256, 256 * i, min(256 * i + 256, rows)))
+    if case.name == "h1024":  # the eight sub-tiles of tile 5, one in each of three others -- the first and the last rows of the set
+        subs = [(5, j) for j in range(8)] + [(0, 0), (10, 3), (15, 7)]
+    elif case.name == "h1024_pad":  # the last 32-row sub-tile that still holds rows
+        subs = [(3, 5)]
+    else:  # one sub-tile per 256-row tile, the first and the last rows of the set among them
+        subs = [(0, 0), (1, 3), (2, 5), (3, 7)]
+    for i, j in subs:
+        lo = 256 * i + 32 * j
+        out.append((f"t32[{i}.{j}]", 32, lo, lo + 32))
+    assert all(0 <= lo < hi <= rows for _, _, lo, hi in out)
+    out.append(("whole", rows, 0, rows))
+    return out
+
+
+def case_conf_kw(case):
+    H1, H2, Ha = case.widths
+    return dict(actor_layer1_size=H1, actor_layer2_size=H2, critic_layer1_size=H1, critic_layer2_size=H2, critic_act_layer_size=Ha)
+
+
+def case_batch(case):
+    """(s, a, r, s2) of N_SETS sets, as tests/test_gpu_wide.py draws them."""
+    rs = np.random.RandomState(case.seed + 1000)
+    n, rows, S = N_SETS, case.rows, case.S
+    s = rs.normal(0, 1.5, size=(n, rows, S)).astype(np.float32)
+    a = rs.uniform(-2.5, 2.5, size=(n, rows, 1)).astype(np.float32)
+    r = -np.abs(rs.normal(0, 0.3, size=(n, rows))).astype(np.float32)
+    s2 = rs.normal(0, 1.5, size=(n, rows, S)).astype(np.float32)
+    return s, a, r, s2
+
+
+def perturbed_slabs(n_sets, S, seed, **confkw):
+    """The host half of tests/test_gpu_mlp.py _perturbed_group: (group on the CPU device, theta, stats, theta_t, stats_t) with the
+    same draws (the GPU tests assert that the two agree bit for bit)."""
+    from avddpg_amd import config, params, vec
+
+    conf = config.Config(**confkw)
+    grp = vec.AgentGroup(n_sets, S, 1, conf, seed=seed, device="cpu")
+    lay, dims = grp.lay, grp.dims
+    rs = np.random.RandomState(seed + 100)
+    th = np.zeros((n_sets, lay.theta_size), np.float32)
+    st = np.zeros((n_sets, lay.stats_size), np.float32)
+    tht, stt = th.copy(), st.copy()
+    for dst_th, dst_st in ((th, st), (tht, stt)):
+        for k in range(n_sets):
+            a, s_ = params.init_weights(lay, rs, dims=dims)
+            aw = params.unpack(lay, a, s_, "actor", dims=dims)
+            cw = params.unpack(lay, a, s_, "critic", dims=dims)
+            for net, var_idx in ((aw, (5, 11)), (cw, (7, 11, 17))):
+                for w in net:
+                    if w.ndim == 1:
+                        w += rs.uniform(-0.3, 0.3, w.shape).astype(np.float32)
+                for i in var_idx:
+                    net[i][:] = np.abs(net[i]) + 0.5
+            aw[12] *= 30
+            cw[18] *= 300
+            params.pack(lay, aw, dst_th[k], dst_st[k], "actor", dims=dims)
+            params.pack(lay, cw, dst_th[k], dst_st[k], "critic", dims=dims)
+    return grp, th, st, tht, stt
+
+
+def case_nets(case, k=CHECK_SET):
+    """(actor, critic, target actor, target critic) of set k in float64, Keras weight order."""
+    from avddpg_amd import params
+
+    grp, th, st, tht, stt = perturbed_slabs(N_SETS, case.S, case.seed, **case_conf_kw(case))
+    c = lambda ws: [w.astype(np.float64) for w in ws]
+    return (c(params.unpack(grp.lay, th[k], st[k], "actor", dims=grp.dims)), c(params.unpack(grp.lay, th[k], st[k], "critic", dims=grp.dims)),
+            c(params.unpack(grp.lay, tht[k], stt[k], "actor", dims=grp.dims)), c(params.unpack(grp.lay, tht[k], stt[k], "critic", dims=grp.dims)))
+
+
+def tile_learn(case, nets, batch, lo, hi, rnd, **kw):
+    """{name: Nt / Ns x learn(rows [lo, hi) of CHECK_SET)}: what learn_shared returns for weight 1 on those rows, 0 elsewhere."""
+    s, a, r, s2 = batch
+    k = CHECK_SET
+    cg, ag, _ = learn((s[k, lo:hi], a[k, lo:hi], r[k, lo:hi, None], s2[k, lo:hi]), *nets, rnd=rnd, **kw)
+    f = (hi - lo) / case.rows
+    return {name: f * g for name, g in zip(NAMES, cg + ag)}
+
+
+@functools.lru_cache(maxsize=None)
+def case_reference(name):
+    """-> (masks, refs, emus, tol): per mask the float64 reference and the bf16-operand oracle of CHECK_SET, and per tile size the
+    pooled tolerance table {t: {tensor: (scale, e_bf16, tol)}}. Cached: every test of a case shares one computation."""
+    case = CASE[name]
+    nets, batch, ms = case_nets(case), case_batch(case), masks(case)
+    refs = [tile_learn(case, nets, batch, lo, hi, identity) for _, _, lo, hi in ms]
+    emus = [tile_learn(case, nets, batch, lo, hi, round_bf16, placement=case.placement) for _, _, lo, hi in ms]
+    tol = {}
+    for t in sorted({m[1] for m in ms}):
+        idx = [i for i, m in enumerate(ms) if m[1] == t]
+        tol[t] = tolerances([refs[i] for i in idx], [emus[i] for i in idx])
+    return ms, refs, emus, tol
+
+
+def skipped(case, t):
+    """Tensors not compared at tile size t (a tolerance at the cap says nothing): listed in CASES, never a head tensor."""
+    return case.drop32 if t == 32 else ()

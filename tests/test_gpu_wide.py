@@ -70,6 +70,7 @@ def test_shared_learner_matches_oracle_on_concatenated_batch(S, P, widths, tol):
             # bf16 GEMM operands (2^-9 relative rounding per element) against the float64 oracle: 2 % of the tensor's max
             # at the reference widths; at BASELINE config 5's hidden = 1024 the first-layer actor gradients sit behind
             # five bf16 GEMMs with 1024-long reductions and only 512 rows to average over here: 8 %
+            # (per tile and tensor, measured against a bf16-operand oracle: docs/wide_tile_parity.md, tests/test_gpu_wide_tiles.py)
             assert _relerr(got, ref) <= tol, (k, name, _relerr(got, ref))
         lo = losses[k].cpu().numpy()
         assert abs(lo[0] - aux["critic_loss"]) <= 1e-2 * abs(aux["critic_loss"])
