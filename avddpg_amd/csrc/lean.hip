@@ -790,10 +790,8 @@ __global__ __launch_bounds__(FT, 2) void learn_kernel_l(avd_mlp_layout L_arg, in
         PH(it == 1 ? 7 : (it == 2 ? 12 : 15));
         if (wg) {
             col_sums(bDZ, LDB, H2, l.db, gout + (crit ? L.cb2 : L.ab2), sink);
-            if constexpr (FUSED) {  // lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t), as adam_polyak_kernel (optim.hip) computes it
-                const int t = upd.step[agent];
-                const float b1p = (float)pow((double)0.9f, (double)t), b2p = (float)pow((double)0.999f, (double)t);
-                const float root = sqrtf(1.0f - b2p);
+            if constexpr (FUSED) {  // the step sizes of this iteration (adam.h), as adam_polyak_kernel (optim.hip) computes them
+                const AdamBias ab = adam_bias(upd.step[agent]);
                 if constexpr (HP) {  // (tau / 1 - tau as well: the W2 epilogues of this pass and the small tensors' update read them)
                     const avd_hparams& h = hp_of(agent, hp...);
                     upd.actor_lr = h.actor_lr, upd.critic_lr = h.critic_lr;
@@ -801,10 +799,8 @@ __global__ __launch_bounds__(FT, 2) void learn_kernel_l(avd_mlp_layout L_arg, in
                 }
                 // wave-uniform values computed on the vector unit: moved to SGPRs so that they cost no vector register for
                 // the rest of the kernel
-                bulk.alpha_a = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(
-                    __builtin_bit_cast(int, (upd.actor_lr * root) / (1.0f - b1p))));
-                bulk.alpha_c = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(
-                    __builtin_bit_cast(int, (upd.critic_lr * root) / (1.0f - b1p))));
+                bulk.alpha_a = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, ab.alpha(upd.actor_lr))));
+                bulk.alpha_c = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, ab.alpha(upd.critic_lr))));
             }
             lds_barrier();
             PH(it == 1 ? 8 : 16);
@@ -857,10 +853,8 @@ __global__ __launch_bounds__(FT, 2) void learn_kernel_l(avd_mlp_layout L_arg, in
             f32x4 w = wi4[i], wt = wt4[i], mm = m4[i], vv = v4[i];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                mm[k] = mm[k] + (gg[k] - mm[k]) * (1.0f - 0.9f);
-                vv[k] = vv[k] + (gg[k] * gg[k] - vv[k]) * (1.0f - 0.999f);
-                w[k] = w[k] - (mm[k] * alpha) / (sqrtf(vv[k]) + 1e-7f);
-                wt[k] = w[k] * bulk.tau + wt[k] * bulk.omt;
+                const AdamElem o = adam_polyak_step(w[k], wt[k], mm[k], vv[k], gg[k], alpha, bulk.tau, bulk.omt);
+                mm[k] = o.m, vv[k] = o.v, w[k] = o.w, wt[k] = o.wt;  // (in this order: it decides what the vectoriser packs)
             }
             wo4[i] = w, wt4[i] = wt, m4[i] = mm, v4[i] = vv;
         }

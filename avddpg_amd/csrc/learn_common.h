@@ -6,6 +6,7 @@
 
 #include <type_traits>
 
+#include "adam.h"
 #include "common.h"
 
 namespace avd {
@@ -82,17 +83,13 @@ struct AdamSink {
     float *wt, *m, *v;
     float alpha_a, alpha_c, tau, omt;
     int actor_size;
+    // every form below: adam_polyak_step (adam.h), the element step adam_polyak_kernel (optim.hip) applies
     __device__ __forceinline__ void put(float* p, float g) const {
-#pragma clang fp contract(off)
         const long off = p - wo;
-        const float alpha = off < actor_size ? alpha_a : alpha_c;
-        float mm = m[off], vv = v[off];
-        mm = mm + (g - mm) * (1.0f - 0.9f);          // TF ApplyAdam, identical to adam_polyak_kernel (optim.hip)
-        vv = vv + (g * g - vv) * (1.0f - 0.999f);
-        const float w = wi[off] - (mm * alpha) / (sqrtf(vv) + 1e-7f);
-        m[off] = mm, v[off] = vv;
-        *p = w;
-        wt[off] = w * tau + wt[off] * omt;  // update_target on the freshly updated weight
+        const AdamElem o = adam_polyak_step(wi[off], wt[off], m[off], v[off], g, off < actor_size ? alpha_a : alpha_c, tau, omt);
+        m[off] = o.m, v[off] = o.v;
+        *p = o.w;
+        wt[off] = o.wt;
     }
     // Two-phase form for bulk gradients (weight-gradient GEMM epilogues): all operand loads of a block are issued
     // first (load2), the arithmetic and the stores follow (update2) -- one memory round trip per block, not per element.
@@ -105,7 +102,6 @@ struct AdamSink {
         q.w[0] = a.x, q.w[1] = a.y, q.t[0] = b.x, q.t[1] = b.y, q.m[0] = c.x, q.m[1] = c.y, q.v[0] = d.x, q.v[1] = d.y;
     }
     __device__ __forceinline__ void update2(const Quad& q, long off, const float (&g)[2]) const {
-#pragma clang fp contract(off)
         const float alpha = off < actor_size ? alpha_a : alpha_c;
         float2 ow, ot, om, ov;
         float* pw = &ow.x;
@@ -114,11 +110,8 @@ struct AdamSink {
         float* pv = &ov.x;
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-            const float mm = q.m[e] + (g[e] - q.m[e]) * (1.0f - 0.9f);
-            const float vv = q.v[e] + (g[e] * g[e] - q.v[e]) * (1.0f - 0.999f);
-            // exact div/sqrt: approximate rcp/sqrt measured no faster (the epilogue is bound by per-CU memory throughput)
-            const float w = q.w[e] - (mm * alpha) / (sqrtf(vv) + 1e-7f);
-            pm[e] = mm, pv[e] = vv, pw[e] = w, pt[e] = w * tau + q.t[e] * omt;
+            const AdamElem o = adam_polyak_step(q.w[e], q.t[e], q.m[e], q.v[e], g[e], alpha, tau, omt);
+            pm[e] = o.m, pv[e] = o.v, pw[e] = o.w, pt[e] = o.wt;
         }
         *(float2*)(wo + off) = ow;
         *(float2*)(wt + off) = ot;
@@ -134,20 +127,7 @@ struct AdamSink {
         q.m = *(const f32x4*)(m + off), q.v = *(const f32x4*)(v + off);
     }
     __device__ __forceinline__ void update4(const Quad4& q, long off, const float (&g)[4]) const {
-#pragma clang fp contract(off)
-        const float alpha = off < actor_size ? alpha_a : alpha_c;
-        f32x4 ow, ot, om, ov;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float mm = q.m[e] + (g[e] - q.m[e]) * (1.0f - 0.9f);
-            const float vv = q.v[e] + (g[e] * g[e] - q.v[e]) * (1.0f - 0.999f);
-            const float w = q.w[e] - (mm * alpha) / (sqrtf(vv) + 1e-7f);
-            om[e] = mm, ov[e] = vv, ow[e] = w, ot[e] = w * tau + q.t[e] * omt;
-        }
-        *(f32x4*)(wo + off) = ow;
-        *(f32x4*)(wt + off) = ot;
-        *(f32x4*)(m + off) = om;
-        *(f32x4*)(v + off) = ov;
+        update4p(q, off < actor_size ? alpha_a : alpha_c, wo + off, wt + off, m + off, v + off, g);
     }
     // Pointer form (lean.hip): the caller passes uniform base + per-lane u32 offset addresses, one per array.
     __device__ __forceinline__ static void load4p(Quad4& q, const float* pw, const float* pt, const float* pm, const float* pv) {
@@ -155,14 +135,11 @@ struct AdamSink {
     }
     __device__ __forceinline__ void update4p(const Quad4& q, float alpha, float* pwo, float* pt, float* pm, float* pv,
                                              const float (&g)[4]) const {
-#pragma clang fp contract(off)
         f32x4 ow, ot, om, ov;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float mm = q.m[e] + (g[e] - q.m[e]) * (1.0f - 0.9f);
-            const float vv = q.v[e] + (g[e] * g[e] - q.v[e]) * (1.0f - 0.999f);
-            const float w = q.w[e] - (mm * alpha) / (sqrtf(vv) + 1e-7f);
-            om[e] = mm, ov[e] = vv, ow[e] = w, ot[e] = w * tau + q.t[e] * omt;
+            const AdamElem o = adam_polyak_step(q.w[e], q.t[e], q.m[e], q.v[e], g[e], alpha, tau, omt);
+            om[e] = o.m, ov[e] = o.v, ow[e] = o.w, ot[e] = o.wt;
         }
         *(f32x4*)pwo = ow;
         *(f32x4*)pt = ot;

@@ -321,13 +321,11 @@ __global__ __launch_bounds__(NTHREADS) void learn_kernel_g(avd_mlp_layout L, int
     BulkSink bulk;
     float* gw2 = ga;  // where gemm_dw "stores": the gradient slab, or the agent's slab of theta_out
     if constexpr (FUSED) {
-        const int t = upd.step[agent];
-        const float b1p = (float)pow((double)0.9f, (double)t), b2p = (float)pow((double)0.999f, (double)t);
-        const float root = sqrtf(1.0f - b2p);
+        const AdamAlphas al = adam_alphas(upd.actor_lr, upd.critic_lr, upd.step[agent]);
         const long o = (long)agent * L.theta_size;
         gw2 = upd.theta_out + o;
         bulk.wo = gw2, bulk.wi = net.th, bulk.wt = theta_t + o, bulk.m = upd.m + o, bulk.v = upd.v + o;
-        bulk.alpha_a = (upd.actor_lr * root) / (1.0f - b1p), bulk.alpha_c = (upd.critic_lr * root) / (1.0f - b1p);
+        bulk.alpha_a = al.a, bulk.alpha_c = al.c;
         bulk.tau = upd.tau, bulk.omt = upd.omt, bulk.actor_size = L.actor_size;
     }
 
@@ -1098,13 +1096,11 @@ __global__ __launch_bounds__(FT) void learn_kernel_t(avd_mlp_layout L, int set_m
     BulkSink bulk;
     float* gw2 = g;  // where gemm_dw "stores": the gradient slab, or the agent's slab of theta_out
     if constexpr (FUSED) {
-        const int t = upd.step[agent];
-        const float b1p = (float)pow((double)0.9f, (double)t), b2p = (float)pow((double)0.999f, (double)t);
-        const float root = sqrtf(1.0f - b2p);
+        const AdamAlphas al = adam_alphas(upd.actor_lr, upd.critic_lr, upd.step[agent]);
         const long o = (long)agent * L.theta_size;
         gw2 = upd.theta_out + o;
         bulk.wo = gw2, bulk.wi = net.th, bulk.wt = theta_t + o, bulk.m = upd.m + o, bulk.v = upd.v + o;
-        bulk.alpha_a = (upd.actor_lr * root) / (1.0f - b1p), bulk.alpha_c = (upd.critic_lr * root) / (1.0f - b1p);
+        bulk.alpha_a = al.a, bulk.alpha_c = al.c;
         bulk.tau = upd.tau, bulk.omt = upd.omt, bulk.actor_size = L.actor_size;
     }
     constexpr float invn = 1.0f / (float)TILE;  // A == 1

@@ -2,14 +2,28 @@
 //
 // All of these are elementwise, HBM-bound streams over flat float32 slabs (16-byte accesses,
 // grid-stride).  Adam follows TF 2.4.1's ApplyAdam functor exactly and is compiled without FMA
-// contraction so the result is bit-identical to the float32 oracle (oracle/mlp.py:adam_update).
+// contraction so the result is bit-identical to the float32 oracle (oracle/mlp.py:adam_update):
+// the element step and the bias-corrected step sizes are adam.h's, shared with the fused learn kernels.
 #include <stdlib.h>
 
+#include "adam.h"
 #include "common.h"
 
 namespace avd {
 
-constexpr float ADAM_B1 = 0.9f, ADAM_B2 = 0.999f, ADAM_EPS = 1e-7f;
+// adam_polyak_step (adam.h) on one float4 group of the four arrays; g: the group's four gradients
+__device__ __forceinline__ void adam_polyak_step4(float4& w, float4& wt, float4& m, float4& v, const float* g, float alpha, float tau,
+                                                  float omt) {
+    float* wp = &w.x;
+    float* tp = &wt.x;
+    float* mp = &m.x;
+    float* vp = &v.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const AdamElem o = adam_polyak_step(wp[k], tp[k], mp[k], vp[k], g[k], alpha, tau, omt);
+        wp[k] = o.w, tp[k] = o.wt, mp[k] = o.m, vp[k] = o.v;
+    }
+}
 
 // A set whose gradient slab is not finite at the head of its actor block or of its critic block (the set learners of fset.hip /
 // fsplit.hip turn a non-finite input or an fp16 overflow into an ALL-NaN block: finalize_*) -- the guarded update leaves such a set
@@ -32,7 +46,6 @@ __global__ __launch_bounds__(256) void adam_polyak_kernel(int theta_size, int ac
                                                           int32_t* __restrict__ step, float actor_lr,
                                                           float critic_lr, float tau, float omt, int32_t* __restrict__ skipped,
                                                           H... hp) {
-#pragma clang fp contract(off)
     const int set = blockIdx.y;
     if constexpr (HP) {
         const avd_hparams& h = hp_of(set, hp...);
@@ -46,30 +59,14 @@ __global__ __launch_bounds__(256) void adam_polyak_kernel(int theta_size, int ac
         }
         return;
     }
-    // beta^t as float32(pow) like the oracle / TF (math_ops.pow on float32 scalars)
-    const float b1p = (float)pow((double)ADAM_B1, (double)t);
-    const float b2p = (float)pow((double)ADAM_B2, (double)t);
-    const float root = sqrtf(1.0f - b2p);
-    const float alpha_a = (actor_lr * root) / (1.0f - b1p);
-    const float alpha_c = (critic_lr * root) / (1.0f - b1p);
+    const AdamAlphas al = adam_alphas(actor_lr, critic_lr, t);
     const int n4 = theta_size / 4;
     const long base = (long)set * n4;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
-        const float alpha = (i * 4 < actor_size) ? alpha_a : alpha_c;  // blocks are 4-float aligned
+        const float alpha = (i * 4 < actor_size) ? al.a : al.c;  // blocks are 4-float aligned
         float4 w = theta[base + i], wt = theta_t[base + i], mm = m[base + i], vv = v[base + i];
         const float4 g = grads[base + i];
-        float* wp = &w.x;
-        float* tp = &wt.x;
-        float* mp = &mm.x;
-        float* vp = &vv.x;
-        const float* gp = &g.x;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            mp[k] = mp[k] + (gp[k] - mp[k]) * (1.0f - ADAM_B1);
-            vp[k] = vp[k] + (gp[k] * gp[k] - vp[k]) * (1.0f - ADAM_B2);
-            wp[k] = wp[k] - (mp[k] * alpha) / (sqrtf(vp[k]) + ADAM_EPS);
-            tp[k] = wp[k] * tau + tp[k] * omt;  // update_target on the freshly updated weight
-        }
+        adam_polyak_step4(w, wt, mm, vv, &g.x, alpha, tau, omt);
         theta[base + i] = w;
         theta_t[base + i] = wt;
         m[base + i] = mm;
@@ -89,34 +86,17 @@ __global__ __launch_bounds__(256) void adam_polyak_ranges_kernel(int theta_size,
                                                                  const int32_t* __restrict__ step, float actor_lr,
                                                                  float critic_lr, float tau, float omt, int a0, int a1,
                                                                  int c0, int c1) {
-#pragma clang fp contract(off)
     const int set = blockIdx.y;
-    const int t = step[set];
-    const float b1p = (float)pow((double)ADAM_B1, (double)t);
-    const float b2p = (float)pow((double)ADAM_B2, (double)t);
-    const float root = sqrtf(1.0f - b2p);
-    const float alpha_a = (actor_lr * root) / (1.0f - b1p);
-    const float alpha_c = (critic_lr * root) / (1.0f - b1p);
+    const AdamAlphas al = adam_alphas(actor_lr, critic_lr, step[set]);
     // compact index over the kept float4 groups: [0,a0) [a1,c0) [c1,theta_size)
     const int n0 = a0 / 4, n1 = (c0 - a1) / 4, n2 = (theta_size - c1) / 4;
     const long base = (long)set * (theta_size / 4);
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n0 + n1 + n2; j += gridDim.x * blockDim.x) {
         const int i = j < n0 ? j : (j < n0 + n1 ? a1 / 4 + (j - n0) : c1 / 4 + (j - n0 - n1));
-        const float alpha = (i * 4 < actor_size) ? alpha_a : alpha_c;
+        const float alpha = (i * 4 < actor_size) ? al.a : al.c;
         float4 w = theta_in[base + i], wt = theta_t[base + i], mm = m[base + i], vv = v[base + i];
         const float4 g = grads[base + i];
-        float* wp = &w.x;
-        float* tp = &wt.x;
-        float* mp = &mm.x;
-        float* vp = &vv.x;
-        const float* gp = &g.x;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            mp[k] = mp[k] + (gp[k] - mp[k]) * (1.0f - ADAM_B1);
-            vp[k] = vp[k] + (gp[k] * gp[k] - vp[k]) * (1.0f - ADAM_B2);
-            wp[k] = wp[k] - (mp[k] * alpha) / (sqrtf(vp[k]) + ADAM_EPS);
-            tp[k] = wp[k] * tau + tp[k] * omt;
-        }
+        adam_polyak_step4(w, wt, mm, vv, &g.x, alpha, tau, omt);
         theta_out[base + i] = w;
         theta_t[base + i] = wt;
         m[base + i] = mm;
@@ -143,15 +123,9 @@ __global__ __launch_bounds__(256) void adam_polyak_rows_kernel(int theta_size, i
                                                                float4* __restrict__ v, const float4* __restrict__ grads,
                                                                const int32_t* __restrict__ step, float actor_lr, float critic_lr,
                                                                float tau, float omt) {
-#pragma clang fp contract(off)
     const int n4 = theta_size / 4;
     for (int set = blockIdx.x; set < n_sets; set += gridDim.x) {
-        const int t = step[set];
-        const float b1p = (float)pow((double)ADAM_B1, (double)t);
-        const float b2p = (float)pow((double)ADAM_B2, (double)t);
-        const float root = sqrtf(1.0f - b2p);
-        const float alpha_a = (actor_lr * root) / (1.0f - b1p);
-        const float alpha_c = (critic_lr * root) / (1.0f - b1p);
+        const AdamAlphas al = adam_alphas(actor_lr, critic_lr, step[set]);
         const long base = (long)set * n4;
         for (int i0 = threadIdx.x; i0 < n4; i0 += 256 * AR_UNR) {
             float4 w[AR_UNR], wt[AR_UNR], mm[AR_UNR], vv[AR_UNR], g[AR_UNR];
@@ -165,19 +139,8 @@ __global__ __launch_bounds__(256) void adam_polyak_rows_kernel(int theta_size, i
             for (int u = 0; u < AR_UNR; ++u) {
                 const int i = i0 + 256 * u;
                 if (i >= n4) break;
-                const float alpha = (i * 4 < actor_size) ? alpha_a : alpha_c;
-                float* wp = &w[u].x;
-                float* tp = &wt[u].x;
-                float* mp = &mm[u].x;
-                float* vp = &vv[u].x;
-                const float* gp = &g[u].x;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    mp[k] = mp[k] + (gp[k] - mp[k]) * (1.0f - ADAM_B1);
-                    vp[k] = vp[k] + (gp[k] * gp[k] - vp[k]) * (1.0f - ADAM_B2);
-                    wp[k] = wp[k] - (mp[k] * alpha) / (sqrtf(vp[k]) + ADAM_EPS);
-                    tp[k] = wp[k] * tau + tp[k] * omt;
-                }
+                const float alpha = (i * 4 < actor_size) ? al.a : al.c;
+                adam_polyak_step4(w[u], wt[u], mm[u], vv[u], &g[u].x, alpha, tau, omt);
                 NTS(w[u], theta_out + base + i), NTS(wt[u], theta_t + base + i), NTS(mm[u], m + base + i), NTS(vv[u], v + base + i);
             }
         }
@@ -206,11 +169,9 @@ __global__ __launch_bounds__(256) void adam_polyak_intra_kernel(int theta_size, 
     const int p = blockIdx.y, n4 = theta_size / 4;
     const long set0 = (long)p * M;
     if (threadIdx.x < M) {
-        const int t = step[set0 + threadIdx.x];
-        const float b1p = (float)pow((double)ADAM_B1, (double)t), b2p = (float)pow((double)ADAM_B2, (double)t);
-        const float root = sqrtf(1.0f - b2p);
-        s_aa[threadIdx.x] = (actor_lr * root) / (1.0f - b1p);
-        s_ac[threadIdx.x] = (critic_lr * root) / (1.0f - b1p);
+        const AdamAlphas al = adam_alphas(actor_lr, critic_lr, step[set0 + threadIdx.x]);
+        s_aa[threadIdx.x] = al.a;
+        s_ac[threadIdx.x] = al.c;
         s_w[threadIdx.x] = weights ? weights[set0 + threadIdx.x] : 1.0f;
     }
     __syncthreads();
@@ -243,17 +204,7 @@ __global__ __launch_bounds__(256) void adam_polyak_intra_kernel(int theta_size, 
             const long o = (set0 + i) * n4 + i4;
             const float alpha = actor ? s_aa[i] : s_ac[i];
             float4 w = theta[o], wt = theta_t[o], mm = m[o], vv = v[o];
-            float* wp = &w.x;
-            float* tp = &wt.x;
-            float* mp = &mm.x;
-            float* vp = &vv.x;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                mp[k] = mp[k] + (gm[k] - mp[k]) * (1.0f - ADAM_B1);
-                vp[k] = vp[k] + (gm[k] * gm[k] - vp[k]) * (1.0f - ADAM_B2);
-                wp[k] = wp[k] - (mp[k] * alpha) / (sqrtf(vp[k]) + ADAM_EPS);
-                tp[k] = wp[k] * tau + tp[k] * omt;
-            }
+            adam_polyak_step4(w, wt, mm, vv, gm, alpha, tau, omt);
             theta[o] = w, theta_t[o] = wt, m[o] = mm, v[o] = vv;
         }
     }
@@ -362,66 +313,6 @@ __global__ void fed_scatter_kernel(int so, int si, int i_begin, int n, const flo
 
 using namespace avd;
 
-static int adam_polyak_launch(const char* who, bool guard, const avd_mlp_layout* lay, int n_sets, float* theta, float* stats, float* theta_t,
-                              float* stats_t, float* m, float* v, const float* grads, int32_t* step, float actor_lr, float critic_lr,
-                              double tau, int32_t* skipped, void* stream) {
-    AVD_REQUIRE(lay && n_sets > 0, "%s: n_sets=%d", who, n_sets);
-    AVD_REQUIRE(theta && stats && theta_t && stats_t && m && v && grads && step, "%s: null pointer", who);
-    AVD_REQUIRE(lay->theta_size % 4 == 0 && lay->actor_size % 4 == 0 && lay->stats_size % 4 == 0, "%s: layout not 4-float aligned", who);
-    const float tauf = (float)tau, omt = (float)(1.0 - tau);  // Python doubles rounded to f32 (ddpgagent.py:47,53)
-    const int n4 = lay->theta_size / 4;
-    int gx = (n4 + 255) / 256;
-    if (n_sets >= 256 && gx > 8) gx = 8;  // many sets: fewer, longer-lived blocks per set
-    if (const char* e = AVD_DIAG_ENV("ADAM_GX")) gx = atoi(e);  // tuning knob (tools/adam_sweep.sh @ tag r06-pre-prune)
-    if (guard)
-        hipLaunchKernelGGL(adam_polyak_kernel<true>, dim3(gx, n_sets), dim3(256), 0, (hipStream_t)stream, lay->theta_size, lay->actor_size,
-                           (float4*)theta, (float4*)theta_t, (float4*)m, (float4*)v, (const float4*)grads, step, actor_lr, critic_lr, tauf,
-                           omt, skipped);
-    else
-        hipLaunchKernelGGL(adam_polyak_kernel<false>, dim3(gx, n_sets), dim3(256), 0, (hipStream_t)stream, lay->theta_size, lay->actor_size,
-                           (float4*)theta, (float4*)theta_t, (float4*)m, (float4*)v, (const float4*)grads, step, actor_lr, critic_lr, tauf,
-                           omt, (int32_t*)nullptr);
-    int rc = check_launch(who);
-    if (rc) return rc;
-    // BN moving stats take part in the soft update too (ddpgagent.py:44-53 iterates .weights)
-    if (guard) {
-        hipLaunchKernelGGL(polyak_guarded_kernel<>, dim3((unsigned)((lay->stats_size + 255) / 256), n_sets), dim3(256), 0, (hipStream_t)stream,
-                           lay->stats_size, stats, stats_t, tauf, omt, grads, lay->theta_size, lay->actor_size);
-        return check_launch(who);
-    }
-    const long ns = (long)n_sets * lay->stats_size;
-    long blocks = (ns + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(polyak_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ns, stats, stats_t,
-                       tauf, omt);
-    return check_launch(who);
-}
-
-// The HP forms of adam_polyak_launch: the same kernels' HP twins, each set's values from row (set / set_block) % n_groups of d_hp.
-template <bool GUARD>
-static int adam_polyak_hp_launch(const char* who, const avd_mlp_layout* lay, int n_sets, float* theta, float* stats, float* theta_t,
-                                 float* stats_t, float* m, float* v, const float* grads, int32_t* step, int32_t* skipped,
-                                 const avd_hparams* d_hp, int n_groups, int set_block, void* stream) {
-    AVD_REQUIRE(lay && n_sets > 0, "%s: n_sets=%d", who, n_sets);
-    AVD_REQUIRE(theta && stats && theta_t && stats_t && m && v && grads && step, "%s: null pointer", who);
-    AVD_REQUIRE(lay->theta_size % 4 == 0 && lay->actor_size % 4 == 0 && lay->stats_size % 4 == 0, "%s: layout not 4-float aligned", who);
-    AVD_REQUIRE_HP(who, d_hp, n_groups, set_block, n_sets);
-    const HpRef hr{d_hp, n_groups, set_block};
-    const int n4 = lay->theta_size / 4;
-    int gx = (n4 + 255) / 256;
-    if (n_sets >= 256 && gx > 8) gx = 8;
-    if (const char* e = AVD_DIAG_ENV("ADAM_GX")) gx = atoi(e);
-    hipLaunchKernelGGL((adam_polyak_kernel<GUARD, true, HpRef>), dim3(gx, n_sets), dim3(256), 0, (hipStream_t)stream, lay->theta_size,
-                       lay->actor_size, (float4*)theta, (float4*)theta_t, (float4*)m, (float4*)v, (const float4*)grads, step, 0.f, 0.f,
-                       0.f, 0.f, GUARD ? skipped : (int32_t*)nullptr, hr);
-    int rc = check_launch(who);
-    if (rc) return rc;
-    // BN moving stats take part in the soft update too (ddpgagent.py:44-53), set by set with the set's tau
-    hipLaunchKernelGGL((polyak_guarded_kernel<GUARD, true, HpRef>), dim3((unsigned)((lay->stats_size + 255) / 256), n_sets), dim3(256),
-                       0, (hipStream_t)stream, lay->stats_size, stats, stats_t, 0.f, 0.f, grads, lay->theta_size, lay->actor_size, hr);
-    return check_launch(who);
-}
-
 // ---- federated weights on the device (workers/trainer.py:385-398; src/server/federated.py:99-118) ----------------------
 // The reference weights agent (p, m) by |1 / mean(its last `weighted_window` episodic rewards)|. In the throughput modes no
 // episodic reward ever reaches the host, so the history lives here: ring[P*M][W] of closed-episode rewards + hist_cnt[P].
@@ -497,32 +388,77 @@ __global__ __launch_bounds__(1024) void fed_weights_kernel(int P, int M, int W, 
     }
 }
 
-extern "C" int avd_adam_polyak_f32(const avd_mlp_layout* lay, int n_sets, float* theta, float* stats, float* theta_t,
-                                   float* stats_t, float* m, float* v, const float* grads, const int32_t* step,
-                                   float actor_lr, float critic_lr, double tau, void* stream) {
-    return adam_polyak_launch("avd_adam_polyak_f32", false, lay, n_sets, theta, stats, theta_t, stats_t, m, v, grads, (int32_t*)step, actor_lr,
-                              critic_lr, tau, nullptr, stream);
-}
+// The scalar update kernels, instantiated here and in this order: the code object then lists every kernel where it did when the scalar
+// and the sweep launchers were two functions, and its assembly compares equal to that text (tools/isa_diff.py).
+template __global__ void avd::adam_polyak_kernel<true>(int, int, float4*, float4*, float4*, float4*, const float4*, int32_t*, float, float,
+                                                        float, float, int32_t*);
+template __global__ void avd::adam_polyak_kernel<false>(int, int, float4*, float4*, float4*, float4*, const float4*, int32_t*, float, float,
+                                                         float, float, int32_t*);
 
-extern "C" int avd_adam_polyak_hp_f32(const avd_mlp_layout* lay, int n_sets, float* theta, float* stats, float* theta_t, float* stats_t,
-                                      float* m, float* v, const float* grads, const int32_t* step, const avd_hparams* d_hp, int n_groups,
-                                      int set_block, void* stream) {
-    return adam_polyak_hp_launch<false>("avd_adam_polyak_hp_f32", lay, n_sets, theta, stats, theta_t, stats_t, m, v, grads, (int32_t*)step,
-                                        nullptr, d_hp, n_groups, set_block, stream);
-}
-
-extern "C" int avd_adam_polyak_guarded_hp_f32(const avd_mlp_layout* lay, int n_sets, float* theta, float* stats, float* theta_t,
-                                              float* stats_t, float* m, float* v, const float* grads, int32_t* step, int32_t* skipped,
-                                              const avd_hparams* d_hp, int n_groups, int set_block, void* stream) {
-    return adam_polyak_hp_launch<true>("avd_adam_polyak_guarded_hp_f32", lay, n_sets, theta, stats, theta_t, stats_t, m, v, grads, step,
-                                       skipped, d_hp, n_groups, set_block, stream);
+// The four avd_adam_polyak_*_f32 entries: Adam + Polyak of n_sets whole slabs, then the BN moving statistics' soft update (they take
+// part in it too: ddpgagent.py:44-53 iterates .weights). GUARD: sets with a NaN gradient slab are left alone and counted in *skipped.
+// hp = one HpRef: each set's step sizes and tau from row (set / set_block) % n_groups of the sweep table (the scalars are unused);
+// no hp: the scalars, tau a Python double rounded to f32 (ddpgagent.py:47,53).
+template <bool GUARD, class... H>
+static int adam_polyak_launch(const char* who, const avd_mlp_layout* lay, int n_sets, float* theta, float* stats, float* theta_t,
+                              float* stats_t, float* m, float* v, const float* grads, int32_t* step, float actor_lr, float critic_lr,
+                              double tau, int32_t* skipped, void* stream, H... hp) {
+    constexpr bool HP = sizeof...(H) > 0;
+    AVD_REQUIRE(lay && n_sets > 0, "%s: n_sets=%d", who, n_sets);
+    AVD_REQUIRE(theta && stats && theta_t && stats_t && m && v && grads && step, "%s: null pointer", who);
+    AVD_REQUIRE(lay->theta_size % 4 == 0 && lay->actor_size % 4 == 0 && lay->stats_size % 4 == 0, "%s: layout not 4-float aligned", who);
+    if constexpr (HP) {
+        const HpRef r{hp...};
+        AVD_REQUIRE_HP(who, r.hp, r.n_groups, r.block, n_sets);
+    }
+    const float tauf = (float)tau, omt = HP ? 0.f : (float)(1.0 - tau);
+    const int n4 = lay->theta_size / 4;
+    int gx = (n4 + 255) / 256;
+    if (n_sets >= 256 && gx > 8) gx = 8;  // many sets: fewer, longer-lived blocks per set
+    if (const char* e = AVD_DIAG_ENV("ADAM_GX")) gx = atoi(e);  // tuning knob (tools/adam_sweep.sh @ tag r06-pre-prune)
+    hipLaunchKernelGGL((adam_polyak_kernel<GUARD, HP, H...>), dim3(gx, n_sets), dim3(256), 0, (hipStream_t)stream, lay->theta_size,
+                       lay->actor_size, (float4*)theta, (float4*)theta_t, (float4*)m, (float4*)v, (const float4*)grads, step, actor_lr,
+                       critic_lr, tauf, omt, GUARD ? skipped : (int32_t*)nullptr, hp...);
+    int rc = check_launch(who);
+    if (rc) return rc;
+    if constexpr (GUARD || HP) {  // set by set: the sets the kernel above skipped are skipped, each set's own tau
+        hipLaunchKernelGGL((polyak_guarded_kernel<GUARD, HP, H...>), dim3((unsigned)((lay->stats_size + 255) / 256), n_sets), dim3(256), 0,
+                           (hipStream_t)stream, lay->stats_size, stats, stats_t, tauf, omt, grads, lay->theta_size, lay->actor_size, hp...);
+    } else {
+        const long ns = (long)n_sets * lay->stats_size;
+        long blocks = (ns + 255) / 256;
+        if (blocks > 2048) blocks = 2048;
+        hipLaunchKernelGGL(polyak_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ns, stats, stats_t, tauf, omt);
+    }
+    return check_launch(who);
 }
 
 extern "C" int avd_adam_polyak_guarded_f32(const avd_mlp_layout* lay, int n_sets, float* theta, float* stats, float* theta_t,
                                            float* stats_t, float* m, float* v, const float* grads, int32_t* step, float actor_lr,
                                            float critic_lr, double tau, int32_t* skipped, void* stream) {
-    return adam_polyak_launch("avd_adam_polyak_guarded_f32", true, lay, n_sets, theta, stats, theta_t, stats_t, m, v, grads, step, actor_lr,
-                              critic_lr, tau, skipped, stream);
+    return adam_polyak_launch<true>("avd_adam_polyak_guarded_f32", lay, n_sets, theta, stats, theta_t, stats_t, m, v, grads, step, actor_lr,
+                                    critic_lr, tau, skipped, stream);
+}
+
+extern "C" int avd_adam_polyak_f32(const avd_mlp_layout* lay, int n_sets, float* theta, float* stats, float* theta_t,
+                                   float* stats_t, float* m, float* v, const float* grads, const int32_t* step,
+                                   float actor_lr, float critic_lr, double tau, void* stream) {
+    return adam_polyak_launch<false>("avd_adam_polyak_f32", lay, n_sets, theta, stats, theta_t, stats_t, m, v, grads, (int32_t*)step,
+                                     actor_lr, critic_lr, tau, nullptr, stream);
+}
+
+extern "C" int avd_adam_polyak_hp_f32(const avd_mlp_layout* lay, int n_sets, float* theta, float* stats, float* theta_t, float* stats_t,
+                                      float* m, float* v, const float* grads, const int32_t* step, const avd_hparams* d_hp, int n_groups,
+                                      int set_block, void* stream) {
+    return adam_polyak_launch<false>("avd_adam_polyak_hp_f32", lay, n_sets, theta, stats, theta_t, stats_t, m, v, grads, (int32_t*)step, 0.f,
+                                     0.f, 0.0, nullptr, stream, HpRef{d_hp, n_groups, set_block});
+}
+
+extern "C" int avd_adam_polyak_guarded_hp_f32(const avd_mlp_layout* lay, int n_sets, float* theta, float* stats, float* theta_t,
+                                              float* stats_t, float* m, float* v, const float* grads, int32_t* step, int32_t* skipped,
+                                              const avd_hparams* d_hp, int n_groups, int set_block, void* stream) {
+    return adam_polyak_launch<true>("avd_adam_polyak_guarded_hp_f32", lay, n_sets, theta, stats, theta_t, stats_t, m, v, grads, step, 0.f,
+                                    0.f, 0.0, skipped, stream, HpRef{d_hp, n_groups, set_block});
 }
 
 int launch_adam_polyak_ranges(const avd_mlp_layout* lay, int n_sets, const float* theta_in, float* theta_out,
@@ -616,6 +552,9 @@ extern "C" int avd_adam_polyak_intra_f32(const avd_mlp_layout* lay, int P, int M
                                          float* stats_t, float* m, float* v, const float* grads, const int32_t* step, const float* weights,
                                          float actor_lr, float critic_lr, double tau, void* stream) {
     AVD_REQUIRE(lay && P > 0 && M > 0 && M <= INTRA_MAX_M && P <= 65535, "avd_adam_polyak_intra_f32: P=%d M=%d (M <= %d)", P, M, INTRA_MAX_M);
+    // (every refusal ahead of the first launch: the statistics' pass below puts P * M on grid.y, and a call refused there would have
+    // stepped theta, m, v and theta_t already)
+    AVD_REQUIRE((long)P * M <= 65535, "avd_adam_polyak_intra_f32: P=%d x M=%d agents exceed the grid limit (65535)", P, M);
     AVD_REQUIRE(theta && stats && theta_t && stats_t && m && v && grads && step, "avd_adam_polyak_intra_f32: null pointer");
     AVD_REQUIRE(lay->theta_size % 4 == 0 && lay->actor_size % 4 == 0, "avd_adam_polyak_intra_f32: layout not 4-float aligned");
     const float tauf = (float)tau, omt = (float)(1.0 - tau);

@@ -386,19 +386,14 @@ class VecTrainer:
                  ptr(ou.state), ptr(self.actions), ptr(self.leader_exog), ou.mean, conf.ou_dt, conf.action_low, conf.action_high,
                  conf.reset_max_u, 1 if conf.rand_gen == conf.uniform else 0, ptr(env.d_seeds), ptr(self.d_hp), self.E, ou.calls,
                  self.exog_calls, ptr(rp.ring), rp.cap, rp.buffer_counter, ptr(self.ep_reward), stream_handle())
-            ou.calls += 1
-            self.exog_calls += 1
-            env.step_count += 1
-            rp.buffer_counter += 1
-            self._added = True
-            return
-        # the seed argument: the scalar seed, or (a batch) the seed table and its length (avd_step_fused_seeds_f32)
-        fn, key = ("avd_step_fused_f32", (self.seed,)) if self.seeds is None else ("avd_step_fused_seeds_f32", (ptr(env.d_seeds), self.E))
-        call(fn, ptr(env.d_consts), self.P, self.L, self.S, ptr(env.x_prev), ptr(env.x), ptr(env.prev_a),
-             ptr(env.cum_accel), ptr(env.reward), ptr(env.term), ptr(env.done), ptr(env.any_done), ptr(other),
-             ptr(self.actor_out), ptr(ou.state), ptr(self.actions), ptr(self.leader_exog), conf.theta, ou.mean, conf.ou_dt,
-             conf.std_dev, conf.action_low, conf.action_high, conf.reset_max_u, 1 if conf.rand_gen == conf.uniform else 0,
-             *key, ou.calls, self.exog_calls, ptr(rp.ring), rp.cap, rp.buffer_counter, ptr(self.ep_reward), stream_handle())
+        else:
+            # the seed argument: the scalar seed, or (a batch) the seed table and its length (avd_step_fused_seeds_f32)
+            fn, key = ("avd_step_fused_f32", (self.seed,)) if self.seeds is None else ("avd_step_fused_seeds_f32", (ptr(env.d_seeds), self.E))
+            call(fn, ptr(env.d_consts), self.P, self.L, self.S, ptr(env.x_prev), ptr(env.x), ptr(env.prev_a),
+                 ptr(env.cum_accel), ptr(env.reward), ptr(env.term), ptr(env.done), ptr(env.any_done), ptr(other),
+                 ptr(self.actor_out), ptr(ou.state), ptr(self.actions), ptr(self.leader_exog), conf.theta, ou.mean, conf.ou_dt,
+                 conf.std_dev, conf.action_low, conf.action_high, conf.reset_max_u, 1 if conf.rand_gen == conf.uniform else 0,
+                 *key, ou.calls, self.exog_calls, ptr(rp.ring), rp.cap, rp.buffer_counter, ptr(self.ep_reward), stream_handle())
         ou.calls += 1
         self.exog_calls += 1
         env.step_count += 1
@@ -461,7 +456,7 @@ class VecTrainer:
                 and is_valid_update_step(conf, i) and is_valid_step_for_federated_training_with_gradients(conf, ep, i)):
             # intrafrl + gradients, every agent stepping with its platoon's mean gradient (:417-431): learn || mean + Adam + Polyak over
             # platoon chunks on two streams (vec.AgentGroup.learn_apply_intra)
-            w = self._intra_weights(ep)
+            w = self._fed_weights(ep, on_device=(P, M))
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             if self.timers is not None:
                 e0.record()
@@ -472,14 +467,8 @@ class VecTrainer:
                 self.timers.setdefault("learn+update", []).append((e0, e1))
             return
         if self.shared and self.shared_engine in ("batched", "fused", "fused3"):
-            weights = None
-            if self._dev_weighted:
-                weights = "device"  # (self._aw / self._wsum, refreshed at the end of every step)
-            elif is_weighted_fed_enabled(conf, ep):
-                if self.fed_weights is None or self.fed_weights[0] != ep:
-                    self.fed_weights = (ep, self._weights_for_fed(ep))
-                weights = self.fed_weights[1]
-            self._timed("learn", self._learn_batched, s, a, r, s2, weights)
+            # (on the device: self._aw / self._wsum, refreshed at the end of every step)
+            self._timed("learn", self._learn_batched, s, a, r, s2, self._fed_weights(ep, on_device="device"))
             # the 16-bit set learners answer a non-finite input / an fp16 overflow with an all-NaN slab: the guarded update then
             # leaves that weight set untouched and counts the event (nonfinite_updates()) instead of poisoning it for good
             self._timed("update", self.agents.apply, self.set_grads, guarded=self.shared_engine in ("fused", "fused3"))
@@ -561,13 +550,7 @@ class VecTrainer:
                 raise RuntimeError("local update requested in shared-set mode")
             self.agents.apply(self.grads)
             return
-        weights = None
-        if self._dev_weighted:
-            weights = self._w_raw.view(P, M)  # (all ones until the weighting is enabled: the weighted formulas then give the plain mean)
-        elif is_weighted_fed_enabled(conf, ep):
-            if self.fed_weights is None or self.fed_weights[0] != ep:
-                self.fed_weights = (ep, self._weights_for_fed(ep))
-            weights = self.fed_weights[1]
+        weights = self._fed_weights(ep, on_device=(P, M))
         method = conf.fed_method
         if is_valid_step_for_federated_training_with_gradients(conf, ep, i):
             if method == conf.intrafrl and self.intra_fused and not self.shared:
@@ -578,8 +561,6 @@ class VecTrainer:
                                total=self.total_platoons)
             if self.shared:
                 self.agents.apply(avg)
-            elif method == conf.intrafrl and self.intra_fused:
-                pass  # (handled above: never reached)
             else:
                 directional = method == conf.intrafrl and conf.intra_directional_averaging
                 vec.fed_scatter(avg, self.grads, P, M, method)
@@ -662,9 +643,12 @@ class VecTrainer:
         from .dist import any_terminal
         return any_terminal(self.env.any_done, self.group)
 
-    def _intra_weights(self, ep):
+    def _fed_weights(self, ep, on_device):
+        """The federated weights [P, M] of episode ep, None for the plain mean. Kept on the device (avd_fed_weights_f32): the raw weights
+        viewed as on_device = (P, M) -- all ones until the weighting is enabled: the weighted formulas then give the plain mean -- or
+        on_device itself where the caller only needs to know that (a string). Otherwise the host's, computed once per episode."""
         if self._dev_weighted:
-            return self._w_raw.view(self.P, self.M)
+            return on_device if isinstance(on_device, str) else self._w_raw.view(*on_device)
         if is_weighted_fed_enabled(self.conf, ep):
             if self.fed_weights is None or self.fed_weights[0] != ep:
                 self.fed_weights = (ep, self._weights_for_fed(ep))

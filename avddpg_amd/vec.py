@@ -541,16 +541,25 @@ class AgentGroup:
         n_agents = s.shape[0]
         if grads is None:
             grads = torch.empty(n_agents, self.lay.theta_size, dtype=torch.float32, device=self.device)
+        args = (self._layp, n_agents, set_mod, ptr(self.theta), ptr(self.stats), ptr(self.theta_t), ptr(self.stats_t), ptr(s), ptr(a), ptr(r),
+                ptr(s2))
         if self.hp is not None:  # each agent's gamma from the sweep table
             tbl, E, blk = self.hp
-            call("avd_learn_hp_f32", self._layp, n_agents, set_mod, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
-                 ptr(self.stats_t), ptr(s), ptr(a), ptr(r), ptr(s2), self.high, ptr(grads), ptr(losses), ptr(tbl), E, blk,
-                 stream_handle())
-            return grads
-        call("avd_learn_f32", self._layp, n_agents, set_mod, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
-             ptr(self.stats_t), ptr(s), ptr(a), ptr(r), ptr(s2), self.config.gamma, self.high, ptr(grads),
-             ptr(losses), stream_handle())
+            call("avd_learn_hp_f32", *args, self.high, ptr(grads), ptr(losses), ptr(tbl), E, blk, stream_handle())
+        else:
+            call("avd_learn_f32", *args, self.config.gamma, self.high, ptr(grads), ptr(losses), stream_handle())
         return grads
+
+    def _workspace(self, attr, size_fn, n_agents):
+        """The scratch buffer of a library call: `size_fn` says how many bytes (n_agents, n_sets) takes; one uint8 tensor per `attr`,
+        which only ever grows."""
+        need = C.c_size_t(0)
+        call(size_fn, self._layp, n_agents, self.n_sets, C.byref(need))
+        ws = getattr(self, attr, None)
+        if ws is None or ws.numel() < need.value:
+            ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            setattr(self, attr, ws)
+        return ws
 
     def learn_shared(self, s, a, r, s2, n_agents, grads=None, losses=None, row_weight=None):
         """Trainer.learn + federated mean for agents that SHARE this group's ``n_sets`` weight sets (interfrl with every
@@ -558,14 +567,9 @@ class AgentGroup:
         s, s2 [n_sets, rows, S], a [n_sets, rows, 1], r [n_sets, rows] with rows = n_agents / n_sets * batch_size.
         row_weight [n_sets, rows] (optional): w_p * P / sum(w) on platoon p's rows = the weighted federated mean.
         Returns the mean gradient per set [n_sets, theta_size]."""
-        import ctypes
         if grads is None:
             grads = torch.empty(self.n_sets, self.lay.theta_size, dtype=torch.float32, device=self.device)
-        need = ctypes.c_size_t(0)
-        call("avd_learn_shared_workspace", self._layp, n_agents, self.n_sets, ctypes.byref(need))
-        ws = getattr(self, "_wide_ws", None)
-        if ws is None or ws.numel() < need.value:
-            ws = self._wide_ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        ws = self._workspace("_wide_ws", "avd_learn_shared_workspace", n_agents)
         call("avd_learn_shared_bf16", self._layp, n_agents, self.n_sets, ptr(self.theta), ptr(self.stats),
              ptr(self.theta_t), ptr(self.stats_t), ptr(s), ptr(a), ptr(r), ptr(s2), ptr(row_weight), self.config.gamma,
              self.high, ptr(grads), ptr(losses), ptr(ws), ws.numel(), stream_handle())
@@ -583,7 +587,6 @@ class AgentGroup:
         second; same stream, same ``grads``, nothing else in between -- VecTrainer(overlap_allreduce=True) puts the critic block's
         all-reduce between them on a side stream).
         Returns the mean gradient per set [n_sets, theta_size]."""
-        import ctypes
         if self.hp is not None and not (split and phase is None):
             self._no_hp("learn_set_fused (bf16 operands, or a phase of the split call)")
         self._check_agent_major(s, a, r, s2, n_agents, agent_weight)
@@ -591,12 +594,7 @@ class AgentGroup:
             grads = torch.empty(self.n_sets, self.lay.theta_size, dtype=torch.float32, device=self.device)
         wsf, fn, attr = (("avd_learn_set_split_workspace", "avd_learn_set_split_f16x3", "_fsplit_ws") if split else
                          ("avd_learn_set_fused_workspace", "avd_learn_set_fused_bf16", "_fset_ws"))
-        need = ctypes.c_size_t(0)
-        call(wsf, self._layp, n_agents, self.n_sets, ctypes.byref(need))
-        ws = getattr(self, attr, None)
-        if ws is None or ws.numel() < need.value:
-            ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
-            setattr(self, attr, ws)
+        ws = self._workspace(attr, wsf, n_agents)
         if phase is not None and not split:
             raise _hip.AvdError("phase= needs split=True (csrc/fsplit.hip)")
         if phase == "actor":
@@ -640,15 +638,10 @@ class AgentGroup:
     def actor_shared(self, states_set_major, n_agents, out=None):
         """actor(state) for agents sharing this group's weight sets as one bf16 GEMM chain per set (csrc/wide.hip):
         states [n_sets, rows, S] set-major, tightly packed -> [n_sets, rows]."""
-        import ctypes
         rows = n_agents // self.n_sets
         if out is None:
             out = torch.empty(self.n_sets, rows, dtype=torch.float32, device=self.device)
-        need = ctypes.c_size_t(0)
-        call("avd_actor_forward_shared_workspace", self._layp, n_agents, self.n_sets, ctypes.byref(need))
-        ws = getattr(self, "_wide_act_ws", None)
-        if ws is None or ws.numel() < need.value:
-            ws = self._wide_act_ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        ws = self._workspace("_wide_act_ws", "avd_actor_forward_shared_workspace", n_agents)
         call("avd_actor_forward_shared_bf16", self._layp, n_agents, self.n_sets, ptr(self.theta), ptr(self.stats),
              ptr(states_set_major), self.high, ptr(out), ptr(ws), ws.numel(), stream_handle())
         return out
@@ -659,28 +652,19 @@ class AgentGroup:
         counted in ``self.nonfinite_skipped`` (device int32; no host synchronisation) -- avd_adam_polyak_guarded_f32."""
         c = self.config
         self.step += 1
-        if self.hp is not None:  # each set's step sizes and tau from the sweep table
-            tbl, E, blk = self.hp
-            if guarded:
-                if getattr(self, "nonfinite_skipped", None) is None:
-                    self.nonfinite_skipped = torch.zeros(1, dtype=torch.int32, device=self.device)
-                call("avd_adam_polyak_guarded_hp_f32", self._layp, self.n_sets, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
-                     ptr(self.stats_t), ptr(self.m), ptr(self.v), ptr(grads), ptr(self.step), ptr(self.nonfinite_skipped), ptr(tbl), E,
-                     blk, stream_handle())
-            else:
-                call("avd_adam_polyak_hp_f32", self._layp, self.n_sets, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
-                     ptr(self.stats_t), ptr(self.m), ptr(self.v), ptr(grads), ptr(self.step), ptr(tbl), E, blk, stream_handle())
-            return
+        args = (self._layp, self.n_sets, ptr(self.theta), ptr(self.stats), ptr(self.theta_t), ptr(self.stats_t), ptr(self.m), ptr(self.v),
+                ptr(grads), ptr(self.step))
+        skipped = ()
         if guarded:
             if getattr(self, "nonfinite_skipped", None) is None:
                 self.nonfinite_skipped = torch.zeros(1, dtype=torch.int32, device=self.device)
-            call("avd_adam_polyak_guarded_f32", self._layp, self.n_sets, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
-                 ptr(self.stats_t), ptr(self.m), ptr(self.v), ptr(grads), ptr(self.step), c.actor_lr, c.critic_lr,
-                 float(c.tau), ptr(self.nonfinite_skipped), stream_handle())
-            return
-        call("avd_adam_polyak_f32", self._layp, self.n_sets, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
-             ptr(self.stats_t), ptr(self.m), ptr(self.v), ptr(grads), ptr(self.step), c.actor_lr, c.critic_lr,
-             float(c.tau), stream_handle())
+            skipped = (ptr(self.nonfinite_skipped),)
+        if self.hp is not None:  # each set's step sizes and tau from the sweep table
+            tbl, E, blk = self.hp
+            call("avd_adam_polyak_guarded_hp_f32" if guarded else "avd_adam_polyak_hp_f32", *args, *skipped, ptr(tbl), E, blk, stream_handle())
+        else:
+            call("avd_adam_polyak_guarded_f32" if guarded else "avd_adam_polyak_f32", *args, c.actor_lr, c.critic_lr, float(c.tau), *skipped,
+                 stream_handle())
 
     def apply_intra(self, grads, P, M, weights=None, lead_skip=False, lo=0, hi=None, stream=None, advance=True):
         """intrafrl + gradients (workers/trainer.py:417-431) for platoons [lo, hi): every agent of a platoon steps with the (weighted)
@@ -709,40 +693,14 @@ class AgentGroup:
         leaves a platoon): chunk c's learn kernel (matrix-core bound, gradients to the slab) runs on the caller's stream, its
         mean + Adam + Polyak pass (an HBM stream, apply_intra) on a side stream under chunk c + 1's learn kernel. Same results as
         learn() followed by apply_intra()."""
-        main = torch.cuda.current_stream()
-        if getattr(self, "_side", None) is None:
-            self._side = torch.cuda.Stream(device=self.device)
-        side = self._side
-        c = self.config
         chunks = max(1, min(chunks, P))
-        bounds = [(P * i) // chunks for i in range(chunks + 1)]
-        T = lambda: torch.cuda.Event(enable_timing=timers is not None)
         # the iteration counts of every stepping agent, ONCE, on the caller's stream: each chunk's pass on the side stream waits for an
         # event recorded after this (one small launch per step instead of one per chunk)
         self.step.view(P, M)[:, (1 if lead_skip else 0):] += 1
-        for i in range(chunks):
-            lo, hi = bounds[i] * M, bounds[i + 1] * M
-            if hi == lo:
-                continue
-            t0, t1 = T(), T()
-            if timers is not None:
-                t0.record(main)
-            call("avd_learn_f32", self._layp, hi - lo, 0, ptr(self.theta[lo:hi]), ptr(self.stats[lo:hi]), ptr(self.theta_t[lo:hi]),
-                 ptr(self.stats_t[lo:hi]), ptr(s[lo:hi]), ptr(a[lo:hi]), ptr(r[lo:hi]), ptr(s2[lo:hi]), c.gamma, self.high,
-                 ptr(grads[lo:hi]), ptr(losses[lo:hi]) if losses is not None else None, _hip.C.c_void_p(main.cuda_stream))
-            t1.record(main)
-            side.wait_event(t1)
-            u0, u1 = T(), T()
-            if timers is not None:
-                u0.record(side)
-            self.apply_intra(grads, P, M, weights=weights, lead_skip=lead_skip, lo=bounds[i], hi=bounds[i + 1], stream=side, advance=False)
-            if timers is not None:
-                u1.record(side)
-                timers.setdefault("learn", []).append((t0, t1))
-                timers.setdefault("update", []).append((u0, u1))
-        done = torch.cuda.Event()
-        done.record(side)
-        main.wait_event(done)
+        self._chunk_pipeline([(P * i) // chunks for i in range(chunks + 1)],
+                             lambda lo, hi, stream: self._learn_slice(s, a, r, s2, grads, losses, lo * M, hi * M, stream),
+                             lambda lo, hi, stream: self.apply_intra(grads, P, M, weights=weights, lead_skip=lead_skip, lo=lo, hi=hi,
+                                                                     stream=stream, advance=False), timers)
 
     def learn_update(self, s, a, r, s2, grads, losses=None, next_states=None, x_stride=None, next_actions=None):
         """Fused Trainer.learn + Adam x2 + update_target for per-agent weight sets (reference nofrl,
@@ -758,30 +716,23 @@ class AgentGroup:
             self.theta_alt = self.theta.clone()  # alignment padding stays zero in both slabs
         c = self.config
         self.step += 1
-        if self.hp is not None:  # each agent's gamma, step sizes and tau from the sweep table
-            tbl, E, blk = self.hp
-            args = (self._layp, n, ptr(self.theta), ptr(self.stats), ptr(self.theta_alt), ptr(self.theta_t), ptr(self.stats_t),
-                    ptr(self.m), ptr(self.v), ptr(self.step), ptr(s), ptr(a), ptr(r), ptr(s2), self.high, ptr(grads), ptr(losses))
-            if next_actions is not None:
-                if self.lay.A != 1:
-                    raise _hip.AvdError("next-action epilogue: A == 1 only")
-                xs = next_states.shape[-1] if x_stride is None else x_stride
-                call("avd_learn_update_act_hp_f32", *args, ptr(next_states), xs, ptr(next_actions), ptr(tbl), E, blk, stream_handle())
-            else:
-                call("avd_learn_update_hp_f32", *args, ptr(tbl), E, blk, stream_handle())
-            self.theta, self.theta_alt = self.theta_alt, self.theta
-            return
-        args = (self._layp, n, ptr(self.theta), ptr(self.stats), ptr(self.theta_alt), ptr(self.theta_t), ptr(self.stats_t),
-                ptr(self.m), ptr(self.v), ptr(self.step), ptr(s), ptr(a), ptr(r), ptr(s2), c.gamma, self.high, c.actor_lr,
-                c.critic_lr, float(c.tau), ptr(grads), ptr(losses))
+        hp = self.hp is not None  # each agent's gamma, step sizes and tau from the sweep table
+        args = (self._layp, n, ptr(self.theta), ptr(self.stats), ptr(self.theta_alt), ptr(self.theta_t), ptr(self.stats_t), ptr(self.m),
+                ptr(self.v), ptr(self.step), ptr(s), ptr(a), ptr(r), ptr(s2))
+        args += (self.high,) if hp else (c.gamma, self.high, c.actor_lr, c.critic_lr, float(c.tau))
+        args += (ptr(grads), ptr(losses))
+        fn = "avd_learn_update_hp_f32" if hp else "avd_learn_update_f32"
         if next_actions is not None:
             # + the agents' next actions actor(next_states) with the updated weights, from the workgroup that wrote them
             if self.lay.A != 1:
                 raise _hip.AvdError("next-action epilogue: A == 1 only")
             xs = next_states.shape[-1] if x_stride is None else x_stride
-            call("avd_learn_update_act_f32", *args, ptr(next_states), xs, ptr(next_actions), stream_handle())
-        else:
-            call("avd_learn_update_f32", *args, stream_handle())
+            args += (ptr(next_states), xs, ptr(next_actions))
+            fn = "avd_learn_update_act_hp_f32" if hp else "avd_learn_update_act_f32"
+        if hp:
+            tbl, E, blk = self.hp
+            args += (ptr(tbl), E, blk)
+        call(fn, *args, stream_handle())
         self.theta, self.theta_alt = self.theta_alt, self.theta
 
     def learn_apply(self, s, a, r, s2, grads, losses=None, chunks=4, timers=None):
@@ -794,35 +745,47 @@ class AgentGroup:
         n = self.n_sets
         if s.shape[0] != n:
             raise _hip.AvdError("learn_apply needs one weight set per agent (set_mod == 0)")
+        c = self.config
+        self.step += 1
+        chunks = max(1, min(chunks, n))
+
+        def update(lo, hi, stream):
+            call("avd_adam_polyak_f32", self._layp, hi - lo, ptr(self.theta[lo:hi]), ptr(self.stats[lo:hi]), ptr(self.theta_t[lo:hi]),
+                 ptr(self.stats_t[lo:hi]), ptr(self.m[lo:hi]), ptr(self.v[lo:hi]), ptr(grads[lo:hi]), ptr(self.step[lo:hi]), c.actor_lr,
+                 c.critic_lr, float(c.tau), _hip.C.c_void_p(stream.cuda_stream))
+
+        self._chunk_pipeline([(n * i) // chunks for i in range(chunks + 1)],
+                             lambda lo, hi, stream: self._learn_slice(s, a, r, s2, grads, losses, lo, hi, stream), update, timers)
+
+    def _learn_slice(self, s, a, r, s2, grads, losses, lo, hi, stream):
+        """avd_learn_f32 of the agents [lo, hi), each with its own weight set, on `stream`."""
+        call("avd_learn_f32", self._layp, hi - lo, 0, ptr(self.theta[lo:hi]), ptr(self.stats[lo:hi]), ptr(self.theta_t[lo:hi]),
+             ptr(self.stats_t[lo:hi]), ptr(s[lo:hi]), ptr(a[lo:hi]), ptr(r[lo:hi]), ptr(s2[lo:hi]), self.config.gamma, self.high,
+             ptr(grads[lo:hi]), ptr(losses[lo:hi]) if losses is not None else None, _hip.C.c_void_p(stream.cuda_stream))
+
+    def _chunk_pipeline(self, bounds, learn, update, timers):
+        """The two-stream pipeline of learn_apply / learn_apply_intra over the slices [bounds[i], bounds[i + 1]): learn(lo, hi, stream) on
+        the caller's stream, update(lo, hi, stream) on the side stream once that slice's learn has finished -- under the next slice's
+        learn -- and the caller's stream joined to the side stream at the end.
+        timers: optional dict of lists collecting (start, end) event pairs per kernel ("learn", "update")."""
         main = torch.cuda.current_stream()
         if getattr(self, "_side", None) is None:
             self._side = torch.cuda.Stream(device=self.device)
         side = self._side
-        c = self.config
-        self.step += 1
-        chunks = max(1, min(chunks, n))
-        bounds = [(n * i) // chunks for i in range(chunks + 1)]
         T = lambda: torch.cuda.Event(enable_timing=timers is not None)
-        for i in range(chunks):
-            lo, hi = bounds[i], bounds[i + 1]
+        for lo, hi in zip(bounds, bounds[1:]):
             if hi == lo:
                 continue
             t0, t1 = T(), T()
             if timers is not None:
                 t0.record(main)
-            call("avd_learn_f32", self._layp, hi - lo, 0, ptr(self.theta[lo:hi]), ptr(self.stats[lo:hi]),
-                 ptr(self.theta_t[lo:hi]), ptr(self.stats_t[lo:hi]), ptr(s[lo:hi]), ptr(a[lo:hi]), ptr(r[lo:hi]),
-                 ptr(s2[lo:hi]), c.gamma, self.high, ptr(grads[lo:hi]), ptr(losses[lo:hi]) if losses is not None else None,
-                 _hip.C.c_void_p(main.cuda_stream))
+            learn(lo, hi, main)
             t1.record(main)
             side.wait_event(t1)
             u0, u1 = T(), T()
             if timers is not None:
                 u0.record(side)
-            call("avd_adam_polyak_f32", self._layp, hi - lo, ptr(self.theta[lo:hi]), ptr(self.stats[lo:hi]),
-                 ptr(self.theta_t[lo:hi]), ptr(self.stats_t[lo:hi]), ptr(self.m[lo:hi]), ptr(self.v[lo:hi]),
-                 ptr(grads[lo:hi]), ptr(self.step[lo:hi]), c.actor_lr, c.critic_lr, float(c.tau),
-                 _hip.C.c_void_p(side.cuda_stream))
+            update(lo, hi, side)
             if timers is not None:
                 u1.record(side)
                 timers.setdefault("learn", []).append((t0, t1))

@@ -77,6 +77,18 @@ def test_error_reporting_without_gpu():
         _hip.call("avd_learn_f32", ctypes.byref(lay), 1, 0, *([None] * 8), 0.99, 2.5, None, None, None)
 
 
+def test_intra_update_refuses_an_oversized_grid_before_any_launch():
+    """avd_adam_polyak_intra_f32 puts P * M on grid.y of its second launch (the statistics' soft update): more than 65535 agents are
+    refused with the other argument checks, ahead of the first launch, so a refused call has stepped nothing. (P <= 65535 and M <= 16
+    alone let 4096 x 16 through to that second launch, after theta, m, v and theta_t had stepped.)"""
+    lay = _hip.make_layout(4, 1, 256, 128, 48, 64)
+    intra = lambda P, M: _hip.call("avd_adam_polyak_intra_f32", ctypes.byref(lay), P, M, 0, *([None] * 9), 1e-4, 1e-3, 0.005, None)
+    with pytest.raises(_hip.AvdError, match=r"avd_adam_polyak_intra_f32: P=4096 x M=16 agents exceed the grid limit"):
+        intra(4096, 16)
+    with pytest.raises(_hip.AvdError, match="avd_adam_polyak_intra_f32: null pointer"):  # 65520 agents: past that check, still no launch
+        intra(4095, 16)
+
+
 def test_learn_shape_check_draws_the_lds_boundary_without_a_launch():
     """avd_learn_check_shape: what avd_learn_f32 / avd_learn_update_f32 would say about a shape, on the host. At 320/160/64 the general
     kernel's tile takes 36968 + 64 S + 448 A floats of the 40960: centralized pl_size 5 fits with 472 to spare, pl_size 6 does not."""
