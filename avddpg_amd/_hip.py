@@ -107,6 +107,7 @@ _PROTOS = {
     "avd_fed_weights_f32": [_i, _i, _i, _P, _P, _i, _P, _P, _P, _P],
     "avd_learn_shared_workspace": [_LP, _i, _i, C.POINTER(C.c_size_t)],
     "avd_learn_shared_bf16": [_LP, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _P, _P, _P, C.c_size_t, _P],
+    "avd_learn_shared_path": [_LP, _i, _i, C.POINTER(C.c_uint)],
     "avd_learn_set_fused_workspace": [_LP, _i, _i, C.POINTER(C.c_size_t)],
     "avd_learn_set_fused_bf16": [_LP, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _P, _P, _P, C.c_size_t, _P],
     "avd_learn_set_split_workspace": [_LP, _i, _i, C.POINTER(C.c_size_t)],

@@ -2684,524 +2684,552 @@ extern "C" int avd_learn_shared_workspace(const avd_mlp_layout* lay, int n_agent
     return AVD_OK;
 }
 
-namespace {
-// one network's prepared operands
-struct NetOps {
-    const float *th, *st;  // [sets][theta_size] (actor block at 0, critic at actor_size), [sets][stats_size]
-    float *inv, *sh, *rs, *mean;  // tables [sets][ldT]: first-layer features at [0, KCp), second layer at [KCp, KCp + H2)
-    bf16 *WT, *Wn;
-    float *bias, *cf, *c0;
-    const void* wf1;  // fused forward: first-layer fragments
-};
-}  // namespace
-
 #define WIDE_CHECK(call)         \
     do {                         \
         int rc_ = (call);        \
         if (rc_) return rc_;     \
     } while (0)
 
-extern "C" int avd_learn_shared_bf16(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta,
-                                     const float* stats, const float* theta_t, const float* stats_t, const float* s,
-                                     const float* a, const float* r, const float* s2, const float* row_weight, float gamma,
-                                     float high, float* grads, float* losses, void* workspace, size_t workspace_bytes,
-                                     void* stream) {
-    int rc = check_wide(lay, n_agents, n_sets, "avd_learn_shared_bf16");
-    if (rc) return rc;
-    AVD_REQUIRE(theta && stats && theta_t && stats_t && s && a && r && s2 && grads && workspace,
-                "avd_learn_shared_bf16: null pointer");
-    const avd_mlp_layout& L = *lay;
-    const Plan pl = make_plan(L, n_agents, n_sets);
-    AVD_REQUIRE(workspace_bytes >= pl.total, "avd_learn_shared_bf16: workspace %zu B < %zu B", workspace_bytes, pl.total);
-    const Dims& d = pl.d;
-    hipStream_t st = (hipStream_t)stream;
-    unsigned char* ws = (unsigned char*)workspace;
-    auto B16 = [&](size_t off) { return (bf16*)(ws + off); };
-    auto F32 = [&](size_t off) { return (float*)(ws + off); };
-    const int sets = n_sets, Ns = d.Ns, Np = d.Np, H1 = d.H1, H2 = d.H2, Ha = d.Ha, KC = d.KC, KCp = d.KCp;
-    const long KCn = rup(KC, 256) + 256, H2n = rup(H2, 256), ldT = pl.ldT;
-    const long setC = (long)Np * KCp, setCT = KCn * Np, setP2 = (long)Np * H2, setZT = H2n * Np;
-    const long setWT = H2n * KCp, setWn = KCn * H2;
-    const int asz = L.actor_size;
-
-    // zero what is accumulated into or read as padding
-    (void)hipMemsetAsync(grads, 0, sizeof(float) * (size_t)sets * L.theta_size, st);
-    (void)hipMemsetAsync(ws + pl.acc, 0, sizeof(float) * sets * 4, st);
-    // (activation buffers need no clearing: their producers write every row < Np and every column < KCp, zeros in the
-    //  padding; rows/columns beyond that only ever feed output elements the GEMM epilogues do not store)
-
-    // second layers of 512 n columns (config 5: 1024): the forward passes run fused (fw::fwd_gen_kernel); AVD_WIDE_FUSED_FWD=0: layer-wise
-    static const char* ff_env = AVD_DIAG_ENV("WIDE_FUSED_FWD");
-    const bool fused_fwd = L.S == 4 && H2 % fw::FC == 0 && H1 % 32 == 0 && KCp % 32 == 0 && KCp / 32 >= fw::FSTG && !(ff_env && ff_env[0] == '0');
-    static const char* fd_env = AVD_DIAG_ENV("WIDE_FUSED_DW");
-    static const char* fx_env = AVD_DIAG_ENV("WIDE_FUSED_DX");
-    static const char* fl_env = AVD_DIAG_ENV("WIDE_FUSED_DELTA");
-    const bool fused_delta = fused_fwd && H1 % 32 == 0 && KCp - H1 == 64 && !(fl_env && fl_env[0] == '0');
+// ---- which kernels a learn runs ---------------------------------------------------------------
+namespace {
+// Decided once per call from the shape (choose_path), read by everything below. Each flag: the kernels it selects in place of
+// which, and the shape fact it rests on.
+struct Path {
+    bool fused_fwd;    // forward passes by fw::fwd_gen_kernel, not l1_fwd + GEMM: S == 4, H2 in fw::FC-column blocks
+    bool fused_delta;  // critic(s, mu) by fw::fwd_delta_kernel on critic(s, a)'s stored activations, not a full pass + dx GEMM + row_dot: KCp - H1 == 64 (two action chunks)
+    bool r1;           // rank-one backward (aux_pack, fw::dw_gen_kernel, w2_post, fw::dx_gen_kernel on the relu mask), not out_bwd + two GEMMs: Np >= 512, H1 = 256 x 2^k
+    bool dual;         // critic(s, a) and critic(s, mu) in ONE fw::fwd_gen_kernel<true, 4>, not <true, 2> + fwd_delta: every r1 shape (fused_delta: two action chunks)
+    bool act_in_dx;    // the critic's action features inside fw::dx_gen_kernel<true>, not l1_fwd + dx GEMM + l1_grads + bn1_flush: H1 == 1024, Ha <= 64
+};
+static bool is_off(const char* v) { return v && v[0] == '0'; }
+// The only reader of the diagnostic build's path switches (AVD_WIDE_*=0 clears a flag and whatever rests on it; null constants in the
+// product), once per process: the A/B tests run one process per setting. Np: the rows per set, padded (Plan).
+static Path choose_path(const avd_mlp_layout& L, int Np) {
+    static const bool no_fwd = is_off(AVD_DIAG_ENV("WIDE_FUSED_FWD")), no_dw = is_off(AVD_DIAG_ENV("WIDE_FUSED_DW")),
+                      no_dx = is_off(AVD_DIAG_ENV("WIDE_FUSED_DX")), no_delta = is_off(AVD_DIAG_ENV("WIDE_FUSED_DELTA")),
+                      no_dual = is_off(AVD_DIAG_ENV("WIDE_DUAL")), no_act = is_off(AVD_DIAG_ENV("WIDE_ACT_IN_DX"));
+    static_assert(8 * fw::FK == 256, "a row range of the rank-one chain is whole 256-row chunks: Np is a multiple");
+    const int H1 = L.H1, KCp = (int)rup(L.H1 + L.Ha, 64);  // (check_wide: H1, hence KCp too, is a multiple of 64)
+    Path p;
+    p.fused_fwd = L.S == 4 && L.H2 % fw::FC == 0 && KCp / 32 >= fw::FSTG && !no_fwd;
+    p.fused_delta = p.fused_fwd && KCp - H1 == 64 && !no_delta;
     // The fused backward kernels exist in the rank-one form only (r06: dZ2 = d (x) cf (.) mask is never materialised; the forward
     // kernels store the relu mask, fw::dw_gen_kernel / fw::dx_gen_kernel / fw::fwd_delta_kernel take d and cf on their other operands):
     // all of them or none -- without one of them the backward pass runs layer-wise from out_bwd_kernel's dZ2.
-    const bool r1 = fused_fwd && fused_delta && Np % (8 * fw::FK) == 0 && Np / (8 * fw::FK) >= 2 &&  // (>= 2 chunks per row range)
-                    Np % 256 == 0 && H1 % 256 == 0 && 32 % (H1 / 256) == 0 && !(fd_env && fd_env[0] == '0') && !(fx_env && fx_env[0] == '0');
-    const bool fused_dw = r1, fused_dx = r1;
-    // critic(s, a) and critic(s, mu) in ONE forward pass (fw::fwd_gen_kernel EPI 4) instead of a pass that stores its signed activations + the
-    // delta pass over them: whenever the rank-one chain runs (the action branch is two chunks: fused_delta)
-    static const char* du_env = AVD_DIAG_ENV("WIDE_DUAL");
-    const bool dual = r1 && KCp / 32 - H1 / 32 == 2 && !(du_env && du_env[0] == '0');
-    static const char* fa_env = AVD_DIAG_ENV("WIDE_ACT_IN_DX");
-    const bool act_in_dx = fused_dx && H1 / 256 == 4 && Ha <= 64 && !(fa_env && fa_env[0] == '0');  // (fw::dx_gen_kernel<true>)
+    p.r1 = p.fused_delta && Np / (8 * fw::FK) >= 2 && H1 % 256 == 0 && 32 % (H1 / 256) == 0 && !no_dw && !no_dx;
+    p.dual = p.r1 && !no_dual;
+    p.act_in_dx = p.r1 && H1 / 256 == 4 && L.Ha <= 64 && !no_act;
+    return p;
+}
+// the diagnostic build's other knobs, read once per process beside the path switches: FwdP::dbg and DxP::abl (work-skipping ablations),
+// and =1: the r03 forward epilogue everywhere (A/B)
+struct Knobs { int fw_dbg, dx_abl; bool fwd_epi0; };
+static const Knobs& knobs() {
+    static const char *dbg = AVD_DIAG_ENV("FW_DBG"), *abl = AVD_DIAG_ENV("WIDE_DX_ABL"), *epi = AVD_DIAG_ENV("WIDE_FWD_EPI0");
+    static const Knobs k = {dbg ? atoi(dbg) : 0, abl ? atoi(abl) : 0, epi && epi[0] == '1'};
+    return k;
+}
+// the > 64 KB dynamic-LDS opt-in of the fw:: kernels, once per DEVICE of this process (the attribute belongs to the device's copy of the function)
+static int opt_in_dynamic_lds() {
     constexpr size_t fw_lds = fw::L_TOTAL, dw_lds = (size_t)fw::FSTG * fw::DW_STG;  // (forward; weight gradient: four stages, its epilogue's scratch inside them)
-    if (fused_fwd) {
-        // the > 64 KB dynamic-LDS opt-in, once per DEVICE of this process (the attribute belongs to the device's copy of the function)
-        static unsigned long long fw_attr_done = 0;  // bit = device ordinal
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev >= 64 || !((fw_attr_done >> dev) & 1ull)) {
-            hipError_t e = hipSuccess;
-            auto opt_in = [&](const void* fn, size_t bytes) {
-                if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-            };
-            opt_in((const void*)fw::fwd_gen_kernel<false, 0>, fw_lds), opt_in((const void*)fw::fwd_gen_kernel<true, 0>, fw_lds);
-            opt_in((const void*)fw::fwd_gen_kernel<false, 1>, fw_lds), opt_in((const void*)fw::fwd_gen_kernel<true, 1>, fw_lds);
-            opt_in((const void*)fw::fwd_gen_kernel<false, 3>, fw_lds), opt_in((const void*)fw::fwd_gen_kernel<true, 2>, fw_lds);
-            opt_in((const void*)fw::fwd_gen_kernel<true, 4>, fw::L_TOTAL_DUAL);
-            opt_in((const void*)fw::dw_gen_kernel<false, 4>, dw_lds), opt_in((const void*)fw::dw_gen_kernel<true, 4>, dw_lds);
-            opt_in((const void*)fw::dw_gen_kernel<false, 8>, dw_lds), opt_in((const void*)fw::dw_gen_kernel<true, 8>, dw_lds);
-            opt_in((const void*)fw::dw_gen_kernel<false, 16>, dw_lds), opt_in((const void*)fw::dw_gen_kernel<true, 16>, dw_lds);
-            opt_in((const void*)fw::dx_gen_kernel<false>, fw::DxL<false>::TOTAL), opt_in((const void*)fw::dx_gen_kernel<true>, fw::DxL<true>::TOTAL);
-            opt_in((const void*)fw::fwd_delta_kernel, fw::DL_TOTAL);
-            if (e != hipSuccess) {
-                set_error("avd_learn_shared_bf16: hipFuncSetAttribute(dynamic LDS %zu B) on device %d: %s", fw_lds, dev, hipGetErrorString(e));
-                return AVD_E_LAUNCH;
-            }
-            if (dev < 64) fw_attr_done |= 1ull << dev;
+    static unsigned long long fw_attr_done = 0;  // bit = device ordinal
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 64 && ((fw_attr_done >> dev) & 1ull)) return AVD_OK;
+    hipError_t e = hipSuccess;
+    auto opt_in = [&](const void* fn, size_t bytes) { if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
+    opt_in((const void*)fw::fwd_gen_kernel<false, 0>, fw_lds), opt_in((const void*)fw::fwd_gen_kernel<true, 0>, fw_lds);
+    opt_in((const void*)fw::fwd_gen_kernel<false, 1>, fw_lds), opt_in((const void*)fw::fwd_gen_kernel<true, 1>, fw_lds);
+    opt_in((const void*)fw::fwd_gen_kernel<false, 3>, fw_lds), opt_in((const void*)fw::fwd_gen_kernel<true, 2>, fw_lds);
+    opt_in((const void*)fw::fwd_gen_kernel<true, 4>, fw::L_TOTAL_DUAL);
+    opt_in((const void*)fw::dw_gen_kernel<false, 4>, dw_lds), opt_in((const void*)fw::dw_gen_kernel<true, 4>, dw_lds);
+    opt_in((const void*)fw::dw_gen_kernel<false, 8>, dw_lds), opt_in((const void*)fw::dw_gen_kernel<true, 8>, dw_lds);
+    opt_in((const void*)fw::dw_gen_kernel<false, 16>, dw_lds), opt_in((const void*)fw::dw_gen_kernel<true, 16>, dw_lds);
+    opt_in((const void*)fw::dx_gen_kernel<false>, fw::DxL<false>::TOTAL), opt_in((const void*)fw::dx_gen_kernel<true>, fw::DxL<true>::TOTAL);
+    opt_in((const void*)fw::fwd_delta_kernel, fw::DL_TOTAL);
+    if (e != hipSuccess) {
+        set_error("avd_learn_shared_bf16: hipFuncSetAttribute(dynamic LDS %zu B) on device %d: %s", fw_lds, dev, hipGetErrorString(e));
+        return AVD_E_LAUNCH;
+    }
+    if (dev < 64) fw_attr_done |= 1ull << dev;
+    return AVD_OK;
+}
+
+// fw::fwd_gen_kernel's cycle stamps (a build with -DAVD_FW_STAMP): the buffer behind FwdP::stamp and its read-out after a launch
+#ifdef AVD_FW_STAMP
+static unsigned long long* fw_stamp_buffer() {
+    static unsigned long long* d_fst = nullptr;
+    if (!d_fst) (void)hipMalloc(&d_fst, (64 + 256 * 16) * 8);
+    return d_fst;
+}
+static void fw_stamp_report(const fw::FwdP& f, const dim3& grid, hipStream_t st) {
+    static int printed = 0;
+    if (printed >= 4 && printed < 8) {  // (the second learn call's four forward passes)
+        static unsigned long long hst[64 + 256 * 16];
+        (void)hipStreamSynchronize(st);
+        (void)hipMemcpy(hst, f.stamp, sizeof(hst), hipMemcpyDeviceToHost);
+        for (int w_ = 0; w_ < 8; ++w_)
+            fprintf(stderr, "fwd_gen wave %d: prepare %llu barrier %llu multiply %llu barrier %llu | boundary: drain %llu epilogue %llu flush+init %llu  (P2 %d) cycles, pair 0\n", w_,
+                    hst[w_ * 8], hst[w_ * 8 + 1], hst[w_ * 8 + 2], hst[w_ * 8 + 3], hst[w_ * 8 + 4], hst[w_ * 8 + 5], hst[w_ * 8 + 6], f.P2 != nullptr);
+        // tile boundaries of pair 0 on the real-time counter (10 ns units, relative to the first)
+        unsigned long long t0 = ~0ull;
+        const int nb = (int)grid.x;
+        for (int b = 0; b < nb; ++b) t0 = hst[64 + b * 16] < t0 ? hst[64 + b * 16] : t0;
+        for (int k = 2; k < 5; ++k) {
+            fprintf(stderr, "fwd_gen tile %d epilogue start (end) per workgroup, x10 ns:", k);
+            for (int b = 0; b < nb; b += 5) fprintf(stderr, " %llu(%llu)", hst[64 + (b * 8 + k) * 2] - t0, hst[64 + (b * 8 + k) * 2 + 1] - hst[64 + (b * 8 + k) * 2]);
+            fprintf(stderr, "\n");
         }
     }
-    // ---- per-net operand preparation: BN tables, folded/transposed bf16 weights, output-layer vectors
+    ++printed;
+}
+#else
+static unsigned long long* fw_stamp_buffer() { return nullptr; }
+static void fw_stamp_report(const fw::FwdP&, const dim3&, hipStream_t) {}
+#endif
+// one network's prepared operands, and the activation buffers its passes work on
+struct NetOps {
+    bool critic;
+    const float *th, *st;  // [sets][theta_size] (actor block at 0, critic at actor_size), [sets][stats_size]
+    float *inv, *sh, *rs, *mean;  // tables [sets][ldT]: first-layer features at [0, KCp), second layer at [KCp, KCp + H2)
+    bf16 *WT, *Wn;  // (Wn: the input gradient's operand, online nets only)
+    float *bias, *cf, *c0;
+    const void* wf1;  // fused forward: first-layer fragments
+    bf16 *C, *CT, *P2;  // first-layer activations, their transpose, second-layer activations: the online actor's own (kept from pass 2 to pass 3), one set for the other nets
+};
+enum Branch { STATE, ACTION };  // the first layer's input branches: states (S = 3 or 4) -> columns [0, H1), actions (1) -> [H1, H1 + Ha)
+// what a fused forward pass leaves in memory beside its output-layer sums: nothing / the second-layer activations (rank-one form, actor:
+// their relu mask instead) / the critic's signed pre-activations (critic(s, mu) continues from them) / the pass's dZ2 (seed -1/N, critic)
+enum class Keep { nothing, activations, signed_pre, seeded_dz2 };
+// One call's context: layout, plan, path, stream, workspace pointers, set strides, the nets. A member function per launch group.
+struct Learn {
+    const avd_mlp_layout& L;
+    const Plan& pl;
+    const Path path;
+    const hipStream_t st;
+    unsigned char* const ws;
+    const float* row_weight = nullptr;  // (the learner's per-row factor and action bound; unused by the acting entry)
+    float high = 0.f;
+    int sets, Ns, Np, H1, H2, Ha, KC, KCp;
+    long ldT, setC, setCT, setP2, setZT, setWT, setWn, setX;
     NetOps net[4];  // 0 actor, 1 critic, 2 target actor, 3 target critic
-    for (int i = 0; i < 4; ++i) {
+    bf16 *dZ2, *dZ2T, *dZ1;
+    float *q, *y, *dq, *a1, *tt, *da, *u, *cs, *acc, *zbuf, *dcl;
+    bf16* B16(size_t off) const { return (bf16*)(ws + off); }
+    float* F32(size_t off) const { return (float*)(ws + off); }
+    Learn(const avd_mlp_layout& lay, const Plan& plan, const Path& p, void* workspace, void* stream)
+        : L(lay), pl(plan), path(p), st((hipStream_t)stream), ws((unsigned char*)workspace) {
+        const Dims& d = pl.d;
+        sets = d.n_sets, Ns = d.Ns, Np = d.Np, H1 = d.H1, H2 = d.H2, Ha = d.Ha, KC = d.KC, KCp = d.KCp;
+        const long KCn = rup(KC, 256) + 256, H2n = rup(H2, 256);
+        ldT = pl.ldT, setC = (long)Np * KCp, setCT = KCn * Np, setP2 = (long)Np * H2, setZT = H2n * Np, setWT = H2n * KCp, setWn = KCn * H2, setX = (long)Ns * L.S;
+        dZ2 = B16(pl.dZ2), dZ2T = B16(pl.dZ2T), dZ1 = B16(pl.dZ1), q = F32(pl.q), y = F32(pl.y), dq = F32(pl.dq), a1 = F32(pl.a1), tt = F32(pl.tt);
+        da = F32(pl.da), u = F32(pl.u), cs = F32(pl.cs), acc = F32(pl.acc), zbuf = F32(pl.zbuf), dcl = F32(pl.dcl);
+    }
+    // net i reads the slabs th / stats
+    NetOps& bind(int i, const float* th, const float* stats) {
         NetOps& n = net[i];
-        const bool critic = (i & 1), target = (i >= 2);
-        n.th = (target ? theta_t : theta) + (critic ? asz : 0);
-        n.st = target ? stats_t : stats;
+        n.critic = i & 1, n.th = th + (n.critic ? L.actor_size : 0), n.st = stats;
         float* tab = F32(pl.tabs[i]);
         n.inv = tab, n.sh = tab + (long)sets * ldT, n.rs = tab + 2L * sets * ldT, n.mean = tab + 3L * sets * ldT;
-        n.WT = B16(pl.WT[i]), n.Wn = target ? nullptr : B16(pl.Wn[i]);
+        n.WT = B16(pl.WT[i]), n.Wn = i < 2 ? B16(pl.Wn[i]) : nullptr;
         n.bias = F32(pl.bias[i]), n.cf = F32(pl.cf[i]), n.c0 = F32(pl.c0[i]), n.wf1 = ws + pl.wf1[i];
-        const int K = critic ? KC : H1;
-        auto tables = [&](int g, int be, int mm, int mv, int len, int t_off, int pad_to) {
-            hipLaunchKernelGGL(bn_tables_kernel, dim3((unsigned)rup(pad_to, 256) / 256, sets), dim3(256), 0, st, n.th, n.st,
-                               (long)L.theta_size, (long)L.stats_size, g, be, mm, mv, len, n.inv, n.sh, n.rs, n.mean, ldT, t_off,
-                               pad_to);
-        };
-        if (critic) {
-            tables(L.cgs, L.cbes, L.cmms, L.cmvs, H1, 0, H1);
-            tables(L.cga, L.cbea, L.cmma, L.cmva, Ha, H1, KCp - H1);
-            tables(L.cg3, L.cbe3, L.cmm3, L.cmv3, H2, KCp, H2);
-        } else {
-            tables(L.ag1, L.abe1, L.amm1, L.amv1, H1, 0, KCp);
-            tables(L.ag2, L.abe2, L.amm2, L.amv2, H2, KCp, H2);
-        }
-        const int w2 = critic ? L.cW2 : L.aW2, b2 = critic ? L.cb2 : L.ab2, w3 = critic ? L.cW3 : L.aW3, b3 = critic ? L.cb3 : L.ab3;
-        hipLaunchKernelGGL(out_coefs_kernel, dim3(sets), dim3(256), 0, st, n.th, (long)L.theta_size, w3, b3, H2, n.inv + KCp,
-                           n.sh + KCp, ldT, n.cf, n.c0, (long)H2);
-        hipLaunchKernelGGL(prep_w2_kernel, dim3((unsigned)rup(H2, 32) / 32, (unsigned)rup(KCp, 32) / 32, sets), dim3(256), 0, st, n.th,
-                           (long)L.theta_size, w2, K, H2, KCp, n.inv, ldT, n.WT, setWT, n.Wn, setWn, fused_fwd ? 1 : 0,
-                           (r1 && n.Wn) ? n.cf : (const float*)nullptr);
-        if (fused_fwd) {
-            const int nfs = H1 / 32, nft = critic ? KCp / 32 : nfs;
-            hipLaunchKernelGGL(fw::prep_wf1_kernel, dim3((unsigned)nft, sets), dim3(64), 0, st, n.th, (long)L.theta_size, L.S,
-                               critic ? L.cWs : L.aW1, critic ? L.cbs : L.ab1, H1, critic ? L.cWa : 0, critic ? L.cba : 0,
-                               critic ? Ha : 0, nfs, nft, (bf16x8*)(ws + pl.wf1[i]));
-        }
-        hipLaunchKernelGGL(bias2_kernel, dim3((unsigned)rup(H2, 64) / 64, sets), dim3(1024), 0, st, n.th, (long)L.theta_size, w2, b2, K,
-                           H2, n.sh, ldT, n.bias, (long)H2);
+        n.C = B16(i ? pl.C : pl.aC), n.CT = B16(i ? pl.CT : pl.aCT), n.P2 = B16(i ? pl.P2 : pl.aP2);
+        return n;
     }
-    WIDE_CHECK(check_launch("avd_learn_shared_bf16: operand preparation"));
-
-    bf16 *C = B16(pl.C), *CT = B16(pl.CT), *P2 = B16(pl.P2), *dZ2 = B16(pl.dZ2), *dZ2T = B16(pl.dZ2T), *dZ1 = B16(pl.dZ1);
-    // the lambdas below work on whichever activation buffers C / CT / P2 currently point to
-    auto use_actor_buffers = [&](bool yes) {
-        C = B16(yes ? pl.aC : pl.C), CT = B16(yes ? pl.aCT : pl.CT), P2 = B16(yes ? pl.aP2 : pl.P2);
-    };
-    float *q = F32(pl.q), *y = F32(pl.y), *dq = F32(pl.dq), *a1 = F32(pl.a1), *tt = F32(pl.tt), *da = F32(pl.da);
-    float *u = F32(pl.u), *cs = F32(pl.cs), *acc = F32(pl.acc), *zbuf = F32(pl.zbuf);
-    const long setX = (long)Ns * L.S;
-    const dim3 g64((unsigned)1, (unsigned)rup(Np, 64) / 64, sets);
-
-    // first layer: states (S = 3 or 4) or actions (1) -> columns [c0, c0 + H)
-    auto l1 = [&](const NetOps& n, bool critic, bool action, const float* X, long set_x, bool transpose) {
-        const int H = action ? Ha : H1, c0 = action ? H1 : 0;
-        const int Hpad = action ? (KCp - H1) : H1;
-        const int w = critic ? (action ? L.cWa : L.cWs) : L.aW1, b = critic ? (action ? L.cba : L.cbs) : L.ab1;
-        dim3 grid((unsigned)rup(Hpad, 64) / 64, g64.y, sets);
-        bf16* ct = transpose ? CT : nullptr;
-        if (action)
-            hipLaunchKernelGGL((l1_fwd_kernel<1>), grid, dim3(256), 0, st, X, set_x, n.th, (long)L.theta_size, w, b, H, Hpad, c0, Ns,
-                               Np, C, (long)KCp, setC, ct, (long)Np, setCT);
-        else if (L.S == 4)
-            hipLaunchKernelGGL((l1_fwd_kernel<4>), grid, dim3(256), 0, st, X, set_x, n.th, (long)L.theta_size, w, b, H, Hpad, c0, Ns,
-                               Np, C, (long)KCp, setC, ct, (long)Np, setCT);
+    // ---- per-net operand preparation: BN tables, output-layer vectors, folded/transposed bf16 weights
+    void bn_tables(const NetOps& n) {
+        auto tables = [&](int g, int be, int mm, int mv, int len, int t_off, int pad_to) {
+            hipLaunchKernelGGL(bn_tables_kernel, dim3((unsigned)rup(pad_to, 256) / 256, sets), dim3(256), 0, st, n.th, n.st, (long)L.theta_size,
+                               (long)L.stats_size, g, be, mm, mv, len, n.inv, n.sh, n.rs, n.mean, ldT, t_off, pad_to);
+        };
+        if (n.critic)
+            tables(L.cgs, L.cbes, L.cmms, L.cmvs, H1, 0, H1), tables(L.cga, L.cbea, L.cmma, L.cmva, Ha, H1, KCp - H1), tables(L.cg3, L.cbe3, L.cmm3, L.cmv3, H2, KCp, H2);
         else
-            hipLaunchKernelGGL((l1_fwd_kernel<3>), grid, dim3(256), 0, st, X, set_x, n.th, (long)L.theta_size, w, b, H, Hpad, c0, Ns,
-                               Np, C, (long)KCp, setC, ct, (long)Np, setCT);
-    };
-    // second layer forward: P2 = relu(C @ WT^T + bias)
+            tables(L.ag1, L.abe1, L.amm1, L.amv1, H1, 0, KCp), tables(L.ag2, L.abe2, L.amm2, L.amv2, H2, KCp, H2);
+    }
+    void out_coefs(const NetOps& n) {
+        hipLaunchKernelGGL(out_coefs_kernel, dim3(sets), dim3(256), 0, st, n.th, (long)L.theta_size, n.critic ? L.cW3 : L.aW3,
+                           n.critic ? L.cb3 : L.ab3, H2, n.inv + KCp, n.sh + KCp, ldT, n.cf, n.c0, (long)H2);
+    }
+    void w2_operands(const NetOps& n) {
+        const int K = n.critic ? KC : H1, w2 = n.critic ? L.cW2 : L.aW2;
+        hipLaunchKernelGGL(prep_w2_kernel, dim3((unsigned)rup(H2, 32) / 32, (unsigned)rup(KCp, 32) / 32, sets), dim3(256), 0, st, n.th,
+                           (long)L.theta_size, w2, K, H2, KCp, n.inv, ldT, n.WT, setWT, n.Wn, setWn, path.fused_fwd ? 1 : 0,
+                           (path.r1 && n.Wn) ? n.cf : (const float*)nullptr);  // (rank-one form: cf rides in Wn, so out_coefs runs first)
+        if (path.fused_fwd) {
+            const int nfs = H1 / 32, nft = n.critic ? KCp / 32 : nfs;
+            hipLaunchKernelGGL(fw::prep_wf1_kernel, dim3((unsigned)nft, sets), dim3(64), 0, st, n.th, (long)L.theta_size, L.S, n.critic ? L.cWs : L.aW1,
+                               n.critic ? L.cbs : L.ab1, H1, n.critic ? L.cWa : 0, n.critic ? L.cba : 0, n.critic ? Ha : 0, nfs, nft, (bf16x8*)n.wf1);
+        }
+        hipLaunchKernelGGL(bias2_kernel, dim3((unsigned)rup(H2, 64) / 64, sets), dim3(1024), 0, st, n.th, (long)L.theta_size, w2,
+                           n.critic ? L.cb2 : L.ab2, K, H2, n.sh, ldT, n.bias, (long)H2);
+    }
+    void prepare_net(const NetOps& n) { bn_tables(n), out_coefs(n), w2_operands(n); }
+
+    // ---- forward
+    void fill_rows(float* z, const float* c0) {  // z[set][row] = c0[set]: the output-layer sums start from the bias term
+        hipLaunchKernelGGL(fill_rows_kernel, dim3((unsigned)rup(Np, 256) / 256, sets), dim3(256), 0, st, z, (long)Np, c0, Np);
+    }
+    // first layer of one branch -> its columns of n.C; transposed: and of n.CT (a weight-gradient GEMM follows)
+    void l1(const NetOps& n, Branch b, const float* X, long set_x, bool transposed) {
+        const bool action = b == ACTION;
+        const int H = action ? Ha : H1, c0 = action ? H1 : 0, Hpad = action ? (KCp - H1) : H1;
+        const int w = n.critic ? (action ? L.cWa : L.cWs) : L.aW1, bo = n.critic ? (action ? L.cba : L.cbs) : L.ab1;
+        dim3 grid((unsigned)rup(Hpad, 64) / 64, (unsigned)rup(Np, 64) / 64, sets);
+        bf16* ct = transposed ? n.CT : nullptr;
+#define AVD_L1_LAUNCH(KIN)                                                                                                          \
+    hipLaunchKernelGGL((l1_fwd_kernel<KIN>), grid, dim3(256), 0, st, X, set_x, n.th, (long)L.theta_size, w, bo, H, Hpad, c0, Ns, Np, \
+                       n.C, (long)KCp, setC, ct, (long)Np, setCT)
+        if (action) AVD_L1_LAUNCH(1); else if (L.S == 4) AVD_L1_LAUNCH(4); else AVD_L1_LAUNCH(3);
+#undef AVD_L1_LAUNCH
+    }
     // fused: first layer + second layer + output-layer dot from the raw inputs (X, act): C is not read
-    // mu2 != NULL (critic): critic(s, act) AND critic(s, mu2) in one pass (fw::fwd_gen_kernel EPI 4): q(s, act) -> q, its relu mask -> the
-    // dZ2 buffer; q(s, mu2) -> zbuf, the action gradient -> da
-    auto l2f = [&](const NetOps& n, bool critic, const float* X, const float* act, long set_act, bool keep_p2, bool dz_out = false,
-                   bool store_pre = false, const float* mu2 = nullptr) {
+    fw::FwdP fwd_params(const NetOps& n, const float* X, const float* act, long set_act) {
         fw::FwdP f;
-        f.mu = mu2, f.setMu = Np, f.z2 = zbuf, f.da = da, f.setDa = Np, f.wa = n.th + L.cWa, f.setTh = L.theta_size, f.Ha = Ha;
-        f.X = X, f.setX = setX, f.act = critic ? act : nullptr, f.setAct = set_act;
-        f.wf1 = (const bf16x8*)n.wf1, f.nfs = H1 / 32, f.nft = critic ? KCp / 32 : H1 / 32;
+        f.mu = nullptr, f.setMu = Np, f.z2 = zbuf, f.da = da, f.setDa = Np, f.wa = n.th + L.cWa, f.setTh = L.theta_size, f.Ha = Ha;
+        f.X = X, f.setX = setX, f.act = n.critic ? act : nullptr, f.setAct = set_act;
+        f.wf1 = (const bf16x8*)n.wf1, f.nfs = H1 / 32, f.nft = n.critic ? KCp / 32 : H1 / 32;
         f.WT = n.WT, f.setWT = setWT, f.ldw = KCp, f.bias = n.bias, f.cf = n.cf, f.c0 = n.c0;
-        f.P2 = keep_p2 ? (dz_out ? dZ2 : P2) : nullptr, f.setP2 = setP2, f.z = critic ? q : zbuf, f.setZ = Np, f.Ns = Ns, f.Np = Np, f.H2 = H2, f.n_sets = sets;
-        f.dz_scale = dz_out ? -1.0f / (float)Ns : 0.f, f.rw = row_weight, f.store_pre = store_pre ? 1 : 0;
-        f.mask_out = (r1 && !critic && keep_p2) ? 1 : 0;  // (rank-one backward: the actor's pass leaves its relu mask, nothing reads its activations)
-        static const char* dbg_env = AVD_DIAG_ENV("FW_DBG");
-        f.dbg = dbg_env ? atoi(dbg_env) : 0;
-        f.stamp = nullptr;
-#ifdef AVD_FW_STAMP
-        static unsigned long long* d_fst = nullptr;
-        if (!d_fst) (void)hipMalloc(&d_fst, (64 + 256 * 16) * 8);
-        f.stamp = d_fst;
-#endif
-        if (H2 > fw::GC)
-            hipLaunchKernelGGL(fill_rows_kernel, dim3((unsigned)rup(Np, 256) / 256, sets), dim3(256), 0, st, f.z, (long)Np, n.c0, Np);
-        const dim3 grid((unsigned)std::min<long>(avd::fset::cu_count(), Np / fw::GR));
-        // the epilogue is a compile-time choice (fw::fwd_gen_kernel): nothing stored / signed bf16(z2) (critic) / relu mask (actor); the
+        f.P2 = nullptr, f.setP2 = setP2, f.z = n.critic ? q : zbuf, f.setZ = Np, f.Ns = Ns, f.Np = Np, f.H2 = H2, f.n_sets = sets;
+        f.dz_scale = 0.f, f.rw = row_weight, f.store_pre = 0, f.mask_out = 0;
+        f.dbg = knobs().fw_dbg, f.stamp = fw_stamp_buffer();
+        return f;
+    }
+    dim3 fwd_grid() const { return dim3((unsigned)std::min<long>(avd::fset::cu_count(), Np / fw::GR)); }
+    int l2_fused(const NetOps& n, const float* X, const float* act, long set_act, Keep keep) {
+        fw::FwdP f = fwd_params(n, X, act, set_act);
+        f.P2 = keep == Keep::nothing ? nullptr : keep == Keep::seeded_dz2 ? dZ2 : n.P2;
+        f.dz_scale = keep == Keep::seeded_dz2 ? -1.0f / (float)Ns : 0.f, f.store_pre = keep == Keep::signed_pre ? 1 : 0;
+        f.mask_out = (path.r1 && !n.critic && keep != Keep::nothing) ? 1 : 0;  // (rank-one backward: the actor's pass leaves its relu mask, nothing reads its activations)
+        if (H2 > fw::GC) fill_rows(f.z, n.c0);
+        // the epilogue is a compile-time choice (fw::fwd_gen_kernel): 1 nothing stored / 2 signed bf16(z2) (critic) / 3 relu mask (actor); 0 the
         // run-time-flag form for what is left (relu'd activations, dZ2 out: the layer-wise backward's operands)
-        static const char* epi_env = AVD_DIAG_ENV("WIDE_FWD_EPI0");  // diagnostics: =1 the r03 epilogue everywhere (A/B)
-        const bool epi0 = epi_env && epi_env[0] == '1';
-        if (mu2) {
-            f.P2 = dZ2, f.dz_scale = -1.0f / (float)Ns, f.store_pre = 0, f.mask_out = 1;
-            hipLaunchKernelGGL(fill_rows_kernel, dim3((unsigned)rup(Np, 256) / 256, sets), dim3(256), 0, st, f.z2, (long)Np, n.c0, Np);
-            (void)hipMemsetAsync(da, 0, sizeof(float) * sets * Np, st);
-            hipLaunchKernelGGL((fw::fwd_gen_kernel<true, 4>), grid, dim3(fw::FT), (size_t)fw::L_TOTAL_DUAL, st, f);
-        } else if (!f.P2 && !epi0) {
-            if (critic)
-                hipLaunchKernelGGL((fw::fwd_gen_kernel<true, 1>), grid, dim3(fw::FT), fw_lds, st, f);
-            else
-                hipLaunchKernelGGL((fw::fwd_gen_kernel<false, 1>), grid, dim3(fw::FT), fw_lds, st, f);
-        } else if (critic && f.store_pre && f.dz_scale == 0.f && !epi0) {
-            hipLaunchKernelGGL((fw::fwd_gen_kernel<true, 2>), grid, dim3(fw::FT), fw_lds, st, f);
-        } else if (!critic && f.mask_out && f.dz_scale == 0.f && !epi0) {
-            hipLaunchKernelGGL((fw::fwd_gen_kernel<false, 3>), grid, dim3(fw::FT), fw_lds, st, f);
-        } else if (critic) {
-            hipLaunchKernelGGL((fw::fwd_gen_kernel<true, 0>), grid, dim3(fw::FT), fw_lds, st, f);
-        } else {
-            hipLaunchKernelGGL((fw::fwd_gen_kernel<false, 0>), grid, dim3(fw::FT), fw_lds, st, f);
-        }
-#ifdef AVD_FW_STAMP
-        {
-            static int printed = 0;
-            if (printed >= 4 && printed < 8) {  // (the second learn call's four forward passes)
-                static unsigned long long hst[64 + 256 * 16];
-                (void)hipStreamSynchronize(st);
-                (void)hipMemcpy(hst, f.stamp, sizeof(hst), hipMemcpyDeviceToHost);
-                for (int w_ = 0; w_ < 8; ++w_)
-                    fprintf(stderr, "fwd_gen wave %d: prepare %llu barrier %llu multiply %llu barrier %llu | boundary: drain %llu epilogue %llu flush+init %llu  (P2 %d) cycles, pair 0\n", w_,
-                            hst[w_ * 8], hst[w_ * 8 + 1], hst[w_ * 8 + 2], hst[w_ * 8 + 3], hst[w_ * 8 + 4], hst[w_ * 8 + 5], hst[w_ * 8 + 6], f.P2 != nullptr);
-                // tile boundaries of pair 0 on the real-time counter (10 ns units, relative to the first)
-                unsigned long long t0 = ~0ull;
-                const int nb = (int)grid.x;
-                for (int b = 0; b < nb; ++b) t0 = hst[64 + b * 16] < t0 ? hst[64 + b * 16] : t0;
-                for (int k = 2; k < 5; ++k) {
-                    fprintf(stderr, "fwd_gen tile %d epilogue start (end) per workgroup, x10 ns:", k);
-                    for (int b = 0; b < nb; b += 5) fprintf(stderr, " %llu(%llu)", hst[64 + (b * 8 + k) * 2] - t0, hst[64 + (b * 8 + k) * 2 + 1] - hst[64 + (b * 8 + k) * 2]);
-                    fprintf(stderr, "\n");
-                }
-            }
-            ++printed;
-        }
-#endif
+        const int epi = knobs().fwd_epi0 ? 0 : keep == Keep::nothing ? 1 : (n.critic && keep == Keep::signed_pre) ? 2 : (keep == Keep::activations && f.mask_out) ? 3 : 0;
+        const dim3 grid = fwd_grid();
+#define AVD_FWD_LAUNCH(C, E) hipLaunchKernelGGL((fw::fwd_gen_kernel<C, E>), grid, dim3(fw::FT), (size_t)fw::L_TOTAL, st, f)
+        if (epi == 2) AVD_FWD_LAUNCH(true, 2);
+        else if (epi == 3) AVD_FWD_LAUNCH(false, 3);
+        else if (epi == 1) { if (n.critic) AVD_FWD_LAUNCH(true, 1); else AVD_FWD_LAUNCH(false, 1); }
+        else { if (n.critic) AVD_FWD_LAUNCH(true, 0); else AVD_FWD_LAUNCH(false, 0); }
+#undef AVD_FWD_LAUNCH
+        fw_stamp_report(f, grid, st);
         return check_launch("avd_learn_shared_bf16: fused forward");
-    };
-    auto l2 = [&](const NetOps& n, bool critic) {
-        GemmP p = {C, n.WT, KCp, KCp, setC, setWT, Ns, H2, critic ? KCp : (int)rup(H1, 64), 1};
+    }
+    // critic(s, act) AND critic(s, mu = a1) in one pass (fw::fwd_gen_kernel EPI 4): q(s, act) -> q, its relu mask -> the dZ2 buffer (pass 1's
+    // backward operand); q(s, mu) -> zbuf, the action gradient dq / d mu -> da
+    int l2_dual(const NetOps& n, const float* X, const float* act, long set_act) {
+        fw::FwdP f = fwd_params(n, X, act, set_act);
+        f.mu = a1, f.P2 = dZ2, f.dz_scale = -1.0f / (float)Ns, f.mask_out = 1;
+        if (H2 > fw::GC) fill_rows(f.z, n.c0);
+        fill_rows(f.z2, n.c0);
+        (void)hipMemsetAsync(da, 0, sizeof(float) * sets * Np, st);
+        const dim3 grid = fwd_grid();
+        hipLaunchKernelGGL((fw::fwd_gen_kernel<true, 4>), grid, dim3(fw::FT), (size_t)fw::L_TOTAL_DUAL, st, f);
+        fw_stamp_report(f, grid, st);
+        return check_launch("avd_learn_shared_bf16: fused forward");
+    }
+    // second layer forward, layer-wise: P2 = relu(C @ WT^T + bias)
+    int l2_gemm(const NetOps& n, const char* who = "avd_learn_shared_bf16: forward GEMM") {
+        GemmP p = {n.C, n.WT, KCp, KCp, setC, setWT, Ns, H2, n.critic ? KCp : (int)rup(H1, 64), 1};
         // the output layer rides on the GEMM epilogue: q (critic) or z (actor, in `da`-free scratch `zbuf`) = c0 + P2 . cf
-        float* zdst = critic ? q : zbuf;
-        hipLaunchKernelGGL(fill_rows_kernel, dim3((unsigned)rup(Np, 256) / 256, sets), dim3(256), 0, st, zdst, (long)Np, n.c0, Np);
-        EpiFwd e = {P2, H2, setP2, n.bias, H2, n.cf, zdst, (long)Np};
-        return launch_gemm(p, e, sets, st, "avd_learn_shared_bf16: forward GEMM");
-    };
-    auto out_layer = [&](const NetOps&, int mode, float* out) {
-        if (mode == 1)  // actor head; the critic's q is complete once the GEMM has run
-            hipLaunchKernelGGL(tanh_rows_kernel, dim3((unsigned)rup(Ns, 256) / 256, sets), dim3(256), 0, st, zbuf, (long)Np, Ns, high,
-                               out, tt);
-    };
-    auto rows = [&](int mode, const float* qv, const float* yt, const float* rd, float gh, float* out) {
+        float* zdst = n.critic ? q : zbuf;
+        fill_rows(zdst, n.c0);
+        EpiFwd e = {n.P2, H2, setP2, n.bias, H2, n.cf, zdst, (long)Np};
+        return launch_gemm(p, e, sets, st, who);
+    }
+    void actor_head() {  // a1 = tanh(zbuf) * high (tt: the tanh, for its backward); the critic's q is complete once its second layer has run
+        hipLaunchKernelGGL(tanh_rows_kernel, dim3((unsigned)rup(Ns, 256) / 256, sets), dim3(256), 0, st, zbuf, (long)Np, Ns, high, a1, tt);
+    }
+    // A whole forward pass of n: q (critic) or a1 (actor). kept: a layer-wise backward pass follows -- both layers' activations stay, the first
+    // layer's with their transposes, whichever way the second runs (the fused form generates the first layer itself and reads no copy in memory).
+    int forward(const NetOps& n, const float* X, const float* act, long set_act, bool kept) {
+        if (!path.fused_fwd || kept) {
+            l1(n, STATE, X, setX, kept);
+            if (n.critic) l1(n, ACTION, act, set_act, kept);
+        }
+        if (path.fused_fwd)  // (the critic(s, a) pass of a learn keeps the sign on its stored activations: critic(s, mu) continues from them)
+            WIDE_CHECK(l2_fused(n, X, act, set_act, !kept ? Keep::nothing : (n.critic && path.fused_delta) ? Keep::signed_pre : Keep::activations));
+        else
+            WIDE_CHECK(l2_gemm(n));
+        if (!n.critic) actor_head();
+        return AVD_OK;
+    }
+    // critic(s, mu) as a delta: z2(mu) = z2(a) + W2[action] (f(mu) - f(a)): 4 k-steps on top of the stored critic(s, a) activations; -> q, da
+    int delta(const float* a) {
+        const NetOps& n = net[1];
+        fill_rows(q, n.c0);
+        fw::DeltaP dl;
+        dl.Zin = n.P2, dl.setZ = setP2, dl.a = a, dl.mu = a1, dl.setA = Ns, dl.setMu = Np, dl.wf1 = (const bf16x8*)n.wf1, dl.nft = KCp / 32,
+        dl.nfs = H1 / 32, dl.WT = n.WT, dl.setWT = setWT, dl.ldw = KCp, dl.cf = n.cf, dl.z = q, dl.setQ = Np;
+        dl.dz_scale = -1.0f / (float)Ns, dl.rw = row_weight, dl.Ns = Ns, dl.Np = Np, dl.H2 = H2, dl.H1 = H1, dl.n_sets = sets;
+        dl.Wn = n.Wn, dl.setWn = setWn, dl.cf_in_wn = path.r1 ? 1 : 0, dl.inv = n.inv, dl.setTab = ldT, dl.th = n.th, dl.setTh = L.theta_size, dl.wa_off = L.cWa, dl.Ha = Ha;
+        dl.da = da, dl.setDa = Np;
+        dl.Mk = path.r1 ? dZ2 : nullptr;  // (critic(s, a)'s relu mask, for the critic's rank-one backward)
+        (void)hipMemsetAsync(da, 0, sizeof(float) * sets * Np, st);
+        hipLaunchKernelGGL(fw::fwd_delta_kernel, dim3((unsigned)std::min<long>(2 * avd::fset::cu_count(), Np / fw::FR)), dim3(fw::FT),
+                           (size_t)fw::DL_TOTAL, st, dl);
+        return check_launch("avd_learn_shared_bf16: critic(s, mu) as a delta");
+    }
+    void rows(int mode, const float* qv, const float* yt, const float* rd, float gh, float* out) {
         hipLaunchKernelGGL(rows_kernel, dim3((unsigned)(rup(Ns, ROWS_PER_BLOCK) / ROWS_PER_BLOCK), sets), dim3(256), 0, st, mode, Ns, (long)Np, qv, yt, rd, gh,
                            out, acc, row_weight);
-    };
-    // Note on row-vector strides: r arrives as [sets][Ns] (stride Ns), internal vectors use stride Np. The TD kernel
-    // reads r with the internal stride, so r is first copied into `da` (free at that point) with the padded stride.
-    // `transpose` = a backward pass follows: the first-layer activations (and their transposes) are materialised for it
-    auto actor_forward = [&](const NetOps& n, const float* X, bool transpose) {
-        // (fused: the forward generates the first layer, dw_gen generates it again, dx_gen regenerates it: no copy in memory)
-        if (!fused_fwd || (transpose && !(fused_dw && fused_dx))) l1(n, false, false, X, setX, transpose && !fused_dw);
-        if (fused_fwd)
-            WIDE_CHECK(l2f(n, false, X, nullptr, 0, transpose));
-        else
-            WIDE_CHECK(l2(n, false));
-        out_layer(n, 1, a1);
-        return AVD_OK;
-    };
-    auto critic_forward = [&](const NetOps& n, const float* X, const float* act, long set_act, bool transpose) {
-        if (!fused_fwd || (transpose && !(fused_dw && fused_dx))) {
-            l1(n, true, false, X, setX, transpose && !fused_dw);
-            l1(n, true, true, act, set_act, transpose && !fused_dw);
+    }
+    void dump_pass2(const float* q_mu) {
+#ifdef AVD_DIAG
+        if (const char* dump = getenv("AVD_WIDE_DUMP")) {  // diagnostics: q(s, mu) and the action gradient of this call, [sets][Np] f32 each
+            std::vector<float> hb(3 * (size_t)sets * Np);
+            (void)hipStreamSynchronize(st);
+            (void)hipMemcpy(hb.data(), q_mu, sizeof(float) * sets * Np, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(hb.data() + (size_t)sets * Np, da, sizeof(float) * sets * Np, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(hb.data() + 2 * (size_t)sets * Np, a1, sizeof(float) * sets * Np, hipMemcpyDeviceToHost);
+            if (FILE* f = fopen(dump, "wb")) fwrite(hb.data(), sizeof(float), hb.size(), f), fclose(f);
         }
-        if (fused_fwd)  // (the critic(s, a) pass of a learn keeps the sign on its stored activations: critic(s, mu) continues from them)
-            WIDE_CHECK(l2f(n, true, X, act, set_act, transpose, false, transpose && fused_delta));
-        else
-            WIDE_CHECK(l2(n, true));
-        out_layer(n, 0, q);
-        return AVD_OK;
-    };
-    // backward of layers 3 and 2 of `n` given the seed d[n]; weight gradients when `wg`
-    auto backward = [&](const NetOps& n, bool critic, const float* dvec, bool wg, int acc_idx, float* gnet, const float* bX = nullptr,
-                        const float* bAct = nullptr, long bSetAct = 0) {
-        (void)hipMemsetAsync(u, 0, sizeof(float) * sets * H2, st);
-        (void)hipMemsetAsync(cs, 0, sizeof(float) * sets * H2, st);
-        const int K = critic ? KC : H1;
-        const int w3 = critic ? L.cW3 : L.aW3, b3 = critic ? L.cb3 : L.ab3, gg = critic ? L.cg3 : L.ag2,
-                  gbe = critic ? L.cbe3 : L.abe2, gb2 = critic ? L.cb2 : L.ab2;
-        if (!fused_dw)
-            hipLaunchKernelGGL(out_bwd_kernel, dim3((unsigned)rup(H2, 64) / 64, g64.y, sets), dim3(256), 0, st, P2, (long)H2, setP2, dvec,
-                               (long)Np, n.cf, (long)H2, H2, Ns, Np, dZ2, wg ? dZ2T : nullptr, (long)Np, setZT, u, cs, (long)H2, 0);
-        if (wg) {
-            if (!fused_dw)
-                hipLaunchKernelGGL(out_grads_kernel, dim3((unsigned)rup(H2, 256) / 256, sets), dim3(256), 0, st, n.th, (long)L.theta_size, w3,
-                                   H2, n.inv + KCp, n.sh + KCp, n.rs + KCp, n.mean + KCp, ldT, u, cs, (long)H2, acc, acc_idx, gnet,
-                                   (long)L.theta_size, w3, b3, gg, gbe, gb2, 1);
-            if (fused_dw) {
-                // rank-one form: the rows' records (|d| x, sign words, d), then G and S2 from the relu mask (critic: left in the dZ2 buffer
-                // by fw::fwd_delta_kernel; actor: stored by its forward pass in place of the activations) -- fw::dw_gen_kernel: first layer
-                // generated per 32-row chunk, mask streamed --, then u, db2 and the cf / sh terms of dW2
-                unsigned char* aux = ws + pl.dZ2T;  // (the transposed gradient matrix of the layer-wise path: free here)
-                const long setAux = (long)(Np / fw::FK + 2) * fw::AUX_REC;  // (+ one record of slack: the stream reads 512 B past the last)
-                hipLaunchKernelGGL(fw::aux_pack_kernel, dim3((unsigned)(Np / fw::FK + 1), sets), dim3(64), 0, st, bX, setX,
-                                   critic ? bAct : (const float*)nullptr, bSetAct, dvec, (long)Np, Ns, Np, aux, setAux, F32(pl.dcl));
-                fw::DwP d2;
-                d2.aux = aux, d2.setAux = setAux;
-                d2.wf1 = (const bf16x8*)n.wf1, d2.nfs = H1 / 32, d2.nft = critic ? KCp / 32 : H1 / 32;
-                d2.ZT = critic ? dZ2 : P2, d2.setZT = setP2, d2.ldz = H2, d2.inv = n.inv, d2.setTab = ldT, d2.s2 = cs;
-                d2.dW = gnet + (critic ? L.cW2 : L.aW2), d2.setW = L.theta_size;
-                d2.Ns = Ns, d2.Np = Np, d2.H2 = H2, d2.K = K, d2.n_sets = sets, d2.nsplit = 8;
-                {   // row ranges per (set, column block): the split whose items fill whole rounds of an XCD's workgroups best
-                    // (rounds x chunks per item; the smaller split on a tie: fewer epilogues)
-                    const int nfb_ = (d2.nft * 32 + 127) / 128, wgs = std::max(1, avd::fset::cu_count() / 8);
-                    long best = -1;
-                    for (int ns = 8; ns <= 32; ns *= 2) {
-                        if (Np % (ns * 32) != 0 || Np / (ns * 32) < 2) continue;
-                        const long items = ((long)sets * (H2 / fw::FC) * ns + 7) / 8 * nfb_;
-                        const long cost = (items + wgs - 1) / wgs * (Np / (ns * 32));
-                        if (best < 0 || cost < best) best = cost, d2.nsplit = ns;
-                    }
-                }
-                const int nfb = (d2.nft * 32 + 127) / 128, items = sets * (H2 / fw::FC) * d2.nsplit * nfb;
-                (void)items;
-                const dim3 grid((unsigned)(avd::fset::cu_count() / 8 * 8));  // (a multiple of the XCD count: see the kernel's item map)
-                // (the rows of a chunk are shared by the first min(8, H1 / 128) feature blocks of a stream for the S2 sum)
-                const int nshare = std::min(8, H1 / 128);
+#endif
+    }
+    // ---- backward of layers 3 and 2 of n given the seed dvec
+    void zero_u_cs() { (void)hipMemsetAsync(u, 0, sizeof(float) * sets * H2, st), (void)hipMemsetAsync(cs, 0, sizeof(float) * sets * H2, st); }
+    void out_grads(const NetOps& n, float* gnet, int acc_idx) {
+        const int w3 = n.critic ? L.cW3 : L.aW3;
+        hipLaunchKernelGGL(out_grads_kernel, dim3((unsigned)rup(H2, 256) / 256, sets), dim3(256), 0, st, n.th, (long)L.theta_size, w3, H2, n.inv + KCp,
+                           n.sh + KCp, n.rs + KCp, n.mean + KCp, ldT, u, cs, (long)H2, acc, acc_idx, gnet, (long)L.theta_size, w3,
+                           n.critic ? L.cb3 : L.ab3, n.critic ? L.cg3 : L.ag2, n.critic ? L.cbe3 : L.abe2, n.critic ? L.cb2 : L.ab2, 1);
+    }
+    // layer-wise: dZ2 from the stored activations (out_bwd_kernel); gnet != NULL: the weight gradients of both layers too
+    int backward_layerwise(const NetOps& n, const float* dvec, float* gnet, int acc_idx) {
+        zero_u_cs();
+        hipLaunchKernelGGL(out_bwd_kernel, dim3((unsigned)rup(H2, 64) / 64, (unsigned)rup(Np, 64) / 64, sets), dim3(256), 0, st, n.P2, (long)H2, setP2, dvec,
+                           (long)Np, n.cf, (long)H2, H2, Ns, Np, dZ2, gnet ? dZ2T : nullptr, (long)Np, setZT, u, cs, (long)H2, 0);
+        if (!gnet) return AVD_OK;
+        out_grads(n, gnet, acc_idx);
+        // dW2 = inv (.) (C^T dZ2) + sh (x) db2: reduction over the rows, split into chunks with f32 atomics
+        int ksplit = 1;
+        while (Np / ksplit > 16384 && Np % (ksplit * 2 * BK) == 0) ksplit *= 2;  // f32 atomics cost ~ one MFMA K-chunk of 4096
+        GemmP p = {n.CT, dZ2T, Np, Np, setCT, setZT, n.critic ? KC : H1, H2, Np / ksplit, ksplit};
+        EpiDw e = {gnet + (n.critic ? L.cW2 : L.aW2), H2, (long)L.theta_size, n.inv, n.sh, cs, ldT, H2, 1.0f};
+        return launch_gemm(p, e, sets, st, "avd_learn_shared_bf16: weight-gradient GEMM");
+    }
+    // row ranges per (set, column block) of fw::dw_gen_kernel: the split whose items fill whole rounds of an XCD's workgroups best
+    // (rounds x chunks per item; the smaller split on a tie: fewer epilogues)
+    int dw_nsplit(int nft) const {
+        const int nfb = (nft * 32 + 127) / 128, wgs = std::max(1, avd::fset::cu_count() / 8);
+        int nsplit = 8;
+        long best = -1;
+        for (int ns = 8; ns <= 32; ns *= 2) {
+            if (Np % (ns * 32) != 0 || Np / (ns * 32) < 2) continue;
+            const long items = ((long)sets * (H2 / fw::FC) * ns + 7) / 8 * nfb;
+            const long cost = (items + wgs - 1) / wgs * (Np / (ns * 32));
+            if (best < 0 || cost < best) best = cost, nsplit = ns;
+        }
+        return nsplit;
+    }
+    // rank-one form: the rows' records (|d| x, sign words, d), then G and S2 from the relu mask (critic: left in the dZ2 buffer
+    // by its forward pass; actor: stored by its forward pass in place of the activations) -- fw::dw_gen_kernel: first layer
+    // generated per 32-row chunk, mask streamed --, then u, db2 and the cf / sh terms of dW2. Always with the weight gradients.
+    int backward_rank1(const NetOps& n, const float* dvec, float* gnet, int acc_idx, const float* X, const float* act, long set_act) {
+        zero_u_cs();
+        const int K = n.critic ? KC : H1;
+        unsigned char* aux = ws + pl.dZ2T;  // (the transposed gradient matrix of the layer-wise path: free here)
+        const long setAux = (long)(Np / fw::FK + 2) * fw::AUX_REC;  // (+ one record of slack: the stream reads 512 B past the last)
+        hipLaunchKernelGGL(fw::aux_pack_kernel, dim3((unsigned)(Np / fw::FK + 1), sets), dim3(64), 0, st, X, setX,
+                           n.critic ? act : (const float*)nullptr, set_act, dvec, (long)Np, Ns, Np, aux, setAux, dcl);
+        fw::DwP d2;
+        d2.aux = aux, d2.setAux = setAux;
+        d2.wf1 = (const bf16x8*)n.wf1, d2.nfs = H1 / 32, d2.nft = n.critic ? KCp / 32 : H1 / 32;
+        d2.ZT = n.critic ? dZ2 : n.P2, d2.setZT = setP2, d2.ldz = H2, d2.inv = n.inv, d2.setTab = ldT, d2.s2 = cs;
+        d2.dW = gnet + (n.critic ? L.cW2 : L.aW2), d2.setW = L.theta_size;
+        d2.Ns = Ns, d2.Np = Np, d2.H2 = H2, d2.K = K, d2.n_sets = sets, d2.nsplit = dw_nsplit(d2.nft);
+        const dim3 grid((unsigned)(avd::fset::cu_count() / 8 * 8));  // (a multiple of the XCD count: see the kernel's item map)
+        constexpr size_t dw_lds = (size_t)fw::FSTG * fw::DW_STG;
+        // (the rows of a chunk are shared by the first min(8, H1 / 128) feature blocks of a stream for the S2 sum)
+        const int nshare = std::min(8, H1 / 128);
 #define AVD_DW_LAUNCH(C, R) hipLaunchKernelGGL((fw::dw_gen_kernel<C, R>), grid, dim3(fw::FT), dw_lds, st, d2)
-                if (nshare == 8) {
-                    if (critic) AVD_DW_LAUNCH(true, 4); else AVD_DW_LAUNCH(false, 4);
-                } else if (nshare == 4) {
-                    if (critic) AVD_DW_LAUNCH(true, 8); else AVD_DW_LAUNCH(false, 8);
-                } else {
-                    if (critic) AVD_DW_LAUNCH(true, 16); else AVD_DW_LAUNCH(false, 16);
-                }
+        if (nshare == 8) { if (n.critic) AVD_DW_LAUNCH(true, 4); else AVD_DW_LAUNCH(false, 4); }
+        else if (nshare == 4) { if (n.critic) AVD_DW_LAUNCH(true, 8); else AVD_DW_LAUNCH(false, 8); }
+        else { if (n.critic) AVD_DW_LAUNCH(true, 16); else AVD_DW_LAUNCH(false, 16); }
 #undef AVD_DW_LAUNCH
-                hipLaunchKernelGGL(w2_post_kernel, dim3((unsigned)rup(H2, 64) / 64, sets), dim3(1024), 0, st, n.th, (long)L.theta_size,
-                                   critic ? L.cW2 : L.aW2, K, H2, n.sh, ldT, n.bias, n.cf, gnet, (long)L.theta_size, u, cs, (long)H2);
-                hipLaunchKernelGGL(out_grads_kernel, dim3((unsigned)rup(H2, 256) / 256, sets), dim3(256), 0, st, n.th, (long)L.theta_size, w3,
-                                   H2, n.inv + KCp, n.sh + KCp, n.rs + KCp, n.mean + KCp, ldT, u, cs, (long)H2, acc, acc_idx, gnet,
-                                   (long)L.theta_size, w3, b3, gg, gbe, gb2, 1);
-                return check_launch("avd_learn_shared_bf16: fused weight gradient");
-            }
-            // dW2 = inv (.) (C^T dZ2) + sh (x) db2: reduction over the rows, split into chunks with f32 atomics
-            int ksplit = 1;
-            while (Np / ksplit > 16384 && Np % (ksplit * 2 * BK) == 0) ksplit *= 2;  // f32 atomics cost ~ one MFMA K-chunk of 4096
-            GemmP p = {CT, dZ2T, Np, Np, setCT, setZT, K, H2, Np / ksplit, ksplit};
-            EpiDw e = {gnet + (critic ? L.cW2 : L.aW2), H2, (long)L.theta_size, n.inv, n.sh, cs, ldT, H2, 1.0f};
-            WIDE_CHECK(launch_gemm(p, e, sets, st, "avd_learn_shared_bf16: weight-gradient GEMM"));
-        }
-        return AVD_OK;
-    };
-    // dX GEMM with the BN/ReLU backward of the first layer(s) over columns [c_begin, c_end)
-    auto dx = [&](const NetOps& n, int c_begin, int c_end, bool wg, bool critic) {
+        hipLaunchKernelGGL(w2_post_kernel, dim3((unsigned)rup(H2, 64) / 64, sets), dim3(1024), 0, st, n.th, (long)L.theta_size,
+                           n.critic ? L.cW2 : L.aW2, K, H2, n.sh, ldT, n.bias, n.cf, gnet, (long)L.theta_size, u, cs, (long)H2);
+        out_grads(n, gnet, acc_idx);
+        return check_launch("avd_learn_shared_bf16: fused weight gradient");
+    }
+    // dX GEMM with the BN/ReLU backward of the first layer(s) over columns [c_begin, c_end); bn_grads: their dgamma / dbeta too
+    int dx_gemm(const NetOps& n, int c_begin, int c_end, bool bn_grads) {
         // (rank-one form: the dZ2 buffer holds the relu mask, Wn carries cf -- the row factor d completes the product)
         GemmP p = {dZ2, n.Wn + (long)c_begin * H2, H2, H2, setP2, setWn, Ns, c_end - c_begin, H2, 1};
-        EpiDx e = {C, dZ1, KCp, setC, n.inv, n.rs, n.mean, nullptr, nullptr, ldT, (long)sets * ldT, c_begin, r1 ? F32(pl.dcl) : (const float*)nullptr, (long)Np};
-        (void)critic;
-        if (wg) {  // dgamma / dbeta of the first layers accumulate in sliced table-shaped scratch, summed by flush_bn1
+        EpiDx e = {n.C, dZ1, KCp, setC, n.inv, n.rs, n.mean, nullptr, nullptr, ldT, (long)sets * ldT, c_begin, path.r1 ? dcl : (const float*)nullptr, (long)Np};
+        if (bn_grads) {  // dgamma / dbeta of the first layers accumulate in sliced table-shaped scratch, summed by flush_bn1
             (void)hipMemsetAsync(ws + pl.bnacc, 0, sizeof(float) * 2 * NSLICE * sets * ldT, st);
-            e.dgamma = F32(pl.bnacc);
-            e.dbeta = e.dgamma + (long)NSLICE * sets * ldT;
+            e.dgamma = F32(pl.bnacc), e.dbeta = e.dgamma + (long)NSLICE * sets * ldT;
         }
         return launch_gemm(p, e, sets, st, "avd_learn_shared_bf16: input-gradient GEMM");
-    };
-    auto l1_grads = [&](const float* X, long set_x, int kin, int c0, int H, float* gnet, int w_off, int b_off) {
+    }
+    void l1_grads(const float* X, long set_x, int kin, int c0, int H, float* gnet, int w_off, int b_off) {
         const int rpb = 2048;
         dim3 grid((unsigned)rup(H, 64) / 64, (unsigned)rup(Ns, rpb) / rpb, sets);
-        if (kin == 1)
-            hipLaunchKernelGGL((l1_grads_kernel<1>), grid, dim3(256), 0, st, X, set_x, dZ1, (long)KCp, setC, c0, H, Ns, rpb, 1.0f, gnet,
-                               (long)L.theta_size, w_off, b_off);
-        else if (kin == 4)
-            hipLaunchKernelGGL((l1_grads_kernel<4>), grid, dim3(256), 0, st, X, set_x, dZ1, (long)KCp, setC, c0, H, Ns, rpb, 1.0f, gnet,
-                               (long)L.theta_size, w_off, b_off);
-        else
-            hipLaunchKernelGGL((l1_grads_kernel<3>), grid, dim3(256), 0, st, X, set_x, dZ1, (long)KCp, setC, c0, H, Ns, rpb, 1.0f, gnet,
-                               (long)L.theta_size, w_off, b_off);
-    };
+#define AVD_L1G_LAUNCH(KIN)                                                                                                             \
+    hipLaunchKernelGGL((l1_grads_kernel<KIN>), grid, dim3(256), 0, st, X, set_x, dZ1, (long)KCp, setC, c0, H, Ns, rpb, 1.0f, gnet, \
+                       (long)L.theta_size, w_off, b_off)
+        if (kin == 1) AVD_L1G_LAUNCH(1); else if (kin == 4) AVD_L1G_LAUNCH(4); else AVD_L1G_LAUNCH(3);
+#undef AVD_L1G_LAUNCH
+    }
     // fused input gradient + first-layer gradients (fw::dx_gen_kernel)
-    auto dx_fused = [&](const NetOps& n, bool critic, float* gnet, const float* X, const float* act, long set_act) {
+    int dx_fused(const NetOps& n, float* gnet, const float* X, const float* act, long set_act) {
         fw::DxP d3;
-        d3.X = X, d3.setX = setX, d3.act = critic ? act : nullptr, d3.setAct = set_act;
-        d3.wf1 = (const bf16x8*)n.wf1, d3.nfs = H1 / 32, d3.nft = critic ? KCp / 32 : H1 / 32;
-        d3.dZ = critic ? dZ2 : P2, d3.setDZ = setP2, d3.d = F32(pl.dcl), d3.setD = Np;  // (the pass's relu mask and seed)
+        d3.X = X, d3.setX = setX, d3.act = n.critic ? act : nullptr, d3.setAct = set_act;
+        d3.wf1 = (const bf16x8*)n.wf1, d3.nfs = H1 / 32, d3.nft = n.critic ? KCp / 32 : H1 / 32;
+        d3.dZ = n.critic ? dZ2 : n.P2, d3.setDZ = setP2, d3.d = dcl, d3.setD = Np;  // (the pass's relu mask and seed)
         d3.Wn = n.Wn, d3.setWn = setWn, d3.inv = n.inv, d3.rs = n.rs, d3.mean = n.mean, d3.setTab = ldT;
-        d3.g = gnet, d3.setG = L.theta_size;
-        d3.w_off[0] = critic ? L.cWs : L.aW1, d3.b_off[0] = critic ? L.cbs : L.ab1, d3.g_off[0] = critic ? L.cgs : L.ag1, d3.be_off[0] = critic ? L.cbes : L.abe1;
+        d3.g = gnet, d3.setG = L.theta_size, d3.abl = knobs().dx_abl;
+        d3.w_off[0] = n.critic ? L.cWs : L.aW1, d3.b_off[0] = n.critic ? L.cbs : L.ab1, d3.g_off[0] = n.critic ? L.cgs : L.ag1, d3.be_off[0] = n.critic ? L.cbes : L.abe1;
         d3.w_off[1] = L.cWa, d3.b_off[1] = L.cba, d3.g_off[1] = L.cga, d3.be_off[1] = L.cbea;
         d3.Ns = Ns, d3.Np = Np, d3.H2 = H2, d3.H1 = H1, d3.Ha = Ha, d3.n_sets = sets;
-        static const char* dxabl = AVD_DIAG_ENV("WIDE_DX_ABL");
-        d3.abl = dxabl ? atoi(dxabl) : 0;
         // one workgroup per CU, dealt round-robin over the 8 XCDs: slots per XCD = CUs / 8 (32 on MI355X), each row group = nfb slots
         const int slots = std::max(1, avd::fset::cu_count() / 8);
         d3.nfb = H1 / 256, d3.groups_per_xcd = std::max(1, slots / d3.nfb);  // (the state features; the critic's 48 action features go the GEMM way)
         // the <false> form serves the state features of both nets; the <true> form also carries the critic's action features (one more
         // MFMA per wave and step, dealt over a row group's FOUR feature blocks: H1 = 1024) -- elsewhere they go the GEMM way
         const dim3 grid((unsigned)(8 * d3.groups_per_xcd * d3.nfb));
-        if (critic && act_in_dx)
+        if (n.critic && path.act_in_dx)
             hipLaunchKernelGGL((fw::dx_gen_kernel<true>), grid, dim3(fw::FT), (size_t)fw::DxL<true>::TOTAL, st, d3);
         else
             hipLaunchKernelGGL((fw::dx_gen_kernel<false>), grid, dim3(fw::FT), (size_t)fw::DxL<false>::TOTAL, st, d3);
         return check_launch("avd_learn_shared_bf16: fused input gradient");
-    };
-    auto flush_bn1 = [&](bool critic, float* gnet, bool state_part = true) {
-        const float* dg = F32(pl.bnacc);
-        const float* dbe = dg + (long)NSLICE * sets * ldT;
+    }
+    // the first layers' dgamma / dbeta out of dx_gemm's sliced scratch (critic: the action branch's, with_state: and the state branch's)
+    void flush_bn1(const NetOps& n, float* gnet, bool with_state) {
+        const float *dg = F32(pl.bnacc), *dbe = dg + (long)NSLICE * sets * ldT;
         auto go = [&](int t_off, int len, int gg, int gbe) {
             hipLaunchKernelGGL(bn1_flush_kernel, dim3((unsigned)rup(len, 256) / 256, sets), dim3(256), 0, st, dg, dbe, ldT,
                                (long)sets * ldT, t_off, len, gnet, (long)L.theta_size, gg, gbe);
         };
-        if (critic) {
-            if (state_part) go(0, H1, L.cgs, L.cbes);
-            go(H1, Ha, L.cga, L.cbea);
-        } else {
-            go(0, H1, L.ag1, L.abe1);
-        }
-    };
-
-    // ---- pass 0: targets  y = r + gamma * Q'(s2, mu'(s2))                                   (trainer.py:493-494)
-    WIDE_CHECK(actor_forward(net[2], s2, false));
-    WIDE_CHECK(critic_forward(net[3], s2, a1, (long)Np, false));
-    (void)hipMemcpy2DAsync(da, sizeof(float) * Np, r, sizeof(float) * Ns, sizeof(float) * Ns, sets, hipMemcpyDeviceToDevice, st);
-    rows(0, q, nullptr, da, gamma, y);
-
-    // ---- pass 1: critic loss and gradient                                                   (trainer.py:495-498)
-    float* gcrit = grads + asz;
-    if (!dual) {
-        WIDE_CHECK(critic_forward(net[1], s, a, (long)Ns, true));
+        if (with_state) go(0, H1, n.critic ? L.cgs : L.ag1, n.critic ? L.cbes : L.abe1);
+        if (n.critic) go(H1, Ha, L.cga, L.cbea);
+    }
+    // ---- passes 1 to 3, one schedule per backward form (pass 0 is the caller's: the same two forward passes in both)
+    // Layer-wise backward: every shape the rank-one chain does not take. The forward passes run fused or not, critic(s, mu) as a delta or not.
+    int learn_layerwise(const float* s, const float* a, float* grads) {
+        float* gcrit = grads + L.actor_size;
+        // pass 1: critic loss and gradient                                                    (trainer.py:495-498)
+        WIDE_CHECK(forward(net[1], s, a, (long)Ns, true));
         rows(1, q, y, nullptr, 0.f, dq);
-    }
-    auto pass1_backward = [&]() {
-        WIDE_CHECK(backward(net[1], true, dq, true, 1, gcrit, s, a, (long)Ns));
-        if (fused_dx) {
-            WIDE_CHECK(dx_fused(net[1], true, gcrit, s, a, (long)Ns));
-            if (!act_in_dx) {
-                // the action branch (48 features): its activations, the small GEMM with the BN / ReLU epilogue, first-layer gradients
-                l1(net[1], true, true, a, (long)Ns, false);
-                WIDE_CHECK(dx(net[1], H1, KC, true, true));
-                l1_grads(a, (long)Ns, 1, H1, Ha, gcrit, L.cWa, L.cba);
-                flush_bn1(true, gcrit, false);
-            }
+        WIDE_CHECK(backward_layerwise(net[1], dq, gcrit, 1));
+        WIDE_CHECK(dx_gemm(net[1], 0, KC, true));
+        l1_grads(s, setX, L.S, 0, H1, gcrit, L.cWs, L.cbs);
+        l1_grads(a, (long)Ns, 1, H1, Ha, gcrit, L.cWa, L.cba);
+        flush_bn1(net[1], gcrit, true);
+        // pass 2: actor through the critic, gradient w.r.t. the action                        (trainer.py:502-506)
+        WIDE_CHECK(forward(net[0], s, nullptr, 0, true));  // activations stay for pass 3
+        // same states, same critic as pass 1: the state columns of C are still valid, only the action branch changes
+        if (path.fused_delta) {
+            WIDE_CHECK(delta(a));
         } else {
-            WIDE_CHECK(dx(net[1], 0, KC, true, true));
-            l1_grads(s, setX, L.S, 0, H1, gcrit, L.cWs, L.cbs);
-            l1_grads(a, (long)Ns, 1, H1, Ha, gcrit, L.cWa, L.cba);
-            flush_bn1(true, gcrit);
+            l1(net[1], ACTION, a1, (long)Np, false);  // (the input-gradient epilogue reads the action columns of C)
+            // (fused: its output-layer backward too -- the seed of this pass is the constant -1/N, so dZ2 leaves the forward kernel)
+            WIDE_CHECK(path.fused_fwd ? l2_fused(net[1], s, a1, (long)Np, Keep::seeded_dz2) : l2_gemm(net[1]));
         }
-        return AVD_OK;
-    };
-    // rank-one form: the forward half of pass 2 runs BEFORE the critic's backward pass (all gradients are taken at the same
-    // pre-update weights, trainer.py:492-506: the order is free) -- the delta kernel, which reads critic(s, a)'s signed activations
-    // anyway, leaves their relu mask for it. The critic's seed stays in `dq`; the seeds of passes 2 / 3 then go to `y` (free after rows(1)).
-    float* dq3 = r1 ? y : dq;
-    if (!r1) WIDE_CHECK(pass1_backward());
-
-    // ---- pass 2: actor through the critic, gradient w.r.t. the action                       (trainer.py:502-506)
-    use_actor_buffers(true);
-    WIDE_CHECK(actor_forward(net[0], s, true));  // activations (rank-one form: their relu mask) stay for pass 3
-    use_actor_buffers(false);
-    // same states, same critic as pass 1: the state columns of C are still valid, only the action branch changes
-    if (dual) {
-        // both critic passes at once: q(s, a) -> q and its relu mask -> dZ2 (pass 1's backward operand); q(s, mu) -> zbuf, dq / d mu -> da
-        WIDE_CHECK(l2f(net[1], true, s, a, (long)Ns, true, false, false, a1));
-        rows(1, q, y, nullptr, 0.f, dq);  // (the critic's seed; reads y before rows(2) below reuses it)
-    } else if (!fused_delta) l1(net[1], true, true, a1, (long)Np, false);  // (the input-gradient epilogue reads the action columns of C)
-    if (dual) {
-    } else if (fused_delta) {  // z2(mu) = z2(a) + W2[action] (f(mu) - f(a)): 4 k-steps on top of the stored critic(s, a) activations
-        hipLaunchKernelGGL(fill_rows_kernel, dim3((unsigned)rup(Np, 256) / 256, sets), dim3(256), 0, st, q, (long)Np, net[1].c0, Np);
-        fw::DeltaP dl;
-        dl.Zin = P2, dl.setZ = setP2, dl.a = a, dl.mu = a1, dl.setA = Ns, dl.setMu = Np, dl.wf1 = (const bf16x8*)net[1].wf1, dl.nft = KCp / 32,
-        dl.nfs = H1 / 32, dl.WT = net[1].WT, dl.setWT = setWT, dl.ldw = KCp, dl.cf = net[1].cf, dl.z = q, dl.setQ = Np;
-        dl.dz_scale = -1.0f / (float)Ns, dl.rw = row_weight, dl.Ns = Ns, dl.Np = Np, dl.H2 = H2, dl.H1 = H1, dl.n_sets = sets;
-        dl.Wn = net[1].Wn, dl.setWn = setWn, dl.cf_in_wn = r1 ? 1 : 0, dl.inv = net[1].inv, dl.setTab = ldT, dl.th = net[1].th, dl.setTh = L.theta_size, dl.wa_off = L.cWa, dl.Ha = Ha;
-        dl.da = da, dl.setDa = Np;
-        dl.Mk = r1 ? dZ2 : nullptr;  // (critic(s, a)'s relu mask, for pass1_backward below)
-        (void)hipMemsetAsync(da, 0, sizeof(float) * sets * Np, st);
-        hipLaunchKernelGGL(fw::fwd_delta_kernel, dim3((unsigned)std::min<long>(2 * avd::fset::cu_count(), Np / fw::FR)), dim3(fw::FT),
-                           (size_t)fw::DL_TOTAL, st, dl);
-        WIDE_CHECK(check_launch("avd_learn_shared_bf16: critic(s, mu) as a delta"));
-    } else if (fused_fwd)  // (its output-layer backward too: the seed of this pass is the constant -1/N, so dZ2 leaves the forward kernel)
-        WIDE_CHECK(l2f(net[1], true, s, a1, (long)Np, true, true));
-    else
-        WIDE_CHECK(l2(net[1], true));
-    out_layer(net[1], 0, q);
-#ifdef AVD_DIAG
-    if (const char* dump = getenv("AVD_WIDE_DUMP")) {  // diagnostics: q(s, mu) and the action gradient of this call, [sets][Np] f32 each
-        std::vector<float> hb(3 * (size_t)sets * Np);
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(hb.data(), dual ? zbuf : q, sizeof(float) * sets * Np, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(hb.data() + (size_t)sets * Np, da, sizeof(float) * sets * Np, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(hb.data() + 2 * (size_t)sets * Np, a1, sizeof(float) * sets * Np, hipMemcpyDeviceToHost);
-        if (FILE* f = fopen(dump, "wb")) fwrite(hb.data(), sizeof(float), hb.size(), f), fclose(f);
-    }
-#endif
-    rows(2, dual ? zbuf : q, nullptr, nullptr, 0.f, dq3);
-    if (!fused_fwd) WIDE_CHECK(backward(net[1], true, dq3, false, 0, nullptr));
-    if (!fused_delta) {
-        WIDE_CHECK(dx(net[1], H1, KC, false, true));
-        // da[n] = sum_k dZ1[n][H1 + k] * Wa[0][k]
-        hipLaunchKernelGGL(row_dot_kernel, dim3((unsigned)rup(Ns, 4) / 4, sets), dim3(256), 0, st, dZ1, (long)KCp, setC, H1, Ha,
-                           net[1].th + L.cWa, (long)L.theta_size, (const float*)nullptr, Ns, 0, 0.f, da, (float*)nullptr, (long)Np);
-    }
-    if (r1) WIDE_CHECK(pass1_backward());
-
-    // ---- pass 3: actor gradient from the activations (rank-one form: the mask) kept in pass 2
-    use_actor_buffers(true);
-    rows(3, nullptr, tt, da, high, dq3);
-    WIDE_CHECK(backward(net[0], false, dq3, true, 3, grads, s));
-    if (fused_dx) {
-        WIDE_CHECK(dx_fused(net[0], false, grads, s, nullptr, 0));
-    } else {
-        WIDE_CHECK(dx(net[0], 0, H1, true, false));
+        dump_pass2(q);
+        rows(2, q, nullptr, nullptr, 0.f, dq);
+        if (!path.fused_fwd) WIDE_CHECK(backward_layerwise(net[1], dq, nullptr, 0));
+        if (!path.fused_delta) {
+            WIDE_CHECK(dx_gemm(net[1], H1, KC, false));
+            // da[n] = sum_k dZ1[n][H1 + k] * Wa[0][k]
+            hipLaunchKernelGGL(row_dot_kernel, dim3((unsigned)rup(Ns, 4) / 4, sets), dim3(256), 0, st, dZ1, (long)KCp, setC, H1, Ha,
+                               net[1].th + L.cWa, (long)L.theta_size, (const float*)nullptr, Ns, 0, 0.f, da, (float*)nullptr, (long)Np);
+        }
+        // pass 3: actor gradient from the activations kept in pass 2
+        rows(3, nullptr, tt, da, high, dq);
+        WIDE_CHECK(backward_layerwise(net[0], dq, grads, 3));
+        WIDE_CHECK(dx_gemm(net[0], 0, H1, true));
         l1_grads(s, setX, L.S, 0, H1, grads, L.aW1, L.ab1);
-        flush_bn1(false, grads);
+        flush_bn1(net[0], grads, true);
+        return AVD_OK;
     }
-    hipLaunchKernelGGL(losses_kernel, dim3(1), dim3(64), 0, st, acc, Ns, sets, losses);
+    // Rank-one backward (path.r1; config 5): every forward pass fused, no first-layer activations in memory.
+    int learn_rank1(const float* s, const float* a, float* grads) {
+        float* gcrit = grads + L.actor_size;
+        // pass 1, forward half: critic loss; signed activations for the delta pass (one-pass form: folded into pass 2 below)
+        if (!path.dual) {
+            WIDE_CHECK(l2_fused(net[1], s, a, (long)Ns, Keep::signed_pre));
+            rows(1, q, y, nullptr, 0.f, dq);
+        }
+        // rank-one form: the forward half of pass 2 runs BEFORE the critic's backward pass (all gradients are taken at the same
+        // pre-update weights, trainer.py:492-506: the order is free) -- the delta kernel, which reads critic(s, a)'s signed activations
+        // anyway, leaves their relu mask for it. The critic's seed stays in `dq`; the seeds of passes 2 / 3 then go to `y` (free after rows(1)).
+        // pass 2: actor through the critic, gradient w.r.t. the action                        (trainer.py:502-506)
+        WIDE_CHECK(l2_fused(net[0], s, nullptr, 0, Keep::activations));  // (their relu mask) stays for pass 3
+        actor_head();
+        if (path.dual) {
+            WIDE_CHECK(l2_dual(net[1], s, a, (long)Ns));
+            rows(1, q, y, nullptr, 0.f, dq);  // (the critic's seed; reads y before rows(2) below reuses it)
+        } else {
+            WIDE_CHECK(delta(a));
+        }
+        const float* q_mu = path.dual ? zbuf : q;
+        dump_pass2(q_mu);
+        rows(2, q_mu, nullptr, nullptr, 0.f, y);
+        // pass 1, backward half: critic gradient                                              (trainer.py:495-498)
+        WIDE_CHECK(backward_rank1(net[1], dq, gcrit, 1, s, a, (long)Ns));
+        WIDE_CHECK(dx_fused(net[1], gcrit, s, a, (long)Ns));
+        if (!path.act_in_dx) {
+            // the action branch (48 features): its activations, the small GEMM with the BN / ReLU epilogue, first-layer gradients
+            l1(net[1], ACTION, a, (long)Ns, false);
+            WIDE_CHECK(dx_gemm(net[1], H1, KC, true));
+            l1_grads(a, (long)Ns, 1, H1, Ha, gcrit, L.cWa, L.cba);
+            flush_bn1(net[1], gcrit, false);
+        }
+        // pass 3: actor gradient from the relu mask kept in pass 2
+        rows(3, nullptr, tt, da, high, y);
+        WIDE_CHECK(backward_rank1(net[0], y, grads, 3, s, nullptr, 0));
+        return dx_fused(net[0], grads, s, nullptr, 0);
+    }
+};
+}  // namespace
+
+extern "C" int avd_learn_shared_path(const avd_mlp_layout* lay, int n_agents, int n_sets, unsigned* flags) {
+    WIDE_CHECK(check_wide(lay, n_agents, n_sets, "avd_learn_shared_path"));
+    AVD_REQUIRE(flags, "avd_learn_shared_path: null pointer");
+    const Path p = choose_path(*lay, make_plan(*lay, n_agents, n_sets).d.Np);
+    *flags = (p.fused_fwd ? AVD_PATH_FUSED_FWD : 0u) | (p.fused_delta ? AVD_PATH_FUSED_DELTA : 0u) | (p.r1 ? AVD_PATH_R1 : 0u) |
+             (p.dual ? AVD_PATH_DUAL : 0u) | (p.act_in_dx ? AVD_PATH_ACT_IN_DX : 0u);
+    return AVD_OK;
+}
+
+extern "C" int avd_learn_shared_bf16(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta,
+                                     const float* stats, const float* theta_t, const float* stats_t, const float* s,
+                                     const float* a, const float* r, const float* s2, const float* row_weight, float gamma,
+                                     float high, float* grads, float* losses, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    WIDE_CHECK(check_wide(lay, n_agents, n_sets, "avd_learn_shared_bf16"));
+    AVD_REQUIRE(theta && stats && theta_t && stats_t && s && a && r && s2 && grads && workspace, "avd_learn_shared_bf16: null pointer");
+    const Plan pl = make_plan(*lay, n_agents, n_sets);
+    AVD_REQUIRE(workspace_bytes >= pl.total, "avd_learn_shared_bf16: workspace %zu B < %zu B", workspace_bytes, pl.total);
+    Learn c(*lay, pl, choose_path(*lay, pl.d.Np), workspace, stream);
+    c.row_weight = row_weight, c.high = high;
+    if (c.path.fused_fwd) WIDE_CHECK(opt_in_dynamic_lds());
+    // zero what is accumulated into or read as padding
+    (void)hipMemsetAsync(grads, 0, sizeof(float) * (size_t)c.sets * lay->theta_size, c.st);
+    (void)hipMemsetAsync(c.acc, 0, sizeof(float) * c.sets * 4, c.st);
+    // (activation buffers need no clearing: their producers write every row < Np and every column < KCp, zeros in the
+    //  padding; rows/columns beyond that only ever feed output elements the GEMM epilogues do not store)
+    for (int i = 0; i < 4; ++i) c.prepare_net(c.bind(i, i < 2 ? theta : theta_t, i < 2 ? stats : stats_t));
+    WIDE_CHECK(check_launch("avd_learn_shared_bf16: operand preparation"));
+    // ---- pass 0: targets  y = r + gamma * Q'(s2, mu'(s2))                                   (trainer.py:493-494)
+    WIDE_CHECK(c.forward(c.net[2], s2, nullptr, 0, false));
+    WIDE_CHECK(c.forward(c.net[3], s2, c.a1, (long)c.Np, false));
+    // Note on row-vector strides: r arrives as [sets][Ns] (stride Ns), internal vectors use stride Np. The TD kernel
+    // reads r with the internal stride, so r is first copied into `da` (free at that point) with the padded stride.
+    (void)hipMemcpy2DAsync(c.da, sizeof(float) * c.Np, r, sizeof(float) * c.Ns, sizeof(float) * c.Ns, c.sets, hipMemcpyDeviceToDevice, c.st);
+    c.rows(0, c.q, nullptr, c.da, gamma, c.y);
+    // ---- passes 1 to 3: critic loss and gradient, actor through the critic, actor gradient
+    WIDE_CHECK(c.path.r1 ? c.learn_rank1(s, a, grads) : c.learn_layerwise(s, a, grads));
+    hipLaunchKernelGGL(losses_kernel, dim3(1), dim3(64), 0, c.st, c.acc, c.Ns, c.sets, losses);
     return check_launch("avd_learn_shared_bf16");
 }
 
 // ---- acting with shared weight sets: actor(state) for every agent of a set as one GEMM chain ---------------
 extern "C" int avd_actor_forward_shared_workspace(const avd_mlp_layout* lay, int n_agents, int n_sets, size_t* bytes) {
-    int rc = check_wide(lay, n_agents, n_sets, "avd_actor_forward_shared_workspace");
-    if (rc) return rc;
+    WIDE_CHECK(check_wide(lay, n_agents, n_sets, "avd_actor_forward_shared_workspace"));
     AVD_REQUIRE(bytes, "avd_actor_forward_shared_workspace: null pointer");
     *bytes = make_plan(*lay, n_agents, n_sets, 1).total;
     return AVD_OK;
@@ -3210,48 +3238,19 @@ extern "C" int avd_actor_forward_shared_workspace(const avd_mlp_layout* lay, int
 extern "C" int avd_actor_forward_shared_bf16(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta,
                                              const float* stats, const float* state, float high, float* out, void* workspace,
                                              size_t workspace_bytes, void* stream) {
-    int rc = check_wide(lay, n_agents, n_sets, "avd_actor_forward_shared_bf16");
-    if (rc) return rc;
+    WIDE_CHECK(check_wide(lay, n_agents, n_sets, "avd_actor_forward_shared_bf16"));
     AVD_REQUIRE(theta && stats && state && out && workspace, "avd_actor_forward_shared_bf16: null pointer");
-    const avd_mlp_layout& L = *lay;
-    const Plan pl = make_plan(L, n_agents, n_sets, 1);
+    const Plan pl = make_plan(*lay, n_agents, n_sets, 1);
     AVD_REQUIRE(workspace_bytes >= pl.total, "avd_actor_forward_shared_bf16: workspace %zu B < %zu B", workspace_bytes, pl.total);
-    const Dims& d = pl.d;
-    hipStream_t st = (hipStream_t)stream;
-    unsigned char* ws = (unsigned char*)workspace;
-    const int sets = n_sets, Ns = d.Ns, Np = d.Np, H1 = d.H1, H2 = d.H2, KCp = d.KCp;
-    const long H2n = rup(H2, 256), ldT = pl.ldT, setC = (long)Np * KCp, setP2 = (long)Np * H2, setWT = H2n * KCp;
-    float* tab = (float*)(ws + pl.tabs[0]);
-    float *inv = tab, *sh = tab + (long)sets * ldT, *rs = tab + 2L * sets * ldT, *mean = tab + 3L * sets * ldT;
-    bf16 *C = (bf16*)(ws + pl.C), *P2 = (bf16*)(ws + pl.P2), *WT = (bf16*)(ws + pl.WT[0]);
-    float *bias = (float*)(ws + pl.bias[0]), *cf = (float*)(ws + pl.cf[0]), *c0 = (float*)(ws + pl.c0[0]), *tt = (float*)(ws + pl.tt);
-    auto tables = [&](int g, int be, int mm, int mv, int len, int t_off, int pad_to) {
-        hipLaunchKernelGGL(bn_tables_kernel, dim3((unsigned)rup(pad_to, 256) / 256, sets), dim3(256), 0, st, theta, stats,
-                           (long)L.theta_size, (long)L.stats_size, g, be, mm, mv, len, inv, sh, rs, mean, ldT, t_off, pad_to);
-    };
-    tables(L.ag1, L.abe1, L.amm1, L.amv1, H1, 0, KCp);
-    tables(L.ag2, L.abe2, L.amm2, L.amv2, H2, KCp, H2);
-    hipLaunchKernelGGL(prep_w2_kernel, dim3((unsigned)rup(H2, 32) / 32, (unsigned)rup(KCp, 32) / 32, sets), dim3(256), 0, st, theta,
-                       (long)L.theta_size, L.aW2, H1, H2, KCp, inv, ldT, WT, setWT, (bf16*)nullptr, 0L, 0, (const float*)nullptr);
-    hipLaunchKernelGGL(bias2_kernel, dim3((unsigned)rup(H2, 64) / 64, sets), dim3(1024), 0, st, theta, (long)L.theta_size, L.aW2, L.ab2,
-                       H1, H2, sh, ldT, bias, (long)H2);
-    hipLaunchKernelGGL(out_coefs_kernel, dim3(sets), dim3(256), 0, st, theta, (long)L.theta_size, L.aW3, L.ab3, H2, inv + KCp, sh + KCp,
-                       ldT, cf, c0, (long)H2);
-    dim3 grid((unsigned)rup(H1, 64) / 64, (unsigned)rup(Np, 64) / 64, sets);
-    if (L.S == 4)
-        hipLaunchKernelGGL((l1_fwd_kernel<4>), grid, dim3(256), 0, st, state, (long)Ns * 4, theta, (long)L.theta_size, L.aW1, L.ab1, H1, H1,
-                           0, Ns, Np, C, (long)KCp, setC, (bf16*)nullptr, 0L, 0L);
-    else
-        hipLaunchKernelGGL((l1_fwd_kernel<3>), grid, dim3(256), 0, st, state, (long)Ns * 3, theta, (long)L.theta_size, L.aW1, L.ab1, H1, H1,
-                           0, Ns, Np, C, (long)KCp, setC, (bf16*)nullptr, 0L, 0L);
-    GemmP p = {C, WT, KCp, KCp, setC, setWT, Ns, H2, (int)rup(H1, 64), 1};
-    float* zbuf = (float*)(ws + pl.zbuf);
-    hipLaunchKernelGGL(fill_rows_kernel, dim3((unsigned)rup(Np, 256) / 256, sets), dim3(256), 0, st, zbuf, (long)Np, c0, Np);
-    EpiFwd e = {P2, H2, setP2, bias, H2, cf, zbuf, (long)Np};
-    WIDE_CHECK(launch_gemm(p, e, sets, st, "avd_actor_forward_shared_bf16: forward GEMM"));
+    Learn c(*lay, pl, Path{}, workspace, stream);  // (the layer-wise forward at every shape)
+    NetOps& n = c.bind(0, theta, stats);
+    n.Wn = nullptr, n.C = c.B16(pl.C), n.P2 = c.B16(pl.P2);  // (no backward pass: no operand for one, the general activation buffers)
+    c.bn_tables(n), c.w2_operands(n), c.out_coefs(n);
+    c.l1(n, STATE, state, c.setX, false);
+    WIDE_CHECK(c.l2_gemm(n, "avd_actor_forward_shared_bf16: forward GEMM"));
     // out is tightly packed [sets][Ns]: strided copy through tanh
-    for (int k = 0; k < sets; ++k)
-        hipLaunchKernelGGL(tanh_rows_kernel, dim3((unsigned)rup(Ns, 256) / 256, 1), dim3(256), 0, st, zbuf + (long)k * Np, 0L, Ns, high,
-                           out + (long)k * Ns, tt + (long)k * Np);
+    for (int k = 0; k < c.sets; ++k)
+        hipLaunchKernelGGL(tanh_rows_kernel, dim3((unsigned)rup(c.Ns, 256) / 256, 1), dim3(256), 0, c.st, c.zbuf + (long)k * c.Np, 0L, c.Ns, high,
+                           out + (long)k * c.Ns, c.tt + (long)k * c.Np);
     return check_launch("avd_actor_forward_shared_bf16");
 }

@@ -451,6 +451,14 @@ int avd_learn_shared_bf16(const avd_mlp_layout* lay, int n_agents, int n_sets, c
                           const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
                           const float* s2, const float* row_weight, float gamma, float high, float* grads, float* losses,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* Which kernels avd_learn_shared_bf16 runs at this shape, on the host, without a HIP call (csrc/wide.hip choose_path): *flags = the
+ * AVD_PATH_* bits. All five: the fused rank-one chain (BASELINE config 5); none: the layer-wise GEMM chain. */
+#define AVD_PATH_FUSED_FWD 1u   /* forward passes: one fused kernel per pass, not first layer + GEMM */
+#define AVD_PATH_FUSED_DELTA 2u /* critic(s, mu) as a delta on critic(s, a)'s stored activations */
+#define AVD_PATH_R1 4u          /* backward passes in the rank-one form, from the stored relu mask */
+#define AVD_PATH_DUAL 8u        /* critic(s, a) and critic(s, mu) in one forward pass */
+#define AVD_PATH_ACT_IN_DX 16u  /* the critic's action features inside the fused input-gradient kernel */
+int avd_learn_shared_path(const avd_mlp_layout* lay, int n_agents, int n_sets, unsigned* flags);
 
 /* The same quantity -- Trainer.learn (workers/trainer.py:472-508) + federated mean over the platoons
  * (src/server/federated.py:47-63, 99-118; workers/trainer.py:400-431) for agents sharing n_sets weight sets -- at the

@@ -302,3 +302,69 @@ def test_bench_plain_run_leaves_everything_but_the_headline_to_full(monkeypatch)
     assert "default_run = (args.full and" in main_src
     assert "if args.full and world == 1 and not args.no_cpu_baseline:" in main_src
     assert "if args.full and (world > 1 or group is not None)" in src
+
+
+_PATH_BITS = ("fused_fwd", "fused_delta", "r1", "dual", "act_in_dx")  # AVD_PATH_* of include/avddpg_hip.h, bit 0 upwards
+_PATH_QUERY = r"""
+import ctypes, sys
+from avddpg_amd import _hip
+lay = _hip.make_layout(4, 1, 1024, 1024, 48, 64)
+flags = ctypes.c_uint(0)
+_hip.call("avd_learn_shared_path", ctypes.byref(lay), 2 * 12, 2, ctypes.byref(flags))
+print("flags", flags.value)
+"""
+
+
+def _path(S, widths, rows, n_sets=2):
+    lay = _hip.make_layout(S, 1, *widths, 64)
+    flags = ctypes.c_uint(0)
+    _hip.call("avd_learn_shared_path", ctypes.byref(lay), n_sets * rows // 64, n_sets, ctypes.byref(flags))
+    assert flags.value < 1 << len(_PATH_BITS)
+    return {name for i, name in enumerate(_PATH_BITS) if flags.value >> i & 1}
+
+
+def test_shared_learner_path_table():
+    """avd_learn_shared_path: which form of avd_learn_shared_bf16 a shape takes, decided on the host by the same choose_path the learner
+    calls (csrc/wide.hip), no HIP call. A condition that slips sends BASELINE config 5 down the layer-wise chain at about half the speed
+    with every oracle test still passing; this table pins the product library's decision. Batches of 64, one action."""
+    everything = set(_PATH_BITS)
+    for rows in (768, 960, 4096):  # (960 pads to 1024 rows)
+        assert _path(4, (1024, 1024, 48), rows) == everything, rows
+    # one 256-row chunk per set: below the rank-one chain's two
+    assert _path(4, (1024, 1024, 48), 192) == {"fused_fwd", "fused_delta"}
+    assert _path(4, (512, 512, 48), 768) == everything - {"act_in_dx"}  # (the action features ride in dx only with four feature blocks)
+    assert _path(4, (256, 128, 48), 384) == set()  # the reference widths: second layer not in 512-column blocks
+    assert _path(3, (1024, 1024, 48), 768) == set()  # the fused first layer is written for S == 4
+    # the action branch must pad to exactly two 32-feature chunks: 1024 + 32 pads to 1088 like 1024 + 48; 1024 + 80 pads to 1152
+    assert _path(4, (1024, 1024, 32), 768) == everything
+    assert _path(4, (1024, 1024, 80), 768) == {"fused_fwd"}
+    with pytest.raises(_hip.AvdError, match="multiples of 64"):
+        _path(4, (320, 160, 48), 768)
+    lay = _hip.make_layout(4, 1, 1024, 1024, 48, 64)
+    with pytest.raises(_hip.AvdError, match="null pointer"):
+        _hip.call("avd_learn_shared_path", ctypes.byref(lay), 24, 2, None)
+
+
+@pytest.mark.parametrize("switch,cleared", [(None, set()), ("AVD_WIDE_DUAL", {"dual"}),
+                                            ("AVD_WIDE_FUSED_DELTA", {"fused_delta", "r1", "dual", "act_in_dx"}),
+                                            ("AVD_WIDE_FUSED_FWD", set(_PATH_BITS))])
+def test_diagnostic_switches_clear_a_path_flag_and_what_rests_on_it(switch, cleared):
+    """The diagnostic library's AVD_WIDE_*=0 switches at 1024/1024/48, 768 rows per set: each clears its flag and every flag that rests
+    on it, nothing else. One child process per setting (the switches are read once per process); the product library reads none."""
+    import subprocess
+    import sys
+
+    assert os.path.exists(_hip.DIAG_LIB_PATH), "the diagnostic library is part of build()"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if not k.startswith("AVD_WIDE_")}
+    env.update(AVDDPG_HIP_LIB=_hip.DIAG_LIB_PATH, PYTHONPATH=root + os.pathsep + env.get("PYTHONPATH", ""))
+    if switch:
+        env[switch] = "0"
+    p = subprocess.run([sys.executable, "-c", _PATH_QUERY], env=env, capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-2000:]
+    flags = int(p.stdout.split("flags")[1])
+    assert {name for i, name in enumerate(_PATH_BITS) if flags >> i & 1} == set(_PATH_BITS) - cleared
+    if switch:  # the product library holds no switch
+        env.pop("AVDDPG_HIP_LIB")
+        p = subprocess.run([sys.executable, "-c", _PATH_QUERY], env=env, capture_output=True, text=True, timeout=120)
+        assert p.returncode == 0 and int(p.stdout.split("flags")[1]) == (1 << len(_PATH_BITS)) - 1, p.stderr[-2000:]
