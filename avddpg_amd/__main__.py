@@ -86,6 +86,14 @@ def _scenario_flags(p, where):
                    help="--scenarios: the amplitude of step, ramp, brake and sine (default: reset_max_u, the scale of leader input the "
                         "actors are trained on)")
     p.add_argument("--scenario_period", type=float, default=None, help="--scenarios: the sine's period in seconds (default 10)")
+    # (absent from the namespace unless given: _disturb(args) reads it)
+    p.add_argument("--disturb", action="append", default=argparse.SUPPRESS, metavar="NAME:key=val,...",
+                   help="--scenarios: also run every scenario x seed under this disturbance (repeat the flag for more levels), all in the "
+                        "same ONE launch, and write robustness.csv: scenarios.csv's columns plus `disturbance` and `score_delta` (score "
+                        "minus the undisturbed score of the same platoon, scenario and seed). Keys: noise_ep, noise_ev, noise_a (sensor "
+                        "noise, standard deviations), v2v_delay (steps, 0..15) and v2v_drop (loss probability) on the communicated "
+                        "predecessor acceleration (Model B), dyn_coeff (the true plant's engine lag; the actors stay as trained), e.g. "
+                        "lag3:v2v_delay=3,v2v_drop=0.1 (not in the reference CLI)")
 
 
 def _check_scenario_flags(ap, args):
@@ -95,8 +103,8 @@ def _check_scenario_flags(ap, args):
     from .scenarios import check_names
 
     if args.scenarios is None:
-        for flag in ("eval_seeds", "scenario_amp", "scenario_period"):
-            if getattr(args, flag) is not None:
+        for flag in ("eval_seeds", "scenario_amp", "scenario_period", "disturb"):
+            if getattr(args, flag, None) is not None:
                 ap.error(f"--{flag} needs --scenarios")
         return
     try:
@@ -112,9 +120,21 @@ def _check_scenario_flags(ap, args):
         ap.error("--scenario_amp must be finite")
     if args.scenario_period is not None and not (math.isfinite(args.scenario_period) and args.scenario_period > 0):
         ap.error("--scenario_period must be finite and > 0")
+    if _disturb(args) is not None:
+        from .scenarios import check_disturbances, parse_disturbance
+
+        try:  # (the Model A refusal needs the run's configuration: evaluator.prepare_disturbed makes it)
+            args.disturb = check_disturbances([parse_disturbance(d) for d in args.disturb])
+        except ValueError as e:
+            ap.error(f"--disturb: {e}")
     if args.mode == "tr" and int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
         # (one of the two choices: refused, rather than every rank writing a scenarios.csv of its own platoons)
         ap.error("--scenarios is not available under a process group of more than one rank (scenarios.csv is not gathered across ranks)")
+
+
+def _disturb(args):
+    """The --disturb levels (checked Disturbances), or None without the flag."""
+    return getattr(args, "disturb", None)
 
 
 def _suite(args):
@@ -131,10 +151,27 @@ def _record_suite(conf, res, args):
 
 
 def _slice(res, e):
-    """Experiment e's CaseResults of a batch's ([E, P, ...] arrays)."""
-    from .evaluator import CaseResults
+    """Experiment e's CaseResults (DisturbedResults) of a batch's ([E, P, ...] arrays)."""
+    from .evaluator import CaseResults, DisturbedResults
 
-    return CaseResults(res.scenarios, res.seeds, res.T, res.scores[e], res.counters[e], {k: v[e] for k, v in res.metrics.items()})
+    rest = (res.seeds, res.T, res.scores[e], res.counters[e], {k: v[e] for k, v in res.metrics.items()})
+    return DisturbedResults(res.scenarios, res.disturbances, *rest) if isinstance(res, DisturbedResults) else CaseResults(res.scenarios, *rest)
+
+
+def _write_suite(d, conf, res, tags, args):
+    """scenarios.csv and conf.json's scenario_suite from a CaseResults; from a DisturbedResults (--disturb) the same from its nominal
+    slice, plus robustness.csv and conf.json's robustness_suite (a list of [name, [[key, value], ...]] pairs). -> the nominal results."""
+    from . import scenarios as _sc
+    from .evaluator import DisturbedResults
+
+    nominal = res
+    if isinstance(res, DisturbedResults):
+        nominal = res.nominal()
+        _sc.write_robustness_csv(os.path.join(d, "robustness.csv"), res, tags)
+        conf.robustness_suite = [[x.name, x.items()] for x in _disturb(args)]
+    _sc.write_csv(os.path.join(d, "scenarios.csv"), nominal, tags)
+    _record_suite(conf, nominal, args)
+    return nominal
 
 
 def get_cmdl_args(argv, conf):
@@ -342,11 +379,9 @@ def main(argv=None, conf=None):
         # average, written into conf.json (the evaluator reseeds the global legacy RNG; run_many puts it back)
         conf.pl_rews_for_simulations = vt.run_simulations()
         conf.pl_rew_for_simulation = float(np.average(conf.pl_rews_for_simulations))
-        if args.scenarios is not None:  # every local platoon over scenarios x seeds, one launch
-            from . import scenarios as _sc
-            res = vt.evaluate_scenarios(**_suite(args))
-            _sc.write_csv(os.path.join(base, "scenarios.csv"), res, range(1, vt.P + 1))
-            _record_suite(conf, res, args)
+        if args.scenarios is not None:  # every local platoon over scenarios (x disturbances) x seeds, one launch
+            res = vt.evaluate_scenarios(**_suite(args)) if _disturb(args) is None else vt.evaluate_robustness(disturbances=_disturb(args), **_suite(args))
+            _write_suite(base, conf, res, range(1, vt.P + 1), args)
         n_save = vt.P if args.save_platoons is None and args.episodes == "reference" else min(vt.P, 4 if args.save_platoons is None else args.save_platoons)
         artifacts.save_agents(base, vt.agents, n_save, vt.M, shared=vt.shared)
         # what ran, beside the reference's fields: how many platoons' agents the directory holds (esim loops over exactly these),
@@ -378,8 +413,9 @@ def main(argv=None, conf=None):
                     raise FileNotFoundError(f"{args.exp_path}: no checkpoint of platoon {p}'s actors (conf.json records {saved} saved platoons)")
                 for m in range(M):
                     grp.set_weights((p - 1) * M + m, "actor", artifacts.load_actor_weights(args.exp_path, p, m + 1))
-            res = evaluator.run_cases(conf, grp, range(saved), **_suite(args))
-            _sc.write_csv(os.path.join(args.exp_path, "scenarios.csv"), res, range(1, saved + 1))
+            res = evaluator.run_cases(conf, grp, range(saved), **_suite(args)) if _disturb(args) is None else \
+                evaluator.run_disturbed(conf, grp, range(saved), disturbances=_disturb(args), **_suite(args))
+            res = _write_suite(args.exp_path, conf, res, range(1, saved + 1), args)  # (conf.json itself is not rewritten)
             print("\n".join(_sc.report_lines(res, range(1, saved + 1))))
             return
         for p in range(1, int(saved) + 1):
@@ -499,7 +535,9 @@ def train_seed_batch(args, conf, base, experiments=None):
     if vt.nonfinite_updates():
         print(f"warning: {vt.nonfinite_updates()} weight-set updates were skipped for non-finite gradients", file=sys.stderr)
     sims = vt.run_simulations()  # [E][P], one rollout launch
-    suite = vt.evaluate_scenarios(**_suite(args)) if args.scenarios is not None else None  # [E, P, scen, seed, ...], one launch
+    suite = None  # [E, P, scen, (dist,) seed, ...], one launch
+    if args.scenarios is not None:
+        suite = vt.evaluate_scenarios(**_suite(args)) if _disturb(args) is None else vt.evaluate_robustness(disturbances=_disturb(args), **_suite(args))
     n_save = min(P, 4 if args.save_platoons is None else args.save_platoons)
     done = []
     for e, (k, d) in enumerate(zip(seeds, dirs)):
@@ -521,9 +559,7 @@ def train_seed_batch(args, conf, base, experiments=None):
                 ce.pbt = [["interval", args.pbt], ["fraction", args.pbt_fraction], ["perturb", list(args.pbt_perturb)],
                           ["lineage", lineage[e]]]
         if suite is not None:
-            from . import scenarios as _sc
-            _sc.write_csv(os.path.join(d, "scenarios.csv"), _slice(suite, e), range(1, P + 1))
-            _record_suite(ce, suite, args)
+            _write_suite(d, ce, _slice(suite, e), range(1, P + 1), args)
         artifacts.config_writer(os.path.join(d, "conf.json"), ce)
         done.append((ce, last[e]))
     return done

@@ -14,6 +14,7 @@ if os.environ.get("AVDDPG_HIP_LIB"):  # diagnostics: A/B another build of the sa
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "avddpg_hip.h")
 AVD_MAX_L = 16
 AVD_EVAL_NMETRIC = 8
+AVD_EVAL_MAX_DELAY = 15
 
 
 class AvdError(RuntimeError):
@@ -122,6 +123,9 @@ _PROTOS = {
                              _P],
     "avd_eval_cases_f32": [_LP, _P, _i, _i, _i, _i, _i, _P, _P, _i, _P, _P, _P, _P, _f, _f, _f, _f, _P, _P, _P],
     "avd_eval_cases_block": [_i, _i],  # returns the block size itself (>= 1), or AVD_E_INVALID: not for call()
+    "avd_eval_cases_dist_f32": [_LP, _P, _i, _i, _i, _i, _i, _P, _P, _i, _P, _P, _P, _P, _f, _f, _f, _f, _P, _P, _P, _P, _P, _P, _P, _P],
+    "avd_eval_cases_dist_block": [_i, _i],  # returns the block size itself, as avd_eval_cases_block
+    "avd_eval_cases_dist_check": [_i, _P, _P, _P],  # HOST arrays
     "avd_gemm_bt_bf16": [_i, _i, _i, _P, C.c_long, _P, C.c_long, _P, C.c_long, _P],
 }
 

@@ -107,6 +107,8 @@ enum PhiloxStream : uint32_t {
     STREAM_OU = 3,
     STREAM_NORMAL = 4,
     STREAM_REPLAY = 5,
+    STREAM_EVAL_OBS = 6,   // disturbed scenario evaluator: sensor noise, (counter, index) = (step, vehicle)
+    STREAM_EVAL_LINK = 7,  // disturbed scenario evaluator: V2V loss, word x
 };
 
 }  // namespace avd

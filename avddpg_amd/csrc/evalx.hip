@@ -11,12 +11,27 @@
 // read as a broadcast by every lane of a wave that works on the same k range.
 //
 // Rows >= K of the tail block are computed on a zero state in LDS only: they read no start state or leader input and write nothing.
+//
+// The DISTURBED variant (avd_eval_cases_dist_f32) is the same kernel text with one trailing DistArgs argument: per case a sensor-noise
+// level, a V2V delay and loss rate on the communicated 4th state, and the true plant's matrices. The actors then read an OBSERVED
+// state; the platoon step, the reward and the metrics keep the true one (the vehicle threads' registers). Without that argument the
+// kernel is the nominal one: same parameter list, same code.
+#include <float.h>
+
 #include "eval_common.h"
 
 namespace avd {
 
 constexpr int CASES_LDS_SHARED = 24 * AVD_MAX_L;                  // sA, sB, sC (floats), one copy per workgroup
 constexpr int CASES_LDS_ROW = 11 * AVD_MAX_L + NTHREADS;          // per row: xin, xs, raw, chain, negr, part (floats); + H1 + H2
+constexpr int DIST_RING = AVD_EVAL_MAX_DELAY + 1;                 // slots of a vehicle's V2V history
+// A vehicle's block in LDS, disturbed only: its case's A, B, C (24), its V2V ring, the last received value, its case's scalars (sigma
+// (3), delay, drop_q, seed (2)), one float of padding: an odd stride puts neighbouring vehicles on different banks. One block per
+// vehicle, the scalars repeated, so that a vehicle thread addresses all of it from one base register.
+constexpr int DIST_HIST = 24, DIST_RECV = DIST_HIST + DIST_RING, DIST_PAR = DIST_RECV + 1, DIST_VEH = DIST_PAR + 7 + 1;
+static_assert(DIST_VEH % 2 == 1, "odd stride");
+constexpr int DIST_LDS_ROW = DIST_VEH * AVD_MAX_L;                // per row
+static_assert((DIST_RING & (DIST_RING - 1)) == 0, "the ring index is taken with a mask");
 
 struct CasesArgs {
     avd_mlp_layout lay;
@@ -31,6 +46,15 @@ struct CasesArgs {
     float high, lo, hi, inv_dt;
     float* counters;          // [G][K][M]
     float* metrics;           // [G][K][L][AVD_EVAL_NMETRIC] or null
+};
+
+// The disturbed variant's per-case tables (device memory, [K] each; scenarios.py forms them)
+struct DistArgs {
+    const float* sigma;          // [K][3] sensor-noise standard deviations of ep, ev, a (finite, >= 0)
+    const int32_t* delay;        // [K] V2V delay in steps, 0 .. AVD_EVAL_MAX_DELAY
+    const uint32_t* drop_q;      // [K] V2V loss: a sample is dropped iff (word >> 8) < drop_q, drop_q = round(p * 2^24)
+    const uint64_t* noise_seed;  // [K] Philox key of the case's draws
+    const float* abc;            // [K][L][24] the true plant's A (16), B (4), C (4) per vehicle, or null: the constants block's
 };
 
 // the RB row operands of one k: xT[k][0..RB)
@@ -48,8 +72,10 @@ __device__ __forceinline__ void load_rows(const float* p, float (&x)[RB]) {
     }
 }
 
-// gemv_relu (learn_common.h) for RB rows: yT[n][r] = relu(sum_k xT[k][r] * W[k][n] + b[n]); part is [RB][NTHREADS]
-template <int RB>
+// gemv_relu (learn_common.h) for RB rows: yT[n][r] = relu(sum_k xT[k][r] * W[k][n] + b[n]); part is [RB][NTHREADS]. UNROLL_K is how
+// many k are in flight (registers against latency hiding): it does not touch the order of a row's sum.
+// 16 rows: two k in flight keep the kernel at 146 VGPRs (3 waves per SIMD)
+template <int RB, int UNROLL_K = (RB >= 16 ? 2 : 4)>
 __device__ __forceinline__ void gemv_relu_rows(const float* xT, int K, const float* __restrict__ W, const float* __restrict__ b, int N,
                                                float* part, float* yT) {
     const int cols = N < NTHREADS ? N : NTHREADS;
@@ -57,7 +83,6 @@ __device__ __forceinline__ void gemv_relu_rows(const float* xT, int K, const flo
     for (int n0 = 0; n0 < N; n0 += cols) {
         const int n = n0 + (threadIdx.x % cols);
         const int kh = threadIdx.x / cols;
-        constexpr int UNROLL_K = RB >= 16 ? 2 : 4;  // 16 rows: two k in flight keep the kernel at 146 VGPRs (3 waves per SIMD)
         float acc[RB];
 #pragma unroll
         for (int r = 0; r < RB; ++r) acc[r] = 0.f;
@@ -125,9 +150,12 @@ __device__ __forceinline__ void block_dot_rows(const float* xT, const float* __r
     __syncthreads();
 }
 
-template <int RB>
-__global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a) {
+// D is empty (the nominal kernel: parameter list and code as before the disturbed variant existed) or one DistArgs
+template <int RB, class... D>
+__global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a, const D... dist) {
 #pragma clang fp contract(off)
+    constexpr bool DIST = sizeof...(D) != 0;
+    constexpr int UK = RB >= 16 || (DIST && RB >= 8) ? 2 : 4;  // disturbed, 8 rows: 170 VGPRs with four k in flight, 2 waves per SIMD
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const avd_mlp_layout& L = a.lay;
     const int tid = threadIdx.x, nv = a.L, g = blockIdx.x, k0 = blockIdx.y * RB;
@@ -135,7 +163,7 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a)
     float* sA = smem;                               // [L][16]
     float* sB = sA + 16 * AVD_MAX_L;                // [L][4]
     float* sC = sB + 4 * AVD_MAX_L;                 // [L][4]
-    float* xs = sC + 4 * AVD_MAX_L;                 // [RB][4 * AVD_MAX_L] platoon states (the actors' input)
+    float* xs = sC + 4 * AVD_MAX_L;                 // [RB][4 * AVD_MAX_L] the actors' input: the platoon states (disturbed: as observed)
     float* xinT = xs + RB * 4 * AVD_MAX_L;          // [S][RB] one model's observation, transposed
     float* raw = xinT + RB * 4 * AVD_MAX_L;         // [RB][AVD_MAX_L] actor outputs, vehicle order (m * A + a)
     float* chain = raw + RB * AVD_MAX_L;            // [RB][AVD_MAX_L]
@@ -143,6 +171,8 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a)
     float* part = negr + RB * AVD_MAX_L;            // [RB][NTHREADS]
     float* h1T = part + RB * NTHREADS;              // [H1][RB]
     float* h2T = h1T + RB * L.H1;                   // [H2][RB]
+    float* vdat = h2T + RB * L.H2;                  // disturbed: [RB][AVD_MAX_L][DIST_VEH], see DIST_VEH. The scalars stay out of the
+                                                    // registers the forward needs: each step's observation phase reads them back
     const int row = tid / nv, v = tid - row * nv;   // vehicle threads: RB * L <= NTHREADS (host check)
     const bool veh = tid < RB * nv;
     const bool live = veh && row < nrows;           // a vehicle of a real case: the only threads that touch x0 / leader / the outputs
@@ -157,8 +187,29 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a)
         return;
     }
     const avd_env_consts* cst = a.cst;
-    for (int i = tid; i < nv * 16; i += NTHREADS) sA[i] = cst->A[i >> 4][i & 15];
-    for (int i = tid; i < nv * 4; i += NTHREADS) sB[i] = cst->B[i >> 2][i & 3], sC[i] = cst->C[i >> 2][i & 3];
+    if constexpr (DIST) {
+        const DistArgs da{dist...};
+        for (int i = tid; i < RB * nv * 24; i += NTHREADS) {
+            const int r = i / (nv * 24), j = i - r * (nv * 24), vi = j / 24, e = j - vi * 24;
+            vdat[(r * AVD_MAX_L + vi) * DIST_VEH + e] = (da.abc && r < nrows) ? da.abc[(long)(k0 + r) * nv * 24 + j]
+                                          : e < 16              ? cst->A[vi][e]
+                                          : e < 20              ? cst->B[vi][e - 16]
+                                                                : cst->C[vi][e - 20];
+        }
+        if (veh) {  // the case's disturbance; rows beyond the tail keep the null one
+            const long k = k0 + row;
+            float* p = vdat + (row * AVD_MAX_L + v) * DIST_VEH + DIST_PAR;
+            const uint64_t seed = live ? da.noise_seed[k] : 0;
+            p[0] = live ? da.sigma[k * 3] : 0.f, p[1] = live ? da.sigma[k * 3 + 1] : 0.f, p[2] = live ? da.sigma[k * 3 + 2] : 0.f;
+            // (the host refuses delays outside the ring; the mask keeps any value inside it)
+            p[3] = __int_as_float(live ? (da.delay[k] & (DIST_RING - 1)) : 0);
+            p[4] = __uint_as_float(live ? da.drop_q[k] : 0u);
+            p[5] = __uint_as_float((uint32_t)seed), p[6] = __uint_as_float((uint32_t)(seed >> 32));
+        }
+    } else {
+        for (int i = tid; i < nv * 16; i += NTHREADS) sA[i] = cst->A[i >> 4][i & 15];
+        for (int i = tid; i < nv * 4; i += NTHREADS) sB[i] = cst->B[i >> 2][i & 3], sC[i] = cst->C[i >> 2][i & 3];
+    }
     for (int i = tid; i < RB * 4 * AVD_MAX_L; i += NTHREADS) xs[i] = 0.f;
     __syncthreads();
     float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -170,10 +221,47 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a)
         xv = make_float4(x0[0], x0[1], x0[2], x0[3]);
         pa = a.prev_a0[(long)(k0 + row) * nv + v];
     }
-    if (veh) ((float4*)(xs + row * 4 * AVD_MAX_L))[v] = xv;
+    if constexpr (DIST) {
+        if (veh) {
+            float* hist = vdat + (row * AVD_MAX_L + v) * DIST_VEH + DIST_HIST;
+            for (int j = 0; j <= DIST_RING; ++j) hist[j] = xv.w;  // steps before the first, and the last received value: x0's
+        }
+    } else {
+        if (veh) ((float4*)(xs + row * 4 * AVD_MAX_L))[v] = xv;
+    }
     __syncthreads();
     const int S = L.S, A = L.A, M = a.M;
     for (int t = 0; t < a.T; ++t) {
+        if constexpr (DIST) {
+            // ---- what the actors see of the true pre-step state xv ----
+            if (veh) {
+                float* vd = vdat + (row * AVD_MAX_L + v) * DIST_VEH;
+                const float* p = vd + DIST_PAR;
+                const float sg_ep = p[0], sg_ev = p[1], sg_a = p[2];
+                const int dly = __float_as_int(p[3]);
+                const uint32_t dq = __float_as_uint(p[4]);
+                const uint64_t nseed = (uint64_t)__float_as_uint(p[5]) | ((uint64_t)__float_as_uint(p[6]) << 32);
+                float* hist = vd + DIST_HIST;  // this vehicle's ring (its own thread's alone), then its last received value
+                float4 ob = xv;
+                hist[t & (DIST_RING - 1)] = xv.w;
+                const float delayed = hist[(t - dly) & (DIST_RING - 1)];  // a slot of a step < 0 has not been overwritten yet
+                // loss: an integer compare on one Philox word (drop_q = 0 never drops: no draw needed)
+                const bool dropped = dq != 0 && (philox_at(nseed, (uint64_t)t, (uint32_t)v, STREAM_EVAL_LINK).x >> 8) < dq;
+                if (!dropped) hist[DIST_RING] = delayed;
+                ob.w = dropped ? hist[DIST_RING] : delayed;
+                if (sg_ep != 0.f || sg_ev != 0.f || sg_a != 0.f) {
+                    const u32x4 r = philox_at(nseed, (uint64_t)t, (uint32_t)v, STREAM_EVAL_OBS);
+                    float n_ev;
+                    const float n_ep = box_muller(r.x, r.y, &n_ev);
+                    const float n_a = box_muller(r.z, r.w, nullptr);
+                    if (sg_ep != 0.f) ob.x = xv.x + sg_ep * n_ep;  // a zero level skips the add: exact by construction
+                    if (sg_ev != 0.f) ob.y = xv.y + sg_ev * n_ev;
+                    if (sg_a != 0.f) ob.z = xv.z + sg_a * n_a;
+                }
+                ((float4*)(xs + row * 4 * AVD_MAX_L))[v] = ob;
+            }
+            __syncthreads();
+        }
         // ---- actor forward of each model, RB rows at once ----
         for (int m = 0; m < M; ++m) {
             const float* th = a.theta + (long)(base + m) * L.theta_size;
@@ -183,10 +271,10 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a)
                 xinT[s * RB + r] = xs[r * 4 * AVD_MAX_L + m * a.x_stride + s];
             }
             __syncthreads();
-            gemv_relu_rows<RB>(xinT, S, th + L.aW1, th + L.ab1, L.H1, part, h1T);
+            gemv_relu_rows<RB, UK>(xinT, S, th + L.aW1, th + L.ab1, L.H1, part, h1T);
             bn_apply_rows<RB>(h1T, L.H1, th + L.ag1, th + L.abe1, st + L.amm1, st + L.amv1);
             __syncthreads();
-            gemv_relu_rows<RB>(h1T, L.H1, th + L.aW2, th + L.ab2, L.H2, part, h2T);
+            gemv_relu_rows<RB, UK>(h1T, L.H1, th + L.aW2, th + L.ab2, L.H2, part, h2T);
             bn_apply_rows<RB>(h2T, L.H2, th + L.ag2, th + L.abe2, st + L.amm2, st + L.amv2);
             __syncthreads();
             for (int k = 0; k < A; ++k) {
@@ -204,14 +292,16 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a)
         VehStep vs = {};
         if (veh) {
             uu = fminf(fmaxf(raw[row * AVD_MAX_L + v], a.lo), a.hi);  // np.clip (ddpgagent.py:27)
-            vs = veh_step_pre(cst, sA + v * 16, sB + v * 4, xv, uu);
+            const float* Av = DIST ? vdat + (row * AVD_MAX_L + v) * DIST_VEH : sA + v * 16;  // this vehicle's A, B (disturbed: its case's)
+            vs = veh_step_pre(cst, Av, DIST ? Av + 16 : sB + v * 4, xv, uu);
             chain[row * AVD_MAX_L + v] = vs.chain;
         }
         __syncthreads();
         if (veh) {
             const float exog = (v == 0) ? (live ? leader[t] : 0.f) : chain[row * AVD_MAX_L + v - 1];
             float4 xn;
-            const float nr = veh_step_post(cst, vs, sB + v * 4, sC + v * 4, xv, pa, uu, exog, xn);
+            const float* Bv = DIST ? vdat + (row * AVD_MAX_L + v) * DIST_VEH + 16 : sB + v * 4;
+            const float nr = veh_step_post(cst, vs, Bv, DIST ? Bv + 4 : sC + v * 4, xv, pa, uu, exog, xn);
             if (M == nv) cnt = cnt + nr;  // counters += env.reward[0]
             else negr[row * AVD_MAX_L + v] = nr;
             // ---- metrics (scenarios.metrics_from_traces: sequential float32 sums in step order, no contraction) ----
@@ -226,7 +316,7 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a)
             mx_ep = fmaxf(mx_ep, fabsf(xn.x)), mx_ev = fmaxf(mx_ev, fabsf(xn.y)), mx_a = fmaxf(mx_a, fabsf(xn.z));
             pa = xv.z;  // prev_x <- x
             xv = xn;
-            ((float4*)(xs + row * 4 * AVD_MAX_L))[v] = xn;
+            if constexpr (!DIST) ((float4*)(xs + row * 4 * AVD_MAX_L))[v] = xn;
         }
         __syncthreads();
         if (M != nv && veh && v == 0) {  // centralized: counters += reward_mean = (1/L) * sum in vehicle order (env.hip)
@@ -246,20 +336,62 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a)
 
 // the block sizes instantiated, largest first
 constexpr int CASES_RB[] = {16, 8, 4, 1};
+// The disturbed kernel's: its 24 + 16 more floats per vehicle slot put 16 rows at 94.7 KB of LDS at the reference widths -- one
+// workgroup per CU where the nominal kernel keeps three. 8 rows take 48.1 KB and keep the three.
+constexpr int DIST_RB[] = {8, 4, 1};
 
-int cases_block(int K, int L) {
-    int rb = CASES_RB[0];
-    for (int c : CASES_RB)  // the smallest block that holds all K cases (no idle rows beyond the tail), else the largest
+template <int N>
+int pick_block(const int (&sizes)[N], int K, int L) {
+    int rb = sizes[0];
+    for (int c : sizes)  // the smallest block that holds all K cases (no idle rows beyond the tail), else the largest
         if (c >= K && c * L <= NTHREADS) rb = c;
     return rb;
 }
 
-template <int RB>
-int launch_cases(const CasesArgs& a, size_t lds, hipStream_t stream) {
+int cases_block(int K, int L) { return pick_block(CASES_RB, K, L); }
+
+template <int RB, class... D>
+int launch_cases(const char* who, const CasesArgs& a, size_t lds, hipStream_t stream, const D&... dist) {
     if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute((const void*)eval_cases_kernel<RB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(eval_cases_kernel<RB>, dim3(a.G, (a.K + RB - 1) / RB), dim3(NTHREADS), lds, stream, a);
-    return check_launch("avd_eval_cases_f32");
+        (void)hipFuncSetAttribute((const void*)eval_cases_kernel<RB, D...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((eval_cases_kernel<RB, D...>), dim3(a.G, (a.K + RB - 1) / RB), dim3(NTHREADS), lds, stream, a, dist...);
+    return check_launch(who);
+}
+
+// The checks, the block size and the argument block of the nominal (dist = false) and the disturbed entry point
+int cases_args(const char* who, const avd_mlp_layout* lay, const avd_env_consts* d_consts, int G, int K, int L, int M, int T,
+               const float* theta, const float* stats, int n_sets, const int32_t* set_base, const float* x0, const float* prev_a0,
+               const float* leader, float high, float lo, float hi, float sample_rate, float* counters, float* metrics, bool dist,
+               CasesArgs& a, int& rb, size_t& lds) {
+    AVD_REQUIRE(lay && d_consts, "%s: null layout or constants", who);
+    AVD_REQUIRE(L >= 1 && L <= AVD_MAX_L, "%s: L=%d (L must be 1..%d)", who, L, AVD_MAX_L);
+    AVD_REQUIRE(M == L || M == 1, "%s: M=%d (M must be L=%d, decentralized, or 1, centralized)", who, M, L);
+    AVD_REQUIRE(G >= 1 && K >= 1 && T >= 1, "%s: G=%d K=%d T=%d (all must be >= 1)", who, G, K, T);
+    AVD_REQUIRE(n_sets >= M, "%s: n_sets=%d (need n_sets >= M=%d)", who, n_sets, M);
+    AVD_REQUIRE(theta && stats && set_base && x0 && prev_a0 && leader && counters, "%s: null pointer", who);
+    AVD_REQUIRE(sample_rate > 0.f, "%s: sample_rate=%g", who, (double)sample_rate);
+    // the model shape the platoon implies: M * A = L actions, observations of 4L / M floats (the first S read)
+    const int x_stride = 4 * L / M;
+    AVD_REQUIRE(lay->A * M == L && lay->S <= x_stride && lay->S >= 1,
+                "%s: layout S=%d A=%d does not fit L=%d M=%d (need A * M == L, S <= %d)", who, lay->S, lay->A, L, M, x_stride);
+    AVD_REQUIRE(lay->H1 > 0 && lay->H2 > 0, "%s: layout H1=%d H2=%d", who, lay->H1, lay->H2);
+    rb = dist ? pick_block(DIST_RB, K, L) : cases_block(K, L);
+    const size_t row = (size_t)CASES_LDS_ROW + (dist ? DIST_LDS_ROW : 0) + lay->H1 + lay->H2;
+    lds = sizeof(float) * ((size_t)CASES_LDS_SHARED + (size_t)rb * row);
+    if (lds > 160 * 1024) {
+        set_error("%s: hidden sizes need %zu B of LDS for blocks of %d cases (> 160 KiB)", who, lds, rb);
+        return AVD_E_UNSUPPORTED;
+    }
+    if ((long)((K + rb - 1) / rb) > 65535) {
+        set_error("%s: K=%d cases in blocks of %d exceed the grid's second dimension", who, K, rb);
+        return AVD_E_UNSUPPORTED;
+    }
+    a.lay = *lay, a.cst = d_consts, a.G = G, a.K = K, a.L = L, a.M = M, a.T = T, a.x_stride = x_stride, a.n_sets = n_sets;
+    a.theta = theta, a.stats = stats, a.set_base = set_base, a.x0 = x0, a.prev_a0 = prev_a0, a.leader = leader;
+    a.high = high, a.lo = lo, a.hi = hi;
+    a.inv_dt = 1.0f / sample_rate;  // host float32 division, as avd_eval_rollout_f32 forms it
+    a.counters = counters, a.metrics = metrics;
+    return AVD_OK;
 }
 
 }  // namespace avd
@@ -276,38 +408,59 @@ extern "C" int avd_eval_cases_f32(const avd_mlp_layout* lay, const avd_env_const
                                   const float* theta, const float* stats, int n_sets, const int32_t* set_base, const float* x0,
                                   const float* prev_a0, const float* leader, float high, float lo, float hi, float sample_rate,
                                   float* counters, float* metrics, void* stream) {
-    AVD_REQUIRE(lay && d_consts, "avd_eval_cases_f32: null layout or constants");
-    AVD_REQUIRE(L >= 1 && L <= AVD_MAX_L, "avd_eval_cases_f32: L=%d (L must be 1..%d)", L, AVD_MAX_L);
-    AVD_REQUIRE(M == L || M == 1, "avd_eval_cases_f32: M=%d (M must be L=%d, decentralized, or 1, centralized)", M, L);
-    AVD_REQUIRE(G >= 1 && K >= 1 && T >= 1, "avd_eval_cases_f32: G=%d K=%d T=%d (all must be >= 1)", G, K, T);
-    AVD_REQUIRE(n_sets >= M, "avd_eval_cases_f32: n_sets=%d (need n_sets >= M=%d)", n_sets, M);
-    AVD_REQUIRE(theta && stats && set_base && x0 && prev_a0 && leader && counters, "avd_eval_cases_f32: null pointer");
-    AVD_REQUIRE(sample_rate > 0.f, "avd_eval_cases_f32: sample_rate=%g", (double)sample_rate);
-    // the model shape the platoon implies: M * A = L actions, observations of 4L / M floats (the first S read)
-    const int x_stride = 4 * L / M;
-    AVD_REQUIRE(lay->A * M == L && lay->S <= x_stride && lay->S >= 1,
-                "avd_eval_cases_f32: layout S=%d A=%d does not fit L=%d M=%d (need A * M == L, S <= %d)", lay->S, lay->A, L, M, x_stride);
-    AVD_REQUIRE(lay->H1 > 0 && lay->H2 > 0, "avd_eval_cases_f32: layout H1=%d H2=%d", lay->H1, lay->H2);
-    const int rb = cases_block(K, L);
-    const size_t lds = sizeof(float) * ((size_t)CASES_LDS_SHARED + (size_t)rb * ((size_t)CASES_LDS_ROW + lay->H1 + lay->H2));
-    if (lds > 160 * 1024) {
-        set_error("avd_eval_cases_f32: hidden sizes need %zu B of LDS for blocks of %d cases (> 160 KiB)", lds, rb);
-        return AVD_E_UNSUPPORTED;
-    }
-    if ((long)((K + rb - 1) / rb) > 65535) {
-        set_error("avd_eval_cases_f32: K=%d cases in blocks of %d exceed the grid's second dimension", K, rb);
-        return AVD_E_UNSUPPORTED;
-    }
+    const char* who = "avd_eval_cases_f32";
     CasesArgs a;
-    a.lay = *lay, a.cst = d_consts, a.G = G, a.K = K, a.L = L, a.M = M, a.T = T, a.x_stride = x_stride, a.n_sets = n_sets;
-    a.theta = theta, a.stats = stats, a.set_base = set_base, a.x0 = x0, a.prev_a0 = prev_a0, a.leader = leader;
-    a.high = high, a.lo = lo, a.hi = hi;
-    a.inv_dt = 1.0f / sample_rate;  // host float32 division, as avd_eval_rollout_f32 forms it
-    a.counters = counters, a.metrics = metrics;
+    int rb;
+    size_t lds;
+    if (const int rc = cases_args(who, lay, d_consts, G, K, L, M, T, theta, stats, n_sets, set_base, x0, prev_a0, leader, high, lo, hi,
+                                  sample_rate, counters, metrics, false, a, rb, lds))
+        return rc;
     switch (rb) {
-        case 16: return launch_cases<16>(a, lds, (hipStream_t)stream);
-        case 8: return launch_cases<8>(a, lds, (hipStream_t)stream);
-        case 4: return launch_cases<4>(a, lds, (hipStream_t)stream);
-        default: return launch_cases<1>(a, lds, (hipStream_t)stream);
+        case 16: return launch_cases<16>(who, a, lds, (hipStream_t)stream);
+        case 8: return launch_cases<8>(who, a, lds, (hipStream_t)stream);
+        case 4: return launch_cases<4>(who, a, lds, (hipStream_t)stream);
+        default: return launch_cases<1>(who, a, lds, (hipStream_t)stream);
+    }
+}
+
+extern "C" int avd_eval_cases_dist_block(int K, int L) {
+    AVD_REQUIRE(K >= 1, "avd_eval_cases_dist_block: K=%d (K must be >= 1)", K);
+    AVD_REQUIRE(L >= 1 && L <= AVD_MAX_L, "avd_eval_cases_dist_block: L=%d (L must be 1..%d)", L, AVD_MAX_L);
+    return pick_block(DIST_RB, K, L);
+}
+
+extern "C" int avd_eval_cases_dist_check(int K, const float* sigma, const int32_t* delay, const uint32_t* drop_q) {
+    const char* who = "avd_eval_cases_dist_check";
+    AVD_REQUIRE(K >= 1, "%s: K=%d (K must be >= 1)", who, K);
+    AVD_REQUIRE(sigma && delay && drop_q, "%s: null pointer", who);
+    for (int k = 0; k < K; ++k) {
+        for (int c = 0; c < 3; ++c)
+            AVD_REQUIRE(sigma[k * 3 + c] >= 0.f && sigma[k * 3 + c] <= FLT_MAX, "%s: sigma[%d][%d]=%g (must be finite and >= 0)", who, k, c,
+                        (double)sigma[k * 3 + c]);
+        AVD_REQUIRE(delay[k] >= 0 && delay[k] <= AVD_EVAL_MAX_DELAY, "%s: delay[%d]=%d (must be 0..%d)", who, k, delay[k],
+                    AVD_EVAL_MAX_DELAY);
+        AVD_REQUIRE(drop_q[k] <= (1u << 24), "%s: drop_q[%d]=%u (must be <= 2^24 = %u)", who, k, drop_q[k], 1u << 24);
+    }
+    return AVD_OK;
+}
+
+extern "C" int avd_eval_cases_dist_f32(const avd_mlp_layout* lay, const avd_env_consts* d_consts, int G, int K, int L, int M, int T,
+                                       const float* theta, const float* stats, int n_sets, const int32_t* set_base, const float* x0,
+                                       const float* prev_a0, const float* leader, float high, float lo, float hi, float sample_rate,
+                                       const float* sigma, const int32_t* delay, const uint32_t* drop_q, const uint64_t* noise_seed,
+                                       const float* abc, float* counters, float* metrics, void* stream) {
+    const char* who = "avd_eval_cases_dist_f32";
+    CasesArgs a;
+    int rb;
+    size_t lds;
+    if (const int rc = cases_args(who, lay, d_consts, G, K, L, M, T, theta, stats, n_sets, set_base, x0, prev_a0, leader, high, lo, hi,
+                                  sample_rate, counters, metrics, true, a, rb, lds))
+        return rc;
+    AVD_REQUIRE(sigma && delay && drop_q && noise_seed, "%s: null disturbance table (only abc may be null)", who);
+    const DistArgs d = {sigma, delay, drop_q, noise_seed, abc};
+    switch (rb) {
+        case 8: return launch_cases<8>(who, a, lds, (hipStream_t)stream, d);
+        case 4: return launch_cases<4>(who, a, lds, (hipStream_t)stream, d);
+        default: return launch_cases<1>(who, a, lds, (hipStream_t)stream, d);
     }
 }

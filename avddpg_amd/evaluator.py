@@ -285,3 +285,100 @@ def run_cases(conf, actors, platoons, scenarios=("gaussian",), seeds=None, amp=N
     b = prepare_cases(conf, actors, platoons, scenarios, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override)
     b.launch()
     return b.results()
+
+
+class DisturbedResults:
+    """What run_disturbed returns: CaseResults' fields with a disturbance axis after the scenario axis -- ``scores`` float32 [NP, n_scen,
+    n_dist + 1, n_seed], ``counters`` [..., M], ``metrics`` {name: [..., L]}, ``summary()`` -- and ``disturbances``, the levels' names
+    with "nominal" first. ``nominal()`` is the undisturbed level as a plain CaseResults."""
+
+    def __init__(self, scenarios, disturbances, seeds, T, scores, counters, metrics):
+        self.scenarios, self.disturbances, self.seeds, self.T = list(scenarios), list(disturbances), list(seeds), int(T)
+        self.scores, self.counters, self.metrics = scores, counters, metrics
+
+    def summary(self):
+        from . import scenarios as _sc
+
+        return _sc.summarise(self.metrics, self.T)
+
+    def nominal(self):
+        return CaseResults(self.scenarios, self.seeds, self.T, self.scores[:, :, 0], self.counters[:, :, 0],
+                           {k: v[:, :, 0] for k, v in self.metrics.items()})
+
+
+class DisturbedBatch(CaseBatch):
+    """The device inputs of one avd_eval_cases_dist_f32 launch (prepare_disturbed): CaseBatch's cases with a disturbance axis between
+    scenario and seed, and the per-case disturbance tables. ``levels`` are the Disturbances, scenarios.NOMINAL first."""
+
+    def __init__(self, conf, actors, platoons, scenarios, disturbances, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override):
+        from . import _hip
+        from . import scenarios as _sc
+
+        levels = [_sc.NOMINAL] + _sc.check_disturbances(disturbances, conf)
+        super().__init__(conf, actors, platoons, scenarios, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override)
+        NC, ND, NS, L, dev = self.NC, len(levels), self.NS, self.L, self.x0.device
+        self.levels, self.ND, self.K = levels, ND, NC * ND * NS
+        # cases: scenarios x levels x seeds, seeds innermost; a case's start state and leader row are its (scenario, seed)'s, always
+        # the nominal configuration's
+        widen = lambda x: x.reshape(NC, 1, NS, *x.shape[1:]).repeat_interleave(ND, dim=1).reshape(self.K, *x.shape[1:]).contiguous()
+        self.leader_h = np.repeat(self.leader_h.reshape(NC, 1, NS, -1), ND, axis=1).reshape(self.K, -1)
+        self.x0, self.pa0, self.leader = widen(self.x0), widen(self.pa0), widen(self.leader)
+        lvl = np.tile(np.repeat(np.arange(ND), NS), NC)  # a case's level
+        self.sigma_h = np.array([d.sigma for d in levels], dtype=np.float32)[lvl]
+        self.delay_h = np.array([int(d.v2v_delay) for d in levels], dtype=np.int32)[lvl]
+        self.drop_q_h = np.array([_sc.drop_threshold(d.v2v_drop) for d in levels], dtype=np.uint32)[lvl]
+        # the noise seed is the case's evaluation seed: every level of a seed shares its draws
+        self.noise_seed_h = np.tile(np.array(self.seeds, dtype=np.uint64), NC * ND)
+        # host check of the tables (the kernel reads them from device memory)
+        _hip.call("avd_eval_cases_dist_check", self.K, self.sigma_h.ctypes.data, self.delay_h.ctypes.data, self.drop_q_h.ctypes.data)
+        up = lambda a, as_type=None: torch.from_numpy(a if as_type is None else a.view(as_type)).to(dev)  # (torch: signed integers)
+        self.sigma, self.delay = up(self.sigma_h), up(self.delay_h)
+        self.drop_q, self.noise_seed = up(self.drop_q_h, np.int32), up(self.noise_seed_h, np.int64)
+        # the true plants: a table only when a level changes the plant (null: the constants block's matrices for every case)
+        self.abc = None
+        if any(d.dyn_coeff is not None for d in levels):
+            self.abc = up(np.stack([_sc.plant_table(conf, L, d.dyn_coeff) for d in levels])[lvl])  # [K, L, 24]
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.counters = torch.empty(self.G, self.K, self.M, **f32)
+        self.metrics = torch.empty(self.G, self.K, L, _hip.AVD_EVAL_NMETRIC, **f32)
+        self.block = int(_hip.lib().avd_eval_cases_dist_block(self.K, L))
+
+    def launch(self):
+        a, c = self.actors, self.conf
+        call("avd_eval_cases_dist_f32", a._layp, ptr(self.env.d_consts), self.G, self.K, self.L, self.M, self.T, ptr(a.theta),
+             ptr(a.stats), a.n_sets, ptr(self.set_base), ptr(self.x0), ptr(self.pa0), ptr(self.leader), a.high, c.action_low,
+             c.action_high, c.sample_rate, ptr(self.sigma), ptr(self.delay), ptr(self.drop_q), ptr(self.noise_seed), ptr(self.abc),
+             ptr(self.counters), ptr(self.metrics), stream_handle())
+
+    def results(self):
+        from . import scenarios as _sc
+
+        c = self.counters.cpu().numpy().reshape(self.G * self.K, self.M)
+        rows = np.array([round(np.average(r), 3) for r in c], dtype=np.float32)  # row by row, as run (:145)
+        sel = [self.group(i) for i in range(self.NP)]
+        shape = (self.G, self.NC, self.ND, self.NS)
+        m = self.metrics.cpu().numpy().reshape(*shape, self.L, -1)[sel]
+        metrics = {n: np.ascontiguousarray(m[..., j]) for j, n in enumerate(_sc.METRICS)}
+        return DisturbedResults(self.scenarios, [d.name for d in self.levels], self.seeds, self.T, rows.reshape(shape)[sel],
+                                c.reshape(*shape, self.M)[sel], metrics)
+
+
+def prepare_disturbed(conf, actors, platoons, scenarios=("gaussian",), disturbances=(), seeds=None, amp=None, period_s=10.0, set_mod=None,
+                      set_bases=None, manual_timestep_override=None):
+    """run_disturbed's host part (run_cases' plus the per-case disturbance tables, checked and uploaded) as a DisturbedBatch."""
+    return DisturbedBatch(conf, actors, platoons, scenarios, disturbances, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override)
+
+
+def run_disturbed(conf, actors, platoons, scenarios=("gaussian",), disturbances=(), seeds=None, amp=None, period_s=10.0, set_mod=None,
+                  set_bases=None, manual_timestep_override=None):
+    """run_cases under disturbances: every platoon's actors over scenarios x [nominal, *disturbances] x seeds (seeds innermost) in ONE
+    launch of the disturbed scenario evaluator (avd_eval_cases_dist_f32, csrc/evalx.hip). A scenarios.Disturbance acts on what the
+    actors observe (sensor noise on ep, ev, a; delay and loss on the communicated 4th state) and on the plant (its engine lag); counters
+    and metrics come from the true state, and start states are always the nominal configuration's. The noise seed of a case is its
+    evaluation seed. Everything else is as in run_cases.
+
+    Returns a DisturbedResults; its ``nominal()`` slice, and every level whose axes are all at their zero, is bit-identical to
+    run_cases on the same scenarios and seeds."""
+    b = prepare_disturbed(conf, actors, platoons, scenarios, disturbances, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override)
+    b.launch()
+    return b.results()

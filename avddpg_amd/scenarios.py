@@ -146,6 +146,146 @@ def write_csv(path, results, platoon_tags):
         w.writerows(csv_rows(results, platoon_tags))
 
 
+# ---- disturbances: what the disturbed scenario evaluator (avd_eval_cases_dist_f32) applies per case ---------------------------------
+
+MAX_DELAY = 15  # AVD_EVAL_MAX_DELAY
+DISTURBANCE_KEYS = ("noise_ep", "noise_ev", "noise_a", "v2v_delay", "v2v_drop", "dyn_coeff")
+
+
+class Disturbance:
+    """One robustness level: sensor-noise standard deviations on the observed ep, ev and a; a delay (steps) and a loss probability on the
+    V2V link that carries the predecessor's acceleration (the 4th Model-B observation); the TRUE plant's engine lag ``dyn_coeff`` (None:
+    the configuration's) while the actors stay those trained on the configuration's. Rewards and metrics come from the true state."""
+
+    def __init__(self, name, noise_ep=0, noise_ev=0, noise_a=0, v2v_delay=0, v2v_drop=0.0, dyn_coeff=None):
+        self.name = str(name)
+        self.noise_ep, self.noise_ev, self.noise_a = noise_ep, noise_ev, noise_a
+        self.v2v_delay, self.v2v_drop, self.dyn_coeff = v2v_delay, v2v_drop, dyn_coeff
+
+    @property
+    def sigma(self):
+        return (float(self.noise_ep), float(self.noise_ev), float(self.noise_a))
+
+    @property
+    def uses_v2v(self):
+        return self.v2v_delay != 0 or self.v2v_drop != 0
+
+    def items(self):
+        """[(key, value)] in DISTURBANCE_KEYS order (conf.json's robustness_suite)."""
+        return [[k, getattr(self, k)] for k in DISTURBANCE_KEYS]
+
+    def __repr__(self):
+        return "Disturbance(" + ", ".join([repr(self.name)] + [f"{k}={v!r}" for k, v in self.items()]) + ")"
+
+
+NOMINAL = Disturbance("nominal")
+
+
+def parse_disturbance(text):
+    """``NAME:key=val,...`` (keys of DISTURBANCE_KEYS) -> Disturbance; ``NAME`` alone is the null disturbance under that name. An unknown
+    key, a key given twice or a value that is no number is a ValueError; the values are checked by check_disturbances."""
+    name, _, spec = str(text).partition(":")
+    name = name.strip()
+    if not name:
+        raise ValueError(f"disturbance {text!r}: no name before ':'")
+    kw = {}
+    for part in [q.strip() for q in spec.split(",") if q.strip()]:
+        key, eq, val = part.partition("=")
+        key, val = key.strip(), val.strip()
+        if not eq or key not in DISTURBANCE_KEYS:
+            raise ValueError(f"disturbance {name!r}: unknown key {key!r} (one of {', '.join(DISTURBANCE_KEYS)}, as key=value)")
+        if key in kw:
+            raise ValueError(f"disturbance {name!r}: {key} given twice")
+        try:
+            kw[key] = int(val) if key == "v2v_delay" else float(val)
+        except ValueError:
+            raise ValueError(f"disturbance {name!r}: {key}={val!r} is not {'an integer' if key == 'v2v_delay' else 'a number'}") from None
+    return Disturbance(name, **kw)
+
+
+def check_disturbances(disturbances, conf=None):
+    """The disturbances as a list. A ValueError for: a non-finite or negative value; a delay outside 0..MAX_DELAY or not an integer; a
+    drop outside [0, 1]; dyn_coeff <= 0; a name listed twice; the reserved name ``nominal``; with ``conf``, a V2V axis under Model A
+    (its 3-state observation has no communicated component)."""
+    out = list(disturbances)
+    for d in out:
+        if not isinstance(d, Disturbance):
+            raise ValueError(f"{d!r} is not a scenarios.Disturbance")
+        if d.name == NOMINAL.name:
+            raise ValueError(f"the disturbance name {NOMINAL.name!r} is reserved for the undisturbed level")
+        for k, v in d.items():
+            if k == "dyn_coeff" and v is None:
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or v < 0:
+                raise ValueError(f"disturbance {d.name!r}: {k}={v!r} must be a finite number >= 0")
+        if d.v2v_delay != int(d.v2v_delay) or not 0 <= d.v2v_delay <= MAX_DELAY:
+            raise ValueError(f"disturbance {d.name!r}: v2v_delay={d.v2v_delay!r} must be an integer in 0..{MAX_DELAY}")
+        if d.v2v_drop > 1:
+            raise ValueError(f"disturbance {d.name!r}: v2v_drop={d.v2v_drop!r} must be in [0, 1]")
+        if d.dyn_coeff is not None and d.dyn_coeff <= 0:
+            raise ValueError(f"disturbance {d.name!r}: dyn_coeff={d.dyn_coeff!r} must be > 0")
+        if conf is not None and conf.model == conf.modelA and d.uses_v2v:
+            raise ValueError(f"disturbance {d.name!r}: v2v_delay / v2v_drop need Model B (Model A observes no communicated state)")
+    names = [d.name for d in out]
+    dup = sorted({n for n in names if names.count(n) > 1})
+    if dup:
+        raise ValueError(f"disturbance(s) {dup} listed more than once")
+    return out
+
+
+def drop_threshold(v2v_drop):
+    """drop_q = round(v2v_drop * 2^24): the device drops a V2V sample iff (philox word >> 8) < drop_q, an integer compare (0: never,
+    2^24: always)."""
+    return int(round(float(v2v_drop) * (1 << 24)))
+
+
+def plant_table(conf, L, dyn_coeff=None):
+    """float32 [L, 24] -- A (16, row-major), B (4), C (4) per vehicle -- of a platoon whose followers all have engine lag ``dyn_coeff``
+    (default conf.dyn_coeff): dynamics.system_matrices in float64 with the tau chaining of dynamics.env_consts (vehicle 0 follows
+    pl_leader_tau, vehicle i >= 1 its predecessor's lag), rounded to float32 once as env_consts rounds."""
+    from . import dynamics
+
+    tau = float(conf.dyn_coeff if dyn_coeff is None else dyn_coeff)
+    out = np.zeros((L, 24), dtype=np.float32)
+    for i in range(L):
+        A, B, Cm = dynamics.system_matrices(conf.method, conf.sample_rate, tau, conf.pl_leader_tau if i == 0 else tau, conf.timegap)
+        if conf.model == conf.modelA and Cm[2] != 0.0:
+            raise ValueError("Model A chain needs C[2] == 0 (acceleration row independent of the exogenous input)")
+        out[i] = np.concatenate([A.ravel(), B, Cm]).astype(np.float32)
+    return out
+
+
+ROBUSTNESS_HEADER = [*CSV_HEADER[:2], "disturbance", *CSV_HEADER[2:], "score_delta"]
+
+
+def robustness_rows(results, platoon_tags):
+    """csv_rows for a DisturbedResults ([P, scen, dist, seed, ...] arrays): one row per (platoon, scenario, disturbance, seed, vehicle),
+    the nominal level first, with the columns of scenarios.csv, the level's name after the scenario's and, last, score_delta = the
+    case's score minus the nominal score of the same platoon, scenario and seed (float32)."""
+    s = results.summary()
+    f = lambda x: "" if np.isnan(x) else repr(float(x))
+    rows = []
+    for i, tag in enumerate(platoon_tags):
+        for c, name in enumerate(results.scenarios):
+            for d, level in enumerate(results.disturbances):
+                for k, seed in enumerate(results.seeds):
+                    for v in range(results.metrics[METRICS[0]].shape[-1]):
+                        at = (i, c, d, k, v)
+                        rows.append([tag, name, level, seed, v + 1, *[f(results.metrics[m][at]) for m in METRICS], f(s["rms_u"][at]),
+                                     f(s["rms_jerk"][at]), f(s["ss_ratio"][at]), f(results.scores[i, c, d, k]),
+                                     f(results.scores[i, c, d, k] - results.scores[i, c, 0, k])])
+    return rows
+
+
+def write_robustness_csv(path, results, platoon_tags):
+    import csv
+
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(ROBUSTNESS_HEADER)
+        w.writerows(robustness_rows(results, platoon_tags))
+
+
 def report_lines(results, platoon_tags):
     """One line per platoon and scenario: the mean score over the seeds, the worst max_abs_ep over seeds and vehicles, and whether
     every seed's rollout was string stable."""

@@ -742,6 +742,32 @@ class VecTrainer:
             return evaluator.CaseResults(r.scenarios, r.seeds, r.T, rep(r.scores), rep(r.counters), {k: rep(v) for k, v in r.metrics.items()})
         return evaluator.run_cases(self.conf, self.agents, platoons, **kw)
 
+    def evaluate_robustness(self, scenarios, disturbances, seeds=None, platoons=None, amp=None, period_s=10.0):
+        """evaluate_scenarios under disturbances: the CURRENT actors of each of this rank's ``platoons`` over leader scenarios x
+        [nominal, *disturbances] x evaluation seeds, from one launch of the disturbed scenario evaluator (evaluator.run_disturbed): a
+        DisturbedResults with scores [P, scen, dist, seed], counters [P, scen, dist, seed, M] and metrics {name: [P, scen, dist, seed,
+        L]}; its nominal() slice equals evaluate_scenarios. A seed batch or sweep: every array gains a leading experiment axis ([E, P,
+        scen, dist, seed, ...]); experiment e's slice equals run_disturbed on experiment_agents(e)."""
+        from . import evaluator
+
+        kw = dict(scenarios=scenarios, disturbances=disturbances, seeds=seeds, amp=amp, period_s=period_s)
+        mapped = lambda r, f: evaluator.DisturbedResults(r.scenarios, r.disturbances, r.seeds, r.T, f(r.scores), f(r.counters),
+                                                         {k: f(v) for k, v in r.metrics.items()})
+        if self.seeds is not None:
+            E, M = self.E, self.M
+            platoons = list(range(self.P_exp)) if platoons is None else list(platoons)
+            n = len(platoons)
+            if self.shared:  # one group per experiment, on its sets e*M .. e*M+M-1
+                r = evaluator.run_disturbed(self.conf, self.agents, list(range(E)), set_mod=M, set_bases=[e * M for e in range(E)], **kw)
+                return mapped(r, lambda x: np.repeat(x[:, None], n, axis=1))
+            r = evaluator.run_disturbed(self.conf, self.agents, [vec.batch_platoon(e, p, E) for e in range(E) for p in platoons], **kw)
+            return mapped(r, lambda x: x.reshape(E, n, *x.shape[1:]))
+        platoons = list(range(self.P)) if platoons is None else list(platoons)
+        if self.shared:
+            r = evaluator.run_disturbed(self.conf, self.agents, [0], set_mod=self.M, **kw)
+            return mapped(r, lambda x: np.repeat(x, len(platoons), axis=0))
+        return evaluator.run_disturbed(self.conf, self.agents, platoons, **kw)
+
     def run_simulations(self):
         """Trainer.run_simulations (workers/trainer.py:537-550): every local platoon's evaluator score over steps_per_episode
         steps divided by re_scalar -- the values the reference appends to conf.pl_rews_for_simulations (:549). Plots and the

@@ -570,6 +570,29 @@ int avd_eval_cases_f32(const avd_mlp_layout* lay, const avd_env_consts* d_consts
  * (>= 1), or AVD_E_INVALID for K < 1 or L outside 1..AVD_MAX_L. */
 int avd_eval_cases_block(int K, int L);
 
+/* ---- disturbed scenario evaluator: avd_eval_cases_f32 with one disturbance per case --------------------------------------------
+ * The disturbance acts on what the actors observe and on the plant; counters and metrics come from the true state. Per step t and
+ * vehicle v, with the true pre-step state x = (ep, ev, a, w), per-case tables in DEVICE memory:
+ *   V2V link (w, the 4th observation): hist[j] = the true w at step j (x0's for j < 0); delayed = hist[t - delay[k]]; the sample is
+ *     dropped iff (philox(noise_seed[k], t, v, stream 7).x >> 8) < drop_q[k] (drop_q = round(p * 2^24): 0 never, 2^24 always);
+ *     received = dropped ? the last received value (x0's at first) : delayed.
+ *   sensor noise: r = philox(noise_seed[k], t, v, stream 6); (n_ep, n_ev) = box_muller(r.x, r.y), n_a = box_muller(r.z, r.w) (cos);
+ *     observed = x + sigma[k][c] * n_c without contraction; a zero sigma skips the add.
+ *   plant: abc[k] [L][24] = the true plant's A (16, row-major), B (4), C (4) per vehicle; NULL: the constants block's for every case.
+ * A case with sigma = 0, delay = 0, drop_q = 0 and the constants block's matrices is bit-identical to avd_eval_cases_f32's. The host
+ * cannot read the tables: avd_eval_cases_dist_check validates HOST copies of them (sigma finite and >= 0, delay 0 ..
+ * AVD_EVAL_MAX_DELAY, drop_q <= 2^24) before the caller uploads them; the kernel takes a delay modulo the ring and is memory-safe for
+ * any value. Blocks of avd_eval_cases_dist_block(K, L) cases (smaller than the nominal kernel's: more LDS per case). */
+#define AVD_EVAL_MAX_DELAY 15
+int avd_eval_cases_dist_f32(const avd_mlp_layout* lay, const avd_env_consts* d_consts, int G, int K, int L, int M, int T,
+                            const float* theta, const float* stats, int n_sets, const int32_t* set_base, const float* x0,
+                            const float* prev_a0, const float* leader, float high, float lo, float hi, float sample_rate,
+                            const float* sigma, const int32_t* delay, const uint32_t* drop_q, const uint64_t* noise_seed,
+                            const float* abc, float* counters, float* metrics, void* stream);
+int avd_eval_cases_dist_block(int K, int L);
+/* host only, no HIP call: sigma [K][3], delay [K], drop_q [K] in HOST memory */
+int avd_eval_cases_dist_check(int K, const float* sigma, const int32_t* delay, const uint32_t* drop_q);
+
 /* D[M][Nc] (f32, ldd) = A[M][K] . B[Nc][K]^T with bf16 operands (K contiguous, K % 64 == 0) and f32 accumulation: the
  * GEMM under avd_learn_shared_bf16, exposed for parity tests. A and B must be readable up to the next multiple of 256
  * rows. */
