@@ -137,6 +137,12 @@ def _disturb(args):
     return getattr(args, "disturb", None)
 
 
+def _record_train_levels(conf, args):
+    """conf.json's train_disturbances: the --train_disturb levels in the shape of robustness_suite ([name, [[key, value], ...]] pairs)."""
+    if getattr(args, "train_disturb", None) is not None:
+        conf.train_disturbances = [[x.name, x.items()] for x in args.train_disturb]
+
+
 def _suite(args):
     """run_cases' keyword arguments from the scenario flags."""
     return dict(scenarios=args.scenarios, seeds=args.eval_seeds, amp=args.scenario_amp,
@@ -240,6 +246,13 @@ def get_cmdl_args(argv, conf):
                                                                         "(default 0.25)")
     tr.add_argument("--pbt_perturb", type=str, default=None, metavar="F1,F2,...",
                     help="--pbt: the factors a replaced experiment's swept values are multiplied by, one drawn per value (default 0.8,1.2)")
+    tr.add_argument("--train_disturb", action="append", default=None, metavar="NAME[:key=val,...]",
+                    help="--rng device: TRAIN under disturbance levels (domain randomisation; repeat the flag for more levels, at most 16): "
+                         "platoon p trains under level p %% n_levels for the whole run. The keys are --disturb's (noise_ep, noise_ev, noise_a, "
+                         "v2v_delay, v2v_drop, dyn_coeff); a bare NAME is the undisturbed level, a clean share of platoons. The replay holds "
+                         "what the agents observed; rewards and episodes come from the true state. conf.json records the levels as "
+                         "train_disturbances. Composes with --seeds, --scenarios and --disturb; not with --sweep / --pbt, the centralized "
+                         "framework or a process group (not in the reference CLI)")
     _scenario_flags(tr, "after training, beside the simulation rewards:")
     tr.add_argument("--out", type=str, default=".outputs")
     es = sub.add_parser("esim", help="run in evaluation/simulator mode")
@@ -270,6 +283,19 @@ def get_cmdl_args(argv, conf):
         for name, _ in args.sweep:  # (the parsed values: argparse also takes abbreviations such as --actor)
             if getattr(args, name, None) is not None:
                 ap.error(f"--sweep {name} and --{name} are mutually exclusive")
+    if getattr(args, "train_disturb", None) is not None:
+        from .scenarios import check_disturbances, parse_disturbance
+
+        if args.rng != "device":
+            ap.error("--train_disturb needs --rng device")
+        if args.sweep is not None:
+            ap.error("--train_disturb does not combine with --sweep / --pbt")
+        if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+            ap.error("--train_disturb is not available under a process group of more than one rank")
+        try:  # (the Model A refusal and the level cap need the run's configuration: trainer.check_train_disturb applies them)
+            args.train_disturb = check_disturbances([parse_disturbance(d) for d in args.train_disturb])
+        except ValueError as e:
+            ap.error(f"--train_disturb: {e}")
     if getattr(args, "pbt", None) is not None or getattr(args, "pbt_fraction", None) is not None or getattr(args, "pbt_perturb", None) is not None:
         if args.pbt is None:
             ap.error("--pbt_fraction / --pbt_perturb need --pbt")
@@ -337,7 +363,13 @@ def main(argv=None, conf=None):
                 raise SystemExit("--episodes platoon needs --rng device")
             from . import evaluator
             nofrl = conf.fed_method == conf.nofrl
-            vt = trainer.VecTrainer(conf, rng="device", auto_reset="platoon", shared_engine=args.engine, fused_update=nofrl)
+            try:
+                vt = trainer.VecTrainer(conf, rng="device", auto_reset="platoon", shared_engine=args.engine, fused_update=nofrl,
+                                        train_disturb=args.train_disturb)
+            except ValueError as e:
+                if args.train_disturb is None:
+                    raise
+                raise SystemExit(f"--train_disturb: {e}")
             vt.reset_episode()
             rng_state = np.random.get_state()
 
@@ -372,7 +404,12 @@ def main(argv=None, conf=None):
             if vt.nonfinite_updates():
                 print(f"warning: {vt.nonfinite_updates()} weight-set updates were skipped for non-finite gradients", file=sys.stderr)
         else:
-            vt = trainer.VecTrainer(conf, rng=args.rng, auto_reset=False, shared_engine=args.engine)
+            try:
+                vt = trainer.VecTrainer(conf, rng=args.rng, auto_reset=False, shared_engine=args.engine, train_disturb=args.train_disturb)
+            except ValueError as e:
+                if args.train_disturb is None:
+                    raise
+                raise SystemExit(f"--train_disturb: {e}")
             ep, avg = vt.run()
             artifacts.generate_csvs(base, conf, ep, avg)
         # Trainer.run / run_simulations (workers/trainer.py:277-280, 537-550): every platoon's evaluator score / re_scalar and their
@@ -392,6 +429,7 @@ def main(argv=None, conf=None):
                               else "per-platoon episodes on the device; schedule predicates on step // steps_per_episode; weighted averaging "
                                    "(if enabled) from step weighted_window x steps_per_episode on, weights from each agent's last "
                                    "weighted_window closed episodes")
+        _record_train_levels(conf, args)
         artifacts.config_writer(os.path.join(base, "conf.json"), conf)
         print(base)
     elif args.mode == "esim":
@@ -468,9 +506,15 @@ def train_seed_batch(args, conf, base, experiments=None):
         seeds, hps, flag = [k for _, _, k in experiments], [h for _, h, _ in experiments], "--sweep"
         dirs = [os.path.join(base, label, f"seed{k}") for label, _, k in experiments]
     E = len(seeds)
+    if getattr(args, "train_disturb", None) is not None:  # (its own refusals under its own flag's name)
+        try:
+            trainer.check_train_disturb(conf, args.train_disturb, "device", None, hparams=hps)
+        except ValueError as e:
+            raise SystemExit(f"--train_disturb: {e}")
     try:
         vt = trainer.VecTrainer(conf, rng="device", auto_reset="platoon", shared_engine=args.engine,
-                                fused_update=conf.fed_method == conf.nofrl, seeds=seeds, hparams=hps)
+                                fused_update=conf.fed_method == conf.nofrl, seeds=seeds, hparams=hps,
+                                train_disturb=getattr(args, "train_disturb", None))
     except ValueError as e:
         raise SystemExit(f"{flag}: {e}")
     vt.reset_episode()
@@ -558,6 +602,7 @@ def train_seed_batch(args, conf, base, experiments=None):
             if use_pbt:  # (lists of pairs, as `sweep`: conf.json keeps lists, not dicts, at the top level)
                 ce.pbt = [["interval", args.pbt], ["fraction", args.pbt_fraction], ["perturb", list(args.pbt_perturb)],
                           ["lineage", lineage[e]]]
+        _record_train_levels(ce, args)
         if suite is not None:
             _write_suite(d, ce, _slice(suite, e), range(1, P + 1), args)
         artifacts.config_writer(os.path.join(d, "conf.json"), ce)

@@ -15,6 +15,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "avddpg_hip.h")
 AVD_MAX_L = 16
 AVD_EVAL_NMETRIC = 8
 AVD_EVAL_MAX_DELAY = 15
+AVD_TRAIN_MAX_LEVELS = 16
 
 
 class AvdError(RuntimeError):
@@ -40,6 +41,11 @@ class HParams(C.Structure):
     """avd_hparams: one experiment's row of a hyperparameter sweep's device table (32 bytes)"""
     _fields_ = [("actor_lr", C.c_float), ("critic_lr", C.c_float), ("tau", C.c_float), ("one_minus_tau", C.c_float),
                 ("gamma", C.c_float), ("ou_theta", C.c_float), ("ou_scale", C.c_float), ("reserved", C.c_float)]
+
+
+class TrainLevel(C.Structure):
+    """avd_train_level: one disturbance level of a training run's device table (32 bytes)"""
+    _fields_ = [("sigma", C.c_float * 3), ("delay", C.c_int32), ("drop_q", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 _LAYOUT_FIELDS = ["S", "A", "H1", "H2", "Ha", "B",
@@ -78,6 +84,12 @@ _PROTOS = {
     "avd_replay_sample_seeds_f32": [_i, _i, _i, _i, _i, _P, _i, _P, _i, _i, _u64, _P, _P, _P, _P, _P, _P],
     "avd_step_fused_hp_f32": [_P, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _f, _f, _f, _i, _P, _P, _i,
                               _u64, _u64, _P, _i, _i64, _P, _P],
+    "avd_step_fused_dist_f32": [_P, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _f, _f, _f, _f, _f, _i, _u64,
+                                _u64, _u64, _P, _i, _i64, _P, _i, _P, _P, _P, _P, _P, _P, _P, _u64, _P],
+    "avd_step_fused_dist_seeds_f32": [_P, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _f, _f, _f, _f, _f, _i,
+                                      _P, _i, _u64, _u64, _P, _i, _i64, _P, _i, _P, _P, _P, _P, _P, _P, _P, _u64, _P],
+    "avd_observe_f32": [_i, _i, _P, _P, _i, _P, _P, _P, _u64, _u64, _P, _P, _P],
+    "avd_observe_seeds_f32": [_i, _i, _P, _P, _i, _P, _P, _P, _P, _i, _u64, _P, _P, _P],
     "avd_learn_hp_f32": [_LP, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _f, _P, _P, _P, _i, _i, _P],
     "avd_learn_update_hp_f32": [_LP, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _P, _P, _P, _i, _i, _P],
     "avd_learn_update_act_hp_f32": [_LP, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _P, _P, _P, _i, _P, _P, _i, _i, _P],

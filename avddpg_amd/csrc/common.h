@@ -109,6 +109,8 @@ enum PhiloxStream : uint32_t {
     STREAM_REPLAY = 5,
     STREAM_EVAL_OBS = 6,   // disturbed scenario evaluator: sensor noise, (counter, index) = (step, vehicle)
     STREAM_EVAL_LINK = 7,  // disturbed scenario evaluator: V2V loss, word x
+    STREAM_TRAIN_OBS = 8,   // training under disturbances: sensor noise, (counter, index) = (observation counter, vehicle)
+    STREAM_TRAIN_LINK = 9,  // training under disturbances: V2V loss, word x
 };
 
 }  // namespace avd

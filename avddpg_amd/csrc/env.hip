@@ -5,6 +5,10 @@
 // the per-platoon any-terminal / mean-reward reductions stay inside LDS.  All arithmetic is
 // written without FMA contraction in the reference's operation order so the float32 result is
 // bit-identical to the float32 oracle (oracle/platoon.py:batched_step).
+#include <float.h>
+
+#include <type_traits>
+
 #include "common.h"
 
 namespace avd {
@@ -291,15 +295,70 @@ struct StepArgs {
     int n_groups;
 };
 
+// ---- training under disturbances (avd_step_fused_dist_f32, avd_observe_f32) ---------------------------------------------------
+// The disturbed step's trailing argument, in the style of HpRef: without it the kernel is the nominal one, same parameter list,
+// same code. Platoon p trains under level (its solo-run index) % n_levels.
+struct DistRef {
+    int n_levels;
+    const avd_train_level* levels;  // [n_levels]
+    const float* plant;             // [n_levels][L][24]: A (16), B (4), C (4) per vehicle
+    const float4* obs_in;           // what the actors saw of x_in (the replay row's s)
+    float4* obs_out;                // the observation of x_out
+    float* link_hist;               // [P*L][16] V2V ring, or NULL with link_recv: no level uses the link
+    float* link_recv;               // [P*L] last received value
+    uint64_t obs_counter;           // Philox call counter of obs_out
+};
+template <class... H>
+constexpr bool has_dist = (std::is_same<H, DistRef>::value || ...);
+__device__ __forceinline__ const DistRef& dist_of(const DistRef& d) { return d; }
+constexpr int LINK_RING = 16;  // slots of a vehicle's V2V history (delays 0 .. 15), indexed by counter & 15
+constexpr int LEVEL_WORDS = sizeof(avd_train_level) / 4;
+static_assert(sizeof(avd_train_level) == 32 && (LINK_RING & (LINK_RING - 1)) == 0, "level rows of 8 words; the ring index is a mask");
+
+__device__ __forceinline__ bool level_uses_link(const avd_train_level& lv) { return lv.delay != 0 || lv.drop_q != 0u; }
+inline bool level_uses_link_host(const avd_train_level& lv) { return lv.delay != 0 || lv.drop_q != 0u; }
+
+// Sensor noise on the first three components of x (the evaluator's model, csrc/evalx.hip): one Philox call per vehicle, unfused
+// multiply and add, a zero sigma keeps the bits of x.
+__device__ __forceinline__ void observe_noise(float4& ob, const float4& x, const avd_train_level& lv, uint64_t key, uint64_t counter,
+                                              uint32_t rv) {
+#pragma clang fp contract(off)
+    const float sg_ep = lv.sigma[0], sg_ev = lv.sigma[1], sg_a = lv.sigma[2];
+    if (sg_ep != 0.f || sg_ev != 0.f || sg_a != 0.f) {
+        const u32x4 r = philox_at(key, counter, rv, STREAM_TRAIN_OBS);
+        float n_ev;
+        const float n_ep = box_muller(r.x, r.y, &n_ev);
+        const float n_a = box_muller(r.z, r.w, nullptr);
+        if (sg_ep != 0.f) ob.x = x.x + sg_ep * n_ep;
+        if (sg_ev != 0.f) ob.y = x.y + sg_ev * n_ev;
+        if (sg_a != 0.f) ob.z = x.z + sg_a * n_a;
+    }
+}
+
 // HP (avd_step_fused_hp_f32, with G): platoon g's ou_theta / ou_scale from the sweep table, row g % n_groups (its experiment)
+// DIST (avd_step_fused_dist_f32, one DistRef in the pack): the platoon's level picks its plant, obs_out observes x_out, the replay row
+// holds observations. The plant rows of ALL levels and the level table are staged in dynamic LDS once per block ([n_levels][L][24]
+// floats, then [n_levels][8] words: at most 25 088 B) in place of the constants block's L rows.
 template <bool G, bool HP = false, class... H>
 __global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs a, H... hp) {
 #pragma clang fp contract(off)
-    __shared__ float sA[AVD_MAX_L][16], sB[AVD_MAX_L][4], sC[AVD_MAX_L][4];
+    constexpr bool DIST = has_dist<H...>;
+    __shared__ float sA[AVD_MAX_L][16], sB[AVD_MAX_L][4], sC[AVD_MAX_L][4];  // (DIST: unused, the rows live in dynamic LDS)
     const avd_env_consts* cst = a.cst;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, L = a.L;
-    for (int i = tid; i < L * 16; i += ENV_THREADS) sA[i >> 4][i & 15] = cst->A[i >> 4][i & 15];
-    for (int i = tid; i < L * 4; i += ENV_THREADS) sB[i >> 2][i & 3] = cst->B[i >> 2][i & 3], sC[i >> 2][i & 3] = cst->C[i >> 2][i & 3];
+    const float* sPlant = nullptr;      // DIST: [n_levels][L][24]
+    const uint32_t* sLevels = nullptr;  // DIST: [n_levels][LEVEL_WORDS]
+    if constexpr (DIST) {
+        extern __shared__ __attribute__((aligned(16))) float dist_lds[];
+        const DistRef& d = dist_of(hp...);
+        const int np = d.n_levels * L * 24, nl = d.n_levels * LEVEL_WORDS;
+        for (int k = tid; k < np; k += ENV_THREADS) dist_lds[k] = d.plant[k];
+        for (int k = tid; k < nl; k += ENV_THREADS) dist_lds[np + k] = __uint_as_float(((const uint32_t*)d.levels)[k]);
+        sPlant = dist_lds, sLevels = (const uint32_t*)(dist_lds + np);
+    } else {
+        for (int i = tid; i < L * 16; i += ENV_THREADS) sA[i >> 4][i & 15] = cst->A[i >> 4][i & 15];
+        for (int i = tid; i < L * 4; i += ENV_THREADS) sB[i >> 2][i & 3] = cst->B[i >> 2][i & 3], sC[i >> 2][i & 3] = cst->C[i >> 2][i & 3];
+    }
     if (blockIdx.x == 0 && tid == 0 && a.any_done_other) *a.any_done_other = 0;
     const int pw = 64 / L;                      // whole platoons per wave
     const int lp = lane / L, i = lane - lp * L;  // platoon of the wave, vehicle
@@ -308,12 +367,16 @@ __global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs 
     const long v = (long)p * L + i;
     float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
     float pa = 0.f, uu = 0.f, exog_own = 0.f;
+    uint64_t okey = 0;  // DIST: the observation's Philox key, vehicle index and level (idle lanes: level 0, nothing stored)
+    uint32_t orv = 0;
+    int lvl = 0;
     if (active) {
         xv = a.x_in[v];
         pa = a.prev_a[v];
         // OUActionNoise.__call__ (src/noise.py:15-19) and policy (agent/ddpgagent.py:22-27)
         uint64_t key;
         const int pl = seed_key<G>(a.seed, a.seeds, a.n_groups, p, key);  // (the solo run's platoon index)
+        if constexpr (DIST) okey = key, orv = G ? (uint32_t)((long)pl * L + i) : (uint32_t)v, lvl = pl % dist_of(hp...).n_levels;
         const u32x4 rn = philox_at(key, a.ou_counter, G ? (uint32_t)((long)pl * L + i) : (uint32_t)v, STREAM_OU);
         const float nrm = box_muller(rn.x, rn.y, nullptr);
         const float st = a.ou_state[v];
@@ -333,9 +396,9 @@ __global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs 
         }
     }
     __syncthreads();
-    const float* Ai = sA[i];
-    const float* Bi = sB[i];
-    const float* Ci = sC[i];
+    const float* Ai = DIST ? sPlant + (lvl * L + i) * 24 : sA[i];
+    const float* Bi = DIST ? Ai + 16 : sB[i];
+    const float* Ci = DIST ? Ai + 20 : sC[i];
     float ax[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) ax[r] = ((Ai[r * 4 + 0] * xv.x + Ai[r * 4 + 1] * xv.y) + Ai[r * 4 + 2] * xv.z) + Ai[r * 4 + 3] * xv.w;
@@ -365,10 +428,34 @@ __global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs 
         if (a.term) a.term[v] = is_term ? 1 : 0;
         if (a.ep_reward) a.ep_reward[v] = a.ep_reward[v] + negr;  // float32 counters (workers/trainer.py:249, 321)
         if (i == 0) a.done[p] = (uint8_t)(((tmask >> (lp * L)) & ((1ull << L) - 1ull)) != 0ull);
+        float4 row_s = xv, row_n = xn;  // the replay row's states: the true ones, or (DIST) what the agent saw of them
+        if constexpr (DIST) {
+            const DistRef& d = dist_of(hp...);
+            avd_train_level lv;
+            lv.sigma[0] = __uint_as_float(sLevels[lvl * LEVEL_WORDS]), lv.sigma[1] = __uint_as_float(sLevels[lvl * LEVEL_WORDS + 1]);
+            lv.sigma[2] = __uint_as_float(sLevels[lvl * LEVEL_WORDS + 2]);
+            lv.delay = (int32_t)sLevels[lvl * LEVEL_WORDS + 3], lv.drop_q = sLevels[lvl * LEVEL_WORDS + 4];
+            float4 ob = xn;
+            if (d.link_hist && level_uses_link(lv)) {  // this vehicle's ring and held value: its own thread's alone
+                float* hist = d.link_hist + v * LINK_RING;
+                const int c = (int)(uint32_t)d.obs_counter;
+                hist[c & (LINK_RING - 1)] = xn.w;
+                // (the host refuses delays outside the ring; the mask keeps any value inside it)
+                const float delayed = hist[(c - lv.delay) & (LINK_RING - 1)];
+                // loss: an integer compare on one Philox word (drop_q = 0 never drops: no draw needed)
+                const bool dropped = lv.drop_q != 0u && (philox_at(okey, d.obs_counter, orv, STREAM_TRAIN_LINK).x >> 8) < lv.drop_q;
+                if (dropped) ob.w = d.link_recv[v];
+                else d.link_recv[v] = ob.w = delayed;
+            }
+            observe_noise(ob, xn, lv, okey, d.obs_counter, orv);
+            d.obs_out[v] = ob;
+            row_n = ob;
+            if (a.ring) row_s = d.obs_in[v];
+        }
         if (a.ring) {  // ReplayBuffer.add (src/replaybuffer.py:36-47): row [s a r s'] at slot counter % capacity
             const int S = a.S, row = 2 * S + 2;
             float* dst = a.ring + ((long)v * a.cap + a.slot) * row;
-            const float xo[4] = {xv.x, xv.y, xv.z, xv.w}, xw[4] = {xn.x, xn.y, xn.z, xn.w};
+            const float xo[4] = {row_s.x, row_s.y, row_s.z, row_s.w}, xw[4] = {row_n.x, row_n.y, row_n.z, row_n.w};
             if (S == 4) {  // 40-byte rows, 8-byte aligned
                 ((float2*)dst)[0] = make_float2(xo[0], xo[1]);
                 ((float2*)dst)[1] = make_float2(xo[2], xo[3]);
@@ -383,6 +470,38 @@ __global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs 
     }
     // any-terminal flag (trainer.py:268): one plain store per workgroup at most, every writer stores the same value
     if (a.any_done && __syncthreads_or(tmask != 0ull) && tid == 0) *a.any_done = 1;
+}
+
+// (Re)observe fresh states (after a reset): obs = the observation of x with the sensor noise of (key, counter, vehicle) and a FRESH
+// link -- ring filled with x.w, held value x.w, observed x.w (the start value, as the evaluator's ring before its first step). One
+// thread per vehicle. only_where_zero [P] / run_if_nonzero (one flag): nullable gates, see include/avddpg_hip.h.
+template <bool G>
+__global__ __launch_bounds__(ENV_THREADS) void observe_kernel(int P, int L, const float4* __restrict__ x, float4* __restrict__ obs,
+                                                              int n_levels, const avd_train_level* __restrict__ levels,
+                                                              float* __restrict__ link_hist, float* __restrict__ link_recv,
+                                                              uint64_t seed, uint64_t counter,
+                                                              const int32_t* __restrict__ only_where_zero,
+                                                              const int32_t* __restrict__ run_if_nonzero,
+                                                              const uint64_t* __restrict__ seeds, int E) {
+    if (run_if_nonzero && *run_if_nonzero == 0) return;  // uniform across the grid
+    const long v = (long)blockIdx.x * ENV_THREADS + threadIdx.x;
+    if (v >= (long)P * L) return;
+    const int p = (int)(v / L), i = (int)(v - (long)p * L);
+    if (only_where_zero && only_where_zero[p] != 0) return;
+    uint64_t key;
+    const int pl = seed_key<G>(seed, seeds, E, p, key);
+    const avd_train_level lv = levels[pl % n_levels];
+    const float4 xv = x[v];
+    float4 ob = xv;
+    observe_noise(ob, xv, lv, key, counter, G ? (uint32_t)((long)pl * L + i) : (uint32_t)v);
+    obs[v] = ob;
+    if (link_hist) {
+        const float4 w4 = make_float4(xv.w, xv.w, xv.w, xv.w);
+        float4* hist = (float4*)(link_hist + v * LINK_RING);
+#pragma unroll
+        for (int k = 0; k < LINK_RING / 4; ++k) hist[k] = w4;
+        link_recv[v] = xv.w;
+    }
 }
 
 __global__ void ou_step_kernel(int n, float* __restrict__ st, const float* __restrict__ normals, float theta,
@@ -510,7 +629,7 @@ static int step_fused_launch(const char* who, const avd_env_consts* d_consts, in
                              float ou_theta, float ou_mean, float ou_dt, float ou_std_dev, float action_low, float action_high,
                              float exog_scale, int exog_uniform, uint64_t seed, const uint64_t* d_seeds, int n_groups,
                              uint64_t ou_counter, uint64_t exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward,
-                             void* stream, const avd_hparams* d_hp = nullptr) {
+                             void* stream, const avd_hparams* d_hp = nullptr, const DistRef* dist = nullptr) {
     AVD_REQUIRE(P > 0 && L > 0 && L <= AVD_MAX_L && (S == 3 || S == 4), "%s: P=%d L=%d S=%d", who, P, L, S);
     AVD_REQUIRE(d_consts && x_in && x_out && prev_a && reward && done && actor_out && ou_state && action && leader_exog,
                 "%s: null pointer", who);
@@ -527,9 +646,42 @@ static int step_fused_launch(const char* who, const avd_env_consts* d_consts, in
     if constexpr (HP)
         hipLaunchKernelGGL((step_fused_kernel<G, true, HpRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS), 0,
                            (hipStream_t)stream, a, HpRef{d_hp, n_groups, 1});
+    else if (dist)
+        hipLaunchKernelGGL((step_fused_kernel<G, false, DistRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS),
+                           sizeof(float) * (size_t)dist->n_levels * (L * 24 + LEVEL_WORDS), (hipStream_t)stream, a, *dist);
     else
         hipLaunchKernelGGL(step_fused_kernel<G>, dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS), 0, (hipStream_t)stream, a);
     return check_launch(who);
+}
+
+// The disturbed step's own arguments, checked (the level table's HOST copy row by row) and packed
+static int dist_args(const char* who, int n_levels, const avd_train_level* h_levels, const avd_train_level* d_levels, const float* d_plant,
+                     const float* obs_in, float* obs_out, float* link_hist, float* link_recv, uint64_t obs_counter, DistRef& d) {
+    AVD_REQUIRE(n_levels >= 1 && n_levels <= AVD_TRAIN_MAX_LEVELS, "%s: n_levels=%d (must be 1..%d)", who, n_levels, AVD_TRAIN_MAX_LEVELS);
+    AVD_REQUIRE(h_levels && d_levels && d_plant && obs_in && obs_out, "%s: null level table, plant table or observation buffer", who);
+    AVD_REQUIRE((link_hist == nullptr) == (link_recv == nullptr), "%s: link_hist and link_recv must both be given or both be null", who);
+    for (int k = 0; k < n_levels; ++k) {
+        const avd_train_level& lv = h_levels[k];
+        for (int c = 0; c < 3; ++c)
+            AVD_REQUIRE(lv.sigma[c] >= 0.f && lv.sigma[c] <= FLT_MAX, "%s: level %d sigma[%d]=%g (must be finite and >= 0)", who, k, c,
+                        (double)lv.sigma[c]);
+        AVD_REQUIRE(lv.delay >= 0 && lv.delay <= LINK_RING - 1, "%s: level %d delay=%d (must be 0..%d)", who, k, lv.delay, LINK_RING - 1);
+        AVD_REQUIRE(lv.drop_q <= (1u << 24), "%s: level %d drop_q=%u (must be <= 2^24 = %u)", who, k, lv.drop_q, 1u << 24);
+        AVD_REQUIRE(link_hist || !level_uses_link_host(lv), "%s: level %d uses the V2V link (delay=%d drop_q=%u) but link_hist is null", who, k,
+                    lv.delay, lv.drop_q);
+    }
+    d.n_levels = n_levels, d.levels = d_levels, d.plant = d_plant, d.obs_in = (const float4*)obs_in, d.obs_out = (float4*)obs_out;
+    d.link_hist = link_hist, d.link_recv = link_recv, d.obs_counter = obs_counter;
+    return AVD_OK;
+}
+
+static int observe_check(const char* who, int P, int L, const float* x, float* obs, int n_levels, const avd_train_level* d_levels,
+                         float* link_hist, float* link_recv) {
+    AVD_REQUIRE(P > 0 && L > 0 && L <= AVD_MAX_L, "%s: P=%d L=%d (L must be 1..%d)", who, P, L, AVD_MAX_L);
+    AVD_REQUIRE(n_levels >= 1 && n_levels <= AVD_TRAIN_MAX_LEVELS, "%s: n_levels=%d (must be 1..%d)", who, n_levels, AVD_TRAIN_MAX_LEVELS);
+    AVD_REQUIRE(x && obs && d_levels, "%s: null pointer", who);
+    AVD_REQUIRE((link_hist == nullptr) == (link_recv == nullptr), "%s: link_hist and link_recv must both be given or both be null", who);
+    return AVD_OK;
 }
 
 extern "C" int avd_step_fused_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
@@ -607,4 +759,66 @@ extern "C" int avd_episode_end_seeds_f32(const avd_env_consts* d_consts, int P, 
                        M, (float4*)x, prev_a, cum_accel, done, ep_len, ep_reward, limit, ret_sum, len_sum, ep_cnt, any_reset, mode, 0,
                        counter, d_seeds, n_groups);
     return check_launch("avd_episode_end_seeds_f32");
+}
+
+// ---- training under disturbances --------------------------------------------------------------------------------------------
+extern "C" int avd_step_fused_dist_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
+                                       float* prev_a, float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done,
+                                       int32_t* any_done_other, const float* actor_out, float* ou_state, float* action,
+                                       float* leader_exog, float ou_theta, float ou_mean, float ou_dt, float ou_std_dev, float action_low,
+                                       float action_high, float exog_scale, int exog_uniform, uint64_t seed, uint64_t ou_counter,
+                                       uint64_t exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward,
+                                       int n_levels, const avd_train_level* h_levels, const avd_train_level* d_levels,
+                                       const float* d_plant, const float* obs_in, float* obs_out, float* link_hist, float* link_recv,
+                                       uint64_t obs_counter, void* stream) {
+    const char* who = "avd_step_fused_dist_f32";
+    DistRef d;
+    if (const int rc = dist_args(who, n_levels, h_levels, d_levels, d_plant, obs_in, obs_out, link_hist, link_recv, obs_counter, d)) return rc;
+    return step_fused_launch<false>(who, d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done, any_done, any_done_other,
+                                    actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt, ou_std_dev, action_low,
+                                    action_high, exog_scale, exog_uniform, seed, nullptr, 1, ou_counter, exog_counter, ring, cap,
+                                    replay_counter, ep_reward, stream, nullptr, &d);
+}
+
+extern "C" int avd_step_fused_dist_seeds_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
+                                             float* prev_a, float* cum_accel, float* reward, uint8_t* term, uint8_t* done,
+                                             int32_t* any_done, int32_t* any_done_other, const float* actor_out, float* ou_state,
+                                             float* action, float* leader_exog, float ou_theta, float ou_mean, float ou_dt,
+                                             float ou_std_dev, float action_low, float action_high, float exog_scale, int exog_uniform,
+                                             const uint64_t* d_seeds, int n_groups, uint64_t ou_counter, uint64_t exog_counter,
+                                             float* ring, int cap, int64_t replay_counter, float* ep_reward, int n_levels,
+                                             const avd_train_level* h_levels, const avd_train_level* d_levels, const float* d_plant,
+                                             const float* obs_in, float* obs_out, float* link_hist, float* link_recv,
+                                             uint64_t obs_counter, void* stream) {
+    const char* who = "avd_step_fused_dist_seeds_f32";
+    AVD_REQUIRE_GROUPS(who, P);
+    DistRef d;
+    if (const int rc = dist_args(who, n_levels, h_levels, d_levels, d_plant, obs_in, obs_out, link_hist, link_recv, obs_counter, d)) return rc;
+    return step_fused_launch<true>(who, d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done, any_done, any_done_other,
+                                   actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt, ou_std_dev, action_low, action_high,
+                                   exog_scale, exog_uniform, 0, d_seeds, n_groups, ou_counter, exog_counter, ring, cap, replay_counter,
+                                   ep_reward, stream, nullptr, &d);
+}
+
+extern "C" int avd_observe_f32(int P, int L, const float* x, float* obs, int n_levels, const avd_train_level* d_levels, float* link_hist,
+                               float* link_recv, uint64_t seed, uint64_t obs_counter, const int32_t* only_where_zero,
+                               const int32_t* run_if_nonzero, void* stream) {
+    if (const int rc = observe_check("avd_observe_f32", P, L, x, obs, n_levels, d_levels, link_hist, link_recv)) return rc;
+    const long n = (long)P * L;
+    hipLaunchKernelGGL(observe_kernel<false>, dim3((unsigned)((n + ENV_THREADS - 1) / ENV_THREADS)), dim3(ENV_THREADS), 0,
+                       (hipStream_t)stream, P, L, (const float4*)x, (float4*)obs, n_levels, d_levels, link_hist, link_recv, seed,
+                       obs_counter, only_where_zero, run_if_nonzero, nullptr, 1);
+    return check_launch("avd_observe_f32");
+}
+
+extern "C" int avd_observe_seeds_f32(int P, int L, const float* x, float* obs, int n_levels, const avd_train_level* d_levels,
+                                     float* link_hist, float* link_recv, const uint64_t* d_seeds, int n_groups, uint64_t obs_counter,
+                                     const int32_t* only_where_zero, const int32_t* run_if_nonzero, void* stream) {
+    if (const int rc = observe_check("avd_observe_seeds_f32", P, L, x, obs, n_levels, d_levels, link_hist, link_recv)) return rc;
+    AVD_REQUIRE_GROUPS("avd_observe_seeds_f32", P);
+    const long n = (long)P * L;
+    hipLaunchKernelGGL(observe_kernel<true>, dim3((unsigned)((n + ENV_THREADS - 1) / ENV_THREADS)), dim3(ENV_THREADS), 0,
+                       (hipStream_t)stream, P, L, (const float4*)x, (float4*)obs, n_levels, d_levels, link_hist, link_recv, 0, obs_counter,
+                       only_where_zero, run_if_nonzero, d_seeds, n_groups);
+    return check_launch("avd_observe_seeds_f32");
 }

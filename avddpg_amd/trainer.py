@@ -111,6 +111,28 @@ def check_sweep(conf, seeds, hparams, shared_engine=None, pipeline_chunks=1):
     return rows
 
 
+def check_train_disturb(conf, train_disturb, rng, group, fused_step=None, hparams=None):
+    """Why a run cannot TRAIN under these disturbance levels (VecTrainer(train_disturb=...)), raised as a ValueError -- or the checked
+    list of scenarios.Disturbance. Called before anything is allocated or launched. The observation model lives in the fused step
+    (avd_step_fused_dist_f32): device RNG, decentralized agents, one GPU, no sweep."""
+    from . import _hip, scenarios
+
+    if conf.framework == conf.cntrl:
+        raise ValueError("training under disturbances needs the decentralized framework: the centralized one has no fused step")
+    if rng != "device":
+        raise ValueError("training under disturbances needs rng='device': the observation model lives in the fused step's launch")
+    if fused_step is not None and not fused_step:
+        raise ValueError("training under disturbances needs the fused step (fused_step=False has no observation model)")
+    if hparams is not None:
+        raise ValueError("training under disturbances does not combine with a hyperparameter sweep or PBT (hparams=...)")
+    if group is not None:
+        raise ValueError("training under disturbances runs on one GPU: no process group")
+    levels = list(train_disturb)
+    if not 1 <= len(levels) <= _hip.AVD_TRAIN_MAX_LEVELS:
+        raise ValueError(f"train_disturb lists {len(levels)} levels: 1 to {_hip.AVD_TRAIN_MAX_LEVELS} (platoon p trains under level p % n_levels)")
+    return scenarios.check_disturbances(levels, conf)
+
+
 # The set learners' largest weight-set count (the shape checks of csrc/fset.hip and csrc/fsplit.hip); the others take any count.
 SET_ENGINE_MAX_SETS = {"fused": 64, "fused3": 64}
 
@@ -118,7 +140,7 @@ SET_ENGINE_MAX_SETS = {"fused": 64, "fused3": 64}
 class VecTrainer:
     def __init__(self, conf, device=None, rng="device", group=None, shared_sets=None, seed=None, auto_reset=False,
                  pipeline_chunks=1, fused_update=False, shared_engine=None, init_seed=None, fused_step=None,
-                 replay_ring=None, overlap_allreduce=None, seeds=None, hparams=None):
+                 replay_ring=None, overlap_allreduce=None, seeds=None, hparams=None, train_disturb=None):
         """group: torch.distributed process group whose ranks each hold ``conf.num_platoons`` platoons
         (interfrl gradients are all-reduced over it). auto_reset: end episodes on the device (no host
         sync per step); needs rng='device'. True: the reference's rule -- any terminal platoon (or the step limit) ends
@@ -140,8 +162,17 @@ class VecTrainer:
         seed=seeds[e], init_seed=seeds[e]) computes alone, bit for bit, wherever a seed batch is; a seed may repeat when its rows
         differ (fused3: experiment e equals a seed batch of the same seeds whose conf holds row e's values -- its reduction tree depends on
         the set count). check_sweep says what else a sweep needs (the per_agent or fused3 engine, the reference widths, no
-        pipeline_chunks)."""
+        pipeline_chunks).
+        train_disturb: a list of 1..16 scenarios.Disturbance levels to TRAIN under (domain randomisation; the evaluator's observation
+        model, see evaluate_robustness): platoon p runs under level p % n_levels for the whole run (a seed batch: the level of its solo
+        run's platoon index, so experiment k still equals its solo run) -- a Disturbance with a name alone is a clean share. The true state
+        advances with the level's plant and gives reward, terminal flags and episodes; the actors act from, and the replay holds, what
+        the agents OBSERVED (env.obs: sensor noise, V2V delay and loss). check_train_disturb says what it needs (device RNG, the fused
+        step, decentralized, one GPU, no sweep). None: nothing changes -- no buffer is made, the same entry points run."""
         conf.refresh()
+        self.levels = None
+        if train_disturb is not None:
+            self.levels = check_train_disturb(conf, train_disturb, rng, group, fused_step, hparams)
         self.conf, self.rng, self.group = conf, rng, group
         self.device = torch.device(device if device is not None else "cuda")
         self.seeds = self.hp_rows = None
@@ -160,7 +191,7 @@ class VecTrainer:
         self.P_exp = conf.num_platoons  # platoons per experiment
         seed = (conf.random_seed if seed is None else seed) if self.seeds is None else None
         self.env = vec.VecPlatoon(self.P, self.L, conf, self.device, rand_states=conf.rand_states, rng=rng, seed=seed or 0,
-                                  seeds=self.seeds, distinct_seeds=distinct)
+                                  seeds=self.seeds, distinct_seeds=distinct, train_disturb=self.levels)
         # models per platoon: L decentralized, 1 centralized (environment.py:35-42). The reference trainer iterates
         # conf.pl_size models (trainer.py:45) and therefore only completes a centralized step when pl_size == 1; for
         # pl_size > 1 this follows the loop shape of its evaluator (workers/evaluator.py:48-91: env.num_models).
@@ -326,11 +357,12 @@ class VecTrainer:
     def _act(self):
         """advance_environment (trainer.py:282-302): actor -> OU noise -> clip, leader exog, env step."""
         conf, P, M = self.conf, self.P, self.M
-        states = self.env.x.view(P * M, self.x_stride)
+        seen = self.env.agent_states()  # env.x, or what the agents observe of it (train_disturb)
+        states = seen.view(P * M, self.x_stride)
         if self.shared and self.shared_engine == "batched" and self.agents.lay.H2 > 256:
             # wide shared sets: every agent re-reading its set's megabytes of weights is the wrong shape; one GEMM
             # chain per set instead (bf16 operands, like this engine's learner)
-            sm = self.env.x.view(self.Pf, self.Mf, 4)[..., :self.S].transpose(0, 1).contiguous()  # set-major [M, P, S]
+            sm = seen.view(self.Pf, self.Mf, 4)[..., :self.S].transpose(0, 1).contiguous()  # set-major [M, P, S]
             o = self.agents.actor_shared(sm, P * M)
             self.actor_out.copy_(o.transpose(0, 1).reshape(P * M, 1))
         elif self._act_ready:
@@ -380,7 +412,20 @@ class VecTrainer:
         env.any_done = env._any_flags[k:k + 1]  # this step's flag (cleared by the previous step's launch, zero at start)
         other = env._any_flags[1 - k:2 - k]
         env.x, env.x_prev = env.x_prev, env.x
-        if self.d_hp is not None:  # a sweep: each platoon's OU theta and scale from its experiment's row (avd_step_fused_hp_f32)
+        if self.levels is not None:
+            # training under disturbances (avd_step_fused_dist_f32): the level's plant, the observation of the new state with the next
+            # observation counter, the replay row from the observation buffers -- which swap where x and x_prev do
+            env.obs, env.obs_prev = env.obs_prev, env.obs
+            env.obs_counter += 1
+            fn, key = ("avd_step_fused_dist_f32", (self.seed,)) if self.seeds is None else ("avd_step_fused_dist_seeds_f32", (ptr(env.d_seeds), self.E))
+            call(fn, ptr(env.d_consts), self.P, self.L, self.S, ptr(env.x_prev), ptr(env.x), ptr(env.prev_a),
+                 ptr(env.cum_accel), ptr(env.reward), ptr(env.term), ptr(env.done), ptr(env.any_done), ptr(other),
+                 ptr(self.actor_out), ptr(ou.state), ptr(self.actions), ptr(self.leader_exog), conf.theta, ou.mean, conf.ou_dt,
+                 conf.std_dev, conf.action_low, conf.action_high, conf.reset_max_u, 1 if conf.rand_gen == conf.uniform else 0,
+                 *key, ou.calls, self.exog_calls, ptr(rp.ring), rp.cap, rp.buffer_counter, ptr(self.ep_reward),
+                 len(self.levels), env.h_levels, ptr(env.d_levels), ptr(env.d_plant), ptr(env.obs_prev), ptr(env.obs),
+                 ptr(env.link_hist), ptr(env.link_recv), env.obs_counter, stream_handle())
+        elif self.d_hp is not None:  # a sweep: each platoon's OU theta and scale from its experiment's row (avd_step_fused_hp_f32)
             call("avd_step_fused_hp_f32", ptr(env.d_consts), self.P, self.L, self.S, ptr(env.x_prev), ptr(env.x), ptr(env.prev_a),
                  ptr(env.cum_accel), ptr(env.reward), ptr(env.term), ptr(env.done), ptr(env.any_done), ptr(other), ptr(self.actor_out),
                  ptr(ou.state), ptr(self.actions), ptr(self.leader_exog), ou.mean, conf.ou_dt, conf.action_low, conf.action_high,
@@ -425,7 +470,7 @@ class VecTrainer:
             xs = self.x_stride
             if self._added:  # the fused step launch has already written the row and the reward counters
                 self._added = False
-            else:
+            else:  # (never with train_disturb: it needs the fused step)
                 self.replay.add(env.x_prev.view(P * M, xs), self.actions.view(P * M, self.A), reward.view(-1),
                                 env.x.view(P * M, xs), xs)
                 self.ep_reward += reward
@@ -443,7 +488,7 @@ class VecTrainer:
             # nofrl: learn + Adam x2 + Polyak of every agent in one kernel (no gradient slab round trip)
             nxt = self.A == 1 and self.auto_reset  # the episode loop's host-side resets go through reset_episode()
             self._timed("learn+update", self.agents.learn_update, s, a, r, s2, self.grads, self.losses,
-                        next_states=env.x.view(P * M, self.x_stride) if nxt else None, x_stride=self.x_stride,
+                        next_states=env.agent_states().view(P * M, self.x_stride) if nxt else None, x_stride=self.x_stride,
                         next_actions=self.actor_out.view(-1) if nxt else None)
             self._act_ready = nxt
             return

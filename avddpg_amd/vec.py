@@ -104,6 +104,18 @@ def batch_platoon(e, p, E):
     return p * E + e
 
 
+def train_level_table(levels, device):
+    """Checked scenarios.Disturbance levels -> (the avd_train_level table as a ctypes array: the HOST copy avd_step_fused_dist_f32
+    validates on every call, the same bytes as a uint8 device tensor the kernels read)."""
+    from .scenarios import drop_threshold
+
+    arr = (_hip.TrainLevel * len(levels))()
+    for row, d in zip(arr, levels):
+        row.sigma[0], row.sigma[1], row.sigma[2] = d.sigma
+        row.delay, row.drop_q = int(d.v2v_delay), drop_threshold(d.v2v_drop)
+    return arr, torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(device)
+
+
 def _no_scalar_draw(what):
     raise _hip.AvdError(f"{what}: an experiment batch (seeds=...) draws only through the *_seeds_* kernels; this path would "
                         "draw with one scalar seed for every experiment")
@@ -113,9 +125,13 @@ class VecPlatoon:
     """P platoons of L vehicles. Batched ``Platoon`` (reference src/environment.py:8-301)."""
 
     def __init__(self, num_platoons, length, config, device=None, rand_states=True, evaluator_states_enabled=False,
-                 rng="host", seed=1, track_aux=False, seeds=None, distinct_seeds=True):
+                 rng="host", seed=1, track_aux=False, seeds=None, distinct_seeds=True, train_disturb=None):
         """seeds: an experiment batch -- len(seeds) experiments of num_platoons / len(seeds) platoons each, interleaved (experiment e's
-        platoon p is platoon p * E + e), each drawing exactly what a solo VecPlatoon with seed=seeds[e] draws (device RNG only)."""
+        platoon p is platoon p * E + e), each drawing exactly what a solo VecPlatoon with seed=seeds[e] draws (device RNG only).
+        train_disturb: scenarios.Disturbance levels to TRAIN under (already checked: trainer.check_train_disturb; device RNG): platoon p
+        runs under level p % n_levels (a batch: the level of its solo run's platoon index) for good. ``self.obs`` / ``self.obs_prev``
+        then hold what the agents observe of ``self.x`` / ``self.x_prev`` (sensor noise, V2V delay and loss; the level's plant drives
+        x) and are swapped where x and x_prev are; every reset re-observes the fresh states (observe). None: none of this exists."""
         self.P, self.L, self.config = int(num_platoons), int(length), config
         self.length = self.L
         self.device = _dev(device)
@@ -164,6 +180,21 @@ class VecPlatoon:
         self.reset_count = 0
         self.step_count = 0
         self.ep_len = self.ep_stats = None  # per-platoon episodes (episode_end), made on first use
+        self.levels = None
+        if train_disturb is not None:
+            from . import scenarios
+
+            self.levels = list(train_disturb)
+            self.h_levels, self.d_levels = train_level_table(self.levels, self.device)
+            self.d_plant = torch.from_numpy(np.stack([scenarios.plant_table(config, L, d.dyn_coeff) for d in self.levels])).to(self.device)
+            self.obs = torch.zeros(P, L, 4, **f32)
+            self.obs_prev = torch.zeros(P, L, 4, **f32)
+            self.link_hist = self.link_recv = None
+            if any(d.uses_v2v for d in self.levels):  # the V2V ring and the held value, only where a level uses the link
+                self.link_hist = torch.zeros(P, L, 16, **f32)
+                self.link_recv = torch.zeros(P, L, **f32)
+            self.obs_counter = 0  # Philox call counter of the observation in self.obs (the host owns it: step t makes t + 1)
+            self.observe()
         if rng == "host":
             # constructor draws of P reference Platoon objects: 2 + 3L each (environment.py:24,32,385)
             self._host_ctor_draws()
@@ -223,6 +254,19 @@ class VecPlatoon:
         self.front_accel = fa.copy()
         return draws, fa
 
+    def observe(self, only_where_zero=None, run_if_nonzero=None):
+        """(Re)observe fresh states (avd_observe_f32): self.obs from self.x with the sensor noise of the current observation counter and a
+        fresh V2V link. only_where_zero: int32 [P], only platoons with a 0 entry (episode_end's ep_len); run_if_nonzero: int32 [1] device
+        flag, nothing happens when it reads 0. Both None: every platoon."""
+        key = (self.seed,) if self.seeds is None else (ptr(self.d_seeds), self.n_groups)
+        call("avd_observe_f32" if self.seeds is None else "avd_observe_seeds_f32", self.P, self.L, ptr(self.x), ptr(self.obs),
+             len(self.levels), ptr(self.d_levels), ptr(self.link_hist), ptr(self.link_recv), *key, self.obs_counter, ptr(only_where_zero),
+             ptr(run_if_nonzero), stream_handle())
+
+    def agent_states(self):
+        """What the agents see of x: the observation buffer when training under disturbances, else the state itself."""
+        return self.x if self.levels is None else self.obs
+
     # -- API ------------------------------------------------------------------------------------
     def observations(self, x=None):
         """[P, L, obs_width] view (decentralized) -- Model A hides x[3] (:518)."""
@@ -239,6 +283,8 @@ class VecPlatoon:
             draws, fa = self._host_reset_draws()
         self._upload_reset(draws, fa, cond)
         self.reset_count += 1
+        if self.levels is not None:
+            self.observe(run_if_nonzero=cond)
         return self.observations()
 
     def episode_end(self, ep_reward, M, limit, any_reset=None):
@@ -259,6 +305,8 @@ class VecPlatoon:
                  ptr(self.done), ptr(self.ep_len), ptr(ep_reward), int(limit), ptr(st["ret_sum"]), ptr(st["len_sum"]),
                  ptr(st["count"]), ptr(any_reset), self._mode(), self.seed, self.reset_count, stream_handle())
         self.reset_count += 1
+        if self.levels is not None:  # (ep_len[p] == 0 exactly on the platoons just reset)
+            self.observe(only_where_zero=self.ep_len)
 
     def ensure_episode_state(self):
         """The per-platoon episode counters of episode_end (made on first use)."""
@@ -292,6 +340,8 @@ class VecPlatoon:
     def step(self, actions, leader_exog):
         """actions [P, L] float32 (device), leader_exog [P]. Returns (obs, reward, done) device tensors;
         ``self.x_prev`` then holds the pre-step state, ``self.any_done`` the any-terminal flag."""
+        if self.levels is not None:
+            raise _hip.AvdError("VecPlatoon.step: training under disturbances runs the fused step only (avd_step_fused_dist_f32)")
         self.x, self.x_prev = self.x_prev, self.x
         call("avd_env_step_f32", ptr(self.d_consts), self.P, self.L, ptr(self.x_prev), ptr(self.x), ptr(self.prev_a),
              ptr(self.cum_accel), ptr(actions), ptr(leader_exog), ptr(self.reward), ptr(self.term), ptr(self.done),

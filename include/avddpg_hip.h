@@ -593,6 +593,63 @@ int avd_eval_cases_dist_block(int K, int L);
 /* host only, no HIP call: sigma [K][3], delay [K], drop_q [K] in HOST memory */
 int avd_eval_cases_dist_check(int K, const float* sigma, const int32_t* delay, const uint32_t* drop_q);
 
+/* ---- training under disturbances: the fused step with an observation model (domain randomisation) --------------------------------
+ * The evaluator's observation model (above) at training time. A run has n_levels (1 .. AVD_TRAIN_MAX_LEVELS) disturbance levels;
+ * platoon p trains under level p % n_levels (an experiment batch: the level of the solo run's platoon index, (g / n_groups) %
+ * n_levels), fixed for the run. The TRUE state x advances as in avd_step_fused_f32, with the level's plant d_plant[level][L][24] (A
+ * 16 row-major, B 4, C 4 per vehicle) in place of the constants block's matrices; reward, terminal flags, done, any_done, ep_reward,
+ * prev_a and cum_accel come from the true state. The actors and the replay see the OBSERVATION o (a float4 per vehicle, laid out
+ * like x) of a true state x, made with observation counter c and vehicle index v (of the solo run):
+ *   sensor noise: r = philox(seed, c, v, stream 8); (n_ep, n_ev) = box_muller(r.x, r.y), n_a = box_muller(r.z, r.w) (cos);
+ *     o[k] = x[k] + sigma[k] * n_k for k < 3, multiply and add unfused; a zero sigma keeps x[k]'s bits.
+ *   V2V link (k = 3), a 16-slot ring link_hist[v] and a held value link_recv[v] per vehicle: hist[c & 15] = x.w; delayed =
+ *     hist[(c - delay) & 15]; the sample is dropped iff drop_q != 0 and (philox(seed, c, v, stream 9).x >> 8) < drop_q; if it is not,
+ *     recv = delayed; o.w = recv. Only levels with delay != 0 or drop_q != 0 touch the link state; link_hist and link_recv may both be
+ *     NULL when no level does (o.w = x.w then).
+ * avd_step_fused_dist_f32 observes the state it produces: obs_out = o(x_out) with obs_counter (the host passes step t's as t + 1).
+ * The replay row is [obs_in[:S], action, -reward, obs_out[:S]]: what the agent saw. actor_out is expected to come from obs_in.
+ * h_levels is the level table in HOST memory, checked on every call (sigma finite and >= 0, delay 0 .. 15, drop_q <= 2^24);
+ * d_levels is the same table in device memory, which the kernel reads. With every level null and the configuration's plant, every
+ * output avd_step_fused_f32 has is bit-identical to it and obs_out has x_out's bits. */
+#define AVD_TRAIN_MAX_LEVELS 16
+typedef struct avd_train_level {
+    float sigma[3];       /* sensor-noise standard deviations of ep, ev, a */
+    int32_t delay;        /* V2V delay in steps, 0 .. 15 */
+    uint32_t drop_q;      /* V2V loss threshold, round(p * 2^24) */
+    uint32_t reserved[3]; /* 32 bytes per level */
+} avd_train_level;
+int avd_step_fused_dist_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out, float* prev_a,
+                            float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done, int32_t* any_done_other,
+                            const float* actor_out, float* ou_state, float* action, float* leader_exog, float ou_theta, float ou_mean,
+                            float ou_dt, float ou_std_dev, float action_low, float action_high, float exog_scale, int exog_uniform,
+                            uint64_t seed, uint64_t ou_counter, uint64_t exog_counter, float* ring, int cap, int64_t replay_counter,
+                            float* ep_reward, int n_levels, const avd_train_level* h_levels, const avd_train_level* d_levels,
+                            const float* d_plant, const float* obs_in, float* obs_out, float* link_hist, float* link_recv,
+                            uint64_t obs_counter, void* stream);
+/* avd_step_fused_dist_f32 with a seed table (as avd_step_fused_seeds_f32). */
+int avd_step_fused_dist_seeds_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out, float* prev_a,
+                                  float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done,
+                                  int32_t* any_done_other, const float* actor_out, float* ou_state, float* action, float* leader_exog,
+                                  float ou_theta, float ou_mean, float ou_dt, float ou_std_dev, float action_low, float action_high,
+                                  float exog_scale, int exog_uniform, const uint64_t* d_seeds, int n_groups, uint64_t ou_counter,
+                                  uint64_t exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward, int n_levels,
+                                  const avd_train_level* h_levels, const avd_train_level* d_levels, const float* d_plant,
+                                  const float* obs_in, float* obs_out, float* link_hist, float* link_recv, uint64_t obs_counter,
+                                  void* stream);
+/* (Re)observe FRESH states: obs = o(x) with the sensor noise of (seed, obs_counter, vehicle) and a fresh link -- the vehicle's ring
+ * filled with its x.w, link_recv = x.w, o.w = x.w (a fresh link holds the start value, as in the evaluator). The host passes the
+ * counter of the observation this one replaces. Two gates, both may be NULL (every platoon is observed then):
+ *   only_where_zero [P]: platoon p is observed only where only_where_zero[p] == 0 (avd_episode_end_f32 leaves ep_len[p] == 0 exactly
+ *     on the platoons it reset);
+ *   run_if_nonzero: one device flag; the launch does nothing when it reads 0 (the any-terminal reset's env.any_done).
+ * One thread per vehicle. d_levels in device memory (validated where the step's host copy is); link_hist / link_recv NULL: no link. */
+int avd_observe_f32(int P, int L, const float* x, float* obs, int n_levels, const avd_train_level* d_levels, float* link_hist,
+                    float* link_recv, uint64_t seed, uint64_t obs_counter, const int32_t* only_where_zero,
+                    const int32_t* run_if_nonzero, void* stream);
+int avd_observe_seeds_f32(int P, int L, const float* x, float* obs, int n_levels, const avd_train_level* d_levels, float* link_hist,
+                          float* link_recv, const uint64_t* d_seeds, int n_groups, uint64_t obs_counter,
+                          const int32_t* only_where_zero, const int32_t* run_if_nonzero, void* stream);
+
 /* D[M][Nc] (f32, ldd) = A[M][K] . B[Nc][K]^T with bf16 operands (K contiguous, K % 64 == 0) and f32 accumulation: the
  * GEMM under avd_learn_shared_bf16, exposed for parity tests. A and B must be readable up to the next multiple of 256
  * rows. */
