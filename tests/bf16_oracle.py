@@ -16,7 +16,10 @@ The acceptance rule (tolerances()): for tensor X over the masks of one case and 
 FLOOR = 1e-4 is the f32 accumulation-order floor (tests/test_gpu_mlp.py GRAD_TOL), FACTOR = 4 the margin for "the error a correct
 lower-precision implementation makes" (tests/test_gpu_mlp.py:112) -- a different placement of the roundings, another summation
 order. Nothing measured from a kernel enters it. CAP: a tolerance above 0.5 would pass a wholly wrong tile (error O(1)); the CPU
-suite asserts that no compared tensor of any case reaches it."""
+suite asserts that no compared tensor of any case reaches it.
+
+The second half holds the agent-major cases of tests/test_gpu_fset_tiles.py (csrc/fset.hip): masks of one agent's 64-row tile through
+agent_weight, every checked set with its own tables, and placement="fset" for the case that needed it (docs/fset_tile_parity.md)."""
 import functools
 from collections import namedtuple
 
@@ -53,28 +56,31 @@ def _layer2(p, inv, sh, W2, b2, mm, fold):
     return mm(p * inv + sh, W2) + b2
 
 
-def actor_forward(w, s, high, mm, fold=False):
+def actor_forward(w, s, high, mm, fold=False, mmx=None):
+    """mmx: the product of the first and the output layer (default: mm; placement "fset": exact)."""
     W1, b1, g1, be1, mm1, mv1, W2, b2, g2, be2, mm2, mv2, W3, b3 = w
+    mmx = mm if mmx is None else mmx
     dt = W1.dtype.type
     s = np.asarray(s, dtype=W1.dtype)
-    p1 = np.maximum(mm(s, W1) + b1, 0)
+    p1 = np.maximum(mmx(s, W1) + b1, 0)
     i1, sh1 = omlp._bn_coeffs(g1, be1, mm1, mv1)
     y1 = p1 * i1 + sh1
     p2 = np.maximum(_layer2(p1, i1, sh1, W2, b2, mm, fold), 0)
     i2, sh2 = omlp._bn_coeffs(g2, be2, mm2, mv2)
     y2 = p2 * i2 + sh2
-    t = np.tanh(mm(y2, W3) + b3)
+    t = np.tanh(mmx(y2, W3) + b3)
     return t * dt(high), (s, p1, y1, p2, y2, t)
 
 
-def critic_forward(w, s, a, mm, fold=False):
+def critic_forward(w, s, a, mm, fold=False, mmx=None):
     Ws, bs, Wa, ba, gs, bes, mms, mvs, ga, bea, mma, mva, W2, b2, g3, be3, mm3, mv3, W3, b3 = w
+    mmx = mm if mmx is None else mmx
     s = np.asarray(s, dtype=Ws.dtype)
     a = np.asarray(a, dtype=Ws.dtype)
-    ps = np.maximum(mm(s, Ws) + bs, 0)
+    ps = np.maximum(mmx(s, Ws) + bs, 0)
     is_, shs = omlp._bn_coeffs(gs, bes, mms, mvs)
     ys = ps * is_ + shs
-    pa = np.maximum(mm(a, Wa) + ba, 0)
+    pa = np.maximum(mmx(a, Wa) + ba, 0)
     ia, sha = omlp._bn_coeffs(ga, bea, mma, mva)
     ya = pa * ia + sha
     c = np.concatenate([ys, ya], axis=1)
@@ -82,13 +88,38 @@ def critic_forward(w, s, a, mm, fold=False):
                     if fold else mm(c, W2) + b2, 0)
     i3, sh3 = omlp._bn_coeffs(g3, be3, mm3, mv3)
     y2 = p2 * i3 + sh3
-    return mm(y2, W3) + b3, (s, a, ps, pa, c, p2, y2)
+    return mmx(y2, W3) + b3, (s, a, ps, pa, c, p2, y2)
 
 
-def critic_backward(w, cache, dq, mm, need_params=True):
+def _fset_layers12_backward(x, p1, inv1, sh1, bn1, W2, dz2, fs):
+    """The second and first layer's backward pass as csrc/fset.hip places its roundings (dw_kernel, dx_kernel, finalize_*): dZ2 rounded
+    ONCE and used everywhere (its column sums are db2), dW2 = inv1 (.) bf16(P1)^T dZ2 + sh1 (x) db2 from the relu'd first layer rounded
+    once, dC = dZ2 . bf16(W2)^T; BN sums of the first layer from the unrounded dC and P1; the masked dC rounded once before it meets
+    the (exact, split) inputs: dW1 = inv1 (.) x^T bf16(dC mask). -> (dW1, db1, dg1, dbe1, dW2, db2, unrounded dz1)."""
+    dz2 = fs(dz2)
+    db2 = dz2.sum(axis=0)
+    dW2 = inv1[:, None] * (fs(p1).T @ dz2) + sh1[:, None] * db2[None, :]
+    dc = dz2 @ fs(W2).T
+    dg1, dbe1, dz1 = omlp._bn_backward(dc, p1, *bn1)
+    v = fs(dc * (p1 > 0))
+    return inv1[None, :] * (x.T @ v), inv1 * v.sum(axis=0), dg1, dbe1, dW2, db2, dz1
+
+
+def critic_backward(w, cache, dq, mm, need_params=True, fs=None):
+    """fs: None, or the rounding of placement "fset" (output layer exact, the rest: _fset_layers12_backward)."""
     Ws, bs, Wa, ba, gs, bes, mms, mvs, ga, bea, mma, mva, W2, b2, g3, be3, mm3, mv3, W3, b3 = w
     s, a, ps, pa, c, p2, y2 = cache
     h1 = Ws.shape[1]
+    if fs is not None:
+        dW3, db3 = y2.T @ dq, dq.sum(axis=0)
+        dg3, dbe3, dz2 = omlp._bn_backward(dq @ W3.T, p2, g3, mm3, mv3)
+        (is_, shs), (ia, sha) = omlp._bn_coeffs(gs, bes, mms, mvs), omlp._bn_coeffs(ga, bea, mma, mva)
+        dWa, dba, dga, dbea, dW2a, db2, dza = _fset_layers12_backward(a, pa, ia, sha, (ga, mma, mva), W2[h1:], dz2, fs)
+        da = dza @ Wa.T  # (head_kernel's action-gradient epilogue: the masked dC and inv_a wa meet in f32)
+        if not need_params:
+            return None, da
+        dWs, dbs, dgs, dbes, dW2s, _, _ = _fset_layers12_backward(s, ps, is_, shs, (gs, mms, mvs), W2[:h1], dz2, fs)
+        return [dWs, dbs, dWa, dba, dgs, dbes, dga, dbea, np.concatenate([dW2s, dW2a], axis=0), db2, dg3, dbe3, dW3, db3], da
     dW3 = mm(y2.T, dq)
     db3 = dq.sum(axis=0)
     dy2 = mm(dq, W3.T)
@@ -108,11 +139,17 @@ def critic_backward(w, cache, dq, mm, need_params=True):
     return [dWs, dbs, dWa, dba, dgs, dbes, dga, dbea, dW2, db2, dg3, dbe3, dW3, db3], da
 
 
-def actor_backward(w, cache, dout, high, mm):
+def actor_backward(w, cache, dout, high, mm, fs=None):
     W1, b1, g1, be1, mm1, mv1, W2, b2, g2, be2, mm2, mv2, W3, b3 = w
     dt = W1.dtype.type
     s, p1, y1, p2, y2, t = cache
     dz3 = dout * dt(high) * (dt(1) - t * t)
+    if fs is not None:
+        dW3, db3 = y2.T @ dz3, dz3.sum(axis=0)
+        dg2, dbe2, dz2 = omlp._bn_backward(dz3 @ W3.T, p2, g2, mm2, mv2)
+        i1, sh1 = omlp._bn_coeffs(g1, be1, mm1, mv1)
+        dW1, db1, dg1, dbe1, dW2, db2, _ = _fset_layers12_backward(s, p1, i1, sh1, (g1, mm1, mv1), W2, dz2, fs)
+        return [dW1, db1, dg1, dbe1, dW2, db2, dg2, dbe2, dW3, db3]
     dW3 = mm(y2.T, dz3)
     db3 = dz3.sum(axis=0)
     dy2 = mm(dz3, W3.T)
@@ -150,35 +187,39 @@ def learn(batch, actor, critic, t_actor, t_critic, gamma=0.99, high=2.5, rnd=rou
     on the action gradient the actor's backward pass starts from (None: untouched).
     placement: "generic" -- both operands of every ``@`` of oracle/mlp.py as written; "dual" / "delta" -- two roundings moved to where
     csrc/wide.hip documents them: the BN scale folded into W2 before rounding in every forward pass (_layer2), and the critic's
-    action gradient in the named kernel's form (_action_gradient). Everything else stays generic."""
-    assert placement in ("generic", "dual", "delta")
+    action gradient in the named kernel's form (_action_gradient). Everything else stays generic.
+    "fset" -- csrc/fset.hip's arithmetic: first layers exact (split operands, 2^-16) and the output layer in f32 (no rounding in
+    either), the BN scale folded into W2 before rounding with the folded bias exact (a bf16 pair), the relu'd first layer and dZ2
+    rounded once (_fset_layers12_backward)."""
+    assert placement in ("generic", "dual", "delta", "fset")
     fold = placement != "generic"
     mm = lambda x, w: np.matmul(rnd(x), rnd(w))
+    mmx, fs = (np.matmul, rnd) if placement == "fset" else (None, None)
     s, a, r, s2 = batch
     dtype = actor[0].dtype
     dt = dtype.type
     s, a, s2 = (np.asarray(v, dtype=dtype) for v in (s, a, s2))
     r = np.asarray(r, dtype=dtype).reshape(len(s), -1)
-    ta, _ = actor_forward(t_actor, s2, high, mm, fold)
-    y = r + dt(gamma) * critic_forward(t_critic, s2, ta, mm, fold)[0]
-    q, cc = critic_forward(critic, s, a, mm, fold)
+    ta, _ = actor_forward(t_actor, s2, high, mm, fold, mmx)
+    y = r + dt(gamma) * critic_forward(t_critic, s2, ta, mm, fold, mmx)[0]
+    q, cc = critic_forward(critic, s, a, mm, fold, mmx)
     n = dt(q.size)
     critic_loss = np.mean(np.square(y - q))
     dq = (dt(2) * (q - y) / n).astype(dtype)
     if dq_scale is not None:
         dq = dq * dq_scale
-    critic_grad, _ = critic_backward(critic, cc, dq, mm)
-    a1, ac = actor_forward(actor, s, high, mm, fold)
-    q1, cc1 = critic_forward(critic, s, a1, mm, fold)
+    critic_grad, _ = critic_backward(critic, cc, dq, mm, fs=fs)
+    a1, ac = actor_forward(actor, s, high, mm, fold, mmx)
+    q1, cc1 = critic_forward(critic, s, a1, mm, fold, mmx)
     actor_loss = -np.mean(q1)
     dq1 = np.full_like(q1, dt(-1) / dt(q1.size))
-    if fold:
+    if placement in ("dual", "delta"):
         da = _action_gradient(critic, cc1, dq1, rnd, placement)
     else:
-        _, da = critic_backward(critic, cc1, dq1, mm, need_params=False)
+        _, da = critic_backward(critic, cc1, dq1, mm, need_params=False, fs=fs)
     if da_scale is not None:
         da = da * da_scale
-    actor_grad = actor_backward(actor, ac, da, high, mm)
+    actor_grad = actor_backward(actor, ac, da, high, mm, fs=fs)
     return critic_grad, actor_grad, dict(critic_loss=critic_loss, actor_loss=actor_loss, y=y, q=q, q1=q1, a1=a1)
 
 
@@ -207,8 +248,9 @@ def violations(got, ref, tol, skip=()):
 
 
 # ---- the cases: shapes from the path conditions of avd_learn_shared_bf16 (csrc/wide.hip, "fused_fwd" ... "act_in_dx") -----------
-Case = namedtuple("Case", "name widths S rows seed path drop32 placement")
-N_SETS, CHECK_SET = 2, 1  # two weight sets (the set stride is exercised); the oracles are computed for the second
+N_SETS, CHECK_SET = 2, 1  # the wide cases: two weight sets (the set stride is exercised); the oracles are computed for the second
+# n_sets weight sets, the oracles computed for the sets of `check` (the fset cases below bring their own)
+Case = namedtuple("Case", "name widths S rows seed path drop32 placement n_sets check", defaults=(N_SETS, (CHECK_SET,)))
 CASES = [
     # fused forward, rank-one backward, critic(s, a) and critic(s, mu) in one pass (dual), fw::dx_gen_kernel<true> (H1 / 256 == 4)
     Case("h1024", (1024, 1024, 48), 4, 4096, 12, "fused fwd + rank-one bwd + dual + dx_gen<true>", (), "dual"),
@@ -252,9 +294,9 @@ def case_conf_kw(case):
 
 
 def case_batch(case):
-    """(s, a, r, s2) of N_SETS sets, as tests/test_gpu_wide.py draws them."""
+    """(s, a, r, s2) of the case's n_sets sets, set-major, as tests/test_gpu_wide.py draws them."""
     rs = np.random.RandomState(case.seed + 1000)
-    n, rows, S = N_SETS, case.rows, case.S
+    n, rows, S = case.n_sets, case.rows, case.S
     s = rs.normal(0, 1.5, size=(n, rows, S)).astype(np.float32)
     a = rs.uniform(-2.5, 2.5, size=(n, rows, 1)).astype(np.float32)
     r = -np.abs(rs.normal(0, 0.3, size=(n, rows))).astype(np.float32)
@@ -263,11 +305,16 @@ def case_batch(case):
 
 
 def perturbed_slabs(n_sets, S, seed, **confkw):
+    return _perturbed_slabs(n_sets, S, seed, tuple(sorted(confkw.items())))
+
+
+@functools.lru_cache(maxsize=4)
+def _perturbed_slabs(n_sets, S, seed, confkw):
     """The host half of tests/test_gpu_mlp.py _perturbed_group: (group on the CPU device, theta, stats, theta_t, stats_t) with the
     same draws (the GPU tests assert that the two agree bit for bit)."""
     from avddpg_amd import config, params, vec
 
-    conf = config.Config(**confkw)
+    conf = config.Config(**dict(confkw))
     grp = vec.AgentGroup(n_sets, S, 1, conf, seed=seed, device="cpu")
     lay, dims = grp.lay, grp.dims
     rs = np.random.RandomState(seed + 100)
@@ -292,40 +339,148 @@ def perturbed_slabs(n_sets, S, seed, **confkw):
     return grp, th, st, tht, stt
 
 
-def case_nets(case, k=CHECK_SET):
-    """(actor, critic, target actor, target critic) of set k in float64, Keras weight order."""
+def case_nets(case, k=None):
+    """(actor, critic, target actor, target critic) of set k (default: the case's first checked set) in float64, Keras weight order."""
     from avddpg_amd import params
 
-    grp, th, st, tht, stt = perturbed_slabs(N_SETS, case.S, case.seed, **case_conf_kw(case))
+    k = case.check[0] if k is None else k
+    grp, th, st, tht, stt = perturbed_slabs(case.n_sets, case.S, case.seed, **case_conf_kw(case))
     c = lambda ws: [w.astype(np.float64) for w in ws]
     return (c(params.unpack(grp.lay, th[k], st[k], "actor", dims=grp.dims)), c(params.unpack(grp.lay, th[k], st[k], "critic", dims=grp.dims)),
             c(params.unpack(grp.lay, tht[k], stt[k], "actor", dims=grp.dims)), c(params.unpack(grp.lay, tht[k], stt[k], "critic", dims=grp.dims)))
 
 
-def tile_learn(case, nets, batch, lo, hi, rnd, **kw):
-    """{name: Nt / Ns x learn(rows [lo, hi) of CHECK_SET)}: what learn_shared returns for weight 1 on those rows, 0 elsewhere."""
+def tile_learn(case, nets, batch, lo, hi, rnd, k=None, **kw):
+    """{name: Nt / Ns x learn(rows [lo, hi) of set k)} of a set-major batch (k: default the case's first checked set; nets: that
+    set's): what the set learners return for weight 1 on those rows, 0 elsewhere."""
     s, a, r, s2 = batch
-    k = CHECK_SET
+    k = case.check[0] if k is None else k
     cg, ag, _ = learn((s[k, lo:hi], a[k, lo:hi], r[k, lo:hi, None], s2[k, lo:hi]), *nets, rnd=rnd, **kw)
     f = (hi - lo) / case.rows
     return {name: f * g for name, g in zip(NAMES, cg + ag)}
 
 
-@functools.lru_cache(maxsize=None)
-def case_reference(name):
-    """-> (masks, refs, emus, tol): per mask the float64 reference and the bf16-operand oracle of CHECK_SET, and per tile size the
-    pooled tolerance table {t: {tensor: (scale, e_bf16, tol)}}. Cached: every test of a case shares one computation."""
-    case = CASE[name]
-    nets, batch, ms = case_nets(case), case_batch(case), masks(case)
-    refs = [tile_learn(case, nets, batch, lo, hi, identity) for _, _, lo, hi in ms]
-    emus = [tile_learn(case, nets, batch, lo, hi, round_bf16, placement=case.placement) for _, _, lo, hi in ms]
+def _reference(case, batch, ms, k):
+    """(masks, refs, emus, tol) of set k of a set-major batch: per mask the float64 reference and the bf16-operand oracle, and per tile
+    size the pooled tolerance table {t: {tensor: (scale, e_bf16, tol)}}."""
+    nets = case_nets(case, k)
+    refs = [tile_learn(case, nets, batch, lo, hi, identity, k=k) for _, _, lo, hi in ms]
+    emus = [tile_learn(case, nets, batch, lo, hi, round_bf16, k=k, placement=case.placement) for _, _, lo, hi in ms]
     tol = {}
-    for t in sorted({m[1] for m in ms}):
+    for t in sorted({m[1] for m in ms}, key=lambda t: (isinstance(t, str), t)):
         idx = [i for i, m in enumerate(ms) if m[1] == t]
         tol[t] = tolerances([refs[i] for i in idx], [emus[i] for i in idx])
     return ms, refs, emus, tol
 
 
+@functools.lru_cache(maxsize=None)
+def case_reference(name):
+    """-> (masks, refs, emus, tol) of the case's first checked set (the wide cases have one). Cached: every test of a case shares one
+    computation."""
+    case = CASE[name]
+    return _reference(case, case_batch(case), masks(case), case.check[0])
+
+
 def skipped(case, t):
     """Tensors not compared at tile size t (a tolerance at the cap says nothing): listed in CASES, never a head tensor."""
     return case.drop32 if t == 32 else ()
+
+
+# ---- the agent-major set learner (csrc/fset.hip, csrc/fsplit.hip): one 64-row tile per agent, masks through agent_weight ---------
+# make_plan gives a set J = min(CUs / n_sets, P) workgroups; workgroup j0 walks the agents (platoons) j0, j0 + J, .. of its set, so P is
+# written through J = max(1, CUs // n_sets) and the caller passes the CU count (the GPU test: the device's; the CPU self-checks: 256).
+FsetSpec = namedtuple("FsetSpec", "name S n_sets seed P platoons check placement why")
+FSET_WIDTHS, FSET_B = (256, 128, 48), 64  # the reference widths, the only ones the engine serves
+FSET = [
+    FsetSpec("fset_64sets", 4, 64, 67, lambda J: 7 * J - 1, lambda J, P: range(P), (0, 37, 63), "fset",
+             "every workgroup walks 7 tiles, the last 6: head_kernel's one-ahead prefetch, a wave pair's second tile in the 4-pair and "
+             "the 6-pair modes, odd and even tile counts for dxa_kernel's parities, the widest set stride"),
+    FsetSpec("fset_modelA_ragged", 3, 5, 62, lambda J: 70, lambda J, P: (0, J - 1, J, J + 18, P - 1), (0, 4), "generic",
+             "ragged tile counts (at 256 CUs J = 51: 19 workgroups with 2 tiles, 32 with 1), Model A input width"),
+    FsetSpec("fset_one_set", 4, 1, 69, lambda J: 300, lambda J, P: (0, J - 1, J, P - 1), (0,), "generic",
+             "every CU on one set, 1-2 tiles each"),
+]
+FSET_SPEC = {c.name: c for c in FSET}
+
+
+def fset_plan(name, cus):
+    """(J, P, masked platoons) of an fset case on a device with `cus` compute units."""
+    spec = FSET_SPEC[name]
+    J = max(1, cus // spec.n_sets)
+    P = spec.P(J)
+    platoons = sorted({p for p in spec.platoons(J, P) if 0 <= p < P})
+    return J, P, platoons
+
+
+def fset_case(name, cus):
+    """The Case of an fset spec: rows = P x 64 per set, its own set count and checked sets (serves case_nets, tile_learn)."""
+    spec = FSET_SPEC[name]
+    _, P, _ = fset_plan(name, cus)
+    return Case(name, FSET_WIDTHS, spec.S, P * FSET_B, spec.seed, spec.why, (), spec.placement, spec.n_sets, spec.check)
+
+
+def fset_batch(case):
+    """(s, a, r, s2) AGENT-major [n_agents, 64, ..] (agent v = p * n_sets + m uses set m), drawn as tests/test_gpu_fset.py::_batch does."""
+    rs = np.random.RandomState(case.seed + 1000)
+    n, B, S = case.n_sets * case.rows // FSET_B, FSET_B, case.S
+    s = rs.normal(0, 1.5, size=(n, B, S)).astype(np.float32)
+    a = rs.uniform(-2.5, 2.5, size=(n, B, 1)).astype(np.float32)
+    r = -np.abs(rs.normal(0, 0.3, size=(n, B))).astype(np.float32)
+    s2 = rs.normal(0, 1.5, size=(n, B, S)).astype(np.float32)
+    return s, a, r, s2
+
+
+def set_major(batch, n_sets):
+    """Agent-major [P * n_sets, 64, ..] -> set-major [n_sets, P * 64, ..]: platoon p's agent of set m is rows [64 p, 64 p + 64) of m."""
+    def sm(x):
+        P = x.shape[0] // n_sets
+        return np.ascontiguousarray(x.reshape(P, n_sets, *x.shape[1:]).swapaxes(0, 1)).reshape(n_sets, P * x.shape[1], *x.shape[2:])
+    return tuple(sm(x) for x in batch)
+
+
+def fset_masks(name, cus):
+    """[(label, tile size, lo, hi)] in set-major rows: weight 1 on every agent of platoon p0 (tile size 64; 1 / P x learn(that agent's
+    rows) for every set at once), and the whole set (tile size "whole")."""
+    _, P, platoons = fset_plan(name, cus)
+    return [(f"p{p0}", FSET_B, FSET_B * p0, FSET_B * p0 + FSET_B) for p0 in platoons] + [("whole", "whole", 0, FSET_B * P)]
+
+
+@functools.lru_cache(maxsize=None)
+def fset_reference(name, cus):
+    """-> (masks, {k: (refs, emus, tol)}) for every checked set k: per mask the float64 reference and the bf16-operand oracle, and per
+    tile size (64, "whole") the tolerance table pooled over that set's masks. Cached per (case, CU count)."""
+    case = fset_case(name, cus)
+    batch, ms = set_major(fset_batch(case), case.n_sets), fset_masks(name, cus)
+    return ms, {k: _reference(case, batch, ms, k)[1:] for k in case.check}
+
+
+def fset_weights(case):
+    """Per-agent factors w_p * P / sum(w) [P, n_sets], different per platoon AND per set: 0.2 ... 3.0 over the platoons with the
+    +-20 % jitter of tests/test_gpu_fset.py's weighted test."""
+    P, M = case.rows // FSET_B, case.n_sets
+    rs = np.random.RandomState(case.seed + 2000)
+    w = np.linspace(0.2, 3.0, P)[:, None].repeat(M, axis=1) * rs.uniform(0.8, 1.2, size=(P, M))
+    return (w * (P / w.sum(axis=0))).astype(np.float32)
+
+
+def weighted_learn(case, nets, batch, k, w, rnd, **kw):
+    """{name: learn(all rows of set k)} with platoon p's rows weighted by w[p, k] on both loss seeds (dq_scale / da_scale): what the set
+    learners return for agent_weight = w."""
+    s, a, r, s2 = batch
+    f = np.repeat(w[:, k].astype(np.float64), FSET_B)[:, None]
+    cg, ag, _ = learn((s[k], a[k], r[k][:, None], s2[k]), *nets, rnd=rnd, dq_scale=f, da_scale=f, **kw)
+    return dict(zip(NAMES, cg + ag))
+
+
+@functools.lru_cache(maxsize=None)
+def fset_weighted_reference(name, cus):
+    """-> (w [P, n_sets], {k: (ref, emu, tol)}): the general-weights reference of every checked set, its own one-mask tolerance table."""
+    case = fset_case(name, cus)
+    batch, w = set_major(fset_batch(case), case.n_sets), fset_weights(case)
+    out = {}
+    for k in case.check:
+        nets = case_nets(case, k)
+        ref = weighted_learn(case, nets, batch, k, w, identity)
+        emu = weighted_learn(case, nets, batch, k, w, round_bf16, placement=case.placement)
+        out[k] = (ref, emu, tolerances([ref], [emu]))
+    return w, out

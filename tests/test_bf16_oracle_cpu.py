@@ -1,6 +1,11 @@
 """tests/bf16_oracle.py checks itself (CPU only): the restated learn() is oracle/mlp.py bit for bit when nothing is rounded, the
 rounding helper is torch.bfloat16's, the acceptance rule of tests/test_gpu_wide_tiles.py CAN fail (a 32-row tile whose gradient is
-missing is rejected on the head tensors), and on the chosen seeds no tolerance reaches the cap at which it would say nothing."""
+missing is rejected on the head tensors), and on the chosen seeds no tolerance reaches the cap at which it would say nothing. The
+same for the agent-major cases of tests/test_gpu_fset_tiles.py (csrc/fset.hip), at 256 compute units: no tolerance at the cap, no
+tensor left out, and a dropped, shifted or missing agent tile is rejected by the per-agent rule where a whole-set one lets it go."""
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -23,7 +28,7 @@ def test_without_rounding_the_module_is_the_oracle_bit_for_bit(S, H1, H2, Ha, B)
     for k in aux:
         assert np.array_equal(aux[k], aux2[k]), k
     # the kernel's placements restate the same function: without rounding they differ from it by float64 summation order alone
-    for placement in ("dual", "delta"):
+    for placement in ("dual", "delta", "fset"):
         cgp, agp, _ = bo.learn(batch, *nets, rnd=bo.identity, placement=placement)
         assert all(np.max(np.abs(x - y)) <= 1e-12 * np.max(np.abs(x)) for x, y in zip(cg + ag, cgp + agp)), placement
     # ... and the rounding is not a no-op, and the fault handles reach the gradients they are meant for (and only those)
@@ -113,3 +118,129 @@ def test_the_rule_rejects_a_32_row_tile_that_is_missing():
             wrong = {n: (np.zeros_like(g) if n[0] == heads[0][0] else g) for n, g in ref.items()}
             bad = {v[0] for v in bo.violations(wrong, ref, tol[32])}
             assert set(heads) <= bad, (label, heads, bad)
+
+
+# ---- the agent-major cases (csrc/fset.hip) ------------------------------------------------------------------------------------------
+CUS = 256  # the plan the CPU self-checks assume (an MI355X); the GPU test takes the device's own count
+FSET_NAMES = [c.name for c in bo.FSET]
+
+
+def test_the_refactored_helpers_give_the_wide_cases_their_old_tolerance_table():
+    """The table of h256x128_S3 (every tile size, every tensor: scale, e_bf16, tolerance) as it was before the helpers took the set count
+    and the checked sets from the case -- recorded to nine digits (another BLAS may sum in another order)."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bf16_oracle_h256x128_S3_tol.json")) as f:
+        want = json.load(f)
+    tol = bo.case_reference("h256x128_S3")[3]
+    assert sorted(want) == sorted(str(t) for t in tol)
+    for t, table in tol.items():
+        for tensor in bo.NAMES:
+            assert np.allclose(table[tensor], want[str(t)][tensor], rtol=1e-9, atol=0), (t, tensor)
+    case = bo.CASE["h256x128_S3"]
+    assert (case.n_sets, case.check) == (bo.N_SETS, (bo.CHECK_SET,))
+
+
+def test_fset_cases_reach_the_paths_they_are_there_for():
+    """At 256 CUs: 64 sets -> J = 4, 27 platoons, workgroups of 7, 7, 7, 6 tiles (more than NW / 2 = 4 and 6: the prefetch branch and a
+    wave pair's second tile; odd and even counts for dxa's parities); 5 sets -> J = 51, 70 platoons, 19 workgroups with 2 tiles and 32
+    with 1; one set -> 256 workgroups, 300 platoons. Masked platoons lie inside the set; checked sets include the first and the last."""
+    tiles = lambda J, P: sorted({(P - j0 + J - 1) // J for j0 in range(J)})
+    J, P, pl = bo.fset_plan("fset_64sets", CUS)
+    assert (J, P) == (4, 27) and tiles(J, P) == [6, 7] and pl == list(range(27))
+    J, P, pl = bo.fset_plan("fset_modelA_ragged", CUS)
+    assert (J, P) == (51, 70) and tiles(J, P) == [1, 2] and pl == [0, 50, 51, 69] and P - J == 19
+    J, P, pl = bo.fset_plan("fset_one_set", CUS)
+    assert (J, P) == (256, 300) and tiles(J, P) == [1, 2] and pl == [0, 255, 256, 299]
+    for cus in (64, 104, 256, 304):  # another part: still inside the set, still 7 tiles in the 64-set case
+        for name in FSET_NAMES:
+            case, (J, P, pl) = bo.fset_case(name, cus), bo.fset_plan(name, cus)
+            assert pl and all(0 <= p < P for p in pl) and case.rows == 64 * P
+            assert 0 in case.check and case.n_sets - 1 in case.check and case.widths == (256, 128, 48)
+        J, P, _ = bo.fset_plan("fset_64sets", cus)
+        assert tiles(J, P) in ([6, 7], [6]) and max(tiles(J, P)) >= 6
+    s, a, r, s2 = bo.fset_batch(bo.fset_case("fset_modelA_ragged", CUS))
+    assert s.shape == (350, 64, 3) and a.shape == (350, 64, 1) and r.shape == (350, 64) and s2.shape == s.shape
+    sm = bo.set_major((s, a, r, s2), 5)  # agent p * M + m -> rows [64 p, 64 p + 64) of set m
+    assert sm[0].shape == (5, 70 * 64, 3) and np.array_equal(sm[0][4, 64 * 69:], s[69 * 5 + 4]) and np.array_equal(sm[2][2, 64:128], r[1 * 5 + 2])
+
+
+@pytest.mark.parametrize("name", FSET_NAMES)
+def test_no_fset_tolerance_reaches_the_cap_and_no_tensor_is_left_out(name):
+    """Every tensor of every checked set at both tile sizes (64 rows = one agent, the whole set): tolerance = max(FLOOR, FACTOR x e_bf16)
+    under CAP; no skip list; the rule accepts the emulation it was derived from. The same for the general-weights reference."""
+    case = bo.fset_case(name, CUS)
+    assert case.drop32 == () and case.placement == ("fset" if name == "fset_64sets" else "generic")
+    ms, per = bo.fset_reference(name, CUS)
+    assert {m[1] for m in ms} == {64, "whole"} and sorted(per) == sorted(case.check)
+    tables = [(k, t, table) for k, (_, _, tol) in per.items() for t, table in tol.items()]
+    if name == "fset_64sets":
+        tables += [(k, "weighted", tol) for k, (_, _, tol) in bo.fset_weighted_reference(name, CUS)[1].items()]
+    for k, t, table in tables:
+        assert sorted(table) == sorted(bo.NAMES)
+        for tensor, (scale, e, limit) in table.items():
+            print(f"{name} set {k} t={t} {tensor}: scale {scale:.3e} e_bf16 {e:.3e} tol {limit:.3e}")
+            assert scale > 0 and np.isfinite(e) and limit == max(bo.FLOOR, bo.FACTOR * e) and limit < bo.CAP, (name, k, t, tensor, e)
+    for k, (refs, emus, tol) in per.items():
+        for ref, emu, (_, t, _, _) in zip(refs, emus, ms):
+            assert bo.violations(emu, ref, tol[t]) == []
+
+
+@pytest.mark.parametrize("name", FSET_NAMES)
+def test_the_per_agent_rule_rejects_a_dropped_and_a_shifted_agent_tile(name):
+    """For every checked set and every masked platoon p0, against the float64 reference of that mask (1 / P x learn(agent p0's rows)):
+    (a) a result WITHOUT the agent's contribution (zeros: the tile was skipped) misses the rule on all 24 tensors;
+    (b) the contribution of the NEIGHBOURING agent p0 + 1 in its place (a tile index off by one) misses it on cWs, cWa, cW3 and cg3 and
+        on at least 14 tensors in all (19 or more in the two cases with few sets). The agents' batches are independent draws of one
+        distribution, so tensors that are sums of like-signed seeds (biases, BN shifts: ab3, abe2, cb2, ..) can agree between two agents
+        to within the bf16 noise of a 64-row tile; the tensors that pair the seeds with the tile's own inputs and activations do not."""
+    case = bo.fset_case(name, CUS)
+    _, P, _ = bo.fset_plan(name, CUS)
+    ms, per = bo.fset_reference(name, CUS)
+    batch = bo.set_major(bo.fset_batch(case), case.n_sets)
+    for k, (refs, _, tol) in per.items():
+        nets = bo.case_nets(case, k)
+        for (label, t, lo, hi), ref in zip(ms, refs):
+            if t != 64:
+                continue
+            gone = {n: np.zeros_like(g) for n, g in ref.items()}
+            assert {v[0] for v in bo.violations(gone, ref, tol[64])} == set(bo.NAMES), (k, label)
+            if hi < case.rows:
+                shifted = bo.tile_learn(case, nets, batch, lo + 64, hi + 64, bo.identity, k=k)
+                bad = {v[0] for v in bo.violations(shifted, ref, tol[64])}
+                assert {"cWs", "cWa", "cW3", "cg3"} <= bad and len(bad) >= (14 if name == "fset_64sets" else 19), (k, label, sorted(bad))
+
+
+def test_a_whole_set_comparison_lets_a_missing_agent_through_where_the_per_agent_masks_do_not():
+    """A whole-set result that lacks ONE agent's tile (whole - 1 / P x learn(agent p0)), every p0 of every checked set.
+    27 platoons (fset_64sets), under the pooled whole-set rule: rejected every time on all 14 critic tensors, and on every head tensor
+    in sets 0 and 37. The heads that ESCAPE: aW3, ab3, ag2 and abe2 of set 63, for all 27 agents -- that set's actor tolerance is
+    0.083 (the action gradient's coherent bf16 offset, docs/fset_tile_parity.md), more than the 1 / 27 an agent carries.
+    70 platoons (fset_modelA_ragged), under the 2e-2 of each tensor's max that tests/test_gpu_fset.py allows: every head tensor of the
+    faulty result PASSES, for every masked agent of both sets (an agent is 1 / 70 = 1.4 % of its set).
+    The per-agent mask of the same agent rejects the missing tile on all 24 tensors (the test above): that is what the masks are for."""
+    ms, per = bo.fset_reference("fset_64sets", CUS)
+    for k, (refs, _, tol) in per.items():
+        whole = refs[-1]
+        assert ms[-1][1] == "whole"
+        for (label, t, _, _), ref in zip(ms[:-1], refs):
+            wrong = {n: whole[n] - ref[n] for n in bo.NAMES}
+            bad = {v[0] for v in bo.violations(wrong, whole, tol["whole"])}
+            assert {n for n in bo.NAMES if n[0] == "c"} <= bad, (k, label, sorted(bad))
+            assert set(bo.HEADS) <= bad or (k == 63 and set(bo.HEADS) - bad == {"aW3", "ab3", "ag2", "abe2"}), (k, label, sorted(bad))
+    ms, per = bo.fset_reference("fset_modelA_ragged", CUS)
+    for k, (refs, _, _) in per.items():
+        whole = refs[-1]
+        for (label, t, _, _), ref in zip(ms[:-1], refs):
+            for n in bo.HEADS:
+                assert np.max(np.abs(ref[n])) <= 2e-2 * np.max(np.abs(whole[n])), (k, label, n)
+
+
+def test_fset_general_weights_are_normalised_and_differ_per_platoon_and_per_set():
+    """The factors of the general-weights test: w_p * P / sum(w) (mean 1 per set), 0.2 ... 3.0 over the platoons with +-20 % jitter, another
+    column for every set; the rule accepts the emulation of that reference. (The platoons' batches are draws of one distribution, so the
+    unweighted mean lies close to any weighted one: the per-agent masks, not this case, are the sharp test of the factor itself.)"""
+    w, per = bo.fset_weighted_reference("fset_64sets", CUS)
+    assert w.shape == (27, 64) and w.dtype == np.float32 and np.allclose(w.mean(axis=0), 1.0, atol=1e-6)
+    assert w.min() > 0.05 and (w.max(axis=0) / w.min(axis=0)).min() > 8
+    assert not np.allclose(w[:, 0], w[:, 63], rtol=1e-2)
+    for k, (ref, emu, tol) in per.items():
+        assert bo.violations(emu, ref, tol) == []

@@ -48,6 +48,9 @@ def test_fused_set_learner_matches_oracle_on_concatenated_batch(S, P, M):
         for name, got, ref in zip(NAMES, gcg + gag, cg + ag):
             # bf16 second-layer operands (2^-9 relative rounding per element) against the float64 oracle: 2 % of the
             # tensor's max (the layer-wise bf16 learner's bound at these widths, tests/test_gpu_wide.py)
+            # (measured per tensor, per agent tile and per whole set, with the bf16 oracle's own error beside it:
+            #  docs/fset_tile_parity.md -- whole sets of 1 728 ... 19 200 rows measured 7e-3 at the most, and 2.1e-2 on every actor tensor of ONE of 64 sets there (weights of its own seed: the action gradient's coherent bf16 offset, which the bf16 oracle shares); an agent tile is 1.4 % of a
+            #  70-platoon set and invisible here, tests/test_gpu_fset_tiles.py holds it to 4 x the bf16 oracle's error)
             assert _relerr(got, ref) <= 2e-2, (k, name, _relerr(got, ref))
         lo = losses[k].cpu().numpy()
         assert abs(lo[0] - aux["critic_loss"]) <= 1e-2 * abs(aux["critic_loss"])
@@ -75,7 +78,7 @@ def test_fused_set_learner_equals_per_agent_kernel_plus_federated_mean_and_layer
     for name, lo, hi in (("actor", 0, lay.actor_size), ("critic", lay.actor_size, lay.theta_size)):
         scale = np.abs(avg[:, lo:hi]).max()
         ef, ew = np.abs(avg[:, lo:hi] - fused[:, lo:hi]).max() / scale, np.abs(avg[:, lo:hi] - wide[:, lo:hi]).max() / scale
-        assert ef <= 2e-2 and np.abs(wide[:, lo:hi] - fused[:, lo:hi]).max() <= 2e-2 * scale, name
+        assert ef <= 2e-2 and np.abs(wide[:, lo:hi] - fused[:, lo:hi]).max() <= 2e-2 * scale, name  # (measured worst per tensor: docs/fset_tile_parity.md)
         assert ef <= 2.0 * ew + 5e-4, (name, ef, ew)  # measured: 0.9 ... 1.7 x the layer-wise learner's error
     # padding floats of the slab stay zero (what Adam relies on)
     assert fused[:, lay.actor_size - 3:lay.actor_size].max() == 0.0 or lay.actor_size % 4 == 0
@@ -158,7 +161,7 @@ def test_full_size_fused_set_learner_is_the_mean_of_its_halves_and_tracks_the_la
     for lo, hi in ((0, lay.actor_size), (lay.actor_size, lay.theta_size)):
         scale = full[:, lo:hi].abs().max().item()
         assert (full[:, lo:hi] - avg[:, lo:hi]).abs().max().item() <= 1e-3 * scale, lo
-        assert (full[:, lo:hi] - wide[:, lo:hi]).abs().max().item() <= 2e-2 * scale, lo
+        assert (full[:, lo:hi] - wide[:, lo:hi]).abs().max().item() <= 2e-2 * scale, lo  # (bf16 class; the per-tensor figures at small sizes: docs/fset_tile_parity.md)
     assert not torch.allclose(halves[0], halves[1])  # the halves are different batches
 
 

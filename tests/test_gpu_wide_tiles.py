@@ -21,19 +21,19 @@ pytestmark = pytest.mark.gpu
 
 
 def _group_and_batch(case):
-    conf, grp = _perturbed_group(bo.N_SETS, S=case.S, seed=case.seed, **bo.case_conf_kw(case))
+    conf, grp = _perturbed_group(case.n_sets, S=case.S, seed=case.seed, **bo.case_conf_kw(case))
     return grp, bo.case_batch(case)
 
 
 def _learn(grp, case, dev, row_weight):
-    n_agents = bo.N_SETS * case.rows // 64
+    n_agents = case.n_sets * case.rows // 64
     g = grp.learn_shared(*dev, n_agents, row_weight=row_weight)
     torch.cuda.synchronize()
     return g.clone()
 
 
 def _weights(case, lo, hi):
-    w = np.zeros((bo.N_SETS, case.rows), np.float32)
+    w = np.zeros((case.n_sets, case.rows), np.float32)
     w[:, lo:hi] = 1.0
     return t(w)
 
@@ -51,7 +51,7 @@ def test_every_tile_mask_matches_the_oracle_within_four_times_the_bf16_oracle_er
     need_gpu()
     case = bo.CASE[name]
     grp, batch = _group_and_batch(case)
-    k = bo.CHECK_SET
+    k = case.check[0]
     for host, devw in zip(bo.case_nets(case, k), _nets(grp, k, np.float64)):  # the CPU-side tables are of THESE weights
         assert all(np.array_equal(x, y) for x, y in zip(host, devw))
     ms, refs, _, tol = bo.case_reference(name)
