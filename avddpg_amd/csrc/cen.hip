@@ -705,10 +705,9 @@ __global__ __launch_bounds__(NT) void learn_kernel_c(avd_mlp_layout L_arg, int s
 struct Span {  // agents [lo, lo + n) of the slabs
     int lo, n;
 };
+// agents sp of c's slabs; the soft-update coefficients of the target statistics (STATS) are c.upd's (zero in the gradient-only call)
 template <int S, int A, bool STATS>
-static int launch_t(const avd_mlp_layout* lay, Span sp, int set_mod, const float* theta, const float* stats, float* theta_t,
-                    float* stats_t, const float* s, const float* a, const float* r, const float* s2, float gamma, float high,
-                    float* grads, float* losses, float tau, float omt, hipStream_t stream) {
+static int launch_t(const LearnCall& c, Span sp) {
     constexpr size_t lds = sizeof(float) * Lds<S, A>::total;
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -722,24 +721,20 @@ static int launch_t(const avd_mlp_layout* lay, Span sp, int set_mod, const float
         if (dev >= 0 && dev < 64) attr[dev].store(true, std::memory_order_release);
     }
     // (a span is addressed by offsetting the per-agent arrays; shared sets -- set_mod > 0 -- only ever come with lo == 0)
-    const long lo = sp.lo, ts = lay->theta_size, ss = lay->stats_size;
-    const long wo = set_mod > 0 ? 0 : lo;
-    hipLaunchKernelGGL((learn_kernel_c<S, A, STATS>), dim3(sp.n), dim3(NT), lds, stream, *lay, set_mod, theta + wo * ts, stats + wo * ss,
-                       theta_t + wo * ts, stats_t + wo * ss, s + lo * TILE * S, a + lo * TILE * A, r + lo * TILE, s2 + lo * TILE * S, gamma,
-                       high, grads + lo * ts, losses ? losses + lo * 2 : nullptr, tau, omt);
-    return check_launch(STATS ? "avd_learn_update_f32 (centralized)" : "avd_learn_f32 (centralized)");
+    const long lo = sp.lo, ts = c.lay->theta_size, ss = c.lay->stats_size;
+    const long wo = c.set_mod > 0 ? 0 : lo;
+    hipLaunchKernelGGL((learn_kernel_c<S, A, STATS>), dim3(sp.n), dim3(NT), lds, c.stream, *c.lay, c.set_mod, c.theta + wo * ts,
+                       c.stats + wo * ss, c.theta_t + wo * ts, c.stats_t + wo * ss, c.s + lo * TILE * S, c.a + lo * TILE * A, c.r + lo * TILE,
+                       c.s2 + lo * TILE * S, c.gamma, c.high, c.grads + lo * ts, c.losses ? c.losses + lo * 2 : nullptr, c.upd.tau, c.upd.omt);
+    return check_learn_launch(c, "centralized");
 }
 
 template <bool STATS>
-static int launch_shape(const avd_mlp_layout* lay, Span sp, int set_mod, const float* theta, const float* stats, float* theta_t,
-                        float* stats_t, const float* s, const float* a, const float* r, const float* s2, float gamma, float high,
-                        float* grads, float* losses, float tau, float omt, hipStream_t stream) {
-    if (lay->S == 20 && lay->A == 5)
-        return launch_t<20, 5, STATS>(lay, sp, set_mod, theta, stats, theta_t, stats_t, s, a, r, s2, gamma, high, grads, losses, tau, omt, stream);
-    if (lay->S == 12 && lay->A == 3)
-        return launch_t<12, 3, STATS>(lay, sp, set_mod, theta, stats, theta_t, stats_t, s, a, r, s2, gamma, high, grads, losses, tau, omt, stream);
-    set_error("cen_launch: shape S=%d A=%d H1=%d H2=%d Ha=%d is not one of the centralized instantiations", lay->S, lay->A, lay->H1,
-              lay->H2, lay->Ha);
+static int launch_shape(const LearnCall& c, Span sp) {
+    if (c.lay->S == 20 && c.lay->A == 5) return launch_t<20, 5, STATS>(c, sp);
+    if (c.lay->S == 12 && c.lay->A == 3) return launch_t<12, 3, STATS>(c, sp);
+    set_error("cen_launch: shape S=%d A=%d H1=%d H2=%d Ha=%d is not one of the centralized instantiations", c.lay->S, c.lay->A, c.lay->H1,
+              c.lay->H2, c.lay->Ha);
     return AVD_E_UNSUPPORTED;
 }
 
@@ -772,18 +767,7 @@ static Side* side_stream(hipStream_t of) {
 
 }  // namespace cen
 
-#ifdef AVD_PHASE_TIMING
-}  // namespace avd
-extern "C" __attribute__((visibility("default"))) int avd_debug_phase_cycles_cen(unsigned long long* h_out, int reset) {
-    if (h_out) (void)hipMemcpyFromSymbol(h_out, HIP_SYMBOL(avd::g_phase_cycles), sizeof(unsigned long long) * 32);
-    if (reset) {
-        unsigned long long z[32] = {0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(avd::g_phase_cycles), z, sizeof(z));
-    }
-    return 0;
-}
-namespace avd {
-#endif
+AVD_PHASE_CYCLES_EXPORT(avd_debug_phase_cycles_cen)
 
 bool cen_supports(const avd_mlp_layout* lay) {
     return lay->B == TILE && lay->H1 == cen::H1 && lay->H2 == cen::H2 && lay->Ha == cen::HA &&
@@ -791,12 +775,7 @@ bool cen_supports(const avd_mlp_layout* lay) {
            lay->ab3 >= 2 * TILE * cen::H2;  // (the kernel parks 2 x 64 x 160 floats at the head of the gradient row's actor block)
 }
 
-int cen_launch(const avd_mlp_layout* lay, int n_agents, int set_mod, const float* theta, const float* stats, const float* theta_t,
-               const float* stats_t, const float* s, const float* a, const float* r, const float* s2, float gamma, float high, float* grads,
-               float* losses, void* stream) {
-    return cen::launch_shape<false>(lay, cen::Span{0, n_agents}, set_mod, theta, stats, (float*)theta_t, (float*)stats_t, s, a, r, s2, gamma,
-                                    high, grads, losses, 0.f, 0.f, (hipStream_t)stream);
-}
+int cen_launch(const LearnCall& c) { return cen::launch_shape<false>(c, cen::Span{0, c.n_agents}); }
 
 // How cen_launch_update cuts n_agents models into chunks: one learn workgroup per CU and chunk, at most MAX_CHUNKS chunks (the chunk
 // grows beyond the CU count instead), one update workgroup per CU (MI355X, 256 CUs, 4096 agents: 6.8 ms per step with 256 / 256, 7.3
@@ -821,13 +800,10 @@ void cen_update_plan(int n_agents, int* chunk_out, int* groups_out) {
 // (adam_polyak_ranges_kernel over the whole slab row: no LDS, few registers -- its workgroups co-reside on CUs whose LDS is held by
 // learn workgroups) under chunk c + 1's MFMAs. The gradients take a round trip through HBM (+1 MB per agent) that the in-kernel form
 // did not need; the side stream is joined into the caller's stream by an event (capturable in a hipGraph).
-int cen_launch_update(const avd_mlp_layout* lay, int n_agents, const float* theta, const float* stats, float* theta_out, float* theta_t,
-                      float* stats_t, float* m, float* v, const int32_t* step, const float* s, const float* a, const float* r,
-                      const float* s2, float gamma, float high, float actor_lr, float critic_lr, double tau, float* grads, float* losses,
-                      void* stream) {
-    hipStream_t main = (hipStream_t)stream;
-    const float tauf = (float)tau, omt = (float)(1.0 - tau);
-    const long ts = lay->theta_size;
+int cen_launch_update(const LearnCall& c) {
+    hipStream_t main = c.stream;
+    const int n_agents = c.n_agents;
+    const long ts = c.lay->theta_size;
     // one learn workgroup per CU and chunk, one update workgroup per CU (MI355X, 256 CUs, 4096 agents: 6.8 ms per step with 256 / 256,
     // 7.3 with chunks of 512, 11.4 with 128; 128 or 192 update workgroups: 8.1, 384 / 512: 6.6 against 6.3)
     int chunk = 0, groups = 0;
@@ -843,17 +819,17 @@ int cen_launch_update(const avd_mlp_layout* lay, int n_agents, const float* thet
         forked = false;
         return hipEventRecord(sd->join, sd->st) == hipSuccess && hipStreamWaitEvent(main, sd->join, 0) == hipSuccess;
     };
-    int c = 0;
-    for (int lo = 0; lo < n_agents; lo += chunk, ++c) {
+    int k = 0;  // chunk index
+    for (int lo = 0; lo < n_agents; lo += chunk, ++k) {
         const cen::Span sp = {lo, n_agents - lo < chunk ? n_agents - lo : chunk};
-        int rc = cen::launch_shape<true>(lay, sp, 0, theta, stats, theta_t, stats_t, s, a, r, s2, gamma, high, grads, losses, tauf, omt, main);
+        int rc = cen::launch_shape<true>(c, sp);
         if (rc) {
             (void)join();
             return rc;
         }
         hipStream_t ust = main;
         if (sd) {
-            if (hipEventRecord(sd->learned[c], main) != hipSuccess || hipStreamWaitEvent(sd->st, sd->learned[c], 0) != hipSuccess) {
+            if (hipEventRecord(sd->learned[k], main) != hipSuccess || hipStreamWaitEvent(sd->st, sd->learned[k], 0) != hipSuccess) {
                 (void)join();
                 return check_launch("avd_learn_update_f32 (centralized): fork");
             }
@@ -861,8 +837,8 @@ int cen_launch_update(const avd_mlp_layout* lay, int n_agents, const float* thet
             ust = sd->st;
         }
         const long o = (long)sp.lo * ts;
-        rc = ::launch_adam_polyak_rows(lay, sp.n, groups, theta + o, theta_out + o, theta_t + o, m + o, v + o, grads + o, step + sp.lo, actor_lr,
-                                       critic_lr, tau, ust);
+        rc = ::launch_adam_polyak_rows(c.lay, sp.n, groups, c.theta + o, c.upd.theta_out + o, c.theta_t + o, c.upd.m + o, c.upd.v + o, c.grads + o,
+                                       c.upd.step + sp.lo, c.upd.actor_lr, c.upd.critic_lr, c.tau, ust);
         if (rc) {
             (void)join();
             return rc;

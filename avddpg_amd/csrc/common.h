@@ -20,6 +20,16 @@ inline int check_launch(const char* what) {
     return AVD_OK;
 }
 
+// Let a kernel take `bytes` of dynamic LDS (above the 48 KB a launch gets without asking), per launch: no cache to go stale per device.
+inline int opt_in_dynamic_lds(const void* fn, size_t bytes, const char* who) {
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) {
+        set_error("%s: hipFuncSetAttribute(%zu B LDS): %s", who, bytes, hipGetErrorString(e));
+        return AVD_E_LAUNCH;
+    }
+    return AVD_OK;
+}
+
 // Diagnostic switches (kernel / tile choices for A/B runs and cross-checks, work-skipping ablations) exist ONLY in the
 // diagnostic build (`make diag`: -DAVD_DIAG -> lib/libavddpg_hip_diag.so). The shipped library reads no environment
 // variable: AVD_DIAG_ENV("X") is getenv("AVD_X") there and a null constant here (the name is not even in the binary;

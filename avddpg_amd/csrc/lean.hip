@@ -884,9 +884,7 @@ __global__ __launch_bounds__(FT, 2) void learn_kernel_l(avd_mlp_layout L_arg, in
 }
 
 template <int S, bool FUSED, class... H>
-static int launch(const avd_mlp_layout* lay, int n_agents, int set_mod, const float* theta, const float* stats,
-                  float* theta_t, float* stats_t, const float* s, const float* a, const float* r, const float* s2,
-                  float gamma, float high, float* grads, float* losses, UpdArgs upd, void* stream, H... hp) {
+static int launch(const LearnCall& c, H... hp) {
     constexpr bool HP = sizeof...(H) > 0;
     constexpr int H1 = 256, H2 = 128, HA = 48;
     size_t lds = sizeof(float) * lds_floats(H1 + HA, H2);
@@ -895,75 +893,31 @@ static int launch(const avd_mlp_layout* lay, int n_agents, int set_mod, const fl
         if (want > lds && want <= 160 * 1024) lds = want;
     }
     static_assert(sizeof(float) * lds_floats(H1 + HA, H2) <= 80 * 1024, "two workgroups per CU");
-    hipError_t e = hipFuncSetAttribute((const void*)learn_kernel_l<S, H1, H2, HA, FUSED, HP, H...>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-        set_error("lean_launch: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
-        return AVD_E_LAUNCH;
-    }
-    hipLaunchKernelGGL((learn_kernel_l<S, H1, H2, HA, FUSED, HP, H...>), dim3(n_agents), dim3(FT), lds, (hipStream_t)stream, *lay,
-                       set_mod, theta, stats, theta_t, stats_t, s, a, r, s2, gamma, high, grads, losses, upd, hp...);
-    if constexpr (HP) return check_launch(FUSED ? "avd_learn_update_hp_f32 (lean)" : "avd_learn_hp_f32 (lean)");
-    return check_launch(FUSED ? "avd_learn_update_f32 (lean)" : "avd_learn_f32 (lean)");
+    if (int rc = opt_in_dynamic_lds((const void*)learn_kernel_l<S, H1, H2, HA, FUSED, HP, H...>, lds, "lean_launch")) return rc;
+    // (the HP twins read gamma from the table: c.gamma is 0 there)
+    hipLaunchKernelGGL((learn_kernel_l<S, H1, H2, HA, FUSED, HP, H...>), dim3(c.n_agents), dim3(FT), lds, c.stream, *c.lay, c.set_mod, c.theta,
+                       c.stats, c.theta_t, c.stats_t, c.s, c.a, c.r, c.s2, c.gamma, c.high, c.grads, c.losses, c.upd, hp...);
+    return check_learn_launch(c, "lean");
+}
+
+// S x FUSED, for the scalar kernels (no H) and for their HP twins (H = HpRef)
+template <class... H>
+static int dispatch(const LearnCall& c, H... hp) {
+    if (c.lay->S == 4) return c.fused ? launch<4, true>(c, hp...) : launch<4, false>(c, hp...);
+    return c.fused ? launch<3, true>(c, hp...) : launch<3, false>(c, hp...);
 }
 
 }  // namespace lean
 
-#ifdef AVD_PHASE_TIMING
-}  // namespace avd
-extern "C" __attribute__((visibility("default"))) int avd_debug_phase_cycles_lean(unsigned long long* h_out, int reset) {
-    if (h_out) (void)hipMemcpyFromSymbol(h_out, HIP_SYMBOL(avd::g_phase_cycles), sizeof(unsigned long long) * 32);
-    if (reset) {
-        unsigned long long z[32] = {0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(avd::g_phase_cycles), z, sizeof(z));
-    }
-    return 0;
-}
-namespace avd {
-#endif
+AVD_PHASE_CYCLES_EXPORT(avd_debug_phase_cycles_lean)
 
-int lean_launch(const avd_mlp_layout* lay, bool fused, int n_agents, int set_mod, const float* theta, const float* stats,
-                float* theta_t, float* stats_t, const float* s, const float* a, const float* r, const float* s2,
-                float gamma, float high, float* grads, float* losses, UpdArgs upd, void* stream) {
-    if (!(lay->A == 1 && lay->H1 == 256 && lay->H2 == 128 && lay->Ha == 48 && (lay->S == 3 || lay->S == 4) &&
-          lay->B == TILE)) {
+int lean_launch(const LearnCall& c) {
+    if (!(reference_widths(*c.lay) && c.lay->B == TILE)) {
         set_error("lean_launch: built for the reference widths 256/128/48, A=1, B=64, S in {3,4}");
         return AVD_E_UNSUPPORTED;
     }
-#define AVD_LEAN(SS, FF)                                                                                              \
-    return lean::launch<SS, FF>(lay, n_agents, set_mod, theta, stats, theta_t, stats_t, s, a, r, s2, gamma, high, grads, \
-                                losses, upd, stream)
-    if (lay->S == 4) {
-        if (fused) AVD_LEAN(4, true);
-        AVD_LEAN(4, false);
-    }
-    if (fused) AVD_LEAN(3, true);
-    AVD_LEAN(3, false);
-#undef AVD_LEAN
-}
-
-// the HP twins (avd_learn_hp_f32, avd_learn_update[_act]_hp_f32): reference widths only, arguments checked by the caller
-int lean_launch_hp(const avd_mlp_layout* lay, bool fused, int n_agents, int set_mod, const float* theta, const float* stats,
-                   float* theta_t, float* stats_t, const float* s, const float* a, const float* r, const float* s2, float high,
-                   float* grads, float* losses, UpdArgs upd, const avd_hparams* d_hp, int n_groups, int set_block, void* stream) {
-    if (!(lay->A == 1 && lay->H1 == 256 && lay->H2 == 128 && lay->Ha == 48 && (lay->S == 3 || lay->S == 4) &&
-          lay->B == TILE)) {
-        set_error("%s: a hyperparameter sweep runs the reference widths 256/128/48, A=1, B=64, S in {3,4} only (got %d/%d/%d, A=%d, "
-                  "B=%d, S=%d)", fused ? "avd_learn_update_hp_f32" : "avd_learn_hp_f32", lay->H1, lay->H2, lay->Ha, lay->A, lay->B,
-                  lay->S);
-        return AVD_E_UNSUPPORTED;
-    }
-    const HpRef hr{d_hp, n_groups, set_block};
-#define AVD_LEAN(SS, FF)                                                                                                       \
-    return lean::launch<SS, FF>(lay, n_agents, set_mod, theta, stats, theta_t, stats_t, s, a, r, s2, 0.f, high, grads, losses, \
-                                upd, stream, hr)
-    if (lay->S == 4) {
-        if (fused) AVD_LEAN(4, true);
-        AVD_LEAN(4, false);
-    }
-    if (fused) AVD_LEAN(3, true);
-    AVD_LEAN(3, false);
-#undef AVD_LEAN
+    if (!c.hp) return lean::dispatch(c);
+    return lean::dispatch(c, *c.hp);
 }
 
 }  // namespace avd

@@ -56,7 +56,18 @@ static __device__ unsigned long long g_phase_cycles[32];  // per translation uni
             atomicAdd(&g_phase_cycles[31], __builtin_amdgcn_s_memrealtime() - ph_r0);       \
         }                                                                                   \
     } while (0)
+// The host read-out of a translation unit's g_phase_cycles (inside namespace avd): copy the 32 sums out, optionally zero them.
+#define AVD_PHASE_CYCLES_EXPORT(name)                                                                                      \
+    extern "C" __attribute__((visibility("default"))) int name(unsigned long long* h_out, int reset) {                     \
+        if (h_out) (void)hipMemcpyFromSymbol(h_out, HIP_SYMBOL(g_phase_cycles), sizeof(unsigned long long) * 32);          \
+        if (reset) {                                                                                                       \
+            unsigned long long z[32] = {0};                                                                                \
+            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_phase_cycles), z, sizeof(z));                                             \
+        }                                                                                                                  \
+        return 0;                                                                                                          \
+    }
 #else
+#define AVD_PHASE_CYCLES_EXPORT(name)
 #define PH_CLK_INIT()
 #define PH_CLK_END()
 #define PH_INIT()
@@ -656,26 +667,50 @@ struct UpdArgs {
     float* act_out;
 };
 
+// ---- host side: which kernel serves a layout, and what an entry point hands that kernel's launcher ----
+// The reference widths (src/config.py:112-117): what learn_kernel_l (lean.hip) and learn_kernel_t (mlp.hip) are instantiated for.
+inline bool reference_widths(const avd_mlp_layout& L) {
+    return L.A == 1 && L.H1 == 256 && L.H2 == 128 && L.Ha == 48 && (L.S == 3 || L.S == 4);
+}
+
+// The four kernels of the per-agent exact-f32 learner, in the order of AVD_LEARN_* (avddpg_hip.h); mlp.hip choose_learner picks one.
+enum class LearnKernel { lean = AVD_LEARN_LEAN, fast = AVD_LEARN_FAST, cen = AVD_LEARN_CEN, general = AVD_LEARN_GENERAL };
+
+// One call of avd_learn*_f32 after its argument checks, with the types the kernels take. Gradient-only calls: fused = false, upd all
+// zero. Update calls: set_mod = 0, grads is the workspace, upd.act_* the optional next-action request. The HP twins: hp set, gamma and
+// upd's step sizes / tau zero (the kernel reads its agent's from the table).
+struct LearnCall {
+    const avd_mlp_layout* lay;
+    int n_agents, set_mod;
+    const float *theta, *stats;
+    float *theta_t, *stats_t;
+    const float *s, *a, *r, *s2;
+    float gamma, high;
+    float *grads, *losses;
+    UpdArgs upd;
+    double tau;  // upd.tau before rounding: what the update passes outside the learn kernels (optim.hip) take
+    bool fused;
+    const HpRef* hp;  // null: the scalar kernels
+    hipStream_t stream;
+    const char* who;  // the entry point, for messages
+};
+
+inline int check_learn_launch(const LearnCall& c, const char* kernel) {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return AVD_OK;
+    set_error("%s (%s): %s", c.who, kernel, hipGetErrorString(e));
+    return AVD_E_LAUNCH;
+}
+
 // cen.hip: learn_kernel_c, the centralized framework's shapes (H1 / H2 / Ha = 320 / 160 / 64, (S, A) = (12, 3) or (20, 5)): gradients
-// out (avd_learn_f32's contract) and the whole update (avd_learn_update_f32's: learn chunks and their Adam + Polyak passes on two streams)
+// out (cen_launch), or the whole update (cen_launch_update: learn chunks and their Adam + Polyak passes on two streams)
 bool cen_supports(const avd_mlp_layout* lay);
 void cen_update_plan(int n_agents, int* chunk_out, int* groups_out);
-int cen_launch(const avd_mlp_layout* lay, int n_agents, int set_mod, const float* theta, const float* stats, const float* theta_t,
-               const float* stats_t, const float* s, const float* a, const float* r, const float* s2, float gamma, float high, float* grads,
-               float* losses, void* stream);
-int cen_launch_update(const avd_mlp_layout* lay, int n_agents, const float* theta, const float* stats, float* theta_out, float* theta_t,
-                      float* stats_t, float* m, float* v, const int32_t* step, const float* s, const float* a, const float* r,
-                      const float* s2, float gamma, float high, float actor_lr, float critic_lr, double tau, float* grads, float* losses,
-                      void* stream);
+int cen_launch(const LearnCall& c);
+int cen_launch_update(const LearnCall& c);
 
-// lean.hip: learn_kernel_l (two workgroups per CU; layer-1 activations recomputed on the fly). Same contract as
-// fast::launch in mlp.hip; the reference widths 256/128/48 with S in {3, 4} only.
-int lean_launch(const avd_mlp_layout* lay, bool fused, int n_agents, int set_mod, const float* theta, const float* stats,
-                float* theta_t, float* stats_t, const float* s, const float* a, const float* r, const float* s2,
-                float gamma, float high, float* grads, float* losses, UpdArgs upd, void* stream);
-// its HP twins: gamma, the step sizes and tau per agent from d_hp (agent j: row (j / set_block) % n_groups); upd's scalars unused
-int lean_launch_hp(const avd_mlp_layout* lay, bool fused, int n_agents, int set_mod, const float* theta, const float* stats,
-                   float* theta_t, float* stats_t, const float* s, const float* a, const float* r, const float* s2, float high,
-                   float* grads, float* losses, UpdArgs upd, const avd_hparams* d_hp, int n_groups, int set_block, void* stream);
+// lean.hip: learn_kernel_l (two workgroups per CU; layer-1 activations recomputed on the fly) and its HP twins, every form of the
+// call; the reference widths only.
+int lean_launch(const LearnCall& c);
 
 }  // namespace avd

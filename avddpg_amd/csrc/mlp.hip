@@ -1326,22 +1326,6 @@ __global__ __launch_bounds__(FT) void learn_kernel_t(avd_mlp_layout L, int set_m
     }
 }
 
-template <int S, int H1, int H2, int HA, bool FUSED>
-static int launch(const avd_mlp_layout* lay, int n_agents, int set_mod, const float* theta, const float* stats,
-                  float* theta_t, float* stats_t, const float* s, const float* a, const float* r, const float* s2,
-                  float gamma, float high, float* grads, float* losses, UpdArgs upd, void* stream) {
-    const size_t lds = sizeof(float) * learn_lds_floats(*lay, FT);
-    hipError_t e = hipFuncSetAttribute((const void*)learn_kernel_t<S, H1, H2, HA, FUSED>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-        set_error("avd_learn_f32: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
-        return AVD_E_LAUNCH;
-    }
-    hipLaunchKernelGGL((learn_kernel_t<S, H1, H2, HA, FUSED>), dim3(n_agents), dim3(FT), lds, (hipStream_t)stream, *lay,
-                       set_mod, theta, stats, theta_t, stats_t, s, a, r, s2, gamma, high, grads, losses, upd);
-    return check_launch(FUSED ? "avd_learn_update_f32" : "avd_learn_f32");
-}
-
 }  // namespace fast
 
 // ------------------------------------------------------------------------------------------
@@ -1478,18 +1462,7 @@ __global__ __launch_bounds__(NTHREADS) void actor_rows_shared_kernel(avd_mlp_lay
     }
 }
 
-#ifdef AVD_PHASE_TIMING
-}  // namespace avd
-extern "C" __attribute__((visibility("default"))) int avd_debug_phase_cycles(unsigned long long* h_out, int reset) {
-    if (h_out) (void)hipMemcpyFromSymbol(h_out, HIP_SYMBOL(avd::g_phase_cycles), sizeof(unsigned long long) * 32);
-    if (reset) {
-        unsigned long long z[32] = {0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(avd::g_phase_cycles), z, sizeof(z));
-    }
-    return 0;
-}
-namespace avd {
-#endif
+AVD_PHASE_CYCLES_EXPORT(avd_debug_phase_cycles)
 
 static inline int round4(int x) { return (x + 3) & ~3; }
 
@@ -1524,13 +1497,6 @@ extern "C" int avd_mlp_layout_init(avd_mlp_layout* o, int S, int A, int H1, int 
     o->cmm3 = take(H2), o->cmv3 = take(H2);
     o->stats_size = p;
     return AVD_OK;
-}
-
-// Which kernel serves the reference widths: learn_kernel_l (lean.hip, two workgroups per CU) unless
-// AVD_LEARN_KERNEL=fast asks for learn_kernel_t (one workgroup per CU, first-layer activations in LDS).
-static bool use_lean_kernel() {
-    const char* k = AVD_DIAG_ENV("LEARN_KERNEL");
-    return !(k && !strcmp(k, "fast"));
 }
 
 static int check_mlp_dims(const avd_mlp_layout* L, const char* who, bool rows_only = false) {
@@ -1625,63 +1591,153 @@ extern "C" int avd_critic_forward_f32(const avd_mlp_layout* lay, int n_agents, i
                        "avd_critic_forward_f32");
 }
 
-extern "C" int avd_learn_f32(const avd_mlp_layout* lay, int n_agents, int set_mod, const float* theta,
-                             const float* stats, const float* theta_t, const float* stats_t, const float* s,
-                             const float* a, const float* r, const float* s2, float gamma, float high, float* grads,
-                             float* losses, void* stream) {
-    int rc = check_learn_shape(lay, "avd_learn_f32");
-    if (rc) return rc;
-    AVD_REQUIRE(n_agents > 0 && set_mod >= 0, "avd_learn_f32: n_agents=%d set_mod=%d", n_agents, set_mod);
-    AVD_REQUIRE(theta && stats && theta_t && stats_t && s && a && r && s2 && grads, "avd_learn_f32: null pointer");
-    // reference widths (src/config.py:112-117) take the dimension-specialised kernel; anything else the general one
-    if (lay->A == 1 && lay->H1 == 256 && lay->H2 == 128 && lay->Ha == 48 && (lay->S == 3 || lay->S == 4) &&
-        !AVD_DIAG_ENV("LEARN_GENERAL")) {
-        const UpdArgs none = {};
-        if (use_lean_kernel())
-            return lean_launch(lay, false, n_agents, set_mod, theta, stats, (float*)theta_t, (float*)stats_t, s, a, r, s2,
-                               gamma, high, grads, losses, none, stream);
-        if (lay->S == 4)
-            return fast::launch<4, 256, 128, 48, false>(lay, n_agents, set_mod, theta, stats, (float*)theta_t,
-                                                        (float*)stats_t, s, a, r, s2, gamma, high, grads, losses, none,
-                                                        stream);
-        return fast::launch<3, 256, 128, 48, false>(lay, n_agents, set_mod, theta, stats, (float*)theta_t,
-                                                    (float*)stats_t, s, a, r, s2, gamma, high, grads, losses, none,
-                                                    stream);
-    }
-    // the centralized framework's shapes (S = 4 L, A = L, widths x 1.2) at L = 3 / 5: their own eight-wave kernel (cen.hip)
-    if (cen_supports(lay) && !AVD_DIAG_ENV("LEARN_GENERAL"))
-        return cen_launch(lay, n_agents, set_mod, theta, stats, theta_t, stats_t, s, a, r, s2, gamma, high, grads, losses, stream);
-    const size_t lds = sizeof(float) * gen::lds_floats(*lay);  // (<= 160 KiB: check_learn_shape)
-    hipError_t e = hipFuncSetAttribute((const void*)gen::learn_kernel_g<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) {
-        set_error("avd_learn_f32: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
-        return AVD_E_LAUNCH;
-    }
-    hipLaunchKernelGGL(gen::learn_kernel_g<false>, dim3(n_agents), dim3(NTHREADS), lds, (hipStream_t)stream, *lay, set_mod,
-                       theta, stats, (float*)theta_t, (float*)stats_t, s, a, r, s2, gamma, high, grads, losses, UpdArgs{});
-    return check_launch("avd_learn_f32");
-}
-
+// ---- the per-agent learner: avd_learn_f32, avd_learn_update[_act]_f32 and their HP twins (DESIGN.md "Per-agent learner") ----
 // optim.hip: Adam+Polyak over the elements of each slab that lie OUTSIDE [skip_a0, skip_a1) and [skip_c0, skip_c1)
 int launch_adam_polyak_ranges(const avd_mlp_layout* lay, int n_sets, const float* theta_in, float* theta_out,
                               float* theta_t, float* m, float* v, const float* grads, const int32_t* step,
                               float actor_lr, float critic_lr, double tau, int skip_a0, int skip_a1, int skip_c0,
                               int skip_c1, void* stream);
 
-static int learn_update_impl(const avd_mlp_layout* lay, int n_agents, const float* theta, const float* stats,
-                             float* theta_out, float* theta_t, float* stats_t, float* m, float* v, const int32_t* step,
-                             const float* s, const float* a, const float* r, const float* s2, float gamma, float high,
-                             float actor_lr, float critic_lr, double tau, float* grads_scratch, float* losses,
-                             const float* next_state, int x_stride, float* next_action, void* stream);
+// Kernel templates are instantiated, and so laid out in the code object, in the order of their first use. The launchers below would
+// change that order; this list keeps the one the file has always had (after the rows kernels), so that the device code of two trees
+// can be compared as text (tools/isa_diff.py).
+[[maybe_unused]] static const void* const learn_kernel_order[] = {
+    (const void*)fast::learn_kernel_t<4, 256, 128, 48, false>, (const void*)fast::learn_kernel_t<3, 256, 128, 48, false>,
+    (const void*)gen::learn_kernel_g<false>,                   (const void*)gen::learn_kernel_g<true>,
+    (const void*)fast::learn_kernel_t<4, 256, 128, 48, true>,  (const void*)fast::learn_kernel_t<3, 256, 128, 48, true>};
 
-extern "C" int avd_learn_update_f32(const avd_mlp_layout* lay, int n_agents, const float* theta, const float* stats,
-                                    float* theta_out, float* theta_t, float* stats_t, float* m, float* v,
-                                    const int32_t* step, const float* s, const float* a, const float* r,
-                                    const float* s2, float gamma, float high, float actor_lr, float critic_lr,
-                                    double tau, float* grads_scratch, float* losses, void* stream) {
-    return learn_update_impl(lay, n_agents, theta, stats, theta_out, theta_t, stats_t, m, v, step, s, a, r, s2, gamma, high,
-                             actor_lr, critic_lr, tau, grads_scratch, losses, nullptr, 0, nullptr, stream);
+// The table: reference widths -> learn_kernel_l (lean.hip, two workgroups per CU), the centralized framework's shapes (S = 4 L, A = L,
+// widths x 1.2, at L = 3 / 5) -> learn_kernel_c (cen.hip), anything else -> learn_kernel_g. The diagnostic build's switches, read on
+// every call (the cross-check tests flip them inside one process): AVD_LEARN_KERNEL=fast sends the reference widths to learn_kernel_t
+// (one workgroup per CU, first-layer activations in LDS); AVD_LEARN_GENERAL (any value; it wins) sends every shape to learn_kernel_g.
+static LearnKernel learn_kernel_of(const avd_mlp_layout& L, bool* switched = nullptr) {
+    const char* k = AVD_DIAG_ENV("LEARN_KERNEL");
+    const bool fast = k && !strcmp(k, "fast"), general = AVD_DIAG_ENV("LEARN_GENERAL") != nullptr;
+    if (switched) *switched = fast || general;
+    if (general) return LearnKernel::general;
+    if (reference_widths(L)) return fast ? LearnKernel::fast : LearnKernel::lean;
+    return cen_supports(&L) ? LearnKernel::cen : LearnKernel::general;
+}
+
+// The one decision of the seven entry points: the shape check, then the table. The HP twins (hp) exist for learn_kernel_l only: every
+// other cell is refused (their two refusals cover the batch size and the LDS bound that check_learn_shape adds to check_mlp_dims).
+static int choose_learner(const avd_mlp_layout* lay, bool hp, const char* who, LearnKernel* kernel) {
+    int rc = hp ? check_mlp_dims(lay, who) : check_learn_shape(lay, who);
+    if (rc) return rc;
+    bool switched = false;
+    *kernel = learn_kernel_of(*lay, &switched);
+    if (hp && switched) {  // (diagnostic build: the scalar entry would run another kernel)
+        set_error("%s: the HP twins exist for learn_kernel_l only; the diagnostic LEARN_KERNEL / LEARN_GENERAL switches select another kernel", who);
+        return AVD_E_UNSUPPORTED;
+    }
+    if (hp && !(*kernel == LearnKernel::lean && lay->B == TILE)) {
+        set_error("%s: a hyperparameter sweep runs the reference widths 256/128/48, A=1, B=64, S in {3,4} only (got %d/%d/%d, A=%d, "
+                  "B=%d, S=%d)", who, lay->H1, lay->H2, lay->Ha, lay->A, lay->B, lay->S);
+        return AVD_E_UNSUPPORTED;
+    }
+    return AVD_OK;
+}
+
+extern "C" int avd_learn_kernel(const avd_mlp_layout* lay, int hp, int* kernel) {
+    AVD_REQUIRE(kernel, "avd_learn_kernel: null");
+    LearnKernel k;
+    int rc = choose_learner(lay, hp != 0, "avd_learn_kernel", &k);
+    if (rc) return rc;
+    *kernel = (int)k;
+    return AVD_OK;
+}
+
+extern "C" int avd_learn_update_plan(const avd_mlp_layout* lay, int n_agents, int* chunk_agents, int* n_chunks, int* update_groups) {
+    AVD_REQUIRE(lay && n_agents > 0 && chunk_agents && n_chunks && update_groups, "avd_learn_update_plan: null / n_agents=%d", n_agents);
+    if (learn_kernel_of(*lay) == LearnKernel::cen) {  // (no shape check: a layout the learner would refuse is described as one launch)
+        cen_update_plan(n_agents, chunk_agents, update_groups);
+        *n_chunks = (n_agents + *chunk_agents - 1) / *chunk_agents;
+    } else {  // one launch over all agents, the update applied inside it
+        *chunk_agents = n_agents, *n_chunks = 1, *update_groups = 0;
+    }
+    return AVD_OK;
+}
+
+template <int S, bool FUSED>
+static int fast_launch_t(const LearnCall& c) {
+    constexpr int H1 = 256, H2 = 128, HA = 48;
+    const size_t lds = sizeof(float) * learn_lds_floats(*c.lay, fast::FT);
+    if (int rc = opt_in_dynamic_lds((const void*)fast::learn_kernel_t<S, H1, H2, HA, FUSED>, lds, c.who)) return rc;
+    hipLaunchKernelGGL((fast::learn_kernel_t<S, H1, H2, HA, FUSED>), dim3(c.n_agents), dim3(fast::FT), lds, c.stream, *c.lay, c.set_mod, c.theta, c.stats,
+                       c.theta_t, c.stats_t, c.s, c.a, c.r, c.s2, c.gamma, c.high, c.grads, c.losses, c.upd);
+    return check_learn_launch(c, "fast");
+}
+
+static int fast_launch(const LearnCall& c) {  // learn_kernel_t: the reference widths
+    if (c.lay->S == 4) return c.fused ? fast_launch_t<4, true>(c) : fast_launch_t<4, false>(c);
+    return c.fused ? fast_launch_t<3, true>(c) : fast_launch_t<3, false>(c);
+}
+
+template <bool FUSED>
+static int general_launch_t(const LearnCall& c) {
+    const size_t lds = sizeof(float) * gen::lds_floats(*c.lay);  // (<= 160 KiB: check_learn_shape)
+    if (int rc = opt_in_dynamic_lds((const void*)gen::learn_kernel_g<FUSED>, lds, c.who)) return rc;
+    hipLaunchKernelGGL(gen::learn_kernel_g<FUSED>, dim3(c.n_agents), dim3(NTHREADS), lds, c.stream, *c.lay, c.set_mod, c.theta, c.stats,
+                       c.theta_t, c.stats_t, c.s, c.a, c.r, c.s2, c.gamma, c.high, c.grads, c.losses, c.upd);
+    return check_learn_launch(c, "general");
+}
+static int general_launch(const LearnCall& c) { return c.fused ? general_launch_t<true>(c) : general_launch_t<false>(c); }
+
+// The learn kernel of a call. Fused: learn_kernel_l and the centralized pipeline do the whole update, learn_kernel_t / learn_kernel_g
+// the two W2 matrices (finish_update does the rest).
+static int launch_learner(LearnKernel k, const LearnCall& c) {
+    switch (k) {
+        case LearnKernel::lean: return lean_launch(c);
+        case LearnKernel::fast: return fast_launch(c);
+        case LearnKernel::cen: return c.fused ? cen_launch_update(c) : cen_launch(c);
+        default: return general_launch(c);
+    }
+}
+
+// What an update call still owes after its learn kernel: the small tensors' Adam + Polyak (everything outside the two W2 matrices)
+// where the kernel has not applied it, and the updated actor on the next states where the kernel has not evaluated it (learn_kernel_l
+// does both itself: one launch for the whole update).
+static int finish_update(LearnKernel k, const LearnCall& c) {
+    if (k == LearnKernel::lean) return AVD_OK;
+    const avd_mlp_layout* lay = c.lay;
+    if (k != LearnKernel::cen) {
+        const int a0 = lay->aW2, a1 = lay->aW2 + lay->H1 * lay->H2;
+        const int c0 = lay->actor_size + lay->cW2, c1 = c0 + (lay->H1 + lay->Ha) * lay->H2;
+        int rc = launch_adam_polyak_ranges(lay, c.n_agents, c.theta, c.upd.theta_out, c.theta_t, c.upd.m, c.upd.v, c.grads, c.upd.step,
+                                           c.upd.actor_lr, c.upd.critic_lr, c.tau, a0, a1, c0, c1, c.stream);
+        if (rc) return rc;
+    }
+    if (!c.upd.act_out) return AVD_OK;
+    return launch_rows(lay, 0, c.n_agents, 0, c.upd.theta_out, c.stats, c.upd.act_x, c.upd.act_x_stride, nullptr, c.high, c.upd.act_out,
+                       c.stream, "avd_learn_update_act_f32(actor)");
+}
+
+// what every entry point only reads: the online weights and the batch
+struct LearnBatch {
+    const float *theta, *stats, *s, *a, *r, *s2;
+};
+
+// avd_learn_f32 and avd_learn_hp_f32 (hp set; gamma unused)
+static int learn_impl(const char* who, const avd_mlp_layout* lay, int n_agents, int set_mod, const LearnBatch& b, const float* theta_t,
+                      const float* stats_t, float gamma, float high, float* grads, float* losses, const HpRef* hp, void* stream) {
+    LearnKernel k;
+    int rc = choose_learner(lay, hp != nullptr, who, &k);
+    if (rc) return rc;
+    AVD_REQUIRE(n_agents > 0 && set_mod >= 0, "%s: n_agents=%d set_mod=%d", who, n_agents, set_mod);
+    AVD_REQUIRE(b.theta && b.stats && theta_t && stats_t && b.s && b.a && b.r && b.s2 && grads, "%s: null pointer", who);
+    if (hp) AVD_REQUIRE_HP(who, hp->hp, hp->n_groups, hp->block, n_agents);
+    // (the kernels take the targets as float*: the fused forms write them; this form only reads)
+    const LearnCall c = {lay, n_agents, set_mod, b.theta, b.stats, const_cast<float*>(theta_t), const_cast<float*>(stats_t), b.s, b.a, b.r,
+                         b.s2, gamma, high, grads, losses, UpdArgs{}, 0.0, false, hp, (hipStream_t)stream, who};
+    return launch_learner(k, c);
+}
+
+extern "C" int avd_learn_f32(const avd_mlp_layout* lay, int n_agents, int set_mod, const float* theta,
+                             const float* stats, const float* theta_t, const float* stats_t, const float* s,
+                             const float* a, const float* r, const float* s2, float gamma, float high, float* grads,
+                             float* losses, void* stream) {
+    return learn_impl("avd_learn_f32", lay, n_agents, set_mod, {theta, stats, s, a, r, s2}, theta_t, stats_t, gamma, high, grads, losses,
+                      nullptr, stream);
 }
 
 // ---- hyperparameter sweeps: the lean learner's HP twins (reference widths only; the general / centralized kernels have none) ----
@@ -1689,69 +1745,44 @@ extern "C" int avd_learn_hp_f32(const avd_mlp_layout* lay, int n_agents, int set
                                 const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
                                 const float* s2, float high, float* grads, float* losses, const avd_hparams* d_hp, int n_groups,
                                 int set_block, void* stream) {
-    int rc = check_mlp_dims(lay, "avd_learn_hp_f32");
-    if (rc) return rc;
-    AVD_REQUIRE(n_agents > 0 && set_mod >= 0, "avd_learn_hp_f32: n_agents=%d set_mod=%d", n_agents, set_mod);
-    AVD_REQUIRE(theta && stats && theta_t && stats_t && s && a && r && s2 && grads, "avd_learn_hp_f32: null pointer");
-    AVD_REQUIRE_HP("avd_learn_hp_f32", d_hp, n_groups, set_block, n_agents);
-    if (!use_lean_kernel() || AVD_DIAG_ENV("LEARN_GENERAL")) {  // (diagnostic build: the scalar entry would run another kernel)
-        set_error("avd_learn_hp_f32: the HP twins exist for learn_kernel_l only; the diagnostic LEARN_KERNEL / LEARN_GENERAL switches select another kernel");
-        return AVD_E_UNSUPPORTED;
-    }
-    return lean_launch_hp(lay, false, n_agents, set_mod, theta, stats, (float*)theta_t, (float*)stats_t, s, a, r, s2, high, grads,
-                          losses, UpdArgs{}, d_hp, n_groups, set_block, stream);
+    const HpRef hr{d_hp, n_groups, set_block};
+    return learn_impl("avd_learn_hp_f32", lay, n_agents, set_mod, {theta, stats, s, a, r, s2}, theta_t, stats_t, 0.f, high, grads, losses,
+                      &hr, stream);
 }
 
-static int learn_update_hp_impl(const char* who, const avd_mlp_layout* lay, int n_agents, const float* theta, const float* stats,
-                                float* theta_out, float* theta_t, float* stats_t, float* m, float* v, const int32_t* step, const float* s,
-                                const float* a, const float* r, const float* s2, float high, float* grads_scratch, float* losses,
-                                const float* next_state, int x_stride, float* next_action, const avd_hparams* d_hp, int n_groups,
-                                int set_block, void* stream) {
-    int rc = check_mlp_dims(lay, who);
+// the scalars of an update: from the caller (avd_learn_update[_act]_f32), or all zero beside a table (the HP twins)
+struct UpdScalars {
+    float gamma, actor_lr, critic_lr;
+    double tau;
+};
+
+// avd_learn_update[_act]_f32 and avd_learn_update[_act]_hp_f32 (hp set): upd carries the slabs and the optional next-action request
+static int learn_update_impl(const char* who, const avd_mlp_layout* lay, int n_agents, const LearnBatch& b, float* theta_t, float* stats_t,
+                             UpdArgs upd, UpdScalars sc, float high, float* grads_scratch, float* losses, const HpRef* hp, void* stream) {
+    LearnKernel k;
+    int rc = choose_learner(lay, hp != nullptr, who, &k);
     if (rc) return rc;
     AVD_REQUIRE(n_agents > 0, "%s: n_agents=%d", who, n_agents);
-    AVD_REQUIRE(theta && stats && theta_out && theta_t && stats_t && m && v && step && s && a && r && s2 && grads_scratch,
+    AVD_REQUIRE(b.theta && b.stats && upd.theta_out && theta_t && stats_t && upd.m && upd.v && upd.step && b.s && b.a && b.r && b.s2 &&
+                    grads_scratch,
                 "%s: null pointer", who);
-    AVD_REQUIRE(theta_out != theta, "%s: theta_out must not alias theta (every pass reads pre-update weights)", who);
-    AVD_REQUIRE_HP(who, d_hp, n_groups, set_block, n_agents);
-    if (!use_lean_kernel() || AVD_DIAG_ENV("LEARN_GENERAL")) {  // (diagnostic build: the scalar entry would run another kernel)
-        set_error("%s: the HP twins exist for learn_kernel_l only; the diagnostic LEARN_KERNEL / LEARN_GENERAL switches select another kernel", who);
-        return AVD_E_UNSUPPORTED;
-    }
-    // the step sizes and tau of UpdArgs come from the table inside the kernel
-    UpdArgs upd = {theta_out, m, v, step, 0.f, 0.f, 0.f, 0.f, next_state, x_stride, next_action};
-    return lean_launch_hp(lay, true, n_agents, 0, theta, stats, theta_t, stats_t, s, a, r, s2, high, grads_scratch, losses, upd, d_hp,
-                          n_groups, set_block, stream);
+    AVD_REQUIRE(upd.theta_out != b.theta, "%s: theta_out must not alias theta (every pass reads pre-update weights)", who);
+    if (hp) AVD_REQUIRE_HP(who, hp->hp, hp->n_groups, hp->block, n_agents);
+    if (!hp)  // (the HP twins: the step sizes and tau come from the table inside the kernel)
+        upd.actor_lr = sc.actor_lr, upd.critic_lr = sc.critic_lr, upd.tau = (float)sc.tau, upd.omt = (float)(1.0 - sc.tau);
+    const LearnCall c = {lay, n_agents, 0, b.theta, b.stats, theta_t, stats_t, b.s, b.a, b.r, b.s2, sc.gamma, high, grads_scratch, losses, upd,
+                         sc.tau, true, hp, (hipStream_t)stream, who};
+    rc = launch_learner(k, c);
+    return rc ? rc : finish_update(k, c);
 }
 
-extern "C" int avd_learn_update_hp_f32(const avd_mlp_layout* lay, int n_agents, const float* theta, const float* stats, float* theta_out,
-                                       float* theta_t, float* stats_t, float* m, float* v, const int32_t* step, const float* s,
-                                       const float* a, const float* r, const float* s2, float high, float* grads_scratch, float* losses,
-                                       const avd_hparams* d_hp, int n_groups, int set_block, void* stream) {
-    return learn_update_hp_impl("avd_learn_update_hp_f32", lay, n_agents, theta, stats, theta_out, theta_t, stats_t, m, v, step, s, a, r,
-                                s2, high, grads_scratch, losses, nullptr, 0, nullptr, d_hp, n_groups, set_block, stream);
-}
-
-extern "C" int avd_learn_update_act_hp_f32(const avd_mlp_layout* lay, int n_agents, const float* theta, const float* stats,
-                                           float* theta_out, float* theta_t, float* stats_t, float* m, float* v, const int32_t* step,
-                                           const float* s, const float* a, const float* r, const float* s2, float high,
-                                           float* grads_scratch, float* losses, const float* next_state, int x_stride,
-                                           float* next_action, const avd_hparams* d_hp, int n_groups, int set_block, void* stream) {
-    AVD_REQUIRE(next_state && next_action && lay && x_stride >= lay->S, "avd_learn_update_act_hp_f32: next_state / x_stride");
-    return learn_update_hp_impl("avd_learn_update_act_hp_f32", lay, n_agents, theta, stats, theta_out, theta_t, stats_t, m, v, step, s,
-                                a, r, s2, high, grads_scratch, losses, next_state, x_stride, next_action, d_hp, n_groups, set_block,
-                                stream);
-}
-
-extern "C" int avd_learn_update_plan(const avd_mlp_layout* lay, int n_agents, int* chunk_agents, int* n_chunks, int* update_groups) {
-    AVD_REQUIRE(lay && n_agents > 0 && chunk_agents && n_chunks && update_groups, "avd_learn_update_plan: null / n_agents=%d", n_agents);
-    if (cen_supports(lay) && !AVD_DIAG_ENV("LEARN_GENERAL")) {
-        cen_update_plan(n_agents, chunk_agents, update_groups);
-        *n_chunks = (n_agents + *chunk_agents - 1) / *chunk_agents;
-    } else {  // one launch over all agents, the update applied inside it
-        *chunk_agents = n_agents, *n_chunks = 1, *update_groups = 0;
-    }
-    return AVD_OK;
+extern "C" int avd_learn_update_f32(const avd_mlp_layout* lay, int n_agents, const float* theta, const float* stats,
+                                    float* theta_out, float* theta_t, float* stats_t, float* m, float* v,
+                                    const int32_t* step, const float* s, const float* a, const float* r,
+                                    const float* s2, float gamma, float high, float actor_lr, float critic_lr,
+                                    double tau, float* grads_scratch, float* losses, void* stream) {
+    return learn_update_impl("avd_learn_update_f32", lay, n_agents, {theta, stats, s, a, r, s2}, theta_t, stats_t,
+                             UpdArgs{theta_out, m, v, step}, {gamma, actor_lr, critic_lr, tau}, high, grads_scratch, losses, nullptr, stream);
 }
 
 extern "C" int avd_learn_update_act_f32(const avd_mlp_layout* lay, int n_agents, const float* theta, const float* stats,
@@ -1761,71 +1792,28 @@ extern "C" int avd_learn_update_act_f32(const avd_mlp_layout* lay, int n_agents,
                                         double tau, float* grads_scratch, float* losses, const float* next_state,
                                         int x_stride, float* next_action, void* stream) {
     AVD_REQUIRE(next_state && next_action && lay && x_stride >= lay->S, "avd_learn_update_act_f32: next_state / x_stride");
-    return learn_update_impl(lay, n_agents, theta, stats, theta_out, theta_t, stats_t, m, v, step, s, a, r, s2, gamma, high,
-                             actor_lr, critic_lr, tau, grads_scratch, losses, next_state, x_stride, next_action, stream);
+    return learn_update_impl("avd_learn_update_f32", lay, n_agents, {theta, stats, s, a, r, s2}, theta_t, stats_t,
+                             UpdArgs{theta_out, m, v, step, 0.f, 0.f, 0.f, 0.f, next_state, x_stride, next_action},
+                             {gamma, actor_lr, critic_lr, tau}, high, grads_scratch, losses, nullptr, stream);
 }
 
-static int learn_update_impl(const avd_mlp_layout* lay, int n_agents, const float* theta, const float* stats,
-                             float* theta_out, float* theta_t, float* stats_t, float* m, float* v, const int32_t* step,
-                             const float* s, const float* a, const float* r, const float* s2, float gamma, float high,
-                             float actor_lr, float critic_lr, double tau, float* grads_scratch, float* losses,
-                             const float* next_state, int x_stride, float* next_action, void* stream) {
-    int rc = check_learn_shape(lay, "avd_learn_update_f32");
-    if (rc) return rc;
-    AVD_REQUIRE(n_agents > 0, "avd_learn_update_f32: n_agents=%d", n_agents);
-    AVD_REQUIRE(theta && stats && theta_out && theta_t && stats_t && m && v && step && s && a && r && s2 && grads_scratch,
-                "avd_learn_update_f32: null pointer");
-    AVD_REQUIRE(theta_out != theta, "avd_learn_update_f32: theta_out must not alias theta (every pass reads pre-update weights)");
-    const int a0 = lay->aW2, a1 = lay->aW2 + lay->H1 * lay->H2;  // the two W2 matrices: updated inside the learn kernels
-    const int c0 = lay->actor_size + lay->cW2, c1 = c0 + (lay->H1 + lay->Ha) * lay->H2;
-    if (!(lay->A == 1 && lay->H1 == 256 && lay->H2 == 128 && lay->Ha == 48 && (lay->S == 3 || lay->S == 4)) ||
-        AVD_DIAG_ENV("LEARN_GENERAL")) {
-        // any other shape the general kernel serves (centralized framework, non-default widths): its fused form
-        const size_t lds = sizeof(float) * gen::lds_floats(*lay);  // (<= 160 KiB: check_learn_shape)
-        hipError_t e = hipFuncSetAttribute((const void*)gen::learn_kernel_g<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) {
-            set_error("avd_learn_update_f32: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
-            return AVD_E_LAUNCH;
-        }
-        const UpdArgs updg = {theta_out, m, v, step, actor_lr, critic_lr, (float)tau, (float)(1.0 - tau), nullptr, 0, nullptr};
-        if (cen_supports(lay) && !AVD_DIAG_ENV("LEARN_GENERAL")) {
-            // the centralized shapes: chunked learn + whole-row Adam / Polyak passes on two streams (cen.hip)
-            rc = cen_launch_update(lay, n_agents, theta, stats, theta_out, theta_t, stats_t, m, v, step, s, a, r, s2, gamma, high, actor_lr,
-                                   critic_lr, tau, grads_scratch, losses, stream);
-            if (rc || !next_action) return rc;
-            return launch_rows(lay, 0, n_agents, 0, theta_out, stats, next_state, x_stride, nullptr, high, next_action, stream,
-                               "avd_learn_update_act_f32(actor)");
-        }
-        hipLaunchKernelGGL(gen::learn_kernel_g<true>, dim3(n_agents), dim3(NTHREADS), lds, (hipStream_t)stream, *lay, 0, theta,
-                           stats, theta_t, stats_t, s, a, r, s2, gamma, high, grads_scratch, losses, updg);
-        rc = check_launch("avd_learn_update_f32 (general)");
-        if (rc) return rc;
-        rc = launch_adam_polyak_ranges(lay, n_agents, theta, theta_out, theta_t, m, v, grads_scratch, step, actor_lr,
-                                       critic_lr, tau, a0, a1, c0, c1, stream);
-        if (rc || !next_action) return rc;
-        return launch_rows(lay, 0, n_agents, 0, theta_out, stats, next_state, x_stride, nullptr, high, next_action, stream,
-                           "avd_learn_update_act_f32(actor)");
-    }
-    UpdArgs upd = {theta_out, m, v, step, actor_lr, critic_lr, (float)tau, (float)(1.0 - tau), nullptr, 0, nullptr};
-    if (use_lean_kernel()) {
-        // learn_kernel_l applies the small tensors' update itself and, on request, evaluates the updated actor on the
-        // agent's next state while its weights are still in L2: one launch for the whole update
-        upd.act_x = next_state, upd.act_x_stride = x_stride, upd.act_out = next_action;
-        return lean_launch(lay, true, n_agents, 0, theta, stats, theta_t, stats_t, s, a, r, s2, gamma, high, grads_scratch,
-                           losses, upd, stream);
-    }
-    if (lay->S == 4)
-        rc = fast::launch<4, 256, 128, 48, true>(lay, n_agents, 0, theta, stats, theta_t, stats_t, s, a, r, s2, gamma,
-                                                 high, grads_scratch, losses, upd, stream);
-    else
-        rc = fast::launch<3, 256, 128, 48, true>(lay, n_agents, 0, theta, stats, theta_t, stats_t, s, a, r, s2, gamma,
-                                                 high, grads_scratch, losses, upd, stream);
-    if (rc) return rc;
-    // the small tensors: everything outside the two W2 matrices (which the learn kernel has already updated)
-    rc = launch_adam_polyak_ranges(lay, n_agents, theta, theta_out, theta_t, m, v, grads_scratch, step, actor_lr, critic_lr,
-                                   tau, a0, a1, c0, c1, stream);
-    if (rc || !next_action) return rc;
-    return launch_rows(lay, 0, n_agents, 0, theta_out, stats, next_state, x_stride, nullptr, high, next_action, stream,
-                       "avd_learn_update_act_f32(actor)");
+extern "C" int avd_learn_update_hp_f32(const avd_mlp_layout* lay, int n_agents, const float* theta, const float* stats, float* theta_out,
+                                       float* theta_t, float* stats_t, float* m, float* v, const int32_t* step, const float* s,
+                                       const float* a, const float* r, const float* s2, float high, float* grads_scratch, float* losses,
+                                       const avd_hparams* d_hp, int n_groups, int set_block, void* stream) {
+    const HpRef hr{d_hp, n_groups, set_block};
+    return learn_update_impl("avd_learn_update_hp_f32", lay, n_agents, {theta, stats, s, a, r, s2}, theta_t, stats_t,
+                             UpdArgs{theta_out, m, v, step}, {}, high, grads_scratch, losses, &hr, stream);
+}
+
+extern "C" int avd_learn_update_act_hp_f32(const avd_mlp_layout* lay, int n_agents, const float* theta, const float* stats,
+                                           float* theta_out, float* theta_t, float* stats_t, float* m, float* v, const int32_t* step,
+                                           const float* s, const float* a, const float* r, const float* s2, float high,
+                                           float* grads_scratch, float* losses, const float* next_state, int x_stride,
+                                           float* next_action, const avd_hparams* d_hp, int n_groups, int set_block, void* stream) {
+    AVD_REQUIRE(next_state && next_action && lay && x_stride >= lay->S, "avd_learn_update_act_hp_f32: next_state / x_stride");
+    const HpRef hr{d_hp, n_groups, set_block};
+    return learn_update_impl("avd_learn_update_act_hp_f32", lay, n_agents, {theta, stats, s, a, r, s2}, theta_t, stats_t,
+                             UpdArgs{theta_out, m, v, step, 0.f, 0.f, 0.f, 0.f, next_state, x_stride, next_action}, {}, high, grads_scratch,
+                             losses, &hr, stream);
 }

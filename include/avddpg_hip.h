@@ -205,6 +205,17 @@ int avd_learn_f32(const avd_mlp_layout* lay, int n_agents, int set_mod, const fl
  * general kernel that does not fit the 160 KiB of LDS). For callers that want to refuse a configuration when it is built. */
 int avd_learn_check_shape(const avd_mlp_layout* lay);
 
+/* Which kernel avd_learn_f32 / avd_learn_update_f32 / avd_learn_update_act_f32 (hp = 0) or their *_hp_* twins (hp != 0) run for this
+ * shape, decided on the host by the function those entry points call, without any HIP call: *kernel = one of AVD_LEARN_*. A shape or
+ * a combination they refuse: their status and message (avd_learn_check_shape's; the HP twins serve the reference widths
+ * 256 / 128 / 48, A = 1, S in {3, 4} only). The product library reads no switch; the diagnostic build's AVD_LEARN_KERNEL=fast and
+ * AVD_LEARN_GENERAL are read on every call. The counterpart of avd_learn_shared_path for the per-agent learner. */
+#define AVD_LEARN_LEAN 0    /* learn_kernel_l (lean.hip): the reference widths, two workgroups per CU */
+#define AVD_LEARN_FAST 1    /* learn_kernel_t (mlp.hip): the reference widths, one workgroup per CU (diagnostic build only) */
+#define AVD_LEARN_CEN 2     /* learn_kernel_c (cen.hip): the centralized framework at L = 3 / 5 */
+#define AVD_LEARN_GENERAL 3 /* learn_kernel_g (mlp.hip): every other shape */
+int avd_learn_kernel(const avd_mlp_layout* lay, int hp, int* kernel);
+
 /* Adam x2 (critic then actor; tf.keras.optimizers.Adam defaults, workers/trainer.py:138-139, 348-349)
  * followed by ddpgagent.update_target over ALL weights incl. BN stats (agent/ddpgagent.py:31-55;
  * workers/trainer.py:352-356), fused per element, for n_sets weight sets.

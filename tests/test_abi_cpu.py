@@ -368,3 +368,165 @@ def test_diagnostic_switches_clear_a_path_flag_and_what_rests_on_it(switch, clea
         env.pop("AVDDPG_HIP_LIB")
         p = subprocess.run([sys.executable, "-c", _PATH_QUERY], env=env, capture_output=True, text=True, timeout=120)
         assert p.returncode == 0 and int(p.stdout.split("flags")[1]) == (1 << len(_PATH_BITS)) - 1, p.stderr[-2000:]
+
+
+# ---- the per-agent exact-f32 learner: which kernel a layout gets, and what its entry points refuse on the host -------------------
+_LEARN_KERNELS = ("lean", "fast", "cen", "general")  # AVD_LEARN_* of include/avddpg_hip.h, 0 upwards
+_REF3, _REF4 = (3, 1, 256, 128, 48), (4, 1, 256, 128, 48)
+_CEN3, _CEN5 = (12, 3, 320, 160, 64), (20, 5, 320, 160, 64)
+_GEN = (5, 2, 128, 64, 32)
+_HP_TWINS = "the HP twins exist for learn_kernel_l only; the diagnostic LEARN_KERNEL / LEARN_GENERAL switches select another kernel"
+_HP_WIDTHS = r"a hyperparameter sweep runs the reference widths 256/128/48, A=1, B=64, S in \{3,4\} only \(got %s\)"
+
+
+def _learn_kernel(dims, hp=0, B=64):
+    lay = _hip.make_layout(*dims, B)
+    k = ctypes.c_int(-1)
+    _hip.call("avd_learn_kernel", ctypes.byref(lay), hp, ctypes.byref(k))
+    return _LEARN_KERNELS[k.value]
+
+
+def test_learn_kernel_table_of_the_product_library():
+    """avd_learn_kernel: the kernel avd_learn_f32 / avd_learn_update*_f32 run for a layout, decided on the host by the choose_learner the
+    entry points call (csrc/mlp.hip), no HIP call. The product library reads no switch: reference widths -> learn_kernel_l, the
+    centralized shapes -> learn_kernel_c, anything else -> learn_kernel_g; the HP twins serve the reference widths only."""
+    assert [_learn_kernel(d) for d in (_REF3, _REF4, _CEN3, _CEN5, _GEN)] == ["lean", "lean", "cen", "cen", "general"]
+    # next to the table's rows: one width or the action count off the reference / centralized shapes
+    assert _learn_kernel((4, 1, 256, 128, 64)) == "general" and _learn_kernel((5, 1, 256, 128, 48)) == "general"
+    assert _learn_kernel((16, 4, 320, 160, 64)) == "general" and _learn_kernel((4, 2, 256, 128, 48)) == "general"
+    assert _learn_kernel(_REF3, hp=1) == "lean" and _learn_kernel(_REF4, hp=1) == "lean"
+    for dims, got in ((_CEN5, "320/160/64, A=5, B=64, S=20"), (_GEN, "128/64/32, A=2, B=64, S=5")):
+        with pytest.raises(_hip.AvdError, match=r"failed \(-3\): avd_learn_kernel: " + _HP_WIDTHS % got):
+            _learn_kernel(dims, hp=1)
+    with pytest.raises(_hip.AvdError, match=r"failed \(-3\): avd_learn_kernel: " + _HP_WIDTHS % "256/128/48, A=1, B=32, S=4"):
+        _learn_kernel(_REF4, hp=1, B=32)
+    # the shape check comes with it
+    with pytest.raises(_hip.AvdError, match=r"failed \(-3\): avd_learn_kernel: batch_size=32; the tile kernels implement B == 64"):
+        _learn_kernel(_REF4, B=32)
+    with pytest.raises(_hip.AvdError, match=r"failed \(-3\): avd_learn_kernel: .*need 164768 B of LDS"):
+        _learn_kernel((24, 6, 320, 160, 64))
+    with pytest.raises(_hip.AvdError, match=r"failed \(-1\): avd_learn_kernel: null"):
+        _hip.call("avd_learn_kernel", ctypes.byref(_hip.make_layout(*_REF4, 64)), 0, None)
+
+
+def test_learn_kernel_switches_of_the_diagnostic_library_take_effect_inside_one_process(monkeypatch):
+    """The diagnostic library's AVD_LEARN_KERNEL=fast and AVD_LEARN_GENERAL (any value, and it wins over `fast`), read on EVERY call:
+    tests/test_gpu_mlp.py and tests/test_gpu_trainer.py set and clear them inside one process. The centralized shapes have no `fast`
+    form; with a switch set the HP twins refuse, before they look at the widths. The product library reads neither."""
+    assert os.path.exists(_hip.DIAG_LIB_PATH), "the diagnostic library is part of build()"
+    shapes = (_REF3, _REF4, _CEN3, _CEN5, _GEN)
+    table = {(): ["lean", "lean", "cen", "cen", "general"], ("KERNEL",): ["fast", "fast", "cen", "cen", "general"],
+             ("GENERAL",): ["general"] * 5, ("KERNEL", "GENERAL"): ["general"] * 5}
+    monkeypatch.delenv("AVD_LEARN_KERNEL", raising=False)
+    monkeypatch.delenv("AVD_LEARN_GENERAL", raising=False)
+    with _hip.diag_library():
+        for setting in ((), ("KERNEL",), ("GENERAL",), ("KERNEL", "GENERAL"), ("KERNEL",), ()):  # set, and cleared again
+            for name, value in (("KERNEL", "fast"), ("GENERAL", "0")):
+                if name in setting:
+                    monkeypatch.setenv("AVD_LEARN_" + name, value)
+                else:
+                    monkeypatch.delenv("AVD_LEARN_" + name, raising=False)
+            assert [_learn_kernel(d) for d in shapes] == table[setting], setting
+            if setting:
+                for dims in (_REF4, _GEN):
+                    with pytest.raises(_hip.AvdError, match=r"failed \(-3\): avd_learn_kernel: " + _HP_TWINS):
+                        _learn_kernel(dims, hp=1)
+            else:
+                assert _learn_kernel(_REF4, hp=1) == "lean"
+        monkeypatch.setenv("AVD_LEARN_KERNEL", "lean")  # any other value: the default
+        assert _learn_kernel(_REF4) == "lean" and _learn_kernel(_REF4, hp=1) == "lean"
+        monkeypatch.setenv("AVD_LEARN_KERNEL", "fast")
+        monkeypatch.setenv("AVD_LEARN_GENERAL", "1")
+    assert [_learn_kernel(d) for d in shapes] == table[()]  # the product library, both switches still set
+
+
+_BOGUS = 0x1000  # non-null "device pointers" that nothing reads (one per argument): every call below is refused on the host
+_SLABS = ("theta", "stats", "theta_out", "theta_t", "stats_t", "m", "v", "step", "s", "a", "r", "s2")
+
+
+def _learn_call(entry, lay, n=2, set_mod=0, x_stride=None, hp=(1, 1), **ptrs):
+    """Call one of the six learn entry points with non-null pointers everywhere but where `ptrs` says otherwise (name=None)."""
+    p = {k: ctypes.c_void_p(_BOGUS * (i + 1)) for i, k in enumerate(_SLABS + ("grads", "losses", "next_state", "next_action", "d_hp"))}
+    p.update(ptrs)
+    layp = None if lay is None else ctypes.byref(lay)
+    update, sweep, act = "update" in entry, "_hp_" in entry, "_act_" in entry
+    args = [layp, n] + ([] if update else [set_mod]) + [p[k] for k in _SLABS if update or k not in ("theta_out", "m", "v", "step")]
+    args += [2.5] if sweep else ([0.99, 2.5, 1e-4, 1e-3, 0.005] if update else [0.99, 2.5])
+    args += [p["grads"], p["losses"]]
+    if act:
+        args += [p["next_state"], (lay.S if lay is not None else 4) if x_stride is None else x_stride, p["next_action"]]
+    if sweep:
+        args += [p["d_hp"], *hp]
+    _hip.call(entry, *args, None)
+
+
+# entry point -> the name its messages carry (the scalar update entries share one)
+_LEARN_ENTRIES = {"avd_learn_f32": "avd_learn_f32", "avd_learn_update_f32": "avd_learn_update_f32",
+                  "avd_learn_update_act_f32": "avd_learn_update_f32", "avd_learn_hp_f32": "avd_learn_hp_f32",
+                  "avd_learn_update_hp_f32": "avd_learn_update_hp_f32", "avd_learn_update_act_hp_f32": "avd_learn_update_act_hp_f32"}
+
+
+@pytest.mark.parametrize("entry", sorted(_LEARN_ENTRIES))
+def test_learn_entry_points_refuse_on_the_host_before_any_hip_call(entry):
+    """Everything the six learn entry points refuse before their first HIP call, one fault per call, with status and message: the
+    contract the entry points keep whichever way their host code is arranged (no GPU here: a call that got past its checks would
+    fail with a HIP error instead)."""
+    who, update, sweep, act = _LEARN_ENTRIES[entry], "update" in entry, "_hp_" in entry, "_act_" in entry
+    ref, refuse = _hip.make_layout(*_REF4, 64), lambda code, msg: pytest.raises(_hip.AvdError, match=rf"failed \({code}\): {msg}")
+    with refuse(-1, f"{entry}: next_state / x_stride" if act else f"{who}: null layout"):
+        _learn_call(entry, None)
+    with refuse(-1, f"{who}: n_agents=0"):
+        _learn_call(entry, ref, n=0)
+    with refuse(-1, f"{who}: n_agents=-3"):
+        _learn_call(entry, ref, n=-3)
+    if not update:
+        with refuse(-1, f"{who}: n_agents=2 set_mod=-1"):
+            _learn_call(entry, ref, set_mod=-1)
+    for name in _SLABS + ("grads",):
+        if update or name not in ("theta_out", "m", "v", "step"):
+            with refuse(-1, f"{who}: null pointer"):
+                _learn_call(entry, ref, **{name: None})
+    if update:
+        with refuse(-1, f"{who}: theta_out must not alias theta"):
+            _learn_call(entry, ref, theta=ctypes.c_void_p(0x2000), theta_out=ctypes.c_void_p(0x2000))
+    if act:
+        for fault in (dict(x_stride=3), dict(next_state=None), dict(next_action=None)):
+            with refuse(-1, f"{entry}: next_state / x_stride"):
+                _learn_call(entry, ref, **fault)
+    if sweep:
+        for fault in (dict(d_hp=None), dict(hp=(0, 1)), dict(hp=(1, 0)), dict(n=6, hp=(2, 2))):
+            with refuse(-1, rf"{who}: d_hp=.* \(the count must be a multiple of n_groups x set_block\)"):
+                _learn_call(entry, ref, **fault)
+    # shapes
+    with refuse(-3, rf"{who}: need S <= 64, A <= 16, H1 and Ha multiples of 16, H2 a multiple of 32 and <= 256 \(got S=4 A=1 H1=256 H2=288 "
+                    r"Ha=48\); pad the widths with zero units"):
+        _learn_call(entry, _hip.make_layout(4, 1, 256, 288, 48, 64))
+    with refuse(-3, rf"{who}: need S <= 64.*got S=12 A=3 H1=307 H2=153 Ha=57"):
+        _learn_call(entry, _hip.make_layout(12, 3, 307, 153, 57, 64))
+    sweep_who = "avd_learn_update(_act)?_hp_f32" if act else who  # (the act twin's width refusal has carried either name)
+    with refuse(-3, f"{sweep_who}: " + _HP_WIDTHS % "256/128/48, A=1, B=32, S=4" if sweep else
+                    f"{who}: batch_size=32; the tile kernels implement B == 64"):
+        _learn_call(entry, _hip.make_layout(*_REF4, 32))
+    with refuse(-3, f"{sweep_who}: " + _HP_WIDTHS % "320/160/64, A=6, B=64, S=24" if sweep else
+                    rf"{who}: S=24 A=6 H1=320 H2=160 Ha=64 need 164768 B of LDS per 64-row tile \(> 160 KiB\)"):
+        _learn_call(entry, _hip.make_layout(24, 6, 320, 160, 64, 64))
+    if sweep:  # the HP twins exist at the reference widths only
+        for dims, got in ((_GEN, "128/64/32, A=2, B=64, S=5"), (_CEN3, "320/160/64, A=3, B=64, S=12"), ((5, 1, 256, 128, 48), "256/128/48, A=1, B=64, S=5")):
+            with refuse(-3, f"{sweep_who}: " + _HP_WIDTHS % got):
+                _learn_call(entry, _hip.make_layout(*dims, 64))
+
+
+def test_learn_update_plan_refuses_null_arguments_and_runs_no_shape_check():
+    """avd_learn_update_plan, the seventh entry of the per-agent learner: null arguments and n_agents <= 0 are refused; a layout the
+    learner itself would refuse is still described (one launch)."""
+    import ctypes as C
+
+    lay, out = _hip.make_layout(*_CEN5, 64), [C.c_int(0) for _ in range(3)]
+    for args in ((None, 8, *map(C.byref, out)), (C.byref(lay), 8, None, C.byref(out[1]), C.byref(out[2])),
+                 (C.byref(lay), 8, C.byref(out[0]), None, C.byref(out[2])), (C.byref(lay), 8, C.byref(out[0]), C.byref(out[1]), None),
+                 (C.byref(lay), -1, *map(C.byref, out))):
+        with pytest.raises(_hip.AvdError, match=rf"failed \(-1\): avd_learn_update_plan: null / n_agents={args[1]}"):
+            _hip.call("avd_learn_update_plan", *args)
+    for dims, B in (((24, 6, 320, 160, 64), 64), (_CEN5, 32), ((4, 1, 256, 288, 48), 64)):
+        _hip.call("avd_learn_update_plan", C.byref(_hip.make_layout(*dims, B)), 100, *map(C.byref, out))
+        assert [o.value for o in out] == [100, 1, 0]
