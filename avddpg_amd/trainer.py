@@ -354,17 +354,21 @@ class VecTrainer:
         self.ep_reward.zero_()
         self.ep_step = 0
 
+    def _act_wide_shared(self, seen):
+        """actor(what the agents see) -> actor_out for wide shared sets: every agent re-reading its set's megabytes of weights is the
+        wrong shape; one GEMM chain per set instead (bf16 operands, like this engine's learner)."""
+        P, M = self.P, self.M
+        sm = seen.view(self.Pf, self.Mf, 4)[..., :self.S].transpose(0, 1).contiguous()  # set-major [M, P, S]
+        o = self.agents.actor_shared(sm, P * M)
+        self.actor_out.copy_(o.transpose(0, 1).reshape(P * M, 1))
+
     def _act(self):
         """advance_environment (trainer.py:282-302): actor -> OU noise -> clip, leader exog, env step."""
         conf, P, M = self.conf, self.P, self.M
         seen = self.env.agent_states()  # env.x, or what the agents observe of it (train_disturb)
         states = seen.view(P * M, self.x_stride)
         if self.shared and self.shared_engine == "batched" and self.agents.lay.H2 > 256:
-            # wide shared sets: every agent re-reading its set's megabytes of weights is the wrong shape; one GEMM
-            # chain per set instead (bf16 operands, like this engine's learner)
-            sm = seen.view(self.Pf, self.Mf, 4)[..., :self.S].transpose(0, 1).contiguous()  # set-major [M, P, S]
-            o = self.agents.actor_shared(sm, P * M)
-            self.actor_out.copy_(o.transpose(0, 1).reshape(P * M, 1))
+            self._act_wide_shared(seen)
         elif self._act_ready:
             # the last fused update left actor(states) in actor_out; recompute only if the episode ended since (any platoon
             # terminal resets ALL platoons, :268-269 -- the flag of the previous step is still set at this point)

@@ -484,3 +484,170 @@ def fset_weighted_reference(name, cus):
         emu = weighted_learn(case, nets, batch, k, w, round_bf16, placement=case.placement)
         out[k] = (ref, emu, tolerances([ref], [emu]))
     return w, out
+
+
+# ---- acting with shared sets (csrc/wide.hip, avd_actor_forward_shared_bf16): the forward cases of tests/test_gpu_act_shared.py ----
+# The layer-wise chain l1_fwd_kernel<S> -> launch_gemm<EpiFwd> -> tanh_rows_kernel on every row of every set, against
+# actor_forward(.., fold=True): the float64 reference (mm = identity) and the bf16-operand oracle (both operands of every product
+# rounded; the kernel rounds the STORED layer-2 activation and keeps cf = inv2 * W3 unrounded -- FACTOR is the margin for that).
+#
+# The rule (fwd_tolerances / fwd_violations), from the two oracles alone, errors relative to `high`:
+#     e_max = max  over all rows and sets of |bf16oracle - ref| / high,     e_rms = the root mean square of the same
+#     pass <=> max error <= max(FWD_TOL, FACTOR * e_max)   AND   rms error <= max(FWD_TOL, FACTOR * e_rms)
+# FWD_TOL = 2e-5: the f32 accumulation-order floor of tests/test_gpu_mlp.py. The rms half is what bites on ONE wrong row tile (the
+# maximum is set by the worst of several hundred rows). FWD_CAP: the budget of the test this one sits beside
+# (tests/test_gpu_wide.py::test_shared_actor_forward_matches_per_agent_rows_kernel) -- no case may be looser.
+FWD_TOL, FWD_CAP, HIGH = 2e-5, 2e-2, 2.5
+FwdCase = namedtuple("FwdCase", "name widths S n_sets P seed std reaches")
+# States: normal, float32, RandomState(seed + 1000) per case. NOT the std 1.5 of the other tests: at 1.5 the perturbed actors' outputs
+# spread by 0.005 .. 0.02 high over a set's rows in every case (the biases dominate the first layer), five to twenty times short of the
+# 0.1 high of fwd_inputs_bite -- a row holding its neighbour's output would pass. The cap held at 1.5 (tolerances 1.7e-3 .. 1.1e-2);
+# the spread did not. The spread grows with the state scale, the bf16-oracle error more slowly, so each case takes the std and the
+# seed (weights and states) below, found by a search over std in {12, 16, 24, 32} and seed + 10 j on the two oracles alone:
+# every set's spread >= 0.1 high AND FACTOR * e_max <= FWD_CAP -- and, for one_row and past_tile, whose last row tile is ONE row, that
+# row's output moves by more than the tolerance whichever 64-wide K block of layer 2 is left out (the planted defects of
+# tests/test_bf16_oracle_cpu.py, which asserts all of this and prints the numbers).
+FWD_CASES = [
+    FwdCase("t256_ragged", (1024, 1024, 48), 4, 2, 700, 61, 24.0, "256-tile kernel, three row tiles, the last with 188 rows; Np = 768 > Ns"),
+    FwdCase("t128_511", (1024, 1024, 48), 4, 2, 511, 72, 12.0, "one row short of the 256-tile condition: 128-tile kernel, K = 1024, ragged fourth tile"),
+    FwdCase("one_row", (512, 320, 48), 4, 3, 1, 83, 24.0, "a set of one row; the output offset k * Ns with Ns = 1"),
+    FwdCase("past_tile", (512, 320, 48), 4, 3, 129, 34, 32.0, "one row in the second 128-row tile; H2n = 512 > H2"),
+    FwdCase("modelA", (256, 512, 48), 3, 2, 600, 55, 24.0, "l1_fwd_kernel<3>, 256-tile kernel at K = 256"),
+    FwdCase("k64_t256", (64, 512, 16), 4, 2, 600, 56, 24.0, "256-tile kernel with two K steps under three stages"),
+    FwdCase("k64_t128", (64, 64, 16), 4, 1, 130, 37, 24.0, "128-tile kernel with a single K step; one set"),
+]
+# VecTrainer's acting path for wide shared sets (_act_wide_shared: the set-major transposition around actor_shared), 8 platoons of 5
+# vehicles at 1024/1024: n_sets = pl_size, P = num_platoons, Model B (S = 4) and Model A (S = 3). Std and seeds found as above on these
+# 40 rows; the weights are loaded into the trainer's group, the states written into the environment ([P, M, 4]: trainer_env_states).
+TRAINER_CASES = [
+    FwdCase("trainer_modelB", (1024, 1024, 48), 4, 5, 8, 131, 24.0, "set-major view of env.x, actor_shared, copy back; 128-tile kernel, 8 rows"),
+    FwdCase("trainer_modelA", (1024, 1024, 48), 3, 5, 8, 132, 24.0, "the same reading three of an agent's four floats"),
+]
+FWD_CASE = {c.name: c for c in FWD_CASES + TRAINER_CASES}
+FwdRef = namedtuple("FwdRef", "x ref emu e_max e_rms tol_max tol_rms c0 active1 active2")
+
+
+def fwd_conf_kw(case):
+    H1, H2, Ha = case.widths
+    return dict(actor_layer1_size=H1, actor_layer2_size=H2, critic_layer1_size=H1, critic_layer2_size=H2, critic_act_layer_size=Ha)
+
+
+def fwd_tile(case):
+    """Rows per tile of the layer-2 GEMM, as launch_gemm (csrc/wide.hip) chooses: 256 from 512 rows and 512 columns upward
+    (K is a multiple of 32 at every width the library takes), else 128."""
+    return 256 if case.P >= 512 and case.widths[1] >= 512 else 128
+
+
+def fwd_last_tile(case):
+    """[lo, hi): the rows of a set's last row tile."""
+    t = fwd_tile(case)
+    return (case.P - 1) // t * t, case.P
+
+
+def fwd_states(case):
+    """[n_sets, P, S] float32, set-major and tightly packed: what AgentGroup.actor_shared takes."""
+    return np.random.RandomState(case.seed + 1000).normal(0, case.std, size=(case.n_sets, case.P, case.S)).astype(np.float32)
+
+
+def fwd_actor(case, k):
+    """Set k's actor in float64, Keras weight order (the slabs the GPU test loads: perturbed_slabs)."""
+    from avddpg_amd import params
+
+    grp, th, st, _, _ = perturbed_slabs(case.n_sets, case.S, case.seed, **fwd_conf_kw(case))
+    return [w.astype(np.float64) for w in params.unpack(grp.lay, th[k], st[k], "actor", dims=grp.dims)]
+
+
+def fwd_rows(w, x, drop_k=None):
+    """tanh(.) * HIGH [rows] of the float64 reference in wide.hip's placement. drop_k: the layer-2 product WITHOUT the 64-wide K
+    block drop_k (the folded bias keeps its sh . W2 term: what a GEMM that skips a K step computes) -- for the planted defects."""
+    mm = np.matmul
+    if drop_k is not None:
+        keep = np.ones(w[0].shape[1], bool)
+        keep[64 * drop_k:64 * drop_k + 64] = False
+        mm = lambda p, v: p[:, keep] @ v[keep]
+    out, cache = actor_forward(w, x, HIGH, mm, fold=True, mmx=np.matmul)
+    return out[:, 0], cache
+
+
+def fwd_c0(w):
+    """b3 + sh2 . W3: the constant term of the output layer, what fill_rows_kernel pre-fills the head sums with."""
+    _, sh2 = omlp._bn_coeffs(*w[8:12])
+    return float(w[13][0] + sh2 @ w[12][:, 0])
+
+
+def fwd_tolerances(ref, emu, high=HIGH):
+    """ref, emu [sets, rows] -> (e_max, e_rms, tol_max, tol_rms)."""
+    d = np.abs(np.asarray(emu, np.float64) - ref) / high
+    e_max, e_rms = float(d.max()), float(np.sqrt(np.mean(d * d)))
+    return e_max, e_rms, max(FWD_TOL, FACTOR * e_max), max(FWD_TOL, FACTOR * e_rms)
+
+
+def fwd_errors(got, ref, high=HIGH):
+    """(max, rms) of |got - ref| / high over all rows and sets."""
+    d = np.abs(np.asarray(got, np.float64) - ref) / high
+    return float(d.max()), float(np.sqrt(np.mean(d * d)))
+
+
+def fwd_violations(got, ref, tol_max, tol_rms, high=HIGH):
+    """[(which, error, tolerance)] of the halves of the rule that `got` [sets, rows] misses (a non-finite result misses both)."""
+    e_max, e_rms = fwd_errors(got, ref, high)
+    return [(n, e, tol) for n, e, tol in (("max", e_max, tol_max), ("rms", e_rms, tol_rms)) if not e <= tol]
+
+
+@functools.lru_cache(maxsize=None)
+def fwd_reference(name):
+    """-> FwdRef of a forward case: the states, for every set the float64 reference and the bf16-operand oracle [sets, P], the rule's
+    four numbers, every set's c0 and the fraction of active units per hidden layer. Cached and shared: treat it as read-only."""
+    case = FWD_CASE[name]
+    x = fwd_states(case)
+    mm16 = lambda p, v: np.matmul(round_bf16(p), round_bf16(v))
+    ref, emu, c0, a1, a2 = [], [], [], [], []
+    for k in range(case.n_sets):
+        w = fwd_actor(case, k)
+        out, cache = fwd_rows(w, x[k])
+        ref.append(out)
+        emu.append(actor_forward(w, x[k], HIGH, mm16, fold=True)[0][:, 0])
+        c0.append(fwd_c0(w))
+        a1.append(float(np.mean(cache[1] > 0)))
+        a2.append(float(np.mean(cache[3] > 0)))
+    ref, emu = np.stack(ref), np.stack(emu)
+    for a in (x, ref, emu):
+        a.setflags(write=False)
+    return FwdRef(x, ref, emu, *fwd_tolerances(ref, emu), tuple(c0), tuple(a1), tuple(a2))
+
+
+def fwd_inputs_bite(ref, active1, active2, c0=None, high=HIGH):
+    """The conditions under which a forward comparison can fail at all (from the float64 reference alone): 20 .. 80 % of the units of both
+    hidden layers active; at least half the rows off tanh's plateau (|tanh| < 0.99); the outputs of a set's rows spread by at least
+    0.1 high -- or, for a set of ONE row (c0 given), that row at least 0.1 high away from tanh(c0) * high, the value a head sum that
+    received nothing would give."""
+    ref = np.asarray(ref)
+    assert all(0.2 <= a <= 0.8 for a in tuple(active1) + tuple(active2)), (active1, active2)
+    assert np.mean(np.abs(ref) < 0.99 * high) >= 0.5, np.mean(np.abs(ref) < 0.99 * high)
+    for k in range(ref.shape[0]):
+        if ref.shape[1] > 1:
+            assert ref[k].std() >= 0.1 * high, (k, ref[k].std())
+        else:
+            assert abs(ref[k, 0] - np.tanh(c0[k]) * high) >= 0.1 * high, (k, ref[k, 0], np.tanh(c0[k]) * high)
+
+
+def fwd_other_S(case, lo, hi):
+    """Rows [lo, hi) of every set as l1_fwd_kernel<the other S> would read them from the packed [sets, P, S] buffer: S = 4 where the case
+    has 3 -- row n of set k starts at float 4 (k P + n) (the fourth float meets no weight row); S = 3 where it has 4 -- row n starts
+    at float 3 (k P + n) and the fourth input is missing. Reads past the buffer's end give 0. -> [sets, hi - lo, S]."""
+    S, So = case.S, 7 - case.S
+    flat = np.concatenate([fwd_states(case).ravel(), np.zeros(So * case.n_sets * case.P + 4, np.float32)])
+    out = np.zeros((case.n_sets, hi - lo, S), np.float32)
+    for k in range(case.n_sets):
+        for n in range(lo, hi):
+            o = So * (k * case.P + n)
+            out[k, n - lo, :3] = flat[o:o + 3]
+    return out
+
+
+def trainer_env_states(case, fill):
+    """fwd_states(case) as the environment holds them: [P, M, 4] float32, agent (p, m) at [p, m, :S]; `fill` in the columns from S on
+    (Model A: the fourth float, which the actor must not read)."""
+    x = np.full((case.P, case.n_sets, 4), fill, np.float32)
+    x[:, :, :case.S] = fwd_states(case).transpose(1, 0, 2)
+    return x

@@ -244,3 +244,97 @@ def test_fset_general_weights_are_normalised_and_differ_per_platoon_and_per_set(
     assert not np.allclose(w[:, 0], w[:, 63], rtol=1e-2)
     for k, (ref, emu, tol) in per.items():
         assert bo.violations(emu, ref, tol) == []
+
+
+# ---- the forward cases of tests/test_gpu_act_shared.py (csrc/wide.hip, avd_actor_forward_shared_bf16) -----------------------------
+FWD_NAMES = [c.name for c in bo.FWD_CASES]
+
+
+def test_forward_cases_reach_the_kernels_they_are_there_for():
+    """launch_gemm's choice restated (fwd_tile): 256-row tiles from 512 rows and 512 columns upward. The table's shapes against it: the
+    last row tile is ragged everywhere, one row in one_row and past_tile, K = H1 = 64 in both k64 cases, S = 3 in modelA alone."""
+    want = {"t256_ragged": (256, 512, 700), "t128_511": (128, 384, 511), "one_row": (128, 0, 1), "past_tile": (128, 128, 129),
+            "modelA": (256, 512, 600), "k64_t256": (256, 512, 600), "k64_t128": (128, 128, 130)}
+    assert sorted(want) == sorted(FWD_NAMES)
+    for c in bo.FWD_CASES:
+        assert (bo.fwd_tile(c), *bo.fwd_last_tile(c)) == want[c.name], c.name
+        assert (c.P - bo.fwd_last_tile(c)[0]) % bo.fwd_tile(c) != 0 and c.S == (3 if c.name == "modelA" else 4)
+        x = bo.fwd_states(c)
+        assert x.shape == (c.n_sets, c.P, c.S) and x.dtype == np.float32 and x.flags.c_contiguous
+    assert {c.n_sets for c in bo.FWD_CASES} == {1, 2, 3} and bo.FWD_CASE["k64_t256"].widths[0] == bo.FWD_CASE["k64_t128"].widths[0] == 64
+
+
+@pytest.mark.parametrize("name", FWD_NAMES)
+def test_forward_case_stays_under_the_cap_and_its_inputs_bite(name):
+    """From the two oracles alone: max(FWD_TOL, FACTOR x e_max) <= FWD_CAP = 2e-2 (never looser than the one-shape test in
+    tests/test_gpu_wide.py), the rms tolerance below the maximum's; the inputs-bite conditions (fwd_inputs_bite); the rule accepts
+    the float64 reference and the bf16 oracle it was derived from."""
+    case, fr = bo.FWD_CASE[name], bo.fwd_reference(name)
+    print(f"{name}: std {case.std} seed {case.seed} e_max {fr.e_max:.3e} e_rms {fr.e_rms:.3e} tol_max {fr.tol_max:.3e} tol_rms {fr.tol_rms:.3e} "
+          f"spread {np.round(fr.ref.std(axis=1) / bo.HIGH, 3)} active {np.round(fr.active1, 2)} {np.round(fr.active2, 2)}")
+    assert fr.ref.shape == fr.emu.shape == (case.n_sets, case.P) and np.isfinite(fr.ref).all() and np.isfinite(fr.emu).all()
+    assert fr.tol_max == max(bo.FWD_TOL, bo.FACTOR * fr.e_max) and fr.tol_rms == max(bo.FWD_TOL, bo.FACTOR * fr.e_rms)
+    assert 0 < fr.e_rms <= fr.e_max and bo.FWD_TOL < fr.tol_rms <= fr.tol_max <= bo.FWD_CAP, (name, fr.tol_max)
+    bo.fwd_inputs_bite(fr.ref, fr.active1, fr.active2, c0=fr.c0 if case.P == 1 else None)
+    assert bo.fwd_violations(fr.ref, fr.ref, fr.tol_max, fr.tol_rms) == []
+    assert bo.fwd_violations(fr.emu, fr.ref, fr.tol_max, fr.tol_rms) == []
+    assert len(bo.fwd_violations(np.full_like(fr.ref, np.nan), fr.ref, fr.tol_max, fr.tol_rms)) == 2  # (a non-finite result fails)
+    for k in range(case.n_sets):  # the reference is oracle/mlp.py's actor (the fold is a float64 regrouping)
+        plain = omlp.actor_forward(bo.fwd_actor(case, k), fr.x[k].astype(np.float64), bo.HIGH)[:, 0]
+        assert np.max(np.abs(plain - fr.ref[k])) <= 1e-9 * bo.HIGH
+
+
+@pytest.mark.parametrize("name", FWD_NAMES)
+def test_the_forward_rule_rejects_planted_defects(name):
+    """Wrong results built from the float64 reference (no kernel): every one misses the rule, in every case where it applies.
+      shifted   every row holds its neighbour's output, within a set                                   (P > 1)
+      swapped   the outputs of the first two sets exchanged                                             (n_sets > 1)
+    and, on the rows of the LAST set's last row tile only (128 or 256 rows as the case's GEMM takes them; 1 .. 188 rows here):
+      stale     left at tanh(c0) * high, the pre-filled head sum that no atomic reached
+      k_block   the layer-2 product without one 64-wide K block -- EVERY block in turn, each result rejected
+      other_S   the states read as l1_fwd_kernel<the other S> reads them (fwd_other_S)"""
+    case, fr = bo.FWD_CASE[name], bo.fwd_reference(name)
+    lo, hi = bo.fwd_last_tile(case)
+    k, w = case.n_sets - 1, bo.fwd_actor(case, case.n_sets - 1)
+    wrong = {}
+    if case.P > 1:
+        wrong["shifted"] = np.roll(fr.ref, -1, axis=1)
+    if case.n_sets > 1:
+        wrong["swapped"] = fr.ref[[1, 0] + list(range(2, case.n_sets))]
+
+    def last_tile(rows):
+        out = fr.ref.copy()
+        out[k, lo:hi] = rows
+        return out
+    wrong["stale"] = last_tile(np.tanh(fr.c0[k]) * bo.HIGH)
+    for j in range(case.widths[0] // 64):
+        wrong[f"k_block[{j}]"] = last_tile(bo.fwd_rows(w, fr.x[k, lo:hi], drop_k=j)[0])
+    wrong["other_S"] = last_tile(bo.fwd_rows(w, bo.fwd_other_S(case, lo, hi)[k])[0])
+    assert len(wrong) == 4 + case.widths[0] // 64 - (case.P == 1) - (case.n_sets == 1)
+    for what, got in wrong.items():
+        bad = bo.fwd_violations(got, fr.ref, fr.tol_max, fr.tol_rms)
+        print(f"{name} {what}: errors {bo.fwd_errors(got, fr.ref)} tolerances {(fr.tol_max, fr.tol_rms)}")
+        assert bad, (name, what, bo.fwd_errors(got, fr.ref), fr.tol_max, fr.tol_rms)
+    # the rms half is what catches one wrong ROW TILE whose worst row stays inside the maximum's tolerance: the last tile of the last set
+    # off by 0.9 x that tolerance passes the max half; it misses the rms half where 0.9 tol_max sqrt(the tile's share of the rows) > tol_rms
+    off = last_tile(fr.ref[k, lo:hi] + 0.9 * fr.tol_max * bo.HIGH)
+    bad = [b[0] for b in bo.fwd_violations(off, fr.ref, fr.tol_max, fr.tol_rms)]
+    caught = 0.9 * fr.tol_max * np.sqrt((hi - lo) / (case.n_sets * case.P)) > fr.tol_rms
+    assert bad == (["rms"] if caught else []) and (caught or name != "t256_ragged"), (name, bad)
+
+
+@pytest.mark.parametrize("name", [c.name for c in bo.TRAINER_CASES])
+def test_trainer_acting_cases_stay_under_the_cap_bite_and_reject_an_axis_swap(name):
+    """The 40 rows of the trainer's acting test (8 platoons x 5 vehicles, 1024/1024): cap, inputs-bite, every action distinct, and the
+    expected outputs with the P and M axes swapped (the set-major block read as agent-major) miss the rule."""
+    case, fr = bo.FWD_CASE[name], bo.fwd_reference(name)
+    print(f"{name}: e_max {fr.e_max:.3e} e_rms {fr.e_rms:.3e} tol_max {fr.tol_max:.3e} tol_rms {fr.tol_rms:.3e} spread {np.round(fr.ref.std(axis=1) / bo.HIGH, 3)}")
+    assert (case.n_sets, case.P, case.widths) == (5, 8, (1024, 1024, 48)) and bo.fwd_tile(case) == 128
+    assert bo.FWD_TOL < fr.tol_rms <= fr.tol_max <= bo.FWD_CAP
+    bo.fwd_inputs_bite(fr.ref, fr.active1, fr.active2)
+    assert len(np.unique(fr.ref)) == 40
+    assert bo.fwd_violations(fr.emu, fr.ref, fr.tol_max, fr.tol_rms) == []
+    swapped = fr.ref.reshape(case.P, case.n_sets).T
+    assert len(bo.fwd_violations(swapped, fr.ref, fr.tol_max, fr.tol_rms)) == 2
+    x = bo.trainer_env_states(case, np.nan)
+    assert x.shape == (8, 5, 4) and np.array_equal(x[3, 2, :case.S], fr.x[2, 3]) and np.isnan(x[..., case.S:]).all()
