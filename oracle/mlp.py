@@ -21,6 +21,8 @@ workers/trainer.py:289, 493-503): ``y = x*inv + (beta - mean*inv)``,
 ``inv = rsqrt(var + 1e-3) * gamma`` (tf.nn.batch_normalization); gamma/beta are
 trainable, moving stats are not.
 """
+import math
+
 import numpy as np
 
 BN_EPS = 1e-3  # Keras BatchNormalization default epsilon
@@ -200,10 +202,29 @@ class RefAdam:
             adam_update(x, m, v, np.asarray(g, dtype=x.dtype), alpha, dt)
 
 
+def adam_beta_power(beta, t, dtype=np.float32):
+    """beta^t in the optimiser's dtype. float32: the target is the EXACT power of
+    float32(beta) rounded once to float32, what a correctly rounded powf gives and
+    what csrc/adam.h:adam_bias aims at with ``(float)pow((double)beta, (double)t)``.
+    It is formed the same way here: libm's float64 pow, then one rounding. That
+    equals the exact rounding unless pow's own error (below 1 ulp of a double)
+    carries the value across a float32 rounding boundary;
+    tests/test_optim_oracle_cpu.py checks the equality on the host it runs on for a
+    sample of step counts (1..3000 and some twenty later ones), not for every t.
+    numpy's float32 power is 1 ulp off for about one step count in seven (beta1
+    from t = 4, beta2 from t = 9)."""
+    dt = np.dtype(dtype).type
+    if dt is np.float32:
+        # math.pow, not np.power: it always calls the C library's pow, while numpy may
+        # pick a vectorised float64 power of its own whose accuracy varies with the CPU
+        return np.float32(math.pow(float(np.float32(beta)), float(t)))
+    return dt(np.power(dt(beta), dt(t)))
+
+
 def adam_alpha(lr, t, dtype=np.float32):
     dt = np.dtype(dtype).type
-    b1p = dt(np.power(dt(ADAM_B1), dt(t)))
-    b2p = dt(np.power(dt(ADAM_B2), dt(t)))
+    b1p = adam_beta_power(ADAM_B1, t, dtype)
+    b2p = adam_beta_power(ADAM_B2, t, dtype)
     return dt(dt(lr) * np.sqrt(dt(1) - b2p) / (dt(1) - b1p))
 
 
