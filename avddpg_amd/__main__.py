@@ -143,6 +143,28 @@ def _record_train_levels(conf, args):
         conf.train_disturbances = [[x.name, x.items()] for x in args.train_disturb]
 
 
+def _record_train_leader(conf, args):
+    """conf.json's train_leader: the --train_leader manoeuvres as [name, [[key, value], ...]] pairs."""
+    if getattr(args, "train_leader", None) is not None:
+        conf.train_leader = [[x.name, x.items()] for x in args.train_leader]
+
+
+def _lead_kw(args):
+    """VecTrainer's train_leader keyword, only where the flag was given."""
+    return {} if getattr(args, "train_leader", None) is None else dict(train_leader=args.train_leader)
+
+
+def _check_train_leader(args, conf, auto_reset, hparams=None):
+    """The --train_leader refusals that need the run's configuration, under the flag's own name, before anything is allocated."""
+    if getattr(args, "train_leader", None) is not None:
+        from . import trainer
+
+        try:
+            trainer.check_train_leader(conf, args.train_leader, args.rng, None, auto_reset, hparams=hparams)
+        except ValueError as e:
+            raise SystemExit(f"--train_leader: {e}")
+
+
 def _suite(args):
     """run_cases' keyword arguments from the scenario flags."""
     return dict(scenarios=args.scenarios, seeds=args.eval_seeds, amp=args.scenario_amp,
@@ -253,6 +275,15 @@ def get_cmdl_args(argv, conf):
                          "what the agents observed; rewards and episodes come from the true state. conf.json records the levels as "
                          "train_disturbances. Composes with --seeds, --scenarios and --disturb; not with --sweep / --pbt, the centralized "
                          "framework or a process group (not in the reference CLI)")
+    tr.add_argument("--train_leader", action="append", default=None, metavar="NAME[:key=val,...]",
+                    help="--rng device: TRAIN under leader manoeuvres (repeat the flag for more, at most 16): platoon p's leader follows "
+                         "manoeuvre (p // n_levels) %% n_manoeuvres for the whole run (n_levels: the --train_disturb level count, 1 without). "
+                         "Keys: profile (one of --scenarios' names; default: NAME if it is one, else gaussian), amp, period (as "
+                         "--scenario_amp / --scenario_period) and noise (times the step's unit draw, on top of the profile; default 0). The "
+                         "input at step k of the platoon's own episode is the array --scenarios evaluates with. The gaussian profile is the "
+                         "reference's training input, a clean share (noise: its scale, default reset_max_u; no amp or period). conf.json "
+                         "records the manoeuvres as train_leader. Composes with --seeds, --train_disturb, --scenarios and --disturb; not with "
+                         "--sweep / --pbt, --rng host, the centralized framework or a process group (not in the reference CLI)")
     _scenario_flags(tr, "after training, beside the simulation rewards:")
     tr.add_argument("--out", type=str, default=".outputs")
     es = sub.add_parser("esim", help="run in evaluation/simulator mode")
@@ -296,6 +327,19 @@ def get_cmdl_args(argv, conf):
             args.train_disturb = check_disturbances([parse_disturbance(d) for d in args.train_disturb])
         except ValueError as e:
             ap.error(f"--train_disturb: {e}")
+    if getattr(args, "train_leader", None) is not None:
+        from .scenarios import check_manoeuvres, parse_manoeuvre
+
+        if args.rng != "device":
+            ap.error("--train_leader needs --rng device")
+        if args.sweep is not None or args.pbt is not None:
+            ap.error("--train_leader does not combine with --sweep / --pbt")
+        if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+            ap.error("--train_leader is not available under a process group of more than one rank")
+        try:  # (what needs the run's configuration: trainer.check_train_leader applies it)
+            args.train_leader = check_manoeuvres([parse_manoeuvre(m) for m in args.train_leader])
+        except ValueError as e:
+            ap.error(f"--train_leader: {e}")
     if getattr(args, "pbt", None) is not None or getattr(args, "pbt_fraction", None) is not None or getattr(args, "pbt_perturb", None) is not None:
         if args.pbt is None:
             ap.error("--pbt_fraction / --pbt_perturb need --pbt")
@@ -363,9 +407,10 @@ def main(argv=None, conf=None):
                 raise SystemExit("--episodes platoon needs --rng device")
             from . import evaluator
             nofrl = conf.fed_method == conf.nofrl
+            _check_train_leader(args, conf, "platoon")
             try:
                 vt = trainer.VecTrainer(conf, rng="device", auto_reset="platoon", shared_engine=args.engine, fused_update=nofrl,
-                                        train_disturb=args.train_disturb)
+                                        train_disturb=args.train_disturb, **_lead_kw(args))
             except ValueError as e:
                 if args.train_disturb is None:
                     raise
@@ -404,8 +449,10 @@ def main(argv=None, conf=None):
             if vt.nonfinite_updates():
                 print(f"warning: {vt.nonfinite_updates()} weight-set updates were skipped for non-finite gradients", file=sys.stderr)
         else:
+            _check_train_leader(args, conf, False)
             try:
-                vt = trainer.VecTrainer(conf, rng=args.rng, auto_reset=False, shared_engine=args.engine, train_disturb=args.train_disturb)
+                vt = trainer.VecTrainer(conf, rng=args.rng, auto_reset=False, shared_engine=args.engine, train_disturb=args.train_disturb,
+                                        **_lead_kw(args))
             except ValueError as e:
                 if args.train_disturb is None:
                     raise
@@ -430,6 +477,7 @@ def main(argv=None, conf=None):
                                    "(if enabled) from step weighted_window x steps_per_episode on, weights from each agent's last "
                                    "weighted_window closed episodes")
         _record_train_levels(conf, args)
+        _record_train_leader(conf, args)
         artifacts.config_writer(os.path.join(base, "conf.json"), conf)
         print(base)
     elif args.mode == "esim":
@@ -511,10 +559,11 @@ def train_seed_batch(args, conf, base, experiments=None):
             trainer.check_train_disturb(conf, args.train_disturb, "device", None, hparams=hps)
         except ValueError as e:
             raise SystemExit(f"--train_disturb: {e}")
+    _check_train_leader(args, conf, "platoon", hparams=hps)
     try:
         vt = trainer.VecTrainer(conf, rng="device", auto_reset="platoon", shared_engine=args.engine,
                                 fused_update=conf.fed_method == conf.nofrl, seeds=seeds, hparams=hps,
-                                train_disturb=getattr(args, "train_disturb", None))
+                                train_disturb=getattr(args, "train_disturb", None), **_lead_kw(args))
     except ValueError as e:
         raise SystemExit(f"{flag}: {e}")
     vt.reset_episode()
@@ -603,6 +652,7 @@ def train_seed_batch(args, conf, base, experiments=None):
                 ce.pbt = [["interval", args.pbt], ["fraction", args.pbt_fraction], ["perturb", list(args.pbt_perturb)],
                           ["lineage", lineage[e]]]
         _record_train_levels(ce, args)
+        _record_train_leader(ce, args)
         if suite is not None:
             _write_suite(d, ce, _slice(suite, e), range(1, P + 1), args)
         artifacts.config_writer(os.path.join(d, "conf.json"), ce)

@@ -16,6 +16,7 @@ AVD_MAX_L = 16
 AVD_EVAL_NMETRIC = 8
 AVD_EVAL_MAX_DELAY = 15
 AVD_TRAIN_MAX_LEVELS = 16
+AVD_TRAIN_MAX_MANOEUVRES = 16
 
 
 class AvdError(RuntimeError):
@@ -88,6 +89,16 @@ _PROTOS = {
                                 _u64, _u64, _P, _i, _i64, _P, _i, _P, _P, _P, _P, _P, _P, _P, _u64, _P],
     "avd_step_fused_dist_seeds_f32": [_P, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _f, _f, _f, _f, _f, _i,
                                       _P, _i, _u64, _u64, _P, _i, _i64, _P, _i, _P, _P, _P, _P, _P, _P, _P, _u64, _P],
+    "avd_step_fused_lead_f32": [_P, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _f, _f, _f, _f, _f, _i, _u64,
+                                _u64, _u64, _P, _i, _i64, _P, _i, _i, _P, _P, _P, _P, _i, _i, _P],
+    "avd_step_fused_lead_seeds_f32": [_P, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _f, _f, _f, _f, _f, _i,
+                                      _P, _i, _u64, _u64, _P, _i, _i64, _P, _i, _i, _P, _P, _P, _P, _i, _i, _P],
+    "avd_step_fused_dist_lead_f32": [_P, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _f, _f, _f, _f, _f, _i,
+                                     _u64, _u64, _u64, _P, _i, _i64, _P, _i, _P, _P, _P, _P, _P, _P, _P, _u64, _i, _i, _P, _P, _P, _P, _i,
+                                     _P],
+    "avd_step_fused_dist_lead_seeds_f32": [_P, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _f, _f, _f, _f, _f,
+                                           _i, _P, _i, _u64, _u64, _P, _i, _i64, _P, _i, _P, _P, _P, _P, _P, _P, _P, _u64, _i, _i, _P, _P,
+                                           _P, _P, _i, _P],
     "avd_observe_f32": [_i, _i, _P, _P, _i, _P, _P, _P, _u64, _u64, _P, _P, _P],
     "avd_observe_seeds_f32": [_i, _i, _P, _P, _i, _P, _P, _P, _P, _i, _u64, _P, _P, _P],
     "avd_learn_hp_f32": [_LP, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _f, _P, _P, _P, _i, _i, _P],

@@ -310,7 +310,32 @@ struct DistRef {
 };
 template <class... H>
 constexpr bool has_dist = (std::is_same<H, DistRef>::value || ...);
-__device__ __forceinline__ const DistRef& dist_of(const DistRef& d) { return d; }
+
+// ---- training under leader manoeuvres (avd_step_fused_lead_f32 and its twins) ------------------------------------------------------
+// Another trailing argument of the same kind, alone or after a DistRef. Platoon p trains under manoeuvre (its solo-run index /
+// n_levels) % n: levels and manoeuvres cross. A deterministic manoeuvre's leader input is its row of the host-made table at the step of
+// the platoon's own episode (ep_len[p], or the host's ep_step when ep_len is null; clamped into the row) plus noise * the step's unit
+// draw; a gaussian one is the nominal input, the unit draw times its noise.
+struct LeadRef {
+    int n, T;
+    const float* table;          // [n][T], rows of gaussian manoeuvres unread
+    const float* noise;          // [n]
+    const uint8_t* is_gaussian;  // [n]
+    const int32_t* ep_len;       // [P] or NULL
+    int ep_step, n_levels;
+};
+template <class... H>
+constexpr bool has_lead = (std::is_same<H, LeadRef>::value || ...);
+// the pack's member of type T
+template <class T, class First, class... Rest>
+__device__ __forceinline__ const T& pack_member(const First& f, const Rest&... r) {
+    if constexpr (std::is_same<T, First>::value) return f;
+    else return pack_member<T>(r...);
+}
+template <class... H>
+__device__ __forceinline__ const DistRef& dist_of(const H&... h) { return pack_member<DistRef>(h...); }
+template <class... H>
+__device__ __forceinline__ const LeadRef& lead_of(const H&... h) { return pack_member<LeadRef>(h...); }
 constexpr int LINK_RING = 16;  // slots of a vehicle's V2V history (delays 0 .. 15), indexed by counter & 15
 constexpr int LEVEL_WORDS = sizeof(avd_train_level) / 4;
 static_assert(sizeof(avd_train_level) == 32 && (LINK_RING & (LINK_RING - 1)) == 0, "level rows of 8 words; the ring index is a mask");
@@ -339,10 +364,12 @@ __device__ __forceinline__ void observe_noise(float4& ob, const float4& x, const
 // DIST (avd_step_fused_dist_f32, one DistRef in the pack): the platoon's level picks its plant, obs_out observes x_out, the replay row
 // holds observations. The plant rows of ALL levels and the level table are staged in dynamic LDS once per block ([n_levels][L][24]
 // floats, then [n_levels][8] words: at most 25 088 B) in place of the constants block's L rows.
+// LEAD (avd_step_fused_lead_f32, one LeadRef in the pack, with or without a DistRef): the leader's input comes from the platoon's
+// manoeuvre. Only the leader's lane reads the table, one float from global memory (16 x T floats would cost more to stage per block).
 template <bool G, bool HP = false, class... H>
 __global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs a, H... hp) {
 #pragma clang fp contract(off)
-    constexpr bool DIST = has_dist<H...>;
+    constexpr bool DIST = has_dist<H...>, LEAD = has_lead<H...>;
     __shared__ float sA[AVD_MAX_L][16], sB[AVD_MAX_L][4], sC[AVD_MAX_L][4];  // (DIST: unused, the rows live in dynamic LDS)
     const avd_env_consts* cst = a.cst;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, L = a.L;
@@ -391,7 +418,20 @@ __global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs 
         a.action[v] = uu;
         if (i == 0) {  // leader exog, redrawn every step (workers/trainer.py:291-295; util.get_random_val)
             const u32x4 re = philox_at(key, a.exog_counter, (uint32_t)pl, STREAM_NORMAL);
-            exog_own = (a.exog_uniform ? uniform_pm1(re.x) : box_muller(re.x, re.y, nullptr)) * a.exog_scale;
+            if constexpr (LEAD) {
+                const LeadRef& ld = lead_of(hp...);
+                const int m = (pl / ld.n_levels) % ld.n;
+                const float d = a.exog_uniform ? uniform_pm1(re.x) : box_muller(re.x, re.y, nullptr), nz = ld.noise[m];
+                if (ld.is_gaussian[m]) {
+                    exog_own = d * nz;
+                } else {  // the table's bits, or one rounded product and one add on top of them
+                    const int k = min(max(ld.ep_len ? ld.ep_len[p] : ld.ep_step, 0), ld.T - 1);
+                    exog_own = ld.table[m * ld.T + k];
+                    if (nz != 0.f) exog_own = exog_own + nz * d;
+                }
+            } else {
+                exog_own = (a.exog_uniform ? uniform_pm1(re.x) : box_muller(re.x, re.y, nullptr)) * a.exog_scale;
+            }
             a.leader_exog[p] = exog_own;
         }
     }
@@ -629,7 +669,8 @@ static int step_fused_launch(const char* who, const avd_env_consts* d_consts, in
                              float ou_theta, float ou_mean, float ou_dt, float ou_std_dev, float action_low, float action_high,
                              float exog_scale, int exog_uniform, uint64_t seed, const uint64_t* d_seeds, int n_groups,
                              uint64_t ou_counter, uint64_t exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward,
-                             void* stream, const avd_hparams* d_hp = nullptr, const DistRef* dist = nullptr) {
+                             void* stream, const avd_hparams* d_hp = nullptr, const DistRef* dist = nullptr,
+                             const LeadRef* lead = nullptr) {
     AVD_REQUIRE(P > 0 && L > 0 && L <= AVD_MAX_L && (S == 3 || S == 4), "%s: P=%d L=%d S=%d", who, P, L, S);
     AVD_REQUIRE(d_consts && x_in && x_out && prev_a && reward && done && actor_out && ou_state && action && leader_exog,
                 "%s: null pointer", who);
@@ -646,6 +687,12 @@ static int step_fused_launch(const char* who, const avd_env_consts* d_consts, in
     if constexpr (HP)
         hipLaunchKernelGGL((step_fused_kernel<G, true, HpRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS), 0,
                            (hipStream_t)stream, a, HpRef{d_hp, n_groups, 1});
+    else if (dist && lead)
+        hipLaunchKernelGGL((step_fused_kernel<G, false, DistRef, LeadRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS),
+                           sizeof(float) * (size_t)dist->n_levels * (L * 24 + LEVEL_WORDS), (hipStream_t)stream, a, *dist, *lead);
+    else if (lead)
+        hipLaunchKernelGGL((step_fused_kernel<G, false, LeadRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS), 0,
+                           (hipStream_t)stream, a, *lead);
     else if (dist)
         hipLaunchKernelGGL((step_fused_kernel<G, false, DistRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS),
                            sizeof(float) * (size_t)dist->n_levels * (L * 24 + LEVEL_WORDS), (hipStream_t)stream, a, *dist);
@@ -672,6 +719,20 @@ static int dist_args(const char* who, int n_levels, const avd_train_level* h_lev
     }
     d.n_levels = n_levels, d.levels = d_levels, d.plant = d_plant, d.obs_in = (const float4*)obs_in, d.obs_out = (float4*)obs_out;
     d.link_hist = link_hist, d.link_recv = link_recv, d.obs_counter = obs_counter;
+    return AVD_OK;
+}
+
+// The manoeuvre step's own arguments, checked and packed (the tables are device memory: their values are the caller's to check)
+static int lead_args(const char* who, int n_manoeuvres, int T, const float* d_table, const float* d_noise, const uint8_t* d_gaussian,
+                     const int32_t* ep_len, int ep_step, int n_levels, LeadRef& l) {
+    AVD_REQUIRE(n_manoeuvres >= 1 && n_manoeuvres <= AVD_TRAIN_MAX_MANOEUVRES, "%s: n_manoeuvres=%d (must be 1..%d)", who, n_manoeuvres,
+                AVD_TRAIN_MAX_MANOEUVRES);
+    AVD_REQUIRE(T >= 4, "%s: T=%d (a manoeuvre needs at least 4 steps)", who, T);
+    AVD_REQUIRE(d_table && d_noise && d_gaussian, "%s: null manoeuvre table, noise table or gaussian flags", who);
+    AVD_REQUIRE(ep_len || (ep_step >= 0 && ep_step < T), "%s: ep_step=%d with a null ep_len (must be in [0, T=%d))", who, ep_step, T);
+    AVD_REQUIRE(n_levels >= 1, "%s: n_levels=%d (must be >= 1)", who, n_levels);
+    l.n = n_manoeuvres, l.T = T, l.table = d_table, l.noise = d_noise, l.is_gaussian = d_gaussian, l.ep_len = ep_len;
+    l.ep_step = ep_step, l.n_levels = n_levels;
     return AVD_OK;
 }
 
@@ -798,6 +859,77 @@ extern "C" int avd_step_fused_dist_seeds_f32(const avd_env_consts* d_consts, int
                                    actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt, ou_std_dev, action_low, action_high,
                                    exog_scale, exog_uniform, 0, d_seeds, n_groups, ou_counter, exog_counter, ring, cap, replay_counter,
                                    ep_reward, stream, nullptr, &d);
+}
+
+// ---- training under leader manoeuvres --------------------------------------------------------------------------------------
+extern "C" int avd_step_fused_lead_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
+    float* prev_a, float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done, int32_t* any_done_other,
+    const float* actor_out, float* ou_state, float* action, float* leader_exog, float ou_theta, float ou_mean, float ou_dt,
+    float ou_std_dev, float action_low, float action_high, float exog_scale, int exog_uniform, uint64_t seed, uint64_t ou_counter,
+    uint64_t exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward, int n_manoeuvres, int T, const float* d_table,
+    const float* d_noise, const uint8_t* d_gaussian, const int32_t* ep_len, int ep_step, int n_levels, void* stream) {
+    const char* who = "avd_step_fused_lead_f32";
+    LeadRef l;
+    if (const int rc = lead_args(who, n_manoeuvres, T, d_table, d_noise, d_gaussian, ep_len, ep_step, n_levels, l)) return rc;
+    return step_fused_launch<false>(who, d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done, any_done, any_done_other,
+                                   actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt, ou_std_dev, action_low, action_high,
+                                   exog_scale, exog_uniform, seed, nullptr, 1, ou_counter, exog_counter, ring, cap, replay_counter,
+                                   ep_reward, stream, nullptr, nullptr, &l);
+}
+
+extern "C" int avd_step_fused_lead_seeds_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
+    float* prev_a, float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done, int32_t* any_done_other,
+    const float* actor_out, float* ou_state, float* action, float* leader_exog, float ou_theta, float ou_mean, float ou_dt,
+    float ou_std_dev, float action_low, float action_high, float exog_scale, int exog_uniform, const uint64_t* d_seeds, int n_groups, uint64_t ou_counter,
+    uint64_t exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward, int n_manoeuvres, int T, const float* d_table,
+    const float* d_noise, const uint8_t* d_gaussian, const int32_t* ep_len, int ep_step, int n_levels, void* stream) {
+    const char* who = "avd_step_fused_lead_seeds_f32";
+    AVD_REQUIRE_GROUPS(who, P);
+    LeadRef l;
+    if (const int rc = lead_args(who, n_manoeuvres, T, d_table, d_noise, d_gaussian, ep_len, ep_step, n_levels, l)) return rc;
+    return step_fused_launch<true>(who, d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done, any_done, any_done_other,
+                                   actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt, ou_std_dev, action_low, action_high,
+                                   exog_scale, exog_uniform, 0, d_seeds, n_groups, ou_counter, exog_counter, ring, cap, replay_counter,
+                                   ep_reward, stream, nullptr, nullptr, &l);
+}
+
+extern "C" int avd_step_fused_dist_lead_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
+    float* prev_a, float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done, int32_t* any_done_other,
+    const float* actor_out, float* ou_state, float* action, float* leader_exog, float ou_theta, float ou_mean, float ou_dt,
+    float ou_std_dev, float action_low, float action_high, float exog_scale, int exog_uniform, uint64_t seed, uint64_t ou_counter,
+    uint64_t exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward, int n_levels, const avd_train_level* h_levels,
+    const avd_train_level* d_levels, const float* d_plant, const float* obs_in, float* obs_out, float* link_hist, float* link_recv,
+    uint64_t obs_counter, int n_manoeuvres, int T, const float* d_table,
+    const float* d_noise, const uint8_t* d_gaussian, const int32_t* ep_len, int ep_step, void* stream) {
+    const char* who = "avd_step_fused_dist_lead_f32";
+    DistRef d;
+    if (const int rc = dist_args(who, n_levels, h_levels, d_levels, d_plant, obs_in, obs_out, link_hist, link_recv, obs_counter, d)) return rc;
+    LeadRef l;
+    if (const int rc = lead_args(who, n_manoeuvres, T, d_table, d_noise, d_gaussian, ep_len, ep_step, n_levels, l)) return rc;
+    return step_fused_launch<false>(who, d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done, any_done, any_done_other,
+                                   actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt, ou_std_dev, action_low, action_high,
+                                   exog_scale, exog_uniform, seed, nullptr, 1, ou_counter, exog_counter, ring, cap, replay_counter,
+                                   ep_reward, stream, nullptr, &d, &l);
+}
+
+extern "C" int avd_step_fused_dist_lead_seeds_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
+    float* prev_a, float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done, int32_t* any_done_other,
+    const float* actor_out, float* ou_state, float* action, float* leader_exog, float ou_theta, float ou_mean, float ou_dt,
+    float ou_std_dev, float action_low, float action_high, float exog_scale, int exog_uniform, const uint64_t* d_seeds, int n_groups, uint64_t ou_counter,
+    uint64_t exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward, int n_levels, const avd_train_level* h_levels,
+    const avd_train_level* d_levels, const float* d_plant, const float* obs_in, float* obs_out, float* link_hist, float* link_recv,
+    uint64_t obs_counter, int n_manoeuvres, int T, const float* d_table,
+    const float* d_noise, const uint8_t* d_gaussian, const int32_t* ep_len, int ep_step, void* stream) {
+    const char* who = "avd_step_fused_dist_lead_seeds_f32";
+    AVD_REQUIRE_GROUPS(who, P);
+    DistRef d;
+    if (const int rc = dist_args(who, n_levels, h_levels, d_levels, d_plant, obs_in, obs_out, link_hist, link_recv, obs_counter, d)) return rc;
+    LeadRef l;
+    if (const int rc = lead_args(who, n_manoeuvres, T, d_table, d_noise, d_gaussian, ep_len, ep_step, n_levels, l)) return rc;
+    return step_fused_launch<true>(who, d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done, any_done, any_done_other,
+                                   actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt, ou_std_dev, action_low, action_high,
+                                   exog_scale, exog_uniform, 0, d_seeds, n_groups, ou_counter, exog_counter, ring, cap, replay_counter,
+                                   ep_reward, stream, nullptr, &d, &l);
 }
 
 extern "C" int avd_observe_f32(int P, int L, const float* x, float* obs, int n_levels, const avd_train_level* d_levels, float* link_hist,

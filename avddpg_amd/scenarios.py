@@ -255,6 +255,116 @@ def plant_table(conf, L, dyn_coeff=None):
     return out
 
 
+# ---- training manoeuvres: what the fused step's leader follows during training (avd_step_fused_lead_f32) -----------------------------
+
+MAX_MANOEUVRES = 16  # AVD_TRAIN_MAX_MANOEUVRES
+MANOEUVRE_KEYS = ("profile", "amp", "period", "noise")
+DEFAULT_PERIOD = 10.0
+
+
+class Manoeuvre:
+    """One training manoeuvre: the leader's input over a platoon's own episode is ``leader_profile(profile, steps_per_episode, conf, amp,
+    period)`` -- the array the scenario evaluator feeds its cases -- plus ``noise`` times the step's unit draw (default 0: the profile
+    alone). ``profile='gaussian'`` is the reference's training input, the unit draw times ``noise`` (default conf.reset_max_u): the clean
+    share of a run; it takes neither amp nor period."""
+
+    def __init__(self, name, profile="gaussian", amp=None, period=DEFAULT_PERIOD, noise=None):
+        self.name, self.profile = str(name), profile
+        self.amp, self.period, self.noise = amp, period, noise
+
+    def items(self):
+        """[(key, value)] in MANOEUVRE_KEYS order (conf.json's train_leader)."""
+        return [[k, getattr(self, k)] for k in MANOEUVRE_KEYS]
+
+    def __repr__(self):
+        return "Manoeuvre(" + ", ".join([repr(self.name)] + [f"{k}={v!r}" for k, v in self.items()]) + ")"
+
+
+def parse_manoeuvre(text):
+    """``NAME[:key=val,...]`` (keys of MANOEUVRE_KEYS) -> Manoeuvre. Without a profile key a NAME that is itself a profile name means
+    that profile, any other NAME the gaussian one. An unknown key, a key given twice, a value that is no number or amp / period beside
+    the gaussian profile is a ValueError; the values are checked by check_manoeuvres."""
+    name, _, spec = str(text).partition(":")
+    name = name.strip()
+    if not name:
+        raise ValueError(f"manoeuvre {text!r}: no name before ':'")
+    kw = {}
+    for part in [q.strip() for q in spec.split(",") if q.strip()]:
+        key, eq, val = part.partition("=")
+        key, val = key.strip(), val.strip()
+        if not eq or key not in MANOEUVRE_KEYS:
+            raise ValueError(f"manoeuvre {name!r}: unknown key {key!r} (one of {', '.join(MANOEUVRE_KEYS)}, as key=value)")
+        if key in kw:
+            raise ValueError(f"manoeuvre {name!r}: {key} given twice")
+        if key == "profile":
+            kw[key] = val
+            continue
+        try:
+            kw[key] = float(val)
+        except ValueError:
+            raise ValueError(f"manoeuvre {name!r}: {key}={val!r} is not a number") from None
+    kw.setdefault("profile", name if name in SCENARIOS else "gaussian")
+    if kw["profile"] == "gaussian" and ("amp" in kw or "period" in kw):
+        raise ValueError(f"manoeuvre {name!r}: the gaussian profile takes neither amp nor period (its scale is noise)")
+    return Manoeuvre(name, **kw)
+
+
+def check_manoeuvres(manoeuvres):
+    """The manoeuvres as a list. A ValueError for: none or more than MAX_MANOEUVRES; an unknown profile; a non-finite value; period <=
+    0; noise < 0; amp or period beside the gaussian profile; a name listed twice."""
+    out = list(manoeuvres)
+    if not 1 <= len(out) <= MAX_MANOEUVRES:
+        raise ValueError(f"{len(out)} manoeuvres listed: 1 to {MAX_MANOEUVRES} (platoon p trains under manoeuvre (p // n_levels) % n_manoeuvres)")
+    for m in out:
+        if not isinstance(m, Manoeuvre):
+            raise ValueError(f"{m!r} is not a scenarios.Manoeuvre")
+        if m.profile not in SCENARIOS:
+            raise ValueError(f"manoeuvre {m.name!r}: unknown profile {m.profile!r}: one of {', '.join(SCENARIOS)}")
+        for k in ("amp", "period", "noise"):
+            v = getattr(m, k)
+            if v is None and k != "period":
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+                raise ValueError(f"manoeuvre {m.name!r}: {k}={v!r} must be a finite number")
+        if m.period <= 0:
+            raise ValueError(f"manoeuvre {m.name!r}: period={m.period!r} must be > 0")
+        if m.noise is not None and m.noise < 0:
+            raise ValueError(f"manoeuvre {m.name!r}: noise={m.noise!r} must be >= 0")
+        if m.profile == "gaussian" and (m.amp is not None or m.period != DEFAULT_PERIOD):
+            raise ValueError(f"manoeuvre {m.name!r}: the gaussian profile takes neither amp nor period (its scale is noise)")
+    names = [m.name for m in out]
+    dup = sorted({n for n in names if names.count(n) > 1})
+    if dup:
+        raise ValueError(f"manoeuvre(s) {dup} listed more than once")
+    return out
+
+
+def manoeuvre_table(conf, manoeuvres):
+    """Checked manoeuvres -> (float32 [n, T] leader inputs, float32 [n] noise scales, bool [n] gaussian flags) with T =
+    conf.steps_per_episode: row m is leader_profile(profile, T, conf, amp, period) -- float64, rounded once; the array evaluator.CaseBatch
+    feeds avd_eval_cases_f32 -- and noise 0 by default; a gaussian manoeuvre's row is unread (zeros), its noise conf.reset_max_u by
+    default."""
+    ms = check_manoeuvres(manoeuvres)
+    T = int(conf.steps_per_episode)
+    check_knobs(T, None, DEFAULT_PERIOD)
+    table = np.zeros((len(ms), T), dtype=np.float32)
+    noise = np.zeros(len(ms), dtype=np.float32)
+    gauss = np.zeros(len(ms), dtype=bool)
+    for k, m in enumerate(ms):
+        gauss[k] = m.profile == "gaussian"
+        if gauss[k]:
+            noise[k] = np.float32(conf.reset_max_u if m.noise is None else m.noise)
+        else:
+            table[k] = leader_profile(m.profile, T, conf, m.amp, m.period)
+            noise[k] = np.float32(0.0 if m.noise is None else m.noise)
+    return table, noise, gauss
+
+
+def manoeuvre_of(q, n_manoeuvres, n_levels=1):
+    """The manoeuvre index of the platoon whose solo-run index is q: levels (q % n_levels) and manoeuvres cross."""
+    return (int(q) // int(n_levels)) % int(n_manoeuvres)
+
+
 ROBUSTNESS_HEADER = [*CSV_HEADER[:2], "disturbance", *CSV_HEADER[2:], "score_delta"]
 
 

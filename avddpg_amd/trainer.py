@@ -133,6 +133,31 @@ def check_train_disturb(conf, train_disturb, rng, group, fused_step=None, hparam
     return scenarios.check_disturbances(levels, conf)
 
 
+def check_train_leader(conf, train_leader, rng, group, auto_reset, fused_step=None, hparams=None):
+    """Why a run cannot TRAIN under these leader manoeuvres (VecTrainer(train_leader=...)), raised as a ValueError -- or the checked list
+    of scenarios.Manoeuvre. Called before anything is allocated or launched. The manoeuvre is read in the fused step's launch
+    (avd_step_fused_lead_f32) at the step of the platoon's own episode: device RNG, decentralized agents, one GPU, no sweep, and an
+    episode rule under which the host or the device holds that step."""
+    from . import scenarios
+
+    if conf.framework == conf.cntrl:
+        raise ValueError("training under leader manoeuvres needs the decentralized framework: the centralized one has no fused step")
+    if rng != "device":
+        raise ValueError("training under leader manoeuvres needs rng='device': the manoeuvre is read in the fused step's launch")
+    if fused_step is not None and not fused_step:
+        raise ValueError("training under leader manoeuvres needs the fused step (fused_step=False draws the leader input in a kernel of its own)")
+    if hparams is not None:
+        raise ValueError("training under leader manoeuvres does not combine with a hyperparameter sweep or PBT (hparams=...)")
+    if group is not None:
+        raise ValueError("training under leader manoeuvres runs on one GPU: no process group")
+    if auto_reset is True:
+        raise ValueError("training under leader manoeuvres needs auto_reset='platoon' or False: with auto_reset=True the conditional reset "
+                         "happens on the device, so neither side holds the episode's step")
+    out = scenarios.check_manoeuvres(train_leader)
+    scenarios.check_knobs(conf.steps_per_episode, None, scenarios.DEFAULT_PERIOD)
+    return out
+
+
 # The set learners' largest weight-set count (the shape checks of csrc/fset.hip and csrc/fsplit.hip); the others take any count.
 SET_ENGINE_MAX_SETS = {"fused": 64, "fused3": 64}
 
@@ -140,7 +165,7 @@ SET_ENGINE_MAX_SETS = {"fused": 64, "fused3": 64}
 class VecTrainer:
     def __init__(self, conf, device=None, rng="device", group=None, shared_sets=None, seed=None, auto_reset=False,
                  pipeline_chunks=1, fused_update=False, shared_engine=None, init_seed=None, fused_step=None,
-                 replay_ring=None, overlap_allreduce=None, seeds=None, hparams=None, train_disturb=None):
+                 replay_ring=None, overlap_allreduce=None, seeds=None, hparams=None, train_disturb=None, train_leader=None):
         """group: torch.distributed process group whose ranks each hold ``conf.num_platoons`` platoons
         (interfrl gradients are all-reduced over it). auto_reset: end episodes on the device (no host
         sync per step); needs rng='device'. True: the reference's rule -- any terminal platoon (or the step limit) ends
@@ -168,11 +193,19 @@ class VecTrainer:
         run's platoon index, so experiment k still equals its solo run) -- a Disturbance with a name alone is a clean share. The true state
         advances with the level's plant and gives reward, terminal flags and episodes; the actors act from, and the replay holds, what
         the agents OBSERVED (env.obs: sensor noise, V2V delay and loss). check_train_disturb says what it needs (device RNG, the fused
-        step, decentralized, one GPU, no sweep). None: nothing changes -- no buffer is made, the same entry points run."""
+        step, decentralized, one GPU, no sweep). None: nothing changes -- no buffer is made, the same entry points run.
+        train_leader: a list of 1..16 scenarios.Manoeuvre to TRAIN under: platoon p's leader follows manoeuvre (q // n_levels) %
+        n_manoeuvres for the whole run, q its solo-run platoon index and n_levels the train_disturb level count (1 without), so levels
+        and manoeuvres cross. The input at step k of the platoon's OWN episode is scenarios.manoeuvre_table's row at k -- the array the
+        scenario evaluator feeds -- plus the manoeuvre's noise times the step's unit draw; a gaussian manoeuvre is the reference's input, the
+        clean share. k is env.ep_len with per-platoon episodes, self.ep_step under the host episode loop (auto_reset=False).
+        check_train_leader says what it needs. None: nothing changes -- no buffer is made, the same entry points run."""
         conf.refresh()
-        self.levels = None
+        self.levels = self.manoeuvres = self.lead = None
         if train_disturb is not None:
             self.levels = check_train_disturb(conf, train_disturb, rng, group, fused_step, hparams)
+        if train_leader is not None:
+            self.manoeuvres = check_train_leader(conf, train_leader, rng, group, auto_reset, fused_step, hparams)
         self.conf, self.rng, self.group = conf, rng, group
         self.device = torch.device(device if device is not None else "cuda")
         self.seeds = self.hp_rows = None
@@ -321,6 +354,13 @@ class VecTrainer:
         self._equal_shards = abs(self.total_platoons - self.P * ws) < 0.5
         self._step_parity = 0
         self._added = False
+        if self.manoeuvres is not None:  # the manoeuvre tables, uploaded once; the episode's step per platoon exists from the start
+            from . import scenarios
+            table, noise, gauss = scenarios.manoeuvre_table(conf, self.manoeuvres)
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+            self.lead = dict(n=len(self.manoeuvres), T=table.shape[1], table=up(table), noise=up(noise), gaussian=up(gauss.astype(np.uint8)))
+            if auto_reset == "platoon":
+                self.env.ensure_episode_state()
         self.fused_update = bool(fused_update)  # nofrl (any framework / widths the learn kernels serve): avd_learn_update_f32
         # fused_update also has the learn kernel evaluate the UPDATED actor on the state the next step acts from
         # (workers/trainer.py:287-289): self.actor_out then already holds the next step's actor outputs unless the states
@@ -416,19 +456,27 @@ class VecTrainer:
         env.any_done = env._any_flags[k:k + 1]  # this step's flag (cleared by the previous step's launch, zero at start)
         other = env._any_flags[1 - k:2 - k]
         env.x, env.x_prev = env.x_prev, env.x
+        lead, tag = (), ""
+        if self.lead is not None:
+            # training under leader manoeuvres (the *_lead_* twins): the tables and the step of the platoon's own episode -- the device's
+            # counters (per-platoon episodes), or the host loop's step for every platoon
+            ld, tag = self.lead, "_lead"
+            per_platoon = self.auto_reset == "platoon"
+            lead = (ld["n"], ld["T"], ptr(ld["table"]), ptr(ld["noise"]), ptr(ld["gaussian"]), ptr(env.ep_len) if per_platoon else None,
+                    0 if per_platoon else min(self.ep_step, ld["T"] - 1))
         if self.levels is not None:
             # training under disturbances (avd_step_fused_dist_f32): the level's plant, the observation of the new state with the next
             # observation counter, the replay row from the observation buffers -- which swap where x and x_prev do
             env.obs, env.obs_prev = env.obs_prev, env.obs
             env.obs_counter += 1
-            fn, key = ("avd_step_fused_dist_f32", (self.seed,)) if self.seeds is None else ("avd_step_fused_dist_seeds_f32", (ptr(env.d_seeds), self.E))
+            fn, key = (f"avd_step_fused_dist{tag}_f32", (self.seed,)) if self.seeds is None else (f"avd_step_fused_dist{tag}_seeds_f32", (ptr(env.d_seeds), self.E))
             call(fn, ptr(env.d_consts), self.P, self.L, self.S, ptr(env.x_prev), ptr(env.x), ptr(env.prev_a),
                  ptr(env.cum_accel), ptr(env.reward), ptr(env.term), ptr(env.done), ptr(env.any_done), ptr(other),
                  ptr(self.actor_out), ptr(ou.state), ptr(self.actions), ptr(self.leader_exog), conf.theta, ou.mean, conf.ou_dt,
                  conf.std_dev, conf.action_low, conf.action_high, conf.reset_max_u, 1 if conf.rand_gen == conf.uniform else 0,
                  *key, ou.calls, self.exog_calls, ptr(rp.ring), rp.cap, rp.buffer_counter, ptr(self.ep_reward),
                  len(self.levels), env.h_levels, ptr(env.d_levels), ptr(env.d_plant), ptr(env.obs_prev), ptr(env.obs),
-                 ptr(env.link_hist), ptr(env.link_recv), env.obs_counter, stream_handle())
+                 ptr(env.link_hist), ptr(env.link_recv), env.obs_counter, *lead, stream_handle())
         elif self.d_hp is not None:  # a sweep: each platoon's OU theta and scale from its experiment's row (avd_step_fused_hp_f32)
             call("avd_step_fused_hp_f32", ptr(env.d_consts), self.P, self.L, self.S, ptr(env.x_prev), ptr(env.x), ptr(env.prev_a),
                  ptr(env.cum_accel), ptr(env.reward), ptr(env.term), ptr(env.done), ptr(env.any_done), ptr(other), ptr(self.actor_out),
@@ -437,12 +485,14 @@ class VecTrainer:
                  self.exog_calls, ptr(rp.ring), rp.cap, rp.buffer_counter, ptr(self.ep_reward), stream_handle())
         else:
             # the seed argument: the scalar seed, or (a batch) the seed table and its length (avd_step_fused_seeds_f32)
-            fn, key = ("avd_step_fused_f32", (self.seed,)) if self.seeds is None else ("avd_step_fused_seeds_f32", (ptr(env.d_seeds), self.E))
+            # (under manoeuvres without levels the twin also takes the level count the assignment divides by: 1)
+            fn, key = (f"avd_step_fused{tag}_f32", (self.seed,)) if self.seeds is None else (f"avd_step_fused{tag}_seeds_f32", (ptr(env.d_seeds), self.E))
             call(fn, ptr(env.d_consts), self.P, self.L, self.S, ptr(env.x_prev), ptr(env.x), ptr(env.prev_a),
                  ptr(env.cum_accel), ptr(env.reward), ptr(env.term), ptr(env.done), ptr(env.any_done), ptr(other),
                  ptr(self.actor_out), ptr(ou.state), ptr(self.actions), ptr(self.leader_exog), conf.theta, ou.mean, conf.ou_dt,
                  conf.std_dev, conf.action_low, conf.action_high, conf.reset_max_u, 1 if conf.rand_gen == conf.uniform else 0,
-                 *key, ou.calls, self.exog_calls, ptr(rp.ring), rp.cap, rp.buffer_counter, ptr(self.ep_reward), stream_handle())
+                 *key, ou.calls, self.exog_calls, ptr(rp.ring), rp.cap, rp.buffer_counter, ptr(self.ep_reward),
+                 *(lead + (1,) if lead else ()), stream_handle())
         ou.calls += 1
         self.exog_calls += 1
         env.step_count += 1

@@ -661,6 +661,50 @@ int avd_observe_seeds_f32(int P, int L, const float* x, float* obs, int n_levels
                           float* link_recv, const uint64_t* d_seeds, int n_groups, uint64_t obs_counter,
                           const int32_t* only_where_zero, const int32_t* run_if_nonzero, void* stream);
 
+/* ---- training under leader manoeuvres: the fused step with the leader's input from a manoeuvre table -------------------------------
+ * A run has n_manoeuvres (1 .. AVD_TRAIN_MAX_MANOEUVRES) training manoeuvres; platoon p trains under manoeuvre (q / n_levels) %
+ * n_manoeuvres for the whole run, q its solo-run platoon index (an experiment batch: g / n_groups) and n_levels the disturbance level
+ * count (1 without levels): levels and manoeuvres cross. Only the leader's exogenous input changes; leader_exog[p] receives the value
+ * used, every other output and every Philox draw is avd_step_fused_f32's (avd_step_fused_dist_f32's). With d the unit draw the nominal
+ * step makes for this platoon and step (same key, exog_counter, index, stream; uniform or normal by exog_uniform):
+ *   d_gaussian[m] != 0: the input is d * d_noise[m] -- with d_noise[m] = exog_scale, bit for bit the nominal launch;
+ *   otherwise: d_table[m][k], plus d_noise[m] * d (product rounded, then one add) when d_noise[m] != 0; k = ep_len[p], the step of the
+ *     platoon's own episode as avd_episode_end_f32 maintains it, or ep_step for every platoon when ep_len is NULL; k is clamped to
+ *     0 .. T - 1.
+ * d_table [n_manoeuvres][T] float32, d_noise [n_manoeuvres] float32 and d_gaussian [n_manoeuvres] bytes are device memory, made on
+ * the host (no transcendental is evaluated on the device); exog_scale is unread. Refused on the host: null tables, n_manoeuvres
+ * outside 1 .. 16, T < 4, a null ep_len with ep_step outside [0, T), n_levels < 1. */
+#define AVD_TRAIN_MAX_MANOEUVRES 16
+int avd_step_fused_lead_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out, float* prev_a,
+    float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done, int32_t* any_done_other, const float*
+    actor_out, float* ou_state, float* action, float* leader_exog, float ou_theta, float ou_mean, float ou_dt, float ou_std_dev,
+    float action_low, float action_high, float exog_scale, int exog_uniform, uint64_t seed, uint64_t ou_counter, uint64_t
+    exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward, int n_manoeuvres, int T, const float* d_table,
+    const float* d_noise, const uint8_t* d_gaussian, const int32_t* ep_len, int ep_step, int n_levels, void* stream);
+int avd_step_fused_lead_seeds_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out, float*
+    prev_a, float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done, int32_t* any_done_other, const float*
+    actor_out, float* ou_state, float* action, float* leader_exog, float ou_theta, float ou_mean, float ou_dt, float ou_std_dev,
+    float action_low, float action_high, float exog_scale, int exog_uniform, const uint64_t* d_seeds, int n_groups, uint64_t
+    ou_counter, uint64_t exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward, int n_manoeuvres, int T,
+    const float* d_table, const float* d_noise, const uint8_t* d_gaussian, const int32_t* ep_len, int ep_step, int n_levels, void*
+    stream);
+int avd_step_fused_dist_lead_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out, float*
+    prev_a, float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done, int32_t* any_done_other, const float*
+    actor_out, float* ou_state, float* action, float* leader_exog, float ou_theta, float ou_mean, float ou_dt, float ou_std_dev,
+    float action_low, float action_high, float exog_scale, int exog_uniform, uint64_t seed, uint64_t ou_counter, uint64_t
+    exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward, int n_levels, const avd_train_level* h_levels,
+    const avd_train_level* d_levels, const float* d_plant, const float* obs_in, float* obs_out, float* link_hist, float* link_recv,
+    uint64_t obs_counter, int n_manoeuvres, int T, const float* d_table, const float* d_noise, const uint8_t* d_gaussian, const
+    int32_t* ep_len, int ep_step, void* stream);
+int avd_step_fused_dist_lead_seeds_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out, float*
+    prev_a, float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done, int32_t* any_done_other, const float*
+    actor_out, float* ou_state, float* action, float* leader_exog, float ou_theta, float ou_mean, float ou_dt, float ou_std_dev,
+    float action_low, float action_high, float exog_scale, int exog_uniform, const uint64_t* d_seeds, int n_groups, uint64_t
+    ou_counter, uint64_t exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward, int n_levels, const
+    avd_train_level* h_levels, const avd_train_level* d_levels, const float* d_plant, const float* obs_in, float* obs_out, float*
+    link_hist, float* link_recv, uint64_t obs_counter, int n_manoeuvres, int T, const float* d_table, const float* d_noise, const
+    uint8_t* d_gaussian, const int32_t* ep_len, int ep_step, void* stream);
+
 /* D[M][Nc] (f32, ldd) = A[M][K] . B[Nc][K]^T with bf16 operands (K contiguous, K % 64 == 0) and f32 accumulation: the
  * GEMM under avd_learn_shared_bf16, exposed for parity tests. A and B must be readable up to the next multiple of 256
  * rows. */
