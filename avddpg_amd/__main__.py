@@ -202,6 +202,69 @@ def _write_suite(d, conf, res, tags, args):
     return nominal
 
 
+def _keep_start(vt, args):
+    """--keep_best: the snapshot slabs and the rollout batch, then the evaluation at step 0. Without the flag: nothing."""
+    if getattr(args, "keep_best", None) is not None:
+        vt.enable_keep_best(args.keep_best_seeds)
+        vt.keep_best_update(0)
+
+
+def _keep_tick(vt, args, k, total):
+    """--keep_best: the evaluation after step k, at every multiple of the interval and at the last step."""
+    if getattr(args, "keep_best", None) is not None and (k % args.keep_best == 0 or k == total):
+        vt.keep_best_update(k)
+
+
+class _KeepResults:
+    """What a --keep_best run writes, read once after training: the retained actors (VecTrainer.best_agents), their simulation rewards
+    (run_simulations on them) and suite (--scenarios), the units' best score and step and the final actors' score."""
+
+    def __init__(self, vt, args):
+        self.vt, self.args = vt, args
+        self.agents = vt.best_agents()
+        self.sims = vt.run_simulations(agents=self.agents)
+        self.score, self.step = vt.best_scores()
+        self.final = vt.last_scores()
+        self.record = [["interval", int(args.keep_best)], ["seeds", list(vt._keep["seeds"])], ["evaluations", int(vt._keep["evaluations"])]]
+        self.suite = None
+        if args.scenarios is not None:
+            kw = dict(agents=self.agents, **_suite(args))
+            self.suite = vt.evaluate_scenarios(**kw) if _disturb(args) is None else vt.evaluate_robustness(disturbances=_disturb(args), **kw)
+
+    def write(self, d, conf, n_save, e=None):
+        """<d>/best/ and <d>/best.csv of a run (e None) or of experiment e of a batch, and conf.keep_best. conf: the directory's Config as
+        its conf.json is about to be written."""
+        import copy
+
+        import numpy as np
+
+        from . import artifacts
+
+        vt, args = self.vt, self.args
+        if e is None:
+            units, sims, agents, suite, P = range(len(self.score)), self.sims, self.agents, self.suite, vt.P
+        else:
+            units = [e] if vt.shared else range(e * vt.P_exp, (e + 1) * vt.P_exp)
+            sims, agents, P = self.sims[e], self.agents.experiment_view(e, vt.E, vt.M, vt.shared), vt.P_exp
+            suite = None if self.suite is None else _slice(self.suite, e)
+        with open(os.path.join(d, "best.csv"), "w") as f:
+            f.write("unit,best_step,best_score,final_score\n")
+            for i, u in enumerate(units):
+                f.write(f"{i},{int(self.step[u])},{'%.9g' % float(self.score[u])},{'%.9g' % float(self.final[u])}\n")
+        bd = os.path.join(d, "best")
+        os.makedirs(bd, exist_ok=True)
+        artifacts.save_agents(bd, agents, n_save, vt.M, shared=vt.shared)
+        cb = copy.copy(conf)
+        cb.pl_rews_for_simulations = list(sims)
+        cb.pl_rew_for_simulation = float(np.average(sims))
+        cb.saved_platoons = int(n_save)
+        cb.keep_best = self.record
+        if suite is not None:
+            _write_suite(bd, cb, suite, range(1, P + 1), args)
+        artifacts.config_writer(os.path.join(bd, "conf.json"), cb)
+        conf.keep_best = self.record[:2] + [["best_pl_rew_for_simulation", cb.pl_rew_for_simulation]]
+
+
 def get_cmdl_args(argv, conf):
     ap = argparse.ArgumentParser(prog="python -m avddpg_amd", description="avddpg hot path on MI355X")
     sub = ap.add_subparsers(dest="mode")
@@ -284,6 +347,18 @@ def get_cmdl_args(argv, conf):
                          "reference's training input, a clean share (noise: its scale, default reset_max_u; no amp or period). conf.json "
                          "records the manoeuvres as train_leader. Composes with --seeds, --train_disturb, --scenarios and --disturb; not with "
                          "--sweep / --pbt, --rng host, the centralized framework or a process group (not in the reference CLI)")
+    tr.add_argument("--keep_best", type=int, default=None, metavar="STEPS",
+                    help="keep the best actors seen in training, on the device: at step 0, at every multiple of STEPS and at the last step "
+                         "one evaluator rollout launch scores every rollout group (a platoon's actors; the shared sets; each experiment's of "
+                         "--seeds / --sweep / --pbt) on the undisturbed evaluator, and a group whose mean score beats its best so far has its "
+                         "actors copied into a snapshot, without a host round trip. Writes <dir>/best/ (the retained actors of the saved "
+                         "platoons under the usual file names, with a conf.json: `esim <dir>/best` works) and <dir>/best.csv (unit, "
+                         "best_step, best_score, final_score); conf.json gains keep_best, sweep.csv the column best_pl_rew_for_simulation. "
+                         "The saved final actors and every other output stay what they are without the flag. Not under a process group of "
+                         "more than one rank (not in the reference CLI)")
+    tr.add_argument("--keep_best_seeds", type=str, default=None, metavar="LIST",
+                    help="--keep_best: the evaluation seeds the retention score averages over (e.g. 6,7-9; default: the configuration's "
+                         "evaluation_seed)")
     _scenario_flags(tr, "after training, beside the simulation rewards:")
     tr.add_argument("--out", type=str, default=".outputs")
     es = sub.add_parser("esim", help="run in evaluation/simulator mode")
@@ -356,6 +431,18 @@ def get_cmdl_args(argv, conf):
             args.pbt, args.pbt_fraction, args.pbt_perturb, _ = check_pbt(args.pbt, fraction, perturb, n_exp, swept)
         except ValueError as e:
             ap.error(f"--pbt: {e}")
+    if getattr(args, "keep_best_seeds", None) is not None and args.keep_best is None:
+        ap.error("--keep_best_seeds needs --keep_best")
+    if getattr(args, "keep_best", None) is not None:
+        if args.keep_best < 1:
+            ap.error(f"--keep_best: STEPS={args.keep_best} must be >= 1")
+        if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+            ap.error("--keep_best is not available under a process group of more than one rank (the snapshot is not gathered across ranks)")
+        if args.keep_best_seeds is not None:
+            try:
+                args.keep_best_seeds = parse_seeds(args.keep_best_seeds)
+            except ValueError as e:
+                ap.error(str(e).replace("--seeds", "--keep_best_seeds"))
     ev = getattr(args, "eval_platoons", None)
     if ev is not None:
         if args.episodes != "platoon":
@@ -416,6 +503,7 @@ def main(argv=None, conf=None):
                     raise
                 raise SystemExit(f"--train_disturb: {e}")
             vt.reset_episode()
+            _keep_start(vt, args)
             rng_state = np.random.get_state()
 
             def score():  # workers/evaluator.py:145 on platoon 1's actors (the evaluator reseeds the global legacy RNG: put it back)
@@ -442,6 +530,7 @@ def main(argv=None, conf=None):
                 f.write(f"0,0,,,{score():.3f}{many()}\n")
                 for k in range(1, conf.total_time_steps + 1):
                     vt.step()
+                    _keep_tick(vt, args, k, conf.total_time_steps)
                     if k % args.report_every == 0 or k == conf.total_time_steps:
                         r, ln, n = vt.env.pop_episode_stats()
                         f.write(f"{k},{n},{r:.5f},{ln:.2f},{score():.3f}{many()}\n")
@@ -457,7 +546,10 @@ def main(argv=None, conf=None):
                 if args.train_disturb is None:
                     raise
                 raise SystemExit(f"--train_disturb: {e}")
-            ep, avg = vt.run()
+            _keep_start(vt, args)
+            ep, avg = vt.run(keep_best_every=args.keep_best)
+            if args.keep_best is not None and vt.steps_total % args.keep_best:  # the last step
+                vt.keep_best_update(vt.steps_total)
             artifacts.generate_csvs(base, conf, ep, avg)
         # Trainer.run / run_simulations (workers/trainer.py:277-280, 537-550): every platoon's evaluator score / re_scalar and their
         # average, written into conf.json (the evaluator reseeds the global legacy RNG; run_many puts it back)
@@ -478,6 +570,8 @@ def main(argv=None, conf=None):
                                    "weighted_window closed episodes")
         _record_train_levels(conf, args)
         _record_train_leader(conf, args)
+        if args.keep_best is not None:
+            _KeepResults(vt, args).write(base, conf, n_save)
         artifacts.config_writer(os.path.join(base, "conf.json"), conf)
         print(base)
     elif args.mode == "esim":
@@ -528,9 +622,11 @@ def train_sweep(args, conf, base):
 
     with open(os.path.join(base, "sweep.csv"), "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(["label", *SWEEP_NAMES, "seed", "pl_rew_for_simulation", "final_evaluator_score"])
+        keep = args.keep_best is not None  # one more column, only under the flag
+        w.writerow(["label", *SWEEP_NAMES, "seed", "pl_rew_for_simulation", "final_evaluator_score"] + (["best_pl_rew_for_simulation"] if keep else []))
         for (label, _, k), (ce, last) in zip(exps, rows):
-            w.writerow([label, *[repr(float(getattr(ce, n))) for n in SWEEP_NAMES], k, repr(ce.pl_rew_for_simulation), last])
+            w.writerow([label, *[repr(float(getattr(ce, n))) for n in SWEEP_NAMES], k, repr(ce.pl_rew_for_simulation), last] +
+                       ([repr(dict(ce.keep_best)["best_pl_rew_for_simulation"])] if keep else []))
 
 
 def train_seed_batch(args, conf, base, experiments=None):
@@ -567,6 +663,7 @@ def train_seed_batch(args, conf, base, experiments=None):
     except ValueError as e:
         raise SystemExit(f"{flag}: {e}")
     vt.reset_episode()
+    _keep_start(vt, args)
     P = vt.P_exp
     n_eval = None if args.eval_platoons is None else (P if args.eval_platoons == "all" else min(P, int(args.eval_platoons)))
     last = [None] * E
@@ -613,6 +710,7 @@ def train_seed_batch(args, conf, base, experiments=None):
             f.write(f"0,0,,,{pt}\n")
         for k in range(1, conf.total_time_steps + 1):
             vt.step()
+            _keep_tick(vt, args, k, conf.total_time_steps)  # (before a PBT generation at the same step: the experiment's own actors)
             if k % args.report_every == 0 or k == conf.total_time_steps:
                 r, ln, n = vt.env.pop_episode_stats(per_experiment=True)
                 for e, (f, pt) in enumerate(zip(files, points())):
@@ -632,6 +730,7 @@ def train_seed_batch(args, conf, base, experiments=None):
     if args.scenarios is not None:
         suite = vt.evaluate_scenarios(**_suite(args)) if _disturb(args) is None else vt.evaluate_robustness(disturbances=_disturb(args), **_suite(args))
     n_save = min(P, 4 if args.save_platoons is None else args.save_platoons)
+    kept = _KeepResults(vt, args) if getattr(args, "keep_best", None) is not None else None
     done = []
     for e, (k, d) in enumerate(zip(seeds, dirs)):
         artifacts.save_agents(d, vt.experiment_agents(e), n_save, vt.M, shared=vt.shared)
@@ -655,6 +754,8 @@ def train_seed_batch(args, conf, base, experiments=None):
         _record_train_leader(ce, args)
         if suite is not None:
             _write_suite(d, ce, _slice(suite, e), range(1, P + 1), args)
+        if kept is not None:  # (after everything else the directory's conf.json records: best/conf.json carries it too)
+            kept.write(d, ce, n_save, e)
         artifacts.config_writer(os.path.join(d, "conf.json"), ce)
         done.append((ce, last[e]))
     return done

@@ -17,6 +17,11 @@ AVD_EVAL_NMETRIC = 8
 AVD_EVAL_MAX_DELAY = 15
 AVD_TRAIN_MAX_LEVELS = 16
 AVD_TRAIN_MAX_MANOEUVRES = 16
+# csrc/best.hip's launch shape (avd_keep_best_f32's copy): threads per block, float4 groups per thread and work item, float4 groups of a
+# snapshot row per work item, and the grid cap the blocks stride over the work items under
+KEEP_THREADS, KEEP_UNR = 256, 4
+KEEP_CHUNK4 = KEEP_THREADS * KEEP_UNR
+KEEP_MAX_BLOCKS = 8192
 
 
 class AvdError(RuntimeError):
@@ -109,6 +114,7 @@ _PROTOS = {
     "avd_learn_set_split_hp_f16x3": [_LP, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _P, _P, _P, C.c_size_t, _P, _i, _i, _P],
     "avd_actor_forward_set_f32": [_LP, _i, _i, _P, _P, _P, _i, _f, _P, _P, _P],
     "avd_copy_experiment_sets_f32": [_LP, _i, _i, _i, _P, _i, _P, _P, _P, _P, _P, _P, _P, _P],
+    "avd_keep_best_f32": [_LP, _i, _i, _i, _i, _P, _P, _P, _P, _P, _i64, _P, _P, _P, _P, _P, _P],
     "avd_replay_add_f32": [_i, _i, _i, _i, _P, _i64, _P, _P, _i, _P, _P, _P],
     "avd_replay_indices": [_i, _i, _i, _u64, _u64, _P, _P],
     "avd_replay_gather_f32": [_i, _i, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P],

@@ -158,6 +158,24 @@ def check_train_leader(conf, train_leader, rng, group, auto_reset, fused_step=No
     return out
 
 
+def check_keep_best(world_size):
+    """Why a run cannot keep the best actors seen (VecTrainer.enable_keep_best), raised as a ValueError -- or None. Called before
+    anything is allocated or launched."""
+    if int(world_size) > 1:
+        raise ValueError("keeping the best actors runs on one rank: nothing is gathered across a process group of more than one rank")
+
+
+def sequential_mean_f32(x):
+    """The retention score of csrc/best.hip on the host: the float32 sum of x in memory order, from the first element, one add at a
+    time, divided by float32(len(x)) (np.average / np.sum add pairwise from 8 elements on)."""
+    x = np.asarray(x, dtype=np.float32).reshape(-1)
+    s = x[0]
+    with np.errstate(all="ignore"):  # (an infinite or NaN counter is a score like any other)
+        for v in x[1:]:
+            s = np.float32(s + v)
+        return np.float32(s / np.float32(x.size))
+
+
 # The set learners' largest weight-set count (the shape checks of csrc/fset.hip and csrc/fsplit.hip); the others take any count.
 SET_ENGINE_MAX_SETS = {"fused": 64, "fused3": 64}
 
@@ -352,6 +370,8 @@ class VecTrainer:
             import torch.distributed as _td
             ws = _td.get_world_size(group)
         self._equal_shards = abs(self.total_platoons - self.P * ws) < 0.5
+        self.world_size = ws
+        self._keep = None  # retention of the best actors seen (enable_keep_best); None: nothing allocated, no entry point called
         self._step_parity = 0
         self._added = False
         if self.manoeuvres is not None:  # the manoeuvre tables, uploaded once; the episode's step per platoon exists from the start
@@ -781,40 +801,46 @@ class VecTrainer:
                 self.all_avg_reward_lists[p][m].append(
                     np.mean(self.all_ep_reward_lists[p][m][-self.conf.reward_averaging_window:]))
 
-    def run(self, number_of_episodes=None):
-        """trainer.py:232-273"""
+    def run(self, number_of_episodes=None, keep_best_every=None):
+        """trainer.py:232-273. keep_best_every (after enable_keep_best): a keep_best_update at every multiple of that many steps."""
         conf = self.conf
+        every = int(keep_best_every) if keep_best_every else 0
         n = conf.number_of_episodes if number_of_episodes is None else number_of_episodes
         for ep in range(n):
             self.episode = ep
             self.reset_episode()
             for i in range(conf.steps_per_episode):
-                if self.step(ep, i):
+                stop = self.step(ep, i)
+                if every and self.steps_total % every == 0:
+                    self.keep_best_update(self.steps_total)
+                if stop:
                     break
             self.update_reward_list(ep)
         return self.all_ep_reward_lists, self.all_avg_reward_lists
 
-    def evaluator_scores(self, platoons=None):
+    def evaluator_scores(self, platoons=None, agents=None):
         """workers/evaluator.py:145 score of the CURRENT actors of each of this rank's ``platoons`` (default: all), from one
         launch of the evaluator rollout kernel (evaluator.run_many); float32 [len(platoons)]. Shared sets: one rollout.
-        A seed batch: ``platoons`` index each experiment's own platoons; float32 [E, len(platoons)], still one launch."""
+        A seed batch: ``platoons`` index each experiment's own platoons; float32 [E, len(platoons)], still one launch.
+        agents: score this group's actors instead (laid out as self.agents: best_agents())."""
         from . import evaluator
 
+        agents = self.agents if agents is None else agents
         if self.seeds is not None:
             E, M = self.E, self.M
             platoons = list(range(self.P_exp)) if platoons is None else list(platoons)
             if self.shared:  # one rollout per experiment, on its sets e*M .. e*M+M-1
-                sc = evaluator.run_many(self.conf, self.agents, list(range(E)), set_mod=M, set_bases=[e * M for e in range(E)])[0]
+                sc = evaluator.run_many(self.conf, agents, list(range(E)), set_mod=M, set_bases=[e * M for e in range(E)])[0]
                 return np.repeat(sc[:, :1], len(platoons), axis=1)
             glob = [vec.batch_platoon(e, p, E) for e in range(E) for p in platoons]
-            return evaluator.run_many(self.conf, self.agents, glob)[0][:, 0].reshape(E, len(platoons))
+            return evaluator.run_many(self.conf, agents, glob)[0][:, 0].reshape(E, len(platoons))
         platoons = list(range(self.P)) if platoons is None else list(platoons)
         if self.shared:
-            sc = evaluator.run_many(self.conf, self.agents, [0], set_mod=self.M)[0]
+            sc = evaluator.run_many(self.conf, agents, [0], set_mod=self.M)[0]
             return np.repeat(sc[:, 0], len(platoons))
-        return evaluator.run_many(self.conf, self.agents, platoons)[0][:, 0]
+        return evaluator.run_many(self.conf, agents, platoons)[0][:, 0]
 
-    def evaluate_scenarios(self, scenarios, seeds=None, platoons=None, amp=None, period_s=10.0):
+    def evaluate_scenarios(self, scenarios, seeds=None, platoons=None, amp=None, period_s=10.0, agents=None):
         """The CURRENT actors of each of this rank's ``platoons`` (default: all) over leader scenarios x evaluation seeds, from one
         launch of the scenario evaluator (evaluator.run_cases): a CaseResults with scores [P, scen, seed], counters [P, scen, seed, M]
         and metrics {name: [P, scen, seed, L]}. Shared sets: one group of rollouts, repeated per platoon.
@@ -822,26 +848,27 @@ class VecTrainer:
         ([E, P, scen, seed, ...]), still from one launch; experiment e's slice equals run_cases on experiment_agents(e)."""
         from . import evaluator
 
+        agents = self.agents if agents is None else agents  # (or a group laid out like it: best_agents())
         kw = dict(scenarios=scenarios, seeds=seeds, amp=amp, period_s=period_s)
         if self.seeds is not None:
             E, M = self.E, self.M
             platoons = list(range(self.P_exp)) if platoons is None else list(platoons)
             n = len(platoons)
             if self.shared:  # one group per experiment, on its sets e*M .. e*M+M-1
-                r = evaluator.run_cases(self.conf, self.agents, list(range(E)), set_mod=M, set_bases=[e * M for e in range(E)], **kw)
+                r = evaluator.run_cases(self.conf, agents, list(range(E)), set_mod=M, set_bases=[e * M for e in range(E)], **kw)
                 lift = lambda x: np.repeat(x[:, None], n, axis=1)
             else:
-                r = evaluator.run_cases(self.conf, self.agents, [vec.batch_platoon(e, p, E) for e in range(E) for p in platoons], **kw)
+                r = evaluator.run_cases(self.conf, agents, [vec.batch_platoon(e, p, E) for e in range(E) for p in platoons], **kw)
                 lift = lambda x: x.reshape(E, n, *x.shape[1:])
             return evaluator.CaseResults(r.scenarios, r.seeds, r.T, lift(r.scores), lift(r.counters), {k: lift(v) for k, v in r.metrics.items()})
         platoons = list(range(self.P)) if platoons is None else list(platoons)
         if self.shared:
-            r = evaluator.run_cases(self.conf, self.agents, [0], set_mod=self.M, **kw)
+            r = evaluator.run_cases(self.conf, agents, [0], set_mod=self.M, **kw)
             rep = lambda x: np.repeat(x, len(platoons), axis=0)
             return evaluator.CaseResults(r.scenarios, r.seeds, r.T, rep(r.scores), rep(r.counters), {k: rep(v) for k, v in r.metrics.items()})
-        return evaluator.run_cases(self.conf, self.agents, platoons, **kw)
+        return evaluator.run_cases(self.conf, agents, platoons, **kw)
 
-    def evaluate_robustness(self, scenarios, disturbances, seeds=None, platoons=None, amp=None, period_s=10.0):
+    def evaluate_robustness(self, scenarios, disturbances, seeds=None, platoons=None, amp=None, period_s=10.0, agents=None):
         """evaluate_scenarios under disturbances: the CURRENT actors of each of this rank's ``platoons`` over leader scenarios x
         [nominal, *disturbances] x evaluation seeds, from one launch of the disturbed scenario evaluator (evaluator.run_disturbed): a
         DisturbedResults with scores [P, scen, dist, seed], counters [P, scen, dist, seed, M] and metrics {name: [P, scen, dist, seed,
@@ -849,6 +876,7 @@ class VecTrainer:
         scen, dist, seed, ...]); experiment e's slice equals run_disturbed on experiment_agents(e)."""
         from . import evaluator
 
+        agents = self.agents if agents is None else agents  # (or a group laid out like it: best_agents())
         kw = dict(scenarios=scenarios, disturbances=disturbances, seeds=seeds, amp=amp, period_s=period_s)
         mapped = lambda r, f: evaluator.DisturbedResults(r.scenarios, r.disturbances, r.seeds, r.T, f(r.scores), f(r.counters),
                                                          {k: f(v) for k, v in r.metrics.items()})
@@ -857,24 +885,106 @@ class VecTrainer:
             platoons = list(range(self.P_exp)) if platoons is None else list(platoons)
             n = len(platoons)
             if self.shared:  # one group per experiment, on its sets e*M .. e*M+M-1
-                r = evaluator.run_disturbed(self.conf, self.agents, list(range(E)), set_mod=M, set_bases=[e * M for e in range(E)], **kw)
+                r = evaluator.run_disturbed(self.conf, agents, list(range(E)), set_mod=M, set_bases=[e * M for e in range(E)], **kw)
                 return mapped(r, lambda x: np.repeat(x[:, None], n, axis=1))
-            r = evaluator.run_disturbed(self.conf, self.agents, [vec.batch_platoon(e, p, E) for e in range(E) for p in platoons], **kw)
+            r = evaluator.run_disturbed(self.conf, agents, [vec.batch_platoon(e, p, E) for e in range(E) for p in platoons], **kw)
             return mapped(r, lambda x: x.reshape(E, n, *x.shape[1:]))
         platoons = list(range(self.P)) if platoons is None else list(platoons)
         if self.shared:
-            r = evaluator.run_disturbed(self.conf, self.agents, [0], set_mod=self.M, **kw)
+            r = evaluator.run_disturbed(self.conf, agents, [0], set_mod=self.M, **kw)
             return mapped(r, lambda x: np.repeat(x, len(platoons), axis=0))
-        return evaluator.run_disturbed(self.conf, self.agents, platoons, **kw)
+        return evaluator.run_disturbed(self.conf, agents, platoons, **kw)
 
-    def run_simulations(self):
+    def run_simulations(self, agents=None):
         """Trainer.run_simulations (workers/trainer.py:537-550): every local platoon's evaluator score over steps_per_episode
         steps divided by re_scalar -- the values the reference appends to conf.pl_rews_for_simulations (:549). Plots and the
         second, manual_timestep_override rollout are out of scope; a multi-rank run scores its own platoons.
         A seed batch: one such list per experiment ([E][P_exp]), from one rollout launch."""
         if self.seeds is not None:
-            return [[float(r / self.conf.re_scalar) for r in row] for row in self.evaluator_scores()]
-        return [float(r / self.conf.re_scalar) for r in self.evaluator_scores()]
+            return [[float(r / self.conf.re_scalar) for r in row] for row in self.evaluator_scores(agents=agents)]
+        return [float(r / self.conf.re_scalar) for r in self.evaluator_scores(agents=agents)]
+
+    # ---- retention of the best actors seen ---------------------------------------------------------------------------------------
+    def enable_keep_best(self, seeds=None):
+        """Keep, on the device, the best actors each rollout group of the evaluator has had at any keep_best_update: prepares ONE
+        rollout batch over exactly the groups evaluator_scores() scores (a *unit*: a platoon's M per-agent sets -- P units; the shared M
+        sets -- one unit; a seed batch: experiment e's platoon p, unit e * P_exp + p, or its M shared sets, unit e) on the evaluation
+        ``seeds`` (default: conf.evaluation_seed), allocates the snapshot slabs (actor span and actor BN statistics per set, a score and
+        a step per unit) and fills the snapshot with the current actors, at score -inf and step -1. The caller's global np.random state
+        is restored. Refused under a process group of more than one rank (nothing is gathered across ranks)."""
+        check_keep_best(getattr(self, "world_size", 1))
+        import ctypes as C
+
+        from . import evaluator
+
+        seeds = [int(self.conf.evaluation_seed)] if seeds is None else [int(k) for k in seeds]
+        ag, M, E = self.agents, self.M, self.E
+        if self.seeds is not None and self.shared:
+            batch = evaluator.prepare_many(self.conf, ag, list(range(E)), set_mod=M, seeds=seeds, set_bases=[e * M for e in range(E)])
+        elif self.seeds is not None:
+            batch = evaluator.prepare_many(self.conf, ag, [vec.batch_platoon(e, p, E) for e in range(E) for p in range(self.P_exp)], seeds=seeds)
+        elif self.shared:
+            batch = evaluator.prepare_many(self.conf, ag, [0], set_mod=M, seeds=seeds)
+        else:
+            batch = evaluator.prepare_many(self.conf, ag, list(range(self.P)), seeds=seeds)
+        NS = batch.NS
+        d_base = batch.set_base[::NS].contiguous()  # a rollout's base is its unit's: rollout u * NS + k
+        h = [int(b) for b in d_base.cpu().tolist()]
+        n_units, lay, dev = len(h), ag.lay, self.device
+        rows = (d_base.long().view(-1, 1) + torch.arange(M, device=dev).view(1, -1)).reshape(-1)
+        self._keep = dict(batch=batch, seeds=seeds, NS=NS, n_units=n_units, d_base=d_base, h_base=(C.c_int32 * n_units)(*h), rows=rows,
+                          theta=ag.theta[rows, :lay.actor_size].contiguous(), stats=ag.stats[rows, :lay.cmms].contiguous(),
+                          score=torch.full((n_units,), float("-inf"), dtype=torch.float32, device=dev),
+                          step=torch.full((n_units,), -1, dtype=torch.int64, device=dev),
+                          improved=torch.zeros(n_units, dtype=torch.int32, device=dev), evaluations=0)
+
+    def keep_best_update(self, step):
+        """One evaluation: the rollout launch over every unit on the CURRENT actors, then the keep launches (AgentGroup.keep_best) -- a
+        unit whose score, the sequential float32 mean of its NS x M counters, is above its best so far has its actors copied into the
+        snapshot and ``step`` recorded. All on the current stream, no host synchronisation; nothing of the training state is written."""
+        k = self._keep
+        if k is None:
+            raise ValueError("keep_best_update needs enable_keep_best() first")
+        k["batch"].launch()
+        self.agents.keep_best(k["d_base"], k["h_base"], self.M, k["NS"], k["batch"].counters, step, k["theta"], k["stats"], k["score"],
+                              k["step"], k["improved"])
+        k["evaluations"] += 1
+
+    def best_scores(self):
+        """(score float32 [n_units], step int64 [n_units]) of the snapshot: each unit's best score and the step it was taken at (-inf and
+        -1 before the first evaluation). Synchronises. Units as in enable_keep_best."""
+        k = self._keep
+        if k is None:
+            raise ValueError("best_scores needs enable_keep_best() first")
+        return k["score"].cpu().numpy(), k["step"].cpu().numpy()
+
+    def last_scores(self):
+        """The retention score of the LAST evaluation's actors per unit, float32 [n_units] (the same formula on the counters the last
+        keep_best_update left; after an evaluation at the last step: the final actors'). Synchronises."""
+        k = self._keep
+        if k is None or not k["evaluations"]:
+            raise ValueError("last_scores needs a keep_best_update() first")
+        c = k["batch"].counters.cpu().numpy().reshape(k["n_units"], -1)
+        return np.array([sequential_mean_f32(row) for row in c], dtype=np.float32)
+
+    def best_agents(self):
+        """The retained actors as an AgentGroup laid out like self.agents (a copy: what artifacts.save_agents, evaluator.run_many,
+        run_cases and run_disturbed take, and experiment_view for a seed batch): its online slabs are clones of the current ones at the
+        full theta_size / stats_size stride with every unit's actor blocks and actor BN statistics replaced by the snapshot's. The
+        critic blocks, and the target slabs (theta_t, stats_t: the trainer's own tensors, not copies), are the FINAL ones -- critics,
+        targets and optimiser state are not part of the snapshot. Built on demand, at the end of a run: it clones the online slabs."""
+        import copy
+
+        k = self._keep
+        if k is None:
+            raise ValueError("best_agents needs enable_keep_best() first")
+        lay, g = self.agents.lay, copy.copy(self.agents)
+        g.theta, g.stats = self.agents.theta.clone(), self.agents.stats.clone()
+        g.theta[k["rows"], :lay.actor_size] = k["theta"]
+        g.stats[k["rows"], :lay.cmms] = k["stats"]
+        for name in ("m", "v", "step", "theta_alt", "hp"):  # optimiser state (and a sweep's table) stays with the trainer
+            setattr(g, name, None)
+        return g
 
     def experiment_agents(self, e):
         """Experiment e's actors / critics (a seed batch) as an AgentGroup laid out like its solo run's (vec.AgentGroup.experiment_view):

@@ -543,6 +543,17 @@ class AgentGroup:
         call("avd_copy_experiment_sets_f32", self._layp, self.n_sets, int(n_groups), int(set_block), arr, len(pairs), ptr(self.theta),
              ptr(self.stats), ptr(self.theta_t), ptr(self.stats_t), ptr(self.m), ptr(self.v), ptr(self.step), stream_handle())
 
+    def keep_best(self, d_set_base, h_set_base, M, NS, counters, step, best_theta, best_stats, best_score, best_step, improved):
+        """Retention of the best actors seen (avd_keep_best_f32, csrc/best.hip) on slabs the caller holds: unit u owns this group's sets
+        d_set_base[u] .. +M-1 (int32 device table; h_set_base its host copy, a ctypes int32 array the entry checks) and the NS x M
+        rollout counters counters[u]; where its score -- their sequential float32 mean -- beats best_score[u], its actor spans and actor
+        BN statistics go to rows u*M .. of best_theta [n_units*M, actor_size] / best_stats [n_units*M, cmms], best_score[u] and
+        best_step[u] (int64) are set and improved[u] (int32) is 1, else 0 and nothing is written. Two launches on the current stream, no
+        host synchronisation. theta and stats are taken at call time: the fused update swaps theta with its ping-pong slab every step."""
+        call("avd_keep_best_f32", self._layp, len(h_set_base), int(M), int(NS), self.n_sets, ptr(d_set_base), h_set_base, ptr(counters),
+             ptr(self.theta), ptr(self.stats), int(step), ptr(best_theta), ptr(best_stats), ptr(best_score), ptr(best_step), ptr(improved),
+             stream_handle())
+
     def _no_hp(self, what):
         if self.hp is not None:
             raise _hip.AvdError(f"{what}: a hyperparameter sweep (set_hparams) has no per-experiment form of this path")

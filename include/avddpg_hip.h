@@ -437,6 +437,23 @@ int avd_copy_experiment_sets_f32(const avd_mlp_layout* lay, int n_sets, int n_gr
                                  float* theta, float* stats, float* theta_t, float* stats_t, float* m, float* v, int32_t* step,
                                  void* stream);
 
+/* ---- keep the best actors seen in training (csrc/best.hip) ----
+ * A unit is one rollout group of the evaluator, addressed as avd_eval_rollout_f32 addresses it: unit u owns the M weight sets
+ * set_base[u] .. set_base[u]+M-1 of the online slabs theta [n_sets, theta_size] / stats [n_sets, stats_size] and the NS rollouts whose
+ * counters are counters[u][k][m] (the [n_units * NS, M] array the rollout just wrote). Its score is the float32 sum of those NS * M
+ * counters in memory order -- from the first element, one unfused add at a time -- divided by (float)(NS * M). The unit improves iff
+ * score > best_score[u]: strict (a tie keeps the older snapshot), and a NaN score never improves; start best_score at -inf and
+ * best_step at -1. For a unit that improved, the actor span theta[set][0 : actor_size] of each of its sets goes to row u*M+m of
+ * best_theta [n_units*M, actor_size], the actor's BN statistics stats[set][0 : cmms] to row u*M+m of best_stats [n_units*M, cmms],
+ * best_score[u] = score, best_step[u] = step_now and improved[u] = 1; for every other unit improved[u] = 0 and nothing else is written.
+ * The online slabs are only read. Two launches on `stream` (the per-unit decision, then the copy that reads improved[]), no copy
+ * between host and device and no synchronisation. d_set_base is the device table the kernels read, h_set_base the caller's host copy
+ * of it, checked here. Refused (AVD_E_INVALID, before any launch, every array unchanged): a null or empty layout, a null pointer, a
+ * slab that is not 16-byte aligned, n_units / M / NS < 1, a set_base entry outside [0, n_sets - M]. */
+int avd_keep_best_f32(const avd_mlp_layout* lay, int n_units, int M, int NS, int n_sets, const int32_t* d_set_base,
+                      const int32_t* h_set_base, const float* counters, const float* theta, const float* stats, int64_t step_now,
+                      float* best_theta, float* best_stats, float* best_score, int64_t* best_step, int32_t* improved, void* stream);
+
 /* actor(state) for agents that SHARE n_sets weight sets (agent v uses set v % n_sets), reference widths, on the f32 matrix
  * cores (csrc/act.hip: v_mfma_f32_32x32x2_f32, exact f32 products -- agent/model.py:26-36 in the reference's arithmetic
  * class). Same values as avd_actor_forward_f32 with set_mod = n_sets up to the f32 summation order (1e-7 relative).
