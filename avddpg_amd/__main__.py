@@ -94,6 +94,19 @@ def _scenario_flags(p, where):
                         "noise, standard deviations), v2v_delay (steps, 0..15) and v2v_drop (loss probability) on the communicated "
                         "predecessor acceleration (Model B), dyn_coeff (the true plant's engine lag; the actors stay as trained), e.g. "
                         "lag3:v2v_delay=3,v2v_drop=0.1 (not in the reference CLI)")
+    # (both absent from the namespace unless given: _baseline_flags(args) reads them)
+    p.add_argument("--baseline", action="append", default=argparse.SUPPRESS, metavar="NAME[:key=val,...]",
+                   help="--scenarios: also run this linear law u = clip(kp ep + kv ev + ka a + kf a_pred) in place of the actors over the "
+                        "same scenarios x seeds x --disturb levels (repeat the flag for more laws, at most 16; ONE launch of the linear "
+                        "scenario evaluator for all of them) and write baseline.csv: scenarios.csv's columns (robustness.csv's with "
+                        "--disturb) with `controller` in place of `platoon` and a trailing `actors_score`, the mean over the run's "
+                        "platoons of the actors' score for the same scenario, disturbance and seed. Keys: kp, kv, ka, kf (kf: Model B), "
+                        "e.g. cacc:kp=0.5,kv=1. Decentralized platoons only (not in the reference CLI)")
+    p.add_argument("--baseline_tune", type=str, default=argparse.SUPPRESS, metavar="GRID",
+                   help="--scenarios: add the law `tuned`: the best of a gain grid by mean counter over the suite's undisturbed cases, "
+                        "searched on the device (one rollout launch over grid x cases, one fitness launch), then evaluated like any "
+                        "--baseline law. GRID: key=lo:hi:n per gain (np.linspace; a missing key is 0), at most 65536 candidates, e.g. "
+                        "kp=0:2:9,kv=0:4:9,ka=-0.5:0:3 (not in the reference CLI)")
 
 
 def _check_scenario_flags(ap, args):
@@ -103,7 +116,7 @@ def _check_scenario_flags(ap, args):
     from .scenarios import check_names
 
     if args.scenarios is None:
-        for flag in ("eval_seeds", "scenario_amp", "scenario_period", "disturb"):
+        for flag in ("eval_seeds", "scenario_amp", "scenario_period", "disturb", "baseline", "baseline_tune"):
             if getattr(args, flag, None) is not None:
                 ap.error(f"--{flag} needs --scenarios")
         return
@@ -127,6 +140,20 @@ def _check_scenario_flags(ap, args):
             args.disturb = check_disturbances([parse_disturbance(d) for d in args.disturb])
         except ValueError as e:
             ap.error(f"--disturb: {e}")
+    if getattr(args, "baseline", None) is not None or getattr(args, "baseline_tune", None) is not None:
+        from . import scenarios as _sc
+
+        try:  # (what needs the run's configuration -- Model A, the centralized framework -- is checked once it is known)
+            args.baseline = _sc.check_baselines([_sc.parse_baseline(b) for b in getattr(args, "baseline", None) or []])
+        except ValueError as e:
+            ap.error(f"--baseline: {e}")
+        if getattr(args, "baseline_tune", None) is not None:
+            if len(args.baseline) + 1 > _sc.MAX_BASELINES:
+                ap.error(f"--baseline: {len(args.baseline)} laws beside --baseline_tune's `tuned`: at most {_sc.MAX_BASELINES} in all")
+            try:
+                args.baseline_tune = (args.baseline_tune, _sc.parse_gain_grid(args.baseline_tune))
+            except ValueError as e:
+                ap.error(f"--baseline_tune: {e}")
     if args.mode == "tr" and int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
         # (one of the two choices: refused, rather than every rank writing a scenarios.csv of its own platoons)
         ap.error("--scenarios is not available under a process group of more than one rank (scenarios.csv is not gathered across ranks)")
@@ -135,6 +162,70 @@ def _check_scenario_flags(ap, args):
 def _disturb(args):
     """The --disturb levels (checked Disturbances), or None without the flag."""
     return getattr(args, "disturb", None)
+
+
+def _exit(msg):
+    raise SystemExit(msg)
+
+
+def _baseline_flags(args):
+    """(the --baseline laws, --baseline_tune's (text, grid) or None), or None without either flag."""
+    laws, tune = getattr(args, "baseline", None), getattr(args, "baseline_tune", None)
+    return None if laws is None and tune is None else (list(laws or []), tune)
+
+
+def _check_baseline_conf(args, conf, refuse):
+    """The --baseline / --baseline_tune refusals that need the run's configuration (Model A with kf, the centralized framework)."""
+    flags = _baseline_flags(args)
+    if flags is None:
+        return
+    from . import scenarios as _sc
+
+    laws, tune = flags
+    try:
+        _sc.check_baselines(laws, conf)
+        if tune is not None and conf.model == conf.modelA and (tune[1][:, 3] != 0).any():
+            raise ValueError("a grid over kf needs Model B (Model A observes no communicated state)")
+    except ValueError as e:
+        refuse(f"--baseline: {e}")
+
+
+class _Baselines:
+    """What --baseline / --baseline_tune compute, once per run: the laws (the grid's best appended as `tuned`) over the suite's cases in
+    one linear-evaluator launch. ``write(d, conf, actors)`` puts baseline.csv into a directory and the record into its Config."""
+
+    def __init__(self, conf, args):
+        from . import evaluator
+        from . import scenarios as _sc
+
+        laws, tune = _baseline_flags(args)
+        self.tune = None
+        try:
+            if tune is not None:  # the search runs over the nominal cases only
+                text, grid = tune
+                best, fit = evaluator.tune_linear(conf, grid, **_suite(args))
+                gains = [float(x) for x in grid[best]]
+                laws = laws + [_sc.LinearLaw(_sc.TUNED, *gains)]
+                self.tune = [["grid", text], ["candidates", int(grid.shape[0])], ["best_index", int(best)],
+                             ["gains", [[k, v] for k, v in zip(_sc.GAIN_KEYS, gains)]], ["fitness", float(fit[best])]]
+            self.laws = laws
+            self.results = evaluator.run_linear(conf, laws, disturbances=_disturb(args) or (), **_suite(args))
+        except ValueError as e:
+            raise SystemExit(f"--baseline: {e}")
+        self.names = [b.name for b in laws]
+
+    def write(self, d, conf, actors):
+        from . import scenarios as _sc
+
+        _sc.write_baseline_csv(os.path.join(d, "baseline.csv"), self.results, self.names, actors)
+        conf.baseline_suite = [[b.name, b.items()] for b in self.laws]
+        if self.tune is not None:
+            conf.baseline_tune = self.tune
+
+    def report(self):
+        from . import scenarios as _sc
+
+        return _sc.baseline_report_lines(self.results, self.names)
 
 
 def _record_train_levels(conf, args):
@@ -449,7 +540,10 @@ def get_cmdl_args(argv, conf):
             ap.error("--eval_platoons needs --episodes platoon")
         if ev != "all" and not (ev.isdigit() and int(ev) >= 1):
             ap.error("--eval_platoons takes a platoon count >= 1 or 'all'")
-    return args, set_args_to_config(args, conf)
+    conf = set_args_to_config(args, conf)
+    if args.mode == "tr":  # (esim checks against the configuration it loads)
+        _check_baseline_conf(args, conf, ap.error)
+    return args, conf
 
 
 def set_args_to_config(args, conf):
@@ -558,6 +652,8 @@ def main(argv=None, conf=None):
         if args.scenarios is not None:  # every local platoon over scenarios (x disturbances) x seeds, one launch
             res = vt.evaluate_scenarios(**_suite(args)) if _disturb(args) is None else vt.evaluate_robustness(disturbances=_disturb(args), **_suite(args))
             _write_suite(base, conf, res, range(1, vt.P + 1), args)
+            if _baseline_flags(args) is not None:
+                _Baselines(conf, args).write(base, conf, res)
         n_save = vt.P if args.save_platoons is None and args.episodes == "reference" else min(vt.P, 4 if args.save_platoons is None else args.save_platoons)
         artifacts.save_agents(base, vt.agents, n_save, vt.M, shared=vt.shared)
         # what ran, beside the reference's fields: how many platoons' agents the directory holds (esim loops over exactly these),
@@ -593,10 +689,15 @@ def main(argv=None, conf=None):
                     raise FileNotFoundError(f"{args.exp_path}: no checkpoint of platoon {p}'s actors (conf.json records {saved} saved platoons)")
                 for m in range(M):
                     grp.set_weights((p - 1) * M + m, "actor", artifacts.load_actor_weights(args.exp_path, p, m + 1))
-            res = evaluator.run_cases(conf, grp, range(saved), **_suite(args)) if _disturb(args) is None else \
+            _check_baseline_conf(args, conf, _exit)
+            full = evaluator.run_cases(conf, grp, range(saved), **_suite(args)) if _disturb(args) is None else \
                 evaluator.run_disturbed(conf, grp, range(saved), disturbances=_disturb(args), **_suite(args))
-            res = _write_suite(args.exp_path, conf, res, range(1, saved + 1), args)  # (conf.json itself is not rewritten)
+            res = _write_suite(args.exp_path, conf, full, range(1, saved + 1), args)  # (conf.json itself is not rewritten)
             print("\n".join(_sc.report_lines(res, range(1, saved + 1))))
+            if _baseline_flags(args) is not None:
+                base = _Baselines(conf, args)
+                base.write(args.exp_path, conf, full)
+                print("\n".join(base.report()))
             return
         for p in range(1, int(saved) + 1):
             if not os.path.exists(os.path.join(args.exp_path, artifacts.FNAME["actor"] % (p, 1) + ".npz")):
@@ -729,6 +830,7 @@ def train_seed_batch(args, conf, base, experiments=None):
     suite = None  # [E, P, scen, (dist,) seed, ...], one launch
     if args.scenarios is not None:
         suite = vt.evaluate_scenarios(**_suite(args)) if _disturb(args) is None else vt.evaluate_robustness(disturbances=_disturb(args), **_suite(args))
+    baselines = _Baselines(conf, args) if suite is not None and _baseline_flags(args) is not None else None  # computed once
     n_save = min(P, 4 if args.save_platoons is None else args.save_platoons)
     kept = _KeepResults(vt, args) if getattr(args, "keep_best", None) is not None else None
     done = []
@@ -754,6 +856,8 @@ def train_seed_batch(args, conf, base, experiments=None):
         _record_train_leader(ce, args)
         if suite is not None:
             _write_suite(d, ce, _slice(suite, e), range(1, P + 1), args)
+            if baselines is not None:
+                baselines.write(d, ce, _slice(suite, e))
         if kept is not None:  # (after everything else the directory's conf.json records: best/conf.json carries it too)
             kept.write(d, ce, n_save, e)
         artifacts.config_writer(os.path.join(d, "conf.json"), ce)

@@ -156,6 +156,8 @@ _PROTOS = {
     "avd_eval_cases_dist_f32": [_LP, _P, _i, _i, _i, _i, _i, _P, _P, _i, _P, _P, _P, _P, _f, _f, _f, _f, _P, _P, _P, _P, _P, _P, _P, _P],
     "avd_eval_cases_dist_block": [_i, _i],  # returns the block size itself, as avd_eval_cases_block
     "avd_eval_cases_dist_check": [_i, _P, _P, _P],  # HOST arrays
+    "avd_eval_linear_f32": [_P, _i, _i, _i, _i, _P, _P, _P, _P, _f, _f, _f, _P, _P, _P, _P, _P, _P, _P, _P],
+    "avd_linear_fitness_f32": [_i, _i, _i, _P, _P, _P],
     "avd_gemm_bt_bf16": [_i, _i, _i, _P, C.c_long, _P, C.c_long, _P, C.c_long, _P],
 }
 

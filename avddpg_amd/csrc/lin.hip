@@ -1,0 +1,220 @@
+// Linear baseline of the scenario evaluator for gfx950: G gain sets x K cases of the evaluator rollout (evalx.hip's cases, start
+// states, leader rows and per-case disturbance tables) in ONE launch, the controller a static gain row per vehicle instead of an MLP:
+//   u = clip(((g0 * ob.x + g1 * ob.y) + g2 * ob.z) + g3 * ob.w, lo, hi)        (Model A: the first three terms; g3 is not read)
+// with ob the observed state. The platoon step, the reward and the terminal test are eval_common.h's; the metrics are evalx.hip's.
+//
+// A rollout is T dependent steps of a few dozen flops and shares nothing with any other, so the kernel is built for occupancy and
+// latency, not bandwidth:
+//   * one lane per (gain set, case, vehicle); the L lanes of a rollout are contiguous inside ONE wave, floor(64 / L) rollouts per wave,
+//     the remaining lanes (and the lanes past the last rollout) return at once: they read nothing and write nothing;
+//   * one wave per workgroup: nothing is shared between waves, and there is no barrier anywhere;
+//   * the predecessor's chain value comes from lane - 1 with __shfl_up (a rollout never straddles a wave), not through LDS;
+//   * a vehicle's plant (A, B, C: 24 floats), gains, disturbance scalars, state and metric accumulators live in registers;
+//   * the V2V ring (disturbed only: 16 floats per lane) lives in LDS as [slot][lane]: the 64 lanes of a slot are 64 consecutive
+//     dwords, so whatever slot each lane addresses (the delay differs per case) lane l hits bank l % 32 and the two 32-lane halves
+//     of a ds_read_b32 / ds_write_b32 are conflict-free. A lane touches only its own column: no barrier. A dynamically indexed
+//     register array would have become scratch. The nominal instantiation allocates no LDS;
+//   * the leader row is read by the vehicle-0 lanes only, one step ahead of its use: the load's latency is off the dependent chain.
+//
+// hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage (profiles/eval_linear_resource_usage.txt):
+//   eval_linear_kernel<>         (nominal):    64 VGPRs, 0 AGPRs, no scratch,    0 B LDS, 8 waves per SIMD
+//   eval_linear_kernel<LinDist>  (disturbed): 118 VGPRs, 0 AGPRs, no scratch, 4096 B LDS, 4 waves per SIMD (the registers are Box-Muller's
+//                                             logf / sinf / cosf and Philox's; at 4096 gain sets x 12 cases x 5 vehicles the launch is
+//                                             4096 waves, 4 per SIMD of 256 CUs, so the count does not limit that shape)
+#include <limits.h>
+
+#include "eval_common.h"
+
+namespace avd {
+
+constexpr int LIN_THREADS = 64;                      // one wave
+constexpr int LIN_RING = AVD_EVAL_MAX_DELAY + 1;     // slots of a vehicle's V2V history
+static_assert((LIN_RING & (LIN_RING - 1)) == 0, "the ring index is taken with a mask");
+
+struct LinArgs {
+    const avd_env_consts* cst;
+    int G, K, L, T;
+    const float* gains;    // [G][L][4]
+    const float* x0;       // [K][L][4]
+    const float* prev_a0;  // [K][L]
+    const float* leader;   // [K][T]
+    float lo, hi, inv_dt;
+    float* counters;       // [G][K][L]
+    float* metrics;        // [G][K][L][AVD_EVAL_NMETRIC] or null
+};
+
+// The disturbed variant's per-case tables: evalx.hip's DistArgs, field for field
+struct LinDist {
+    const float* sigma;          // [K][3]
+    const int32_t* delay;        // [K]
+    const uint32_t* drop_q;      // [K]
+    const uint64_t* noise_seed;  // [K]
+    const float* abc;            // [K][L][24] or null: the constants block's
+};
+
+// D is empty (nominal: the constants block's plant, a perfect observation, no LDS) or one LinDist
+template <class... D>
+__global__ __launch_bounds__(LIN_THREADS) void eval_linear_kernel(const LinArgs a, const D... dist) {
+#pragma clang fp contract(off)
+    constexpr bool DIST = sizeof...(D) != 0;
+    const int nv = a.L, lane = threadIdx.x;
+    const int per_wave = LIN_THREADS / nv;
+    const int rw = lane / nv, v = lane - rw * nv;
+    const long roll = (long)blockIdx.x * per_wave + rw;  // (gain set, case) index of this lane's rollout
+    if (rw >= per_wave || roll >= (long)a.G * a.K) return;
+    const int g = (int)(roll / a.K), k = (int)(roll - (long)g * a.K);
+    const avd_env_consts* cst = a.cst;
+    const long kv = (long)k * nv + v;
+    // this vehicle's plant A (16, row-major), B (4), C (4): registers for the whole rollout
+    float abc[24];
+    bool table = false;
+    if constexpr (DIST) {
+        const LinDist da{dist...};
+        if (da.abc) {
+            table = true;
+#pragma unroll
+            for (int e = 0; e < 24; ++e) abc[e] = da.abc[kv * 24 + e];
+        }
+    }
+    if (!table) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) abc[e] = cst->A[v][e];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) abc[16 + e] = cst->B[v][e], abc[20 + e] = cst->C[v][e];
+    }
+    const float* gp = a.gains + ((long)g * nv + v) * 4;
+    const float4 gn = make_float4(gp[0], gp[1], gp[2], gp[3]);
+    float4 xv = make_float4(a.x0[kv * 4], a.x0[kv * 4 + 1], a.x0[kv * 4 + 2], a.x0[kv * 4 + 3]);
+    float pa = a.prev_a0[kv], cnt = 0.f;
+    float mx_ep = 0.f, mx_ev = 0.f, mx_a = 0.f, su2 = 0.f, sj2 = 0.f, nterm = 0.f, first = -1.0f;
+    const bool model_a = cst->model_a != 0;
+    const float* leader = a.leader + (long)k * a.T;
+    float lead_next = (v == 0) ? leader[0] : 0.f;
+    // ---- the case's disturbance (disturbed only) ----
+    float sg_ep = 0.f, sg_ev = 0.f, sg_a = 0.f, recv = 0.f;
+    int dly = 0;
+    uint32_t dq = 0;
+    uint64_t nseed = 0;
+    float* ring = nullptr;
+    if constexpr (DIST) {
+        __shared__ float s_ring[LIN_RING * LIN_THREADS];  // [slot][lane]
+        const LinDist da{dist...};
+        sg_ep = da.sigma[k * 3L], sg_ev = da.sigma[k * 3L + 1], sg_a = da.sigma[k * 3L + 2];
+        dly = da.delay[k] & (LIN_RING - 1);  // (the host refuses delays outside the ring; the mask keeps any value inside it)
+        dq = da.drop_q[k];
+        nseed = da.noise_seed[k];
+        ring = s_ring + lane;
+#pragma unroll
+        for (int j = 0; j < LIN_RING; ++j) ring[j * LIN_THREADS] = xv.w;  // steps before the first: x0's
+        recv = xv.w;                                                       // and the last received value
+    }
+    for (int t = 0; t < a.T; ++t) {
+        const float lead = lead_next;
+        if (v == 0 && t + 1 < a.T) lead_next = leader[t + 1];  // next step's, in flight during this one
+        // ---- what the controller sees of the true pre-step state xv: eval_cases_kernel<RB, DistArgs>, evalx.hip lines 245-260 ----
+        float4 ob = xv;
+        if constexpr (DIST) {
+            ring[(t & (LIN_RING - 1)) * LIN_THREADS] = xv.w;
+            const float delayed = ring[((t - dly) & (LIN_RING - 1)) * LIN_THREADS];  // a slot of a step < 0 has not been overwritten yet
+            // loss: an integer compare on one Philox word (drop_q = 0 never drops: no draw needed)
+            const bool dropped = dq != 0 && (philox_at(nseed, (uint64_t)t, (uint32_t)v, STREAM_EVAL_LINK).x >> 8) < dq;
+            if (!dropped) recv = delayed;
+            ob.w = recv;
+            if (sg_ep != 0.f || sg_ev != 0.f || sg_a != 0.f) {
+                const u32x4 r = philox_at(nseed, (uint64_t)t, (uint32_t)v, STREAM_EVAL_OBS);
+                float n_ev;
+                const float n_ep = box_muller(r.x, r.y, &n_ev);
+                const float n_a = box_muller(r.z, r.w, nullptr);
+                if (sg_ep != 0.f) ob.x = xv.x + sg_ep * n_ep;  // a zero level skips the add: exact by construction
+                if (sg_ev != 0.f) ob.y = xv.y + sg_ev * n_ev;
+                if (sg_a != 0.f) ob.z = xv.z + sg_a * n_a;
+            }
+        }
+        // ---- the linear law, platoon step ----
+        float z = (gn.x * ob.x + gn.y * ob.y) + gn.z * ob.z;
+        if (!model_a) z = z + gn.w * ob.w;
+        const float uu = fminf(fmaxf(z, a.lo), a.hi);  // np.clip
+        const VehStep vs = veh_step_pre(cst, abc, abc + 16, xv, uu);
+        const float up = __shfl_up(vs.chain, 1);  // lane - 1: the predecessor of every vehicle but the first
+        const float exog = (v == 0) ? lead : up;
+        float4 xn;
+        const float nr = veh_step_post(cst, vs, abc + 16, abc + 20, xv, pa, uu, exog, xn);
+        cnt = cnt + nr;  // counters += env.reward[0], per vehicle (decentralized)
+        // ---- metrics: evalx.hip lines 307-318 (scenarios.metrics_from_traces: sequential float32 sums in step order) ----
+        const bool is_term = ((fabsf(xv.x) > cst->max_ep) || (fabsf(xv.y) > cst->max_ev)) && (cst->can_terminate != 0);  // veh_step_post's test
+        if (is_term) {
+            nterm = nterm + 1.0f;
+            if (first < 0.f) first = (float)t;
+        }
+        const float jerk = (xv.z - pa) * a.inv_dt;
+        su2 = su2 + uu * uu;
+        sj2 = sj2 + jerk * jerk;
+        mx_ep = fmaxf(mx_ep, fabsf(xn.x)), mx_ev = fmaxf(mx_ev, fabsf(xn.y)), mx_a = fmaxf(mx_a, fabsf(xn.z));
+        pa = xv.z;  // prev_x <- x
+        xv = xn;
+    }
+    a.counters[roll * nv + v] = cnt;
+    if (a.metrics) {
+        float* o = a.metrics + (roll * nv + v) * AVD_EVAL_NMETRIC;
+        o[0] = mx_ep, o[1] = mx_ev, o[2] = mx_a, o[3] = su2, o[4] = sj2, o[5] = nterm, o[6] = first, o[7] = fabsf(xv.x);
+    }
+}
+
+// One thread per gain set: the sequential float32 sum of its K * L counters in (k, v) order, divided by (float)(K * L)
+__global__ __launch_bounds__(256) void linear_fitness_kernel(int G, long n, const float* __restrict__ counters, float* __restrict__ fitness) {
+#pragma clang fp contract(off)
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= G) return;
+    const float* c = counters + (long)g * n;
+    float s = 0.f;
+    for (long i = 0; i < n; ++i) s = s + c[i];
+    fitness[g] = s / (float)n;
+}
+
+template <class... D>
+int launch_linear(const char* who, const LinArgs& a, long blocks, hipStream_t stream, const D&... dist) {
+    hipLaunchKernelGGL((eval_linear_kernel<D...>), dim3((unsigned)blocks), dim3(LIN_THREADS), 0, stream, a, dist...);
+    return check_launch(who);
+}
+
+}  // namespace avd
+
+using namespace avd;
+
+extern "C" int avd_eval_linear_f32(const avd_env_consts* d_consts, int G, int K, int L, int T, const float* gains, const float* x0,
+                                   const float* prev_a0, const float* leader, float lo, float hi, float sample_rate, const float* sigma,
+                                   const int32_t* delay, const uint32_t* drop_q, const uint64_t* noise_seed, const float* abc,
+                                   float* counters, float* metrics, void* stream) {
+    const char* who = "avd_eval_linear_f32";
+    AVD_REQUIRE(d_consts && gains && x0 && prev_a0 && leader && counters, "%s: null pointer", who);
+    AVD_REQUIRE(L >= 1 && L <= AVD_MAX_L, "%s: L=%d (L must be 1..%d)", who, L, AVD_MAX_L);
+    AVD_REQUIRE(G >= 1 && K >= 1 && T >= 1, "%s: G=%d K=%d T=%d (all must be >= 1)", who, G, K, T);
+    AVD_REQUIRE(sample_rate > 0.f, "%s: sample_rate=%g", who, (double)sample_rate);
+    const bool dist = sigma || delay || drop_q || noise_seed || abc;
+    AVD_REQUIRE(!dist || (sigma && delay && drop_q && noise_seed),
+                "%s: null disturbance table (all five null: the nominal plant and a perfect observation; otherwise only abc may be null)", who);
+    const long long rollouts = (long long)G * K, per_wave = LIN_THREADS / L;
+    const long long blocks = (rollouts + per_wave - 1) / per_wave;
+    if (blocks > INT_MAX) {
+        set_error("%s: G=%d x K=%d = %lld rollouts, %lld per workgroup at L=%d, need %lld workgroups (the grid holds %d)", who, G, K, rollouts,
+                  per_wave, L, blocks, INT_MAX);
+        return AVD_E_UNSUPPORTED;
+    }
+    LinArgs a;
+    a.cst = d_consts, a.G = G, a.K = K, a.L = L, a.T = T, a.gains = gains, a.x0 = x0, a.prev_a0 = prev_a0, a.leader = leader;
+    a.lo = lo, a.hi = hi;
+    a.inv_dt = 1.0f / sample_rate;  // host float32 division, as avd_eval_cases_f32 forms it
+    a.counters = counters, a.metrics = metrics;
+    if (!dist) return launch_linear(who, a, (long)blocks, (hipStream_t)stream);
+    const LinDist d = {sigma, delay, drop_q, noise_seed, abc};
+    return launch_linear(who, a, (long)blocks, (hipStream_t)stream, d);
+}
+
+extern "C" int avd_linear_fitness_f32(int G, int K, int L, const float* counters, float* fitness, void* stream) {
+    const char* who = "avd_linear_fitness_f32";
+    AVD_REQUIRE(counters && fitness, "%s: null pointer", who);
+    AVD_REQUIRE(L >= 1 && L <= AVD_MAX_L, "%s: L=%d (L must be 1..%d)", who, L, AVD_MAX_L);
+    AVD_REQUIRE(G >= 1 && K >= 1, "%s: G=%d K=%d (both must be >= 1)", who, G, K);
+    hipLaunchKernelGGL(linear_fitness_kernel, dim3((G + 255) / 256), dim3(256), 0, (hipStream_t)stream, G, (long)K * L, counters, fitness);
+    return check_launch(who);
+}

@@ -181,6 +181,45 @@ class CaseResults:
         return _sc.summarise(self.metrics, self.T)
 
 
+def _case_tables(conf, names, starts, T, amp, period_s):
+    """The cases of a scenario suite -- scenarios x seeds, seeds innermost; a case's start state is its seed's, its leader row its
+    scenario's (gaussian: its seed's) -- from the seeds' ``_start`` results: (leader rows float32 [K, T] on the host, x0 [K, L, 4] and
+    prev_a0 [K, L] on the device)."""
+    from . import scenarios as _sc
+
+    L, NC, NS = conf.pl_size, len(names), len(starts)
+    prof = {n: _sc.leader_profile(n, T, conf, amp, period_s) for n in names if n != "gaussian"}
+    leader_h = np.stack([starts[k][1] if n == "gaussian" else prof[n] for n in names for k in range(NS)])
+    x0 = torch.stack([e.x.reshape(L, 4) for e, _, _ in starts]).repeat(NC, 1, 1).contiguous()
+    pa0 = torch.stack([e.prev_a.reshape(L) for e, _, _ in starts]).repeat(NC, 1).contiguous()
+    return leader_h, x0, pa0
+
+
+def _level_tables(conf, levels, seeds, NC, L):
+    """The per-case disturbance tables of scenarios x levels x seeds (seeds innermost) on the host: (sigma float32 [K, 3], delay int32
+    [K], drop_q uint32 [K], noise_seed uint64 [K], abc float32 [K, L, 24] or None when no level changes the plant), checked by
+    avd_eval_cases_dist_check. The noise seed is the case's evaluation seed: every level of a seed shares its draws."""
+    from . import _hip
+    from . import scenarios as _sc
+
+    ND, NS = len(levels), len(seeds)
+    lvl = np.tile(np.repeat(np.arange(ND), NS), NC)  # a case's level
+    sigma = np.array([d.sigma for d in levels], dtype=np.float32)[lvl]
+    delay = np.array([int(d.v2v_delay) for d in levels], dtype=np.int32)[lvl]
+    drop_q = np.array([_sc.drop_threshold(d.v2v_drop) for d in levels], dtype=np.uint32)[lvl]
+    noise_seed = np.tile(np.array(seeds, dtype=np.uint64), NC * ND)
+    _hip.call("avd_eval_cases_dist_check", NC * ND * NS, sigma.ctypes.data, delay.ctypes.data, drop_q.ctypes.data)
+    abc = None
+    if any(d.dyn_coeff is not None for d in levels):
+        abc = np.stack([_sc.plant_table(conf, L, d.dyn_coeff) for d in levels])[lvl]  # [K, L, 24]
+    return sigma, delay, drop_q, noise_seed, abc
+
+
+def _upload(a, dev, as_type=None):
+    """A host table on the device (torch holds signed integers: unsigned tables go up as their signed views)."""
+    return torch.from_numpy(a if as_type is None else a.view(as_type)).to(dev)
+
+
 class CaseBatch:
     """The device inputs of one avd_eval_cases_f32 launch (prepare_cases); ``launch()`` enqueues it on the current stream,
     ``results()`` reads counters and metrics back. run_cases = prepare_cases + launch + results. ``block`` is the number of cases per
@@ -231,11 +270,7 @@ class CaseBatch:
         f32 = dict(dtype=torch.float32, device=dev)
         self.conf, self.actors, self.env, self.T, self.L, self.M, self.NP, self.NS, self.NC = conf, actors, env, T, L, M, NP, NS, NC
         self.scenarios, self.seeds = names, seeds
-        # cases: scenarios x seeds, seeds innermost; a case's start state is its seed's, its leader row its scenario's (gaussian: its seed's)
-        prof = {n: _sc.leader_profile(n, T, conf, amp, period_s) for n in names if n != "gaussian"}
-        self.leader_h = np.stack([starts[k][1] if n == "gaussian" else prof[n] for n in names for k in range(NS)])
-        self.x0 = torch.stack([e.x.reshape(L, 4) for e, _, _ in starts]).repeat(NC, 1, 1).contiguous()
-        self.pa0 = torch.stack([e.prev_a.reshape(L) for e, _, _ in starts]).repeat(NC, 1).contiguous()
+        self.leader_h, self.x0, self.pa0 = _case_tables(conf, names, starts, T, amp, period_s)
         self.leader = torch.from_numpy(self.leader_h).to(dev)
         self.set_base = torch.tensor(bases, dtype=torch.int32, device=dev)
         self.counters = torch.empty(self.G, self.K, M, **f32)
@@ -323,21 +358,12 @@ class DisturbedBatch(CaseBatch):
         widen = lambda x: x.reshape(NC, 1, NS, *x.shape[1:]).repeat_interleave(ND, dim=1).reshape(self.K, *x.shape[1:]).contiguous()
         self.leader_h = np.repeat(self.leader_h.reshape(NC, 1, NS, -1), ND, axis=1).reshape(self.K, -1)
         self.x0, self.pa0, self.leader = widen(self.x0), widen(self.pa0), widen(self.leader)
-        lvl = np.tile(np.repeat(np.arange(ND), NS), NC)  # a case's level
-        self.sigma_h = np.array([d.sigma for d in levels], dtype=np.float32)[lvl]
-        self.delay_h = np.array([int(d.v2v_delay) for d in levels], dtype=np.int32)[lvl]
-        self.drop_q_h = np.array([_sc.drop_threshold(d.v2v_drop) for d in levels], dtype=np.uint32)[lvl]
-        # the noise seed is the case's evaluation seed: every level of a seed shares its draws
-        self.noise_seed_h = np.tile(np.array(self.seeds, dtype=np.uint64), NC * ND)
-        # host check of the tables (the kernel reads them from device memory)
-        _hip.call("avd_eval_cases_dist_check", self.K, self.sigma_h.ctypes.data, self.delay_h.ctypes.data, self.drop_q_h.ctypes.data)
-        up = lambda a, as_type=None: torch.from_numpy(a if as_type is None else a.view(as_type)).to(dev)  # (torch: signed integers)
-        self.sigma, self.delay = up(self.sigma_h), up(self.delay_h)
-        self.drop_q, self.noise_seed = up(self.drop_q_h, np.int32), up(self.noise_seed_h, np.int64)
-        # the true plants: a table only when a level changes the plant (null: the constants block's matrices for every case)
-        self.abc = None
-        if any(d.dyn_coeff is not None for d in levels):
-            self.abc = up(np.stack([_sc.plant_table(conf, L, d.dyn_coeff) for d in levels])[lvl])  # [K, L, 24]
+        # the tables, host-checked (the kernel reads them from device memory); the true plants: a table only when a level changes the
+        # plant (null: the constants block's matrices for every case)
+        self.sigma_h, self.delay_h, self.drop_q_h, self.noise_seed_h, abc_h = _level_tables(conf, levels, self.seeds, NC, L)
+        self.sigma, self.delay = _upload(self.sigma_h, dev), _upload(self.delay_h, dev)
+        self.drop_q, self.noise_seed = _upload(self.drop_q_h, dev, np.int32), _upload(self.noise_seed_h, dev, np.int64)
+        self.abc = None if abc_h is None else _upload(abc_h, dev)
         f32 = dict(dtype=torch.float32, device=dev)
         self.counters = torch.empty(self.G, self.K, self.M, **f32)
         self.metrics = torch.empty(self.G, self.K, L, _hip.AVD_EVAL_NMETRIC, **f32)
@@ -382,3 +408,132 @@ def run_disturbed(conf, actors, platoons, scenarios=("gaussian",), disturbances=
     b = prepare_disturbed(conf, actors, platoons, scenarios, disturbances, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override)
     b.launch()
     return b.results()
+
+
+class LinearBatch:
+    """The device inputs of one avd_eval_linear_f32 launch (prepare_linear, tune_linear): G gain sets ``gains`` float32 [G, L, 4] over the
+    cases CaseBatch (no disturbances) or DisturbedBatch builds -- same ``_start``, same leader profiles, same level tables, seeds
+    innermost. ``launch()`` enqueues it on the current stream, ``results()`` reads counters and metrics back (first axis: the gain
+    sets). ``metrics=False`` passes the kernel a null metrics pointer. The raw form: under Model A the kernel does not read a row's 4th
+    gain (prepare_linear and tune_linear refuse a non-zero one)."""
+
+    def __init__(self, conf, gains, scenarios, disturbances, seeds, amp, period_s, manual_timestep_override, metrics=True):
+        from . import _hip
+        from . import scenarios as _sc
+
+        if conf.framework == conf.cntrl:
+            raise ValueError("a linear baseline is a per-vehicle law: not available for the centralized framework")
+        names = _sc.check_names(scenarios)
+        seeds = [int(conf.evaluation_seed)] if seeds is None else [int(s) for s in seeds]
+        if not seeds:
+            raise ValueError("run_linear needs at least one seed")
+        if len(set(seeds)) != len(seeds):
+            raise ValueError(f"seeds {seeds}: a seed is listed more than once")
+        disturbances = list(disturbances)
+        levels = [_sc.NOMINAL] + _sc.check_disturbances(disturbances, conf) if disturbances else None
+        T = get_number_of_timesteps_for_plot(conf, manual_timestep_override)
+        amp, period_s = _sc.check_knobs(T, amp, period_s)
+        L = conf.pl_size
+        gains = np.ascontiguousarray(np.asarray(gains, dtype=np.float32))
+        if gains.ndim != 3 or gains.shape[0] < 1 or gains.shape[1:] != (L, 4) or not np.isfinite(gains).all():
+            raise ValueError(f"gains of shape {gains.shape}: need finite [G >= 1, L = {L}, 4]")
+        saved = np.random.get_state()
+        try:
+            starts = [_start(conf, True, manual_timestep_override, evaluation_seed=sd) for sd in seeds]
+        finally:
+            np.random.set_state(saved)
+        env = starts[0][0]
+        dev = env.device
+        NC, NS = len(names), len(seeds)
+        self.conf, self.env, self.T, self.L, self.NS, self.NC = conf, env, T, L, NS, NC
+        self.scenarios, self.seeds, self.levels, self.ND = names, seeds, levels, (len(levels) if levels else None)
+        self.G, self.K = gains.shape[0], NC * NS
+        self.gains_h, self.gains = gains, torch.from_numpy(gains).to(dev)
+        self.leader_h, self.x0, self.pa0 = _case_tables(conf, names, starts, T, amp, period_s)
+        self.leader = torch.from_numpy(self.leader_h).to(dev)
+        self.sigma = self.delay = self.drop_q = self.noise_seed = self.abc = None
+        if levels:  # cases: scenarios x levels x seeds, as DisturbedBatch widens them
+            ND = self.ND
+            self.K = NC * ND * NS
+            widen = lambda x: x.reshape(NC, 1, NS, *x.shape[1:]).repeat_interleave(ND, dim=1).reshape(self.K, *x.shape[1:]).contiguous()
+            self.leader_h = np.repeat(self.leader_h.reshape(NC, 1, NS, -1), ND, axis=1).reshape(self.K, -1)
+            self.x0, self.pa0, self.leader = widen(self.x0), widen(self.pa0), widen(self.leader)
+            sigma, delay, drop_q, noise_seed, abc = _level_tables(conf, levels, seeds, NC, L)
+            self.sigma, self.delay = _upload(sigma, dev), _upload(delay, dev)
+            self.drop_q, self.noise_seed = _upload(drop_q, dev, np.int32), _upload(noise_seed, dev, np.int64)
+            self.abc = None if abc is None else _upload(abc, dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.counters = torch.empty(self.G, self.K, L, **f32)
+        self.metrics = torch.empty(self.G, self.K, L, _hip.AVD_EVAL_NMETRIC, **f32) if metrics else None
+
+    def launch(self):
+        c = self.conf
+        call("avd_eval_linear_f32", ptr(self.env.d_consts), self.G, self.K, self.L, self.T, ptr(self.gains), ptr(self.x0), ptr(self.pa0),
+             ptr(self.leader), c.action_low, c.action_high, c.sample_rate, ptr(self.sigma), ptr(self.delay), ptr(self.drop_q),
+             ptr(self.noise_seed), ptr(self.abc), ptr(self.counters), ptr(self.metrics), stream_handle())
+
+    def fitness(self):
+        """One avd_linear_fitness_f32 launch over the counters of ``launch()``: float32 [G] on the host (the only read-back)."""
+        out = torch.empty(self.G, dtype=torch.float32, device=self.counters.device)
+        call("avd_linear_fitness_f32", self.G, self.K, self.L, ptr(self.counters), ptr(out), stream_handle())
+        return out.cpu().numpy()
+
+    def results(self):
+        from . import scenarios as _sc
+
+        if self.metrics is None:
+            raise ValueError("this batch was prepared without metrics (tune_linear): read fitness()")
+        c = self.counters.cpu().numpy().reshape(self.G * self.K, self.L)
+        rows = np.array([round(np.average(r), 3) for r in c], dtype=np.float32)  # row by row, as run (:145)
+        shape = (self.G, self.NC, self.NS) if self.levels is None else (self.G, self.NC, self.ND, self.NS)
+        m = self.metrics.cpu().numpy().reshape(*shape, self.L, -1)
+        metrics = {n: np.ascontiguousarray(m[..., j]) for j, n in enumerate(_sc.METRICS)}
+        if self.levels is None:
+            return CaseResults(self.scenarios, self.seeds, self.T, rows.reshape(shape), c.reshape(*shape, self.L), metrics)
+        return DisturbedResults(self.scenarios, [d.name for d in self.levels], self.seeds, self.T, rows.reshape(shape),
+                                c.reshape(*shape, self.L), metrics)
+
+
+def prepare_linear(conf, laws, scenarios=("gaussian",), disturbances=(), seeds=None, amp=None, period_s=10.0, manual_timestep_override=None):
+    """run_linear's host part (laws checked, cases built as run_cases / run_disturbed build them, device inputs uploaded) as a
+    LinearBatch."""
+    from . import scenarios as _sc
+
+    laws = _sc.check_baselines(laws, conf, reserved=())
+    if not laws:
+        raise ValueError("run_linear needs at least one law")
+    gains = np.stack([b.gains(conf.pl_size) for b in laws])
+    b = LinearBatch(conf, gains, scenarios, disturbances, seeds, amp, period_s, manual_timestep_override)
+    b.laws = laws
+    return b
+
+
+def run_linear(conf, laws, scenarios=("gaussian",), disturbances=(), seeds=None, amp=None, period_s=10.0, manual_timestep_override=None):
+    """Linear baselines over the scenario suite: every scenarios.LinearLaw of ``laws`` over scenarios x [nominal, *disturbances] x seeds
+    in ONE launch of the linear scenario evaluator (avd_eval_linear_f32, csrc/lin.hip), one lane per (law, case, vehicle). The cases,
+    the observation model, the platoon step, the reward and the metrics are run_cases' / run_disturbed's; only the controller differs: u
+    = clip(kp ep + kv ev + ka a + kf a_pred) on the observed state. Decentralized platoons only.
+
+    Returns a CaseResults (no disturbances) or a DisturbedResults whose first axis is the law axis instead of the platoon axis."""
+    b = prepare_linear(conf, laws, scenarios, disturbances, seeds, amp, period_s, manual_timestep_override)
+    b.launch()
+    return b.results()
+
+
+def tune_linear(conf, grid, scenarios=("gaussian",), disturbances=(), seeds=None, amp=None, period_s=10.0, manual_timestep_override=None):
+    """A gain search on the device: every row (kp, kv, ka, kf) of ``grid`` float32 [G, 4] (scenarios.parse_gain_grid) as a homogeneous
+    law -- the same row for every vehicle -- over the suite's cases in ONE rollout launch without metrics, then ONE fitness launch
+    (avd_linear_fitness_f32: a candidate's mean counter over cases and vehicles, a sequential float32 sum) and a read-back of G floats.
+    -> (best_index, fitness float32 [G]): the host's arg-max, the first index among equals, a NaN never wins."""
+    from . import scenarios as _sc
+
+    grid = np.asarray(grid, dtype=np.float32)
+    if grid.ndim != 2 or grid.shape[1] != 4 or not 1 <= grid.shape[0] <= _sc.MAX_GRID:
+        raise ValueError(f"grid of shape {grid.shape}: need [1 .. {_sc.MAX_GRID}, 4]")
+    if conf.model == conf.modelA and np.any(grid[:, 3] != 0):
+        raise ValueError("a grid over kf needs Model B (Model A observes no communicated state)")
+    gains = np.repeat(grid[:, None, :], conf.pl_size, axis=1)
+    b = LinearBatch(conf, gains, scenarios, disturbances, seeds, amp, period_s, manual_timestep_override, metrics=False)
+    b.launch()
+    fit = b.fitness()
+    return _sc.first_argmax(fit), fit

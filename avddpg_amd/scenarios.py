@@ -255,6 +255,166 @@ def plant_table(conf, L, dyn_coeff=None):
     return out
 
 
+# ---- linear baselines: what the linear scenario evaluator (avd_eval_linear_f32) runs in place of the actors --------------------------
+
+MAX_BASELINES = 16
+MAX_GRID = 65536
+GAIN_KEYS = ("kp", "kv", "ka", "kf")
+TUNED = "tuned"  # the name --baseline_tune gives the grid's best law
+
+
+class LinearLaw:
+    """One static feedback law per vehicle, u = clip(kp * ep + kv * ev + ka * a + kf * a_pred, action_low, action_high) on the observed
+    state: the constant-time-headway controller of the platooning literature (ep already holds the headway term), with the
+    predecessor's communicated acceleration as feed-forward under Model B. ``table`` ([L][4], one (kp, kv, ka, kf) row per vehicle)
+    overrides the four scalars."""
+
+    def __init__(self, name, kp=0, kv=0, ka=0, kf=0, table=None):
+        self.name = str(name)
+        self.kp, self.kv, self.ka, self.kf = kp, kv, ka, kf
+        self.table = None if table is None else np.asarray(table)
+
+    def items(self):
+        """[(key, value)] in GAIN_KEYS order (conf.json's baseline_suite), then the table when there is one."""
+        out = [[k, getattr(self, k)] for k in GAIN_KEYS]
+        return out if self.table is None else out + [["table", np.asarray(self.table, dtype=np.float64).tolist()]]
+
+    def gains(self, L):
+        """float32 [L, 4]: the table, or the scalars repeated for every vehicle."""
+        if self.table is not None:
+            t = np.asarray(self.table, dtype=np.float32)
+            if t.shape != (int(L), 4):
+                raise ValueError(f"baseline {self.name!r}: a gain table of shape {t.shape} for a platoon of {L} (need [{L}, 4])")
+            return np.ascontiguousarray(t)
+        return np.ascontiguousarray(np.tile(np.array([self.kp, self.kv, self.ka, self.kf], dtype=np.float32), (int(L), 1)))
+
+    def __repr__(self):
+        return "LinearLaw(" + ", ".join([repr(self.name)] + [f"{k}={v!r}" for k, v in self.items()]) + ")"
+
+
+def parse_baseline(text):
+    """``NAME[:key=val,...]`` (keys of GAIN_KEYS) -> LinearLaw; ``NAME`` alone is the zero law under that name. An unknown key, a key
+    given twice or a value that is no number is a ValueError; the values are checked by check_baselines."""
+    name, _, spec = str(text).partition(":")
+    name = name.strip()
+    if not name:
+        raise ValueError(f"baseline {text!r}: no name before ':'")
+    kw = {}
+    for part in [q.strip() for q in spec.split(",") if q.strip()]:
+        key, eq, val = part.partition("=")
+        key, val = key.strip(), val.strip()
+        if not eq or key not in GAIN_KEYS:
+            raise ValueError(f"baseline {name!r}: unknown key {key!r} (one of {', '.join(GAIN_KEYS)}, as key=value)")
+        if key in kw:
+            raise ValueError(f"baseline {name!r}: {key} given twice")
+        try:
+            kw[key] = float(val)
+        except ValueError:
+            raise ValueError(f"baseline {name!r}: {key}={val!r} is not a number") from None
+    return LinearLaw(name, **kw)
+
+
+def check_baselines(laws, conf=None, reserved=(TUNED,)):
+    """The laws as a list. A ValueError for: more than MAX_BASELINES; a non-finite gain or a gain that is no number; a table that is
+    not [*, 4]; a name listed twice; the reserved name ``tuned``; with ``conf``, a non-zero kf under Model A (its 3-state observation
+    has no communicated component), a table whose row count is not conf.pl_size, and the centralized framework (a linear law is per
+    vehicle)."""
+    out = list(laws)
+    if len(out) > MAX_BASELINES:
+        raise ValueError(f"{len(out)} baselines listed: at most {MAX_BASELINES}")
+    if conf is not None and conf.framework == conf.cntrl:
+        raise ValueError("a linear baseline is a per-vehicle law: not available for the centralized framework")
+    for b in out:
+        if not isinstance(b, LinearLaw):
+            raise ValueError(f"{b!r} is not a scenarios.LinearLaw")
+        if b.name in reserved:
+            raise ValueError(f"the baseline name {b.name!r} is reserved for the law --baseline_tune picks")
+        for k in GAIN_KEYS:
+            v = getattr(b, k)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+                raise ValueError(f"baseline {b.name!r}: {k}={v!r} must be a finite number")
+        uses_kf = b.kf != 0
+        if b.table is not None:
+            t = np.asarray(b.table)
+            if t.ndim != 2 or t.shape[1] != 4 or t.shape[0] < 1 or not np.issubdtype(t.dtype, np.number) or not np.isfinite(t).all():
+                raise ValueError(f"baseline {b.name!r}: table must be a finite [L, 4] array (got shape {t.shape})")
+            if conf is not None and t.shape[0] != conf.pl_size:
+                raise ValueError(f"baseline {b.name!r}: a gain table of {t.shape[0]} rows for pl_size={conf.pl_size}")
+            uses_kf = bool(np.any(t[:, 3] != 0))
+        if conf is not None and conf.model == conf.modelA and uses_kf:
+            raise ValueError(f"baseline {b.name!r}: kf needs Model B (Model A observes no communicated state)")
+    names = [b.name for b in out]
+    dup = sorted({n for n in names if names.count(n) > 1})
+    if dup:
+        raise ValueError(f"baseline(s) {dup} listed more than once")
+    return out
+
+
+def parse_gain_grid(text):
+    """``kp=lo:hi:n,kv=...`` (keys of GAIN_KEYS; ``key=value`` is the single value) -> float32 [G, 4]: per key np.linspace(lo, hi, n) in
+    float64, then cast; a missing key is the single value 0; the product in kp, kv, ka, kf order, the last varying fastest. A
+    ValueError for an unknown key, a key given twice, n < 1 or no integer, a non-finite bound, an empty grid text and G > MAX_GRID."""
+    axes = {}
+    parts = [q.strip() for q in str(text).split(",") if q.strip()]
+    if not parts:
+        raise ValueError(f"gain grid {text!r}: no axis given (kp=lo:hi:n,...)")
+    for part in parts:
+        key, eq, val = part.partition("=")
+        key, val = key.strip(), val.strip()
+        if not eq or key not in GAIN_KEYS:
+            raise ValueError(f"gain grid: unknown key {key!r} (one of {', '.join(GAIN_KEYS)}, as key=lo:hi:n)")
+        if key in axes:
+            raise ValueError(f"gain grid: {key} given twice")
+        f = [x.strip() for x in val.split(":")]
+        try:
+            if len(f) == 1:
+                lo = hi = float(f[0])
+                n = 1
+            elif len(f) == 3:
+                lo, hi, n = float(f[0]), float(f[1]), int(f[2])
+            else:
+                raise ValueError
+        except ValueError:
+            raise ValueError(f"gain grid: {key}={val!r} is not lo:hi:n (two numbers and an integer) or a single number") from None
+        if n < 1:
+            raise ValueError(f"gain grid: {key} has n={n} points (n must be >= 1)")
+        if not (math.isfinite(lo) and math.isfinite(hi)):
+            raise ValueError(f"gain grid: {key}={val!r} has a non-finite bound")
+        axes[key] = (lo, hi, n)
+    G = 1
+    for _, _, n in axes.values():
+        G *= n
+    if G > MAX_GRID:
+        raise ValueError(f"gain grid: {G} candidates (at most {MAX_GRID})")
+    cols = [np.linspace(*axes[k]) if k in axes else np.zeros(1) for k in GAIN_KEYS]
+    mesh = np.meshgrid(*cols, indexing="ij")
+    return np.ascontiguousarray(np.stack([m.ravel() for m in mesh], axis=1).astype(np.float32))
+
+
+def first_argmax(fitness):
+    """The index of the largest value of a 1-d array: the first among equals; a NaN never wins (all NaN: index 0)."""
+    f = np.asarray(fitness)
+    best = 0
+    for i in range(1, f.shape[0]):
+        if not np.isnan(f[i]) and (np.isnan(f[best]) or f[i] > f[best]):
+            best = i
+    return best
+
+
+def fitness_of(counters):
+    """float32 [G] from counters [G, K, L]: per gain set the sequential float32 sum in (k, v) order divided by float32(K * L) -- the
+    loop avd_linear_fitness_f32 runs on the device, bit for bit."""
+    c = np.asarray(counters, dtype=np.float32)
+    c = c.reshape(c.shape[0], -1)
+    out = np.zeros(c.shape[0], dtype=np.float32)
+    for g in range(c.shape[0]):
+        s = np.float32(0.0)
+        for x in c[g]:
+            s = np.float32(s + x)
+        out[g] = s / np.float32(c.shape[1])
+    return out
+
+
 # ---- training manoeuvres: what the fused step's leader follows during training (avd_step_fused_lead_f32) -----------------------------
 
 MAX_MANOEUVRES = 16  # AVD_TRAIN_MAX_MANOEUVRES
@@ -394,6 +554,43 @@ def write_robustness_csv(path, results, platoon_tags):
         w = csv.writer(fh)
         w.writerow(ROBUSTNESS_HEADER)
         w.writerows(robustness_rows(results, platoon_tags))
+
+
+BASELINE_HEADER = ["controller", *CSV_HEADER[1:], "actors_score"]
+BASELINE_ROBUSTNESS_HEADER = ["controller", *ROBUSTNESS_HEADER[1:], "actors_score"]
+
+
+def actors_mean_score(actors):
+    """float32 [scen, (dist,) seed]: the mean over the platoon axis of the actors' scores (a CaseResults or DisturbedResults)."""
+    return np.mean(np.asarray(actors.scores, dtype=np.float32), axis=0, dtype=np.float32)
+
+
+def baseline_rows(results, laws, actors):
+    """csv_rows / robustness_rows for a run_linear result (first axis: the laws) with the law's name in the first column and, last,
+    actors_score: the mean over the run's platoons of the actors' score for the same (scenario, disturbance, seed)."""
+    f = lambda x: "" if np.isnan(x) else repr(float(x))
+    mean = actors_mean_score(actors)
+    disturbed = hasattr(results, "disturbances")
+    rows = robustness_rows(results, laws) if disturbed else csv_rows(results, laws)
+    nv = results.metrics[METRICS[0]].shape[-1]
+    per_law = len(rows) // max(1, len(laws))
+    flat = np.repeat(mean.reshape(-1), nv)  # (scenario, (disturbance,) seed, vehicle) order, as the rows of one law
+    return [r + [f(flat[i % per_law])] for i, r in enumerate(rows)]
+
+
+def write_baseline_csv(path, results, laws, actors):
+    import csv
+
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(BASELINE_ROBUSTNESS_HEADER if hasattr(results, "disturbances") else BASELINE_HEADER)
+        w.writerows(baseline_rows(results, laws, actors))
+
+
+def baseline_report_lines(results, laws):
+    """One line per law and scenario, as report_lines words a platoon's (nominal level of a disturbed result)."""
+    nominal = results.nominal() if hasattr(results, "disturbances") else results
+    return [ln.replace("platoon ", "baseline ", 1) for ln in report_lines(nominal, laws)]
 
 
 def report_lines(results, platoon_tags):

@@ -621,6 +621,27 @@ int avd_eval_cases_dist_block(int K, int L);
 /* host only, no HIP call: sigma [K][3], delay [K], drop_q [K] in HOST memory */
 int avd_eval_cases_dist_check(int K, const float* sigma, const int32_t* delay, const uint32_t* drop_q);
 
+/* ---- linear baseline of the scenario evaluator: the cases above under a static gain row per vehicle instead of an actor ------------
+ * G gain sets x K cases in ONE launch. gains[g] [L][4] is gain set g's row (g0, g1, g2, g3) per vehicle; case k is x0[k] [L][4],
+ * prev_a0[k] [L], leader[k] [T] and, disturbed, sigma[k] [3], delay[k], drop_q[k], noise_seed[k], abc[k] [L][24] exactly as
+ * avd_eval_cases_dist_f32 reads them (DEVICE memory; avd_eval_cases_dist_check validates host copies). All five tables NULL: the
+ * constants block's plant and a perfect observation; abc alone may be NULL; any other mix is AVD_E_INVALID. Per step and vehicle,
+ * with ob the observed state formed as avd_eval_cases_dist_f32 forms it (same ring, same Philox streams, counter = step, index =
+ * vehicle, a zero sigma skips its add):
+ *   u = clip(((g0 * ob[0] + g1 * ob[1]) + g2 * ob[2]) + g3 * ob[3], lo, hi)   without contraction; Model A: the first three terms
+ * then the platoon step, reward and terminal test of avd_eval_cases_f32 on the true state. counters[g][k] [L]: per vehicle, the
+ * sequential float32 sum of the step's -reward (the decentralized convention). metrics[g][k] [L][AVD_EVAL_NMETRIC] (or NULL): the
+ * eight metrics of avd_eval_cases_f32, same statements, same order. One lane per (gain set, case, vehicle), floor(64 / L) rollouts
+ * per one-wave workgroup; a G x K that needs more than 2^31 - 1 workgroups is AVD_E_UNSUPPORTED. Every argument is checked on the
+ * host before any HIP call. */
+int avd_eval_linear_f32(const avd_env_consts* d_consts, int G, int K, int L, int T, const float* gains, const float* x0,
+                        const float* prev_a0, const float* leader, float lo, float hi, float sample_rate, const float* sigma,
+                        const int32_t* delay, const uint32_t* drop_q, const uint64_t* noise_seed, const float* abc, float* counters,
+                        float* metrics, void* stream);
+/* fitness[g] = (the sequential float32 sum of counters[g] [K][L] in (k, v) order) / (float)(K * L): one thread per gain set,
+ * bit-identical to the same loop in NumPy float32. */
+int avd_linear_fitness_f32(int G, int K, int L, const float* counters, float* fitness, void* stream);
+
 /* ---- training under disturbances: the fused step with an observation model (domain randomisation) --------------------------------
  * The evaluator's observation model (above) at training time. A run has n_levels (1 .. AVD_TRAIN_MAX_LEVELS) disturbance levels;
  * platoon p trains under level p % n_levels (an experiment batch: the level of the solo run's platoon index, (g / n_groups) %
