@@ -256,6 +256,53 @@ def _check_train_leader(args, conf, auto_reset, hparams=None):
             raise SystemExit(f"--train_leader: {e}")
 
 
+def _residual_kw(args):
+    """VecTrainer's residual keyword, only where the flag was given (a `tuned` law has been searched by then: _resolve_residual)."""
+    return {} if getattr(args, "residual", None) is None else dict(residual=args.residual)
+
+
+def _resolve_residual(args, conf, auto_reset, hparams=None):
+    """--residual before anything is allocated: the word `tuned` becomes the law --baseline_tune's grid picks on the suite's nominal cases
+    (evaluator.tune_linear, run once: the baseline section reuses the result), then the refusals that need the run's configuration,
+    under the flag's own name."""
+    law = getattr(args, "residual", None)
+    if law is None:
+        return
+    from . import scenarios as _sc
+    from . import trainer
+
+    try:
+        if law == _sc.TUNED:
+            args.baselines = _Baselines(conf, args)
+            args.residual = law = _sc.ResidualLaw(*[v for _, v in dict(args.baselines.tune)["gains"]], source="tuned")
+        trainer.check_residual(conf, law, args.rng, int(os.environ.get("WORLD_SIZE", "1") or 1), hparams=hparams)
+    except ValueError as e:
+        raise SystemExit(f"--residual: {e}")
+
+
+def _record_residual(conf, args):
+    """conf.json's residual_law: the law the saved actors correct (esim applies it: the actors alone are not the policy)."""
+    if getattr(args, "residual", None) is not None:
+        conf.residual_law = args.residual.record()
+
+
+def _baselines(conf, args):
+    """The run's baseline section, computed once (--residual tuned has already searched the grid)."""
+    if getattr(args, "baselines", None) is None:
+        args.baselines = _Baselines(conf, args)
+    return args.baselines
+
+
+def _saved_residual(exp_path):
+    """The residual law an experiment directory's conf.json records, or None."""
+    import json
+
+    from . import scenarios as _sc
+
+    with open(os.path.join(exp_path, "conf.json")) as f:
+        return _sc.ResidualLaw.from_record(json.load(f).get("residual_law"))
+
+
 def _suite(args):
     """run_cases' keyword arguments from the scenario flags."""
     return dict(scenarios=args.scenarios, seeds=args.eval_seeds, amp=args.scenario_amp,
@@ -438,6 +485,14 @@ def get_cmdl_args(argv, conf):
                          "reference's training input, a clean share (noise: its scale, default reset_max_u; no amp or period). conf.json "
                          "records the manoeuvres as train_leader. Composes with --seeds, --train_disturb, --scenarios and --disturb; not with "
                          "--sweep / --pbt, --rng host, the centralized framework or a process group (not in the reference CLI)")
+    tr.add_argument("--residual", type=str, default=None, metavar="SPEC",
+                    help="--rng device: train the actors as a RESIDUAL on a static linear law, kp=..,kv=..[,ka=..,kf=..,scale=..] (scale in "
+                         "(0, 1], default 1: the correction's authority), or the word `tuned`: the law --baseline_tune's grid picks on the "
+                         "--scenarios suite, searched before training. The plant receives clip(law(observation) + scale * action); the "
+                         "replay and the learners keep the action. conf.json records residual_law, and `esim <dir>` applies it in every "
+                         "mode. Composes with --seeds, --train_disturb, --train_leader, --keep_best, --scenarios, --disturb, --baseline "
+                         "and every --engine; not with --sweep / --pbt, --rng host, the centralized framework or a process group of "
+                         "more than one rank (not in the reference CLI)")
     tr.add_argument("--keep_best", type=int, default=None, metavar="STEPS",
                     help="keep the best actors seen in training, on the device: at step 0, at every multiple of STEPS and at the last step "
                          "one evaluator rollout launch scores every rollout group (a platoon's actors; the shared sets; each experiment's of "
@@ -506,6 +561,23 @@ def get_cmdl_args(argv, conf):
             args.train_leader = check_manoeuvres([parse_manoeuvre(m) for m in args.train_leader])
         except ValueError as e:
             ap.error(f"--train_leader: {e}")
+    if getattr(args, "residual", None) is not None:
+        from . import scenarios as _sc
+
+        if args.rng != "device":
+            ap.error("--residual needs --rng device")
+        if args.sweep is not None or args.pbt is not None:
+            ap.error("--residual does not combine with --sweep / --pbt")
+        if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+            ap.error("--residual is not available under a process group of more than one rank")
+        try:  # (what needs the run's configuration: trainer.check_residual applies it)
+            args.residual = _sc.parse_residual(args.residual)
+            if args.residual != _sc.TUNED:
+                _sc.check_residual(args.residual)
+        except ValueError as e:
+            ap.error(f"--residual: {e}")
+        if args.residual == _sc.TUNED and (args.scenarios is None or getattr(args, "baseline_tune", None) is None):
+            ap.error("--residual tuned needs --scenarios and --baseline_tune (the grid the law is searched on)")
     if getattr(args, "pbt", None) is not None or getattr(args, "pbt_fraction", None) is not None or getattr(args, "pbt_perturb", None) is not None:
         if args.pbt is None:
             ap.error("--pbt_fraction / --pbt_perturb need --pbt")
@@ -589,9 +661,10 @@ def main(argv=None, conf=None):
             from . import evaluator
             nofrl = conf.fed_method == conf.nofrl
             _check_train_leader(args, conf, "platoon")
+            _resolve_residual(args, conf, "platoon")
             try:
                 vt = trainer.VecTrainer(conf, rng="device", auto_reset="platoon", shared_engine=args.engine, fused_update=nofrl,
-                                        train_disturb=args.train_disturb, **_lead_kw(args))
+                                        train_disturb=args.train_disturb, **_lead_kw(args), **_residual_kw(args))
             except ValueError as e:
                 if args.train_disturb is None:
                     raise
@@ -606,6 +679,10 @@ def main(argv=None, conf=None):
                     import copy
                     grp = copy.copy(vt.agents)
                     grp.theta, grp.stats, grp.n_sets = vt.agents.theta[:vt.M], vt.agents.stats[:vt.M], vt.M
+                if vt.residual is not None:  # the residual policy's score: the rollout kernel with the law (the same value a batch writes)
+                    # (no set_state here as below: run_many restores the global np.random state itself -- with the zero law this line
+                    # must leave every later draw, and so every output file, what the path below leaves)
+                    return float(evaluator.run_many(conf, grp, [0], set_mod=vt.M if vt.shared else 0, base_law=vt.residual)[0][0, 0])
                 r = evaluator.run(conf=conf, actors=grp, pl_idx=1, set_mod=vt.M if vt.shared else 0)[0]
                 np.random.set_state(rng_state)
                 return float(r)
@@ -633,9 +710,10 @@ def main(argv=None, conf=None):
                 print(f"warning: {vt.nonfinite_updates()} weight-set updates were skipped for non-finite gradients", file=sys.stderr)
         else:
             _check_train_leader(args, conf, False)
+            _resolve_residual(args, conf, False)
             try:
                 vt = trainer.VecTrainer(conf, rng=args.rng, auto_reset=False, shared_engine=args.engine, train_disturb=args.train_disturb,
-                                        **_lead_kw(args))
+                                        **_lead_kw(args), **_residual_kw(args))
             except ValueError as e:
                 if args.train_disturb is None:
                     raise
@@ -653,7 +731,7 @@ def main(argv=None, conf=None):
             res = vt.evaluate_scenarios(**_suite(args)) if _disturb(args) is None else vt.evaluate_robustness(disturbances=_disturb(args), **_suite(args))
             _write_suite(base, conf, res, range(1, vt.P + 1), args)
             if _baseline_flags(args) is not None:
-                _Baselines(conf, args).write(base, conf, res)
+                _baselines(conf, args).write(base, conf, res)
         n_save = vt.P if args.save_platoons is None and args.episodes == "reference" else min(vt.P, 4 if args.save_platoons is None else args.save_platoons)
         artifacts.save_agents(base, vt.agents, n_save, vt.M, shared=vt.shared)
         # what ran, beside the reference's fields: how many platoons' agents the directory holds (esim loops over exactly these),
@@ -666,6 +744,7 @@ def main(argv=None, conf=None):
                                    "weighted_window closed episodes")
         _record_train_levels(conf, args)
         _record_train_leader(conf, args)
+        _record_residual(conf, args)
         if args.keep_best is not None:
             _KeepResults(vt, args).write(base, conf, n_save)
         artifacts.config_writer(os.path.join(base, "conf.json"), conf)
@@ -680,6 +759,7 @@ def main(argv=None, conf=None):
         # a run saved with --save_platoons N holds the first N platoons' agents: conf.json says how many (older directories: all)
         import json
         saved = json.load(open(os.path.join(args.exp_path, "conf.json"))).get("saved_platoons", conf.num_platoons)
+        law = _saved_residual(args.exp_path)  # (None: the actors alone, today's entry points; read once for every mode below)
         if args.scenarios is not None:  # ALL saved platoons' actors in one group, one launch
             from . import scenarios as _sc
             saved = int(saved)
@@ -690,8 +770,8 @@ def main(argv=None, conf=None):
                 for m in range(M):
                     grp.set_weights((p - 1) * M + m, "actor", artifacts.load_actor_weights(args.exp_path, p, m + 1))
             _check_baseline_conf(args, conf, _exit)
-            full = evaluator.run_cases(conf, grp, range(saved), **_suite(args)) if _disturb(args) is None else \
-                evaluator.run_disturbed(conf, grp, range(saved), disturbances=_disturb(args), **_suite(args))
+            full = evaluator.run_cases(conf, grp, range(saved), base_law=law, **_suite(args)) if _disturb(args) is None else \
+                evaluator.run_disturbed(conf, grp, range(saved), disturbances=_disturb(args), base_law=law, **_suite(args))
             res = _write_suite(args.exp_path, conf, full, range(1, saved + 1), args)  # (conf.json itself is not rewritten)
             print("\n".join(_sc.report_lines(res, range(1, saved + 1))))
             if _baseline_flags(args) is not None:
@@ -705,7 +785,10 @@ def main(argv=None, conf=None):
             grp = vec.AgentGroup(M, shape.num_states, shape.num_actions, conf, hidd_mult=shape.hidden_multiplier)
             for m in range(M):
                 grp.set_weights(m, "actor", artifacts.load_actor_weights(args.exp_path, p, m + 1))
-            rew, _ = evaluator.run(conf=conf, actors=grp, pl_idx=p, manual_timestep_override=args.n_timesteps)
+            if law is not None:  # a residual policy: the rollout kernel with the law in front of the plant
+                rew = evaluator.run_many(conf, grp, [0], manual_timestep_override=args.n_timesteps, base_law=law)[0][0, 0]
+            else:
+                rew, _ = evaluator.run(conf=conf, actors=grp, pl_idx=p, manual_timestep_override=args.n_timesteps)
             print(f"platoon {p}: cumulative platoon reward {rew}")
     else:
         raise SystemExit("modes: tr, esim")
@@ -757,10 +840,11 @@ def train_seed_batch(args, conf, base, experiments=None):
         except ValueError as e:
             raise SystemExit(f"--train_disturb: {e}")
     _check_train_leader(args, conf, "platoon", hparams=hps)
+    _resolve_residual(args, conf, "platoon", hparams=hps)
     try:
         vt = trainer.VecTrainer(conf, rng="device", auto_reset="platoon", shared_engine=args.engine,
                                 fused_update=conf.fed_method == conf.nofrl, seeds=seeds, hparams=hps,
-                                train_disturb=getattr(args, "train_disturb", None), **_lead_kw(args))
+                                train_disturb=getattr(args, "train_disturb", None), **_lead_kw(args), **_residual_kw(args))
     except ValueError as e:
         raise SystemExit(f"{flag}: {e}")
     vt.reset_episode()
@@ -830,7 +914,7 @@ def train_seed_batch(args, conf, base, experiments=None):
     suite = None  # [E, P, scen, (dist,) seed, ...], one launch
     if args.scenarios is not None:
         suite = vt.evaluate_scenarios(**_suite(args)) if _disturb(args) is None else vt.evaluate_robustness(disturbances=_disturb(args), **_suite(args))
-    baselines = _Baselines(conf, args) if suite is not None and _baseline_flags(args) is not None else None  # computed once
+    baselines = _baselines(conf, args) if suite is not None and _baseline_flags(args) is not None else None  # computed once
     n_save = min(P, 4 if args.save_platoons is None else args.save_platoons)
     kept = _KeepResults(vt, args) if getattr(args, "keep_best", None) is not None else None
     done = []
@@ -854,6 +938,7 @@ def train_seed_batch(args, conf, base, experiments=None):
                           ["lineage", lineage[e]]]
         _record_train_levels(ce, args)
         _record_train_leader(ce, args)
+        _record_residual(ce, args)
         if suite is not None:
             _write_suite(d, ce, _slice(suite, e), range(1, P + 1), args)
             if baselines is not None:

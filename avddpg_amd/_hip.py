@@ -104,6 +104,9 @@ _PROTOS = {
     "avd_step_fused_dist_lead_seeds_f32": [_P, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _f, _f, _f, _f, _f,
                                            _i, _P, _i, _u64, _u64, _P, _i, _i64, _P, _i, _P, _P, _P, _P, _P, _P, _P, _u64, _i, _i, _P, _P,
                                            _P, _P, _i, _P],
+    "avd_step_fused_res_f32": [_P, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _f, _f, _f, _f, _f, _i, _u64,
+                               _u64, _u64, _P, _i, _i64, _P, _P, _i, _i, _P, _P, _P, _P, _P, _P, _P, _u64, _i, _i, _P, _P, _P, _P, _i,
+                               _P, _f, _P, _P],
     "avd_observe_f32": [_i, _i, _P, _P, _i, _P, _P, _P, _u64, _u64, _P, _P, _P],
     "avd_observe_seeds_f32": [_i, _i, _P, _P, _i, _P, _P, _P, _P, _i, _u64, _P, _P, _P],
     "avd_learn_hp_f32": [_LP, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _f, _P, _P, _P, _i, _i, _P],
@@ -156,6 +159,10 @@ _PROTOS = {
     "avd_eval_cases_dist_f32": [_LP, _P, _i, _i, _i, _i, _i, _P, _P, _i, _P, _P, _P, _P, _f, _f, _f, _f, _P, _P, _P, _P, _P, _P, _P, _P],
     "avd_eval_cases_dist_block": [_i, _i],  # returns the block size itself, as avd_eval_cases_block
     "avd_eval_cases_dist_check": [_i, _P, _P, _P],  # HOST arrays
+    "avd_eval_rollout_res_f32": [_LP, _P, _i, _i, _i, _i, _P, _P, _i, _P, _P, _P, _P, _i, _P, _f, _f, _f, _f, _P, _i, _P, _P, _P, _P,
+                                 _P, _f, _P],
+    "avd_eval_cases_res_f32": [_LP, _P, _i, _i, _i, _i, _i, _P, _P, _i, _P, _P, _P, _P, _f, _f, _f, _f, _P, _P, _P, _P, _P, _P, _f, _P,
+                               _P, _P],
     "avd_eval_linear_f32": [_P, _i, _i, _i, _i, _P, _P, _P, _P, _f, _f, _f, _P, _P, _P, _P, _P, _P, _P, _P],
     "avd_linear_fitness_f32": [_i, _i, _i, _P, _P, _P],
     "avd_gemm_bt_bf16": [_i, _i, _i, _P, C.c_long, _P, C.c_long, _P, C.c_long, _P],

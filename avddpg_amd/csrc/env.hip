@@ -9,7 +9,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "eval_common.h"
 
 namespace avd {
 
@@ -336,6 +336,20 @@ template <class... H>
 __device__ __forceinline__ const DistRef& dist_of(const H&... h) { return pack_member<DistRef>(h...); }
 template <class... H>
 __device__ __forceinline__ const LeadRef& lead_of(const H&... h) { return pack_member<LeadRef>(h...); }
+
+// ---- training a residual on a linear law (avd_step_fused_res_f32) --------------------------------------------------------------
+// A third trailing argument, the last of the pack, after a DistRef and / or a LeadRef or alone. Seen from the agent the law is part of the
+// environment: the plant, the reward's norm_u and the value chained to the follower take u = residual_law(gains row of the vehicle, what
+// the agent observes of the pre-step state, scale, the agent's action); action[], the replay row and the learners keep the agent's action.
+struct BaseRef {
+    const float* gains;  // [L][4]: (kp, kv, ka, kf) per vehicle
+    float scale;         // the residual's authority, in (0, 1]
+    float* applied;      // [P*L] u, or NULL
+};
+template <class... H>
+constexpr bool has_base = (std::is_same<H, BaseRef>::value || ...);
+template <class... H>
+__device__ __forceinline__ const BaseRef& base_of(const H&... h) { return pack_member<BaseRef>(h...); }
 constexpr int LINK_RING = 16;  // slots of a vehicle's V2V history (delays 0 .. 15), indexed by counter & 15
 constexpr int LEVEL_WORDS = sizeof(avd_train_level) / 4;
 static_assert(sizeof(avd_train_level) == 32 && (LINK_RING & (LINK_RING - 1)) == 0, "level rows of 8 words; the ring index is a mask");
@@ -366,10 +380,12 @@ __device__ __forceinline__ void observe_noise(float4& ob, const float4& x, const
 // floats, then [n_levels][8] words: at most 25 088 B) in place of the constants block's L rows.
 // LEAD (avd_step_fused_lead_f32, one LeadRef in the pack, with or without a DistRef): the leader's input comes from the platoon's
 // manoeuvre. Only the leader's lane reads the table, one float from global memory (16 x T floats would cost more to stage per block).
+// BASE (avd_step_fused_res_f32, one BaseRef last in the pack): the plant takes u, the law's output plus scale * the agent's action uu.
+// Each lane reads its vehicle's gain row as one 16-byte load (L rows, the same for every platoon: cache hits after the first wave).
 template <bool G, bool HP = false, class... H>
 __global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs a, H... hp) {
 #pragma clang fp contract(off)
-    constexpr bool DIST = has_dist<H...>, LEAD = has_lead<H...>;
+    constexpr bool DIST = has_dist<H...>, LEAD = has_lead<H...>, BASE = has_base<H...>;
     __shared__ float sA[AVD_MAX_L][16], sB[AVD_MAX_L][4], sC[AVD_MAX_L][4];  // (DIST: unused, the rows live in dynamic LDS)
     const avd_env_consts* cst = a.cst;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, L = a.L;
@@ -394,6 +410,8 @@ __global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs 
     const long v = (long)p * L + i;
     float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
     float pa = 0.f, uu = 0.f, exog_own = 0.f;
+    float ub = 0.f;                                   // BASE: what the plant receives (otherwise uu itself)
+    float4 seen = make_float4(0.f, 0.f, 0.f, 0.f);  // BASE with DIST: what the agent observed of x_in (the replay row's s)
     uint64_t okey = 0;  // DIST: the observation's Philox key, vehicle index and level (idle lanes: level 0, nothing stored)
     uint32_t orv = 0;
     int lvl = 0;
@@ -416,6 +434,13 @@ __global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs 
         a.ou_state[v] = noise;
         uu = fminf(fmaxf(a.actor_out[v] + noise, a.lo), a.hi);
         a.action[v] = uu;
+        if constexpr (BASE) {
+            const BaseRef& b = base_of(hp...);
+            float4 ob = xv;
+            if constexpr (DIST) ob = seen = dist_of(hp...).obs_in[v];
+            ub = residual_law(((const float4*)b.gains)[i], ob, cst->model_a != 0, b.scale, uu, a.lo, a.hi);
+            if (b.applied) b.applied[v] = ub;
+        }
         if (i == 0) {  // leader exog, redrawn every step (workers/trainer.py:291-295; util.get_random_val)
             const u32x4 re = philox_at(key, a.exog_counter, (uint32_t)pl, STREAM_NORMAL);
             if constexpr (LEAD) {
@@ -443,12 +468,13 @@ __global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs 
 #pragma unroll
     for (int r = 0; r < 4; ++r) ax[r] = ((Ai[r * 4 + 0] * xv.x + Ai[r * 4 + 1] * xv.y) + Ai[r * 4 + 2] * xv.z) + Ai[r * 4 + 3] * xv.w;
     // what the follower behind needs: Model B the action, Model A the post-step accel -- one lane up
-    const float chain = cst->model_a ? (ax[2] + Bi[2] * uu) : uu;
+    const float u = BASE ? ub : uu;  // the plant's input
+    const float chain = cst->model_a ? (ax[2] + Bi[2] * u) : u;
     const float from_pred = __shfl_up(chain, 1);
     const float exog = (i == 0) ? exog_own : from_pred;
     const float norm_ep = fabsf(xv.x) / cst->max_ep;
     const float norm_ev = fabsf(xv.y) / cst->max_ev;
-    const float norm_u = fabsf(uu) / cst->abs_action_high;
+    const float norm_u = fabsf(u) / cst->abs_action_high;
     const float n_jerk = fabsf(xv.z - pa) / cst->two_max_a;
     const bool is_term = active && ((fabsf(xv.x) > cst->max_ep) || (fabsf(xv.y) > cst->max_ev)) && (cst->can_terminate != 0);
     float rew = (((cst->ca * norm_ep + cst->cb * norm_ev) + cst->cc * norm_u) + cst->cd * n_jerk) * cst->re_scalar;
@@ -457,10 +483,10 @@ __global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs 
     const unsigned long long tmask = __ballot(is_term);
     if (active) {
         float4 xn;
-        xn.x = (ax[0] + Bi[0] * uu) + Ci[0] * exog;
-        xn.y = (ax[1] + Bi[1] * uu) + Ci[1] * exog;
-        xn.z = (ax[2] + Bi[2] * uu) + Ci[2] * exog;
-        xn.w = (ax[3] + Bi[3] * uu) + Ci[3] * exog;
+        xn.x = (ax[0] + Bi[0] * u) + Ci[0] * exog;
+        xn.y = (ax[1] + Bi[1] * u) + Ci[1] * exog;
+        xn.z = (ax[2] + Bi[2] * u) + Ci[2] * exog;
+        xn.w = (ax[3] + Bi[3] * u) + Ci[3] * exog;
         a.x_out[v] = xn;
         a.prev_a[v] = xv.z;
         if (a.cum_accel) a.cum_accel[v] = a.cum_accel[v] + xv.z;
@@ -490,7 +516,8 @@ __global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs 
             observe_noise(ob, xn, lv, okey, d.obs_counter, orv);
             d.obs_out[v] = ob;
             row_n = ob;
-            if (a.ring) row_s = d.obs_in[v];
+            if constexpr (BASE) row_s = seen;
+            else if (a.ring) row_s = d.obs_in[v];
         }
         if (a.ring) {  // ReplayBuffer.add (src/replaybuffer.py:36-47): row [s a r s'] at slot counter % capacity
             const int S = a.S, row = 2 * S + 2;
@@ -670,7 +697,7 @@ static int step_fused_launch(const char* who, const avd_env_consts* d_consts, in
                              float exog_scale, int exog_uniform, uint64_t seed, const uint64_t* d_seeds, int n_groups,
                              uint64_t ou_counter, uint64_t exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward,
                              void* stream, const avd_hparams* d_hp = nullptr, const DistRef* dist = nullptr,
-                             const LeadRef* lead = nullptr) {
+                             const LeadRef* lead = nullptr, const BaseRef* base = nullptr) {
     AVD_REQUIRE(P > 0 && L > 0 && L <= AVD_MAX_L && (S == 3 || S == 4), "%s: P=%d L=%d S=%d", who, P, L, S);
     AVD_REQUIRE(d_consts && x_in && x_out && prev_a && reward && done && actor_out && ou_state && action && leader_exog,
                 "%s: null pointer", who);
@@ -687,6 +714,18 @@ static int step_fused_launch(const char* who, const avd_env_consts* d_consts, in
     if constexpr (HP)
         hipLaunchKernelGGL((step_fused_kernel<G, true, HpRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS), 0,
                            (hipStream_t)stream, a, HpRef{d_hp, n_groups, 1});
+    else if (base && dist && lead)  // the residual's four forms (avd_step_fused_res_f32): the BaseRef last in the pack
+        hipLaunchKernelGGL((step_fused_kernel<G, false, DistRef, LeadRef, BaseRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS),
+                           sizeof(float) * (size_t)dist->n_levels * (L * 24 + LEVEL_WORDS), (hipStream_t)stream, a, *dist, *lead, *base);
+    else if (base && lead)
+        hipLaunchKernelGGL((step_fused_kernel<G, false, LeadRef, BaseRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS), 0,
+                           (hipStream_t)stream, a, *lead, *base);
+    else if (base && dist)
+        hipLaunchKernelGGL((step_fused_kernel<G, false, DistRef, BaseRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS),
+                           sizeof(float) * (size_t)dist->n_levels * (L * 24 + LEVEL_WORDS), (hipStream_t)stream, a, *dist, *base);
+    else if (base)
+        hipLaunchKernelGGL((step_fused_kernel<G, false, BaseRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS), 0,
+                           (hipStream_t)stream, a, *base);
     else if (dist && lead)
         hipLaunchKernelGGL((step_fused_kernel<G, false, DistRef, LeadRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS),
                            sizeof(float) * (size_t)dist->n_levels * (L * 24 + LEVEL_WORDS), (hipStream_t)stream, a, *dist, *lead);
@@ -930,6 +969,42 @@ extern "C" int avd_step_fused_dist_lead_seeds_f32(const avd_env_consts* d_consts
                                    actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt, ou_std_dev, action_low, action_high,
                                    exog_scale, exog_uniform, 0, d_seeds, n_groups, ou_counter, exog_counter, ring, cap, replay_counter,
                                    ep_reward, stream, nullptr, &d, &l);
+}
+
+// ---- training a residual on a linear law: ONE entry point for the nominal, seed-batch, disturbed and manoeuvre forms ------------------
+extern "C" int avd_step_fused_res_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
+    float* prev_a, float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done, int32_t* any_done_other,
+    const float* actor_out, float* ou_state, float* action, float* leader_exog, float ou_theta, float ou_mean, float ou_dt,
+    float ou_std_dev, float action_low, float action_high, float exog_scale, int exog_uniform, uint64_t seed, uint64_t ou_counter,
+    uint64_t exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward, const uint64_t* d_seeds, int n_groups,
+    int n_levels, const avd_train_level* h_levels, const avd_train_level* d_levels, const float* d_plant, const float* obs_in,
+    float* obs_out, float* link_hist, float* link_recv, uint64_t obs_counter, int n_manoeuvres, int T, const float* d_table,
+    const float* d_noise, const uint8_t* d_gaussian, const int32_t* ep_len, int ep_step, const float* d_gains, float scale,
+    float* applied, void* stream) {
+    const char* who = "avd_step_fused_res_f32";
+    if (const int rc = residual_check(who, d_gains, scale, L, L)) return rc;  // (the fused step is decentralized by construction)
+    AVD_REQUIRE(n_levels >= 0 && n_manoeuvres >= 0, "%s: n_levels=%d n_manoeuvres=%d (0: none)", who, n_levels, n_manoeuvres);
+    AVD_REQUIRE(!obs_in || ((uintptr_t)obs_in & 15) == 0, "%s: obs_in=%p (must be 16-byte aligned)", who, (const void*)obs_in);
+    DistRef d;
+    LeadRef l;
+    if (n_levels > 0)
+        if (const int rc = dist_args(who, n_levels, h_levels, d_levels, d_plant, obs_in, obs_out, link_hist, link_recv, obs_counter, d)) return rc;
+    if (n_manoeuvres > 0)
+        if (const int rc = lead_args(who, n_manoeuvres, T, d_table, d_noise, d_gaussian, ep_len, ep_step, n_levels > 0 ? n_levels : 1, l)) return rc;
+    const BaseRef b = {d_gains, scale, applied};
+    const DistRef* dp = n_levels > 0 ? &d : nullptr;
+    const LeadRef* lp = n_manoeuvres > 0 ? &l : nullptr;
+    if (d_seeds) {
+        AVD_REQUIRE_GROUPS(who, P);
+        return step_fused_launch<true>(who, d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done, any_done, any_done_other,
+                                       actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt, ou_std_dev, action_low, action_high,
+                                       exog_scale, exog_uniform, 0, d_seeds, n_groups, ou_counter, exog_counter, ring, cap, replay_counter,
+                                       ep_reward, stream, nullptr, dp, lp, &b);
+    }
+    return step_fused_launch<false>(who, d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done, any_done, any_done_other,
+                                    actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt, ou_std_dev, action_low, action_high,
+                                    exog_scale, exog_uniform, seed, nullptr, 1, ou_counter, exog_counter, ring, cap, replay_counter,
+                                    ep_reward, stream, nullptr, dp, lp, &b);
 }
 
 extern "C" int avd_observe_f32(int P, int L, const float* x, float* obs, int n_levels, const avd_train_level* d_levels, float* link_hist,

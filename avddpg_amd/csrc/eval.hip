@@ -39,8 +39,12 @@ struct EvalArgs {
     float *tr_states, *tr_actions, *tr_jerks;  // [n_trace][T][L][obs_width], [n_trace][T][L], [n_trace][T][L]
 };
 
-__global__ __launch_bounds__(NTHREADS) void eval_rollout_kernel(const EvalArgs a) {
+// B is empty (the actors alone: parameter list and code as before the residual variant existed) or one ResArgs: the plant, the reward
+// and the traces take residual_law(the vehicle's gain row, its state, scale, the actor's clipped action)
+template <class... B>
+__global__ __launch_bounds__(NTHREADS) void eval_rollout_kernel(const EvalArgs a, const B... res) {
 #pragma clang fp contract(off)
+    constexpr bool RES = pack_has<ResArgs, B...>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const avd_mlp_layout& L = a.lay;
     const int tid = threadIdx.x, nv = a.L, r = blockIdx.x;
@@ -107,6 +111,10 @@ __global__ __launch_bounds__(NTHREADS) void eval_rollout_kernel(const EvalArgs a
         VehStep vs = {};
         if (veh) {
             uu = fminf(fmaxf(raw[tid], a.lo), a.hi);  // np.clip (ddpgagent.py:27)
+            if constexpr (RES) {
+                const ResArgs& b = pack_get<ResArgs>(res...);
+                uu = residual_law(((const float4*)b.gains)[tid], ((const float4*)xs)[tid], cst->model_a != 0, b.scale, uu, a.lo, a.hi);
+            }
             vs = veh_step_pre(cst, sA + tid * 16, sB + tid * 4, xv, uu);
             chain[tid] = vs.chain;
         }
@@ -143,31 +151,31 @@ __global__ __launch_bounds__(NTHREADS) void eval_rollout_kernel(const EvalArgs a
 
 using namespace avd;
 
-extern "C" int avd_eval_rollout_f32(const avd_mlp_layout* lay, const avd_env_consts* d_consts, int R, int L, int M, int T,
+static int rollout_launch(const char* who, const ResArgs* res, const avd_mlp_layout* lay, const avd_env_consts* d_consts, int R, int L, int M, int T,
                                     const float* theta, const float* stats, int n_sets, const int32_t* set_base, const float* x0,
                                     const float* prev_a0, const float* leader, int n_start, const int32_t* start_idx, float high,
                                     float lo, float hi, float sample_rate, float* counters, int n_trace, const int32_t* trace_idx,
                                     float* tr_states, float* tr_actions, float* tr_jerks, void* stream) {
-    AVD_REQUIRE(lay && d_consts, "avd_eval_rollout_f32: null layout or constants");
-    AVD_REQUIRE(L >= 1 && L <= AVD_MAX_L, "avd_eval_rollout_f32: L=%d (L must be 1..%d)", L, AVD_MAX_L);
-    AVD_REQUIRE(M == L || M == 1, "avd_eval_rollout_f32: M=%d (M must be L=%d, decentralized, or 1, centralized)", M, L);
-    AVD_REQUIRE(R >= 1 && T >= 1, "avd_eval_rollout_f32: R=%d T=%d (both must be >= 1)", R, T);
-    AVD_REQUIRE(n_sets >= M && n_start >= 1, "avd_eval_rollout_f32: n_sets=%d n_start=%d (need n_sets >= M=%d, n_start >= 1)",
+    AVD_REQUIRE(lay && d_consts, "%s: null layout or constants", who);
+    AVD_REQUIRE(L >= 1 && L <= AVD_MAX_L, "%s: L=%d (L must be 1..%d)", who, L, AVD_MAX_L);
+    AVD_REQUIRE(M == L || M == 1, "%s: M=%d (M must be L=%d, decentralized, or 1, centralized)", who, M, L);
+    AVD_REQUIRE(R >= 1 && T >= 1, "%s: R=%d T=%d (both must be >= 1)", who, R, T);
+    AVD_REQUIRE(n_sets >= M && n_start >= 1, "%s: n_sets=%d n_start=%d (need n_sets >= M=%d, n_start >= 1)", who,
                 n_sets, n_start, M);
     AVD_REQUIRE(theta && stats && set_base && x0 && prev_a0 && leader && start_idx && counters,
-                "avd_eval_rollout_f32: null pointer");
+                "%s: null pointer", who);
     AVD_REQUIRE(n_trace >= 0 && (n_trace == 0 || (trace_idx && tr_states && tr_actions && tr_jerks)),
-                "avd_eval_rollout_f32: n_trace=%d needs trace_idx and the three trace buffers", n_trace);
-    AVD_REQUIRE(sample_rate > 0.f, "avd_eval_rollout_f32: sample_rate=%g", (double)sample_rate);
+                "%s: n_trace=%d needs trace_idx and the three trace buffers", who, n_trace);
+    AVD_REQUIRE(sample_rate > 0.f, "%s: sample_rate=%g", who, (double)sample_rate);
     // the model shape the platoon implies: M * A = L actions, observations of 4L / M floats (the first S read)
     const int x_stride = 4 * L / M;
     AVD_REQUIRE(lay->A * M == L && lay->S <= x_stride && lay->S >= 1,
-                "avd_eval_rollout_f32: layout S=%d A=%d does not fit L=%d M=%d (need A * M == L, S <= %d)", lay->S, lay->A, L, M,
+                "%s: layout S=%d A=%d does not fit L=%d M=%d (need A * M == L, S <= %d)", who, lay->S, lay->A, L, M,
                 x_stride);
-    AVD_REQUIRE(lay->H1 > 0 && lay->H2 > 0, "avd_eval_rollout_f32: layout H1=%d H2=%d", lay->H1, lay->H2);
+    AVD_REQUIRE(lay->H1 > 0 && lay->H2 > 0, "%s: layout H1=%d H2=%d", who, lay->H1, lay->H2);
     const size_t lds = sizeof(float) * ((size_t)EVAL_LDS_FIXED + NTHREADS + lay->H1 + lay->H2);
     if (lds > 160 * 1024) {
-        set_error("avd_eval_rollout_f32: hidden sizes need %zu B of LDS (> 160 KiB)", lds);
+        set_error("%s: hidden sizes need %zu B of LDS (> 160 KiB)", who, lds);
         return AVD_E_UNSUPPORTED;
     }
     EvalArgs a;
@@ -179,8 +187,37 @@ extern "C" int avd_eval_rollout_f32(const avd_mlp_layout* lay, const avd_env_con
     a.inv_dt = 1.0f / sample_rate;  // host float32 division, as torch forms the reciprocal of a Python-scalar divisor
     a.counters = counters, a.n_trace = n_trace, a.trace_idx = trace_idx;
     a.tr_states = tr_states, a.tr_actions = tr_actions, a.tr_jerks = tr_jerks;
+    if (res) {
+        if (const int rc = residual_check(who, res->gains, res->scale, M, L)) return rc;
+        if (lds > 48 * 1024)
+            (void)hipFuncSetAttribute((const void*)eval_rollout_kernel<ResArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(eval_rollout_kernel<ResArgs>, dim3(R), dim3(NTHREADS), lds, (hipStream_t)stream, a, *res);
+        return check_launch(who);
+    }
     if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute((const void*)eval_rollout_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(eval_rollout_kernel, dim3(R), dim3(NTHREADS), lds, (hipStream_t)stream, a);
-    return check_launch("avd_eval_rollout_f32");
+        (void)hipFuncSetAttribute((const void*)eval_rollout_kernel<>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(eval_rollout_kernel<>, dim3(R), dim3(NTHREADS), lds, (hipStream_t)stream, a);
+    return check_launch(who);
+}
+
+extern "C" int avd_eval_rollout_f32(const avd_mlp_layout* lay, const avd_env_consts* d_consts, int R, int L, int M, int T,
+                                    const float* theta, const float* stats, int n_sets, const int32_t* set_base, const float* x0,
+                                    const float* prev_a0, const float* leader, int n_start, const int32_t* start_idx, float high,
+                                    float lo, float hi, float sample_rate, float* counters, int n_trace, const int32_t* trace_idx,
+                                    float* tr_states, float* tr_actions, float* tr_jerks, void* stream) {
+    return rollout_launch("avd_eval_rollout_f32", nullptr, lay, d_consts, R, L, M, T, theta, stats, n_sets, set_base, x0, prev_a0, leader,
+                          n_start, start_idx, high, lo, hi, sample_rate, counters, n_trace, trace_idx, tr_states, tr_actions, tr_jerks, stream);
+}
+
+// The rollout of a residual policy: the actors' clipped action r enters the plant as residual_law(gains row, state, scale, r); the
+// action trace holds that plant input. Decentralized agents only.
+extern "C" int avd_eval_rollout_res_f32(const avd_mlp_layout* lay, const avd_env_consts* d_consts, int R, int L, int M, int T,
+                                        const float* theta, const float* stats, int n_sets, const int32_t* set_base, const float* x0,
+                                        const float* prev_a0, const float* leader, int n_start, const int32_t* start_idx, float high,
+                                        float lo, float hi, float sample_rate, float* counters, int n_trace, const int32_t* trace_idx,
+                                        float* tr_states, float* tr_actions, float* tr_jerks, const float* d_gains, float scale,
+                                        void* stream) {
+    const ResArgs res = {d_gains, scale};
+    return rollout_launch("avd_eval_rollout_res_f32", &res, lay, d_consts, R, L, M, T, theta, stats, n_sets, set_base, x0, prev_a0, leader,
+                          n_start, start_idx, high, lo, hi, sample_rate, counters, n_trace, trace_idx, tr_states, tr_actions, tr_jerks, stream);
 }

@@ -39,4 +39,38 @@ __device__ __forceinline__ float veh_step_post(const avd_env_consts* cst, const 
     return -rew;
 }
 
+// The residual policy's plant input (avd_step_fused_res_f32, avd_eval_rollout_res_f32, avd_eval_cases_res_f32): the linear law of
+// eval_linear_kernel (lin.hip: the same two lines, the feed-forward term skipped under Model A) on what the agent observes, plus
+// scale * the agent's action r, clipped. Zero gains and scale 1 give clip(r).
+__device__ __forceinline__ float residual_law(float4 gn, float4 ob, bool model_a, float scale, float r, float lo, float hi) {
+#pragma clang fp contract(off)
+    float z = (gn.x * ob.x + gn.y * ob.y) + gn.z * ob.z;
+    if (!model_a) z = z + gn.w * ob.w;
+    return fminf(fmaxf(z + scale * r, lo), hi);  // np.clip
+}
+
+// The evaluator kernels' trailing argument of a residual policy: the law's gain rows and the residual's authority
+struct ResArgs {
+    const float* gains;  // [L][4]: (kp, kv, ka, kf) per vehicle
+    float scale;         // in (0, 1]
+};
+template <class T, class... H>
+constexpr bool pack_has = (std::is_same<H, T>::value || ...);
+template <class T, class First, class... Rest>
+__device__ __forceinline__ const T& pack_get(const First& f, const Rest&... r) {
+    if constexpr (std::is_same<T, First>::value) return f;
+    else return pack_get<T>(r...);
+}
+
+// The residual entry points' own arguments, checked: 16-byte aligned gain rows, scale in (0, 1], decentralized agents
+inline int residual_check(const char* who, const float* gains, float scale, int M, int L) {
+    AVD_REQUIRE(gains && ((uintptr_t)gains & 15) == 0, "%s: gains=%p (must be a non-null, 16-byte aligned [L][4] table)", who, (const void*)gains);
+    AVD_REQUIRE(scale > 0.f && scale <= 1.f, "%s: scale=%g (must be in (0, 1])", who, (double)scale);
+    if (M != L) {
+        set_error("%s: M=%d L=%d (a residual on a per-vehicle law needs decentralized agents, M == L)", who, M, L);
+        return AVD_E_UNSUPPORTED;
+    }
+    return AVD_OK;
+}
+
 }  // namespace avd

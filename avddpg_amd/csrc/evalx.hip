@@ -150,11 +150,12 @@ __device__ __forceinline__ void block_dot_rows(const float* xT, const float* __r
     __syncthreads();
 }
 
-// D is empty (the nominal kernel: parameter list and code as before the disturbed variant existed) or one DistArgs
+// D is empty (the nominal kernel: parameter list and code as before the disturbed variant existed), one DistArgs, one ResArgs (a
+// residual policy: the plant input is residual_law on the row's xs entry -- under DistArgs the observation) or a DistArgs then a ResArgs
 template <int RB, class... D>
 __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a, const D... dist) {
 #pragma clang fp contract(off)
-    constexpr bool DIST = sizeof...(D) != 0;
+    constexpr bool DIST = pack_has<DistArgs, D...>, RES = pack_has<ResArgs, D...>;
     constexpr int UK = RB >= 16 || (DIST && RB >= 8) ? 2 : 4;  // disturbed, 8 rows: 170 VGPRs with four k in flight, 2 waves per SIMD
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const avd_mlp_layout& L = a.lay;
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a,
     }
     const avd_env_consts* cst = a.cst;
     if constexpr (DIST) {
-        const DistArgs da{dist...};
+        const DistArgs& da = pack_get<DistArgs>(dist...);
         for (int i = tid; i < RB * nv * 24; i += NTHREADS) {
             const int r = i / (nv * 24), j = i - r * (nv * 24), vi = j / 24, e = j - vi * 24;
             vdat[(r * AVD_MAX_L + vi) * DIST_VEH + e] = (da.abc && r < nrows) ? da.abc[(long)(k0 + r) * nv * 24 + j]
@@ -292,6 +293,11 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a,
         VehStep vs = {};
         if (veh) {
             uu = fminf(fmaxf(raw[row * AVD_MAX_L + v], a.lo), a.hi);  // np.clip (ddpgagent.py:27)
+            if constexpr (RES) {  // traces, reward and metrics below take the plant's input
+                const ResArgs& b = pack_get<ResArgs>(dist...);
+                uu = residual_law(((const float4*)b.gains)[v], ((const float4*)(xs + row * 4 * AVD_MAX_L))[v], cst->model_a != 0, b.scale, uu,
+                                  a.lo, a.hi);
+            }
             const float* Av = DIST ? vdat + (row * AVD_MAX_L + v) * DIST_VEH : sA + v * 16;  // this vehicle's A, B (disturbed: its case's)
             vs = veh_step_pre(cst, Av, DIST ? Av + 16 : sB + v * 4, xv, uu);
             chain[row * AVD_MAX_L + v] = vs.chain;
@@ -462,5 +468,41 @@ extern "C" int avd_eval_cases_dist_f32(const avd_mlp_layout* lay, const avd_env_
         case 8: return launch_cases<8>(who, a, lds, (hipStream_t)stream, d);
         case 4: return launch_cases<4>(who, a, lds, (hipStream_t)stream, d);
         default: return launch_cases<1>(who, a, lds, (hipStream_t)stream, d);
+    }
+}
+
+// The scenario evaluator for a residual policy, nominal (all five disturbance tables null) or disturbed (only abc may be null, with
+// avd_eval_cases_dist_f32's block sizes): the actors' clipped action r enters the plant as residual_law(gains row, what the vehicle
+// observes, scale, r). Decentralized agents only.
+extern "C" int avd_eval_cases_res_f32(const avd_mlp_layout* lay, const avd_env_consts* d_consts, int G, int K, int L, int M, int T,
+                                      const float* theta, const float* stats, int n_sets, const int32_t* set_base, const float* x0,
+                                      const float* prev_a0, const float* leader, float high, float lo, float hi, float sample_rate,
+                                      const float* sigma, const int32_t* delay, const uint32_t* drop_q, const uint64_t* noise_seed,
+                                      const float* abc, const float* d_gains, float scale, float* counters, float* metrics, void* stream) {
+    const char* who = "avd_eval_cases_res_f32";
+    const bool dist = sigma || delay || drop_q || noise_seed || abc;
+    AVD_REQUIRE(!dist || (sigma && delay && drop_q && noise_seed),
+                "%s: null disturbance table (all five null: the nominal plant and a perfect observation; otherwise only abc may be null)", who);
+    CasesArgs a;
+    int rb;
+    size_t lds;
+    if (const int rc = cases_args(who, lay, d_consts, G, K, L, M, T, theta, stats, n_sets, set_base, x0, prev_a0, leader, high, lo, hi,
+                                  sample_rate, counters, metrics, dist, a, rb, lds))
+        return rc;
+    if (const int rc = residual_check(who, d_gains, scale, M, L)) return rc;
+    const ResArgs r = {d_gains, scale};
+    if (dist) {
+        const DistArgs d = {sigma, delay, drop_q, noise_seed, abc};
+        switch (rb) {
+            case 8: return launch_cases<8>(who, a, lds, (hipStream_t)stream, d, r);
+            case 4: return launch_cases<4>(who, a, lds, (hipStream_t)stream, d, r);
+            default: return launch_cases<1>(who, a, lds, (hipStream_t)stream, d, r);
+        }
+    }
+    switch (rb) {
+        case 16: return launch_cases<16>(who, a, lds, (hipStream_t)stream, r);
+        case 8: return launch_cases<8>(who, a, lds, (hipStream_t)stream, r);
+        case 4: return launch_cases<4>(who, a, lds, (hipStream_t)stream, r);
+        default: return launch_cases<1>(who, a, lds, (hipStream_t)stream, r);
     }
 }

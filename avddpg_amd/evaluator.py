@@ -57,11 +57,21 @@ def run(conf=None, actors=None, pl_idx=None, seed=True, manual_timestep_override
                         counters=counters.cpu().numpy(), leader=inputs)
 
 
+def _base_gains(base_law, conf, dev):
+    """A residual policy's law (scenarios.ResidualLaw) checked and on the device: (gains float32 [L, 4], scale) -- or (None, None)."""
+    if base_law is None:
+        return None, None
+    from . import scenarios as _sc
+
+    _sc.check_residual(base_law, conf)
+    return torch.from_numpy(base_law.gains(conf.pl_size)).to(dev), float(base_law.scale)
+
+
 class RolloutBatch:
     """The device inputs of one avd_eval_rollout_f32 launch (prepare_many); ``launch()`` enqueues it on the current stream,
     ``results()`` reads the counters and traces back. run_many = prepare_many + launch + results."""
 
-    def __init__(self, conf, actors, platoons, set_mod, seeds, manual_timestep_override, trace, set_bases=None):
+    def __init__(self, conf, actors, platoons, set_mod, seeds, manual_timestep_override, trace, set_bases=None, base_law=None):
         platoons = [int(p) for p in platoons]
         seeds = [int(conf.evaluation_seed)] if seeds is None else [int(s) for s in seeds]
         if not platoons or not seeds:
@@ -118,9 +128,16 @@ class RolloutBatch:
         self.tr_s = torch.empty(nt, T, L, env.obs_width, **f32) if nt else None
         self.tr_a = torch.empty(nt, T, L, **f32) if nt else None
         self.tr_j = torch.empty(nt, T, L, **f32) if nt else None
+        self.gains, self.res_scale = _base_gains(base_law, conf, dev)
 
     def launch(self):
         a, c = self.actors, self.conf
+        if self.gains is not None:  # a residual policy: the law in front of the plant (avd_eval_rollout_res_f32)
+            call("avd_eval_rollout_res_f32", a._layp, ptr(self.env.d_consts), self.n_roll, self.L, self.M, self.T, ptr(a.theta), ptr(a.stats),
+                 a.n_sets, ptr(self.set_base), ptr(self.x0), ptr(self.pa0), ptr(self.leader), self.NS, ptr(self.start_idx), a.high,
+                 c.action_low, c.action_high, c.sample_rate, ptr(self.counters), len(self.tr_roll), ptr(self.tr_idx), ptr(self.tr_s),
+                 ptr(self.tr_a), ptr(self.tr_j), ptr(self.gains), self.res_scale, stream_handle())
+            return
         call("avd_eval_rollout_f32", a._layp, ptr(self.env.d_consts), self.n_roll, self.L, self.M, self.T, ptr(a.theta), ptr(a.stats),
              a.n_sets, ptr(self.set_base), ptr(self.x0), ptr(self.pa0), ptr(self.leader), self.NS, ptr(self.start_idx), a.high,
              c.action_low, c.action_high, c.sample_rate, ptr(self.counters), len(self.tr_roll), ptr(self.tr_idx), ptr(self.tr_s),
@@ -140,12 +157,12 @@ class RolloutBatch:
         return scores, cnt, traces
 
 
-def prepare_many(conf, actors, platoons, set_mod=None, seeds=None, manual_timestep_override=None, trace=(), set_bases=None):
+def prepare_many(conf, actors, platoons, set_mod=None, seeds=None, manual_timestep_override=None, trace=(), set_bases=None, base_law=None):
     """run_many's host part (start states and leader inputs drawn, device inputs uploaded) as a RolloutBatch."""
-    return RolloutBatch(conf, actors, platoons, set_mod, seeds, manual_timestep_override, trace, set_bases)
+    return RolloutBatch(conf, actors, platoons, set_mod, seeds, manual_timestep_override, trace, set_bases, base_law)
 
 
-def run_many(conf, actors, platoons, set_mod=None, seeds=None, manual_timestep_override=None, trace=(), set_bases=None):
+def run_many(conf, actors, platoons, set_mod=None, seeds=None, manual_timestep_override=None, trace=(), set_bases=None, base_law=None):
     """The rollout of ``run`` for many platoons' actors and evaluation seeds at once: ONE launch of the evaluator rollout
     kernel (avd_eval_rollout_f32, csrc/eval.hip), one workgroup per (platoon, seed). What Trainer.run_simulations
     (workers/trainer.py:537-550) and esim (run.py:60-70) do platoon by platoon.
@@ -157,11 +174,13 @@ def run_many(conf, actors, platoons, set_mod=None, seeds=None, manual_timestep_o
     seeds: evaluation seeds (default ``(conf.evaluation_seed,)``); each one's start state and leader inputs are drawn on the
     host exactly as ``run`` draws them, and the caller's global ``np.random`` state is restored on return.
     trace: (i, k) index pairs into the result (or plain i for k = 0) whose per-step traces are returned.
+    base_law: a scenarios.ResidualLaw the actors correct (avd_eval_rollout_res_f32): the plant input, and the ``inputs`` trace, is
+    clip(law(state) + scale * the actors' action). None: the actors alone, today's entry point with today's arguments.
 
     Returns (scores, counters, traces): scores float32 [len(platoons), len(seeds)] (round(mean(counters), 3), :145),
     counters float32 [len(platoons), len(seeds), M], traces {(i, k): dict like run's}. Entry [i, k] is bit-identical to
     ``run`` with ``evaluation_seed = seeds[k]`` on platoon ``platoons[i]``'s sets."""
-    b = prepare_many(conf, actors, platoons, set_mod, seeds, manual_timestep_override, trace, set_bases)
+    b = prepare_many(conf, actors, platoons, set_mod, seeds, manual_timestep_override, trace, set_bases, base_law)
     b.launch()
     return b.results()
 
@@ -225,7 +244,7 @@ class CaseBatch:
     ``results()`` reads counters and metrics back. run_cases = prepare_cases + launch + results. ``block`` is the number of cases per
     workgroup the kernel uses for this batch (avd_eval_cases_block)."""
 
-    def __init__(self, conf, actors, platoons, scenarios, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override):
+    def __init__(self, conf, actors, platoons, scenarios, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override, base_law=None):
         from . import _hip
         from . import scenarios as _sc
 
@@ -276,9 +295,16 @@ class CaseBatch:
         self.counters = torch.empty(self.G, self.K, M, **f32)
         self.metrics = torch.empty(self.G, self.K, L, _hip.AVD_EVAL_NMETRIC, **f32)
         self.block = int(_hip.lib().avd_eval_cases_block(self.K, L))
+        self.gains, self.res_scale = _base_gains(base_law, conf, dev)
 
     def launch(self):
         a, c = self.actors, self.conf
+        if self.gains is not None:  # a residual policy (avd_eval_cases_res_f32, no disturbance tables)
+            call("avd_eval_cases_res_f32", a._layp, ptr(self.env.d_consts), self.G, self.K, self.L, self.M, self.T, ptr(a.theta),
+                 ptr(a.stats), a.n_sets, ptr(self.set_base), ptr(self.x0), ptr(self.pa0), ptr(self.leader), a.high, c.action_low,
+                 c.action_high, c.sample_rate, None, None, None, None, None, ptr(self.gains), self.res_scale, ptr(self.counters),
+                 ptr(self.metrics), stream_handle())
+            return
         call("avd_eval_cases_f32", a._layp, ptr(self.env.d_consts), self.G, self.K, self.L, self.M, self.T, ptr(a.theta), ptr(a.stats),
              a.n_sets, ptr(self.set_base), ptr(self.x0), ptr(self.pa0), ptr(self.leader), a.high, c.action_low, c.action_high,
              c.sample_rate, ptr(self.counters), ptr(self.metrics), stream_handle())
@@ -297,13 +323,13 @@ class CaseBatch:
 
 
 def prepare_cases(conf, actors, platoons, scenarios=("gaussian",), seeds=None, amp=None, period_s=10.0, set_mod=None, set_bases=None,
-                  manual_timestep_override=None):
+                  manual_timestep_override=None, base_law=None):
     """run_cases' host part (start states drawn, leader profiles made, device inputs uploaded) as a CaseBatch."""
-    return CaseBatch(conf, actors, platoons, scenarios, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override)
+    return CaseBatch(conf, actors, platoons, scenarios, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override, base_law)
 
 
 def run_cases(conf, actors, platoons, scenarios=("gaussian",), seeds=None, amp=None, period_s=10.0, set_mod=None, set_bases=None,
-              manual_timestep_override=None):
+              manual_timestep_override=None, base_law=None):
     """Every platoon's actors over a library of leader scenarios x evaluation seeds in ONE launch of the scenario evaluator
     (avd_eval_cases_f32, csrc/evalx.hip): one workgroup per (platoon, block of cases), each weight element read once per block, the
     per-vehicle control metrics reduced on the device. The reference's evaluator names these input responses and fills in only the
@@ -313,11 +339,12 @@ def run_cases(conf, actors, platoons, scenarios=("gaussian",), seeds=None, amp=N
     seeds: evaluation seeds (default ``(conf.evaluation_seed,)``). Cases are scenarios x seeds, seeds innermost; a case's start state
     is drawn as ``run`` draws it for its seed, and only the gaussian scenario's leader inputs depend on the seed. The caller's global
     ``np.random`` state is restored on return. actors / platoons / set_mod / set_bases address weight sets as in ``run_many``.
+    base_law: a scenarios.ResidualLaw the actors correct (avd_eval_cases_res_f32), as in ``run_many``; sum_u2 is then the plant input's.
 
     Returns a CaseResults. Entry [i, s, k] of its counters is bit-identical to the rollout kernel's (run_many) on the same start state
     and leader row -- for the gaussian scenario, to ``run_many(seeds=seeds)[1][i, k]`` -- and its metrics to
     scenarios.metrics_from_traces on that rollout's traces."""
-    b = prepare_cases(conf, actors, platoons, scenarios, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override)
+    b = prepare_cases(conf, actors, platoons, scenarios, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override, base_law)
     b.launch()
     return b.results()
 
@@ -345,12 +372,13 @@ class DisturbedBatch(CaseBatch):
     """The device inputs of one avd_eval_cases_dist_f32 launch (prepare_disturbed): CaseBatch's cases with a disturbance axis between
     scenario and seed, and the per-case disturbance tables. ``levels`` are the Disturbances, scenarios.NOMINAL first."""
 
-    def __init__(self, conf, actors, platoons, scenarios, disturbances, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override):
+    def __init__(self, conf, actors, platoons, scenarios, disturbances, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override,
+                 base_law=None):
         from . import _hip
         from . import scenarios as _sc
 
         levels = [_sc.NOMINAL] + _sc.check_disturbances(disturbances, conf)
-        super().__init__(conf, actors, platoons, scenarios, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override)
+        super().__init__(conf, actors, platoons, scenarios, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override, base_law)
         NC, ND, NS, L, dev = self.NC, len(levels), self.NS, self.L, self.x0.device
         self.levels, self.ND, self.K = levels, ND, NC * ND * NS
         # cases: scenarios x levels x seeds, seeds innermost; a case's start state and leader row are its (scenario, seed)'s, always
@@ -371,6 +399,12 @@ class DisturbedBatch(CaseBatch):
 
     def launch(self):
         a, c = self.actors, self.conf
+        if self.gains is not None:  # a residual policy: the law acts on the observation (avd_eval_cases_res_f32 with the tables)
+            call("avd_eval_cases_res_f32", a._layp, ptr(self.env.d_consts), self.G, self.K, self.L, self.M, self.T, ptr(a.theta),
+                 ptr(a.stats), a.n_sets, ptr(self.set_base), ptr(self.x0), ptr(self.pa0), ptr(self.leader), a.high, c.action_low,
+                 c.action_high, c.sample_rate, ptr(self.sigma), ptr(self.delay), ptr(self.drop_q), ptr(self.noise_seed), ptr(self.abc),
+                 ptr(self.gains), self.res_scale, ptr(self.counters), ptr(self.metrics), stream_handle())
+            return
         call("avd_eval_cases_dist_f32", a._layp, ptr(self.env.d_consts), self.G, self.K, self.L, self.M, self.T, ptr(a.theta),
              ptr(a.stats), a.n_sets, ptr(self.set_base), ptr(self.x0), ptr(self.pa0), ptr(self.leader), a.high, c.action_low,
              c.action_high, c.sample_rate, ptr(self.sigma), ptr(self.delay), ptr(self.drop_q), ptr(self.noise_seed), ptr(self.abc),
@@ -390,22 +424,24 @@ class DisturbedBatch(CaseBatch):
 
 
 def prepare_disturbed(conf, actors, platoons, scenarios=("gaussian",), disturbances=(), seeds=None, amp=None, period_s=10.0, set_mod=None,
-                      set_bases=None, manual_timestep_override=None):
+                      set_bases=None, manual_timestep_override=None, base_law=None):
     """run_disturbed's host part (run_cases' plus the per-case disturbance tables, checked and uploaded) as a DisturbedBatch."""
-    return DisturbedBatch(conf, actors, platoons, scenarios, disturbances, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override)
+    return DisturbedBatch(conf, actors, platoons, scenarios, disturbances, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override,
+                          base_law)
 
 
 def run_disturbed(conf, actors, platoons, scenarios=("gaussian",), disturbances=(), seeds=None, amp=None, period_s=10.0, set_mod=None,
-                  set_bases=None, manual_timestep_override=None):
+                  set_bases=None, manual_timestep_override=None, base_law=None):
     """run_cases under disturbances: every platoon's actors over scenarios x [nominal, *disturbances] x seeds (seeds innermost) in ONE
     launch of the disturbed scenario evaluator (avd_eval_cases_dist_f32, csrc/evalx.hip). A scenarios.Disturbance acts on what the
     actors observe (sensor noise on ep, ev, a; delay and loss on the communicated 4th state) and on the plant (its engine lag); counters
     and metrics come from the true state, and start states are always the nominal configuration's. The noise seed of a case is its
-    evaluation seed. Everything else is as in run_cases.
+    evaluation seed. Everything else is as in run_cases; with base_law the law reads the vehicle's OBSERVATION.
 
     Returns a DisturbedResults; its ``nominal()`` slice, and every level whose axes are all at their zero, is bit-identical to
     run_cases on the same scenarios and seeds."""
-    b = prepare_disturbed(conf, actors, platoons, scenarios, disturbances, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override)
+    b = prepare_disturbed(conf, actors, platoons, scenarios, disturbances, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override,
+                          base_law)
     b.launch()
     return b.results()
 

@@ -350,6 +350,82 @@ def check_baselines(laws, conf=None, reserved=(TUNED,)):
     return out
 
 
+# ---- residual policies: the actors correct a linear law (tr --residual; avd_step_fused_res_f32, avd_eval_*_res_f32) ------------------
+
+RESIDUAL_NAME = "residual"
+
+
+class ResidualLaw(LinearLaw):
+    """A LinearLaw the actors are trained as a correction to: the plant receives u = clip(law(observed state) + scale * r, action_low,
+    action_high) with r the agent's action. ``scale`` in (0, 1] is the residual's authority (1: the correction can span the whole
+    action range). ``source`` records where the gains came from (conf.json's residual_law): "given" or "tuned"."""
+
+    def __init__(self, kp=0, kv=0, ka=0, kf=0, table=None, scale=1.0, name=RESIDUAL_NAME, source="given"):
+        super().__init__(name, kp, kv, ka, kf, table)
+        self.scale, self.source = scale, str(source)
+
+    def record(self):
+        """conf.json's residual_law entry, a list of pairs (conf.json keeps lists, not dicts): the gains in GAIN_KEYS order, the scale,
+        the table when there is one, the source."""
+        out = [[k, float(getattr(self, k))] for k in GAIN_KEYS] + [["scale", float(self.scale)]]
+        if self.table is not None:
+            out.append(["table", np.asarray(self.table, dtype=np.float64).tolist()])
+        return out + [["source", self.source]]
+
+    @classmethod
+    def from_record(cls, pairs):
+        """The law of a conf.json's residual_law entry (None stays None); an unknown or repeated key is a ValueError."""
+        if pairs is None:
+            return None
+        keys = [k for k, _ in pairs]
+        bad = sorted({k for k in keys if k not in GAIN_KEYS + ("scale", "table", "source") or keys.count(k) > 1})
+        if bad:
+            raise ValueError(f"residual_law: unknown or repeated key(s) {bad}")
+        d = dict(pairs)
+        return cls(*(d.get(k, 0) for k in GAIN_KEYS), table=d.get("table"), scale=d.get("scale", 1.0), source=d.get("source", "given"))
+
+    def __repr__(self):
+        return "ResidualLaw(" + ", ".join([f"{k}={v!r}" for k, v in self.items()] + [f"scale={self.scale!r}"]) + ")"
+
+
+def parse_residual(text):
+    """``kp=2,kv=1[,ka=..,kf=..,scale=..]`` -> ResidualLaw, or the word ``tuned`` -> TUNED (the caller searches the gains). An unknown
+    key, a key given twice, a value that is no number or an empty text is a ValueError; the values are checked by check_residual."""
+    text = str(text).strip()
+    if text == TUNED:
+        return TUNED
+    keys = GAIN_KEYS + ("scale",)
+    kw = {}
+    parts = [q.strip() for q in text.split(",") if q.strip()]
+    if not parts:
+        raise ValueError(f"residual {text!r}: no gain given (kp=..,kv=..[,ka=..,kf=..,scale=..], or the word {TUNED!r})")
+    for part in parts:
+        key, eq, val = part.partition("=")
+        key, val = key.strip(), val.strip()
+        if not eq or key not in keys:
+            raise ValueError(f"residual: unknown key {key!r} (one of {', '.join(keys)}, as key=value, or the word {TUNED!r})")
+        if key in kw:
+            raise ValueError(f"residual: {key} given twice")
+        try:
+            kw[key] = float(val)
+        except ValueError:
+            raise ValueError(f"residual: {key}={val!r} is not a number") from None
+    return ResidualLaw(**kw)
+
+
+def check_residual(law, conf=None):
+    """The law, checked. A ValueError for: not a ResidualLaw; check_baselines' rules (a non-finite gain, a table that is not [*, 4];
+    with ``conf`` a non-zero kf under Model A, a table whose row count is not conf.pl_size, the centralized framework); a scale that is
+    no number in (0, 1]."""
+    if not isinstance(law, ResidualLaw):
+        raise ValueError(f"{law!r} is not a scenarios.ResidualLaw")
+    check_baselines([law], conf, reserved=())
+    sc = law.scale
+    if isinstance(sc, bool) or not isinstance(sc, (int, float, np.integer, np.floating)) or not (0 < sc <= 1):
+        raise ValueError(f"residual: scale={sc!r} must be a number in (0, 1]")
+    return law
+
+
 def parse_gain_grid(text):
     """``kp=lo:hi:n,kv=...`` (keys of GAIN_KEYS; ``key=value`` is the single value) -> float32 [G, 4]: per key np.linspace(lo, hi, n) in
     float64, then cast; a missing key is the single value 0; the product in kp, kv, ka, kf order, the last varying fastest. A

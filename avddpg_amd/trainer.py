@@ -158,6 +158,27 @@ def check_train_leader(conf, train_leader, rng, group, auto_reset, fused_step=No
     return out
 
 
+def check_residual(conf, residual, rng, world_size=1, fused_step=None, hparams=None):
+    """Why a run cannot train its actors as a RESIDUAL on this linear law (VecTrainer(residual=...)), raised as a ValueError -- or the
+    checked scenarios.ResidualLaw. Called before anything is allocated or launched. The law sits in the fused step's launch
+    (avd_step_fused_res_f32): device RNG, decentralized agents, one rank, no sweep."""
+    from . import scenarios
+
+    if conf.framework == conf.cntrl:
+        raise ValueError("a residual policy needs the decentralized framework: a linear law is per vehicle and the centralized framework "
+                         "has no fused step")
+    if rng != "device":
+        raise ValueError("a residual policy needs rng='device': the law is applied in the fused step's launch")
+    if fused_step is not None and not fused_step:
+        raise ValueError("a residual policy needs the fused step (fused_step=False has no law in front of the plant)")
+    if hparams is not None:
+        raise ValueError("a residual policy does not combine with a hyperparameter sweep or PBT (hparams=...): the sweep's step has no "
+                         "residual twin")
+    if int(world_size) > 1:
+        raise ValueError("a residual policy runs on one rank: no process group of more than one rank")
+    return scenarios.check_residual(residual, conf)
+
+
 def check_keep_best(world_size):
     """Why a run cannot keep the best actors seen (VecTrainer.enable_keep_best), raised as a ValueError -- or None. Called before
     anything is allocated or launched."""
@@ -183,7 +204,8 @@ SET_ENGINE_MAX_SETS = {"fused": 64, "fused3": 64}
 class VecTrainer:
     def __init__(self, conf, device=None, rng="device", group=None, shared_sets=None, seed=None, auto_reset=False,
                  pipeline_chunks=1, fused_update=False, shared_engine=None, init_seed=None, fused_step=None,
-                 replay_ring=None, overlap_allreduce=None, seeds=None, hparams=None, train_disturb=None, train_leader=None):
+                 replay_ring=None, overlap_allreduce=None, seeds=None, hparams=None, train_disturb=None, train_leader=None,
+                 residual=None):
         """group: torch.distributed process group whose ranks each hold ``conf.num_platoons`` platoons
         (interfrl gradients are all-reduced over it). auto_reset: end episodes on the device (no host
         sync per step); needs rng='device'. True: the reference's rule -- any terminal platoon (or the step limit) ends
@@ -217,9 +239,22 @@ class VecTrainer:
         and manoeuvres cross. The input at step k of the platoon's OWN episode is scenarios.manoeuvre_table's row at k -- the array the
         scenario evaluator feeds -- plus the manoeuvre's noise times the step's unit draw; a gaussian manoeuvre is the reference's input, the
         clean share. k is env.ep_len with per-platoon episodes, self.ep_step under the host episode loop (auto_reset=False).
-        check_train_leader says what it needs. None: nothing changes -- no buffer is made, the same entry points run."""
+        check_train_leader says what it needs. None: nothing changes -- no buffer is made, the same entry points run.
+        residual: a scenarios.ResidualLaw the actors are trained as a correction to (residual policy learning): the plant, the reward's
+        control term and the value chained to the follower take u = clip(law(what the agent observes) + scale * r), r the agent's
+        noisy clipped action; self.actions and the replay keep r, so no learner changes, and self.applied holds u. The step runs
+        avd_step_fused_res_f32 (with seeds, train_disturb and train_leader as given) and every evaluation this trainer makes passes
+        the law. check_residual says what it needs. None: nothing changes -- no buffer is made, the same entry points run."""
         conf.refresh()
         self.levels = self.manoeuvres = self.lead = None
+        self.residual = None
+        if residual is not None:
+            ranks = 1
+            if group is not None:
+                import torch.distributed as _td
+                ranks = _td.get_world_size(group)
+            self.residual = check_residual(conf, residual, rng, ranks, fused_step, hparams)
+        self.res_gains = self.applied = None
         if train_disturb is not None:
             self.levels = check_train_disturb(conf, train_disturb, rng, group, fused_step, hparams)
         if train_leader is not None:
@@ -381,6 +416,11 @@ class VecTrainer:
             self.lead = dict(n=len(self.manoeuvres), T=table.shape[1], table=up(table), noise=up(noise), gaussian=up(gauss.astype(np.uint8)))
             if auto_reset == "platoon":
                 self.env.ensure_episode_state()
+        if self.residual is not None:  # the gain table, uploaded once; what the plant received, one float per vehicle
+            if not self.fused_step:
+                raise ValueError("a residual policy needs the fused step (fused_step=False has no law in front of the plant)")
+            self.res_gains = torch.from_numpy(self.residual.gains(self.L)).to(self.device)
+            self.applied = torch.zeros(self.P, self.L, **f32)
         self.fused_update = bool(fused_update)  # nofrl (any framework / widths the learn kernels serve): avd_learn_update_f32
         # fused_update also has the learn kernel evaluate the UPDATED actor on the state the next step acts from
         # (workers/trainer.py:287-289): self.actor_out then already holds the next step's actor outputs unless the states
@@ -484,7 +524,25 @@ class VecTrainer:
             per_platoon = self.auto_reset == "platoon"
             lead = (ld["n"], ld["T"], ptr(ld["table"]), ptr(ld["noise"]), ptr(ld["gaussian"]), ptr(env.ep_len) if per_platoon else None,
                     0 if per_platoon else min(self.ep_step, ld["T"] - 1))
-        if self.levels is not None:
+        if self.residual is not None:
+            # a residual policy: ONE entry point for every combination (seed table or none, levels or none, manoeuvres or none)
+            if self.levels is not None:
+                env.obs, env.obs_prev = env.obs_prev, env.obs
+                env.obs_counter += 1
+                dist = (len(self.levels), env.h_levels, ptr(env.d_levels), ptr(env.d_plant), ptr(env.obs_prev), ptr(env.obs),
+                        ptr(env.link_hist), ptr(env.link_recv), env.obs_counter)
+            else:
+                dist = (0, None, None, None, None, None, None, None, 0)
+            key = (self.seed, ) if self.seeds is None else (0, )
+            grp = (None, 1) if self.seeds is None else (ptr(env.d_seeds), self.E)
+            call("avd_step_fused_res_f32", ptr(env.d_consts), self.P, self.L, self.S, ptr(env.x_prev), ptr(env.x), ptr(env.prev_a),
+                 ptr(env.cum_accel), ptr(env.reward), ptr(env.term), ptr(env.done), ptr(env.any_done), ptr(other),
+                 ptr(self.actor_out), ptr(ou.state), ptr(self.actions), ptr(self.leader_exog), conf.theta, ou.mean, conf.ou_dt,
+                 conf.std_dev, conf.action_low, conf.action_high, conf.reset_max_u, 1 if conf.rand_gen == conf.uniform else 0,
+                 *key, ou.calls, self.exog_calls, ptr(rp.ring), rp.cap, rp.buffer_counter, ptr(self.ep_reward), *grp, *dist,
+                 *(lead if lead else (0, 0, None, None, None, None, 0)), ptr(self.res_gains), float(self.residual.scale),
+                 ptr(self.applied), stream_handle())
+        elif self.levels is not None:
             # training under disturbances (avd_step_fused_dist_f32): the level's plant, the observation of the new state with the next
             # observation counter, the replay row from the observation buffers -- which swap where x and x_prev do
             env.obs, env.obs_prev = env.obs_prev, env.obs
@@ -830,15 +888,15 @@ class VecTrainer:
             E, M = self.E, self.M
             platoons = list(range(self.P_exp)) if platoons is None else list(platoons)
             if self.shared:  # one rollout per experiment, on its sets e*M .. e*M+M-1
-                sc = evaluator.run_many(self.conf, agents, list(range(E)), set_mod=M, set_bases=[e * M for e in range(E)])[0]
+                sc = evaluator.run_many(self.conf, agents, list(range(E)), set_mod=M, set_bases=[e * M for e in range(E)], base_law=self.residual)[0]
                 return np.repeat(sc[:, :1], len(platoons), axis=1)
             glob = [vec.batch_platoon(e, p, E) for e in range(E) for p in platoons]
-            return evaluator.run_many(self.conf, agents, glob)[0][:, 0].reshape(E, len(platoons))
+            return evaluator.run_many(self.conf, agents, glob, base_law=self.residual)[0][:, 0].reshape(E, len(platoons))
         platoons = list(range(self.P)) if platoons is None else list(platoons)
         if self.shared:
-            sc = evaluator.run_many(self.conf, agents, [0], set_mod=self.M)[0]
+            sc = evaluator.run_many(self.conf, agents, [0], set_mod=self.M, base_law=self.residual)[0]
             return np.repeat(sc[:, 0], len(platoons))
-        return evaluator.run_many(self.conf, agents, platoons)[0][:, 0]
+        return evaluator.run_many(self.conf, agents, platoons, base_law=self.residual)[0][:, 0]
 
     def evaluate_scenarios(self, scenarios, seeds=None, platoons=None, amp=None, period_s=10.0, agents=None):
         """The CURRENT actors of each of this rank's ``platoons`` (default: all) over leader scenarios x evaluation seeds, from one
@@ -849,7 +907,7 @@ class VecTrainer:
         from . import evaluator
 
         agents = self.agents if agents is None else agents  # (or a group laid out like it: best_agents())
-        kw = dict(scenarios=scenarios, seeds=seeds, amp=amp, period_s=period_s)
+        kw = dict(scenarios=scenarios, seeds=seeds, amp=amp, period_s=period_s, base_law=self.residual)
         if self.seeds is not None:
             E, M = self.E, self.M
             platoons = list(range(self.P_exp)) if platoons is None else list(platoons)
@@ -877,7 +935,7 @@ class VecTrainer:
         from . import evaluator
 
         agents = self.agents if agents is None else agents  # (or a group laid out like it: best_agents())
-        kw = dict(scenarios=scenarios, disturbances=disturbances, seeds=seeds, amp=amp, period_s=period_s)
+        kw = dict(scenarios=scenarios, disturbances=disturbances, seeds=seeds, amp=amp, period_s=period_s, base_law=self.residual)
         mapped = lambda r, f: evaluator.DisturbedResults(r.scenarios, r.disturbances, r.seeds, r.T, f(r.scores), f(r.counters),
                                                          {k: f(v) for k, v in r.metrics.items()})
         if self.seeds is not None:
@@ -920,13 +978,14 @@ class VecTrainer:
         seeds = [int(self.conf.evaluation_seed)] if seeds is None else [int(k) for k in seeds]
         ag, M, E = self.agents, self.M, self.E
         if self.seeds is not None and self.shared:
-            batch = evaluator.prepare_many(self.conf, ag, list(range(E)), set_mod=M, seeds=seeds, set_bases=[e * M for e in range(E)])
+            batch = evaluator.prepare_many(self.conf, ag, list(range(E)), set_mod=M, seeds=seeds, set_bases=[e * M for e in range(E)], base_law=self.residual)
         elif self.seeds is not None:
-            batch = evaluator.prepare_many(self.conf, ag, [vec.batch_platoon(e, p, E) for e in range(E) for p in range(self.P_exp)], seeds=seeds)
+            batch = evaluator.prepare_many(self.conf, ag, [vec.batch_platoon(e, p, E) for e in range(E) for p in range(self.P_exp)], seeds=seeds,
+                                           base_law=self.residual)
         elif self.shared:
-            batch = evaluator.prepare_many(self.conf, ag, [0], set_mod=M, seeds=seeds)
+            batch = evaluator.prepare_many(self.conf, ag, [0], set_mod=M, seeds=seeds, base_law=self.residual)
         else:
-            batch = evaluator.prepare_many(self.conf, ag, list(range(self.P)), seeds=seeds)
+            batch = evaluator.prepare_many(self.conf, ag, list(range(self.P)), seeds=seeds, base_law=self.residual)
         NS = batch.NS
         d_base = batch.set_base[::NS].contiguous()  # a rollout's base is its unit's: rollout u * NS + k
         h = [int(b) for b in d_base.cpu().tolist()]

@@ -743,6 +743,46 @@ int avd_step_fused_dist_lead_seeds_f32(const avd_env_consts* d_consts, int P, in
     link_hist, float* link_recv, uint64_t obs_counter, int n_manoeuvres, int T, const float* d_table, const float* d_noise, const
     uint8_t* d_gaussian, const int32_t* ep_len, int ep_step, void* stream);
 
+/* ---- a residual policy on a static linear law: the fused step and the evaluators with the law in front of the plant ------------------
+ * The agent's action r is a correction to a per-vehicle linear law. With ob what the agent observes of the pre-step state, (kp, kv,
+ * ka, kf) = d_gains[vehicle] (DEVICE memory, [L][4] float32, 16-byte aligned; its values are the caller's to check) and scale in (0, 1]
+ * the residual's authority, the plant receives, in float32 without contraction and in this order,
+ *   z = (kp*ob.x + kv*ob.y) + ka*ob.z;   z = z + kf*ob.w (Model B only);   u = fminf(fmaxf(z + scale*r, action_low), action_high)
+ * -- avd_eval_linear_f32's law plus scale * r. u drives the plant, the reward's norm_u term and the value chained to the follower; the
+ * learners keep seeing r. Zero gains and scale = 1 give u = clip(r): every output is then the twin entry point's.
+ *
+ * avd_step_fused_res_f32: ONE entry point for avd_step_fused_f32 and its seed-batch, disturbed and manoeuvre twins. d_seeds NULL: the
+ * scalar seed keys the draws (n_groups unread); otherwise the table of n_groups seeds does, as in the *_seeds_* twins (seed unread).
+ * n_levels = 0: no disturbance levels (the level arguments unread, ob = x_in); otherwise avd_step_fused_dist_f32's arguments, and ob =
+ * obs_in, the observation the replay row stores. n_manoeuvres = 0: the nominal leader input; otherwise avd_step_fused_lead_f32's
+ * arguments (the level count the assignment divides by is n_levels, 1 without levels). r = clip(actor_out + OU noise), as in every
+ * twin: action[] and the replay row [s, r, reward, s'] hold r; applied [P*L] (or NULL) receives u. Refused on the host, before any
+ * launch: what the twins refuse, null or misaligned d_gains, a misaligned obs_in, scale outside (0, 1], negative counts.
+ *
+ * avd_eval_rollout_res_f32 / avd_eval_cases_res_f32: avd_eval_rollout_f32 / avd_eval_cases_dist_f32 with r = clip(tanh(.) * high) and
+ * ob the vehicle's state (disturbed cases: its observation); the action trace, the reward and sum_u2 take u. The cases form serves both
+ * kinds of run: all five disturbance tables NULL is the nominal evaluator (avd_eval_cases_f32's block sizes), otherwise only abc may be
+ * NULL (avd_eval_cases_dist_f32's). Actors whose output is zero give avd_eval_linear_f32's counters and metrics for the same gains.
+ * Decentralized agents only: M != L is AVD_E_UNSUPPORTED. */
+int avd_step_fused_res_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out, float* prev_a,
+    float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done, int32_t* any_done_other, const float*
+    actor_out, float* ou_state, float* action, float* leader_exog, float ou_theta, float ou_mean, float ou_dt, float ou_std_dev,
+    float action_low, float action_high, float exog_scale, int exog_uniform, uint64_t seed, uint64_t ou_counter, uint64_t
+    exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward, const uint64_t* d_seeds, int n_groups, int n_levels,
+    const avd_train_level* h_levels, const avd_train_level* d_levels, const float* d_plant, const float* obs_in, float* obs_out,
+    float* link_hist, float* link_recv, uint64_t obs_counter, int n_manoeuvres, int T, const float* d_table, const float* d_noise,
+    const uint8_t* d_gaussian, const int32_t* ep_len, int ep_step, const float* d_gains, float scale, float* applied, void* stream);
+int avd_eval_rollout_res_f32(const avd_mlp_layout* lay, const avd_env_consts* d_consts, int R, int L, int M, int T, const float* theta,
+                             const float* stats, int n_sets, const int32_t* set_base, const float* x0, const float* prev_a0,
+                             const float* leader, int n_start, const int32_t* start_idx, float high, float lo, float hi,
+                             float sample_rate, float* counters, int n_trace, const int32_t* trace_idx, float* tr_states,
+                             float* tr_actions, float* tr_jerks, const float* d_gains, float scale, void* stream);
+int avd_eval_cases_res_f32(const avd_mlp_layout* lay, const avd_env_consts* d_consts, int G, int K, int L, int M, int T,
+                           const float* theta, const float* stats, int n_sets, const int32_t* set_base, const float* x0,
+                           const float* prev_a0, const float* leader, float high, float lo, float hi, float sample_rate,
+                           const float* sigma, const int32_t* delay, const uint32_t* drop_q, const uint64_t* noise_seed,
+                           const float* abc, const float* d_gains, float scale, float* counters, float* metrics, void* stream);
+
 /* D[M][Nc] (f32, ldd) = A[M][K] . B[Nc][K]^T with bf16 operands (K contiguous, K % 64 == 0) and f32 accumulation: the
  * GEMM under avd_learn_shared_bf16, exposed for parity tests. A and B must be readable up to the next multiple of 256
  * rows. */
