@@ -107,6 +107,14 @@ def _scenario_flags(p, where):
                         "searched on the device (one rollout launch over grid x cases, one fitness launch), then evaluated like any "
                         "--baseline law. GRID: key=lo:hi:n per gain (np.linspace; a missing key is 0), at most 65536 candidates, e.g. "
                         "kp=0:2:9,kv=0:4:9,ka=-0.5:0:3 (not in the reference CLI)")
+    p.add_argument("--baseline_search", type=str, default=argparse.SUPPRESS, metavar="SPEC",
+                   help="--scenarios: add the law `searched`: the best gain table of a cross-entropy search that stays on the device (per "
+                        "generation: sample, roll out, fitness, refit; nothing is read back until the last), one gain row per vehicle "
+                        "(per_vehicle=0: one row for all), then evaluated like any --baseline law. SPEC: key=lo:hi per gain (a missing key "
+                        "is frozen at 0, a single value frozen there) and pop (2..65536), gens, elite (a fraction <= 0.5), alpha, min_std, "
+                        "seed, per_vehicle, over (nominal: the fitness is over the undisturbed cases; all: over the --disturb levels "
+                        "too), e.g. kp=0:3,kv=0:4,ka=-1:0,kf=0:1,pop=1024,gens=30. With --baseline_tune the search starts from the "
+                        "grid's pick (not in the reference CLI)")
 
 
 def _check_scenario_flags(ap, args):
@@ -116,7 +124,7 @@ def _check_scenario_flags(ap, args):
     from .scenarios import check_names
 
     if args.scenarios is None:
-        for flag in ("eval_seeds", "scenario_amp", "scenario_period", "disturb", "baseline", "baseline_tune"):
+        for flag in ("eval_seeds", "scenario_amp", "scenario_period", "disturb", "baseline", "baseline_tune", "baseline_search"):
             if getattr(args, flag, None) is not None:
                 ap.error(f"--{flag} needs --scenarios")
         return
@@ -140,13 +148,24 @@ def _check_scenario_flags(ap, args):
             args.disturb = check_disturbances([parse_disturbance(d) for d in args.disturb])
         except ValueError as e:
             ap.error(f"--disturb: {e}")
-    if getattr(args, "baseline", None) is not None or getattr(args, "baseline_tune", None) is not None:
+    if any(getattr(args, f, None) is not None for f in ("baseline", "baseline_tune", "baseline_search")):
         from . import scenarios as _sc
 
+        search = getattr(args, "baseline_search", None)
         try:  # (what needs the run's configuration -- Model A, the centralized framework -- is checked once it is known)
-            args.baseline = _sc.check_baselines([_sc.parse_baseline(b) for b in getattr(args, "baseline", None) or []])
+            args.baseline = _sc.check_baselines([_sc.parse_baseline(b) for b in getattr(args, "baseline", None) or []],
+                                                reserved=(_sc.TUNED,) if search is None else (_sc.TUNED, _sc.SEARCHED))
         except ValueError as e:
             ap.error(f"--baseline: {e}")
+        if search is not None:
+            extra = 1 + (getattr(args, "baseline_tune", None) is not None)
+            if len(args.baseline) + extra > _sc.MAX_BASELINES:
+                also = " and --baseline_tune's `tuned`" if extra == 2 else ""
+                ap.error(f"--baseline: {len(args.baseline)} laws beside --baseline_search's `searched`{also}: at most {_sc.MAX_BASELINES} in all")
+            try:
+                args.baseline_search = _sc.check_search(_sc.parse_search(search))
+            except ValueError as e:
+                ap.error(f"--baseline_search: {e}")
         if getattr(args, "baseline_tune", None) is not None:
             if len(args.baseline) + 1 > _sc.MAX_BASELINES:
                 ap.error(f"--baseline: {len(args.baseline)} laws beside --baseline_tune's `tuned`: at most {_sc.MAX_BASELINES} in all")
@@ -169,9 +188,15 @@ def _exit(msg):
 
 
 def _baseline_flags(args):
-    """(the --baseline laws, --baseline_tune's (text, grid) or None), or None without either flag."""
+    """(the --baseline laws, --baseline_tune's (text, grid) or None), or None without any of --baseline, --baseline_tune and
+    --baseline_search (whose SearchSpace _search_flag returns)."""
     laws, tune = getattr(args, "baseline", None), getattr(args, "baseline_tune", None)
-    return None if laws is None and tune is None else (list(laws or []), tune)
+    return None if laws is None and tune is None and _search_flag(args) is None else (list(laws or []), tune)
+
+
+def _search_flag(args):
+    """--baseline_search's checked SearchSpace, or None without the flag."""
+    return getattr(args, "baseline_search", None)
 
 
 def _check_baseline_conf(args, conf, refuse):
@@ -188,6 +213,11 @@ def _check_baseline_conf(args, conf, refuse):
             raise ValueError("a grid over kf needs Model B (Model A observes no communicated state)")
     except ValueError as e:
         refuse(f"--baseline: {e}")
+    if _search_flag(args) is not None:
+        try:
+            _sc.check_search(_search_flag(args), conf)
+        except ValueError as e:
+            refuse(f"--baseline_search: {e}")
 
 
 class _Baselines:
@@ -198,8 +228,10 @@ class _Baselines:
         from . import evaluator
         from . import scenarios as _sc
 
+        import numpy as np
+
         laws, tune = _baseline_flags(args)
-        self.tune = None
+        self.tune = self.search = self.found = None
         try:
             if tune is not None:  # the search runs over the nominal cases only
                 text, grid = tune
@@ -208,6 +240,13 @@ class _Baselines:
                 laws = laws + [_sc.LinearLaw(_sc.TUNED, *gains)]
                 self.tune = [["grid", text], ["candidates", int(grid.shape[0])], ["best_index", int(best)],
                              ["gains", [[k, v] for k, v in zip(_sc.GAIN_KEYS, gains)]], ["fitness", float(fit[best])]]
+            space = _search_flag(args)
+            if space is not None:  # from the grid's pick when there is one: candidate 0 of generation 0 is then that law
+                if tune is not None:
+                    space = _sc.check_search(space.with_init(np.asarray(grid[best], dtype=np.float32)[None, :]), conf)
+                self.found = evaluator.search_linear(conf, space, disturbances=_disturb(args) or (), **_suite(args))
+                laws = laws + [self.found.law]
+                self.search = self.found.record(space.text)
             self.laws = laws
             self.results = evaluator.run_linear(conf, laws, disturbances=_disturb(args) or (), **_suite(args))
         except ValueError as e:
@@ -221,11 +260,18 @@ class _Baselines:
         conf.baseline_suite = [[b.name, b.items()] for b in self.laws]
         if self.tune is not None:
             conf.baseline_tune = self.tune
+        if self.search is not None:
+            conf.baseline_search = self.search
 
     def report(self):
         from . import scenarios as _sc
 
-        return _sc.baseline_report_lines(self.results, self.names)
+        lines = _sc.baseline_report_lines(self.results, self.names)
+        if self.found is not None:
+            f = self.found
+            lines.append(f"baseline {_sc.SEARCHED} search: fitness {f.fitness:.6f} at generation {f.generation} of {f.gens} "
+                         f"(pop {f.pop}, {f.n_elite} elites, {f.K} cases, {f.best_gains.shape[0]} searched row(s))")
+        return lines
 
 
 def _record_train_levels(conf, args):
@@ -275,6 +321,9 @@ def _resolve_residual(args, conf, auto_reset, hparams=None):
         if law == _sc.TUNED:
             args.baselines = _Baselines(conf, args)
             args.residual = law = _sc.ResidualLaw(*[v for _, v in dict(args.baselines.tune)["gains"]], source="tuned")
+        elif law == _sc.SEARCHED:
+            args.baselines = _Baselines(conf, args)
+            args.residual = law = _sc.ResidualLaw(table=args.baselines.found.law.table, source="searched")
         trainer.check_residual(conf, law, args.rng, int(os.environ.get("WORLD_SIZE", "1") or 1), hparams=hparams)
     except ValueError as e:
         raise SystemExit(f"--residual: {e}")
@@ -572,12 +621,14 @@ def get_cmdl_args(argv, conf):
             ap.error("--residual is not available under a process group of more than one rank")
         try:  # (what needs the run's configuration: trainer.check_residual applies it)
             args.residual = _sc.parse_residual(args.residual)
-            if args.residual != _sc.TUNED:
+            if args.residual not in (_sc.TUNED, _sc.SEARCHED):
                 _sc.check_residual(args.residual)
         except ValueError as e:
             ap.error(f"--residual: {e}")
         if args.residual == _sc.TUNED and (args.scenarios is None or getattr(args, "baseline_tune", None) is None):
             ap.error("--residual tuned needs --scenarios and --baseline_tune (the grid the law is searched on)")
+        if args.residual == _sc.SEARCHED and (args.scenarios is None or getattr(args, "baseline_search", None) is None):
+            ap.error("--residual searched needs --scenarios and --baseline_search (the space the law is searched in)")
     if getattr(args, "pbt", None) is not None or getattr(args, "pbt_fraction", None) is not None or getattr(args, "pbt_perturb", None) is not None:
         if args.pbt is None:
             ap.error("--pbt_fraction / --pbt_perturb need --pbt")

@@ -165,6 +165,8 @@ _PROTOS = {
                                _P, _P],
     "avd_eval_linear_f32": [_P, _i, _i, _i, _i, _P, _P, _P, _P, _f, _f, _f, _P, _P, _P, _P, _P, _P, _P, _P],
     "avd_linear_fitness_f32": [_i, _i, _i, _P, _P, _P],
+    "avd_search_sample_f32": [_i, _i, _i, _P, _P, _P, _P, _u64, _u64, _P, _P],
+    "avd_search_refit_f32": [_i, _i, _i, _i, _f, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _P],
     "avd_gemm_bt_bf16": [_i, _i, _i, _P, C.c_long, _P, C.c_long, _P, C.c_long, _P],
 }
 

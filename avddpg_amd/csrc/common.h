@@ -121,6 +121,7 @@ enum PhiloxStream : uint32_t {
     STREAM_EVAL_LINK = 7,  // disturbed scenario evaluator: V2V loss, word x
     STREAM_TRAIN_OBS = 8,   // training under disturbances: sensor noise, (counter, index) = (observation counter, vehicle)
     STREAM_TRAIN_LINK = 9,  // training under disturbances: V2V loss, word x
+    STREAM_SEARCH = 10,     // gain search: a candidate row's four normals, (counter, index) = (generation, candidate * R + row)
 };
 
 }  // namespace avd

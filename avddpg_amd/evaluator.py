@@ -1,6 +1,8 @@
 """Evaluator rollout over the HIP kernels: the compute part of reference ``workers/evaluator.py:16-158``
 (deterministic-start, noise-free rollout of trained actors; returns the mean episodic reward rounded to 3
 digits, :145, :158). Figures / LaTeX are out of scope of the hot path; the traces they were drawn from are returned."""
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -508,11 +510,17 @@ class LinearBatch:
              ptr(self.leader), c.action_low, c.action_high, c.sample_rate, ptr(self.sigma), ptr(self.delay), ptr(self.drop_q),
              ptr(self.noise_seed), ptr(self.abc), ptr(self.counters), ptr(self.metrics), stream_handle())
 
+    def enqueue_fitness(self, out=None):
+        """One avd_linear_fitness_f32 launch over the counters of ``launch()`` on the current stream, into ``out`` (float32 [G] on the
+        device; allocated when None). Nothing is read back."""
+        if out is None:
+            out = torch.empty(self.G, dtype=torch.float32, device=self.counters.device)
+        call("avd_linear_fitness_f32", self.G, self.K, self.L, ptr(self.counters), ptr(out), stream_handle())
+        return out
+
     def fitness(self):
         """One avd_linear_fitness_f32 launch over the counters of ``launch()``: float32 [G] on the host (the only read-back)."""
-        out = torch.empty(self.G, dtype=torch.float32, device=self.counters.device)
-        call("avd_linear_fitness_f32", self.G, self.K, self.L, ptr(self.counters), ptr(out), stream_handle())
-        return out.cpu().numpy()
+        return self.enqueue_fitness().cpu().numpy()
 
     def results(self):
         from . import scenarios as _sc
@@ -573,3 +581,78 @@ def tune_linear(conf, grid, scenarios=("gaussian",), disturbances=(), seeds=None
     b.launch()
     fit = b.fitness()
     return _sc.first_argmax(fit), fit
+
+
+class SearchResult:
+    """What search_linear returns: ``law`` the best-ever table as a scenarios.LinearLaw (a tied search's row repeated over the vehicles),
+    ``fitness`` and ``generation`` of that table, ``history`` float32 [gens, 4] (per generation: the best fitness, the elites' mean
+    fitness, the best-ever fitness so far, the number of valid elites), the final ``mean`` / ``std`` float32 [R, 4], ``best_gains``
+    float32 [R, 4], the counts ``pop``, ``gens``, ``n_elite``, ``K`` (cases per candidate) and ``trace`` (None, or with trace=True a dict
+    of per-generation arrays: gains [gens, G, L, 4], fitness [gens, G], elite_idx [gens, n_elite], mean / std [gens, R, 4] BEFORE the
+    generation's refit)."""
+
+    def __init__(self, law, fitness, generation, history, mean, std, best_gains, pop, gens, n_elite, K, trace):
+        self.law, self.fitness, self.generation, self.history = law, float(fitness), int(generation), history
+        self.mean, self.std, self.best_gains, self.trace = mean, std, best_gains, trace
+        self.pop, self.gens, self.n_elite, self.K = int(pop), int(gens), int(n_elite), int(K)
+
+    def record(self, text=None):
+        """conf.json's baseline_search entry, a list of pairs (conf.json keeps lists, not dicts)."""
+        return [["spec", text], ["pop", self.pop], ["gens", self.gens], ["n_elite", self.n_elite], ["cases", self.K],
+                ["table", np.asarray(self.law.table, dtype=np.float64).tolist()], ["fitness", self.fitness], ["generation", self.generation],
+                ["history", np.asarray(self.history, dtype=np.float64).tolist()]]
+
+
+def search_linear(conf, space, scenarios=("gaussian",), disturbances=(), seeds=None, amp=None, period_s=10.0, manual_timestep_override=None,
+                  trace=False, name=None):
+    """A cross-entropy search over gain tables, resident on the device: ``space`` (scenarios.SearchSpace) gives the bounds per gain, the
+    population, the generations and whether every vehicle has its own row (R = L searched rows) or all share one (R = 1). ONE
+    LinearBatch of ``pop`` gain sets without metrics is built; per generation four launches are enqueued on the current stream --
+    avd_search_sample_f32 writes the batch's gains (candidate 0 is the current mean), avd_eval_linear_f32 rolls them out,
+    avd_linear_fitness_f32 reduces the counters, avd_search_refit_f32 ranks the candidates, refits mean and std to the elites and keeps
+    the best-ever table -- with the generation number passed by value, and nothing is read back until the last generation is enqueued.
+    The fitness is tune_linear's: a candidate's mean counter over the suite's undisturbed cases (``space.over == "nominal"``) or over
+    scenarios x [nominal, *disturbances] x seeds (``"all"``). -> a SearchResult; with ``trace`` every generation's candidates, fitness,
+    elites and pre-refit distribution are kept (device-to-device copies into slabs, read back at the end)."""
+    from . import scenarios as _sc
+
+    space = _sc.check_search(space, conf)
+    L, G, gens, n_elite = conf.pl_size, int(space.pop), int(space.gens), space.n_elite()
+    R = space.rows(L)
+    lo_h, hi_h, mean_h, std_h, min_h = space.tables(L)
+    levels = list(disturbances) if space.over == "all" else []
+    b = LinearBatch(conf, np.zeros((G, L, 4), dtype=np.float32), scenarios, levels, seeds, amp, period_s, manual_timestep_override,
+                    metrics=False)
+    dev = b.counters.device
+    up = lambda x: torch.from_numpy(x).to(dev)
+    lo, hi, mean, std, min_std = up(lo_h), up(hi_h), up(mean_h), up(std_h), up(min_h)
+    f32 = dict(dtype=torch.float32, device=dev)
+    best_gains, best_fit = torch.zeros(R, 4, **f32), torch.full((1,), -np.inf, **f32)
+    best_gen = torch.full((1,), -1, dtype=torch.int32, device=dev)
+    fit, history = torch.empty(G, **f32), torch.zeros(gens, 4, **f32)
+    elite = torch.zeros(gens if trace else 1, n_elite, dtype=torch.int32, device=dev)
+    slab = None
+    if trace:
+        slab = dict(gains=torch.empty(gens, G, L, 4, **f32), fitness=torch.empty(gens, G, **f32), mean=torch.empty(gens, R, 4, **f32),
+                    std=torch.empty(gens, R, 4, **f32))
+    seed = int(conf.evaluation_seed if space.seed is None else space.seed)
+    row = lambda t, i: C.c_void_p(t.data_ptr() + i * t.stride(0) * t.element_size())
+    for gen in range(gens):
+        call("avd_search_sample_f32", G, L, R, ptr(mean), ptr(std), ptr(lo), ptr(hi), seed, gen, ptr(b.gains), stream_handle())
+        b.launch()
+        b.enqueue_fitness(fit)
+        if trace:
+            slab["gains"][gen].copy_(b.gains), slab["fitness"][gen].copy_(fit), slab["mean"][gen].copy_(mean), slab["std"][gen].copy_(std)
+        call("avd_search_refit_f32", G, L, R, n_elite, float(space.alpha), ptr(b.gains), ptr(fit), ptr(min_std), ptr(mean), ptr(std),
+             ptr(best_gains), ptr(best_fit), ptr(best_gen), gen, row(elite, gen if trace else 0), row(history, gen), stream_handle())
+    at = int(best_gen.cpu()[0])
+    if at < 0:
+        raise ValueError("search: no candidate of any generation had a finite fitness")
+    bg = best_gains.cpu().numpy()
+    table = np.ascontiguousarray(np.repeat(bg, L, axis=0) if R == 1 else bg)
+    tr = None
+    if trace:
+        tr = {k: v.cpu().numpy() for k, v in slab.items()}
+        tr["elite_idx"] = elite.cpu().numpy()
+    return SearchResult(_sc.LinearLaw(_sc.SEARCHED if name is None else name, table=table), best_fit.cpu().numpy()[0], at,
+                        history.cpu().numpy(), mean.cpu().numpy(), std.cpu().numpy(), bg, G, gens, n_elite, b.K, tr)

@@ -328,7 +328,8 @@ def check_baselines(laws, conf=None, reserved=(TUNED,)):
         if not isinstance(b, LinearLaw):
             raise ValueError(f"{b!r} is not a scenarios.LinearLaw")
         if b.name in reserved:
-            raise ValueError(f"the baseline name {b.name!r} is reserved for the law --baseline_tune picks")
+            flag = "--baseline_search finds" if b.name == "searched" else "--baseline_tune picks"
+            raise ValueError(f"the baseline name {b.name!r} is reserved for the law {flag}")
         for k in GAIN_KEYS:
             v = getattr(b, k)
             if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
@@ -394,6 +395,8 @@ def parse_residual(text):
     text = str(text).strip()
     if text == TUNED:
         return TUNED
+    if text == SEARCHED:
+        return SEARCHED
     keys = GAIN_KEYS + ("scale",)
     kw = {}
     parts = [q.strip() for q in text.split(",") if q.strip()]
@@ -489,6 +492,151 @@ def fitness_of(counters):
             s = np.float32(s + x)
         out[g] = s / np.float32(c.shape[1])
     return out
+
+
+# ---- gain search: a cross-entropy search over gain tables (evaluator.search_linear; avd_search_sample_f32, avd_search_refit_f32) -----
+
+SEARCHED = "searched"  # the name --baseline_search gives the search's best law
+MAX_POP, MAX_GENS = 65536, 10000
+SEARCH_OVER = ("nominal", "all")
+SEARCH_KEYS = GAIN_KEYS + ("pop", "gens", "elite", "alpha", "min_std", "seed", "per_vehicle", "over")
+
+
+class SearchSpace:
+    """What evaluator.search_linear searches: ``bounds`` {key of GAIN_KEYS: (lo, hi)} -- a missing key is frozen at 0, lo == hi frozen at
+    that value -- and the search's knobs: ``pop`` candidates per generation, ``gens`` generations, ``elite`` the fraction refitted to
+    (floor(elite * pop) candidates), ``alpha`` the refit's step, ``min_std`` the floor of a dimension's standard deviation as a fraction
+    of hi - lo, ``seed`` (None: the Config's evaluation_seed), ``per_vehicle`` (one gain row per vehicle; False: one row for all),
+    ``over`` ("nominal": the fitness is over the undisturbed cases; "all": over the disturbance levels too) and ``init``, an optional
+    [L or 1][4] start mean (default: the midpoint of the bounds). The start std is (hi - lo) / 2."""
+
+    def __init__(self, bounds, pop=1024, gens=30, elite=0.125, alpha=0.7, min_std=0.01, seed=None, per_vehicle=True, over="nominal",
+                 init=None, text=None):
+        self.bounds = {k: (v if isinstance(v, (tuple, list)) else (v, v)) for k, v in dict(bounds).items()}
+        self.pop, self.gens, self.elite, self.alpha, self.min_std = pop, gens, elite, alpha, min_std
+        self.seed, self.per_vehicle, self.over, self.text = seed, per_vehicle, over, text
+        self.init = None if init is None else np.asarray(init)
+
+    def n_elite(self):
+        return int(math.floor(self.elite * self.pop))
+
+    def rows(self, L):
+        """R: the searched rows of a platoon of L."""
+        return int(L) if self.per_vehicle else 1
+
+    def tables(self, L):
+        """float32 [R, 4] each: (lo, hi, mean, std, min_std) of a checked space, formed in float64 and rounded once."""
+        R = self.rows(L)
+        lo = np.array([self.bounds.get(k, (0.0, 0.0))[0] for k in GAIN_KEYS], dtype=np.float64)
+        hi = np.array([self.bounds.get(k, (0.0, 0.0))[1] for k in GAIN_KEYS], dtype=np.float64)
+        mean = np.tile((lo + hi) / 2, (R, 1))
+        if self.init is not None:
+            init = np.asarray(self.init, dtype=np.float64)
+            mean = np.tile(init, (R, 1)) if init.shape[0] == 1 else init.copy()
+            if mean.shape != (R, 4):
+                raise ValueError(f"search: init of shape {init.shape} for {R} searched row(s) (need [{R}, 4] or [1, 4])")
+        f = lambda x: np.ascontiguousarray(np.tile(x, (R, 1)).astype(np.float32))
+        return f(lo), f(hi), np.ascontiguousarray(mean.astype(np.float32)), f((hi - lo) / 2), f(float(self.min_std) * (hi - lo))
+
+    def with_init(self, init):
+        """The same space starting from ``init`` ([L or 1][4])."""
+        return SearchSpace(self.bounds, self.pop, self.gens, self.elite, self.alpha, self.min_std, self.seed, self.per_vehicle, self.over,
+                           init, self.text)
+
+    def __repr__(self):
+        return (f"SearchSpace({self.bounds!r}, pop={self.pop!r}, gens={self.gens!r}, elite={self.elite!r}, alpha={self.alpha!r}, "
+                f"min_std={self.min_std!r}, seed={self.seed!r}, per_vehicle={self.per_vehicle!r}, over={self.over!r})")
+
+
+def parse_search(text):
+    """``kp=0:3,kv=0:4,ka=-1:0,kf=0:1,pop=1024,gens=30,elite=0.125,alpha=0.7,min_std=0.01,seed=6,per_vehicle=1,over=nominal`` ->
+    SearchSpace: a gain key takes ``lo:hi`` (or a single value: frozen there), the other keys of SEARCH_KEYS one value. An unknown key, a
+    key given twice, a value that is no number or an empty text is a ValueError; the values are checked by check_search."""
+    parts = [q.strip() for q in str(text).split(",") if q.strip()]
+    if not parts:
+        raise ValueError(f"search {text!r}: no bound given (kp=lo:hi,...[,pop=..,gens=..,elite=..])")
+    bounds, kw = {}, {}
+    for part in parts:
+        key, eq, val = part.partition("=")
+        key, val = key.strip(), val.strip()
+        if not eq or key not in SEARCH_KEYS:
+            raise ValueError(f"search: unknown key {key!r} (one of {', '.join(SEARCH_KEYS)}, as key=value)")
+        if key in bounds or key in kw:
+            raise ValueError(f"search: {key} given twice")
+        try:
+            if key in GAIN_KEYS:
+                f = [float(x) for x in val.split(":")]
+                if len(f) not in (1, 2):
+                    raise ValueError
+                bounds[key] = (f[0], f[-1])
+            elif key in ("pop", "gens", "seed"):
+                kw[key] = int(val)
+            elif key == "per_vehicle":
+                if val.lower() not in ("0", "1", "true", "false"):
+                    raise ValueError
+                kw[key] = val.lower() in ("1", "true")
+            elif key == "over":
+                kw[key] = val
+            else:
+                kw[key] = float(val)
+        except ValueError:
+            what = "lo:hi (two numbers) or a single number" if key in GAIN_KEYS else \
+                "an integer" if key in ("pop", "gens", "seed") else "0 or 1" if key == "per_vehicle" else "a number"
+            raise ValueError(f"search: {key}={val!r} is not {what}") from None
+    return SearchSpace(bounds, text=str(text).strip(), **kw)
+
+
+def check_search(space, conf=None):
+    """The space, checked. A ValueError for: not a SearchSpace; an unknown gain key; a non-finite bound; lo > hi; pop outside [2,
+    MAX_POP]; gens outside [1, MAX_GENS]; elite > 0.5 or floor(elite * pop) < 2; alpha outside (0, 1]; a negative min_std; an unknown
+    ``over``; a negative seed; no searched dimension at all; an init that is not finite [*, 4] or lies outside the bounds; with ``conf``,
+    a non-zero kf bound under Model A, the centralized framework and an init whose row count is neither 1 nor the searched rows."""
+    if not isinstance(space, SearchSpace):
+        raise ValueError(f"{space!r} is not a scenarios.SearchSpace")
+    num = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
+    whole = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer))
+    bad = sorted(k for k in space.bounds if k not in GAIN_KEYS)
+    if bad:
+        raise ValueError(f"search: unknown gain key(s) {bad} (one of {', '.join(GAIN_KEYS)})")
+    for k, (lo, hi) in space.bounds.items():
+        if not (num(lo) and num(hi) and math.isfinite(lo) and math.isfinite(hi)):
+            raise ValueError(f"search: {k}={lo!r}:{hi!r} has a non-finite bound")
+        if lo > hi:
+            raise ValueError(f"search: {k} has lo={lo!r} > hi={hi!r}")
+    if not whole(space.pop) or not 2 <= space.pop <= MAX_POP:
+        raise ValueError(f"search: pop={space.pop!r} must be an integer in [2, {MAX_POP}]")
+    if not whole(space.gens) or not 1 <= space.gens <= MAX_GENS:
+        raise ValueError(f"search: gens={space.gens!r} must be an integer in [1, {MAX_GENS}]")
+    if not num(space.elite) or not space.elite <= 0.5 or space.n_elite() < 2:
+        raise ValueError(f"search: elite={space.elite!r} with pop={space.pop} (need elite <= 0.5 and floor(elite * pop) >= 2)")
+    if not num(space.alpha) or not 0 < space.alpha <= 1:
+        raise ValueError(f"search: alpha={space.alpha!r} must be a number in (0, 1]")
+    if not num(space.min_std) or not (space.min_std >= 0 and math.isfinite(space.min_std)):
+        raise ValueError(f"search: min_std={space.min_std!r} must be a finite number >= 0")
+    if space.over not in SEARCH_OVER:
+        raise ValueError(f"search: over={space.over!r} (one of {', '.join(SEARCH_OVER)})")
+    if space.seed is not None and (not whole(space.seed) or not 0 <= space.seed < 2 ** 64):
+        raise ValueError(f"search: seed={space.seed!r} must be an integer in [0, 2^64)")
+    if not any(lo < hi for lo, hi in space.bounds.values()):
+        raise ValueError("search: no searched dimension (every gain is frozen: give at least one key lo:hi with lo < hi)")
+    lo = np.array([space.bounds.get(k, (0.0, 0.0))[0] for k in GAIN_KEYS], dtype=np.float64)
+    hi = np.array([space.bounds.get(k, (0.0, 0.0))[1] for k in GAIN_KEYS], dtype=np.float64)
+    if space.init is not None:
+        t = np.asarray(space.init)
+        if t.ndim != 2 or t.shape[1] != 4 or t.shape[0] < 1 or not np.issubdtype(t.dtype, np.number) or not np.isfinite(t).all():
+            raise ValueError(f"search: init must be a finite [L or 1, 4] array (got shape {t.shape})")
+        t32 = t.astype(np.float32)  # (as the device sees them: a float32 grid value on a bound stays on it)
+        if np.any(t32 < lo.astype(np.float32)) or np.any(t32 > hi.astype(np.float32)):
+            raise ValueError(f"search: init {t.tolist()} lies outside the bounds lo={lo.tolist()} hi={hi.tolist()}")
+    if conf is not None:
+        if conf.framework == conf.cntrl:
+            raise ValueError("a linear baseline is a per-vehicle law: not available for the centralized framework")
+        if conf.model == conf.modelA and (lo[3] != 0 or hi[3] != 0):
+            raise ValueError("a search over kf needs Model B (Model A observes no communicated state)")
+        if space.init is not None and space.init.shape[0] not in (1, space.rows(conf.pl_size)):
+            raise ValueError(f"search: init of {space.init.shape[0]} rows for {space.rows(conf.pl_size)} searched row(s) "
+                             f"(pl_size={conf.pl_size}, per_vehicle={bool(space.per_vehicle)})")
+    return space
 
 
 # ---- training manoeuvres: what the fused step's leader follows during training (avd_step_fused_lead_f32) -----------------------------

@@ -642,6 +642,38 @@ int avd_eval_linear_f32(const avd_env_consts* d_consts, int G, int K, int L, int
  * bit-identical to the same loop in NumPy float32. */
 int avd_linear_fitness_f32(int G, int K, int L, const float* counters, float* fitness, void* stream);
 
+/* ---- gain search: a cross-entropy search over gain tables around the two launches above (csrc/search.hip) -----------------------
+ * A generation is avd_search_sample_f32 -> avd_eval_linear_f32 -> avd_linear_fitness_f32 -> avd_search_refit_f32 on one stream;
+ * nothing comes back to the host between generations. R searched rows: R = L (one gain row per vehicle) or R = 1 (tied: every vehicle
+ * takes row 0). mean, std, lo, hi, min_std, best_gains are [R][4] in DEVICE memory, dimension d = r * 4 + c. All arithmetic is float32
+ * without contraction, in the order written here.
+ *
+ * avd_search_sample_f32: gains [G][L][4] (out), one thread per (candidate g, vehicle v), r = (R == 1 ? 0 : v):
+ *   w = philox(seed, generation, g * R + r, stream 10); (n0, n1) = box_muller(w.x, w.y) (cos, sin), (n2, n3) = box_muller(w.z, w.w);
+ *   x = mean[r][c] when g == 0 or std[r][c] == 0 (the add is skipped: exact), else mean[r][c] + std[r][c] * n_c;
+ *   gains[g][v][c] = fminf(fmaxf(x, lo[r][c]), hi[r][c]).
+ * Candidate 0 of every generation is the current mean. AVD_E_INVALID: a null pointer, G < 1, L outside 1 .. AVD_MAX_L, R not 1 or L.
+ *
+ * avd_search_refit_f32: two kernels. Rank: candidate i precedes j iff fitness[i] is not NaN and (fitness[j] is NaN or f_i > f_j or
+ * (f_i == f_j and i < j)); among NaNs the lower index precedes. A candidate's rank is the number of candidates that precede it (a
+ * permutation); elite_idx[rank] = i for rank < n_elite (int32 [n_elite], out: NaN candidates fill the places past the valid ones).
+ * Refit, one wave, lane d: E = min(n_elite, the number of non-NaN fitnesses). E == 0: mean, std and best_* stay untouched,
+ * history_row = {NaN, NaN, best_fitness, 0}. Otherwise, with x_k = gains[elite_idx[k]][r][c], k = 0 .. E - 1 in rank order:
+ *   s = 0; for k: s = s + x_k;               m  = s / (float)E
+ *   q = 0; for k: t = x_k - m; q = q + t * t;  sd = sqrtf(q / (float)E)
+ *   if (std[d] != 0) { mean[d] = mean[d] + alpha * (m - mean[d]); std[d] = fmaxf(std[d] + alpha * (sd - std[d]), min_std[d]); }
+ * (a frozen dimension, std == 0, never moves). Best-ever record: if best_gen[0] < 0 (none yet) or fitness[elite_idx[0]] >
+ * best_fitness[0] (strict: the first generation that reaches a value keeps it), best_gains = that candidate's R rows, best_fitness
+ * its fitness, best_gen = generation. history_row [4] (out) = {fitness[elite_idx[0]], (the sequential sum of the E elite fitnesses
+ * in rank order) / (float)E, best_fitness after the update, (float)E}. Plain stores by the lanes that own the values; no atomics.
+ * AVD_E_INVALID: a null pointer, G outside 1 .. 65536 (every pair of candidates is compared), L, R as above, n_elite outside 1 .. G,
+ * alpha outside (0, 1], generation < 0. */
+int avd_search_sample_f32(int G, int L, int R, const float* mean, const float* std, const float* lo, const float* hi, uint64_t seed,
+                          uint64_t generation, float* gains, void* stream);
+int avd_search_refit_f32(int G, int L, int R, int n_elite, float alpha, const float* gains, const float* fitness, const float* min_std,
+                         float* mean, float* std, float* best_gains, float* best_fitness, int32_t* best_gen, int generation,
+                         int32_t* elite_idx, float* history_row, void* stream);
+
 /* ---- training under disturbances: the fused step with an observation model (domain randomisation) --------------------------------
  * The evaluator's observation model (above) at training time. A run has n_levels (1 .. AVD_TRAIN_MAX_LEVELS) disturbance levels;
  * platoon p trains under level p % n_levels (an experiment batch: the level of the solo run's platoon index, (g / n_groups) %
