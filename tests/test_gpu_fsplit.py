@@ -12,7 +12,8 @@ workers/trainer.py:472-508), so the bar is float32's own, enforced here rather t
 
 Covered: conditioned inputs (no relu ties) AND unconditioned inputs with every out-of-tolerance tensor traced to a tie row;
 the exact-f32 per-agent kernel + fed_mean; bit-identical reruns; fp16 overflow and non-finite inputs -> NaN; at 4096 x 5 the
-float64 oracle on two whole sets, the f32 engine on all five and the mean-of-halves property; VecTrainer trajectories."""
+float64 oracle on two whole sets, the f32 engine on all five and the mean-of-halves property; VecTrainer trajectories.
+One agent's 64-row tile at every tile ordinal of a workgroup: tests/test_gpu_fsplit_tiles.py, docs/fsplit_tile_parity.md."""
 import numpy as np
 import pytest
 import torch
@@ -20,6 +21,7 @@ import torch
 from avddpg_amd import config, vec
 from oracle import mlp as omlp
 from tests.gpu_util import need_gpu, t
+from tests.split_oracle import tie_rows
 from tests.test_gpu_fset import NAMES, _batch
 from tests.test_gpu_mlp import GRAD_TOL, _nets, _perturbed_group, _relerr
 
@@ -39,22 +41,7 @@ def _tie_mask(grp, M, S, s, a, tie=1e-6, sets=None):
         sel = np.arange(k, s.shape[0], M)
         x = s[sel].reshape(-1, s.shape[2])[:, :S].astype(np.float64)
         act = a[sel].reshape(-1, 1).astype(np.float64)
-        W1, b1, _, _, _, _, W2, b2 = an[:8]
-        z1 = x @ W1 + b1
-        y1 = np.maximum(z1, 0) * omlp._bn_coeffs(*an[2:6])[0] + omlp._bn_coeffs(*an[2:6])[1]
-        pre = [z1, y1 @ W2 + b2]
-        mu = omlp.actor_forward(an, x, 2.5)
-        Ws, bs, Wa, ba = cn[:4]
-        CW2, cb2 = cn[12], cn[13]
-        ys = np.maximum(x @ Ws + bs, 0) * omlp._bn_coeffs(*cn[4:8])[0] + omlp._bn_coeffs(*cn[4:8])[1]
-        pre.append(x @ Ws + bs)
-        for u in (act, mu):
-            za = u @ Wa + ba
-            ya = np.maximum(za, 0) * omlp._bn_coeffs(*cn[8:12])[0] + omlp._bn_coeffs(*cn[8:12])[1]
-            pre += [za, np.concatenate([ys, ya], axis=1) @ CW2 + cb2]
-        t_ = np.zeros(len(x), bool)
-        for z in pre:
-            t_ |= (np.abs(z) < tie * np.abs(z).max()).any(axis=1)
+        t_ = tie_rows(an, cn, x, act, tie)  # (the float64 arithmetic: tests/split_oracle.py)
         bad[sel] = t_.reshape(len(sel), -1)
     return bad
 

@@ -1,7 +1,8 @@
 """dx_kernel (csrc/fsplit.hip) pipelines its tile loop across tiles: row half 1 of tile t is finished in the iteration of tile
 t + 1, the input images and row factors rotate through three LDS slots and the sm images through two, and the last tile's row
 half 1 runs after the loop. Every slot phase and tile count per workgroup from 1 to 5 is taken here against the float64 oracle
-(tests/test_gpu_fsplit.py covers 1-2 tiles and the full 4096 x 5 size)."""
+(tests/test_gpu_fsplit.py covers 1-2 tiles and the full 4096 x 5 size).
+These compare the mean over a set; tile by tile through 33 ordinals: tests/test_gpu_fsplit_tiles.py, docs/fsplit_tile_parity.md."""
 import numpy as np
 import pytest
 import torch
