@@ -357,23 +357,6 @@ static_assert(sizeof(avd_train_level) == 32 && (LINK_RING & (LINK_RING - 1)) == 
 __device__ __forceinline__ bool level_uses_link(const avd_train_level& lv) { return lv.delay != 0 || lv.drop_q != 0u; }
 inline bool level_uses_link_host(const avd_train_level& lv) { return lv.delay != 0 || lv.drop_q != 0u; }
 
-// Sensor noise on the first three components of x (the evaluator's model, csrc/evalx.hip): one Philox call per vehicle, unfused
-// multiply and add, a zero sigma keeps the bits of x.
-__device__ __forceinline__ void observe_noise(float4& ob, const float4& x, const avd_train_level& lv, uint64_t key, uint64_t counter,
-                                              uint32_t rv) {
-#pragma clang fp contract(off)
-    const float sg_ep = lv.sigma[0], sg_ev = lv.sigma[1], sg_a = lv.sigma[2];
-    if (sg_ep != 0.f || sg_ev != 0.f || sg_a != 0.f) {
-        const u32x4 r = philox_at(key, counter, rv, STREAM_TRAIN_OBS);
-        float n_ev;
-        const float n_ep = box_muller(r.x, r.y, &n_ev);
-        const float n_a = box_muller(r.z, r.w, nullptr);
-        if (sg_ep != 0.f) ob.x = x.x + sg_ep * n_ep;
-        if (sg_ev != 0.f) ob.y = x.y + sg_ev * n_ev;
-        if (sg_a != 0.f) ob.z = x.z + sg_a * n_a;
-    }
-}
-
 // HP (avd_step_fused_hp_f32, with G): platoon g's ou_theta / ou_scale from the sweep table, row g % n_groups (its experiment)
 // DIST (avd_step_fused_dist_f32, one DistRef in the pack): the platoon's level picks its plant, obs_out observes x_out, the replay row
 // holds observations. The plant rows of ALL levels and the level table are staged in dynamic LDS once per block ([n_levels][L][24]
@@ -513,7 +496,7 @@ __global__ __launch_bounds__(ENV_THREADS) void step_fused_kernel(const StepArgs 
                 if (dropped) ob.w = d.link_recv[v];
                 else d.link_recv[v] = ob.w = delayed;
             }
-            observe_noise(ob, xn, lv, okey, d.obs_counter, orv);
+            observe_noise(ob, xn, lv.sigma[0], lv.sigma[1], lv.sigma[2], okey, d.obs_counter, orv, STREAM_TRAIN_OBS);  // the evaluator's model
             d.obs_out[v] = ob;
             row_n = ob;
             if constexpr (BASE) row_s = seen;
@@ -560,7 +543,7 @@ __global__ __launch_bounds__(ENV_THREADS) void observe_kernel(int P, int L, cons
     const avd_train_level lv = levels[pl % n_levels];
     const float4 xv = x[v];
     float4 ob = xv;
-    observe_noise(ob, xv, lv, key, counter, G ? (uint32_t)((long)pl * L + i) : (uint32_t)v);
+    observe_noise(ob, xv, lv.sigma[0], lv.sigma[1], lv.sigma[2], key, counter, G ? (uint32_t)((long)pl * L + i) : (uint32_t)v, STREAM_TRAIN_OBS);
     obs[v] = ob;
     if (link_hist) {
         const float4 w4 = make_float4(xv.w, xv.w, xv.w, xv.w);

@@ -24,14 +24,12 @@ namespace avd {
 
 constexpr int CASES_LDS_SHARED = 24 * AVD_MAX_L;                  // sA, sB, sC (floats), one copy per workgroup
 constexpr int CASES_LDS_ROW = 11 * AVD_MAX_L + NTHREADS;          // per row: xin, xs, raw, chain, negr, part (floats); + H1 + H2
-constexpr int DIST_RING = AVD_EVAL_MAX_DELAY + 1;                 // slots of a vehicle's V2V history
 // A vehicle's block in LDS, disturbed only: its case's A, B, C (24), its V2V ring, the last received value, its case's scalars (sigma
 // (3), delay, drop_q, seed (2)), one float of padding: an odd stride puts neighbouring vehicles on different banks. One block per
 // vehicle, the scalars repeated, so that a vehicle thread addresses all of it from one base register.
-constexpr int DIST_HIST = 24, DIST_RECV = DIST_HIST + DIST_RING, DIST_PAR = DIST_RECV + 1, DIST_VEH = DIST_PAR + 7 + 1;
+constexpr int DIST_HIST = 24, DIST_RECV = DIST_HIST + EVAL_RING, DIST_PAR = DIST_RECV + 1, DIST_VEH = DIST_PAR + 7 + 1;
 static_assert(DIST_VEH % 2 == 1, "odd stride");
 constexpr int DIST_LDS_ROW = DIST_VEH * AVD_MAX_L;                // per row
-static_assert((DIST_RING & (DIST_RING - 1)) == 0, "the ring index is taken with a mask");
 
 struct CasesArgs {
     avd_mlp_layout lay;
@@ -46,15 +44,6 @@ struct CasesArgs {
     float high, lo, hi, inv_dt;
     float* counters;          // [G][K][M]
     float* metrics;           // [G][K][L][AVD_EVAL_NMETRIC] or null
-};
-
-// The disturbed variant's per-case tables (device memory, [K] each; scenarios.py forms them)
-struct DistArgs {
-    const float* sigma;          // [K][3] sensor-noise standard deviations of ep, ev, a (finite, >= 0)
-    const int32_t* delay;        // [K] V2V delay in steps, 0 .. AVD_EVAL_MAX_DELAY
-    const uint32_t* drop_q;      // [K] V2V loss: a sample is dropped iff (word >> 8) < drop_q, drop_q = round(p * 2^24)
-    const uint64_t* noise_seed;  // [K] Philox key of the case's draws
-    const float* abc;            // [K][L][24] the true plant's A (16), B (4), C (4) per vehicle, or null: the constants block's
 };
 
 // the RB row operands of one k: xT[k][0..RB)
@@ -203,7 +192,7 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a,
             const uint64_t seed = live ? da.noise_seed[k] : 0;
             p[0] = live ? da.sigma[k * 3] : 0.f, p[1] = live ? da.sigma[k * 3 + 1] : 0.f, p[2] = live ? da.sigma[k * 3 + 2] : 0.f;
             // (the host refuses delays outside the ring; the mask keeps any value inside it)
-            p[3] = __int_as_float(live ? (da.delay[k] & (DIST_RING - 1)) : 0);
+            p[3] = __int_as_float(live ? (da.delay[k] & (EVAL_RING - 1)) : 0);
             p[4] = __uint_as_float(live ? da.drop_q[k] : 0u);
             p[5] = __uint_as_float((uint32_t)seed), p[6] = __uint_as_float((uint32_t)(seed >> 32));
         }
@@ -215,7 +204,7 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a,
     __syncthreads();
     float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
     float pa = 0.f, cnt = 0.f;
-    float mx_ep = 0.f, mx_ev = 0.f, mx_a = 0.f, su2 = 0.f, sj2 = 0.f, nterm = 0.f, first = -1.0f;
+    VehMetrics met;
     const float* leader = a.leader + (long)(k0 + (live ? row : 0)) * a.T;
     if (live) {
         const float* x0 = a.x0 + ((long)(k0 + row) * nv + v) * 4;
@@ -225,7 +214,7 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a,
     if constexpr (DIST) {
         if (veh) {
             float* hist = vdat + (row * AVD_MAX_L + v) * DIST_VEH + DIST_HIST;
-            for (int j = 0; j <= DIST_RING; ++j) hist[j] = xv.w;  // steps before the first, and the last received value: x0's
+            for (int j = 0; j <= EVAL_RING; ++j) hist[j] = xv.w;  // steps before the first, and the last received value: x0's
         }
     } else {
         if (veh) ((float4*)(xs + row * 4 * AVD_MAX_L))[v] = xv;
@@ -244,21 +233,8 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a,
                 const uint64_t nseed = (uint64_t)__float_as_uint(p[5]) | ((uint64_t)__float_as_uint(p[6]) << 32);
                 float* hist = vd + DIST_HIST;  // this vehicle's ring (its own thread's alone), then its last received value
                 float4 ob = xv;
-                hist[t & (DIST_RING - 1)] = xv.w;
-                const float delayed = hist[(t - dly) & (DIST_RING - 1)];  // a slot of a step < 0 has not been overwritten yet
-                // loss: an integer compare on one Philox word (drop_q = 0 never drops: no draw needed)
-                const bool dropped = dq != 0 && (philox_at(nseed, (uint64_t)t, (uint32_t)v, STREAM_EVAL_LINK).x >> 8) < dq;
-                if (!dropped) hist[DIST_RING] = delayed;
-                ob.w = dropped ? hist[DIST_RING] : delayed;
-                if (sg_ep != 0.f || sg_ev != 0.f || sg_a != 0.f) {
-                    const u32x4 r = philox_at(nseed, (uint64_t)t, (uint32_t)v, STREAM_EVAL_OBS);
-                    float n_ev;
-                    const float n_ep = box_muller(r.x, r.y, &n_ev);
-                    const float n_a = box_muller(r.z, r.w, nullptr);
-                    if (sg_ep != 0.f) ob.x = xv.x + sg_ep * n_ep;  // a zero level skips the add: exact by construction
-                    if (sg_ev != 0.f) ob.y = xv.y + sg_ev * n_ev;
-                    if (sg_a != 0.f) ob.z = xv.z + sg_a * n_a;
-                }
+                ob.w = v2v_link<1>(hist, hist[EVAL_RING], xv.w, t, dly, dq, nseed, (uint32_t)v);
+                observe_noise(ob, xv, sg_ep, sg_ev, sg_a, nseed, (uint64_t)t, (uint32_t)v, STREAM_EVAL_OBS);
                 ((float4*)(xs + row * 4 * AVD_MAX_L))[v] = ob;
             }
             __syncthreads();
@@ -310,16 +286,7 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a,
             const float nr = veh_step_post(cst, vs, Bv, DIST ? Bv + 4 : sC + v * 4, xv, pa, uu, exog, xn);
             if (M == nv) cnt = cnt + nr;  // counters += env.reward[0]
             else negr[row * AVD_MAX_L + v] = nr;
-            // ---- metrics (scenarios.metrics_from_traces: sequential float32 sums in step order, no contraction) ----
-            const bool is_term = ((fabsf(xv.x) > cst->max_ep) || (fabsf(xv.y) > cst->max_ev)) && (cst->can_terminate != 0);  // veh_step_post's test
-            if (is_term) {
-                nterm = nterm + 1.0f;
-                if (first < 0.f) first = (float)t;
-            }
-            const float jerk = (xv.z - pa) * a.inv_dt;
-            su2 = su2 + uu * uu;
-            sj2 = sj2 + jerk * jerk;
-            mx_ep = fmaxf(mx_ep, fabsf(xn.x)), mx_ev = fmaxf(mx_ev, fabsf(xn.y)), mx_a = fmaxf(mx_a, fabsf(xn.z));
+            met.step(cst, xv, xn, pa, uu, a.inv_dt, t);
             pa = xv.z;  // prev_x <- x
             xv = xn;
             if constexpr (!DIST) ((float4*)(xs + row * 4 * AVD_MAX_L))[v] = xn;
@@ -333,10 +300,7 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a,
     }
     if (live) {
         if (v < M) a.counters[cas * M + v] = cnt;
-        if (a.metrics) {
-            float* o = a.metrics + (cas * nv + v) * AVD_EVAL_NMETRIC;
-            o[0] = mx_ep, o[1] = mx_ev, o[2] = mx_a, o[3] = su2, o[4] = sj2, o[5] = nterm, o[6] = first, o[7] = fabsf(xv.x);
-        }
+        if (a.metrics) met.store(a.metrics + (cas * nv + v) * AVD_EVAL_NMETRIC, xv);
     }
 }
 
@@ -354,21 +318,31 @@ int pick_block(const int (&sizes)[N], int K, int L) {
     return rb;
 }
 
-int cases_block(int K, int L) { return pick_block(CASES_RB, K, L); }
-
-template <int RB, class... D>
-int launch_cases(const char* who, const CasesArgs& a, size_t lds, hipStream_t stream, const D&... dist) {
-    if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute((const void*)eval_cases_kernel<RB, D...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((eval_cases_kernel<RB, D...>), dim3(a.G, (a.K + RB - 1) / RB), dim3(NTHREADS), lds, stream, a, dist...);
-    return check_launch(who);
+// The one dispatch from a block size to its kernel instantiation: CASES_RB's sizes, with a DistArgs in the pack DIST_RB's
+template <class... D>
+int launch_cases(const char* who, int rb, const CasesArgs& a, size_t lds, hipStream_t stream, const D&... dist) {
+    const auto go = [&](auto size) {
+        constexpr int RB = decltype(size)::value;
+        if (lds > 48 * 1024)
+            (void)hipFuncSetAttribute((const void*)eval_cases_kernel<RB, D...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL((eval_cases_kernel<RB, D...>), dim3(a.G, (a.K + RB - 1) / RB), dim3(NTHREADS), lds, stream, a, dist...);
+        return check_launch(who);
+    };
+    if constexpr (!pack_has<DistArgs, D...>)
+        if (rb == 16) return go(std::integral_constant<int, 16>{});
+    switch (rb) {
+        case 8: return go(std::integral_constant<int, 8>{});
+        case 4: return go(std::integral_constant<int, 4>{});
+        default: return go(std::integral_constant<int, 1>{});
+    }
 }
 
-// The checks, the block size and the argument block of the nominal (dist = false) and the disturbed entry point
-int cases_args(const char* who, const avd_mlp_layout* lay, const avd_env_consts* d_consts, int G, int K, int L, int M, int T,
-               const float* theta, const float* stats, int n_sets, const int32_t* set_base, const float* x0, const float* prev_a0,
-               const float* leader, float high, float lo, float hi, float sample_rate, float* counters, float* metrics, bool dist,
-               CasesArgs& a, int& rb, size_t& lds) {
+// Every cases entry point: the checks, the block size, the argument block and the launch. dist: the disturbed variant's tables, or
+// null (the nominal kernel); res: a residual policy's law, or null.
+int cases_launch(const char* who, const DistArgs* dist, const ResArgs* res, const avd_mlp_layout* lay, const avd_env_consts* d_consts, int G,
+                 int K, int L, int M, int T, const float* theta, const float* stats, int n_sets, const int32_t* set_base, const float* x0,
+                 const float* prev_a0, const float* leader, float high, float lo, float hi, float sample_rate, float* counters,
+                 float* metrics, void* stream) {
     AVD_REQUIRE(lay && d_consts, "%s: null layout or constants", who);
     AVD_REQUIRE(L >= 1 && L <= AVD_MAX_L, "%s: L=%d (L must be 1..%d)", who, L, AVD_MAX_L);
     AVD_REQUIRE(M == L || M == 1, "%s: M=%d (M must be L=%d, decentralized, or 1, centralized)", who, M, L);
@@ -381,9 +355,9 @@ int cases_args(const char* who, const avd_mlp_layout* lay, const avd_env_consts*
     AVD_REQUIRE(lay->A * M == L && lay->S <= x_stride && lay->S >= 1,
                 "%s: layout S=%d A=%d does not fit L=%d M=%d (need A * M == L, S <= %d)", who, lay->S, lay->A, L, M, x_stride);
     AVD_REQUIRE(lay->H1 > 0 && lay->H2 > 0, "%s: layout H1=%d H2=%d", who, lay->H1, lay->H2);
-    rb = dist ? pick_block(DIST_RB, K, L) : cases_block(K, L);
+    const int rb = dist ? pick_block(DIST_RB, K, L) : pick_block(CASES_RB, K, L);
     const size_t row = (size_t)CASES_LDS_ROW + (dist ? DIST_LDS_ROW : 0) + lay->H1 + lay->H2;
-    lds = sizeof(float) * ((size_t)CASES_LDS_SHARED + (size_t)rb * row);
+    const size_t lds = sizeof(float) * ((size_t)CASES_LDS_SHARED + (size_t)rb * row);
     if (lds > 160 * 1024) {
         set_error("%s: hidden sizes need %zu B of LDS for blocks of %d cases (> 160 KiB)", who, lds, rb);
         return AVD_E_UNSUPPORTED;
@@ -392,12 +366,20 @@ int cases_args(const char* who, const avd_mlp_layout* lay, const avd_env_consts*
         set_error("%s: K=%d cases in blocks of %d exceed the grid's second dimension", who, K, rb);
         return AVD_E_UNSUPPORTED;
     }
+    if (dist) AVD_REQUIRE(dist->sigma && dist->delay && dist->drop_q && dist->noise_seed, "%s: null disturbance table (only abc may be null)", who);
+    if (res)
+        if (const int rc = residual_check(who, res->gains, res->scale, M, L)) return rc;
+    CasesArgs a;
     a.lay = *lay, a.cst = d_consts, a.G = G, a.K = K, a.L = L, a.M = M, a.T = T, a.x_stride = x_stride, a.n_sets = n_sets;
     a.theta = theta, a.stats = stats, a.set_base = set_base, a.x0 = x0, a.prev_a0 = prev_a0, a.leader = leader;
     a.high = high, a.lo = lo, a.hi = hi;
     a.inv_dt = 1.0f / sample_rate;  // host float32 division, as avd_eval_rollout_f32 forms it
     a.counters = counters, a.metrics = metrics;
-    return AVD_OK;
+    const hipStream_t s = (hipStream_t)stream;
+    if (dist && res) return launch_cases(who, rb, a, lds, s, *dist, *res);
+    if (dist) return launch_cases(who, rb, a, lds, s, *dist);
+    if (res) return launch_cases(who, rb, a, lds, s, *res);
+    return launch_cases(who, rb, a, lds, s);
 }
 
 }  // namespace avd
@@ -407,26 +389,15 @@ using namespace avd;
 extern "C" int avd_eval_cases_block(int K, int L) {
     AVD_REQUIRE(K >= 1, "avd_eval_cases_block: K=%d (K must be >= 1)", K);
     AVD_REQUIRE(L >= 1 && L <= AVD_MAX_L, "avd_eval_cases_block: L=%d (L must be 1..%d)", L, AVD_MAX_L);
-    return cases_block(K, L);
+    return pick_block(CASES_RB, K, L);
 }
 
 extern "C" int avd_eval_cases_f32(const avd_mlp_layout* lay, const avd_env_consts* d_consts, int G, int K, int L, int M, int T,
                                   const float* theta, const float* stats, int n_sets, const int32_t* set_base, const float* x0,
                                   const float* prev_a0, const float* leader, float high, float lo, float hi, float sample_rate,
                                   float* counters, float* metrics, void* stream) {
-    const char* who = "avd_eval_cases_f32";
-    CasesArgs a;
-    int rb;
-    size_t lds;
-    if (const int rc = cases_args(who, lay, d_consts, G, K, L, M, T, theta, stats, n_sets, set_base, x0, prev_a0, leader, high, lo, hi,
-                                  sample_rate, counters, metrics, false, a, rb, lds))
-        return rc;
-    switch (rb) {
-        case 16: return launch_cases<16>(who, a, lds, (hipStream_t)stream);
-        case 8: return launch_cases<8>(who, a, lds, (hipStream_t)stream);
-        case 4: return launch_cases<4>(who, a, lds, (hipStream_t)stream);
-        default: return launch_cases<1>(who, a, lds, (hipStream_t)stream);
-    }
+    return cases_launch("avd_eval_cases_f32", nullptr, nullptr, lay, d_consts, G, K, L, M, T, theta, stats, n_sets, set_base, x0, prev_a0,
+                        leader, high, lo, hi, sample_rate, counters, metrics, stream);
 }
 
 extern "C" int avd_eval_cases_dist_block(int K, int L) {
@@ -455,20 +426,9 @@ extern "C" int avd_eval_cases_dist_f32(const avd_mlp_layout* lay, const avd_env_
                                        const float* prev_a0, const float* leader, float high, float lo, float hi, float sample_rate,
                                        const float* sigma, const int32_t* delay, const uint32_t* drop_q, const uint64_t* noise_seed,
                                        const float* abc, float* counters, float* metrics, void* stream) {
-    const char* who = "avd_eval_cases_dist_f32";
-    CasesArgs a;
-    int rb;
-    size_t lds;
-    if (const int rc = cases_args(who, lay, d_consts, G, K, L, M, T, theta, stats, n_sets, set_base, x0, prev_a0, leader, high, lo, hi,
-                                  sample_rate, counters, metrics, true, a, rb, lds))
-        return rc;
-    AVD_REQUIRE(sigma && delay && drop_q && noise_seed, "%s: null disturbance table (only abc may be null)", who);
     const DistArgs d = {sigma, delay, drop_q, noise_seed, abc};
-    switch (rb) {
-        case 8: return launch_cases<8>(who, a, lds, (hipStream_t)stream, d);
-        case 4: return launch_cases<4>(who, a, lds, (hipStream_t)stream, d);
-        default: return launch_cases<1>(who, a, lds, (hipStream_t)stream, d);
-    }
+    return cases_launch("avd_eval_cases_dist_f32", &d, nullptr, lay, d_consts, G, K, L, M, T, theta, stats, n_sets, set_base, x0, prev_a0,
+                        leader, high, lo, hi, sample_rate, counters, metrics, stream);
 }
 
 // The scenario evaluator for a residual policy, nominal (all five disturbance tables null) or disturbed (only abc may be null, with
@@ -480,29 +440,11 @@ extern "C" int avd_eval_cases_res_f32(const avd_mlp_layout* lay, const avd_env_c
                                       const float* sigma, const int32_t* delay, const uint32_t* drop_q, const uint64_t* noise_seed,
                                       const float* abc, const float* d_gains, float scale, float* counters, float* metrics, void* stream) {
     const char* who = "avd_eval_cases_res_f32";
-    const bool dist = sigma || delay || drop_q || noise_seed || abc;
+    const bool dist = sigma || delay || drop_q || noise_seed || abc;  // which variant: a mix of null and non-null tables is refused first
     AVD_REQUIRE(!dist || (sigma && delay && drop_q && noise_seed),
                 "%s: null disturbance table (all five null: the nominal plant and a perfect observation; otherwise only abc may be null)", who);
-    CasesArgs a;
-    int rb;
-    size_t lds;
-    if (const int rc = cases_args(who, lay, d_consts, G, K, L, M, T, theta, stats, n_sets, set_base, x0, prev_a0, leader, high, lo, hi,
-                                  sample_rate, counters, metrics, dist, a, rb, lds))
-        return rc;
-    if (const int rc = residual_check(who, d_gains, scale, M, L)) return rc;
+    const DistArgs d = {sigma, delay, drop_q, noise_seed, abc};
     const ResArgs r = {d_gains, scale};
-    if (dist) {
-        const DistArgs d = {sigma, delay, drop_q, noise_seed, abc};
-        switch (rb) {
-            case 8: return launch_cases<8>(who, a, lds, (hipStream_t)stream, d, r);
-            case 4: return launch_cases<4>(who, a, lds, (hipStream_t)stream, d, r);
-            default: return launch_cases<1>(who, a, lds, (hipStream_t)stream, d, r);
-        }
-    }
-    switch (rb) {
-        case 16: return launch_cases<16>(who, a, lds, (hipStream_t)stream, r);
-        case 8: return launch_cases<8>(who, a, lds, (hipStream_t)stream, r);
-        case 4: return launch_cases<4>(who, a, lds, (hipStream_t)stream, r);
-        default: return launch_cases<1>(who, a, lds, (hipStream_t)stream, r);
-    }
+    return cases_launch(who, dist ? &d : nullptr, &r, lay, d_consts, G, K, L, M, T, theta, stats, n_sets, set_base, x0, prev_a0, leader, high,
+                        lo, hi, sample_rate, counters, metrics, stream);
 }

@@ -1,7 +1,8 @@
 // Linear baseline of the scenario evaluator for gfx950: G gain sets x K cases of the evaluator rollout (evalx.hip's cases, start
 // states, leader rows and per-case disturbance tables) in ONE launch, the controller a static gain row per vehicle instead of an MLP:
 //   u = clip(((g0 * ob.x + g1 * ob.y) + g2 * ob.z) + g3 * ob.w, lo, hi)        (Model A: the first three terms; g3 is not read)
-// with ob the observed state. The platoon step, the reward and the terminal test are eval_common.h's; the metrics are evalx.hip's.
+// with ob the observed state. The law, the observation model (V2V link, sensor noise), the platoon step, the reward and the metrics are
+// eval_common.h's: eval_cases_kernel's (evalx.hip) text.
 //
 // A rollout is T dependent steps of a few dozen flops and shares nothing with any other, so the kernel is built for occupancy and
 // latency, not bandwidth:
@@ -18,7 +19,7 @@
 //
 // hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage (profiles/eval_linear_resource_usage.txt):
 //   eval_linear_kernel<>         (nominal):    64 VGPRs, 0 AGPRs, no scratch,    0 B LDS, 8 waves per SIMD
-//   eval_linear_kernel<LinDist>  (disturbed): 118 VGPRs, 0 AGPRs, no scratch, 4096 B LDS, 4 waves per SIMD (the registers are Box-Muller's
+//   eval_linear_kernel<DistArgs> (disturbed): 118 VGPRs, 0 AGPRs, no scratch, 4096 B LDS, 4 waves per SIMD (the registers are Box-Muller's
 //                                             logf / sinf / cosf and Philox's; at 4096 gain sets x 12 cases x 5 vehicles the launch is
 //                                             4096 waves, 4 per SIMD of 256 CUs, so the count does not limit that shape)
 #include <limits.h>
@@ -27,9 +28,7 @@
 
 namespace avd {
 
-constexpr int LIN_THREADS = 64;                      // one wave
-constexpr int LIN_RING = AVD_EVAL_MAX_DELAY + 1;     // slots of a vehicle's V2V history
-static_assert((LIN_RING & (LIN_RING - 1)) == 0, "the ring index is taken with a mask");
+constexpr int LIN_THREADS = 64;  // one wave
 
 struct LinArgs {
     const avd_env_consts* cst;
@@ -43,16 +42,7 @@ struct LinArgs {
     float* metrics;        // [G][K][L][AVD_EVAL_NMETRIC] or null
 };
 
-// The disturbed variant's per-case tables: evalx.hip's DistArgs, field for field
-struct LinDist {
-    const float* sigma;          // [K][3]
-    const int32_t* delay;        // [K]
-    const uint32_t* drop_q;      // [K]
-    const uint64_t* noise_seed;  // [K]
-    const float* abc;            // [K][L][24] or null: the constants block's
-};
-
-// D is empty (nominal: the constants block's plant, a perfect observation, no LDS) or one LinDist
+// D is empty (nominal: the constants block's plant, a perfect observation, no LDS) or one DistArgs
 template <class... D>
 __global__ __launch_bounds__(LIN_THREADS) void eval_linear_kernel(const LinArgs a, const D... dist) {
 #pragma clang fp contract(off)
@@ -69,7 +59,7 @@ __global__ __launch_bounds__(LIN_THREADS) void eval_linear_kernel(const LinArgs 
     float abc[24];
     bool table = false;
     if constexpr (DIST) {
-        const LinDist da{dist...};
+        const DistArgs da{dist...};
         if (da.abc) {
             table = true;
 #pragma unroll
@@ -86,7 +76,7 @@ __global__ __launch_bounds__(LIN_THREADS) void eval_linear_kernel(const LinArgs 
     const float4 gn = make_float4(gp[0], gp[1], gp[2], gp[3]);
     float4 xv = make_float4(a.x0[kv * 4], a.x0[kv * 4 + 1], a.x0[kv * 4 + 2], a.x0[kv * 4 + 3]);
     float pa = a.prev_a0[kv], cnt = 0.f;
-    float mx_ep = 0.f, mx_ev = 0.f, mx_a = 0.f, su2 = 0.f, sj2 = 0.f, nterm = 0.f, first = -1.0f;
+    VehMetrics met;
     const bool model_a = cst->model_a != 0;
     const float* leader = a.leader + (long)k * a.T;
     float lead_next = (v == 0) ? leader[0] : 0.f;
@@ -97,67 +87,40 @@ __global__ __launch_bounds__(LIN_THREADS) void eval_linear_kernel(const LinArgs 
     uint64_t nseed = 0;
     float* ring = nullptr;
     if constexpr (DIST) {
-        __shared__ float s_ring[LIN_RING * LIN_THREADS];  // [slot][lane]
-        const LinDist da{dist...};
+        __shared__ float s_ring[EVAL_RING * LIN_THREADS];  // [slot][lane]
+        const DistArgs da{dist...};
         sg_ep = da.sigma[k * 3L], sg_ev = da.sigma[k * 3L + 1], sg_a = da.sigma[k * 3L + 2];
-        dly = da.delay[k] & (LIN_RING - 1);  // (the host refuses delays outside the ring; the mask keeps any value inside it)
+        dly = da.delay[k] & (EVAL_RING - 1);  // (the host refuses delays outside the ring; the mask keeps any value inside it)
         dq = da.drop_q[k];
         nseed = da.noise_seed[k];
         ring = s_ring + lane;
 #pragma unroll
-        for (int j = 0; j < LIN_RING; ++j) ring[j * LIN_THREADS] = xv.w;  // steps before the first: x0's
-        recv = xv.w;                                                       // and the last received value
+        for (int j = 0; j < EVAL_RING; ++j) ring[j * LIN_THREADS] = xv.w;  // steps before the first: x0's
+        recv = xv.w;                                                        // and the last received value
     }
     for (int t = 0; t < a.T; ++t) {
         const float lead = lead_next;
         if (v == 0 && t + 1 < a.T) lead_next = leader[t + 1];  // next step's, in flight during this one
-        // ---- what the controller sees of the true pre-step state xv: eval_cases_kernel<RB, DistArgs>, evalx.hip lines 245-260 ----
+        // ---- what the controller sees of the true pre-step state xv ----
         float4 ob = xv;
         if constexpr (DIST) {
-            ring[(t & (LIN_RING - 1)) * LIN_THREADS] = xv.w;
-            const float delayed = ring[((t - dly) & (LIN_RING - 1)) * LIN_THREADS];  // a slot of a step < 0 has not been overwritten yet
-            // loss: an integer compare on one Philox word (drop_q = 0 never drops: no draw needed)
-            const bool dropped = dq != 0 && (philox_at(nseed, (uint64_t)t, (uint32_t)v, STREAM_EVAL_LINK).x >> 8) < dq;
-            if (!dropped) recv = delayed;
-            ob.w = recv;
-            if (sg_ep != 0.f || sg_ev != 0.f || sg_a != 0.f) {
-                const u32x4 r = philox_at(nseed, (uint64_t)t, (uint32_t)v, STREAM_EVAL_OBS);
-                float n_ev;
-                const float n_ep = box_muller(r.x, r.y, &n_ev);
-                const float n_a = box_muller(r.z, r.w, nullptr);
-                if (sg_ep != 0.f) ob.x = xv.x + sg_ep * n_ep;  // a zero level skips the add: exact by construction
-                if (sg_ev != 0.f) ob.y = xv.y + sg_ev * n_ev;
-                if (sg_a != 0.f) ob.z = xv.z + sg_a * n_a;
-            }
+            ob.w = v2v_link<LIN_THREADS>(ring, recv, xv.w, t, dly, dq, nseed, (uint32_t)v);
+            observe_noise(ob, xv, sg_ep, sg_ev, sg_a, nseed, (uint64_t)t, (uint32_t)v, STREAM_EVAL_OBS);
         }
         // ---- the linear law, platoon step ----
-        float z = (gn.x * ob.x + gn.y * ob.y) + gn.z * ob.z;
-        if (!model_a) z = z + gn.w * ob.w;
-        const float uu = fminf(fmaxf(z, a.lo), a.hi);  // np.clip
+        const float uu = fminf(fmaxf(linear_law(gn, ob, model_a), a.lo), a.hi);  // np.clip
         const VehStep vs = veh_step_pre(cst, abc, abc + 16, xv, uu);
         const float up = __shfl_up(vs.chain, 1);  // lane - 1: the predecessor of every vehicle but the first
         const float exog = (v == 0) ? lead : up;
         float4 xn;
         const float nr = veh_step_post(cst, vs, abc + 16, abc + 20, xv, pa, uu, exog, xn);
         cnt = cnt + nr;  // counters += env.reward[0], per vehicle (decentralized)
-        // ---- metrics: evalx.hip lines 307-318 (scenarios.metrics_from_traces: sequential float32 sums in step order) ----
-        const bool is_term = ((fabsf(xv.x) > cst->max_ep) || (fabsf(xv.y) > cst->max_ev)) && (cst->can_terminate != 0);  // veh_step_post's test
-        if (is_term) {
-            nterm = nterm + 1.0f;
-            if (first < 0.f) first = (float)t;
-        }
-        const float jerk = (xv.z - pa) * a.inv_dt;
-        su2 = su2 + uu * uu;
-        sj2 = sj2 + jerk * jerk;
-        mx_ep = fmaxf(mx_ep, fabsf(xn.x)), mx_ev = fmaxf(mx_ev, fabsf(xn.y)), mx_a = fmaxf(mx_a, fabsf(xn.z));
+        met.step(cst, xv, xn, pa, uu, a.inv_dt, t);
         pa = xv.z;  // prev_x <- x
         xv = xn;
     }
     a.counters[roll * nv + v] = cnt;
-    if (a.metrics) {
-        float* o = a.metrics + (roll * nv + v) * AVD_EVAL_NMETRIC;
-        o[0] = mx_ep, o[1] = mx_ev, o[2] = mx_a, o[3] = su2, o[4] = sj2, o[5] = nterm, o[6] = first, o[7] = fabsf(xv.x);
-    }
+    if (a.metrics) met.store(a.metrics + (roll * nv + v) * AVD_EVAL_NMETRIC, xv);
 }
 
 // One thread per gain set: the sequential float32 sum of its K * L counters in (k, v) order, divided by (float)(K * L)
@@ -206,7 +169,7 @@ extern "C" int avd_eval_linear_f32(const avd_env_consts* d_consts, int G, int K,
     a.inv_dt = 1.0f / sample_rate;  // host float32 division, as avd_eval_cases_f32 forms it
     a.counters = counters, a.metrics = metrics;
     if (!dist) return launch_linear(who, a, (long)blocks, (hipStream_t)stream);
-    const LinDist d = {sigma, delay, drop_q, noise_seed, abc};
+    const DistArgs d = {sigma, delay, drop_q, noise_seed, abc};
     return launch_linear(who, a, (long)blocks, (hipStream_t)stream, d);
 }
 

@@ -69,6 +69,38 @@ def _base_gains(base_law, conf, dev):
     return torch.from_numpy(base_law.gains(conf.pl_size)).to(dev), float(base_law.scale)
 
 
+def _starts(conf, seeds, manual_timestep_override):
+    """``_start`` for every evaluation seed, the caller's global ``np.random`` state restored."""
+    saved = np.random.get_state()
+    try:
+        return [_start(conf, True, manual_timestep_override, evaluation_seed=sd) for sd in seeds]
+    finally:
+        np.random.set_state(saved)
+
+
+def _address_sets(who, actors, env, platoons, set_mod, set_bases):
+    """The weight sets ``platoons`` / ``set_mod`` / ``set_bases`` address in ``actors`` (run_many's docstring), checked. -> (shared,
+    per_entry, bases): shared sets or per-agent ones; one result per entry of ``platoons`` (per-agent sets, or shared sets with
+    set_bases) or ONE for all of them (shared sets: every platoon's result is the same); the first set of each result."""
+    M, lay = env.num_models, actors.lay
+    if (lay.S, lay.A) != (env.num_states, env.num_actions):
+        raise ValueError(f"actors have S={lay.S} A={lay.A}, the platoon needs S={env.num_states} A={env.num_actions}")
+    shared = set_mod is not None and set_mod != 0
+    if shared and set_mod != M:
+        raise ValueError(f"set_mod={set_mod}: {who} addresses per-agent sets (None / 0) or shared sets (set_mod = M = {M})")
+    if not shared and min(platoons) < 0:
+        raise ValueError("negative platoon index")
+    if set_bases is not None:
+        set_bases = [int(b) for b in set_bases]
+        if not shared or len(set_bases) != len(platoons) or min(set_bases) < 0:
+            raise ValueError(f"set_bases={set_bases}: shared sets only (set_mod = M), one non-negative base per platoon entry")
+    need = (M + (max(set_bases) if set_bases else 0)) if shared else (max(platoons) + 1) * M
+    if need > actors.n_sets:
+        raise ValueError(f"platoons {platoons} need {need} weight sets, the group holds {actors.n_sets}")
+    per_entry = not shared or set_bases is not None
+    return shared, per_entry, [0] if not per_entry else (set_bases if shared else [p * M for p in platoons])
+
+
 class RolloutBatch:
     """The device inputs of one avd_eval_rollout_f32 launch (prepare_many); ``launch()`` enqueues it on the current stream,
     ``results()`` reads the counters and traces back. run_many = prepare_many + launch + results."""
@@ -79,31 +111,11 @@ class RolloutBatch:
         if not platoons or not seeds:
             raise ValueError("run_many needs at least one platoon and one seed")
         NP, NS = len(platoons), len(seeds)
-        saved = np.random.get_state()
-        try:
-            starts = [_start(conf, True, manual_timestep_override, evaluation_seed=sd) for sd in seeds]
-        finally:
-            np.random.set_state(saved)
+        starts = _starts(conf, seeds, manual_timestep_override)
         env, _, T = starts[0]
         L, M = conf.pl_size, env.num_models
-        lay = actors.lay
-        if (lay.S, lay.A) != (env.num_states, env.num_actions):
-            raise ValueError(f"actors have S={lay.S} A={lay.A}, the platoon needs S={env.num_states} A={env.num_actions}")
-        shared = set_mod is not None and set_mod != 0
-        if shared and set_mod != M:
-            raise ValueError(f"set_mod={set_mod}: run_many addresses per-agent sets (None / 0) or shared sets (set_mod = M = {M})")
-        if not shared and min(platoons) < 0:
-            raise ValueError("negative platoon index")
-        if set_bases is not None:
-            set_bases = [int(b) for b in set_bases]
-            if not shared or len(set_bases) != NP or min(set_bases) < 0:
-                raise ValueError(f"set_bases={set_bases}: shared sets only (set_mod = M), one non-negative base per platoon entry")
-        need = (M + (max(set_bases) if set_bases else 0)) if shared else (max(platoons) + 1) * M
-        if need > actors.n_sets:
-            raise ValueError(f"platoons {platoons} need {need} weight sets, the group holds {actors.n_sets}")
-        # rollouts: shared sets one per seed (every platoon's result is the same) -- or, with set_bases, one per (entry, seed); per-agent
-        # sets one per (platoon, seed)
-        per_entry = not shared or set_bases is not None
+        # rollouts: one per (result, seed)
+        _, per_entry, bases = _address_sets("run_many", actors, env, platoons, set_mod, set_bases)
         self.roll = (lambda i, k: i * NS + k) if per_entry else (lambda i, k: k)
         self.n_roll = NP * NS if per_entry else NS
         want = []
@@ -120,8 +132,7 @@ class RolloutBatch:
         self.x0 = torch.stack([e.x.reshape(L, 4) for e, _, _ in starts]).contiguous()
         self.pa0 = torch.stack([e.prev_a.reshape(L) for e, _, _ in starts]).contiguous()
         self.leader = torch.from_numpy(np.stack(self.leader_h)).to(dev)
-        bases = [0] * NS if not per_entry else ([b for b in set_bases for _ in seeds] if shared else [p * M for p in platoons for _ in seeds])
-        self.set_base = torch.tensor(bases, **i32)
+        self.set_base = torch.tensor([b for b in bases for _ in seeds], **i32)
         self.start_idx = torch.tensor(list(range(NS)) * (NP if per_entry else 1), **i32)
         if self.set_base.numel() != self.n_roll or self.start_idx.numel() != self.n_roll:  # (the kernel reads both per rollout)
             raise AssertionError(f"rollout tables of {self.set_base.numel()} / {self.start_idx.numel()} entries for {self.n_roll} rollouts")
@@ -134,16 +145,11 @@ class RolloutBatch:
 
     def launch(self):
         a, c = self.actors, self.conf
-        if self.gains is not None:  # a residual policy: the law in front of the plant (avd_eval_rollout_res_f32)
-            call("avd_eval_rollout_res_f32", a._layp, ptr(self.env.d_consts), self.n_roll, self.L, self.M, self.T, ptr(a.theta), ptr(a.stats),
-                 a.n_sets, ptr(self.set_base), ptr(self.x0), ptr(self.pa0), ptr(self.leader), self.NS, ptr(self.start_idx), a.high,
-                 c.action_low, c.action_high, c.sample_rate, ptr(self.counters), len(self.tr_roll), ptr(self.tr_idx), ptr(self.tr_s),
-                 ptr(self.tr_a), ptr(self.tr_j), ptr(self.gains), self.res_scale, stream_handle())
-            return
-        call("avd_eval_rollout_f32", a._layp, ptr(self.env.d_consts), self.n_roll, self.L, self.M, self.T, ptr(a.theta), ptr(a.stats),
-             a.n_sets, ptr(self.set_base), ptr(self.x0), ptr(self.pa0), ptr(self.leader), self.NS, ptr(self.start_idx), a.high,
-             c.action_low, c.action_high, c.sample_rate, ptr(self.counters), len(self.tr_roll), ptr(self.tr_idx), ptr(self.tr_s),
-             ptr(self.tr_a), ptr(self.tr_j), stream_handle())
+        res = () if self.gains is None else (ptr(self.gains), self.res_scale)  # a residual policy: the law in front of the plant
+        call("avd_eval_rollout_res_f32" if res else "avd_eval_rollout_f32", a._layp, ptr(self.env.d_consts), self.n_roll, self.L, self.M,
+             self.T, ptr(a.theta), ptr(a.stats), a.n_sets, ptr(self.set_base), ptr(self.x0), ptr(self.pa0), ptr(self.leader), self.NS,
+             ptr(self.start_idx), a.high, c.action_low, c.action_high, c.sample_rate, ptr(self.counters), len(self.tr_roll),
+             ptr(self.tr_idx), ptr(self.tr_s), ptr(self.tr_a), ptr(self.tr_j), *res, stream_handle())
 
     def results(self):
         c = self.counters.cpu().numpy()
@@ -202,20 +208,6 @@ class CaseResults:
         return _sc.summarise(self.metrics, self.T)
 
 
-def _case_tables(conf, names, starts, T, amp, period_s):
-    """The cases of a scenario suite -- scenarios x seeds, seeds innermost; a case's start state is its seed's, its leader row its
-    scenario's (gaussian: its seed's) -- from the seeds' ``_start`` results: (leader rows float32 [K, T] on the host, x0 [K, L, 4] and
-    prev_a0 [K, L] on the device)."""
-    from . import scenarios as _sc
-
-    L, NC, NS = conf.pl_size, len(names), len(starts)
-    prof = {n: _sc.leader_profile(n, T, conf, amp, period_s) for n in names if n != "gaussian"}
-    leader_h = np.stack([starts[k][1] if n == "gaussian" else prof[n] for n in names for k in range(NS)])
-    x0 = torch.stack([e.x.reshape(L, 4) for e, _, _ in starts]).repeat(NC, 1, 1).contiguous()
-    pa0 = torch.stack([e.prev_a.reshape(L) for e, _, _ in starts]).repeat(NC, 1).contiguous()
-    return leader_h, x0, pa0
-
-
 def _level_tables(conf, levels, seeds, NC, L):
     """The per-case disturbance tables of scenarios x levels x seeds (seeds innermost) on the host: (sigma float32 [K, 3], delay int32
     [K], drop_q uint32 [K], noise_seed uint64 [K], abc float32 [K, L, 24] or None when no level changes the plant), checked by
@@ -241,87 +233,112 @@ def _upload(a, dev, as_type=None):
     return torch.from_numpy(a if as_type is None else a.view(as_type)).to(dev)
 
 
-class CaseBatch:
-    """The device inputs of one avd_eval_cases_f32 launch (prepare_cases); ``launch()`` enqueues it on the current stream,
-    ``results()`` reads counters and metrics back. run_cases = prepare_cases + launch + results. ``block`` is the number of cases per
-    workgroup the kernel uses for this batch (avd_eval_cases_block)."""
+class _Suite:
+    """The cases of a scenario suite, built once for whichever batch runs them: scenarios x seeds -- with ``levels`` (Disturbances,
+    scenarios.NOMINAL first) scenarios x levels x seeds -- seeds innermost. A case's start state is its seed's, drawn as ``run`` draws
+    it and always the nominal configuration's; its leader row is its scenario's (gaussian: its seed's). Fields: ``scenarios``,
+    ``seeds``, ``levels`` (or None), the counts ``NC``, ``ND`` (None without levels), ``NS``, ``K`` cases, ``T`` steps, ``L``, ``env``;
+    ``leader_h`` float32 [K, T] on the host; on the device ``leader``, ``x0`` [K, L, 4], ``pa0`` [K, L] and the level tables ``sigma``,
+    ``delay``, ``drop_q``, ``noise_seed``, ``abc`` of _level_tables (all None without levels; abc None when no level changes the plant: the
+    constants block's matrices for every case), ``sigma_h`` ... their host copies."""
 
-    def __init__(self, conf, actors, platoons, scenarios, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override, base_law=None):
-        from . import _hip
+    def __init__(self, conf, scenarios, levels, seeds, amp, period_s, manual_timestep_override, no_seed):
         from . import scenarios as _sc
 
-        platoons = [int(p) for p in platoons]
         names = _sc.check_names(scenarios)
         seeds = [int(conf.evaluation_seed)] if seeds is None else [int(s) for s in seeds]
-        if not platoons or not seeds:
-            raise ValueError("run_cases needs at least one platoon and one seed")
+        if not seeds:
+            raise ValueError(no_seed)
         if len(set(seeds)) != len(seeds):
             raise ValueError(f"seeds {seeds}: a seed is listed more than once")
         T = get_number_of_timesteps_for_plot(conf, manual_timestep_override)
         amp, period_s = _sc.check_knobs(T, amp, period_s)
-        NP, NS, NC = len(platoons), len(seeds), len(names)
-        saved = np.random.get_state()
-        try:
-            starts = [_start(conf, True, manual_timestep_override, evaluation_seed=sd) for sd in seeds]
-        finally:
-            np.random.set_state(saved)
+        starts = _starts(conf, seeds, manual_timestep_override)
         env = starts[0][0]
-        L, M = conf.pl_size, env.num_models
-        lay = actors.lay
-        if (lay.S, lay.A) != (env.num_states, env.num_actions):
-            raise ValueError(f"actors have S={lay.S} A={lay.A}, the platoon needs S={env.num_states} A={env.num_actions}")
-        shared = set_mod is not None and set_mod != 0
-        if shared and set_mod != M:
-            raise ValueError(f"set_mod={set_mod}: run_cases addresses per-agent sets (None / 0) or shared sets (set_mod = M = {M})")
-        if not shared and min(platoons) < 0:
-            raise ValueError("negative platoon index")
-        if set_bases is not None:
-            set_bases = [int(b) for b in set_bases]
-            if not shared or len(set_bases) != NP or min(set_bases) < 0:
-                raise ValueError(f"set_bases={set_bases}: shared sets only (set_mod = M), one non-negative base per platoon entry")
-        need = (M + (max(set_bases) if set_bases else 0)) if shared else (max(platoons) + 1) * M
-        if need > actors.n_sets:
-            raise ValueError(f"platoons {platoons} need {need} weight sets, the group holds {actors.n_sets}")
-        # groups: shared sets ONE (every platoon's result is the same) -- or, with set_bases, one per entry; per-agent sets one per platoon
-        per_entry = not shared or set_bases is not None
-        bases = [0] if not per_entry else (set_bases if shared else [p * M for p in platoons])
-        self.group = (lambda i: i) if per_entry else (lambda i: 0)
-        self.G, self.K = len(bases), NC * NS
-        dev = env.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.conf, self.actors, self.env, self.T, self.L, self.M, self.NP, self.NS, self.NC = conf, actors, env, T, L, M, NP, NS, NC
-        self.scenarios, self.seeds = names, seeds
-        self.leader_h, self.x0, self.pa0 = _case_tables(conf, names, starts, T, amp, period_s)
+        dev, L, NC, NS = env.device, conf.pl_size, len(names), len(seeds)
+        rep = 1 if levels is None else len(levels)  # a (scenario, seed)'s cases
+        self.scenarios, self.seeds, self.levels, self.env = names, seeds, levels, env
+        self.L, self.T, self.NC, self.ND, self.NS, self.K = L, T, NC, (None if levels is None else rep), NS, NC * rep * NS
+        prof = {n: _sc.leader_profile(n, T, conf, amp, period_s) for n in names if n != "gaussian"}
+        self.leader_h = np.stack([starts[k][1] if n == "gaussian" else prof[n] for n in names for _ in range(rep) for k in range(NS)])
         self.leader = torch.from_numpy(self.leader_h).to(dev)
-        self.set_base = torch.tensor(bases, dtype=torch.int32, device=dev)
-        self.counters = torch.empty(self.G, self.K, M, **f32)
-        self.metrics = torch.empty(self.G, self.K, L, _hip.AVD_EVAL_NMETRIC, **f32)
-        self.block = int(_hip.lib().avd_eval_cases_block(self.K, L))
-        self.gains, self.res_scale = _base_gains(base_law, conf, dev)
+        self.x0 = torch.stack([e.x.reshape(L, 4) for e, _, _ in starts]).repeat(NC * rep, 1, 1).contiguous()
+        self.pa0 = torch.stack([e.prev_a.reshape(L) for e, _, _ in starts]).repeat(NC * rep, 1).contiguous()
+        self.sigma_h = self.delay_h = self.drop_q_h = self.noise_seed_h = self.abc_h = None
+        self.sigma = self.delay = self.drop_q = self.noise_seed = self.abc = None
+        if levels is not None:  # host-checked: the kernels read them from device memory
+            self.sigma_h, self.delay_h, self.drop_q_h, self.noise_seed_h, self.abc_h = _level_tables(conf, levels, seeds, NC, L)
+            self.sigma, self.delay = _upload(self.sigma_h, dev), _upload(self.delay_h, dev)
+            self.drop_q, self.noise_seed = _upload(self.drop_q_h, dev, np.int32), _upload(self.noise_seed_h, dev, np.int64)
+            self.abc = None if self.abc_h is None else _upload(self.abc_h, dev)
+
+    def outputs(self, G, width, metrics=True):
+        """-> (counters [G, K, width], metrics [G, K, L, AVD_EVAL_NMETRIC] or None) for G groups, uninitialised, on the device."""
+        from . import _hip
+
+        f32 = dict(dtype=torch.float32, device=self.env.device)
+        return torch.empty(G, self.K, width, **f32), (torch.empty(G, self.K, self.L, _hip.AVD_EVAL_NMETRIC, **f32) if metrics else None)
+
+
+def _case_results(b, sel=slice(None)):
+    """A launched case batch's read-back: counters -> scores rounded row by row, as run (:145) -> the groups ``sel`` -> the metric dict
+    -> a CaseResults, or with levels a DisturbedResults."""
+    from . import scenarios as _sc
+
+    W = b.counters.shape[-1]
+    c = b.counters.cpu().numpy().reshape(b.G * b.K, W)
+    rows = np.array([round(np.average(r), 3) for r in c], dtype=np.float32)
+    shape = (b.G, b.NC, b.NS) if b.levels is None else (b.G, b.NC, b.ND, b.NS)
+    m = b.metrics.cpu().numpy().reshape(*shape, b.L, -1)[sel]
+    metrics = {n: np.ascontiguousarray(m[..., j]) for j, n in enumerate(_sc.METRICS)}
+    scores, cnt = rows.reshape(shape)[sel], c.reshape(*shape, W)[sel]
+    if b.levels is None:
+        return CaseResults(b.scenarios, b.seeds, b.T, scores, cnt, metrics)
+    return DisturbedResults(b.scenarios, [d.name for d in b.levels], b.seeds, b.T, scores, cnt, metrics)
+
+
+class CaseBatch:
+    """The device inputs of one avd_eval_cases_f32 launch (prepare_cases); ``launch()`` enqueues it on the current stream,
+    ``results()`` reads counters and metrics back. run_cases = prepare_cases + launch + results. ``block`` is the number of cases per
+    workgroup the kernel uses for this batch (avd_eval_cases_block; with ``levels``, DisturbedBatch's, avd_eval_cases_dist_block). The
+    cases and their tables are a _Suite's fields."""
+
+    def __init__(self, conf, actors, platoons, scenarios, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override, base_law=None,
+                 levels=None):
+        from . import _hip
+
+        platoons = [int(p) for p in platoons]
+        no_entry = "run_cases needs at least one platoon and one seed"
+        if not platoons:
+            raise ValueError(no_entry)
+        suite = _Suite(conf, scenarios, levels, seeds, amp, period_s, manual_timestep_override, no_entry)
+        vars(self).update(vars(suite))
+        # groups: ONE result for all platoons, or one per entry (_address_sets)
+        _, per_entry, bases = _address_sets("run_cases", actors, self.env, platoons, set_mod, set_bases)
+        self.group = (lambda i: i) if per_entry else (lambda i: 0)
+        self.conf, self.actors, self.M, self.NP, self.G = conf, actors, self.env.num_models, len(platoons), len(bases)
+        self.set_base = torch.tensor(bases, dtype=torch.int32, device=self.env.device)
+        self.counters, self.metrics = suite.outputs(self.G, self.M)
+        self.block = int((_hip.lib().avd_eval_cases_block if levels is None else _hip.lib().avd_eval_cases_dist_block)(self.K, self.L))
+        self.gains, self.res_scale = _base_gains(base_law, conf, self.env.device)
 
     def launch(self):
         a, c = self.actors, self.conf
-        if self.gains is not None:  # a residual policy (avd_eval_cases_res_f32, no disturbance tables)
-            call("avd_eval_cases_res_f32", a._layp, ptr(self.env.d_consts), self.G, self.K, self.L, self.M, self.T, ptr(a.theta),
-                 ptr(a.stats), a.n_sets, ptr(self.set_base), ptr(self.x0), ptr(self.pa0), ptr(self.leader), a.high, c.action_low,
-                 c.action_high, c.sample_rate, None, None, None, None, None, ptr(self.gains), self.res_scale, ptr(self.counters),
-                 ptr(self.metrics), stream_handle())
-            return
-        call("avd_eval_cases_f32", a._layp, ptr(self.env.d_consts), self.G, self.K, self.L, self.M, self.T, ptr(a.theta), ptr(a.stats),
-             a.n_sets, ptr(self.set_base), ptr(self.x0), ptr(self.pa0), ptr(self.leader), a.high, c.action_low, c.action_high,
-             c.sample_rate, ptr(self.counters), ptr(self.metrics), stream_handle())
+        common = (a._layp, ptr(self.env.d_consts), self.G, self.K, self.L, self.M, self.T, ptr(a.theta), ptr(a.stats), a.n_sets,
+                  ptr(self.set_base), ptr(self.x0), ptr(self.pa0), ptr(self.leader), a.high, c.action_low, c.action_high, c.sample_rate)
+        tables = (ptr(self.sigma), ptr(self.delay), ptr(self.drop_q), ptr(self.noise_seed), ptr(self.abc))  # null without levels
+        out = (ptr(self.counters), ptr(self.metrics), stream_handle())
+        if self.gains is not None:  # a residual policy: the law acts on what the vehicle observes
+            call("avd_eval_cases_res_f32", *common, *tables, ptr(self.gains), self.res_scale, *out)
+        elif self.levels is not None:
+            call("avd_eval_cases_dist_f32", *common, *tables, *out)
+        else:
+            call("avd_eval_cases_f32", *common, *out)
 
     def results(self):
-        from . import scenarios as _sc
+        return _case_results(self, [self.group(i) for i in range(self.NP)])
 
-        c = self.counters.cpu().numpy().reshape(self.G * self.K, self.M)
-        rows = np.array([round(np.average(r), 3) for r in c], dtype=np.float32)  # row by row, as run (:145)
-        sel = [self.group(i) for i in range(self.NP)]
-        scores = rows.reshape(self.G, self.NC, self.NS)[sel]
-        cnt = c.reshape(self.G, self.NC, self.NS, self.M)[sel]
-        m = self.metrics.cpu().numpy().reshape(self.G, self.NC, self.NS, self.L, -1)[sel]
-        metrics = {n: np.ascontiguousarray(m[..., j]) for j, n in enumerate(_sc.METRICS)}
-        return CaseResults(self.scenarios, self.seeds, self.T, scores, cnt, metrics)
+
 
 
 def prepare_cases(conf, actors, platoons, scenarios=("gaussian",), seeds=None, amp=None, period_s=10.0, set_mod=None, set_bases=None,
@@ -371,58 +388,15 @@ class DisturbedResults:
 
 
 class DisturbedBatch(CaseBatch):
-    """The device inputs of one avd_eval_cases_dist_f32 launch (prepare_disturbed): CaseBatch's cases with a disturbance axis between
-    scenario and seed, and the per-case disturbance tables. ``levels`` are the Disturbances, scenarios.NOMINAL first."""
+    """The device inputs of one avd_eval_cases_dist_f32 launch (prepare_disturbed): CaseBatch with ``levels`` -- a disturbance axis
+    between scenario and seed, and the per-case disturbance tables. ``levels`` are the Disturbances, scenarios.NOMINAL first."""
 
     def __init__(self, conf, actors, platoons, scenarios, disturbances, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override,
                  base_law=None):
-        from . import _hip
         from . import scenarios as _sc
 
         levels = [_sc.NOMINAL] + _sc.check_disturbances(disturbances, conf)
-        super().__init__(conf, actors, platoons, scenarios, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override, base_law)
-        NC, ND, NS, L, dev = self.NC, len(levels), self.NS, self.L, self.x0.device
-        self.levels, self.ND, self.K = levels, ND, NC * ND * NS
-        # cases: scenarios x levels x seeds, seeds innermost; a case's start state and leader row are its (scenario, seed)'s, always
-        # the nominal configuration's
-        widen = lambda x: x.reshape(NC, 1, NS, *x.shape[1:]).repeat_interleave(ND, dim=1).reshape(self.K, *x.shape[1:]).contiguous()
-        self.leader_h = np.repeat(self.leader_h.reshape(NC, 1, NS, -1), ND, axis=1).reshape(self.K, -1)
-        self.x0, self.pa0, self.leader = widen(self.x0), widen(self.pa0), widen(self.leader)
-        # the tables, host-checked (the kernel reads them from device memory); the true plants: a table only when a level changes the
-        # plant (null: the constants block's matrices for every case)
-        self.sigma_h, self.delay_h, self.drop_q_h, self.noise_seed_h, abc_h = _level_tables(conf, levels, self.seeds, NC, L)
-        self.sigma, self.delay = _upload(self.sigma_h, dev), _upload(self.delay_h, dev)
-        self.drop_q, self.noise_seed = _upload(self.drop_q_h, dev, np.int32), _upload(self.noise_seed_h, dev, np.int64)
-        self.abc = None if abc_h is None else _upload(abc_h, dev)
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.counters = torch.empty(self.G, self.K, self.M, **f32)
-        self.metrics = torch.empty(self.G, self.K, L, _hip.AVD_EVAL_NMETRIC, **f32)
-        self.block = int(_hip.lib().avd_eval_cases_dist_block(self.K, L))
-
-    def launch(self):
-        a, c = self.actors, self.conf
-        if self.gains is not None:  # a residual policy: the law acts on the observation (avd_eval_cases_res_f32 with the tables)
-            call("avd_eval_cases_res_f32", a._layp, ptr(self.env.d_consts), self.G, self.K, self.L, self.M, self.T, ptr(a.theta),
-                 ptr(a.stats), a.n_sets, ptr(self.set_base), ptr(self.x0), ptr(self.pa0), ptr(self.leader), a.high, c.action_low,
-                 c.action_high, c.sample_rate, ptr(self.sigma), ptr(self.delay), ptr(self.drop_q), ptr(self.noise_seed), ptr(self.abc),
-                 ptr(self.gains), self.res_scale, ptr(self.counters), ptr(self.metrics), stream_handle())
-            return
-        call("avd_eval_cases_dist_f32", a._layp, ptr(self.env.d_consts), self.G, self.K, self.L, self.M, self.T, ptr(a.theta),
-             ptr(a.stats), a.n_sets, ptr(self.set_base), ptr(self.x0), ptr(self.pa0), ptr(self.leader), a.high, c.action_low,
-             c.action_high, c.sample_rate, ptr(self.sigma), ptr(self.delay), ptr(self.drop_q), ptr(self.noise_seed), ptr(self.abc),
-             ptr(self.counters), ptr(self.metrics), stream_handle())
-
-    def results(self):
-        from . import scenarios as _sc
-
-        c = self.counters.cpu().numpy().reshape(self.G * self.K, self.M)
-        rows = np.array([round(np.average(r), 3) for r in c], dtype=np.float32)  # row by row, as run (:145)
-        sel = [self.group(i) for i in range(self.NP)]
-        shape = (self.G, self.NC, self.ND, self.NS)
-        m = self.metrics.cpu().numpy().reshape(*shape, self.L, -1)[sel]
-        metrics = {n: np.ascontiguousarray(m[..., j]) for j, n in enumerate(_sc.METRICS)}
-        return DisturbedResults(self.scenarios, [d.name for d in self.levels], self.seeds, self.T, rows.reshape(shape)[sel],
-                                c.reshape(*shape, self.M)[sel], metrics)
+        super().__init__(conf, actors, platoons, scenarios, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override, base_law, levels)
 
 
 def prepare_disturbed(conf, actors, platoons, scenarios=("gaussian",), disturbances=(), seeds=None, amp=None, period_s=10.0, set_mod=None,
@@ -450,59 +424,25 @@ def run_disturbed(conf, actors, platoons, scenarios=("gaussian",), disturbances=
 
 class LinearBatch:
     """The device inputs of one avd_eval_linear_f32 launch (prepare_linear, tune_linear): G gain sets ``gains`` float32 [G, L, 4] over the
-    cases CaseBatch (no disturbances) or DisturbedBatch builds -- same ``_start``, same leader profiles, same level tables, seeds
-    innermost. ``launch()`` enqueues it on the current stream, ``results()`` reads counters and metrics back (first axis: the gain
+    cases of CaseBatch (no disturbances) or DisturbedBatch: the same _Suite. ``launch()`` enqueues it on the current stream, ``results()`` reads counters and metrics back (first axis: the gain
     sets). ``metrics=False`` passes the kernel a null metrics pointer. The raw form: under Model A the kernel does not read a row's 4th
     gain (prepare_linear and tune_linear refuse a non-zero one)."""
 
     def __init__(self, conf, gains, scenarios, disturbances, seeds, amp, period_s, manual_timestep_override, metrics=True):
-        from . import _hip
         from . import scenarios as _sc
 
         if conf.framework == conf.cntrl:
             raise ValueError("a linear baseline is a per-vehicle law: not available for the centralized framework")
-        names = _sc.check_names(scenarios)
-        seeds = [int(conf.evaluation_seed)] if seeds is None else [int(s) for s in seeds]
-        if not seeds:
-            raise ValueError("run_linear needs at least one seed")
-        if len(set(seeds)) != len(seeds):
-            raise ValueError(f"seeds {seeds}: a seed is listed more than once")
         disturbances = list(disturbances)
         levels = [_sc.NOMINAL] + _sc.check_disturbances(disturbances, conf) if disturbances else None
-        T = get_number_of_timesteps_for_plot(conf, manual_timestep_override)
-        amp, period_s = _sc.check_knobs(T, amp, period_s)
-        L = conf.pl_size
         gains = np.ascontiguousarray(np.asarray(gains, dtype=np.float32))
-        if gains.ndim != 3 or gains.shape[0] < 1 or gains.shape[1:] != (L, 4) or not np.isfinite(gains).all():
-            raise ValueError(f"gains of shape {gains.shape}: need finite [G >= 1, L = {L}, 4]")
-        saved = np.random.get_state()
-        try:
-            starts = [_start(conf, True, manual_timestep_override, evaluation_seed=sd) for sd in seeds]
-        finally:
-            np.random.set_state(saved)
-        env = starts[0][0]
-        dev = env.device
-        NC, NS = len(names), len(seeds)
-        self.conf, self.env, self.T, self.L, self.NS, self.NC = conf, env, T, L, NS, NC
-        self.scenarios, self.seeds, self.levels, self.ND = names, seeds, levels, (len(levels) if levels else None)
-        self.G, self.K = gains.shape[0], NC * NS
-        self.gains_h, self.gains = gains, torch.from_numpy(gains).to(dev)
-        self.leader_h, self.x0, self.pa0 = _case_tables(conf, names, starts, T, amp, period_s)
-        self.leader = torch.from_numpy(self.leader_h).to(dev)
-        self.sigma = self.delay = self.drop_q = self.noise_seed = self.abc = None
-        if levels:  # cases: scenarios x levels x seeds, as DisturbedBatch widens them
-            ND = self.ND
-            self.K = NC * ND * NS
-            widen = lambda x: x.reshape(NC, 1, NS, *x.shape[1:]).repeat_interleave(ND, dim=1).reshape(self.K, *x.shape[1:]).contiguous()
-            self.leader_h = np.repeat(self.leader_h.reshape(NC, 1, NS, -1), ND, axis=1).reshape(self.K, -1)
-            self.x0, self.pa0, self.leader = widen(self.x0), widen(self.pa0), widen(self.leader)
-            sigma, delay, drop_q, noise_seed, abc = _level_tables(conf, levels, seeds, NC, L)
-            self.sigma, self.delay = _upload(sigma, dev), _upload(delay, dev)
-            self.drop_q, self.noise_seed = _upload(drop_q, dev, np.int32), _upload(noise_seed, dev, np.int64)
-            self.abc = None if abc is None else _upload(abc, dev)
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.counters = torch.empty(self.G, self.K, L, **f32)
-        self.metrics = torch.empty(self.G, self.K, L, _hip.AVD_EVAL_NMETRIC, **f32) if metrics else None
+        if gains.ndim != 3 or gains.shape[0] < 1 or gains.shape[1:] != (conf.pl_size, 4) or not np.isfinite(gains).all():
+            raise ValueError(f"gains of shape {gains.shape}: need finite [G >= 1, L = {conf.pl_size}, 4]")
+        suite = _Suite(conf, scenarios, levels, seeds, amp, period_s, manual_timestep_override, "run_linear needs at least one seed")
+        vars(self).update(vars(suite))
+        self.conf, self.G = conf, gains.shape[0]
+        self.gains_h, self.gains = gains, torch.from_numpy(gains).to(self.env.device)
+        self.counters, self.metrics = suite.outputs(self.G, self.L, metrics)
 
     def launch(self):
         c = self.conf
@@ -523,19 +463,9 @@ class LinearBatch:
         return self.enqueue_fitness().cpu().numpy()
 
     def results(self):
-        from . import scenarios as _sc
-
         if self.metrics is None:
             raise ValueError("this batch was prepared without metrics (tune_linear): read fitness()")
-        c = self.counters.cpu().numpy().reshape(self.G * self.K, self.L)
-        rows = np.array([round(np.average(r), 3) for r in c], dtype=np.float32)  # row by row, as run (:145)
-        shape = (self.G, self.NC, self.NS) if self.levels is None else (self.G, self.NC, self.ND, self.NS)
-        m = self.metrics.cpu().numpy().reshape(*shape, self.L, -1)
-        metrics = {n: np.ascontiguousarray(m[..., j]) for j, n in enumerate(_sc.METRICS)}
-        if self.levels is None:
-            return CaseResults(self.scenarios, self.seeds, self.T, rows.reshape(shape), c.reshape(*shape, self.L), metrics)
-        return DisturbedResults(self.scenarios, [d.name for d in self.levels], self.seeds, self.T, rows.reshape(shape),
-                                c.reshape(*shape, self.L), metrics)
+        return _case_results(self)
 
 
 def prepare_linear(conf, laws, scenarios=("gaussian",), disturbances=(), seeds=None, amp=None, period_s=10.0, manual_timestep_override=None):

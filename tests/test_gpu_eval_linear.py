@@ -64,6 +64,37 @@ def test_zero_gains_equal_the_disturbed_evaluator_on_actors_with_a_zero_last_lay
     _same_results(plain, ref.nominal(), "nominal")
 
 
+def test_every_batch_class_builds_the_same_case_tables_and_outputs_of_its_own_size():
+    """One suite, T = 40 past the 16-slot ring, one level with every axis on: LinearBatch, DisturbedBatch and CaseBatch hold the same
+    tables case for case, and each allocates counters and metrics for its own K. No rollout is launched."""
+    need_gpu()
+    L, names, seeds, T = 3, ("gaussian", "step"), (1, 2), 40
+    conf = config.Config(pl_size=L)
+    full = Disturbance("full", noise_ep=0.05, noise_ev=0.04, noise_a=0.02, v2v_delay=15, v2v_drop=0.3, dyn_coeff=0.15)
+    grp = _group(conf, 2 * L, 4, 1, seed=77)
+    gains = np.zeros((5, L, 4), dtype=np.float32)
+    cases = evaluator.prepare_cases(conf, grp, [0, 1], names, seeds=seeds, manual_timestep_override=T)
+    dist = evaluator.prepare_disturbed(conf, grp, [0, 1], names, [full], seeds=seeds, manual_timestep_override=T)
+    lin = evaluator.LinearBatch(conf, gains, names, [full], seeds, None, 10.0, T)
+    plain = evaluator.LinearBatch(conf, gains, names, [], seeds, None, 10.0, T)
+    tables = ("x0", "pa0", "leader", "sigma", "delay", "drop_q", "noise_seed", "abc")
+    assert (cases.K, dist.K, lin.K, plain.K) == (4, 8, 8, 4) and (dist.ND, lin.ND) == (2, 2)
+    for n in tables:
+        assert torch.equal(getattr(lin, n), getattr(dist, n)), n
+    assert np.array_equal(lin.leader_h, dist.leader_h) and np.array_equal(plain.leader_h, cases.leader_h)
+    assert float(dist.sigma.min()) == 0.0 < float(dist.sigma.max()) and int(dist.delay.max()) == 15 and dist.abc.shape == (8, L, 24)
+    assert 0 < int(dist.drop_q.max()) < 1 << 24
+    for n in tables[:3]:
+        assert torch.equal(getattr(plain, n), getattr(cases, n)), n
+        wide = getattr(dist, n).reshape(2, 2, 2, *getattr(dist, n).shape[1:])  # [scenario, level, seed, ...]
+        assert torch.equal(wide[:, 0].reshape(getattr(cases, n).shape), getattr(cases, n)), n
+    for n in tables[3:]:
+        assert getattr(plain, n) is None, n
+    for b in (cases, dist, lin, plain):  # (decentralized: one counter per vehicle)
+        assert tuple(b.counters.shape) == (b.G, b.K, L) and tuple(b.metrics.shape) == (b.G, b.K, L, _hip.AVD_EVAL_NMETRIC)
+    assert (cases.G, dist.G, lin.G, plain.G) == (2, 2, 5, 5)
+
+
 # ---- 2. the float64 oracle ---------------------------------------------------------------------------------------------------------------
 
 def _table(kind, L):
