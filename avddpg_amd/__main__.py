@@ -115,6 +115,15 @@ def _scenario_flags(p, where):
                         "seed, per_vehicle, over (nominal: the fitness is over the undisturbed cases; all: over the --disturb levels "
                         "too), e.g. kp=0:3,kv=0:4,ka=-1:0,kf=0:1,pop=1024,gens=30. With --baseline_tune the search starts from the "
                         "grid's pick (not in the reference CLI)")
+    p.add_argument("--freq_response", type=str, default=argparse.SUPPRESS, metavar="SPEC",
+                   help="the frequency response of every platoon's actors: sinusoidal leader inputs at n log-spaced frequencies (Hz, snapped "
+                        "to whole cycles in the measuring window) x --eval_seeds x every --disturb level in ONE launch, the single-bin "
+                        "Fourier sums reduced on the device, and the same for every --baseline / tuned / searched law; writes "
+                        "frequency.csv -- one row per (controller, disturbance, seed, frequency, vehicle) with the amplitudes and phases of "
+                        "ep, ev, a, w, u, the vehicle-to-vehicle gains gain_a and gain_ep, and for laws the float64 theory's gain_a -- and "
+                        "conf.json's frequency_suite with the peak gain per controller and level (string stable: every peak <= 1). "
+                        "Independent of --scenarios (--eval_seeds, --disturb and --baseline are then accepted without it). SPEC: "
+                        "fmin=0.02,fmax=2,n=16[,amp=A,settle=0.5,steps=N] (not in the reference CLI)")
 
 
 def _check_scenario_flags(ap, args):
@@ -123,15 +132,25 @@ def _check_scenario_flags(ap, args):
 
     from .scenarios import check_names
 
+    if _freq(args) is not None:
+        from .scenarios import parse_frequency
+
+        try:  # (the window's length needs the run's configuration unless steps is given: _check_freq_conf)
+            args.freq_response = parse_frequency(args.freq_response)
+        except ValueError as e:
+            ap.error(f"--freq_response: {e}")
     if args.scenarios is None:
+        shared = ("eval_seeds", "disturb", "baseline") if _freq(args) is not None else ()  # what --freq_response uses too
         for flag in ("eval_seeds", "scenario_amp", "scenario_period", "disturb", "baseline", "baseline_tune", "baseline_search"):
-            if getattr(args, flag, None) is not None:
+            if getattr(args, flag, None) is not None and flag not in shared:
                 ap.error(f"--{flag} needs --scenarios")
-        return
-    try:
-        args.scenarios = check_names([n.strip() for n in args.scenarios.split(",")])
-    except ValueError as e:
-        ap.error(f"--scenarios: {e}")
+        if _freq(args) is None:
+            return
+    else:
+        try:
+            args.scenarios = check_names([n.strip() for n in args.scenarios.split(",")])
+        except ValueError as e:
+            ap.error(f"--scenarios: {e}")
     if args.eval_seeds is not None:
         try:
             args.eval_seeds = parse_seeds(args.eval_seeds)
@@ -175,12 +194,19 @@ def _check_scenario_flags(ap, args):
                 ap.error(f"--baseline_tune: {e}")
     if args.mode == "tr" and int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
         # (one of the two choices: refused, rather than every rank writing a scenarios.csv of its own platoons)
+        if args.scenarios is None:
+            ap.error("--freq_response is not available under a process group of more than one rank (frequency.csv is not gathered across ranks)")
         ap.error("--scenarios is not available under a process group of more than one rank (scenarios.csv is not gathered across ranks)")
 
 
 def _disturb(args):
     """The --disturb levels (checked Disturbances), or None without the flag."""
     return getattr(args, "disturb", None)
+
+
+def _freq(args):
+    """--freq_response's FrequencySpec (its text before _check_scenario_flags), or None without the flag."""
+    return getattr(args, "freq_response", None)
 
 
 def _exit(msg):
@@ -218,6 +244,91 @@ def _check_baseline_conf(args, conf, refuse):
             _sc.check_search(_search_flag(args), conf)
         except ValueError as e:
             refuse(f"--baseline_search: {e}")
+
+
+def _check_freq_conf(args, conf, refuse):
+    """The --freq_response refusals that need the run's configuration: the window's length, a V2V level under Model A."""
+    if _freq(args) is None:
+        return
+    from . import scenarios as _sc
+
+    try:
+        _sc.check_frequency(_freq(args), conf)
+        _sc.check_disturbances(_disturb(args) or [], conf)
+    except ValueError as e:
+        refuse(f"--freq_response: {e}")
+
+
+class _Frequency:
+    """What --freq_response computes beside the actors' response, once per run: the laws' (--baseline, and with --scenarios the `tuned`
+    and `searched` laws) in one launch of the linear frequency evaluator, with the float64 theory of each law and level.
+    ``write(d, conf, actors, tags)`` puts frequency.csv into a directory and frequency_suite into its Config."""
+
+    def __init__(self, conf, args, baselines=None):
+        import numpy as np
+
+        from . import evaluator
+        from . import scenarios as _sc
+
+        self.spec, self.levels, self.seeds = _freq(args), _disturb(args) or [], args.eval_seeds
+        laws = baselines.laws if baselines is not None else (_baseline_flags(args) or ([], None))[0]
+        self.laws = None
+        if laws:
+            try:
+                res = evaluator.run_linear_frequency(conf, laws, self.spec, self.levels, self.seeds)
+            except ValueError as e:
+                raise SystemExit(f"--freq_response: {e}")
+            theory = np.stack([np.stack([_sc.linear_frequency_response(conf, b.gains(conf.pl_size), res.cycles, res.W, lv.dyn_coeff)["gain_a"]
+                                         for lv in [_sc.NOMINAL] + list(self.levels)]) for b in laws])  # [G, ND, F, L]
+            self.laws = (res, [b.name for b in laws], theory)
+
+    def actors(self, vt, agents=None):
+        """The trainer's actors over the same sweep, one launch ([P, ...]; a seed batch or sweep: [E, P, ...])."""
+        try:
+            return vt.evaluate_frequency(self.spec, self.levels, self.seeds, agents=agents)
+        except ValueError as e:
+            raise SystemExit(f"--freq_response: {e}")
+
+    def entries(self, actors, tags):
+        return [(actors, [str(t) for t in tags], None)] + ([self.laws] if self.laws is not None else [])
+
+    def record(self, actors, tags):
+        """conf.json's frequency_suite, a list of pairs (conf.json keeps lists, not dicts)."""
+        from . import scenarios as _sc
+
+        peaks = [row for res, names, _ in self.entries(actors, tags) for row in _sc.frequency_peaks(res, names)]
+        return [["spec", self.spec.items()], ["freqs_hz", [float(f) for f in actors.freqs_hz]], ["cycles", [int(c) for c in actors.cycles]],
+                ["window", int(actors.W)], ["seeds", [int(k) for k in actors.seeds]], ["disturbances", list(actors.disturbances)],
+                ["peaks", [["controller", "disturbance", "peak_gain_a", "freq_hz", "vehicle", "string_stable"]] + peaks]]
+
+    def write(self, d, conf, actors, tags):
+        from . import scenarios as _sc
+
+        _sc.write_frequency_csv(os.path.join(d, "frequency.csv"), self.entries(actors, tags))
+        conf.frequency_suite = self.record(actors, tags)
+
+    def report(self, actors, tags):
+        from . import scenarios as _sc
+
+        lines = _sc.frequency_report_lines(actors, [str(t) for t in tags])
+        return lines if self.laws is None else lines + _sc.frequency_report_lines(self.laws[0], self.laws[1], "baseline")
+
+
+def _frequency(conf, args):
+    """The run's frequency section (None without the flag), computed once; the laws are the baseline section's when --scenarios made one."""
+    if _freq(args) is None:
+        return None
+    if getattr(args, "frequency", None) is None:
+        args.frequency = _Frequency(conf, args, _baselines(conf, args) if args.scenarios is not None and _baseline_flags(args) is not None else None)
+    return args.frequency
+
+
+def _freq_slice(res, e):
+    """Experiment e's FrequencyResults of a batch's ([E, P, ...] arrays)."""
+    from .evaluator import FrequencyResults
+
+    return FrequencyResults(res.freqs_hz, res.cycles, res.W, res.T, res.disturbances, res.seeds, res.spectrum[e], res.scores[e],
+                            res.counters[e], {k: v[e] for k, v in res.metrics.items()})
 
 
 class _Baselines:
@@ -417,6 +528,7 @@ class _KeepResults:
         if args.scenarios is not None:
             kw = dict(agents=self.agents, **_suite(args))
             self.suite = vt.evaluate_scenarios(**kw) if _disturb(args) is None else vt.evaluate_robustness(disturbances=_disturb(args), **kw)
+        self.freq = None if _freq(args) is None else _frequency(vt.conf, args).actors(vt, self.agents)
 
     def write(self, d, conf, n_save, e=None):
         """<d>/best/ and <d>/best.csv of a run (e None) or of experiment e of a batch, and conf.keep_best. conf: the directory's Config as
@@ -429,11 +541,12 @@ class _KeepResults:
 
         vt, args = self.vt, self.args
         if e is None:
-            units, sims, agents, suite, P = range(len(self.score)), self.sims, self.agents, self.suite, vt.P
+            units, sims, agents, suite, freq, P = range(len(self.score)), self.sims, self.agents, self.suite, self.freq, vt.P
         else:
             units = [e] if vt.shared else range(e * vt.P_exp, (e + 1) * vt.P_exp)
             sims, agents, P = self.sims[e], self.agents.experiment_view(e, vt.E, vt.M, vt.shared), vt.P_exp
             suite = None if self.suite is None else _slice(self.suite, e)
+            freq = None if self.freq is None else _freq_slice(self.freq, e)
         with open(os.path.join(d, "best.csv"), "w") as f:
             f.write("unit,best_step,best_score,final_score\n")
             for i, u in enumerate(units):
@@ -448,6 +561,8 @@ class _KeepResults:
         cb.keep_best = self.record
         if suite is not None:
             _write_suite(bd, cb, suite, range(1, P + 1), args)
+        if freq is not None:
+            _frequency(vt.conf, args).write(bd, cb, freq, range(1, P + 1))
         artifacts.config_writer(os.path.join(bd, "conf.json"), cb)
         conf.keep_best = self.record[:2] + [["best_pl_rew_for_simulation", cb.pl_rew_for_simulation]]
 
@@ -666,6 +781,7 @@ def get_cmdl_args(argv, conf):
     conf = set_args_to_config(args, conf)
     if args.mode == "tr":  # (esim checks against the configuration it loads)
         _check_baseline_conf(args, conf, ap.error)
+        _check_freq_conf(args, conf, ap.error)
     return args, conf
 
 
@@ -783,6 +899,8 @@ def main(argv=None, conf=None):
             _write_suite(base, conf, res, range(1, vt.P + 1), args)
             if _baseline_flags(args) is not None:
                 _baselines(conf, args).write(base, conf, res)
+        if _freq(args) is not None:  # the same platoons and laws over the frequency sweep, one launch each
+            _frequency(conf, args).write(base, conf, _frequency(conf, args).actors(vt), range(1, vt.P + 1))
         n_save = vt.P if args.save_platoons is None and args.episodes == "reference" else min(vt.P, 4 if args.save_platoons is None else args.save_platoons)
         artifacts.save_agents(base, vt.agents, n_save, vt.M, shared=vt.shared)
         # what ran, beside the reference's fields: how many platoons' agents the directory holds (esim loops over exactly these),
@@ -811,7 +929,7 @@ def main(argv=None, conf=None):
         import json
         saved = json.load(open(os.path.join(args.exp_path, "conf.json"))).get("saved_platoons", conf.num_platoons)
         law = _saved_residual(args.exp_path)  # (None: the actors alone, today's entry points; read once for every mode below)
-        if args.scenarios is not None:  # ALL saved platoons' actors in one group, one launch
+        if args.scenarios is not None or _freq(args) is not None:  # ALL saved platoons' actors in one group, one launch
             from . import scenarios as _sc
             saved = int(saved)
             grp = vec.AgentGroup(saved * M, shape.num_states, shape.num_actions, conf, hidd_mult=shape.hidden_multiplier)
@@ -821,14 +939,23 @@ def main(argv=None, conf=None):
                 for m in range(M):
                     grp.set_weights((p - 1) * M + m, "actor", artifacts.load_actor_weights(args.exp_path, p, m + 1))
             _check_baseline_conf(args, conf, _exit)
-            full = evaluator.run_cases(conf, grp, range(saved), base_law=law, **_suite(args)) if _disturb(args) is None else \
-                evaluator.run_disturbed(conf, grp, range(saved), disturbances=_disturb(args), base_law=law, **_suite(args))
-            res = _write_suite(args.exp_path, conf, full, range(1, saved + 1), args)  # (conf.json itself is not rewritten)
-            print("\n".join(_sc.report_lines(res, range(1, saved + 1))))
-            if _baseline_flags(args) is not None:
-                base = _Baselines(conf, args)
-                base.write(args.exp_path, conf, full)
-                print("\n".join(base.report()))
+            _check_freq_conf(args, conf, _exit)
+            base = None
+            if args.scenarios is not None:
+                base = _esim_suite(args, conf, grp, saved, law)
+            if _freq(args) is not None:  # frequency.csv, and frequency_suite added to the directory's conf.json (nothing else in it changes)
+                fq = _Frequency(conf, args, base)
+                try:
+                    res = evaluator.run_frequency(conf, grp, range(saved), fq.spec, fq.levels, fq.seeds, base_law=law)
+                except ValueError as e:
+                    raise SystemExit(f"--freq_response: {e}")
+                _sc.write_frequency_csv(os.path.join(args.exp_path, "frequency.csv"), fq.entries(res, range(1, saved + 1)))
+                path = os.path.join(args.exp_path, "conf.json")
+                js = json.load(open(path))
+                js["frequency_suite"] = fq.record(res, range(1, saved + 1))
+                with open(path, "w") as f:
+                    json.dump(js, f)
+                print("\n".join(fq.report(res, range(1, saved + 1))))
             return
         for p in range(1, int(saved) + 1):
             if not os.path.exists(os.path.join(args.exp_path, artifacts.FNAME["actor"] % (p, 1) + ".npz")):
@@ -843,6 +970,24 @@ def main(argv=None, conf=None):
             print(f"platoon {p}: cumulative platoon reward {rew}")
     else:
         raise SystemExit("modes: tr, esim")
+
+
+def _esim_suite(args, conf, grp, saved, law):
+    """esim --scenarios: the saved platoons over the suite, scenarios.csv (robustness.csv, baseline.csv) and the report lines. -> the
+    baseline section, or None without its flags."""
+    from . import evaluator
+    from . import scenarios as _sc
+
+    full = evaluator.run_cases(conf, grp, range(saved), base_law=law, **_suite(args)) if _disturb(args) is None else \
+        evaluator.run_disturbed(conf, grp, range(saved), disturbances=_disturb(args), base_law=law, **_suite(args))
+    res = _write_suite(args.exp_path, conf, full, range(1, saved + 1), args)  # (conf.json itself is not rewritten)
+    print("\n".join(_sc.report_lines(res, range(1, saved + 1))))
+    if _baseline_flags(args) is not None:
+        base = _Baselines(conf, args)
+        base.write(args.exp_path, conf, full)
+        print("\n".join(base.report()))
+        return base
+    return None
 
 
 def train_sweep(args, conf, base):
@@ -966,6 +1111,7 @@ def train_seed_batch(args, conf, base, experiments=None):
     if args.scenarios is not None:
         suite = vt.evaluate_scenarios(**_suite(args)) if _disturb(args) is None else vt.evaluate_robustness(disturbances=_disturb(args), **_suite(args))
     baselines = _baselines(conf, args) if suite is not None and _baseline_flags(args) is not None else None  # computed once
+    freq = None if _freq(args) is None else _frequency(conf, args).actors(vt)  # [E, P, F, dist, seed, ...], one launch
     n_save = min(P, 4 if args.save_platoons is None else args.save_platoons)
     kept = _KeepResults(vt, args) if getattr(args, "keep_best", None) is not None else None
     done = []
@@ -994,6 +1140,8 @@ def train_seed_batch(args, conf, base, experiments=None):
             _write_suite(d, ce, _slice(suite, e), range(1, P + 1), args)
             if baselines is not None:
                 baselines.write(d, ce, _slice(suite, e))
+        if freq is not None:
+            _frequency(conf, args).write(d, ce, _freq_slice(freq, e), range(1, P + 1))
         if kept is not None:  # (after everything else the directory's conf.json records: best/conf.json carries it too)
             kept.write(d, ce, n_save, e)
         artifacts.config_writer(os.path.join(d, "conf.json"), ce)

@@ -14,6 +14,7 @@ if os.environ.get("AVDDPG_HIP_LIB"):  # diagnostics: A/B another build of the sa
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "avddpg_hip.h")
 AVD_MAX_L = 16
 AVD_EVAL_NMETRIC = 8
+AVD_EVAL_NSPEC = 10
 AVD_EVAL_MAX_DELAY = 15
 AVD_TRAIN_MAX_LEVELS = 16
 AVD_TRAIN_MAX_MANOEUVRES = 16
@@ -165,6 +166,9 @@ _PROTOS = {
                                _P, _P],
     "avd_eval_linear_f32": [_P, _i, _i, _i, _i, _P, _P, _P, _P, _f, _f, _f, _P, _P, _P, _P, _P, _P, _P, _P],
     "avd_linear_fitness_f32": [_i, _i, _i, _P, _P, _P],
+    "avd_eval_cases_freq_f32": [_LP, _P, _i, _i, _i, _i, _i, _P, _P, _i, _P, _P, _P, _P, _f, _f, _f, _f, _P, _P, _P, _P, _P, _P, _f, _P,
+                                _P, _P, _P, _P],
+    "avd_eval_linear_freq_f32": [_P, _i, _i, _i, _i, _P, _P, _P, _P, _f, _f, _f, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "avd_search_sample_f32": [_i, _i, _i, _P, _P, _P, _P, _u64, _u64, _P, _P],
     "avd_search_refit_f32": [_i, _i, _i, _i, _f, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _P],
     "avd_gemm_bt_bf16": [_i, _i, _i, _P, C.c_long, _P, C.c_long, _P, C.c_long, _P],

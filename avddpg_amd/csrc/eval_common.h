@@ -127,6 +127,51 @@ struct VehMetrics {
     }
 };
 
+// The evaluator kernels' trailing argument of a frequency sweep (avd_eval_cases_freq_f32, avd_eval_linear_freq_f32): per case and step
+// the pair (c, s) every signal is multiplied with, and where the vehicles' sums go. The window is the table's: a (0, 0) pair adds 0.
+struct FreqArgs {
+    const float* basis;  // [K][T][2], 8-byte aligned
+    float* spectrum;     // [G][K][L][AVD_EVAL_NSPEC]
+};
+
+// A vehicle's single-bin Fourier sums (scenarios.spectrum_from_traces: sequential float32 adds in step order, the product rounded
+// first): (re, im) of the post-step ep, ev, a, w and of the step's plant input u, in that order
+struct VehSpectrum {
+    float s[AVD_EVAL_NSPEC] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+
+    __device__ __forceinline__ void step(float4 xn, float uu, float2 cs) {
+#pragma clang fp contract(off)
+        const float x[5] = {xn.x, xn.y, xn.z, xn.w, uu};
+#pragma unroll
+        for (int i = 0; i < 5; ++i) s[2 * i] = s[2 * i] + x[i] * cs.x, s[2 * i + 1] = s[2 * i + 1] + x[i] * cs.y;
+    }
+    // o: the vehicle's AVD_EVAL_NSPEC floats, `stride` apart: the raw sums (the host scales them)
+    __device__ __forceinline__ void store(float* o, int stride = 1) const {
+#pragma unroll
+        for (int i = 0; i < AVD_EVAL_NSPEC; ++i) o[i * stride] = s[i];
+    }
+    __device__ __forceinline__ void load(const float* o, int stride) {
+#pragma unroll
+        for (int i = 0; i < AVD_EVAL_NSPEC; ++i) s[i] = o[i * stride];
+    }
+    // The sums kept in LDS between steps, slot i of a thread at o[i * stride] (the thread's own words: no barrier), where ten more
+    // live registers across the step would cost a wave per SIMD
+    static __device__ __forceinline__ void step_lds(float* o, int stride, float4 xn, float uu, float2 cs) {
+        VehSpectrum sp;
+        sp.load(o, stride);
+        sp.step(xn, uu, cs);
+        sp.store(o, stride);
+    }
+};
+
+// The frequency entry points' own arguments, checked: both tables non-null, the basis pairs 8-byte aligned (read as float2)
+inline int freq_check(const char* who, const FreqArgs& f) {
+    AVD_REQUIRE(f.basis && ((uintptr_t)f.basis & 7) == 0, "%s: basis=%p (must be a non-null, 8-byte aligned [K][T][2] table)", who,
+                (const void*)f.basis);
+    AVD_REQUIRE(f.spectrum, "%s: null spectrum", who);
+    return AVD_OK;
+}
+
 // The evaluator kernels' trailing argument of a residual policy: the law's gain rows and the residual's authority
 struct ResArgs {
     const float* gains;  // [L][4]: (kp, kv, ka, kf) per vehicle

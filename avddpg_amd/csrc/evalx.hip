@@ -139,12 +139,20 @@ __device__ __forceinline__ void block_dot_rows(const float* xT, const float* __r
     __syncthreads();
 }
 
+// Where a frequency sweep's ten sums per vehicle live between steps: in registers where the instantiation keeps its waves per SIMD with
+// them (the nominal 16-row kernel, whose 53.7 KB of LDS at the reference widths leave no room for 10 KB more beside three workgroups per
+// CU), else in LDS as [AVD_EVAL_NSPEC][RB * AVD_MAX_L], a vehicle thread's own column (no barrier, no bank conflict)
+constexpr bool spec_in_lds(int rb, bool dist) { return dist || rb < 16; }
+constexpr int SPEC_LDS_ROW = AVD_EVAL_NSPEC * AVD_MAX_L;  // per row
+
 // D is empty (the nominal kernel: parameter list and code as before the disturbed variant existed), one DistArgs, one ResArgs (a
-// residual policy: the plant input is residual_law on the row's xs entry -- under DistArgs the observation) or a DistArgs then a ResArgs
+// residual policy: the plant input is residual_law on the row's xs entry -- under DistArgs the observation) or a DistArgs then a ResArgs;
+// a FreqArgs last adds the single-bin Fourier sums of a frequency sweep (the vehicle threads' alone)
 template <int RB, class... D>
 __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a, const D... dist) {
 #pragma clang fp contract(off)
-    constexpr bool DIST = pack_has<DistArgs, D...>, RES = pack_has<ResArgs, D...>;
+    constexpr bool DIST = pack_has<DistArgs, D...>, RES = pack_has<ResArgs, D...>, FREQ = pack_has<FreqArgs, D...>;
+    constexpr bool SPEC_LDS = FREQ && spec_in_lds(RB, DIST);
     constexpr int UK = RB >= 16 || (DIST && RB >= 8) ? 2 : 4;  // disturbed, 8 rows: 170 VGPRs with four k in flight, 2 waves per SIMD
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const avd_mlp_layout& L = a.lay;
@@ -163,6 +171,7 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a,
     float* h2T = h1T + RB * L.H1;                   // [H2][RB]
     float* vdat = h2T + RB * L.H2;                  // disturbed: [RB][AVD_MAX_L][DIST_VEH], see DIST_VEH. The scalars stay out of the
                                                     // registers the forward needs: each step's observation phase reads them back
+    float* spec = vdat + (DIST ? RB * DIST_LDS_ROW : 0) + tid;  // frequency sweep, SPEC_LDS: this vehicle thread's column of the sums
     const int row = tid / nv, v = tid - row * nv;   // vehicle threads: RB * L <= NTHREADS (host check)
     const bool veh = tid < RB * nv;
     const bool live = veh && row < nrows;           // a vehicle of a real case: the only threads that touch x0 / leader / the outputs
@@ -173,6 +182,9 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a,
             if (v < a.M) a.counters[cas * a.M + v] = __builtin_nanf("");
             if (a.metrics)
                 for (int i = 0; i < AVD_EVAL_NMETRIC; ++i) a.metrics[(cas * nv + v) * AVD_EVAL_NMETRIC + i] = __builtin_nanf("");
+            if constexpr (FREQ)
+                for (int i = 0; i < AVD_EVAL_NSPEC; ++i)
+                    pack_get<FreqArgs>(dist...).spectrum[(cas * nv + v) * AVD_EVAL_NSPEC + i] = __builtin_nanf("");
         }
         return;
     }
@@ -205,6 +217,9 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a,
     float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
     float pa = 0.f, cnt = 0.f;
     VehMetrics met;
+    VehSpectrum spc;
+    if constexpr (SPEC_LDS)
+        if (veh) spc.store(spec, RB * AVD_MAX_L);  // zeros
     const float* leader = a.leader + (long)(k0 + (live ? row : 0)) * a.T;
     if (live) {
         const float* x0 = a.x0 + ((long)(k0 + row) * nv + v) * 4;
@@ -267,6 +282,9 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a,
         // ---- noise-free policy, platoon step ----
         float uu = 0.f;
         VehStep vs = {};
+        float2 cs = make_float2(0.f, 0.f);
+        if constexpr (FREQ)  // this step's basis pair: in flight over the barrier below
+            if (live) cs = ((const float2*)pack_get<FreqArgs>(dist...).basis)[(long)(k0 + row) * a.T + t];
         if (veh) {
             uu = fminf(fmaxf(raw[row * AVD_MAX_L + v], a.lo), a.hi);  // np.clip (ddpgagent.py:27)
             if constexpr (RES) {  // traces, reward and metrics below take the plant's input
@@ -287,6 +305,8 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a,
             if (M == nv) cnt = cnt + nr;  // counters += env.reward[0]
             else negr[row * AVD_MAX_L + v] = nr;
             met.step(cst, xv, xn, pa, uu, a.inv_dt, t);
+            if constexpr (SPEC_LDS) VehSpectrum::step_lds(spec, RB * AVD_MAX_L, xn, uu, cs);
+            else if constexpr (FREQ) spc.step(xn, uu, cs);
             pa = xv.z;  // prev_x <- x
             xv = xn;
             if constexpr (!DIST) ((float4*)(xs + row * 4 * AVD_MAX_L))[v] = xn;
@@ -301,6 +321,10 @@ __global__ __launch_bounds__(NTHREADS) void eval_cases_kernel(const CasesArgs a,
     if (live) {
         if (v < M) a.counters[cas * M + v] = cnt;
         if (a.metrics) met.store(a.metrics + (cas * nv + v) * AVD_EVAL_NMETRIC, xv);
+        if constexpr (FREQ) {
+            if constexpr (SPEC_LDS) spc.load(spec, RB * AVD_MAX_L);
+            spc.store(pack_get<FreqArgs>(dist...).spectrum + (cas * nv + v) * AVD_EVAL_NSPEC);
+        }
     }
 }
 
@@ -338,8 +362,8 @@ int launch_cases(const char* who, int rb, const CasesArgs& a, size_t lds, hipStr
 }
 
 // Every cases entry point: the checks, the block size, the argument block and the launch. dist: the disturbed variant's tables, or
-// null (the nominal kernel); res: a residual policy's law, or null.
-int cases_launch(const char* who, const DistArgs* dist, const ResArgs* res, const avd_mlp_layout* lay, const avd_env_consts* d_consts, int G,
+// null (the nominal kernel); res: a residual policy's law, or null; freq: a frequency sweep's basis and spectrum, or null.
+int cases_launch(const char* who, const DistArgs* dist, const ResArgs* res, const FreqArgs* freq, const avd_mlp_layout* lay, const avd_env_consts* d_consts, int G,
                  int K, int L, int M, int T, const float* theta, const float* stats, int n_sets, const int32_t* set_base, const float* x0,
                  const float* prev_a0, const float* leader, float high, float lo, float hi, float sample_rate, float* counters,
                  float* metrics, void* stream) {
@@ -356,7 +380,8 @@ int cases_launch(const char* who, const DistArgs* dist, const ResArgs* res, cons
                 "%s: layout S=%d A=%d does not fit L=%d M=%d (need A * M == L, S <= %d)", who, lay->S, lay->A, L, M, x_stride);
     AVD_REQUIRE(lay->H1 > 0 && lay->H2 > 0, "%s: layout H1=%d H2=%d", who, lay->H1, lay->H2);
     const int rb = dist ? pick_block(DIST_RB, K, L) : pick_block(CASES_RB, K, L);
-    const size_t row = (size_t)CASES_LDS_ROW + (dist ? DIST_LDS_ROW : 0) + lay->H1 + lay->H2;
+    const size_t row = (size_t)CASES_LDS_ROW + (dist ? DIST_LDS_ROW : 0) + (freq && spec_in_lds(rb, dist != nullptr) ? SPEC_LDS_ROW : 0) +
+                       lay->H1 + lay->H2;
     const size_t lds = sizeof(float) * ((size_t)CASES_LDS_SHARED + (size_t)rb * row);
     if (lds > 160 * 1024) {
         set_error("%s: hidden sizes need %zu B of LDS for blocks of %d cases (> 160 KiB)", who, lds, rb);
@@ -369,6 +394,8 @@ int cases_launch(const char* who, const DistArgs* dist, const ResArgs* res, cons
     if (dist) AVD_REQUIRE(dist->sigma && dist->delay && dist->drop_q && dist->noise_seed, "%s: null disturbance table (only abc may be null)", who);
     if (res)
         if (const int rc = residual_check(who, res->gains, res->scale, M, L)) return rc;
+    if (freq)
+        if (const int rc = freq_check(who, *freq)) return rc;
     CasesArgs a;
     a.lay = *lay, a.cst = d_consts, a.G = G, a.K = K, a.L = L, a.M = M, a.T = T, a.x_stride = x_stride, a.n_sets = n_sets;
     a.theta = theta, a.stats = stats, a.set_base = set_base, a.x0 = x0, a.prev_a0 = prev_a0, a.leader = leader;
@@ -376,6 +403,12 @@ int cases_launch(const char* who, const DistArgs* dist, const ResArgs* res, cons
     a.inv_dt = 1.0f / sample_rate;  // host float32 division, as avd_eval_rollout_f32 forms it
     a.counters = counters, a.metrics = metrics;
     const hipStream_t s = (hipStream_t)stream;
+    if (freq) {  // the same packs with the FreqArgs last
+        if (dist && res) return launch_cases(who, rb, a, lds, s, *dist, *res, *freq);
+        if (dist) return launch_cases(who, rb, a, lds, s, *dist, *freq);
+        if (res) return launch_cases(who, rb, a, lds, s, *res, *freq);
+        return launch_cases(who, rb, a, lds, s, *freq);
+    }
     if (dist && res) return launch_cases(who, rb, a, lds, s, *dist, *res);
     if (dist) return launch_cases(who, rb, a, lds, s, *dist);
     if (res) return launch_cases(who, rb, a, lds, s, *res);
@@ -396,7 +429,7 @@ extern "C" int avd_eval_cases_f32(const avd_mlp_layout* lay, const avd_env_const
                                   const float* theta, const float* stats, int n_sets, const int32_t* set_base, const float* x0,
                                   const float* prev_a0, const float* leader, float high, float lo, float hi, float sample_rate,
                                   float* counters, float* metrics, void* stream) {
-    return cases_launch("avd_eval_cases_f32", nullptr, nullptr, lay, d_consts, G, K, L, M, T, theta, stats, n_sets, set_base, x0, prev_a0,
+    return cases_launch("avd_eval_cases_f32", nullptr, nullptr, nullptr, lay, d_consts, G, K, L, M, T, theta, stats, n_sets, set_base, x0, prev_a0,
                         leader, high, lo, hi, sample_rate, counters, metrics, stream);
 }
 
@@ -427,7 +460,7 @@ extern "C" int avd_eval_cases_dist_f32(const avd_mlp_layout* lay, const avd_env_
                                        const float* sigma, const int32_t* delay, const uint32_t* drop_q, const uint64_t* noise_seed,
                                        const float* abc, float* counters, float* metrics, void* stream) {
     const DistArgs d = {sigma, delay, drop_q, noise_seed, abc};
-    return cases_launch("avd_eval_cases_dist_f32", &d, nullptr, lay, d_consts, G, K, L, M, T, theta, stats, n_sets, set_base, x0, prev_a0,
+    return cases_launch("avd_eval_cases_dist_f32", &d, nullptr, nullptr, lay, d_consts, G, K, L, M, T, theta, stats, n_sets, set_base, x0, prev_a0,
                         leader, high, lo, hi, sample_rate, counters, metrics, stream);
 }
 
@@ -445,6 +478,25 @@ extern "C" int avd_eval_cases_res_f32(const avd_mlp_layout* lay, const avd_env_c
                 "%s: null disturbance table (all five null: the nominal plant and a perfect observation; otherwise only abc may be null)", who);
     const DistArgs d = {sigma, delay, drop_q, noise_seed, abc};
     const ResArgs r = {d_gains, scale};
-    return cases_launch(who, dist ? &d : nullptr, &r, lay, d_consts, G, K, L, M, T, theta, stats, n_sets, set_base, x0, prev_a0, leader, high,
+    return cases_launch(who, dist ? &d : nullptr, &r, nullptr, lay, d_consts, G, K, L, M, T, theta, stats, n_sets, set_base, x0, prev_a0, leader, high,
                         lo, hi, sample_rate, counters, metrics, stream);
+}
+
+// The scenario evaluator of a frequency sweep: avd_eval_cases_res_f32's arguments (all five disturbance tables null: the nominal plant;
+// d_gains null: no residual law, scale unread) plus the per-case basis table and the spectrum output.
+extern "C" int avd_eval_cases_freq_f32(const avd_mlp_layout* lay, const avd_env_consts* d_consts, int G, int K, int L, int M, int T,
+                                       const float* theta, const float* stats, int n_sets, const int32_t* set_base, const float* x0,
+                                       const float* prev_a0, const float* leader, float high, float lo, float hi, float sample_rate,
+                                       const float* sigma, const int32_t* delay, const uint32_t* drop_q, const uint64_t* noise_seed,
+                                       const float* abc, const float* d_gains, float scale, float* counters, float* metrics,
+                                       const float* basis, float* spectrum, void* stream) {
+    const char* who = "avd_eval_cases_freq_f32";
+    const bool dist = sigma || delay || drop_q || noise_seed || abc;
+    AVD_REQUIRE(!dist || (sigma && delay && drop_q && noise_seed),
+                "%s: null disturbance table (all five null: the nominal plant and a perfect observation; otherwise only abc may be null)", who);
+    const DistArgs d = {sigma, delay, drop_q, noise_seed, abc};
+    const ResArgs r = {d_gains, scale};
+    const FreqArgs f = {basis, spectrum};
+    return cases_launch(who, dist ? &d : nullptr, d_gains ? &r : nullptr, &f, lay, d_consts, G, K, L, M, T, theta, stats, n_sets, set_base, x0,
+                        prev_a0, leader, high, lo, hi, sample_rate, counters, metrics, stream);
 }

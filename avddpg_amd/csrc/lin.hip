@@ -22,6 +22,8 @@
 //   eval_linear_kernel<DistArgs> (disturbed): 118 VGPRs, 0 AGPRs, no scratch, 4096 B LDS, 4 waves per SIMD (the registers are Box-Muller's
 //                                             logf / sinf / cosf and Philox's; at 4096 gain sets x 12 cases x 5 vehicles the launch is
 //                                             4096 waves, 4 per SIMD of 256 CUs, so the count does not limit that shape)
+//   with a FreqArgs (a frequency sweep's ten sums per lane; profiles/eval_freq_resource_usage.txt): 80 VGPRs, 6 waves per SIMD nominal;
+//                                             134 VGPRs, 3 waves per SIMD disturbed; no scratch
 #include <limits.h>
 
 #include "eval_common.h"
@@ -42,11 +44,14 @@ struct LinArgs {
     float* metrics;        // [G][K][L][AVD_EVAL_NMETRIC] or null
 };
 
-// D is empty (nominal: the constants block's plant, a perfect observation, no LDS) or one DistArgs
+// D is empty (nominal: the constants block's plant, a perfect observation, no LDS) or one DistArgs; a FreqArgs last adds the single-bin
+// Fourier sums of a frequency sweep: every live lane reads its case's basis pair one step ahead of its use, as vehicle 0 reads the
+// leader row (the L lanes of a rollout read the same address), and keeps its ten sums in registers (in LDS columns they cost the same
+// 16 registers -- 80 and 134 either way, no scratch: profiles/eval_freq_resource_usage.txt)
 template <class... D>
 __global__ __launch_bounds__(LIN_THREADS) void eval_linear_kernel(const LinArgs a, const D... dist) {
 #pragma clang fp contract(off)
-    constexpr bool DIST = sizeof...(D) != 0;
+    constexpr bool DIST = pack_has<DistArgs, D...>, FREQ = pack_has<FreqArgs, D...>;
     const int nv = a.L, lane = threadIdx.x;
     const int per_wave = LIN_THREADS / nv;
     const int rw = lane / nv, v = lane - rw * nv;
@@ -59,7 +64,7 @@ __global__ __launch_bounds__(LIN_THREADS) void eval_linear_kernel(const LinArgs 
     float abc[24];
     bool table = false;
     if constexpr (DIST) {
-        const DistArgs da{dist...};
+        const DistArgs& da = pack_get<DistArgs>(dist...);
         if (da.abc) {
             table = true;
 #pragma unroll
@@ -88,7 +93,7 @@ __global__ __launch_bounds__(LIN_THREADS) void eval_linear_kernel(const LinArgs 
     float* ring = nullptr;
     if constexpr (DIST) {
         __shared__ float s_ring[EVAL_RING * LIN_THREADS];  // [slot][lane]
-        const DistArgs da{dist...};
+        const DistArgs& da = pack_get<DistArgs>(dist...);
         sg_ep = da.sigma[k * 3L], sg_ev = da.sigma[k * 3L + 1], sg_a = da.sigma[k * 3L + 2];
         dly = da.delay[k] & (EVAL_RING - 1);  // (the host refuses delays outside the ring; the mask keeps any value inside it)
         dq = da.drop_q[k];
@@ -98,9 +103,19 @@ __global__ __launch_bounds__(LIN_THREADS) void eval_linear_kernel(const LinArgs 
         for (int j = 0; j < EVAL_RING; ++j) ring[j * LIN_THREADS] = xv.w;  // steps before the first: x0's
         recv = xv.w;                                                        // and the last received value
     }
+    const float2* basis = nullptr;
+    float2 cs_next = make_float2(0.f, 0.f);
+    VehSpectrum spc;
+    if constexpr (FREQ) {
+        basis = (const float2*)pack_get<FreqArgs>(dist...).basis + (long)k * a.T;
+        cs_next = basis[0];
+    }
     for (int t = 0; t < a.T; ++t) {
         const float lead = lead_next;
         if (v == 0 && t + 1 < a.T) lead_next = leader[t + 1];  // next step's, in flight during this one
+        const float2 cs = cs_next;
+        if constexpr (FREQ)
+            if (t + 1 < a.T) cs_next = basis[t + 1];
         // ---- what the controller sees of the true pre-step state xv ----
         float4 ob = xv;
         if constexpr (DIST) {
@@ -116,11 +131,15 @@ __global__ __launch_bounds__(LIN_THREADS) void eval_linear_kernel(const LinArgs 
         const float nr = veh_step_post(cst, vs, abc + 16, abc + 20, xv, pa, uu, exog, xn);
         cnt = cnt + nr;  // counters += env.reward[0], per vehicle (decentralized)
         met.step(cst, xv, xn, pa, uu, a.inv_dt, t);
+        if constexpr (FREQ) spc.step(xn, uu, cs);
         pa = xv.z;  // prev_x <- x
         xv = xn;
     }
     a.counters[roll * nv + v] = cnt;
     if (a.metrics) met.store(a.metrics + (roll * nv + v) * AVD_EVAL_NMETRIC, xv);
+    if constexpr (FREQ) {
+        spc.store(pack_get<FreqArgs>(dist...).spectrum + (roll * nv + v) * AVD_EVAL_NSPEC);
+    }
 }
 
 // One thread per gain set: the sequential float32 sum of its K * L counters in (k, v) order, divided by (float)(K * L)
@@ -144,11 +163,11 @@ int launch_linear(const char* who, const LinArgs& a, long blocks, hipStream_t st
 
 using namespace avd;
 
-extern "C" int avd_eval_linear_f32(const avd_env_consts* d_consts, int G, int K, int L, int T, const float* gains, const float* x0,
-                                   const float* prev_a0, const float* leader, float lo, float hi, float sample_rate, const float* sigma,
-                                   const int32_t* delay, const uint32_t* drop_q, const uint64_t* noise_seed, const float* abc,
-                                   float* counters, float* metrics, void* stream) {
-    const char* who = "avd_eval_linear_f32";
+// Both linear entry points: the checks, the argument block and the launch. freq: a frequency sweep's basis and spectrum, or null.
+static int linear_launch(const char* who, const FreqArgs* freq, const avd_env_consts* d_consts, int G, int K, int L, int T, const float* gains,
+                         const float* x0, const float* prev_a0, const float* leader, float lo, float hi, float sample_rate,
+                         const float* sigma, const int32_t* delay, const uint32_t* drop_q, const uint64_t* noise_seed, const float* abc,
+                         float* counters, float* metrics, void* stream) {
     AVD_REQUIRE(d_consts && gains && x0 && prev_a0 && leader && counters, "%s: null pointer", who);
     AVD_REQUIRE(L >= 1 && L <= AVD_MAX_L, "%s: L=%d (L must be 1..%d)", who, L, AVD_MAX_L);
     AVD_REQUIRE(G >= 1 && K >= 1 && T >= 1, "%s: G=%d K=%d T=%d (all must be >= 1)", who, G, K, T);
@@ -163,14 +182,36 @@ extern "C" int avd_eval_linear_f32(const avd_env_consts* d_consts, int G, int K,
                   per_wave, L, blocks, INT_MAX);
         return AVD_E_UNSUPPORTED;
     }
+    if (freq)
+        if (const int rc = freq_check(who, *freq)) return rc;
     LinArgs a;
     a.cst = d_consts, a.G = G, a.K = K, a.L = L, a.T = T, a.gains = gains, a.x0 = x0, a.prev_a0 = prev_a0, a.leader = leader;
     a.lo = lo, a.hi = hi;
     a.inv_dt = 1.0f / sample_rate;  // host float32 division, as avd_eval_cases_f32 forms it
     a.counters = counters, a.metrics = metrics;
-    if (!dist) return launch_linear(who, a, (long)blocks, (hipStream_t)stream);
     const DistArgs d = {sigma, delay, drop_q, noise_seed, abc};
+    if (freq) return dist ? launch_linear(who, a, (long)blocks, (hipStream_t)stream, d, *freq) : launch_linear(who, a, (long)blocks, (hipStream_t)stream, *freq);
+    if (!dist) return launch_linear(who, a, (long)blocks, (hipStream_t)stream);
     return launch_linear(who, a, (long)blocks, (hipStream_t)stream, d);
+}
+
+extern "C" int avd_eval_linear_f32(const avd_env_consts* d_consts, int G, int K, int L, int T, const float* gains, const float* x0,
+                                   const float* prev_a0, const float* leader, float lo, float hi, float sample_rate, const float* sigma,
+                                   const int32_t* delay, const uint32_t* drop_q, const uint64_t* noise_seed, const float* abc,
+                                   float* counters, float* metrics, void* stream) {
+    return linear_launch("avd_eval_linear_f32", nullptr, d_consts, G, K, L, T, gains, x0, prev_a0, leader, lo, hi, sample_rate, sigma, delay,
+                         drop_q, noise_seed, abc, counters, metrics, stream);
+}
+
+// The linear scenario evaluator of a frequency sweep: avd_eval_linear_f32's arguments plus the per-case basis table and the spectrum output
+extern "C" int avd_eval_linear_freq_f32(const avd_env_consts* d_consts, int G, int K, int L, int T, const float* gains, const float* x0,
+                                        const float* prev_a0, const float* leader, float lo, float hi, float sample_rate,
+                                        const float* sigma, const int32_t* delay, const uint32_t* drop_q, const uint64_t* noise_seed,
+                                        const float* abc, float* counters, float* metrics, const float* basis, float* spectrum,
+                                        void* stream) {
+    const FreqArgs f = {basis, spectrum};
+    return linear_launch("avd_eval_linear_freq_f32", &f, d_consts, G, K, L, T, gains, x0, prev_a0, leader, lo, hi, sample_rate, sigma, delay,
+                         drop_q, noise_seed, abc, counters, metrics, stream);
 }
 
 extern "C" int avd_linear_fitness_f32(int G, int K, int L, const float* counters, float* fitness, void* stream) {

@@ -242,10 +242,17 @@ class _Suite:
     ``delay``, ``drop_q``, ``noise_seed``, ``abc`` of _level_tables (all None without levels; abc None when no level changes the plant: the
     constants block's matrices for every case), ``sigma_h`` ... their host copies."""
 
-    def __init__(self, conf, scenarios, levels, seeds, amp, period_s, manual_timestep_override, no_seed):
+    def __init__(self, conf, scenarios, levels, seeds, amp, period_s, manual_timestep_override, no_seed, rows=None):
         from . import scenarios as _sc
 
-        names = _sc.check_names(scenarios)
+        if rows is not None:  # explicit leader rows float32 [NC, T] named by ``scenarios`` (a frequency sweep's): T is theirs
+            rows = np.ascontiguousarray(np.asarray(rows, dtype=np.float32))
+            names = [str(n) for n in scenarios]
+            if rows.ndim != 2 or rows.shape[0] != len(names) or not names or not np.isfinite(rows).all():
+                raise ValueError(f"leader rows of shape {rows.shape} for {len(names)} names: need finite [NC >= 1, T]")
+            manual_timestep_override = rows.shape[1]
+        else:
+            names = _sc.check_names(scenarios)
         seeds = [int(conf.evaluation_seed)] if seeds is None else [int(s) for s in seeds]
         if not seeds:
             raise ValueError(no_seed)
@@ -259,8 +266,11 @@ class _Suite:
         rep = 1 if levels is None else len(levels)  # a (scenario, seed)'s cases
         self.scenarios, self.seeds, self.levels, self.env = names, seeds, levels, env
         self.L, self.T, self.NC, self.ND, self.NS, self.K = L, T, NC, (None if levels is None else rep), NS, NC * rep * NS
-        prof = {n: _sc.leader_profile(n, T, conf, amp, period_s) for n in names if n != "gaussian"}
-        self.leader_h = np.stack([starts[k][1] if n == "gaussian" else prof[n] for n in names for _ in range(rep) for k in range(NS)])
+        if rows is not None:
+            self.leader_h = np.repeat(rows, rep * NS, axis=0)
+        else:
+            prof = {n: _sc.leader_profile(n, T, conf, amp, period_s) for n in names if n != "gaussian"}
+            self.leader_h = np.stack([starts[k][1] if n == "gaussian" else prof[n] for n in names for _ in range(rep) for k in range(NS)])
         self.leader = torch.from_numpy(self.leader_h).to(dev)
         self.x0 = torch.stack([e.x.reshape(L, 4) for e, _, _ in starts]).repeat(NC * rep, 1, 1).contiguous()
         self.pa0 = torch.stack([e.prev_a.reshape(L) for e, _, _ in starts]).repeat(NC * rep, 1).contiguous()
@@ -304,14 +314,14 @@ class CaseBatch:
     cases and their tables are a _Suite's fields."""
 
     def __init__(self, conf, actors, platoons, scenarios, seeds, amp, period_s, set_mod, set_bases, manual_timestep_override, base_law=None,
-                 levels=None):
+                 levels=None, rows=None):
         from . import _hip
 
         platoons = [int(p) for p in platoons]
         no_entry = "run_cases needs at least one platoon and one seed"
         if not platoons:
             raise ValueError(no_entry)
-        suite = _Suite(conf, scenarios, levels, seeds, amp, period_s, manual_timestep_override, no_entry)
+        suite = _Suite(conf, scenarios, levels, seeds, amp, period_s, manual_timestep_override, no_entry, rows)
         vars(self).update(vars(suite))
         # groups: ONE result for all platoons, or one per entry (_address_sets)
         _, per_entry, bases = _address_sets("run_cases", actors, self.env, platoons, set_mod, set_bases)
@@ -322,12 +332,16 @@ class CaseBatch:
         self.block = int((_hip.lib().avd_eval_cases_block if levels is None else _hip.lib().avd_eval_cases_dist_block)(self.K, self.L))
         self.gains, self.res_scale = _base_gains(base_law, conf, self.env.device)
 
-    def launch(self):
+    def _args(self):
+        """-> (common, tables, out): the argument groups every cases entry point shares."""
         a, c = self.actors, self.conf
         common = (a._layp, ptr(self.env.d_consts), self.G, self.K, self.L, self.M, self.T, ptr(a.theta), ptr(a.stats), a.n_sets,
                   ptr(self.set_base), ptr(self.x0), ptr(self.pa0), ptr(self.leader), a.high, c.action_low, c.action_high, c.sample_rate)
         tables = (ptr(self.sigma), ptr(self.delay), ptr(self.drop_q), ptr(self.noise_seed), ptr(self.abc))  # null without levels
-        out = (ptr(self.counters), ptr(self.metrics), stream_handle())
+        return common, tables, (ptr(self.counters), ptr(self.metrics), stream_handle())
+
+    def launch(self):
+        common, tables, out = self._args()
         if self.gains is not None:  # a residual policy: the law acts on what the vehicle observes
             call("avd_eval_cases_res_f32", *common, *tables, ptr(self.gains), self.res_scale, *out)
         elif self.levels is not None:
@@ -428,7 +442,7 @@ class LinearBatch:
     sets). ``metrics=False`` passes the kernel a null metrics pointer. The raw form: under Model A the kernel does not read a row's 4th
     gain (prepare_linear and tune_linear refuse a non-zero one)."""
 
-    def __init__(self, conf, gains, scenarios, disturbances, seeds, amp, period_s, manual_timestep_override, metrics=True):
+    def __init__(self, conf, gains, scenarios, disturbances, seeds, amp, period_s, manual_timestep_override, metrics=True, rows=None):
         from . import scenarios as _sc
 
         if conf.framework == conf.cntrl:
@@ -438,17 +452,20 @@ class LinearBatch:
         gains = np.ascontiguousarray(np.asarray(gains, dtype=np.float32))
         if gains.ndim != 3 or gains.shape[0] < 1 or gains.shape[1:] != (conf.pl_size, 4) or not np.isfinite(gains).all():
             raise ValueError(f"gains of shape {gains.shape}: need finite [G >= 1, L = {conf.pl_size}, 4]")
-        suite = _Suite(conf, scenarios, levels, seeds, amp, period_s, manual_timestep_override, "run_linear needs at least one seed")
+        suite = _Suite(conf, scenarios, levels, seeds, amp, period_s, manual_timestep_override, "run_linear needs at least one seed", rows)
         vars(self).update(vars(suite))
         self.conf, self.G = conf, gains.shape[0]
         self.gains_h, self.gains = gains, torch.from_numpy(gains).to(self.env.device)
         self.counters, self.metrics = suite.outputs(self.G, self.L, metrics)
 
-    def launch(self):
+    def _args(self):
         c = self.conf
-        call("avd_eval_linear_f32", ptr(self.env.d_consts), self.G, self.K, self.L, self.T, ptr(self.gains), ptr(self.x0), ptr(self.pa0),
-             ptr(self.leader), c.action_low, c.action_high, c.sample_rate, ptr(self.sigma), ptr(self.delay), ptr(self.drop_q),
-             ptr(self.noise_seed), ptr(self.abc), ptr(self.counters), ptr(self.metrics), stream_handle())
+        return (ptr(self.env.d_consts), self.G, self.K, self.L, self.T, ptr(self.gains), ptr(self.x0), ptr(self.pa0), ptr(self.leader),
+                c.action_low, c.action_high, c.sample_rate, ptr(self.sigma), ptr(self.delay), ptr(self.drop_q), ptr(self.noise_seed),
+                ptr(self.abc), ptr(self.counters), ptr(self.metrics))
+
+    def launch(self):
+        call("avd_eval_linear_f32", *self._args(), stream_handle())
 
     def enqueue_fitness(self, out=None):
         """One avd_linear_fitness_f32 launch over the counters of ``launch()`` on the current stream, into ``out`` (float32 [G] on the
@@ -586,3 +603,130 @@ def search_linear(conf, space, scenarios=("gaussian",), disturbances=(), seeds=N
         tr["elite_idx"] = elite.cpu().numpy()
     return SearchResult(_sc.LinearLaw(_sc.SEARCHED if name is None else name, table=table), best_fit.cpu().numpy()[0], at,
                         history.cpu().numpy(), mean.cpu().numpy(), std.cpu().numpy(), bg, G, gens, n_elite, b.K, tr)
+
+
+# ---- frequency response: a sweep of sinusoidal leader inputs as cases, a single-bin Fourier sum per vehicle and signal on the device ----
+
+class FrequencyResults:
+    """What run_frequency / run_linear_frequency return: ``freqs_hz`` float64 [F] (the frequencies driven) and their ``cycles`` in the
+    window of ``W`` steps (of ``T``), ``disturbances`` (the levels' names, "nominal" first), ``seeds``; ``spectrum`` float32 [G, F, ND,
+    NS, L, 10] the raw sums (scenarios.SIGNALS), ``summary()`` scenarios.frequency_summary of it, and the usual
+    ``scores`` [G, F, ND, NS], ``counters`` [..., M], ``metrics`` {name: [..., L]}. G: the platoon entries, or the laws."""
+
+    def __init__(self, freqs_hz, cycles, W, T, disturbances, seeds, spectrum, scores, counters, metrics):
+        self.freqs_hz, self.cycles, self.W, self.T = np.asarray(freqs_hz, dtype=np.float64), np.asarray(cycles), int(W), int(T)
+        self.disturbances, self.seeds = list(disturbances), list(seeds)
+        self.spectrum, self.scores, self.counters, self.metrics = spectrum, scores, counters, metrics
+
+    def summary(self):
+        from . import scenarios as _sc
+
+        return _sc.frequency_summary(self.spectrum, self.W, self.freqs_hz, axis=self.spectrum.ndim - 5)  # [..., F, ND, NS, L, 10]
+
+
+class _FrequencyMixin:
+    """What the two frequency batches share: the sweep's tables before the base class builds its suite, the spectrum output after, and
+    the read-back."""
+
+    def _sweep(self, spec, conf, disturbances):
+        from . import scenarios as _sc
+
+        spec = _sc.check_frequency(spec, conf)
+        self.spec, (_, self.t0, self.W) = spec, spec.window(conf)
+        self.cycles, self.freqs_hz = spec.cycles(conf), spec.freqs_hz(conf)
+        self._basis_f = _sc.frequency_basis(spec, conf)
+        disturbances = list(disturbances)
+        levels = [_sc.NOMINAL] + _sc.check_disturbances(disturbances, conf) if disturbances else None
+        return [f"f{int(c)}" for c in self.cycles], _sc.frequency_leader(spec, conf), levels
+
+    def _outputs(self):
+        from . import _hip
+
+        per = self.K // self.NC  # a frequency's cases: levels x seeds
+        self.basis_h = np.repeat(self._basis_f, per, axis=0)  # [K, T, 2]
+        self.basis = torch.from_numpy(self.basis_h).to(self.env.device)
+        self.spectrum = torch.empty(self.G, self.K, self.L, _hip.AVD_EVAL_NSPEC, dtype=torch.float32, device=self.env.device)
+
+    def _frequency_results(self, sel=slice(None)):
+        r = super().results()
+        ND = 1 if self.levels is None else self.ND
+        G = r.scores.shape[0]
+        shape = (G, self.NC, ND, self.NS)
+        sp = self.spectrum.cpu().numpy().reshape(self.G, self.NC, ND, self.NS, self.L, -1)[sel]
+        names = ["nominal"] if self.levels is None else [d.name for d in self.levels]
+        return FrequencyResults(self.freqs_hz, self.cycles, self.W, self.T, names, self.seeds, np.ascontiguousarray(sp),
+                                r.scores.reshape(shape), r.counters.reshape(*shape, -1),
+                                {k: v.reshape(*shape, self.L) for k, v in r.metrics.items()})
+
+
+class FrequencyBatch(_FrequencyMixin, CaseBatch):
+    """The device inputs of one avd_eval_cases_freq_f32 launch (prepare_frequency): CaseBatch's, the cases a frequency sweep's -- frequencies x
+    [nominal, *disturbances] x seeds, seeds innermost -- plus ``basis`` [K, T, 2] and ``spectrum`` [G, K, L, 10]."""
+
+    def __init__(self, conf, actors, platoons, spec, disturbances, seeds, set_mod, set_bases, base_law):
+        names, rows, levels = self._sweep(spec, conf, disturbances)
+        super().__init__(conf, actors, platoons, names, seeds, None, 10.0, set_mod, set_bases, None, base_law, levels, rows)
+        self._outputs()
+
+    def launch(self):
+        common, tables, out = self._args()
+        call("avd_eval_cases_freq_f32", *common, *tables, ptr(self.gains), self.res_scale if self.gains is not None else 1.0, *out[:2],
+             ptr(self.basis), ptr(self.spectrum), out[2])
+
+    def results(self):
+        return self._frequency_results([self.group(i) for i in range(self.NP)])
+
+
+class LinearFrequencyBatch(_FrequencyMixin, LinearBatch):
+    """The device inputs of one avd_eval_linear_freq_f32 launch (prepare_linear_frequency): LinearBatch's over a frequency sweep's cases."""
+
+    def __init__(self, conf, gains, spec, disturbances, seeds):
+        names, rows, _ = self._sweep(spec, conf, disturbances)
+        super().__init__(conf, gains, names, disturbances, seeds, None, 10.0, None, True, rows)
+        self._outputs()
+
+    def launch(self):
+        call("avd_eval_linear_freq_f32", *self._args(), ptr(self.basis), ptr(self.spectrum), stream_handle())
+
+    def results(self):
+        return self._frequency_results()
+
+
+def prepare_frequency(conf, actors, platoons, spec, disturbances=(), seeds=None, set_mod=None, set_bases=None, base_law=None):
+    """run_frequency's host part (the sweep's leader rows and basis table made, start states drawn, device inputs uploaded) as a
+    FrequencyBatch."""
+    return FrequencyBatch(conf, actors, platoons, spec, disturbances, seeds, set_mod, set_bases, base_law)
+
+
+def run_frequency(conf, actors, platoons, spec, disturbances=(), seeds=None, set_mod=None, set_bases=None, base_law=None):
+    """The frequency response of every platoon's actors in ONE launch of avd_eval_cases_freq_f32 (csrc/evalx.hip): ``spec`` (a
+    scenarios.FrequencySpec) gives the sinusoidal leader inputs, one per snapped frequency; the cases are frequencies x [nominal,
+    *disturbances] x seeds, seeds innermost, with run_cases' start states; per vehicle the kernel accumulates the single-bin Fourier
+    sums of the post-step state and the plant input over the spec's window beside the usual counters and metrics (which are bit-identical
+    to run_cases' / run_disturbed's on the same cases). actors / platoons / set_mod / set_bases / base_law as in run_cases. The caller's
+    global ``np.random`` state is restored. -> a FrequencyResults; its spectrum is bit-identical to scenarios.spectrum_from_traces on
+    the rollout's traces."""
+    b = prepare_frequency(conf, actors, platoons, spec, disturbances, seeds, set_mod, set_bases, base_law)
+    b.launch()
+    return b.results()
+
+
+def prepare_linear_frequency(conf, laws, spec, disturbances=(), seeds=None):
+    """run_linear_frequency's host part as a LinearFrequencyBatch."""
+    from . import scenarios as _sc
+
+    laws = _sc.check_baselines(laws, conf, reserved=())
+    if not laws:
+        raise ValueError("run_linear_frequency needs at least one law")
+    b = LinearFrequencyBatch(conf, np.stack([w.gains(conf.pl_size) for w in laws]), spec, disturbances, seeds)
+    b.laws = laws
+    return b
+
+
+def run_linear_frequency(conf, laws, spec, disturbances=(), seeds=None):
+    """run_frequency for linear laws (scenarios.LinearLaw) in ONE launch of avd_eval_linear_freq_f32 (csrc/lin.hip): the first axis of
+    the FrequencyResults is the law axis. Decentralized platoons only. scenarios.linear_frequency_response is the float64 theory an
+    unclipped law's gain_a is compared with."""
+    b = prepare_linear_frequency(conf, laws, spec, disturbances, seeds)
+    b.launch()
+    return b.results()

@@ -146,6 +146,291 @@ def write_csv(path, results, platoon_tags):
         w.writerows(csv_rows(results, platoon_tags))
 
 
+# ---- frequency response: what the frequency entry points (avd_eval_cases_freq_f32, avd_eval_linear_freq_f32) reduce -----------------
+
+NSPEC = 10  # AVD_EVAL_NSPEC
+SIGNALS = ("ep", "ev", "a", "w", "u")  # a vehicle's (re, im) pairs, in this order
+FREQUENCY_KEYS = ("fmin", "fmax", "n", "amp", "settle", "steps")
+MAX_FREQUENCIES = 256
+MIN_WINDOW = 8
+
+
+class FrequencySpec:
+    """A frequency sweep: ``n`` log-spaced frequencies from ``fmin`` to ``fmax`` (Hz), each a sinusoidal leader input of amplitude ``amp``
+    (None: conf.reset_max_u) over ``steps`` steps (None: conf.steps_per_episode), measured over the last ``1 - settle`` of the rollout.
+    With T = steps, t0 = floor(settle * T) and W = T - t0, a frequency is snapped to a whole number of cycles in the window (cycles =
+    round(f * W * sample_rate), kept in 1 .. ceil(W / 2) - 1, duplicates dropped), so that the single-bin sum has no leakage; the
+    frequency reported is cycles / (W * sample_rate)."""
+
+    def __init__(self, fmin, fmax, n, amp=None, settle=0.5, steps=None, text=None):
+        self.fmin, self.fmax, self.n, self.amp, self.settle, self.steps, self.text = fmin, fmax, n, amp, settle, steps, text
+
+    def window(self, conf):
+        """-> (T, t0, W), checked."""
+        check_frequency(self, conf)
+        T = int(conf.steps_per_episode if self.steps is None else self.steps)
+        t0 = int(math.floor(float(self.settle) * T))
+        return T, t0, T - t0
+
+    def cycles(self, conf):
+        """int64 [F]: the snapped cycle counts, ascending, without duplicates."""
+        _, _, W = self.window(conf)
+        f = np.geomspace(float(self.fmin), float(self.fmax), int(self.n)) if int(self.n) > 1 else np.array([float(self.fmin)])
+        c = np.clip(np.rint(f * W * float(conf.sample_rate)), 1, -(-W // 2) - 1).astype(np.int64)
+        return np.unique(c)
+
+    def freqs_hz(self, conf):
+        """float64 [F]: the frequencies actually driven, cycles / (W * sample_rate)."""
+        _, _, W = self.window(conf)
+        return self.cycles(conf) / (W * float(conf.sample_rate))
+
+    def items(self):
+        return [[k, getattr(self, k)] for k in FREQUENCY_KEYS]
+
+    def __repr__(self):
+        return "FrequencySpec(" + ", ".join(f"{k}={v!r}" for k, v in self.items()) + ")"
+
+
+def check_frequency(spec, conf=None):
+    """The spec, checked. A ValueError for: not a FrequencySpec; a non-finite value; fmin <= 0 or fmin > fmax; n no integer in 1 ..
+    MAX_FREQUENCIES; settle outside [0, 1); steps no integer >= 1; a window W = T - floor(settle * T) < MIN_WINDOW (with ``conf``, or
+    with steps given)."""
+    if not isinstance(spec, FrequencySpec):
+        raise ValueError(f"{spec!r} is not a scenarios.FrequencySpec")
+    num = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and math.isfinite(v)
+    whole = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer))
+    for k in ("fmin", "fmax", "settle"):
+        if not num(getattr(spec, k)):
+            raise ValueError(f"frequency: {k}={getattr(spec, k)!r} must be a finite number")
+    if spec.amp is not None and not num(spec.amp):
+        raise ValueError(f"frequency: amp={spec.amp!r} must be a finite number")
+    if spec.fmin <= 0 or spec.fmin > spec.fmax:
+        raise ValueError(f"frequency: fmin={spec.fmin!r} fmax={spec.fmax!r} (need 0 < fmin <= fmax)")
+    if not whole(spec.n) or not 1 <= spec.n <= MAX_FREQUENCIES:
+        raise ValueError(f"frequency: n={spec.n!r} must be an integer in 1..{MAX_FREQUENCIES}")
+    if not 0 <= spec.settle < 1:
+        raise ValueError(f"frequency: settle={spec.settle!r} must be in [0, 1)")
+    if spec.steps is not None and (not whole(spec.steps) or spec.steps < 1):
+        raise ValueError(f"frequency: steps={spec.steps!r} must be an integer >= 1")
+    T = spec.steps if spec.steps is not None else (None if conf is None else int(conf.steps_per_episode))
+    if T is not None:
+        W = int(T) - int(math.floor(float(spec.settle) * int(T)))
+        if W < MIN_WINDOW:
+            raise ValueError(f"frequency: a window of W={W} steps (T={T}, settle={spec.settle!r}): need W >= {MIN_WINDOW}")
+    return spec
+
+
+def parse_frequency(text):
+    """``fmin=0.02,fmax=2,n=16[,amp=A,settle=0.5,steps=N]`` -> FrequencySpec, checked by check_frequency. An unknown key, a key given
+    twice, a missing fmin / fmax / n or a value that is no number is a ValueError."""
+    kw = {}
+    for part in [q.strip() for q in str(text).split(",") if q.strip()]:
+        key, eq, val = part.partition("=")
+        key, val = key.strip(), val.strip()
+        if not eq or key not in FREQUENCY_KEYS:
+            raise ValueError(f"frequency: unknown key {key!r} (one of {', '.join(FREQUENCY_KEYS)}, as key=value)")
+        if key in kw:
+            raise ValueError(f"frequency: {key} given twice")
+        try:
+            kw[key] = int(val) if key in ("n", "steps") else float(val)
+        except ValueError:
+            raise ValueError(f"frequency: {key}={val!r} is not {'an integer' if key in ('n', 'steps') else 'a number'}") from None
+    missing = [k for k in ("fmin", "fmax", "n") if k not in kw]
+    if missing:
+        raise ValueError(f"frequency {text!r}: {', '.join(missing)} missing (fmin=..,fmax=..,n=..[,amp=..,settle=..,steps=..])")
+    return check_frequency(FrequencySpec(text=str(text).strip(), **kw))
+
+
+def _frequency_angle(spec, conf):
+    """float64 [F, T]: 2 pi cycles (k - t0) / W, and t0."""
+    T, t0, W = spec.window(conf)
+    k = np.arange(T, dtype=np.float64)
+    return 2.0 * np.pi * spec.cycles(conf)[:, None].astype(np.float64) * (k[None, :] - t0) / W, t0
+
+
+def frequency_leader(spec, conf):
+    """float32 [F, T]: the leader's input per frequency, amp * sin(2 pi cycles (k - t0) / W) for every step k (the sinusoid runs through
+    the settling steps too), computed in float64 and rounded once, as leader_profile does. amp defaults to conf.reset_max_u."""
+    ang, _ = _frequency_angle(spec, conf)
+    amp = float(conf.reset_max_u if spec.amp is None else spec.amp)
+    return np.ascontiguousarray((amp * np.sin(ang)).astype(np.float32))
+
+
+def frequency_basis(spec, conf):
+    """float32 [F, T, 2]: (cos, sin) of the leader's angle for the steps k >= t0 of the window and (0, 0) before: the window is in the
+    table, the device loop has no branch on t0. float64, rounded once."""
+    ang, t0 = _frequency_angle(spec, conf)
+    out = np.stack([np.cos(ang), np.sin(ang)], axis=-1)
+    out[:, :t0] = 0.0
+    return np.ascontiguousarray(out.astype(np.float32))
+
+
+def spectrum_from_traces(traces, basis_row):
+    """The ten single-bin Fourier sums per vehicle, float32 [L, NSPEC] -- (re, im) of ep, ev, a, w, u -- from one rollout's trace dict as
+    ``evaluator.run_many`` returns it (``states`` [T, L, >= 3] post-step states, ``inputs`` [T, L] plant inputs) and the case's basis
+    row [T, 2]: per step, re = re + x * c and im = im + x * s in float32, the product rounded first, sequential adds in step order -- what
+    the frequency entry points accumulate, bit for bit. Traces of width 3 (Model A's hide w) leave the w pair NaN."""
+    st = np.asarray(traces["states"], dtype=np.float32)
+    u = np.asarray(traces["inputs"], dtype=np.float32)
+    b = np.asarray(basis_row, dtype=np.float32)
+    T, L = u.shape
+    if b.shape != (T, 2) or st.shape[:2] != (T, L) or st.shape[2] < 3:
+        raise ValueError(f"states {st.shape}, inputs {u.shape}, basis {b.shape}: need [T, L, >= 3], [T, L], [T, 2]")
+    sig = [st[:, :, c] for c in range(min(4, st.shape[2]))]
+    if len(sig) < 4:
+        sig.append(None)
+    sig.append(u)
+    out = np.zeros((L, NSPEC), dtype=np.float32)
+    for i, x in enumerate(sig):
+        if x is None:
+            out[:, 2 * i:2 * i + 2] = np.nan
+            continue
+        re, im = np.zeros(L, dtype=np.float32), np.zeros(L, dtype=np.float32)
+        for t in range(T):
+            re = re + x[t] * b[t, 0]
+            im = im + x[t] * b[t, 1]
+        out[:, 2 * i], out[:, 2 * i + 1] = re, im
+    return out
+
+
+def _ratio(num, den):
+    """num / den (complex), NaN where den is 0 or either is NaN."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where((np.abs(den) > 0) & ~np.isnan(num), num / np.where(den == 0, 1, den), np.nan + 0j)
+
+
+def _gains_of(X):
+    """complex [..., L, 5] -> (gain_a, gain_ep, phase_a) float64 [..., L] by the rules of frequency_summary."""
+    a, w, ep = X[..., 2], X[..., 3], X[..., 0]
+    ra = np.concatenate([_ratio(a[..., :1], w[..., :1]), _ratio(a[..., 1:], a[..., :-1])], axis=-1)
+    rep = np.concatenate([np.full_like(ep[..., :1], np.nan), _ratio(ep[..., 1:], ep[..., :-1])], axis=-1)
+    return np.abs(ra), np.abs(rep), np.angle(ra)
+
+
+def _peaks(gain_a, freqs_hz, axis):
+    """Per vehicle the largest defined gain_a over the frequency axis, its index (-1: none defined) and frequency, and string_stable."""
+    g = np.moveaxis(np.asarray(gain_a, dtype=np.float64), axis, 0)
+    defined = ~np.isnan(g)
+    filled = np.where(defined, g, -np.inf)
+    idx = np.where(defined.any(axis=0), filled.argmax(axis=0), -1)
+    peak = np.where(idx >= 0, np.take_along_axis(filled, np.maximum(idx, 0)[None], axis=0)[0], np.nan)
+    out = dict(peak_gain_a=peak, peak_index=idx, string_stable=np.all(np.isnan(peak) | (peak <= 1), axis=-1))
+    if freqs_hz is not None:
+        out["peak_freq_hz"] = np.where(idx >= 0, np.asarray(freqs_hz, dtype=np.float64)[np.maximum(idx, 0)], np.nan)
+    return out
+
+
+def frequency_summary(spectrum, W, freqs_hz=None, axis=0):
+    """Derived values from raw sums [..., L, NSPEC] whose axis ``axis`` is the frequency axis, in float64: the complex amplitudes X =
+    (2 / W) (re - j im) as ``amp`` and ``phase`` [..., L, 5] (SIGNALS order); gain_a[i] = |A_i| / |A_{i-1}|, vehicle 0 against its own w
+    (the leader's acceleration as its model holds it); gain_ep[i] = |EP_i| / |EP_{i-1}|, NaN for vehicle 0; phase_a the angle of
+    gain_a's ratio; a ratio is NaN where its denominator is 0. Per vehicle, peak_gain_a over the frequency axis, its peak_index and
+    (with ``freqs_hz``) peak_freq_hz; string_stable [...] is True when every defined peak is <= 1.
+    The states are sampled post-step and u pre-step, against the angle of the step: every state carries one step's phase lead over u.
+    The magnitudes, and the ratios between states, do not depend on it."""
+    sp = np.asarray(spectrum, dtype=np.float64)
+    if sp.shape[-1] != NSPEC:
+        raise ValueError(f"spectrum of shape {sp.shape}: the last axis holds the {NSPEC} sums")
+    X = (2.0 / float(W)) * (sp[..., 0::2] - 1j * sp[..., 1::2])
+    ga, gep, pa = _gains_of(X)
+    out = dict(amp=np.abs(X), phase=np.angle(X), gain_a=ga, gain_ep=gep, phase_a=pa)
+    out.update(_peaks(ga, freqs_hz, axis))
+    return out
+
+
+def linear_frequency_response(conf, gains, cycles, W, dyn_coeff=None):
+    """The float64 THEORY of an unclipped linear law on the nominal observation: per frequency z = exp(2 pi j cycles / W) and vehicle i,
+    X_i = (z I - A_i - B_i g_i^T)^-1 C_i exog_i with exog_0 = 1 (the leader's input), and for i >= 1 exog_i = g_{i-1}^T X_{i-1} under
+    Model B (the predecessor's plant input) or the predecessor's post-step acceleration z X_{i-1}[2] under Model A (whose law reads the
+    first three states only). gains [L, 4]; the matrices are dynamics.system_matrices with env_consts' tau chaining and every follower's
+    engine lag ``dyn_coeff`` (None: conf.dyn_coeff). -> dict(X complex [F, L, 5] (SIGNALS order, per unit leader input), gain_a, gain_ep,
+    phase_a [F, L], and frequency_summary's peaks over the frequency axis)."""
+    from . import dynamics
+
+    g = np.asarray(gains, dtype=np.float64)
+    L = int(conf.pl_size)
+    if g.shape != (L, 4):
+        raise ValueError(f"gains of shape {g.shape}: need [{L}, 4]")
+    model_a = conf.model == conf.modelA
+    if model_a:
+        g = g * np.array([1.0, 1.0, 1.0, 0.0])
+    tau = float(conf.dyn_coeff if dyn_coeff is None else dyn_coeff)
+    cyc = np.atleast_1d(np.asarray(cycles, dtype=np.float64))
+    X = np.zeros((cyc.shape[0], L, 5), dtype=np.complex128)
+    for f, c in enumerate(cyc):
+        z = np.exp(2j * np.pi * c / float(W))
+        exog = 1.0 + 0j
+        for i in range(L):
+            A, B, Cm = dynamics.system_matrices(conf.method, conf.sample_rate, tau, conf.pl_leader_tau if i == 0 else tau, conf.timegap)
+            x = np.linalg.solve(z * np.eye(4) - A - np.outer(B, g[i]), Cm * exog)
+            u = g[i] @ x
+            X[f, i, :4], X[f, i, 4] = x, u
+            exog = z * x[2] if model_a else u
+    ga, gep, pa = _gains_of(X)
+    out = dict(X=X, gain_a=ga, gain_ep=gep, phase_a=pa)
+    out.update(_peaks(ga, None, 0))
+    return out
+
+
+FREQUENCY_HEADER = ["controller", "disturbance", "seed", "freq_hz", "cycles", "vehicle", *[f"amp_{n}" for n in SIGNALS],
+                    *[f"phase_{n}" for n in SIGNALS], "gain_a", "gain_ep", "phase_a", "gain_a_theory"]
+
+
+def frequency_rows(results, tags, theory=None):
+    """One row per (controller, disturbance, seed, frequency, vehicle) of a FrequencyResults (spectrum [G, F, ND, NS, L, NSPEC]): the
+    frequency driven and its cycle count, the five amplitudes and phases, gain_a, gain_ep, phase_a and gain_a_theory -- ``theory``
+    float64 [G, ND, F, L] for laws (linear_frequency_response with each level's dyn_coeff), None for actors: the column stays empty.
+    Numbers are written with repr(float); a NaN is an empty field. tags: the first column's value per controller."""
+    s = results.summary()
+    f = lambda x: "" if np.isnan(x) else repr(float(x))
+    rows = []
+    for i, tag in enumerate(tags):
+        for d, level in enumerate(results.disturbances):
+            for k, seed in enumerate(results.seeds):
+                for q, hz in enumerate(results.freqs_hz):
+                    for v in range(results.spectrum.shape[-2]):
+                        at = (i, q, d, k, v)
+                        rows.append([tag, level, seed, repr(float(hz)), int(results.cycles[q]), v + 1, *[f(x) for x in s["amp"][at]],
+                                     *[f(x) for x in s["phase"][at]], f(s["gain_a"][at]), f(s["gain_ep"][at]), f(s["phase_a"][at]),
+                                     "" if theory is None else f(theory[i, d, q, v])])
+    return rows
+
+
+def write_frequency_csv(path, entries):
+    """frequency.csv: entries is a list of (results, tags, theory) as frequency_rows takes them (the actors', then the laws')."""
+    import csv
+
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(FREQUENCY_HEADER)
+        for results, tags, theory in entries:
+            w.writerows(frequency_rows(results, tags, theory))
+
+
+def frequency_peaks(results, tags):
+    """[[controller, level, peak gain_a, its frequency (Hz), its vehicle (1-based), string_stable]] per controller and level: gain_a is
+    averaged over the seeds first, then the peak is taken over frequencies and vehicles."""
+    ga = results.summary()["gain_a"]
+    n = np.sum(~np.isnan(ga), axis=3)
+    g = np.where(n > 0, np.nansum(ga, axis=3) / np.maximum(n, 1), np.nan)  # [G, F, ND, L]: the mean of the defined seeds
+    out = []
+    for i, tag in enumerate(tags):
+        for d, level in enumerate(results.disturbances):
+            p = _peaks(g[i, :, d], results.freqs_hz, 0)
+            if np.all(np.isnan(p["peak_gain_a"])):
+                out.append([tag, level, None, None, None, bool(p["string_stable"])])
+                continue
+            v = int(np.nanargmax(p["peak_gain_a"]))
+            out.append([tag, level, float(p["peak_gain_a"][v]), float(p["peak_freq_hz"][v]), v + 1, bool(p["string_stable"])])
+    return out
+
+
+def frequency_report_lines(results, tags, what="platoon"):
+    """One line per controller and level: the peak gain_a, where it is and whether the string is stable."""
+    return [f"{what} {tag} {level}: peak gain_a " + ("undefined" if pk is None else f"{pk:.4f} at {hz:.4f} Hz (vehicle {v})") +
+            f" string_stable {ok}" for tag, level, pk, hz, v, ok in frequency_peaks(results, tags)]
+
+
 # ---- disturbances: what the disturbed scenario evaluator (avd_eval_cases_dist_f32) applies per case ---------------------------------
 
 MAX_DELAY = 15  # AVD_EVAL_MAX_DELAY

@@ -898,6 +898,23 @@ class VecTrainer:
             return np.repeat(sc[:, 0], len(platoons))
         return evaluator.run_many(self.conf, agents, platoons, base_law=self.residual)[0][:, 0]
 
+    def _evaluator_addressing(self, platoons):
+        """How the scenario evaluators address this trainer's actors for ``platoons`` (default: all; a seed batch or sweep: each
+        experiment's own) -> (entries, keywords, lift): the platoon entries and set_mod / set_bases keywords of evaluator.run_cases and
+        its kin, and the map from a result array (first axis: the entries) to the caller's -- [P, ...], or [E, P, ...] for a seed batch
+        or sweep. Shared sets: one group of rollouts (per experiment), repeated per platoon."""
+        if self.seeds is not None:
+            E, M = self.E, self.M
+            platoons = list(range(self.P_exp)) if platoons is None else list(platoons)
+            n = len(platoons)
+            if self.shared:  # one group per experiment, on its sets e*M .. e*M+M-1
+                return list(range(E)), dict(set_mod=M, set_bases=[e * M for e in range(E)]), lambda x: np.repeat(x[:, None], n, axis=1)
+            return [vec.batch_platoon(e, p, E) for e in range(E) for p in platoons], {}, lambda x: x.reshape(E, n, *x.shape[1:])
+        platoons = list(range(self.P)) if platoons is None else list(platoons)
+        if self.shared:
+            return [0], dict(set_mod=self.M), lambda x: np.repeat(x, len(platoons), axis=0)
+        return platoons, {}, lambda x: x
+
     def evaluate_scenarios(self, scenarios, seeds=None, platoons=None, amp=None, period_s=10.0, agents=None):
         """The CURRENT actors of each of this rank's ``platoons`` (default: all) over leader scenarios x evaluation seeds, from one
         launch of the scenario evaluator (evaluator.run_cases): a CaseResults with scores [P, scen, seed], counters [P, scen, seed, M]
@@ -907,24 +924,10 @@ class VecTrainer:
         from . import evaluator
 
         agents = self.agents if agents is None else agents  # (or a group laid out like it: best_agents())
-        kw = dict(scenarios=scenarios, seeds=seeds, amp=amp, period_s=period_s, base_law=self.residual)
-        if self.seeds is not None:
-            E, M = self.E, self.M
-            platoons = list(range(self.P_exp)) if platoons is None else list(platoons)
-            n = len(platoons)
-            if self.shared:  # one group per experiment, on its sets e*M .. e*M+M-1
-                r = evaluator.run_cases(self.conf, agents, list(range(E)), set_mod=M, set_bases=[e * M for e in range(E)], **kw)
-                lift = lambda x: np.repeat(x[:, None], n, axis=1)
-            else:
-                r = evaluator.run_cases(self.conf, agents, [vec.batch_platoon(e, p, E) for e in range(E) for p in platoons], **kw)
-                lift = lambda x: x.reshape(E, n, *x.shape[1:])
-            return evaluator.CaseResults(r.scenarios, r.seeds, r.T, lift(r.scores), lift(r.counters), {k: lift(v) for k, v in r.metrics.items()})
-        platoons = list(range(self.P)) if platoons is None else list(platoons)
-        if self.shared:
-            r = evaluator.run_cases(self.conf, agents, [0], set_mod=self.M, **kw)
-            rep = lambda x: np.repeat(x, len(platoons), axis=0)
-            return evaluator.CaseResults(r.scenarios, r.seeds, r.T, rep(r.scores), rep(r.counters), {k: rep(v) for k, v in r.metrics.items()})
-        return evaluator.run_cases(self.conf, agents, platoons, **kw)
+        entries, addr, lift = self._evaluator_addressing(platoons)
+        r = evaluator.run_cases(self.conf, agents, entries, scenarios=scenarios, seeds=seeds, amp=amp, period_s=period_s,
+                                base_law=self.residual, **addr)
+        return evaluator.CaseResults(r.scenarios, r.seeds, r.T, lift(r.scores), lift(r.counters), {k: lift(v) for k, v in r.metrics.items()})
 
     def evaluate_robustness(self, scenarios, disturbances, seeds=None, platoons=None, amp=None, period_s=10.0, agents=None):
         """evaluate_scenarios under disturbances: the CURRENT actors of each of this rank's ``platoons`` over leader scenarios x
@@ -935,23 +938,26 @@ class VecTrainer:
         from . import evaluator
 
         agents = self.agents if agents is None else agents  # (or a group laid out like it: best_agents())
-        kw = dict(scenarios=scenarios, disturbances=disturbances, seeds=seeds, amp=amp, period_s=period_s, base_law=self.residual)
-        mapped = lambda r, f: evaluator.DisturbedResults(r.scenarios, r.disturbances, r.seeds, r.T, f(r.scores), f(r.counters),
-                                                         {k: f(v) for k, v in r.metrics.items()})
-        if self.seeds is not None:
-            E, M = self.E, self.M
-            platoons = list(range(self.P_exp)) if platoons is None else list(platoons)
-            n = len(platoons)
-            if self.shared:  # one group per experiment, on its sets e*M .. e*M+M-1
-                r = evaluator.run_disturbed(self.conf, agents, list(range(E)), set_mod=M, set_bases=[e * M for e in range(E)], **kw)
-                return mapped(r, lambda x: np.repeat(x[:, None], n, axis=1))
-            r = evaluator.run_disturbed(self.conf, agents, [vec.batch_platoon(e, p, E) for e in range(E) for p in platoons], **kw)
-            return mapped(r, lambda x: x.reshape(E, n, *x.shape[1:]))
-        platoons = list(range(self.P)) if platoons is None else list(platoons)
-        if self.shared:
-            r = evaluator.run_disturbed(self.conf, agents, [0], set_mod=self.M, **kw)
-            return mapped(r, lambda x: np.repeat(x, len(platoons), axis=0))
-        return evaluator.run_disturbed(self.conf, agents, platoons, **kw)
+        entries, addr, lift = self._evaluator_addressing(platoons)
+        r = evaluator.run_disturbed(self.conf, agents, entries, scenarios=scenarios, disturbances=disturbances, seeds=seeds, amp=amp,
+                                    period_s=period_s, base_law=self.residual, **addr)
+        return evaluator.DisturbedResults(r.scenarios, r.disturbances, r.seeds, r.T, lift(r.scores), lift(r.counters),
+                                          {k: lift(v) for k, v in r.metrics.items()})
+
+    def evaluate_frequency(self, spec, disturbances=(), seeds=None, platoons=None, agents=None):
+        """The frequency response of the CURRENT actors of each of this rank's ``platoons`` (default: all): ``spec`` (a
+        scenarios.FrequencySpec) over frequencies x [nominal, *disturbances] x evaluation seeds, from one launch of the frequency
+        evaluator (evaluator.run_frequency; a residual policy's law in front of the plant): a FrequencyResults with spectrum [P, F,
+        dist, seed, L, 10], scores [P, F, dist, seed], counters and metrics. Platoons and experiments are addressed as in
+        evaluate_scenarios: a seed batch or sweep gives every array a leading experiment axis, experiment e's slice equal to
+        run_frequency on experiment_agents(e)."""
+        from . import evaluator
+
+        agents = self.agents if agents is None else agents  # (or a group laid out like it: best_agents())
+        entries, addr, lift = self._evaluator_addressing(platoons)
+        r = evaluator.run_frequency(self.conf, agents, entries, spec, disturbances, seeds, base_law=self.residual, **addr)
+        return evaluator.FrequencyResults(r.freqs_hz, r.cycles, r.W, r.T, r.disturbances, r.seeds, lift(r.spectrum), lift(r.scores),
+                                          lift(r.counters), {k: lift(v) for k, v in r.metrics.items()})
 
     def run_simulations(self, agents=None):
         """Trainer.run_simulations (workers/trainer.py:537-550): every local platoon's evaluator score over steps_per_episode

@@ -815,6 +815,29 @@ int avd_eval_cases_res_f32(const avd_mlp_layout* lay, const avd_env_consts* d_co
                            const float* sigma, const int32_t* delay, const uint32_t* drop_q, const uint64_t* noise_seed,
                            const float* abc, const float* d_gains, float scale, float* counters, float* metrics, void* stream);
 
+/* ---- frequency response: the scenario evaluators with a single-bin Fourier sum per vehicle and signal -------------------------------
+ * A frequency sweep is a set of cases: case k's leader row is a sinusoid and basis[k] [T][2] (DEVICE memory, 8-byte aligned) holds,
+ * per step, the pair (c, s) = (cos, sin) of the case's angle inside the measuring window and (0, 0) before it. At step t of case k,
+ * for the four components of the post-step true state and for the step's plant input u, in float32 without contraction,
+ *   re = re + x * c;   im = im + x * s        (sequential adds in step order, the product rounded first)
+ * and spectrum[g][k] [L][AVD_EVAL_NSPEC] receives the raw sums (re, im) of ep, ev, a, w, u in that order; the host scales them
+ * (scenarios.frequency_summary). Counters and metrics are the twin entry point's, bit for bit.
+ * avd_eval_cases_freq_f32: avd_eval_cases_res_f32's arguments; all five disturbance tables NULL is the nominal plant
+ * (avd_eval_cases_f32's block sizes), d_gains NULL means no residual law (scale unread, M = 1 allowed). A set_base out of range makes
+ * the group's spectrum NaN as well. avd_eval_linear_freq_f32: avd_eval_linear_f32's arguments. Both refuse, on the host and before any
+ * HIP call, what their twins refuse, a NULL basis or spectrum and a basis that is not 8-byte aligned. */
+#define AVD_EVAL_NSPEC 10
+int avd_eval_cases_freq_f32(const avd_mlp_layout* lay, const avd_env_consts* d_consts, int G, int K, int L, int M, int T,
+                            const float* theta, const float* stats, int n_sets, const int32_t* set_base, const float* x0,
+                            const float* prev_a0, const float* leader, float high, float lo, float hi, float sample_rate,
+                            const float* sigma, const int32_t* delay, const uint32_t* drop_q, const uint64_t* noise_seed,
+                            const float* abc, const float* d_gains, float scale, float* counters, float* metrics, const float* basis,
+                            float* spectrum, void* stream);
+int avd_eval_linear_freq_f32(const avd_env_consts* d_consts, int G, int K, int L, int T, const float* gains, const float* x0,
+                             const float* prev_a0, const float* leader, float lo, float hi, float sample_rate, const float* sigma,
+                             const int32_t* delay, const uint32_t* drop_q, const uint64_t* noise_seed, const float* abc,
+                             float* counters, float* metrics, const float* basis, float* spectrum, void* stream);
+
 /* D[M][Nc] (f32, ldd) = A[M][K] . B[Nc][K]^T with bf16 operands (K contiguous, K % 64 == 0) and f32 accumulation: the
  * GEMM under avd_learn_shared_bf16, exposed for parity tests. A and B must be readable up to the next multiple of 256
  * rows. */
