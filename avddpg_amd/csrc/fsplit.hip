@@ -305,9 +305,18 @@ __global__ __launch_bounds__(320) void prep_kernel(const PrepArgs a) {
     const float SW = pow2_for(__uint_as_float(mx)), SWC = pow2_for(__uint_as_float(mxc));
     // what the prep1 and pack roles of the front launch found (they cannot set *bad themselves: that launch clears it): the blocks of
     // net 0, set 0 share the words between them
-    if (net == 0 && set == 0)
-        for (int w = n * 320 + f; w < a.n_fflag; w += H2 * 320)
-            if (a.fflag[w]) atomicOr(a.bad, 1);
+    // (r14: four words per wait -- clamped index, masked value -- where a rolled loop waited for each word in turn)
+    if (net == 0 && set == 0) {
+        unsigned any = 0;
+        for (int w0 = n * 320 + f; w0 < a.n_fflag; w0 += 4 * H2 * 320) {
+            unsigned v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = a.fflag[min(w0 + u * H2 * 320, a.n_fflag - 1)];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) any |= w0 + u * H2 * 320 < a.n_fflag ? v[u] : 0u;
+        }
+        if (any) atomicOr(a.bad, 1);
+    }
     float shw = 0.f;
     if (f < KP) {
         float w = 0.f, inv = 0.f;
@@ -529,19 +538,6 @@ __global__ __launch_bounds__(NT) void head_kernel(const HeadArgs p, H... hp) {
     __shared__ __attribute__((aligned(16))) unsigned waps[BOTH ? 48 : 4];
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5, q = w >> 1, rh = w & 1;
     const int set = blockIdx.x % p.n_sets, j0 = blockIdx.x / p.n_sets, J = gridDim.x / p.n_sets, P = p.n_agents / p.n_sets;
-    for (int i = tid; i < 2 * H2 * (K / 8); i += NTH) {
-        const int hl = i / (H2 * (K / 8)), rem = i - hl * (H2 * (K / 8)), n = rem / (K / 8), c = rem - n * (K / 8);
-        const f16* src = (hl ? p.net.Wlo : p.net.Whi) + ((long)set * H2 + n) * K + 8 * c;
-        *(uint4*)(&wimg[hl][n * LD + 8 * c]) = *(const uint4*)src;
-    }
-    const float* vec = p.net.vec + (long)set * VEC;
-    // acc = SW S1 z2: the scales of the fp16 operands are folded into the f32 tables (bias in, output weights out)
-    const float SW = vec[2 * H2 + 1], sc = SW * S1, isc = 1.f / sc;
-    if (tid < H2) b2s[tid] = vec[tid] * sc, c3s[tid] = vec[H2 + tid] * isc;
-    if (BOTH && tid < 48) waps[tid] = p.net.wap[(long)set * 48 + tid];
-    const float d3 = vec[2 * H2];
-    const f16x8* wf1 = p.net.wf1h + (long)set * NGT_MAX * 64 + lane;  // + 64 ft
-    const f32x16 zero16 = {};
 #ifdef AVD_STAMP
     unsigned long long hacc[4] = {0, 0, 0, 0}, hlast = __builtin_amdgcn_s_memtime();
     const unsigned long long hstart = hlast;
@@ -549,19 +545,9 @@ __global__ __launch_bounds__(NT) void head_kernel(const HeadArgs p, H... hp) {
 #else
 #define HSTAMP(i)
 #endif
-    float Dacc = 0.f, Lacc = 0.f, Dacc2 = 0.f, Lacc2 = 0.f, gmax = 0.f;
-    // fp16 overflow watch. An activation S1 P1 >= 65520 converts to the pair (hi, lo) = (+inf, -inf), and whatever the weights,
-    // w_hi inf + w_lo inf - w_hi inf is NaN in EVERY second-layer accumulator of that batch row (0 inf is NaN too): one
-    // accumulator per row and sweep is looked at (bit test: the file is built with -fno-honor-nans), |bits| max-accumulated.
-    unsigned watch = 0;
-    auto look = [&](float x) {
-        unsigned u = __float_as_uint(x);
-        asm volatile("" : "+v"(u));  // (keeps the no-nans optimiser from reasoning about the float)
-        u &= 0x7fffffffu;
-        watch = watch > u ? watch : u;
-    };
-    __syncthreads();
-
+    const float* vec = p.net.vec + (long)set * VEC;
+    const f16x8* wf1 = p.net.wf1h + (long)set * NGT_MAX * 64 + lane;  // + 64 ft
+    const f32x16 zero16 = {};
     const int ntile = j0 < P ? (P - j0 + J - 1) / J : 0;  // tiles of this workgroup: j0, j0 + J, ..
     const int row = 32 * rh + r;
     f16x8 nx = {};
@@ -576,11 +562,6 @@ __global__ __launch_bounds__(NT) void head_kernel(const HeadArgs p, H... hp) {
         if (BOTH) ny = p.yin[ri];
         if (BOTH && p.aw) nw = p.aw[agent];
     };
-    const f16* whi0 = &wimg[0][r * LD + 8 * h];  // + 32 t LD + 16 ks
-    const f16* wlo0 = &wimg[1][r * LD + 8 * h];
-    // the sequence of feature tiles of a unit: tiles 0 .. NFT - 1; HEAD_BOTH: + the action tiles 8, 9 once more (input mu)
-    constexpr int NSEQ = BOTH ? 8 : NFT;  // HEAD_BOTH: the state tiles; the action tiles are streamed per column tile below
-    HSTAMP(3);  // image fill, tables, first fetch
     // The two waves of a SIMD (w and w + 4) are arbitrated oldest first: with equal shares, waves 0..3 ran 12.0 k cycles per unit
     // and waves 4..7 20.4 k until the old ones were done, then finished alone at 61 % of the matrix pipe (s_memtime stamps, r03;
     // s_setprio does not change it). The tiles are therefore dealt FAST : SLOW per wave pair in periods of 2 (FAST + SLOW) tiles
@@ -590,7 +571,56 @@ __global__ __launch_bounds__(NT) void head_kernel(const HeadArgs p, H... hp) {
     const int cnt = qs < 2 ? FAST : SLOW, start = qs < 2 ? qs * FAST : 2 * FAST + (qs - 2) * SLOW;
     int k = start, pos = 0;  // the wave pair's current tile and its place in the pair's group of cnt
     auto next_tile = [&](int kk, int pp) { return pp + 1 == cnt ? kk + PERIOD - cnt + 1 : kk + 1; };
+    // Start-up (r14): EVERY load in front of the barrier is requested before the first of them is waited for -- the tables, the
+    // first tile's first-layer fragments (only to have their lines near: the tile loop reads them itself), the wave's first inputs,
+    // then the thread's whole share of the weight image (16 / 19 x 16 bytes in registers: the accumulators are not alive yet) --
+    // and only then stored to LDS. As a rolled loop of load, wait, store the image alone was 16 / 19 dependent round trips of all
+    // 51 workgroups of a set to the same lines, with the tables and the first fetch serially behind it.
+    const float SW = vec[2 * H2 + 1], d3 = vec[2 * H2];
+    const float vb = vec[tid & (H2 - 1)], vc = vec[H2 + (tid & (H2 - 1))];
+    unsigned wv = 0;
+    if constexpr (BOTH) wv = p.net.wap[(long)set * 48 + (tid < 48 ? tid : 47)];
+    f16x8 warm0 = wf1[0], warm1 = wf1[64];
     if (k < ntile) fetch_in(k);
+    // the image: thread tid takes the 16-byte chunks tid, tid + NTH, .. of [hi | lo][n][K / 8], contiguous in global memory
+    constexpr int PER = H2 * (K / 8), NLD = 2 * PER / NTH;
+    static_assert(2 * PER % NTH == 0, "the image is a whole number of chunks per thread");
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    u32x4 img[NLD];
+    static_for<0, NLD>([&](auto u_c) {  // (static_for: constant indices, the array never exists in memory)
+        constexpr int u = decltype(u_c)::value;
+        const int i = tid + u * NTH, hl = i / PER, rem = i - hl * PER;
+        img[u] = *(const u32x4*)((hl ? p.net.Wlo : p.net.Whi) + (long)set * H2 * K + 8 * rem);
+    });
+    __builtin_amdgcn_sched_barrier(0);
+    // acc = SW S1 z2: the scales of the fp16 operands are folded into the f32 tables (bias in, output weights out)
+    const float sc = SW * S1, isc = 1.f / sc;
+    if (tid < H2) b2s[tid] = vb * sc, c3s[tid] = vc * isc;
+    if (BOTH && tid < 48) waps[tid] = wv;
+    static_for<0, NLD>([&](auto u_c) {
+        constexpr int u = decltype(u_c)::value;
+        const int i = tid + u * NTH, hl = i / PER, rem = i - hl * PER, n = rem / (K / 8), c = rem - n * (K / 8);
+        *(u32x4*)(&wimg[hl][n * LD + 8 * c]) = img[u];
+    });
+    asm volatile("" ::"v"(warm0), "v"(warm1));
+    float Dacc = 0.f, Lacc = 0.f, Dacc2 = 0.f, Lacc2 = 0.f, gmax = 0.f;
+    // fp16 overflow watch. An activation S1 P1 >= 65520 converts to the pair (hi, lo) = (+inf, -inf), and whatever the weights,
+    // w_hi inf + w_lo inf - w_hi inf is NaN in EVERY second-layer accumulator of that batch row (0 inf is NaN too): one
+    // accumulator per row and sweep is looked at (bit test: the file is built with -fno-honor-nans), |bits| max-accumulated.
+    unsigned watch = 0;
+    auto look = [&](float x) {
+        unsigned u = __float_as_uint(x);
+        asm volatile("" : "+v"(u));  // (keeps the no-nans optimiser from reasoning about the float)
+        u &= 0x7fffffffu;
+        watch = watch > u ? watch : u;
+    };
+    __syncthreads();
+
+    const f16* whi0 = &wimg[0][r * LD + 8 * h];  // + 32 t LD + 16 ks
+    const f16* wlo0 = &wimg[1][r * LD + 8 * h];
+    // the sequence of feature tiles of a unit: tiles 0 .. NFT - 1; HEAD_BOTH: + the action tiles 8, 9 once more (input mu)
+    constexpr int NSEQ = BOTH ? 8 : NFT;  // HEAD_BOTH: the state tiles; the action tiles are streamed per column tile below
+    HSTAMP(3);  // image fill, tables, first fetch (from the kernel's first instruction)
     for (int ui = 0; k < ntile; ++ui, k = next_tile(k, pos), pos = pos + 1 == cnt ? 0 : pos + 1) {
         const int agent = (j0 + k * J) * p.n_sets + set;
         const long ri = (long)agent * TILE + row;
@@ -986,7 +1016,7 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
     __shared__ float gred[8];
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
     const int set = blockIdx.x % p.n_sets, j0 = blockIdx.x / p.n_sets, J = gridDim.x / p.n_sets, P = p.n_agents / p.n_sets;
-    const float gsc = set_gscale(p.part_m, set, p.n_sets, J, gred);  // 2^kg
+    float gsc;  // 2^kg: set_gscale, below -- behind the requests for everything that does not depend on it
     const f16x8* wf1 = p.net.wf1h + (long)set * NGT_MAX * 64 + lane;
     // this wave's extra piece
     const int xt = NET::critic ? 8 + (w >> 2) : 8, xrh = NET::critic ? (w >> 1) & 1 : (w >> 2) & 1, xc0 = NET::critic ? 2 * (w & 1) : (w & 3);
@@ -1152,6 +1182,9 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
     if (j0 < P) fetch_m(j0, ma, ga);
     fetch_x(j0);
     if (j0 + J < P) fetch_m(j0 + J, mb, gb);
+    // (r14) the weight fragments and the first two tiles' operands are in flight while set_gscale loads, reduces and meets its
+    // barrier: one round trip to memory in front of the tile loop, not two in a row
+    gsc = set_gscale(p.part_m, set, p.n_sets, J, gred);
     stage_m(0, ma, ga), stage_x(j0, 0);
     __syncthreads();
 #ifdef AVD_STAMP
@@ -1258,7 +1291,6 @@ __global__ __launch_bounds__(NT) void dx_kernel(const DxArgs p) {
     const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, r = lane & 31, h = lane >> 5, ft = w;
     const int set = blockIdx.x % p.n_sets, j0 = blockIdx.x / p.n_sets, J = gridDim.x / p.n_sets, P = p.n_agents / p.n_sets;
     const f32x16 zero16 = {};
-    const float gsc = set_gscale(p.part_m, set, p.n_sets, J, gred);  // 2^kg
     f16x8 wch[8], wcl[8];
     {
         const long at = ((long)set * KP + 32 * ft + r) * H2 + 8 * h;
@@ -1269,7 +1301,7 @@ __global__ __launch_bounds__(NT) void dx_kernel(const DxArgs p) {
     // on the fp16 W2c operand) -- |dC_s| <= 128 x 2^13 and |g3| 2^kg < 1 give |d_s| < 2^15: the fp16 pair of the masked gradient
     // cannot overflow -- and the per-feature sums are divided by vs once, at the end (powers of two: exact).
     const float swc = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(p.net.vec[(long)set * VEC + 2 * H2 + 2])));
-    const float gv = gsc * VSH, vs = gsc * swc * VSH;
+    float gv, vs;  // gsc VSH, gsc swc VSH: behind set_gscale, which runs AFTER the first two tiles' fetches are out (below)
     const f16x8 wf = p.net.wf1h[((long)set * NGT_MAX + ft) * 64 + lane];  // (scaled by S1: p1 = S1 z1, U1 rescaled at the end)
     f32x16 V = zero16;
     for (int i = tid; i < 3 * 2 * 32 * 32; i += NT) {  // columns 9.. stay zero, column 8 is the ones column (bias)
@@ -1436,12 +1468,30 @@ __global__ __launch_bounds__(NT) void dx_kernel(const DxArgs p) {
         if (!(FSPLIT_ABL(p.abl) & 2)) __syncthreads();
         DXSTAMP(3);
     };
-    __syncthreads();  // the zero / ones fill above before the first stage_x
+    // (r14) Start-up: the resident fragments (above), tile j0 and tile j0 + J are all requested before set_gscale's own loads, so
+    // that ONE round trip to memory stands in front of the tile loop; until r14 the chain was scale -> barrier -> fragments and
+    // tile j0 -> its staging -> tile j0 + J. The first tile waits in a second set of registers until the scale is known.
+    unsigned dm0 = 0;
+    float gn0 = 0.f, gs0 = 0.f;
+    f16x8 xfa = {}, xfb = {};
     if (j0 < P) {
-        fetch(j0), fetch_x(j0), stage(0, 0), stage_x(0);
-        xf0 = xfn0, xf1 = xfn1;
+        fetch(j0), fetch_x(j0);
+        dm0 = dm, gn0 = gn, gs0 = gs, xfa = xfn0, xfb = xfn1;
         const int n1 = j0 + J < P ? j0 + J : j0;
         fetch(n1), fetch_x(n1);
+    }
+    {
+        const float gsc = set_gscale(p.part_m, set, p.n_sets, J, gred);  // 2^kg (its barrier: also the zero / ones fill above before the first stage_x)
+        gv = gsc * VSH, vs = gsc * swc * VSH;
+    }
+    if (j0 < P) {
+        const unsigned dm1 = dm;
+        const float gn1 = gn, gs1 = gs;
+        const f16x8 xfc = xfn0, xfd = xfn1;
+        dm = dm0, gn = gn0, gs = gs0, xfn0 = xfa, xfn1 = xfb;
+        stage(0, 0), stage_x(0);
+        xf0 = xfn0, xf1 = xfn1;
+        dm = dm1, gn = gn1, gs = gs1, xfn0 = xfc, xfn1 = xfd;
     }
     __syncthreads();
     if (j0 < P) {
@@ -1494,7 +1544,6 @@ __global__ __launch_bounds__(NT) void dxa_kernel(const DxArgs p) {
     const int set = blockIdx.x % p.n_sets, j0 = blockIdx.x / p.n_sets, J = gridDim.x / p.n_sets, P = p.n_agents / p.n_sets;
     const f32x16 zero16 = {};
     const int ft = 8 + ftl, f = 32 * ftl + r;  // this lane's action feature (f >= 48: padding, zero weights)
-    const float gsc = set_gscale(p.part_m, set, p.n_sets, J, gred);
     f16x8 wch[8], wcl[8];
     {
         const long at = ((long)set * KP + 32 * ft + r) * H2 + 8 * h;
@@ -1502,7 +1551,6 @@ __global__ __launch_bounds__(NT) void dxa_kernel(const DxArgs p) {
         for (int s = 0; s < 8; ++s) wch[s] = *(const f16x8*)(p.net.Wchi + at + 16 * s), wcl[s] = *(const f16x8*)(p.net.Wclo + at + 16 * s);
     }
     const float swc = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(p.net.vec[(long)set * VEC + 2 * H2 + 2])));
-    const float gv = gsc * VSH, vs = gsc * swc * VSH;  // the scaled domain of dx_kernel (nothing here needs it for range: one scale for both kernels)
     const float* th = p.net.th + (long)set * p.net.th_stride;
     const float wa = f < HA ? th[p.L_cWa + f] : 0.f, ba = f < HA ? th[p.L_cba + f] : 0.f;
     float Sa = 0.f, Sb = 0.f;
@@ -1552,6 +1600,9 @@ __global__ __launch_bounds__(NT) void dxa_kernel(const DxArgs p) {
     };
     if (par < ntile) DXA_FETCH(par, mA, gA, aA);
     if (par + 2 < ntile) DXA_FETCH(par + 2, mB, gB, aB);
+    // (r14) the row factor's scale LAST: the resident fragments and both prefetched units are in flight under its loads and barrier
+    const float gsc = set_gscale(p.part_m, set, p.n_sets, J, gred);
+    const float gv = gsc * VSH, vs = gsc * swc * VSH;  // the scaled domain of dx_kernel (nothing here needs it for range: one scale for both kernels)
     for (int k = par; k < ntile; k += 4) {
         DXA_PUT(0, gA, aA);
         {
@@ -1663,9 +1714,37 @@ static int check_shape(const avd_mlp_layout* L, int n_agents, int n_sets, const 
 //   (fset.hip launch_finalize: column items; W2 rows | feature items; t1 -- 41 us where four launches took 48). Every cross-block
 //   dependence is a launch boundary; the workspace and the slab may hold anything when a call begins (tests/test_gpu_fsplit_glue.py).
 //   Same box, 400-learn rounds alternated: 1785.5-1786.5 -> 1754.6-1757.0 us per learn (profiles/r09_glue_ab_learn_time.txt).
+//   r14: what a workgroup of the ten persistent kernels does in front of its first tile. The heads filled their LDS weight image in a
+//   rolled loop of load, wait, store -- 16 (actor) / 19 (critic) dependent round trips per thread, all workgroups of a set on the same
+//   lines, the tables and the first fetch behind it; dw / dx / dxa ran set_gscale (loads, a reduction, a barrier) BEFORE they asked for
+//   their resident fragments and first tiles. Now every load in front of the first barrier is requested before the first wait (heads:
+//   21-28 in flight, the image held in registers the accumulators do not need yet) and set_gscale runs behind the requests. No
+//   arithmetic, tile map or LDS layout changed: same bits (profiles/r14_startup_bit_identity.txt), same registers, no scratch
+//   (r14_startup_static.txt). Heads' start-up 12.4-16.9 k -> 6.6-8.0 k cycles, 2.6-4.1 % -> 1.3-2.2 % of the kernel (r14_startup_stamps.txt);
+//   same box, 400-learn rounds alternated: 1775.7-1780.6 -> 1727.4-1731.0 us per learn (r14_startup_ab_learn_time.txt).
 //   Not done: finalize in TWO launches -- finalize_w2 is not independent of the column items (it adds sh1 * db2 read back from the
 //   slab), so the column items keep a launch of their own; the actor seed folded into HEAD_BOTH (7 us and a boundary: not tried).
 enum Phase { PH_CRITIC = 1, PH_ACTOR = 2, PH_BOTH = 3 };
+#ifdef AVD_STAMP
+// Diagnostic build with -DAVD_STAMP: the heads' s_memtime stamps (head_kernel: HSTAMP; workgroup 16, per wave the cycles of 0 unit start,
+// 1 feature tiles, 2 epilogue, 3 start-up) land in host-visible memory, one region of 128 words per net, and AVD_FSPLIT_STAMPS=1 prints
+// them after every call (profiles/r14_startup_stamps.txt).
+static unsigned long long* head_stamps() {
+    static unsigned long long* m = nullptr;
+    if (!m && hipHostMalloc(&m, 4 * 128 * 8, hipHostMallocDefault) == hipSuccess) memset(m, 0, 4 * 128 * 8);
+    return m;
+}
+static void print_head_stamps(hipStream_t st) {
+    (void)hipStreamSynchronize(st);
+    static const char* who[4] = {"actor OUT_TANH_SAVE", "critic HEAD_BOTH", "target actor OUT_TANH", "target critic OUT_TD"};
+    for (int ni = 0; ni < 4; ++ni)
+        for (int w = 0; w < 8; ++w) {
+            const unsigned long long* s = head_stamps() + 128 * ni + 8 * w;
+            fprintf(stderr, "HSTAMP %-22s wave %d: start-up %8llu  unit-start %8llu  tiles %9llu  epilogue %8llu  start-up share %.4f\n", who[ni], w,
+                    s[3], s[0], s[1], s[2], (double)s[3] / (double)(s[0] + s[1] + s[2] + s[3] + 1));
+        }
+}
+#endif
 template <int S, class... H>
 static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, const float* theta, const float* stats, const float* theta_t,
                const float* stats_t, const float* s, const float* a, const float* r, const float* s2, const float* aw, float gamma,
@@ -1702,6 +1781,9 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
     auto head = [&](auto kern, int ni, const f16x8* x, const float* act, const float* rr, const float* yin, float* out, float* part_s,
                     auto... extra) {
         h.net = net[ni], h.xf = x, h.act = act, h.r = rr, h.yin = yin, h.out = out, h.part_s = part_s;
+#ifdef AVD_STAMP
+        h.stamp = head_stamps() + 128 * ni;  // one region per head launch (net index): read back below
+#endif
         hipLaunchKernelGGL(kern, grid, block, 0, st, h, extra...);
     };
     DwArgs dw;
@@ -1775,6 +1857,9 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
         if (phases == PH_ACTOR) launch_finalize(fa, st, 0, 1);
         else launch_finalize(fa, st, 0, 2);
     }
+#ifdef AVD_STAMP
+    if (AVD_DIAG_ENV("FSPLIT_STAMPS")) print_head_stamps(st);
+#endif
     return check_launch("avd_learn_set_split");
 }
 
