@@ -446,6 +446,68 @@ def _record_residual(conf, args):
         conf.residual_law = args.residual.record()
 
 
+def _warm_kw(args):
+    """VecTrainer's warm_start / actor_hold keywords, only where a flag was given (`tuned` / `searched` resolved: _resolve_warm_start)."""
+    kw = {} if getattr(args, "warm_start", None) is None else dict(warm_start=args.warm_start)
+    return kw if getattr(args, "actor_hold", None) is None else dict(kw, actor_hold=args.actor_hold)
+
+
+def _resolve_warm_start(args, conf, hparams=None):
+    """--warm_start / --actor_hold before anything is allocated: the words `tuned` / `searched` become the law --baseline_tune /
+    --baseline_search find (computed once: the baseline section reuses it), then the refusals that need the run's configuration, under
+    the flag's own name."""
+    from . import scenarios as _sc
+    from . import trainer
+
+    hold = getattr(args, "actor_hold", None)
+    if hold is not None:
+        if hold >= conf.total_time_steps:
+            raise SystemExit(f"--actor_hold: N={hold} must be below the run's {conf.total_time_steps} steps")
+        try:
+            trainer.check_actor_hold(hold, hparams)
+        except ValueError as e:
+            raise SystemExit(f"--actor_hold: {e}")
+    spec = getattr(args, "warm_start", None)
+    if spec is None:
+        return
+    try:
+        if spec in (_sc.TUNED, _sc.SEARCHED):
+            args.baselines = _baselines(conf, args)
+            fit = _sc.WarmStart()  # (the flag's other keys do not exist beside the word: the default fit)
+            if spec == _sc.TUNED:
+                law = _sc.LinearLaw(_sc.TUNED, *[v for _, v in dict(args.baselines.tune)["gains"]])
+            else:
+                law = _sc.LinearLaw(_sc.SEARCHED, table=args.baselines.found.law.table)
+            args.warm_start = spec = fit.with_gains(law, source=spec)
+        trainer.check_warm_start(conf, spec, args.rng, int(os.environ.get("WORLD_SIZE", "1") or 1), hparams=hparams,
+                                 residual=getattr(args, "residual", None))
+    except ValueError as e:
+        raise SystemExit(f"--warm_start: {e}")
+
+
+def _warm_fit(vt, args):
+    """--warm_start: the fit, before the step-0 evaluations (--keep_best's first snapshot is the fitted actors), then the fitted actors'
+    evaluator score from one rollout launch. Leaves (mean final fit loss, score) per experiment in args.warm_result. Without the
+    flag: nothing."""
+    if getattr(args, "warm_start", None) is None:
+        return
+    import numpy as np
+
+    loss = np.asarray(vt.fit_warm_start(), dtype=np.float64).reshape(vt.E, vt.M).mean(axis=1)
+    sc = np.asarray(vt.evaluator_scores([0]), dtype=np.float64).reshape(vt.E, -1)[:, 0]
+    args.warm_result = [(float(loss[e]), float(sc[e])) for e in range(vt.E)]
+
+
+def _record_warm(conf, args, e=0):
+    """conf.json's warm_start (a list of pairs: the law's record, the mean final fit loss, the fitted actors' evaluator score) and
+    actor_hold, only where the flags were given."""
+    if getattr(args, "warm_start", None) is not None:
+        loss, score = args.warm_result[e]
+        conf.warm_start = [["law", args.warm_start.record()], ["fit_loss", loss], ["evaluator_score", score]]
+    if getattr(args, "actor_hold", None) is not None:
+        conf.actor_hold = int(args.actor_hold)
+
+
 def _baselines(conf, args):
     """The run's baseline section, computed once (--residual tuned has already searched the grid)."""
     if getattr(args, "baselines", None) is None:
@@ -657,6 +719,21 @@ def get_cmdl_args(argv, conf):
                          "mode. Composes with --seeds, --train_disturb, --train_leader, --keep_best, --scenarios, --disturb, --baseline "
                          "and every --engine; not with --sweep / --pbt, --rng host, the centralized framework or a process group of "
                          "more than one rank (not in the reference CLI)")
+    tr.add_argument("--warm_start", type=str, default=None, metavar="SPEC",
+                    help="--rng device: before training, FIT the actors to a static linear law on the device (imitation pre-training): "
+                         "kp=..,kv=..[,ka=..,kf=..,steps=..,lr=..,ep=..,ev=..,a=..], or the word `tuned` / `searched` (the law "
+                         "--baseline_tune / --baseline_search finds on the --scenarios suite). steps (default 2000) Adam steps of size lr "
+                         "(1e-3) on batches of 64 states uniform in the box +-(ep, ev, a, a) (defaults reset_ep_max, reset_max_ev, 1), the "
+                         "target the law's clipped action; critics, targets' relation to their nets and every Adam state stay as "
+                         "constructed. conf.json records warm_start (the law, the mean final fit loss, the fitted actors' evaluator score); "
+                         "with --keep_best the step-0 snapshot is the fitted actors. Composes with --seeds, --train_disturb, --train_leader, "
+                         "--keep_best and every --engine; not with --residual, --sweep / --pbt, --rng host, the centralized framework or a "
+                         "process group of more than one rank (not in the reference CLI)")
+    tr.add_argument("--actor_hold", type=int, default=None, metavar="N",
+                    help="hold the actors still for the first N learner calls (the steps past the replay gate): the actor's step size "
+                         "handed to the update is 0 for them, so the critic learns to evaluate the policy it was handed (a --warm_start fit, "
+                         "or a --residual law) before the actors move; the configuration's step size afterwards. conf.json records "
+                         "actor_hold. N from 1 to below the run's step count; not with --sweep / --pbt (not in the reference CLI)")
     tr.add_argument("--keep_best", type=int, default=None, metavar="STEPS",
                     help="keep the best actors seen in training, on the device: at step 0, at every multiple of STEPS and at the last step "
                          "one evaluator rollout launch scores every rollout group (a platoon's actors; the shared sets; each experiment's of "
@@ -744,6 +821,32 @@ def get_cmdl_args(argv, conf):
             ap.error("--residual tuned needs --scenarios and --baseline_tune (the grid the law is searched on)")
         if args.residual == _sc.SEARCHED and (args.scenarios is None or getattr(args, "baseline_search", None) is None):
             ap.error("--residual searched needs --scenarios and --baseline_search (the space the law is searched in)")
+    if getattr(args, "warm_start", None) is not None:
+        from . import scenarios as _sc
+
+        if args.rng != "device":
+            ap.error("--warm_start needs --rng device")
+        if args.sweep is not None or args.pbt is not None:
+            ap.error("--warm_start does not combine with --sweep / --pbt")
+        if getattr(args, "residual", None) is not None:
+            ap.error("--warm_start does not combine with --residual (the law would act twice)")
+        if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+            ap.error("--warm_start is not available under a process group of more than one rank")
+        try:  # (what needs the run's configuration: trainer.check_warm_start applies it)
+            args.warm_start = _sc.parse_warm_start(args.warm_start)
+            if args.warm_start not in (_sc.TUNED, _sc.SEARCHED):
+                _sc.check_warm_start(args.warm_start)
+        except ValueError as e:
+            ap.error(f"--warm_start: {e}")
+        if args.warm_start == _sc.TUNED and (args.scenarios is None or getattr(args, "baseline_tune", None) is None):
+            ap.error("--warm_start tuned needs --scenarios and --baseline_tune (the grid the law is searched on)")
+        if args.warm_start == _sc.SEARCHED and (args.scenarios is None or getattr(args, "baseline_search", None) is None):
+            ap.error("--warm_start searched needs --scenarios and --baseline_search (the space the law is searched in)")
+    if getattr(args, "actor_hold", None) is not None:
+        if args.actor_hold < 1:
+            ap.error(f"--actor_hold: N={args.actor_hold} must be >= 1")
+        if args.sweep is not None or args.pbt is not None:
+            ap.error("--actor_hold does not combine with --sweep / --pbt")
     if getattr(args, "pbt", None) is not None or getattr(args, "pbt_fraction", None) is not None or getattr(args, "pbt_perturb", None) is not None:
         if args.pbt is None:
             ap.error("--pbt_fraction / --pbt_perturb need --pbt")
@@ -782,6 +885,16 @@ def get_cmdl_args(argv, conf):
     if args.mode == "tr":  # (esim checks against the configuration it loads)
         _check_baseline_conf(args, conf, ap.error)
         _check_freq_conf(args, conf, ap.error)
+        if getattr(args, "actor_hold", None) is not None and args.actor_hold >= conf.total_time_steps:
+            ap.error(f"--actor_hold: N={args.actor_hold} must be below the run's {conf.total_time_steps} steps")
+        ws = getattr(args, "warm_start", None)
+        if ws is not None and not isinstance(ws, str):  # (`tuned` / `searched`: checked once the law exists, _resolve_warm_start)
+            from . import trainer as _tr
+
+            try:
+                _tr.check_warm_start(conf, ws, args.rng, 1, residual=getattr(args, "residual", None))
+            except ValueError as e:
+                ap.error(f"--warm_start: {e}")
     return args, conf
 
 
@@ -829,14 +942,16 @@ def main(argv=None, conf=None):
             nofrl = conf.fed_method == conf.nofrl
             _check_train_leader(args, conf, "platoon")
             _resolve_residual(args, conf, "platoon")
+            _resolve_warm_start(args, conf)
             try:
                 vt = trainer.VecTrainer(conf, rng="device", auto_reset="platoon", shared_engine=args.engine, fused_update=nofrl,
-                                        train_disturb=args.train_disturb, **_lead_kw(args), **_residual_kw(args))
+                                        train_disturb=args.train_disturb, **_lead_kw(args), **_residual_kw(args), **_warm_kw(args))
             except ValueError as e:
                 if args.train_disturb is None:
                     raise
                 raise SystemExit(f"--train_disturb: {e}")
             vt.reset_episode()
+            _warm_fit(vt, args)
             _keep_start(vt, args)
             rng_state = np.random.get_state()
 
@@ -878,13 +993,15 @@ def main(argv=None, conf=None):
         else:
             _check_train_leader(args, conf, False)
             _resolve_residual(args, conf, False)
+            _resolve_warm_start(args, conf)
             try:
                 vt = trainer.VecTrainer(conf, rng=args.rng, auto_reset=False, shared_engine=args.engine, train_disturb=args.train_disturb,
-                                        **_lead_kw(args), **_residual_kw(args))
+                                        **_lead_kw(args), **_residual_kw(args), **_warm_kw(args))
             except ValueError as e:
                 if args.train_disturb is None:
                     raise
                 raise SystemExit(f"--train_disturb: {e}")
+            _warm_fit(vt, args)
             _keep_start(vt, args)
             ep, avg = vt.run(keep_best_every=args.keep_best)
             if args.keep_best is not None and vt.steps_total % args.keep_best:  # the last step
@@ -914,6 +1031,7 @@ def main(argv=None, conf=None):
         _record_train_levels(conf, args)
         _record_train_leader(conf, args)
         _record_residual(conf, args)
+        _record_warm(conf, args)
         if args.keep_best is not None:
             _KeepResults(vt, args).write(base, conf, n_save)
         artifacts.config_writer(os.path.join(base, "conf.json"), conf)
@@ -1037,13 +1155,15 @@ def train_seed_batch(args, conf, base, experiments=None):
             raise SystemExit(f"--train_disturb: {e}")
     _check_train_leader(args, conf, "platoon", hparams=hps)
     _resolve_residual(args, conf, "platoon", hparams=hps)
+    _resolve_warm_start(args, conf, hparams=hps)
     try:
         vt = trainer.VecTrainer(conf, rng="device", auto_reset="platoon", shared_engine=args.engine,
                                 fused_update=conf.fed_method == conf.nofrl, seeds=seeds, hparams=hps,
-                                train_disturb=getattr(args, "train_disturb", None), **_lead_kw(args), **_residual_kw(args))
+                                train_disturb=getattr(args, "train_disturb", None), **_lead_kw(args), **_residual_kw(args), **_warm_kw(args))
     except ValueError as e:
         raise SystemExit(f"{flag}: {e}")
     vt.reset_episode()
+    _warm_fit(vt, args)
     _keep_start(vt, args)
     P = vt.P_exp
     n_eval = None if args.eval_platoons is None else (P if args.eval_platoons == "all" else min(P, int(args.eval_platoons)))
@@ -1136,6 +1256,7 @@ def train_seed_batch(args, conf, base, experiments=None):
         _record_train_levels(ce, args)
         _record_train_leader(ce, args)
         _record_residual(ce, args)
+        _record_warm(ce, args, e)
         if suite is not None:
             _write_suite(d, ce, _slice(suite, e), range(1, P + 1), args)
             if baselines is not None:

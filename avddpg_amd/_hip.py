@@ -126,6 +126,8 @@ _PROTOS = {
     "avd_actor_forward_cond_f32": [_LP, _i, _i, _P, _P, _P, _i, _f, _P, _P, _P],
     "avd_critic_forward_f32": [_LP, _i, _i, _P, _P, _P, _i, _P, _P, _P],
     "avd_learn_f32": [_LP, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _P, _P, _P],
+    "avd_actor_clone_f32": [_LP, _i, _P, _P, _P, _P, _f, _P, _P, _P],
+    "avd_clone_sample_f32": [_i, _i, _i, _P, _P, _f, _f, _i, _u64, _u64, _P, _i, _P, _P, _P],
     "avd_learn_check_shape": [_LP],
     "avd_learn_kernel": [_LP, _i, C.POINTER(C.c_int)],
     "avd_learn_update_f32": [_LP, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _f, _f, _d, _P, _P, _P],

@@ -122,6 +122,7 @@ enum PhiloxStream : uint32_t {
     STREAM_TRAIN_OBS = 8,   // training under disturbances: sensor noise, (counter, index) = (observation counter, vehicle)
     STREAM_TRAIN_LINK = 9,  // training under disturbances: V2V loss, word x
     STREAM_SEARCH = 10,     // gain search: a candidate row's four normals, (counter, index) = (generation, candidate * R + row)
+    STREAM_CLONE = 11,      // warm start: a fit row's state words, (counter, index) = (fit step, vehicle index * 64 + row)
 };
 
 }  // namespace avd

@@ -477,6 +477,93 @@ __global__ __launch_bounds__(NTHREADS) void learn_kernel_g(avd_mlp_layout L, int
     }
 }
 
+// Supervised learner of the actor alone (avd_actor_clone_f32): the "actor forward" of learn_kernel_g followed by its pass 3, with
+// dLb/dmu = 2 (mu - u*) / (64 A) where that pass takes the critic's action gradient l.sDa. Lb = mean over 64 A of (mu(s) - u*)^2.
+// One workgroup per weight set; the row grads[set] is written whole: actor block = dLb/dtheta_actor, critic block and padding = 0.
+// LDS: what the actor touches only -- bufA is [64][ld_of(H1)] (no action branch), no reward / action / target rows; sY holds u*.
+__host__ __device__ inline size_t clone_lds_floats(const avd_mlp_layout& L) {
+    return (size_t)TILE * ld_of(L.H1) + (size_t)TILE * ld_of(L.H2) + 2 * L.H1 + 5 * L.H2 + TILE * L.S + 4 * TILE * L.A + 8;
+}
+__device__ __forceinline__ GLds carve_clone(float* p, const avd_mlp_layout& L) {
+    GLds l = {};
+    l.bufA = p, p += TILE * ld_of(L.H1);
+    l.bufB = p, p += TILE * ld_of(L.H2);
+    l.invA = p, p += L.H1;
+    l.shA = p, p += L.H1;
+    l.invB = p, p += L.H2;
+    l.shB = p, p += L.H2;
+    l.rsB = p, p += L.H2;
+    l.mmB = p, p += L.H2;
+    l.db = p, p += L.H2;
+    l.sX = p, p += TILE * L.S;
+    l.sY = p, p += TILE * L.A;
+    l.sQ = p, p += TILE * L.A;
+    l.sT = p, p += TILE * L.A;
+    l.sD = p, p += TILE * L.A;
+    l.red = p;
+    return l;
+}
+
+__global__ __launch_bounds__(NTHREADS) void actor_clone_kernel(avd_mlp_layout L, const float* __restrict__ theta,
+                                                                const float* __restrict__ stats, const float* __restrict__ s,
+                                                                const float* __restrict__ u, float high, float* __restrict__ grads,
+                                                                float* __restrict__ losses) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    GLds l = carve_clone(smem, L);
+    const int S = L.S, A = L.A, H1 = L.H1, H2 = L.H2;
+    const int ldA = ld_of(H1), ldB = ld_of(H2);
+    const int set = blockIdx.x, tid = threadIdx.x;
+    const float* th = theta + (long)set * L.theta_size;
+    const float* st = stats + (long)set * L.stats_size;
+    float* ga = grads + (long)set * L.theta_size;
+    const float invn = 1.0f / (float)(TILE * A);
+
+    for (int i = tid; i < TILE * S; i += NTHREADS) l.sX[i] = s[(long)set * TILE * S + i];
+    for (int i = tid; i < TILE * A; i += NTHREADS) l.sY[i] = u[(long)set * TILE * A + i];
+    if (tid == 0)  // alignment padding of the actor block, as in learn_kernel_g
+        for (int i = L.ab3 + A; i < L.actor_size; ++i) ga[i] = 0.f;
+    for (int i = L.actor_size + tid; i < L.theta_size; i += NTHREADS) ga[i] = 0.f;  // the critic takes no step from this slab
+    {
+        float t = warm(th, 0, L.aW2) + warm(th, L.ab2, L.actor_size) + warm(st, 0, L.cmms);
+        asm volatile("" ::"v"(t));  // keep the loads
+    }
+    lds_barrier();
+    // ---- actor forward (agent/model.py:26-36)
+    l1_fwd(LDSP(l.sX), S, CGLBP(th + L.aW1), CGLBP(th + L.ab1), CGLBP(th + L.ag1), CGLBP(th + L.abe1), CGLBP(st + L.amm1),
+           CGLBP(st + L.amv1), H1, LDSP(l.bufA), ldA, 0, LDSP(l.invA), LDSP(l.shA));
+    coefs_b(th + L.ag2, th + L.abe2, st + L.amm2, st + L.amv2, H2, l);
+    lds_barrier();
+    gemm_fwd_relu(l.bufA, ldA, l.invA, l.shA, H1, th + L.aW2, th + L.ab2, H2, l.bufB, ldB);
+    lds_barrier();
+    narrow_gemm(LDSP(l.bufB), ldB, LDSP(l.invB), LDSP(l.shB), H2, CGLBP(th + L.aW3), A, 1, A, CGLBP(th + L.ab3), LDSP(l.sQ));
+    lds_barrier();
+    // ---- Lb and its gradient through tanh(.) * high
+    for (int i = tid; i < TILE * A; i += NTHREADS) {
+        const float t = tanhf(l.sQ[i]);
+        const float e = t * high - l.sY[i];
+        l.sT[i] = e * e;
+        l.sD[i] = (2.0f * e * invn) * high * (1.0f - t * t);
+    }
+    lds_barrier();
+    const float lb = block_sum(l.sT, TILE * A, l.red) * invn;
+    if (tid == 0 && losses) losses[set] = lb;
+    // ---- actor backward (learn_kernel_g's pass 3). out_bwd is inlined at this, its only call site here: as a function it keeps its 2 x 32
+    // row registers across a call boundary and spills 620 B per lane to scratch; inlined into a kernel it needs none.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wignored-attributes"  // (the statement attribute is meant to override the function's noinline)
+    [[clang::always_inline]] out_bwd(LDSP(l.bufB), LDSP(l.invB), LDSP(l.shB), LDSP(l.rsB), LDSP(l.mmB), ldB, LDSP(l.sD),
+                                     CGLBP(th + L.aW3), H2, A, GLBP(ga + L.aW3), GLBP(ga + L.ab3), GLBP(ga + L.ag2), GLBP(ga + L.abe2));
+#pragma clang diagnostic pop
+    lds_barrier();
+    col_sums(l.bufB, ldB, H2, l.db, ga + L.ab2);
+    lds_barrier();
+    gemm_dw(l.bufA, ldA, l.invA, l.shA, H1, l.bufB, ldB, l.db, H2, ga + L.aW2);
+    lds_barrier();
+    gemm_dx_bn(l.bufB, ldB, H2, th + L.aW2, 0, H1, l.bufA, ldA, th + L.ag1, st + L.amm1, st + L.amv1, ga + L.ag1, ga + L.abe1);
+    lds_barrier();
+    l1_grads(LDSP(l.sX), S, LDSP(l.bufA), ldA, 0, H1, GLBP(ga + L.aW1), GLBP(ga + L.ab1));
+}
+
 }  // namespace gen
 
 // ------------------------------------------------------------------------------------------
@@ -1738,6 +1825,21 @@ extern "C" int avd_learn_f32(const avd_mlp_layout* lay, int n_agents, int set_mo
                              float* losses, void* stream) {
     return learn_impl("avd_learn_f32", lay, n_agents, set_mod, {theta, stats, s, a, r, s2}, theta_t, stats_t, gamma, high, grads, losses,
                       nullptr, stream);
+}
+
+// ---- supervised fit of the actor alone (DESIGN.md "Actor clone"): actor_clone_kernel, one workgroup per weight set ----
+extern "C" int avd_actor_clone_f32(const avd_mlp_layout* lay, int n_sets, const float* theta, const float* stats, const float* s,
+                                   const float* u_target, float high, float* grads, float* losses, void* stream) {
+    const char* who = "avd_actor_clone_f32";
+    int rc = check_learn_shape(lay, who);  // the learner's domain, B == 64 and its LDS bound (the clone's plan is a subset of it)
+    if (rc) return rc;
+    AVD_REQUIRE(n_sets > 0, "%s: n_sets=%d", who, n_sets);
+    AVD_REQUIRE(theta && stats && s && u_target && grads, "%s: null pointer", who);
+    const size_t lds = sizeof(float) * gen::clone_lds_floats(*lay);
+    if ((rc = opt_in_dynamic_lds((const void*)gen::actor_clone_kernel, lds, who))) return rc;
+    hipLaunchKernelGGL(gen::actor_clone_kernel, dim3(n_sets), dim3(NTHREADS), lds, (hipStream_t)stream, *lay, theta, stats, s, u_target, high,
+                       grads, losses);
+    return check_launch(who);
 }
 
 // ---- hyperparameter sweeps: the lean learner's HP twins (reference widths only; the general / centralized kernels have none) ----

@@ -714,6 +714,120 @@ def check_residual(law, conf=None):
     return law
 
 
+# ---- warm start: the actors are fitted to a linear law before training (tr --warm_start; avd_clone_sample_f32, avd_actor_clone_f32) ----
+
+WARM_START_NAME = "warm_start"
+WARM_START_MAX_STEPS = 100000
+_WARM_KEYS = GAIN_KEYS + ("steps", "lr", "ep", "ev", "a")
+
+
+class WarmStart(LinearLaw):
+    """A LinearLaw the actors are fitted to before the first training step (imitation pre-training): ``steps`` Adam steps of size
+    ``lr`` on batches of 64 states drawn uniformly in the box (ep, ev, a, a_pred) = +-(ep, ev, a, a), the target the law's clipped
+    action. ``ep`` / ``ev`` / ``a`` left None take conf.reset_ep_max, conf.reset_max_ev and 1.0 (``a`` also bounds a_pred). ``source``
+    records where the gains came from: "given", "tuned" or "searched"."""
+
+    def __init__(self, kp=0, kv=0, ka=0, kf=0, table=None, steps=2000, lr=1e-3, ep=None, ev=None, a=None, name=WARM_START_NAME,
+                 source="given"):
+        super().__init__(name, kp, kv, ka, kf, table)
+        self.steps, self.lr, self.ep, self.ev, self.a, self.source = steps, lr, ep, ev, a, str(source)
+
+    def box(self, conf):
+        """float32 [4]: the half-widths of (ep, ev, a, a_pred), the defaults filled in from ``conf``."""
+        ep = conf.reset_ep_max if self.ep is None else self.ep
+        ev = conf.reset_max_ev if self.ev is None else self.ev
+        a = 1.0 if self.a is None else self.a
+        return np.array([ep, ev, a, a], dtype=np.float32)
+
+    def record(self):
+        """conf.json's warm_start law, a list of pairs like ResidualLaw.record: the gains, steps, lr, the box half-widths that were
+        given (a default is left out and comes back as None), the table when there is one, the source."""
+        out = [[k, float(getattr(self, k))] for k in GAIN_KEYS] + [["steps", int(self.steps)], ["lr", float(self.lr)]]
+        out += [[k, float(getattr(self, k))] for k in ("ep", "ev", "a") if getattr(self, k) is not None]
+        if self.table is not None:
+            out.append(["table", np.asarray(self.table, dtype=np.float64).tolist()])
+        return out + [["source", self.source]]
+
+    @classmethod
+    def from_record(cls, pairs):
+        """The spec of a conf.json's warm_start law (None stays None); an unknown or repeated key is a ValueError."""
+        if pairs is None:
+            return None
+        keys = [k for k, _ in pairs]
+        bad = sorted({k for k in keys if k not in _WARM_KEYS + ("table", "source") or keys.count(k) > 1})
+        if bad:
+            raise ValueError(f"warm_start: unknown or repeated key(s) {bad}")
+        d = dict(pairs)
+        return cls(*(d.get(k, 0) for k in GAIN_KEYS), table=d.get("table"), steps=d.get("steps", 2000), lr=d.get("lr", 1e-3),
+                   ep=d.get("ep"), ev=d.get("ev"), a=d.get("a"), source=d.get("source", "given"))
+
+    def with_gains(self, law, source):
+        """This spec's fit settings around another law's gains (the tuned / searched law)."""
+        return WarmStart(law.kp, law.kv, law.ka, law.kf, table=law.table, steps=self.steps, lr=self.lr, ep=self.ep, ev=self.ev, a=self.a,
+                         source=source)
+
+    def __repr__(self):
+        return "WarmStart(" + ", ".join([f"{k}={v!r}" for k, v in self.items()] + [f"steps={self.steps!r}", f"lr={self.lr!r}"]) + ")"
+
+
+def parse_warm_start(text):
+    """``kp=2,kv=1[,ka=..,kf=..,steps=..,lr=..,ep=..,ev=..,a=..]`` -> WarmStart, or the words ``tuned`` / ``searched`` -> TUNED /
+    SEARCHED (the caller takes the gains --baseline_tune / --baseline_search find), as parse_residual. An unknown key, a key given
+    twice, a value that is no number or an empty text is a ValueError; the values are checked by check_warm_start."""
+    text = str(text).strip()
+    if text == TUNED:
+        return TUNED
+    if text == SEARCHED:
+        return SEARCHED
+    kw = {}
+    parts = [q.strip() for q in text.split(",") if q.strip()]
+    if not parts:
+        raise ValueError(f"warm_start {text!r}: no gain given (kp=..,kv=..[,ka=..,kf=..,steps=..,lr=..,ep=..,ev=..,a=..], or the word "
+                         f"{TUNED!r} / {SEARCHED!r})")
+    for part in parts:
+        key, eq, val = part.partition("=")
+        key, val = key.strip(), val.strip()
+        if not eq or key not in _WARM_KEYS:
+            raise ValueError(f"warm_start: unknown key {key!r} (one of {', '.join(_WARM_KEYS)}, as key=value, or the word {TUNED!r} / "
+                             f"{SEARCHED!r})")
+        if key in kw:
+            raise ValueError(f"warm_start: {key} given twice")
+        try:
+            kw[key] = float(val)
+        except ValueError:
+            raise ValueError(f"warm_start: {key}={val!r} is not a number") from None
+    if "steps" in kw:
+        if not math.isfinite(kw["steps"]) or kw["steps"] != int(kw["steps"]):
+            raise ValueError(f"warm_start: steps={kw['steps']!r} is not a whole number")
+        kw["steps"] = int(kw["steps"])
+    return WarmStart(**kw)
+
+
+def check_warm_start(spec, conf=None):
+    """The spec, checked. A ValueError for: not a WarmStart; check_baselines' rules (a non-finite gain, a table that is not [*, 4];
+    with ``conf`` a non-zero kf under Model A, a table whose row count is not conf.pl_size, the centralized framework); steps that is
+    no whole number in 1 .. WARM_START_MAX_STEPS; an lr that is not a finite number > 0; a box half-width that is given and is not a
+    finite number > 0."""
+    if not isinstance(spec, WarmStart):
+        raise ValueError(f"{spec!r} is not a scenarios.WarmStart")
+    check_baselines([spec], conf, reserved=())
+    st = spec.steps
+    if isinstance(st, bool) or not isinstance(st, (int, np.integer)) or not (1 <= st <= WARM_START_MAX_STEPS):
+        raise ValueError(f"warm_start: steps={st!r} must be a whole number in 1 .. {WARM_START_MAX_STEPS}")
+    number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and math.isfinite(v)
+    if not number(spec.lr) or not spec.lr > 0:
+        raise ValueError(f"warm_start: lr={spec.lr!r} must be a finite number > 0")
+    for k in ("ep", "ev", "a"):
+        v = getattr(spec, k)
+        if v is not None and (not number(v) or not v > 0):
+            raise ValueError(f"warm_start: {k}={v!r} must be a finite number > 0")
+    if conf is not None:
+        for k, v in zip(("ep", "ev", "a"), spec.box(conf)[:3]):
+            if not (math.isfinite(float(v)) and v > 0):
+                raise ValueError(f"warm_start: the box half-width {k}={float(v)!r} must be a finite number > 0")
+    return spec
+
+
 def parse_gain_grid(text):
     """``kp=lo:hi:n,kv=...`` (keys of GAIN_KEYS; ``key=value`` is the single value) -> float32 [G, 4]: per key np.linspace(lo, hi, n) in
     float64, then cast; a missing key is the single value 0; the product in kp, kv, ka, kf order, the last varying fastest. A

@@ -179,6 +179,35 @@ def check_residual(conf, residual, rng, world_size=1, fused_step=None, hparams=N
     return scenarios.check_residual(residual, conf)
 
 
+def check_warm_start(conf, warm_start, rng, world_size=1, hparams=None, residual=None):
+    """Why a run cannot start its actors from a fit to this linear law (VecTrainer(warm_start=...)), raised as a ValueError -- or the
+    checked scenarios.WarmStart. Called before anything is allocated or launched. The fit draws on the device (avd_clone_sample_f32),
+    fits one actor per vehicle, on one rank, outside any sweep; with a residual policy the law would act twice."""
+    from . import scenarios
+
+    if conf.framework == conf.cntrl:
+        raise ValueError("a warm start needs the decentralized framework: a linear law is per vehicle")
+    if rng != "device":
+        raise ValueError("a warm start needs rng='device': the fit's states are drawn on the device")
+    if residual is not None:
+        raise ValueError("a warm start does not combine with a residual policy: the law would act twice")
+    if hparams is not None:
+        raise ValueError("a warm start does not combine with a hyperparameter sweep or PBT (hparams=...)")
+    if int(world_size) > 1:
+        raise ValueError("a warm start runs on one rank: no process group of more than one rank")
+    return scenarios.check_warm_start(warm_start, conf)
+
+
+def check_actor_hold(actor_hold, hparams=None):
+    """Why a run cannot hold its actors still for its first ``actor_hold`` learner calls, raised as a ValueError -- or the count."""
+    if isinstance(actor_hold, bool) or not isinstance(actor_hold, (int, np.integer)) or actor_hold < 0:
+        raise ValueError(f"actor_hold={actor_hold!r} must be a whole number >= 0")
+    if actor_hold and hparams is not None:
+        raise ValueError("actor_hold does not combine with a hyperparameter sweep or PBT (hparams=...): a sweep's update reads its step "
+                         "sizes from its table")
+    return int(actor_hold)
+
+
 def check_keep_best(world_size):
     """Why a run cannot keep the best actors seen (VecTrainer.enable_keep_best), raised as a ValueError -- or None. Called before
     anything is allocated or launched."""
@@ -205,7 +234,7 @@ class VecTrainer:
     def __init__(self, conf, device=None, rng="device", group=None, shared_sets=None, seed=None, auto_reset=False,
                  pipeline_chunks=1, fused_update=False, shared_engine=None, init_seed=None, fused_step=None,
                  replay_ring=None, overlap_allreduce=None, seeds=None, hparams=None, train_disturb=None, train_leader=None,
-                 residual=None):
+                 residual=None, warm_start=None, actor_hold=0):
         """group: torch.distributed process group whose ranks each hold ``conf.num_platoons`` platoons
         (interfrl gradients are all-reduced over it). auto_reset: end episodes on the device (no host
         sync per step); needs rng='device'. True: the reference's rule -- any terminal platoon (or the step limit) ends
@@ -244,7 +273,15 @@ class VecTrainer:
         control term and the value chained to the follower take u = clip(law(what the agent observes) + scale * r), r the agent's
         noisy clipped action; self.actions and the replay keep r, so no learner changes, and self.applied holds u. The step runs
         avd_step_fused_res_f32 (with seeds, train_disturb and train_leader as given) and every evaluation this trainer makes passes
-        the law. check_residual says what it needs. None: nothing changes -- no buffer is made, the same entry points run."""
+        the law. check_residual says what it needs. None: nothing changes -- no buffer is made, the same entry points run.
+        warm_start: a scenarios.WarmStart the actors are fitted to before the first step (imitation pre-training; AgentGroup.clone_fit):
+        fit_warm_start() runs the fit -- once; the first step() runs it if nobody has -- and is refused once an update has been made.
+        check_warm_start says what it needs. None: nothing is allocated, neither entry point of the fit is called.
+        actor_hold: N > 0 holds the actors still for the first N learner calls (the steps past the replay gate): the actor's step size
+        handed to the update is 0 for them (AgentGroup.actor_lr), the configuration's afterwards. No kernel changes: w - 0 * x = w keeps
+        the actor's bits, and the actor's Adam moments and iteration count keep accumulating under the hold. The critic learns to
+        evaluate the policy it was handed; every engine and framework that does not read its step sizes from a sweep table. 0: the
+        configuration's step size is passed as always."""
         conf.refresh()
         self.levels = self.manoeuvres = self.lead = None
         self.residual = None
@@ -255,6 +292,15 @@ class VecTrainer:
                 ranks = _td.get_world_size(group)
             self.residual = check_residual(conf, residual, rng, ranks, fused_step, hparams)
         self.res_gains = self.applied = None
+        self.warm_start = self.warm_start_losses = None
+        if warm_start is not None:
+            ranks = 1
+            if group is not None:
+                import torch.distributed as _td
+                ranks = _td.get_world_size(group)
+            self.warm_start = check_warm_start(conf, warm_start, rng, ranks, hparams, residual)
+        self.actor_hold = check_actor_hold(actor_hold, hparams)
+        self.learner_calls = 0  # steps that passed the replay gate (what actor_hold counts)
         if train_disturb is not None:
             self.levels = check_train_disturb(conf, train_disturb, rng, group, fused_step, hparams)
         if train_leader is not None:
@@ -616,6 +662,9 @@ class VecTrainer:
         s, a, r, s2 = batch
         fed = is_fed_enabled(conf)
         self.updates += self.n_agents
+        if self.actor_hold:  # the actor's step size of this learner call: 0 under the hold, then the configuration's again
+            self.agents.actor_lr = 0.0 if self.learner_calls < self.actor_hold else None
+        self.learner_calls += 1
         if not fed and self.fused_update:
             # nofrl: learn + Adam x2 + Polyak of every agent in one kernel (no gradient slab round trip)
             nxt = self.A == 1 and self.auto_reset  # the episode loop's host-side resets go through reset_episode()
@@ -776,6 +825,8 @@ class VecTrainer:
         ep = self.episode if ep is None else ep
         i = self.ep_step if i is None else i
         self._flag_exchanged = False
+        if self.warm_start is not None and self.warm_start_losses is None:
+            self.fit_warm_start()
         self._timed("act+env", self._act)
         self._train(ep, i)
         self.env_steps += self.P
@@ -875,6 +926,20 @@ class VecTrainer:
                     break
             self.update_reward_list(ep)
         return self.all_ep_reward_lists, self.all_avg_reward_lists
+
+    def fit_warm_start(self):
+        """The warm start's fit (AgentGroup.clone_fit with this trainer's seed or seed table), once, before the first update: the actors
+        of every platoon become the fitted ones, targets equal to them, the critics and every Adam state as constructed. Returns the
+        last fit step's losses, float32 [E * M] (kept in self.warm_start_losses); one synchronisation, at the end of the fit."""
+        if self.warm_start is None:
+            raise ValueError("fit_warm_start needs VecTrainer(warm_start=...)")
+        if self.warm_start_losses is not None:
+            raise ValueError("the warm start has already been fitted: it runs once")
+        if self.updates or self.learner_calls:
+            raise ValueError("the warm start comes before the first update: this trainer has already made one")
+        self.warm_start_losses = self.agents.clone_fit(self.warm_start, seeds=self.seeds, M=self.M, seed=self.seed)
+        self._act_ready = False
+        return self.warm_start_losses
 
     def evaluator_scores(self, platoons=None, agents=None):
         """workers/evaluator.py:145 score of the CURRENT actors of each of this rank's ``platoons`` (default: all), from one

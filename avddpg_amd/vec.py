@@ -524,6 +524,79 @@ class AgentGroup:
         # a hyperparameter sweep: (avd_hparams device table, n_groups, set_block) -- set / agent j takes row (j // set_block) % n_groups;
         # learn / apply / learn_update then go through the *_hp_* entry points (set_hparams)
         self.hp = None
+        # the actor's step size every update call passes by value: None = the configuration's (see actor_lr)
+        self._actor_lr = None
+
+    @property
+    def actor_lr(self):
+        """The actor's Adam step size handed to the update kernels (apply, apply_intra, learn_update, learn_apply): the
+        configuration's, unless one has been set. Setting 0 holds the actors still (VecTrainer(actor_hold=N)): w - 0 * x = w keeps
+        every actor weight's bits, while the actor's Adam moments and iteration count keep accumulating; None gives the
+        configuration's back. A hyperparameter sweep reads its step sizes from its table, not from here."""
+        return self.config.actor_lr if self._actor_lr is None else self._actor_lr
+
+    @actor_lr.setter
+    def actor_lr(self, value):
+        self._actor_lr = None if value is None else float(value)
+
+    def clone_fit(self, spec, seeds=None, M=None, seed=None, loss_log=None):
+        """Imitation warm start: fit the actors to the linear law ``spec`` (scenarios.WarmStart) by spec.steps Adam steps of size spec.lr
+        on fresh batches of 64 states drawn uniformly in spec.box(config), the target the law's clipped action.
+        The E * M sets of platoon 0 are fitted (E = len(seeds) experiments, or 1; M vehicle indices; set j is experiment (j // M) % E,
+        vehicle j % M -- the layout of AgentGroup(seeds=..., seed_block=M)), each step three launches: avd_clone_sample_f32 (Philox
+        key = seeds[e], or ``seed`` / config.random_seed; counter = the fit step), avd_actor_clone_f32, avd_adam_polyak_f32 with
+        actor_lr = spec.lr and tau = 1. The gradient slab's critic block is zero and so are the moments, so the critic keeps its bits;
+        tau = 1 leaves every target equal to its online net. Afterwards m, v and step of the fitted sets are zero again (DDPG's Adam
+        starts as in a cold run) and the fitted rows of theta, theta_t (and learn_update's ping-pong slab, if it exists) are copied
+        to the same (experiment, vehicle) set of every other platoon: per-agent sets stay identical across platoons, as after the
+        reference's initialisation. With n_sets == E * M (shared sets) nothing is copied. Refused once any update has been made.
+        Returns the last step's losses [E * M] on the host; the one synchronisation is that read. loss_log (optional, a device
+        tensor [steps, E * M]) receives every step's losses."""
+        from . import scenarios
+        scenarios.check_warm_start(spec, self.config)
+        self._no_hp("clone_fit")
+        c, lay = self.config, self.lay
+        if lay.A != 1 or lay.S not in (3, 4):
+            raise _hip.AvdError(f"clone_fit: a linear law is per vehicle (S in (3, 4), A = 1), got S={lay.S} A={lay.A}")
+        if M is None:
+            M = c.pl_size
+        M = int(M)
+        E = 1 if seeds is None else len(seeds)
+        n_fit = E * M
+        if M < 1 or self.n_sets % n_fit:
+            raise ValueError(f"clone_fit: {self.n_sets} sets are not a multiple of {E} experiments x {M} vehicles")
+        d_seeds = None if seeds is None else seed_table(seeds, self.device, distinct=False)[1]
+        key = int(c.random_seed if seed is None else seed) if seeds is None else 0
+        f32 = dict(dtype=torch.float32, device=self.device)
+        gains = torch.from_numpy(spec.gains(M)).to(self.device)
+        box = torch.from_numpy(spec.box(c)).to(self.device)
+        s = torch.empty(n_fit, lay.B, lay.S, **f32)
+        u = torch.empty(n_fit, lay.B, 1, **f32)
+        grads = torch.empty(n_fit, lay.theta_size, **f32)
+        losses = torch.zeros(n_fit, **f32)
+        model_a = 1 if c.model == c.modelA else 0
+        sl = slice(0, n_fit)
+        th, st, tht, stt, m, v = (x[sl] for x in (self.theta, self.stats, self.theta_t, self.stats_t, self.m, self.v))
+        # Adam's iteration count of every fit step, laid out once: no launch of its own between the three of a step
+        counts = torch.arange(1, int(spec.steps) + 1, dtype=torch.int32, device=self.device).repeat_interleave(n_fit).view(-1, n_fit)
+        stream = stream_handle()
+        for k in range(int(spec.steps)):
+            out = losses if loss_log is None else loss_log[k]
+            call("avd_clone_sample_f32", n_fit, lay.S, M, ptr(gains), ptr(box), float(c.action_low), float(c.action_high), model_a, key, k,
+                 ptr(d_seeds), E, ptr(s), ptr(u), stream)
+            call("avd_actor_clone_f32", self._layp, n_fit, ptr(th), ptr(st), ptr(s), ptr(u), self.high, ptr(grads), ptr(out), stream)
+            call("avd_adam_polyak_f32", self._layp, n_fit, ptr(th), ptr(st), ptr(tht), ptr(stt), ptr(m), ptr(v), ptr(grads), ptr(counts[k]),
+                 float(spec.lr), c.critic_lr, 1.0, stream)
+        m.zero_(), v.zero_(), self.step[sl].zero_()
+        if self.n_sets > n_fit:  # every other platoon's set of the same (experiment, vehicle)
+            T, reps = lay.theta_size, self.n_sets // n_fit - 1
+            for slab in (self.theta, self.theta_t):
+                slab.view(-1, n_fit, T)[1:].copy_(slab.view(-1, n_fit, T)[:1].expand(reps, n_fit, T))
+        if getattr(self, "theta_alt", None) is not None:
+            self.theta_alt.copy_(self.theta)
+        if loss_log is not None:
+            losses = loss_log[int(spec.steps) - 1]
+        return losses.cpu().numpy()
 
     def set_hparams(self, table, n_groups, set_block):
         """Route learn / apply / learn_update through the *_hp_* entry points with this avd_hparams table (vec.hparams_table)."""
@@ -724,7 +797,7 @@ class AgentGroup:
             tbl, E, blk = self.hp
             call("avd_adam_polyak_guarded_hp_f32" if guarded else "avd_adam_polyak_hp_f32", *args, *skipped, ptr(tbl), E, blk, stream_handle())
         else:
-            call("avd_adam_polyak_guarded_f32" if guarded else "avd_adam_polyak_f32", *args, c.actor_lr, c.critic_lr, float(c.tau), *skipped,
+            call("avd_adam_polyak_guarded_f32" if guarded else "avd_adam_polyak_f32", *args, self.actor_lr, c.critic_lr, float(c.tau), *skipped,
                  stream_handle())
 
     def apply_intra(self, grads, P, M, weights=None, lead_skip=False, lo=0, hi=None, stream=None, advance=True):
@@ -746,7 +819,7 @@ class AgentGroup:
         a, b = lo * M, hi * M
         call("avd_adam_polyak_intra_f32", self._layp, hi - lo, M, 1 if lead_skip else 0, ptr(self.theta[a:b]), ptr(self.stats[a:b]),
              ptr(self.theta_t[a:b]), ptr(self.stats_t[a:b]), ptr(self.m[a:b]), ptr(self.v[a:b]), ptr(grads[a:b]), ptr(self.step[a:b]),
-             ptr(None if weights is None else weights.reshape(-1)[a:b]), c.actor_lr, c.critic_lr, float(c.tau),
+             ptr(None if weights is None else weights.reshape(-1)[a:b]), self.actor_lr, c.critic_lr, float(c.tau),
              stream_handle() if stream is None else _hip.C.c_void_p(stream.cuda_stream))
 
     def learn_apply_intra(self, s, a, r, s2, grads, P, M, losses=None, chunks=8, weights=None, lead_skip=False, timers=None):
@@ -780,7 +853,7 @@ class AgentGroup:
         hp = self.hp is not None  # each agent's gamma, step sizes and tau from the sweep table
         args = (self._layp, n, ptr(self.theta), ptr(self.stats), ptr(self.theta_alt), ptr(self.theta_t), ptr(self.stats_t), ptr(self.m),
                 ptr(self.v), ptr(self.step), ptr(s), ptr(a), ptr(r), ptr(s2))
-        args += (self.high,) if hp else (c.gamma, self.high, c.actor_lr, c.critic_lr, float(c.tau))
+        args += (self.high,) if hp else (c.gamma, self.high, self.actor_lr, c.critic_lr, float(c.tau))
         args += (ptr(grads), ptr(losses))
         fn = "avd_learn_update_hp_f32" if hp else "avd_learn_update_f32"
         if next_actions is not None:
@@ -812,7 +885,7 @@ class AgentGroup:
 
         def update(lo, hi, stream):
             call("avd_adam_polyak_f32", self._layp, hi - lo, ptr(self.theta[lo:hi]), ptr(self.stats[lo:hi]), ptr(self.theta_t[lo:hi]),
-                 ptr(self.stats_t[lo:hi]), ptr(self.m[lo:hi]), ptr(self.v[lo:hi]), ptr(grads[lo:hi]), ptr(self.step[lo:hi]), c.actor_lr,
+                 ptr(self.stats_t[lo:hi]), ptr(self.m[lo:hi]), ptr(self.v[lo:hi]), ptr(grads[lo:hi]), ptr(self.step[lo:hi]), self.actor_lr,
                  c.critic_lr, float(c.tau), _hip.C.c_void_p(stream.cuda_stream))
 
         self._chunk_pipeline([(n * i) // chunks for i in range(chunks + 1)],

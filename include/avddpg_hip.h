@@ -200,6 +200,29 @@ int avd_learn_f32(const avd_mlp_layout* lay, int n_agents, int set_mod, const fl
                   const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
                   const float* s2, float gamma, float high, float* grads, float* losses, void* stream);
 
+/* Supervised learner of the actor alone (imitation warm start): one 256-thread workgroup per weight set, B = 64.
+ *   s [n_sets][64][S], u_target [n_sets][64][A];  Lb = mean over 64 * A of (mu(s) - u_target)^2, mu = tanh(.) * high, BatchNormalization
+ *   in the inference form as everywhere.
+ *   grads [n_sets][theta_size], the whole row written: actor block = dLb/dactor in avd_learn_f32's slab layout (alignment padding
+ *   zero), critic block = zeros, so the slab goes straight into avd_adam_polyak_f32.  losses [n_sets] = Lb, or NULL.
+ *   theta and stats are read only. The actor forward and the actor's backward pass of avd_learn_f32's general kernel, on the exact-f32
+ *   matrix cores, with dLb/dmu = 2 (mu - u_target) / (64 A) as the upstream gradient. Shape domain: avd_learn_check_shape's; a shape
+ *   outside it, B != 64 and null pointers are refused on the host before any HIP call. */
+int avd_actor_clone_f32(const avd_mlp_layout* lay, int n_sets, const float* theta, const float* stats, const float* s,
+                        const float* u_target, float high, float* grads, float* losses, void* stream);
+
+/* One fit step's batch for avd_actor_clone_f32 (A = 1), one thread per (set j, row b): vehicle index m = j % M, experiment
+ * e = (j / M) % E (E = 1 and d_seeds = NULL without a seed table);
+ *   w = philox(d_seeds ? d_seeds[e] : seed, counter, m * 64 + b, stream 11);  counter = the fit step;
+ *   s[j][b][c] = uniform_pm1(w_c) * d_box[c] for c < S (S in {3, 4}; d_box [4] in device memory; uniform_pm1 = U[-1, 1) from the
+ *   word's top 24 bits, as avd_uniform_f32);
+ *   u_target[j][b] = fminf(fmaxf(((g0 * s0 + g1 * s1) + g2 * s2) + g3 * s3, lo), hi), g = d_gains[m] ([M][4]); under model_a (and
+ *   for S = 3) the g3 term is skipped. float32 without contraction: avd_eval_linear_f32's law.
+ * The draw depends on neither the number of sets per (e, m) nor E: experiment e of a seed batch draws what its solo run draws.
+ * AVD_E_INVALID: S not 3 or 4, M or E < 1, n_sets not a positive multiple of E * M, E > 1 without d_seeds, lo > hi, a null pointer. */
+int avd_clone_sample_f32(int n_sets, int S, int M, const float* d_gains, const float* d_box, float lo, float hi, int model_a,
+                         uint64_t seed, uint64_t counter, const uint64_t* d_seeds, int E, float* s, float* u_target, void* stream);
+
 /* Whether avd_learn_f32 / avd_learn_update_f32 serve this shape, without launching anything: AVD_OK, or the status and
  * avd_last_error() message those calls would give for it (widths outside the domain above, B != 64, or a 64-row tile of the
  * general kernel that does not fit the 160 KiB of LDS). For callers that want to refuse a configuration when it is built. */
