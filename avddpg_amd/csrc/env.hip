@@ -597,6 +597,28 @@ __global__ void uniform_kernel(int n, float* __restrict__ out, float half_width,
 
 using namespace avd;
 
+// Kernel templates are instantiated, and so laid out in the code object, in the order of their first use. The shared launch paths
+// below (one per twin pair, one for the fused step's seventeen packs) would change that order; this list keeps the one the file has
+// always had, so that the device code of two trees can be compared as text (tools/isa_diff.py). The step's packs: the scalar seed's
+// eight, the seed table's eight, the sweep's last.
+#define AVD_STEP_PACKS(G)                                                                                                               \
+    (const void*)step_fused_kernel<G, false, DistRef, LeadRef, BaseRef>, (const void*)step_fused_kernel<G, false, LeadRef, BaseRef>,  \
+    (const void*)step_fused_kernel<G, false, DistRef, BaseRef>, (const void*)step_fused_kernel<G, false, BaseRef>,                    \
+    (const void*)step_fused_kernel<G, false, DistRef, LeadRef>, (const void*)step_fused_kernel<G, false, LeadRef>,                    \
+    (const void*)step_fused_kernel<G, false, DistRef>, (const void*)step_fused_kernel<G>
+[[maybe_unused]] static const void* const env_kernel_order[] = {
+    (const void*)env_reset_kernel<false>, (const void*)episode_end_kernel<false>,
+    AVD_STEP_PACKS(false), AVD_STEP_PACKS(true), (const void*)step_fused_kernel<true, true, HpRef>,
+    (const void*)env_reset_kernel<true>, (const void*)episode_end_kernel<true>,
+    (const void*)observe_kernel<false>, (const void*)observe_kernel<true>};
+#undef AVD_STEP_PACKS
+
+// ---- experiment batches: the draw kernels keyed by a device seed table (G = true) ----------------------------------------
+// P is the batch's platoon count (n_groups experiments x P / n_groups platoons each, interleaved: g = p*n_groups + e).
+#define AVD_REQUIRE_GROUPS(who, P)                                                                                            \
+    AVD_REQUIRE(d_seeds && n_groups >= 1 && (P) > 0 && (P) % n_groups == 0, "%s: d_seeds=%p n_groups=%d P=%d (P must be a " \
+                "multiple of n_groups)", who, (const void*)d_seeds, n_groups, (int)(P))
+
 extern "C" int avd_env_step_f32(const avd_env_consts* d_consts, int P, int L, const float* x_in, float* x_out,
                                 float* prev_a, float* cum_accel, const float* u, const float* leader_exog,
                                 float* reward, uint8_t* term, uint8_t* done, float* reward_mean, int32_t* any_done,
@@ -612,32 +634,66 @@ extern "C" int avd_env_step_f32(const avd_env_consts* d_consts, int P, int L, co
     return check_launch("avd_env_step_f32");
 }
 
+// The reset entry points. G: the seed table's twin (its group check after the others; seed unread); otherwise d_seeds is null
+template <bool G>
+static int env_reset_impl(const char* who, const avd_env_consts* d_consts, int P, int L, float* x, float* prev_a, float* cum_accel,
+                          const float* draws, const float* front_accel, int mode, uint64_t seed, const uint64_t* d_seeds, int n_groups,
+                          uint64_t counter, const int32_t* cond, void* stream) {
+    AVD_REQUIRE(P > 0 && L > 0 && L <= AVD_MAX_L, "%s: P=%d L=%d", who, P, L);
+    AVD_REQUIRE(d_consts && x && prev_a, "%s: null pointer", who);
+    AVD_REQUIRE(mode >= 0 && mode <= 2, "%s: mode %d", who, mode);
+    if constexpr (G) AVD_REQUIRE_GROUPS(who, P);
+    const int pb = ENV_THREADS / L;
+    hipLaunchKernelGGL(env_reset_kernel<G>, dim3((P + pb - 1) / pb), dim3(ENV_THREADS), 0, (hipStream_t)stream, d_consts, P, L,
+                       (float4*)x, prev_a, cum_accel, draws, front_accel, mode, seed, counter, cond, d_seeds, n_groups);
+    return check_launch(who);
+}
+
 extern "C" int avd_env_reset_f32(const avd_env_consts* d_consts, int P, int L, float* x, float* prev_a,
                                  float* cum_accel, const float* draws, const float* front_accel, int mode,
                                  uint64_t seed, uint64_t counter, const int32_t* cond, void* stream) {
-    AVD_REQUIRE(P > 0 && L > 0 && L <= AVD_MAX_L, "avd_env_reset_f32: P=%d L=%d", P, L);
-    AVD_REQUIRE(d_consts && x && prev_a, "avd_env_reset_f32: null pointer");
-    AVD_REQUIRE(mode >= 0 && mode <= 2, "avd_env_reset_f32: mode %d", mode);
+    return env_reset_impl<false>("avd_env_reset_f32", d_consts, P, L, x, prev_a, cum_accel, draws, front_accel, mode, seed, nullptr, 1,
+                                 counter, cond, stream);
+}
+
+extern "C" int avd_env_reset_seeds_f32(const avd_env_consts* d_consts, int P, int L, float* x, float* prev_a, float* cum_accel,
+                                       int mode, const uint64_t* d_seeds, int n_groups, uint64_t counter, const int32_t* cond,
+                                       void* stream) {
+    return env_reset_impl<true>("avd_env_reset_seeds_f32", d_consts, P, L, x, prev_a, cum_accel, nullptr, nullptr, mode, 0, d_seeds,
+                                n_groups, counter, cond, stream);
+}
+
+// The episode-end entry points, in the same way
+template <bool G>
+static int episode_end_impl(const char* who, const avd_env_consts* d_consts, int P, int L, int M, float* x, float* prev_a,
+                            float* cum_accel, const uint8_t* done, int32_t* ep_len, float* ep_reward, int limit, float* ret_sum,
+                            float* len_sum, int32_t* ep_cnt, int32_t* any_reset, int mode, uint64_t seed, const uint64_t* d_seeds,
+                            int n_groups, uint64_t counter, void* stream) {
+    AVD_REQUIRE(P > 0 && L > 0 && L <= AVD_MAX_L && M >= 1 && M <= L, "%s: P=%d L=%d M=%d", who, P, L, M);
+    AVD_REQUIRE(d_consts && x && prev_a && done && ep_len && ep_reward && ret_sum && len_sum && ep_cnt, "%s: null pointer", who);
+    AVD_REQUIRE(limit >= 1 && mode >= 0 && mode <= 2, "%s: limit=%d mode=%d", who, limit, mode);
+    if constexpr (G) AVD_REQUIRE_GROUPS(who, P);
     const int pb = ENV_THREADS / L;
-    const int grid = (P + pb - 1) / pb;
-    hipLaunchKernelGGL(env_reset_kernel<false>, dim3(grid), dim3(ENV_THREADS), 0, (hipStream_t)stream, d_consts, P, L,
-                       (float4*)x, prev_a, cum_accel, draws, front_accel, mode, seed, counter, cond, nullptr, 1);
-    return check_launch("avd_env_reset_f32");
+    hipLaunchKernelGGL(episode_end_kernel<G>, dim3((P + pb - 1) / pb), dim3(ENV_THREADS), 0, (hipStream_t)stream, d_consts, P, L, M,
+                       (float4*)x, prev_a, cum_accel, done, ep_len, ep_reward, limit, ret_sum, len_sum, ep_cnt, any_reset, mode, seed,
+                       counter, d_seeds, n_groups);
+    return check_launch(who);
 }
 
 extern "C" int avd_episode_end_f32(const avd_env_consts* d_consts, int P, int L, int M, float* x, float* prev_a, float* cum_accel,
                                    const uint8_t* done, int32_t* ep_len, float* ep_reward, int limit, float* ret_sum,
                                    float* len_sum, int32_t* ep_cnt, int32_t* any_reset, int mode, uint64_t seed,
                                    uint64_t counter, void* stream) {
-    AVD_REQUIRE(P > 0 && L > 0 && L <= AVD_MAX_L && M >= 1 && M <= L, "avd_episode_end_f32: P=%d L=%d M=%d", P, L, M);
-    AVD_REQUIRE(d_consts && x && prev_a && done && ep_len && ep_reward && ret_sum && len_sum && ep_cnt,
-                "avd_episode_end_f32: null pointer");
-    AVD_REQUIRE(limit >= 1 && mode >= 0 && mode <= 2, "avd_episode_end_f32: limit=%d mode=%d", limit, mode);
-    const int pb = ENV_THREADS / L;
-    hipLaunchKernelGGL(episode_end_kernel<false>, dim3((P + pb - 1) / pb), dim3(ENV_THREADS), 0, (hipStream_t)stream, d_consts, P, L,
-                       M, (float4*)x, prev_a, cum_accel, done, ep_len, ep_reward, limit, ret_sum, len_sum, ep_cnt, any_reset, mode,
-                       seed, counter, nullptr, 1);
-    return check_launch("avd_episode_end_f32");
+    return episode_end_impl<false>("avd_episode_end_f32", d_consts, P, L, M, x, prev_a, cum_accel, done, ep_len, ep_reward, limit, ret_sum,
+                                   len_sum, ep_cnt, any_reset, mode, seed, nullptr, 1, counter, stream);
+}
+
+extern "C" int avd_episode_end_seeds_f32(const avd_env_consts* d_consts, int P, int L, int M, float* x, float* prev_a,
+                                         float* cum_accel, const uint8_t* done, int32_t* ep_len, float* ep_reward, int limit,
+                                         float* ret_sum, float* len_sum, int32_t* ep_cnt, int32_t* any_reset, int mode,
+                                         const uint64_t* d_seeds, int n_groups, uint64_t counter, void* stream) {
+    return episode_end_impl<true>("avd_episode_end_seeds_f32", d_consts, P, L, M, x, prev_a, cum_accel, done, ep_len, ep_reward, limit,
+                                  ret_sum, len_sum, ep_cnt, any_reset, mode, 0, d_seeds, n_groups, counter, stream);
 }
 
 extern "C" int avd_ou_step_f32(int n, float* ou_state, const float* normals, float theta, float mean, float dt,
@@ -671,55 +727,56 @@ extern "C" int avd_uniform_f32(int n, float* out, float half_width, uint64_t see
     return check_launch("avd_uniform_f32");
 }
 
-// the two step_fused entry points: arguments checked, StepArgs filled, step_fused_kernel<G> launched
-template <bool G, bool HP = false>
-static int step_fused_launch(const char* who, const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
-                             float* prev_a, float* cum_accel, float* reward, uint8_t* term, uint8_t* done, int32_t* any_done,
-                             int32_t* any_done_other, const float* actor_out, float* ou_state, float* action, float* leader_exog,
-                             float ou_theta, float ou_mean, float ou_dt, float ou_std_dev, float action_low, float action_high,
-                             float exog_scale, int exog_uniform, uint64_t seed, const uint64_t* d_seeds, int n_groups,
-                             uint64_t ou_counter, uint64_t exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward,
-                             void* stream, const avd_hparams* d_hp = nullptr, const DistRef* dist = nullptr,
-                             const LeadRef* lead = nullptr, const BaseRef* base = nullptr) {
-    AVD_REQUIRE(P > 0 && L > 0 && L <= AVD_MAX_L && (S == 3 || S == 4), "%s: P=%d L=%d S=%d", who, P, L, S);
-    AVD_REQUIRE(d_consts && x_in && x_out && prev_a && reward && done && actor_out && ou_state && action && leader_exog,
+// ---- the fused step's host side ------------------------------------------------------------------------
+// What an entry point of the fused step asks for. Every avd_step_fused_* wrapper makes one (AVD_STEP_CALL), gives it its seed key and
+// its variant's parts after checking them, and hands it to step_fused_run: the one place with the step's own checks and the launch.
+struct StepCall {
+    StepArgs a;  // the common block as the kernel takes it. The seed key: a.seed, or a.seeds + a.n_groups. a.slot: step_fused_run's
+    int64_t replay_counter;
+    const avd_hparams* hp;  // the sweep's table (with a seed table), or null
+    const DistRef* dist;    // the parts of the kernel's pack, each null where the entry point has none
+    const LeadRef* lead;
+    const BaseRef* base;
+    hipStream_t stream;
+    const char* who;  // the entry point, for messages
+};
+
+// StepCall c of the wrapper it stands in, from the parameter names that all ten signatures share; the key is the scalar seed 0 until
+// the wrapper sets its own. theta_, std_dev_: ou_theta and ou_std_dev, or the sweep's zeros (per platoon there: its kernel reads neither).
+#define AVD_STEP_CALL(c, who_, theta_, std_dev_)                                                                                       \
+    StepCall c = {};                                                                                                                     \
+    c.who = who_, c.stream = (hipStream_t)stream, c.replay_counter = replay_counter, c.a.cst = d_consts, c.a.P = P, c.a.L = L, c.a.S = S; \
+    c.a.x_in = (const float4*)x_in, c.a.x_out = (float4*)x_out, c.a.prev_a = prev_a, c.a.cum_accel = cum_accel, c.a.reward = reward;     \
+    c.a.term = term, c.a.done = done, c.a.any_done = any_done, c.a.any_done_other = any_done_other, c.a.actor_out = actor_out;           \
+    c.a.ou_state = ou_state, c.a.action = action, c.a.leader_exog = leader_exog, c.a.theta = theta_, c.a.mean = ou_mean, c.a.dt = ou_dt; \
+    c.a.scale = std_dev_ * (float)sqrt((double)ou_dt); /* as avd_ou_step_f32 */                                                          \
+    c.a.lo = action_low, c.a.hi = action_high, c.a.exog_scale = exog_scale, c.a.exog_uniform = exog_uniform, c.a.n_groups = 1;           \
+    c.a.ou_counter = ou_counter, c.a.exog_counter = exog_counter, c.a.ring = ring, c.a.cap = cap, c.a.ep_reward = ep_reward
+
+// The step's own checks, then one launch of step_fused_kernel<G, HP, the parts present...>: G from the seed table, the pack in the
+// kernel's order (DistRef, LeadRef, BaseRef), or the sweep's lone HpRef
+static int step_fused_run(const StepCall& c) {
+    StepArgs a = c.a;
+    const char* who = c.who;
+    AVD_REQUIRE(a.P > 0 && a.L > 0 && a.L <= AVD_MAX_L && (a.S == 3 || a.S == 4), "%s: P=%d L=%d S=%d", who, a.P, a.L, a.S);
+    AVD_REQUIRE(a.cst && a.x_in && a.x_out && a.prev_a && a.reward && a.done && a.actor_out && a.ou_state && a.action && a.leader_exog,
                 "%s: null pointer", who);
-    AVD_REQUIRE(!ring || (cap > 0 && replay_counter >= 0), "%s: cap=%d counter=%ld", who, cap, (long)replay_counter);
-    StepArgs a;
-    a.cst = d_consts, a.P = P, a.L = L, a.S = S, a.x_in = (const float4*)x_in, a.x_out = (float4*)x_out, a.prev_a = prev_a;
-    a.cum_accel = cum_accel, a.reward = reward, a.term = term, a.done = done, a.any_done = any_done, a.any_done_other = any_done_other;
-    a.actor_out = actor_out, a.ou_state = ou_state, a.action = action, a.leader_exog = leader_exog;
-    a.theta = ou_theta, a.mean = ou_mean, a.dt = ou_dt, a.scale = ou_std_dev * (float)sqrt((double)ou_dt);  // as avd_ou_step_f32
-    a.lo = action_low, a.hi = action_high, a.exog_scale = exog_scale, a.exog_uniform = exog_uniform;
-    a.seed = seed, a.ou_counter = ou_counter, a.exog_counter = exog_counter, a.seeds = d_seeds, a.n_groups = n_groups;
-    a.ring = ring, a.cap = cap, a.slot = ring ? (int)(replay_counter % cap) : 0, a.ep_reward = ep_reward;
-    const int per_block = (ENV_THREADS / 64) * (64 / L);
-    if constexpr (HP)
-        hipLaunchKernelGGL((step_fused_kernel<G, true, HpRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS), 0,
-                           (hipStream_t)stream, a, HpRef{d_hp, n_groups, 1});
-    else if (base && dist && lead)  // the residual's four forms (avd_step_fused_res_f32): the BaseRef last in the pack
-        hipLaunchKernelGGL((step_fused_kernel<G, false, DistRef, LeadRef, BaseRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS),
-                           sizeof(float) * (size_t)dist->n_levels * (L * 24 + LEVEL_WORDS), (hipStream_t)stream, a, *dist, *lead, *base);
-    else if (base && lead)
-        hipLaunchKernelGGL((step_fused_kernel<G, false, LeadRef, BaseRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS), 0,
-                           (hipStream_t)stream, a, *lead, *base);
-    else if (base && dist)
-        hipLaunchKernelGGL((step_fused_kernel<G, false, DistRef, BaseRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS),
-                           sizeof(float) * (size_t)dist->n_levels * (L * 24 + LEVEL_WORDS), (hipStream_t)stream, a, *dist, *base);
-    else if (base)
-        hipLaunchKernelGGL((step_fused_kernel<G, false, BaseRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS), 0,
-                           (hipStream_t)stream, a, *base);
-    else if (dist && lead)
-        hipLaunchKernelGGL((step_fused_kernel<G, false, DistRef, LeadRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS),
-                           sizeof(float) * (size_t)dist->n_levels * (L * 24 + LEVEL_WORDS), (hipStream_t)stream, a, *dist, *lead);
-    else if (lead)
-        hipLaunchKernelGGL((step_fused_kernel<G, false, LeadRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS), 0,
-                           (hipStream_t)stream, a, *lead);
-    else if (dist)
-        hipLaunchKernelGGL((step_fused_kernel<G, false, DistRef>), dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS),
-                           sizeof(float) * (size_t)dist->n_levels * (L * 24 + LEVEL_WORDS), (hipStream_t)stream, a, *dist);
-    else
-        hipLaunchKernelGGL(step_fused_kernel<G>, dim3((P + per_block - 1) / per_block), dim3(ENV_THREADS), 0, (hipStream_t)stream, a);
+    AVD_REQUIRE(!a.ring || (a.cap > 0 && c.replay_counter >= 0), "%s: cap=%d counter=%ld", who, a.cap, (long)c.replay_counter);
+    a.slot = a.ring ? (int)(c.replay_counter % a.cap) : 0;
+    const int per_block = (ENV_THREADS / 64) * (64 / a.L);
+    const dim3 grid((a.P + per_block - 1) / per_block);
+    const size_t lds = c.dist ? sizeof(float) * (size_t)c.dist->n_levels * (a.L * 24 + LEVEL_WORDS) : 0;  // the levels' plant rows and table
+    const std::false_type no{};
+    const auto go = [&](auto g, auto hp, const auto&... r) {
+        hipLaunchKernelGGL((step_fused_kernel<decltype(g)::value, decltype(hp)::value, std::decay_t<decltype(r)>...>), grid, dim3(ENV_THREADS),
+                           lds, c.stream, a, r...);
+    };
+    const auto with_base = [&](auto g, const auto&... r) { c.base ? go(g, no, r..., *c.base) : go(g, no, r...); };
+    const auto with_lead = [&](auto g, const auto&... r) { c.lead ? with_base(g, r..., *c.lead) : with_base(g, r...); };
+    const auto with_dist = [&](auto g) { c.dist ? with_lead(g, *c.dist) : with_lead(g); };
+    if (c.hp) go(std::true_type{}, std::true_type{}, HpRef{c.hp, a.n_groups, 1});  // (avd_step_fused_hp_f32 has required the seed table)
+    else if (a.seeds) with_dist(std::true_type{});
+    else with_dist(no);
     return check_launch(who);
 }
 
@@ -758,15 +815,6 @@ static int lead_args(const char* who, int n_manoeuvres, int T, const float* d_ta
     return AVD_OK;
 }
 
-static int observe_check(const char* who, int P, int L, const float* x, float* obs, int n_levels, const avd_train_level* d_levels,
-                         float* link_hist, float* link_recv) {
-    AVD_REQUIRE(P > 0 && L > 0 && L <= AVD_MAX_L, "%s: P=%d L=%d (L must be 1..%d)", who, P, L, AVD_MAX_L);
-    AVD_REQUIRE(n_levels >= 1 && n_levels <= AVD_TRAIN_MAX_LEVELS, "%s: n_levels=%d (must be 1..%d)", who, n_levels, AVD_TRAIN_MAX_LEVELS);
-    AVD_REQUIRE(x && obs && d_levels, "%s: null pointer", who);
-    AVD_REQUIRE((link_hist == nullptr) == (link_recv == nullptr), "%s: link_hist and link_recv must both be given or both be null", who);
-    return AVD_OK;
-}
-
 extern "C" int avd_step_fused_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
                                   float* prev_a, float* cum_accel, float* reward, uint8_t* term, uint8_t* done,
                                   int32_t* any_done, int32_t* any_done_other, const float* actor_out, float* ou_state,
@@ -774,17 +822,10 @@ extern "C" int avd_step_fused_f32(const avd_env_consts* d_consts, int P, int L, 
                                   float action_low, float action_high, float exog_scale, int exog_uniform, uint64_t seed,
                                   uint64_t ou_counter, uint64_t exog_counter, float* ring, int cap, int64_t replay_counter,
                                   float* ep_reward, void* stream) {
-    return step_fused_launch<false>("avd_step_fused_f32", d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done,
-                                    any_done, any_done_other, actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt,
-                                    ou_std_dev, action_low, action_high, exog_scale, exog_uniform, seed, nullptr, 1, ou_counter,
-                                    exog_counter, ring, cap, replay_counter, ep_reward, stream);
+    AVD_STEP_CALL(c, "avd_step_fused_f32", ou_theta, ou_std_dev);
+    c.a.seed = seed;
+    return step_fused_run(c);
 }
-
-// ---- experiment batches: the draw kernels keyed by a device seed table (G = true) ----------------------------------------
-// P is the batch's platoon count (n_groups experiments x P / n_groups platoons each, interleaved: g = p*n_groups + e).
-#define AVD_REQUIRE_GROUPS(who, P)                                                                                            \
-    AVD_REQUIRE(d_seeds && n_groups >= 1 && (P) > 0 && (P) % n_groups == 0, "%s: d_seeds=%p n_groups=%d P=%d (P must be a " \
-                "multiple of n_groups)", who, (const void*)d_seeds, n_groups, (int)(P))
 
 extern "C" int avd_step_fused_seeds_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
                                         float* prev_a, float* cum_accel, float* reward, uint8_t* term, uint8_t* done,
@@ -793,11 +834,11 @@ extern "C" int avd_step_fused_seeds_f32(const avd_env_consts* d_consts, int P, i
                                         float ou_std_dev, float action_low, float action_high, float exog_scale, int exog_uniform,
                                         const uint64_t* d_seeds, int n_groups, uint64_t ou_counter, uint64_t exog_counter,
                                         float* ring, int cap, int64_t replay_counter, float* ep_reward, void* stream) {
-    AVD_REQUIRE_GROUPS("avd_step_fused_seeds_f32", P);
-    return step_fused_launch<true>("avd_step_fused_seeds_f32", d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done,
-                                   any_done, any_done_other, actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt,
-                                   ou_std_dev, action_low, action_high, exog_scale, exog_uniform, 0, d_seeds, n_groups, ou_counter,
-                                   exog_counter, ring, cap, replay_counter, ep_reward, stream);
+    const char* who = "avd_step_fused_seeds_f32";
+    AVD_REQUIRE_GROUPS(who, P);
+    AVD_STEP_CALL(c, who, ou_theta, ou_std_dev);
+    c.a.seeds = d_seeds, c.a.n_groups = n_groups;
+    return step_fused_run(c);
 }
 
 extern "C" int avd_step_fused_hp_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
@@ -806,42 +847,13 @@ extern "C" int avd_step_fused_hp_f32(const avd_env_consts* d_consts, int P, int 
                                      float ou_mean, float ou_dt, float action_low, float action_high, float exog_scale, int exog_uniform,
                                      const uint64_t* d_seeds, const avd_hparams* d_hp, int n_groups, uint64_t ou_counter,
                                      uint64_t exog_counter, float* ring, int cap, int64_t replay_counter, float* ep_reward, void* stream) {
-    AVD_REQUIRE_GROUPS("avd_step_fused_hp_f32", P);
-    AVD_REQUIRE_HP("avd_step_fused_hp_f32", d_hp, n_groups, 1, P);
+    const char* who = "avd_step_fused_hp_f32";
+    AVD_REQUIRE_GROUPS(who, P);
+    AVD_REQUIRE_HP(who, d_hp, n_groups, 1, P);
     // (the scalar theta / scale the kernel would read are replaced per platoon; zeros here keep them out of the arithmetic)
-    return step_fused_launch<true, true>("avd_step_fused_hp_f32", d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done,
-                                         any_done, any_done_other, actor_out, ou_state, action, leader_exog, 0.f, ou_mean, ou_dt, 0.f,
-                                         action_low, action_high, exog_scale, exog_uniform, 0, d_seeds, n_groups, ou_counter,
-                                         exog_counter, ring, cap, replay_counter, ep_reward, stream, d_hp);
-}
-
-extern "C" int avd_env_reset_seeds_f32(const avd_env_consts* d_consts, int P, int L, float* x, float* prev_a, float* cum_accel,
-                                       int mode, const uint64_t* d_seeds, int n_groups, uint64_t counter, const int32_t* cond,
-                                       void* stream) {
-    AVD_REQUIRE(P > 0 && L > 0 && L <= AVD_MAX_L, "avd_env_reset_seeds_f32: P=%d L=%d", P, L);
-    AVD_REQUIRE(d_consts && x && prev_a, "avd_env_reset_seeds_f32: null pointer");
-    AVD_REQUIRE(mode >= 0 && mode <= 2, "avd_env_reset_seeds_f32: mode %d", mode);
-    AVD_REQUIRE_GROUPS("avd_env_reset_seeds_f32", P);
-    const int pb = ENV_THREADS / L;
-    hipLaunchKernelGGL(env_reset_kernel<true>, dim3((P + pb - 1) / pb), dim3(ENV_THREADS), 0, (hipStream_t)stream, d_consts, P, L,
-                       (float4*)x, prev_a, cum_accel, nullptr, nullptr, mode, 0, counter, cond, d_seeds, n_groups);
-    return check_launch("avd_env_reset_seeds_f32");
-}
-
-extern "C" int avd_episode_end_seeds_f32(const avd_env_consts* d_consts, int P, int L, int M, float* x, float* prev_a,
-                                         float* cum_accel, const uint8_t* done, int32_t* ep_len, float* ep_reward, int limit,
-                                         float* ret_sum, float* len_sum, int32_t* ep_cnt, int32_t* any_reset, int mode,
-                                         const uint64_t* d_seeds, int n_groups, uint64_t counter, void* stream) {
-    AVD_REQUIRE(P > 0 && L > 0 && L <= AVD_MAX_L && M >= 1 && M <= L, "avd_episode_end_seeds_f32: P=%d L=%d M=%d", P, L, M);
-    AVD_REQUIRE(d_consts && x && prev_a && done && ep_len && ep_reward && ret_sum && len_sum && ep_cnt,
-                "avd_episode_end_seeds_f32: null pointer");
-    AVD_REQUIRE(limit >= 1 && mode >= 0 && mode <= 2, "avd_episode_end_seeds_f32: limit=%d mode=%d", limit, mode);
-    AVD_REQUIRE_GROUPS("avd_episode_end_seeds_f32", P);
-    const int pb = ENV_THREADS / L;
-    hipLaunchKernelGGL(episode_end_kernel<true>, dim3((P + pb - 1) / pb), dim3(ENV_THREADS), 0, (hipStream_t)stream, d_consts, P, L,
-                       M, (float4*)x, prev_a, cum_accel, done, ep_len, ep_reward, limit, ret_sum, len_sum, ep_cnt, any_reset, mode, 0,
-                       counter, d_seeds, n_groups);
-    return check_launch("avd_episode_end_seeds_f32");
+    AVD_STEP_CALL(c, who, 0.f, 0.f);
+    c.a.seeds = d_seeds, c.a.n_groups = n_groups, c.hp = d_hp;
+    return step_fused_run(c);
 }
 
 // ---- training under disturbances --------------------------------------------------------------------------------------------
@@ -857,10 +869,9 @@ extern "C" int avd_step_fused_dist_f32(const avd_env_consts* d_consts, int P, in
     const char* who = "avd_step_fused_dist_f32";
     DistRef d;
     if (const int rc = dist_args(who, n_levels, h_levels, d_levels, d_plant, obs_in, obs_out, link_hist, link_recv, obs_counter, d)) return rc;
-    return step_fused_launch<false>(who, d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done, any_done, any_done_other,
-                                    actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt, ou_std_dev, action_low,
-                                    action_high, exog_scale, exog_uniform, seed, nullptr, 1, ou_counter, exog_counter, ring, cap,
-                                    replay_counter, ep_reward, stream, nullptr, &d);
+    AVD_STEP_CALL(c, who, ou_theta, ou_std_dev);
+    c.a.seed = seed, c.dist = &d;
+    return step_fused_run(c);
 }
 
 extern "C" int avd_step_fused_dist_seeds_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
@@ -877,10 +888,9 @@ extern "C" int avd_step_fused_dist_seeds_f32(const avd_env_consts* d_consts, int
     AVD_REQUIRE_GROUPS(who, P);
     DistRef d;
     if (const int rc = dist_args(who, n_levels, h_levels, d_levels, d_plant, obs_in, obs_out, link_hist, link_recv, obs_counter, d)) return rc;
-    return step_fused_launch<true>(who, d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done, any_done, any_done_other,
-                                   actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt, ou_std_dev, action_low, action_high,
-                                   exog_scale, exog_uniform, 0, d_seeds, n_groups, ou_counter, exog_counter, ring, cap, replay_counter,
-                                   ep_reward, stream, nullptr, &d);
+    AVD_STEP_CALL(c, who, ou_theta, ou_std_dev);
+    c.a.seeds = d_seeds, c.a.n_groups = n_groups, c.dist = &d;
+    return step_fused_run(c);
 }
 
 // ---- training under leader manoeuvres --------------------------------------------------------------------------------------
@@ -893,10 +903,9 @@ extern "C" int avd_step_fused_lead_f32(const avd_env_consts* d_consts, int P, in
     const char* who = "avd_step_fused_lead_f32";
     LeadRef l;
     if (const int rc = lead_args(who, n_manoeuvres, T, d_table, d_noise, d_gaussian, ep_len, ep_step, n_levels, l)) return rc;
-    return step_fused_launch<false>(who, d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done, any_done, any_done_other,
-                                   actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt, ou_std_dev, action_low, action_high,
-                                   exog_scale, exog_uniform, seed, nullptr, 1, ou_counter, exog_counter, ring, cap, replay_counter,
-                                   ep_reward, stream, nullptr, nullptr, &l);
+    AVD_STEP_CALL(c, who, ou_theta, ou_std_dev);
+    c.a.seed = seed, c.lead = &l;
+    return step_fused_run(c);
 }
 
 extern "C" int avd_step_fused_lead_seeds_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
@@ -909,10 +918,9 @@ extern "C" int avd_step_fused_lead_seeds_f32(const avd_env_consts* d_consts, int
     AVD_REQUIRE_GROUPS(who, P);
     LeadRef l;
     if (const int rc = lead_args(who, n_manoeuvres, T, d_table, d_noise, d_gaussian, ep_len, ep_step, n_levels, l)) return rc;
-    return step_fused_launch<true>(who, d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done, any_done, any_done_other,
-                                   actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt, ou_std_dev, action_low, action_high,
-                                   exog_scale, exog_uniform, 0, d_seeds, n_groups, ou_counter, exog_counter, ring, cap, replay_counter,
-                                   ep_reward, stream, nullptr, nullptr, &l);
+    AVD_STEP_CALL(c, who, ou_theta, ou_std_dev);
+    c.a.seeds = d_seeds, c.a.n_groups = n_groups, c.lead = &l;
+    return step_fused_run(c);
 }
 
 extern "C" int avd_step_fused_dist_lead_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
@@ -928,10 +936,9 @@ extern "C" int avd_step_fused_dist_lead_f32(const avd_env_consts* d_consts, int 
     if (const int rc = dist_args(who, n_levels, h_levels, d_levels, d_plant, obs_in, obs_out, link_hist, link_recv, obs_counter, d)) return rc;
     LeadRef l;
     if (const int rc = lead_args(who, n_manoeuvres, T, d_table, d_noise, d_gaussian, ep_len, ep_step, n_levels, l)) return rc;
-    return step_fused_launch<false>(who, d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done, any_done, any_done_other,
-                                   actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt, ou_std_dev, action_low, action_high,
-                                   exog_scale, exog_uniform, seed, nullptr, 1, ou_counter, exog_counter, ring, cap, replay_counter,
-                                   ep_reward, stream, nullptr, &d, &l);
+    AVD_STEP_CALL(c, who, ou_theta, ou_std_dev);
+    c.a.seed = seed, c.dist = &d, c.lead = &l;
+    return step_fused_run(c);
 }
 
 extern "C" int avd_step_fused_dist_lead_seeds_f32(const avd_env_consts* d_consts, int P, int L, int S, const float* x_in, float* x_out,
@@ -948,10 +955,9 @@ extern "C" int avd_step_fused_dist_lead_seeds_f32(const avd_env_consts* d_consts
     if (const int rc = dist_args(who, n_levels, h_levels, d_levels, d_plant, obs_in, obs_out, link_hist, link_recv, obs_counter, d)) return rc;
     LeadRef l;
     if (const int rc = lead_args(who, n_manoeuvres, T, d_table, d_noise, d_gaussian, ep_len, ep_step, n_levels, l)) return rc;
-    return step_fused_launch<true>(who, d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done, any_done, any_done_other,
-                                   actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt, ou_std_dev, action_low, action_high,
-                                   exog_scale, exog_uniform, 0, d_seeds, n_groups, ou_counter, exog_counter, ring, cap, replay_counter,
-                                   ep_reward, stream, nullptr, &d, &l);
+    AVD_STEP_CALL(c, who, ou_theta, ou_std_dev);
+    c.a.seeds = d_seeds, c.a.n_groups = n_groups, c.dist = &d, c.lead = &l;
+    return step_fused_run(c);
 }
 
 // ---- training a residual on a linear law: ONE entry point for the nominal, seed-batch, disturbed and manoeuvre forms ------------------
@@ -975,40 +981,41 @@ extern "C" int avd_step_fused_res_f32(const avd_env_consts* d_consts, int P, int
     if (n_manoeuvres > 0)
         if (const int rc = lead_args(who, n_manoeuvres, T, d_table, d_noise, d_gaussian, ep_len, ep_step, n_levels > 0 ? n_levels : 1, l)) return rc;
     const BaseRef b = {d_gains, scale, applied};
-    const DistRef* dp = n_levels > 0 ? &d : nullptr;
-    const LeadRef* lp = n_manoeuvres > 0 ? &l : nullptr;
-    if (d_seeds) {
-        AVD_REQUIRE_GROUPS(who, P);
-        return step_fused_launch<true>(who, d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done, any_done, any_done_other,
-                                       actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt, ou_std_dev, action_low, action_high,
-                                       exog_scale, exog_uniform, 0, d_seeds, n_groups, ou_counter, exog_counter, ring, cap, replay_counter,
-                                       ep_reward, stream, nullptr, dp, lp, &b);
-    }
-    return step_fused_launch<false>(who, d_consts, P, L, S, x_in, x_out, prev_a, cum_accel, reward, term, done, any_done, any_done_other,
-                                    actor_out, ou_state, action, leader_exog, ou_theta, ou_mean, ou_dt, ou_std_dev, action_low, action_high,
-                                    exog_scale, exog_uniform, seed, nullptr, 1, ou_counter, exog_counter, ring, cap, replay_counter,
-                                    ep_reward, stream, nullptr, dp, lp, &b);
+    if (d_seeds) AVD_REQUIRE_GROUPS(who, P);
+    AVD_STEP_CALL(c, who, ou_theta, ou_std_dev);
+    if (d_seeds) c.a.seeds = d_seeds, c.a.n_groups = n_groups;  // (seed unread)
+    else c.a.seed = seed;
+    c.dist = n_levels > 0 ? &d : nullptr, c.lead = n_manoeuvres > 0 ? &l : nullptr, c.base = &b;
+    return step_fused_run(c);
+}
+
+// The observation entry points: the checks once, the seed table's twin with its group check after them
+template <bool G>
+static int observe_impl(const char* who, int P, int L, const float* x, float* obs, int n_levels, const avd_train_level* d_levels,
+                        float* link_hist, float* link_recv, uint64_t seed, const uint64_t* d_seeds, int n_groups, uint64_t obs_counter,
+                        const int32_t* only_where_zero, const int32_t* run_if_nonzero, void* stream) {
+    AVD_REQUIRE(P > 0 && L > 0 && L <= AVD_MAX_L, "%s: P=%d L=%d (L must be 1..%d)", who, P, L, AVD_MAX_L);
+    AVD_REQUIRE(n_levels >= 1 && n_levels <= AVD_TRAIN_MAX_LEVELS, "%s: n_levels=%d (must be 1..%d)", who, n_levels, AVD_TRAIN_MAX_LEVELS);
+    AVD_REQUIRE(x && obs && d_levels, "%s: null pointer", who);
+    AVD_REQUIRE((link_hist == nullptr) == (link_recv == nullptr), "%s: link_hist and link_recv must both be given or both be null", who);
+    if constexpr (G) AVD_REQUIRE_GROUPS(who, P);
+    const long n = (long)P * L;
+    hipLaunchKernelGGL(observe_kernel<G>, dim3((unsigned)((n + ENV_THREADS - 1) / ENV_THREADS)), dim3(ENV_THREADS), 0, (hipStream_t)stream, P,
+                       L, (const float4*)x, (float4*)obs, n_levels, d_levels, link_hist, link_recv, seed, obs_counter, only_where_zero,
+                       run_if_nonzero, d_seeds, n_groups);
+    return check_launch(who);
 }
 
 extern "C" int avd_observe_f32(int P, int L, const float* x, float* obs, int n_levels, const avd_train_level* d_levels, float* link_hist,
                                float* link_recv, uint64_t seed, uint64_t obs_counter, const int32_t* only_where_zero,
                                const int32_t* run_if_nonzero, void* stream) {
-    if (const int rc = observe_check("avd_observe_f32", P, L, x, obs, n_levels, d_levels, link_hist, link_recv)) return rc;
-    const long n = (long)P * L;
-    hipLaunchKernelGGL(observe_kernel<false>, dim3((unsigned)((n + ENV_THREADS - 1) / ENV_THREADS)), dim3(ENV_THREADS), 0,
-                       (hipStream_t)stream, P, L, (const float4*)x, (float4*)obs, n_levels, d_levels, link_hist, link_recv, seed,
-                       obs_counter, only_where_zero, run_if_nonzero, nullptr, 1);
-    return check_launch("avd_observe_f32");
+    return observe_impl<false>("avd_observe_f32", P, L, x, obs, n_levels, d_levels, link_hist, link_recv, seed, nullptr, 1, obs_counter,
+                               only_where_zero, run_if_nonzero, stream);
 }
 
 extern "C" int avd_observe_seeds_f32(int P, int L, const float* x, float* obs, int n_levels, const avd_train_level* d_levels,
                                      float* link_hist, float* link_recv, const uint64_t* d_seeds, int n_groups, uint64_t obs_counter,
                                      const int32_t* only_where_zero, const int32_t* run_if_nonzero, void* stream) {
-    if (const int rc = observe_check("avd_observe_seeds_f32", P, L, x, obs, n_levels, d_levels, link_hist, link_recv)) return rc;
-    AVD_REQUIRE_GROUPS("avd_observe_seeds_f32", P);
-    const long n = (long)P * L;
-    hipLaunchKernelGGL(observe_kernel<true>, dim3((unsigned)((n + ENV_THREADS - 1) / ENV_THREADS)), dim3(ENV_THREADS), 0,
-                       (hipStream_t)stream, P, L, (const float4*)x, (float4*)obs, n_levels, d_levels, link_hist, link_recv, 0, obs_counter,
-                       only_where_zero, run_if_nonzero, d_seeds, n_groups);
-    return check_launch("avd_observe_seeds_f32");
+    return observe_impl<true>("avd_observe_seeds_f32", P, L, x, obs, n_levels, d_levels, link_hist, link_recv, 0, d_seeds, n_groups,
+                              obs_counter, only_where_zero, run_if_nonzero, stream);
 }

@@ -570,53 +570,35 @@ class VecTrainer:
             per_platoon = self.auto_reset == "platoon"
             lead = (ld["n"], ld["T"], ptr(ld["table"]), ptr(ld["noise"]), ptr(ld["gaussian"]), ptr(env.ep_len) if per_platoon else None,
                     0 if per_platoon else min(self.ep_step, ld["T"] - 1))
-        if self.residual is not None:
-            # a residual policy: ONE entry point for every combination (seed table or none, levels or none, manoeuvres or none)
-            if self.levels is not None:
-                env.obs, env.obs_prev = env.obs_prev, env.obs
-                env.obs_counter += 1
-                dist = (len(self.levels), env.h_levels, ptr(env.d_levels), ptr(env.d_plant), ptr(env.obs_prev), ptr(env.obs),
-                        ptr(env.link_hist), ptr(env.link_recv), env.obs_counter)
-            else:
-                dist = (0, None, None, None, None, None, None, None, 0)
-            key = (self.seed, ) if self.seeds is None else (0, )
-            grp = (None, 1) if self.seeds is None else (ptr(env.d_seeds), self.E)
-            call("avd_step_fused_res_f32", ptr(env.d_consts), self.P, self.L, self.S, ptr(env.x_prev), ptr(env.x), ptr(env.prev_a),
-                 ptr(env.cum_accel), ptr(env.reward), ptr(env.term), ptr(env.done), ptr(env.any_done), ptr(other),
-                 ptr(self.actor_out), ptr(ou.state), ptr(self.actions), ptr(self.leader_exog), conf.theta, ou.mean, conf.ou_dt,
-                 conf.std_dev, conf.action_low, conf.action_high, conf.reset_max_u, 1 if conf.rand_gen == conf.uniform else 0,
-                 *key, ou.calls, self.exog_calls, ptr(rp.ring), rp.cap, rp.buffer_counter, ptr(self.ep_reward), *grp, *dist,
-                 *(lead if lead else (0, 0, None, None, None, None, 0)), ptr(self.res_gains), float(self.residual.scale),
-                 ptr(self.applied), stream_handle())
-        elif self.levels is not None:
+        dist = None
+        if self.levels is not None:
             # training under disturbances (avd_step_fused_dist_f32): the level's plant, the observation of the new state with the next
             # observation counter, the replay row from the observation buffers -- which swap where x and x_prev do
             env.obs, env.obs_prev = env.obs_prev, env.obs
             env.obs_counter += 1
-            fn, key = (f"avd_step_fused_dist{tag}_f32", (self.seed,)) if self.seeds is None else (f"avd_step_fused_dist{tag}_seeds_f32", (ptr(env.d_seeds), self.E))
-            call(fn, ptr(env.d_consts), self.P, self.L, self.S, ptr(env.x_prev), ptr(env.x), ptr(env.prev_a),
-                 ptr(env.cum_accel), ptr(env.reward), ptr(env.term), ptr(env.done), ptr(env.any_done), ptr(other),
-                 ptr(self.actor_out), ptr(ou.state), ptr(self.actions), ptr(self.leader_exog), conf.theta, ou.mean, conf.ou_dt,
-                 conf.std_dev, conf.action_low, conf.action_high, conf.reset_max_u, 1 if conf.rand_gen == conf.uniform else 0,
-                 *key, ou.calls, self.exog_calls, ptr(rp.ring), rp.cap, rp.buffer_counter, ptr(self.ep_reward),
-                 len(self.levels), env.h_levels, ptr(env.d_levels), ptr(env.d_plant), ptr(env.obs_prev), ptr(env.obs),
-                 ptr(env.link_hist), ptr(env.link_recv), env.obs_counter, *lead, stream_handle())
-        elif self.d_hp is not None:  # a sweep: each platoon's OU theta and scale from its experiment's row (avd_step_fused_hp_f32)
-            call("avd_step_fused_hp_f32", ptr(env.d_consts), self.P, self.L, self.S, ptr(env.x_prev), ptr(env.x), ptr(env.prev_a),
-                 ptr(env.cum_accel), ptr(env.reward), ptr(env.term), ptr(env.done), ptr(env.any_done), ptr(other), ptr(self.actor_out),
-                 ptr(ou.state), ptr(self.actions), ptr(self.leader_exog), ou.mean, conf.ou_dt, conf.action_low, conf.action_high,
-                 conf.reset_max_u, 1 if conf.rand_gen == conf.uniform else 0, ptr(env.d_seeds), ptr(self.d_hp), self.E, ou.calls,
-                 self.exog_calls, ptr(rp.ring), rp.cap, rp.buffer_counter, ptr(self.ep_reward), stream_handle())
-        else:
-            # the seed argument: the scalar seed, or (a batch) the seed table and its length (avd_step_fused_seeds_f32)
-            # (under manoeuvres without levels the twin also takes the level count the assignment divides by: 1)
-            fn, key = (f"avd_step_fused{tag}_f32", (self.seed,)) if self.seeds is None else (f"avd_step_fused{tag}_seeds_f32", (ptr(env.d_seeds), self.E))
-            call(fn, ptr(env.d_consts), self.P, self.L, self.S, ptr(env.x_prev), ptr(env.x), ptr(env.prev_a),
-                 ptr(env.cum_accel), ptr(env.reward), ptr(env.term), ptr(env.done), ptr(env.any_done), ptr(other),
-                 ptr(self.actor_out), ptr(ou.state), ptr(self.actions), ptr(self.leader_exog), conf.theta, ou.mean, conf.ou_dt,
-                 conf.std_dev, conf.action_low, conf.action_high, conf.reset_max_u, 1 if conf.rand_gen == conf.uniform else 0,
-                 *key, ou.calls, self.exog_calls, ptr(rp.ring), rp.cap, rp.buffer_counter, ptr(self.ep_reward),
-                 *(lead + (1,) if lead else ()), stream_handle())
+            dist = (len(self.levels), env.h_levels, ptr(env.d_levels), ptr(env.d_plant), ptr(env.obs_prev), ptr(env.obs),
+                    ptr(env.link_hist), ptr(env.link_recv), env.obs_counter)
+        # every entry point's list: head, its seed key, mid, its own tail, the stream
+        head = (ptr(env.d_consts), self.P, self.L, self.S, ptr(env.x_prev), ptr(env.x), ptr(env.prev_a), ptr(env.cum_accel),
+                ptr(env.reward), ptr(env.term), ptr(env.done), ptr(env.any_done), ptr(other), ptr(self.actor_out), ptr(ou.state),
+                ptr(self.actions), ptr(self.leader_exog), conf.theta, ou.mean, conf.ou_dt, conf.std_dev, conf.action_low,
+                conf.action_high, conf.reset_max_u, 1 if conf.rand_gen == conf.uniform else 0)
+        mid = (ou.calls, self.exog_calls, ptr(rp.ring), rp.cap, rp.buffer_counter, ptr(self.ep_reward))
+        grp = None if self.seeds is None else (ptr(env.d_seeds), self.E)  # a batch's seed table and its length (the *_seeds_* twins)
+        key, sfx = ((self.seed,), "_f32") if grp is None else (grp, "_seeds_f32")
+        if self.residual is not None:
+            # a residual policy: ONE entry point for every combination (seed table or none, levels or none, manoeuvres or none)
+            fn, key = "avd_step_fused_res_f32", ((self.seed,) if grp is None else (0,))
+            tail = (*(grp or (None, 1)), *(dist or (0, None, None, None, None, None, None, None, 0)),
+                    *(lead or (0, 0, None, None, None, None, 0)), ptr(self.res_gains), float(self.residual.scale), ptr(self.applied))
+        elif dist:
+            fn, tail = f"avd_step_fused_dist{tag}{sfx}", dist + lead
+        elif self.d_hp is not None:  # a sweep: each platoon's OU theta and scale from its experiment's row, so no scalar theta / std_dev
+            fn, tail = "avd_step_fused_hp_f32", ()
+            head, key = head[:17] + (ou.mean, conf.ou_dt) + head[21:], (grp[0], ptr(self.d_hp), grp[1])
+        else:  # (under manoeuvres without levels the twin also takes the level count the assignment divides by: 1)
+            fn, tail = f"avd_step_fused{tag}{sfx}", (lead + (1,) if lead else ())
+        call(fn, *head, *key, *mid, *tail, stream_handle())
         ou.calls += 1
         self.exog_calls += 1
         env.step_count += 1

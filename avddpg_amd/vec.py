@@ -228,14 +228,13 @@ class VecPlatoon:
         self._upload_reset(draws, self.front_accel)
 
     def _upload_reset(self, draws, fa, cond=None):
-        if self.seeds is not None:
-            call("avd_env_reset_seeds_f32", ptr(self.d_consts), self.P, self.L, ptr(self.x), ptr(self.prev_a), ptr(self.cum_accel),
-                 self._mode(), ptr(self.d_seeds), self.n_groups, self.reset_count, ptr(cond), stream_handle())
-            return
-        d = torch.from_numpy(draws.astype(np.float32)).to(self.device) if draws is not None else None
-        f = torch.from_numpy(np.asarray(fa, dtype=np.float32)).to(self.device) if fa is not None else None
-        call("avd_env_reset_f32", ptr(self.d_consts), self.P, self.L, ptr(self.x), ptr(self.prev_a),
-             ptr(self.cum_accel), ptr(d), ptr(f), self._mode(), self.seed, self.reset_count, ptr(cond),
+        if self.seeds is not None:  # (a seed batch draws on the device: no host draws to upload)
+            fn, key = "avd_env_reset_seeds_f32", (self._mode(), ptr(self.d_seeds), self.n_groups)
+        else:
+            d = torch.from_numpy(draws.astype(np.float32)).to(self.device) if draws is not None else None
+            f = torch.from_numpy(np.asarray(fa, dtype=np.float32)).to(self.device) if fa is not None else None
+            fn, key = "avd_env_reset_f32", (ptr(d), ptr(f), self._mode(), self.seed)
+        call(fn, ptr(self.d_consts), self.P, self.L, ptr(self.x), ptr(self.prev_a), ptr(self.cum_accel), *key, self.reset_count, ptr(cond),
              stream_handle())
 
     def _host_reset_draws(self):
@@ -296,14 +295,10 @@ class VecPlatoon:
             raise ValueError("per-platoon episode ends need rng='device'")
         self.ensure_episode_state()
         st = self.ep_stats
-        if self.seeds is not None:
-            call("avd_episode_end_seeds_f32", ptr(self.d_consts), self.P, self.L, M, ptr(self.x), ptr(self.prev_a), ptr(self.cum_accel),
-                 ptr(self.done), ptr(self.ep_len), ptr(ep_reward), int(limit), ptr(st["ret_sum"]), ptr(st["len_sum"]),
-                 ptr(st["count"]), ptr(any_reset), self._mode(), ptr(self.d_seeds), self.n_groups, self.reset_count, stream_handle())
-        else:
-            call("avd_episode_end_f32", ptr(self.d_consts), self.P, self.L, M, ptr(self.x), ptr(self.prev_a), ptr(self.cum_accel),
-                 ptr(self.done), ptr(self.ep_len), ptr(ep_reward), int(limit), ptr(st["ret_sum"]), ptr(st["len_sum"]),
-                 ptr(st["count"]), ptr(any_reset), self._mode(), self.seed, self.reset_count, stream_handle())
+        key = (self.seed,) if self.seeds is None else (ptr(self.d_seeds), self.n_groups)
+        call("avd_episode_end_f32" if self.seeds is None else "avd_episode_end_seeds_f32", ptr(self.d_consts), self.P, self.L, M,
+             ptr(self.x), ptr(self.prev_a), ptr(self.cum_accel), ptr(self.done), ptr(self.ep_len), ptr(ep_reward), int(limit),
+             ptr(st["ret_sum"]), ptr(st["len_sum"]), ptr(st["count"]), ptr(any_reset), self._mode(), *key, self.reset_count, stream_handle())
         self.reset_count += 1
         if self.levels is not None:  # (ep_len[p] == 0 exactly on the platoons just reset)
             self.observe(only_where_zero=self.ep_len)

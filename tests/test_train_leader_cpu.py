@@ -188,6 +188,36 @@ def test_lead_entry_points_refuse_on_the_host_before_any_hip_call(entry):
     assert "#define AVD_TRAIN_MAX_MANOEUVRES 16" in open(_hip.HEADER_PATH).read()
 
 
+# every entry point of the fused step, by the parts of its argument list: (seed table, sweep table, levels, manoeuvres, residual law)
+STEP_ENTRIES = {
+    "avd_step_fused_f32": "", "avd_step_fused_seeds_f32": "s", "avd_step_fused_hp_f32": "sh", "avd_step_fused_dist_f32": "d",
+    "avd_step_fused_dist_seeds_f32": "sd", "avd_step_fused_lead_f32": "l", "avd_step_fused_lead_seeds_f32": "sl",
+    "avd_step_fused_dist_lead_f32": "dl", "avd_step_fused_dist_lead_seeds_f32": "sdl", "avd_step_fused_res_f32": "r"}
+
+
+def test_step_entries_are_all_of_the_abi():
+    assert sorted(STEP_ENTRIES) == sorted(n for n in _hip._PROTOS if n.startswith("avd_step_fused"))
+
+
+@pytest.mark.parametrize("entry", STEP_ENTRIES)
+def test_every_step_entry_point_reaches_the_common_check_under_its_own_name(entry):
+    """Valid arguments of the entry point's own (so every check of its variant passes) and a platoon of 17: the step's own first check
+    refuses it on the host, with the name of the entry point that was called."""
+    parts = STEP_ENTRIES[entry]
+    head = [_B(0), 8, 17, 4, _B(1), _B(2), _B(3), None, _B(4), None, _B(5), None, None, _B(6), _B(7), _B(8), _B(9)]
+    head += [0.0, 0.1, -2.5, 2.5, 0.1, 0] if "h" in parts else [0.15, 0.0, 0.1, 0.2, -2.5, 2.5, 0.1, 0]
+    key = [_B(10), _B(11), 2] if "h" in parts else [_B(10), 2] if "s" in parts else [7]
+    mid = [3, 4, None, 8, 0, None]  # counters, no ring, no episodic reward counters
+    levels = (_hip.TrainLevel * 2)()  # (host memory the level checks read: zeros, a perfect observation and no link)
+    dist = [2, levels, _B(20), _B(21), _B(22), _B(23), None, None, 1]
+    lead = [2, 12, _B(40), _B(41), _B(42), _B(43), 0]
+    tail = (dist if "d" in parts else []) + (lead + ([] if "d" in parts else [1]) if "l" in parts else [])
+    if "r" in parts:  # the one residual entry point, in its fullest form: seed table, levels, manoeuvres
+        tail = [_B(10), 2] + dist + lead + [_B(50), 0.5, None]
+    with pytest.raises(_hip.AvdError, match=rf"failed \(-1\): {entry}: P=8 L=17 S=4$"):
+        _hip.call(entry, *head, *key, *mid, *tail, None)
+
+
 # ---- the CLI ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("argv,msg", [
     (["--rng", "host", "--train_leader", "brake"], "--train_leader needs --rng device"),
