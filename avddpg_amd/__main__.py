@@ -508,6 +508,46 @@ def _record_warm(conf, args, e=0):
         conf.actor_hold = int(args.actor_hold)
 
 
+def _anchor_kw(args):
+    """VecTrainer's anchor keyword, only where the flag was given (`tuned` / `searched` resolved: _resolve_anchor)."""
+    return {} if getattr(args, "anchor", None) is None else dict(anchor=args.anchor)
+
+
+def _resolve_anchor(args, conf, hparams=None):
+    """--anchor before anything is allocated: the words `tuned` / `searched` become the law --baseline_tune / --baseline_search find
+    (computed once: the baseline section reuses it) around the flag's weight and decay, then the refusals that need the run's
+    configuration, under the flag's own name."""
+    from . import scenarios as _sc
+    from . import trainer
+
+    spec = getattr(args, "anchor", None)
+    if spec is None:
+        return
+    try:
+        if spec.pending:
+            args.baselines = _baselines(conf, args)
+            if spec.source == _sc.TUNED:
+                law = _sc.LinearLaw(_sc.TUNED, *[v for _, v in dict(args.baselines.tune)["gains"]])
+            else:
+                law = _sc.LinearLaw(_sc.SEARCHED, table=args.baselines.found.law.table)
+            args.anchor = spec = spec.with_gains(law, source=spec.source)
+        trainer.check_anchor(conf, spec, args.engine, int(os.environ.get("WORLD_SIZE", "1") or 1), hparams=hparams)
+    except ValueError as e:
+        raise SystemExit(f"--anchor: {e}")
+
+
+def _record_anchor(conf, args, vt, e=0):
+    """conf.json's anchor (a list of pairs: the law's record, the anchor loss per weight set of experiment e at the first learner call
+    and at the last), only where the flag was given. The two device tensors are read here, after training."""
+    if getattr(args, "anchor", None) is None:
+        return
+    if getattr(args, "anchor_result", None) is None:
+        first = vt.anchor_loss_first if vt.anchor_loss_first is not None else vt.anchor_losses()
+        args.anchor_result = (first.cpu().tolist(), vt.anchor_losses().cpu().tolist())
+    first, last = ([float(x) for x in v[e * vt.M:(e + 1) * vt.M]] for v in args.anchor_result)
+    conf.anchor = [["law", args.anchor.record()], ["anchor_loss_first", first], ["anchor_loss_last", last]]
+
+
 def _baselines(conf, args):
     """The run's baseline section, computed once (--residual tuned has already searched the grid)."""
     if getattr(args, "baselines", None) is None:
@@ -729,6 +769,17 @@ def get_cmdl_args(argv, conf):
                          "with --keep_best the step-0 snapshot is the fitted actors. Composes with --seeds, --train_disturb, --train_leader, "
                          "--keep_best and every --engine; not with --residual, --sweep / --pbt, --rng host, the centralized framework or a "
                          "process group of more than one rank (not in the reference CLI)")
+    tr.add_argument("--anchor", type=str, default=None, metavar="SPEC",
+                    help="anchor the actors to a linear CACC law WHILE they train (TD3+BC's behaviour-cloning term): kp=2,kv=1[,ka=..,kf=..,"
+                         "weight=..,decay=..]; the word tuned / searched may stand in place of the gains (the law --baseline_tune / "
+                         "--baseline_search finds), followed by the other keys. The actor loss becomes -q(s, mu(s)) + weight * (mu(s) - "
+                         "u*(s))^2, u* the law's clipped action on the sampled state, added to the critic's action gradient in the split set "
+                         "learner's seed launch; weight >= 0 (default 1), decay = N ramps it linearly to 0 over the first N learner calls "
+                         "(0: constant). conf.json records anchor (the law, and the mean (mu - u*)^2 per weight set at the first and the "
+                         "last learner call). Needs --engine fused3 (shared-set interfrl); combines with --seeds, --warm_start, "
+                         "--actor_hold, --train_disturb, --train_leader, --keep_best and --residual (the target is then a law for the "
+                         "correction); not with --sweep / --pbt, a process group of more than one rank or the centralized framework "
+                         "(not in the reference CLI)")
     tr.add_argument("--actor_hold", type=int, default=None, metavar="N",
                     help="hold the actors still for the first N learner calls (the steps past the replay gate): the actor's step size "
                          "handed to the update is 0 for them, so the critic learns to evaluate the policy it was handed (a --warm_start fit, "
@@ -842,6 +893,24 @@ def get_cmdl_args(argv, conf):
             ap.error("--warm_start tuned needs --scenarios and --baseline_tune (the grid the law is searched on)")
         if args.warm_start == _sc.SEARCHED and (args.scenarios is None or getattr(args, "baseline_search", None) is None):
             ap.error("--warm_start searched needs --scenarios and --baseline_search (the space the law is searched in)")
+    if getattr(args, "anchor", None) is not None:
+        from . import scenarios as _sc
+
+        if args.sweep is not None or args.pbt is not None:
+            ap.error("--anchor does not combine with --sweep / --pbt (the table-driven learn call has no anchored form)")
+        if args.engine != "fused3":
+            ap.error(f"--anchor needs --engine fused3 (the split set learner holds the anchored seed), got --engine {args.engine}")
+        if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+            ap.error("--anchor is not available under a process group of more than one rank")
+        try:  # (what needs the run's configuration: trainer.check_anchor applies it)
+            args.anchor = _sc.parse_anchor(args.anchor)
+            _sc.check_anchor(args.anchor)
+        except ValueError as e:
+            ap.error(f"--anchor: {e}")
+        if args.anchor.pending and args.anchor.source == _sc.TUNED and (args.scenarios is None or getattr(args, "baseline_tune", None) is None):
+            ap.error("--anchor tuned needs --scenarios and --baseline_tune (the grid the law is searched on)")
+        if args.anchor.pending and args.anchor.source == _sc.SEARCHED and (args.scenarios is None or getattr(args, "baseline_search", None) is None):
+            ap.error("--anchor searched needs --scenarios and --baseline_search (the space the law is searched in)")
     if getattr(args, "actor_hold", None) is not None:
         if args.actor_hold < 1:
             ap.error(f"--actor_hold: N={args.actor_hold} must be >= 1")
@@ -895,6 +964,14 @@ def get_cmdl_args(argv, conf):
                 _tr.check_warm_start(conf, ws, args.rng, 1, residual=getattr(args, "residual", None))
             except ValueError as e:
                 ap.error(f"--warm_start: {e}")
+        an = getattr(args, "anchor", None)
+        if an is not None and not an.pending:  # (`tuned` / `searched`: checked once the law exists, _resolve_anchor)
+            from . import trainer as _tr
+
+            try:
+                _tr.check_anchor(conf, an, args.engine, 1)
+            except ValueError as e:
+                ap.error(f"--anchor: {e}")
     return args, conf
 
 
@@ -943,9 +1020,10 @@ def main(argv=None, conf=None):
             _check_train_leader(args, conf, "platoon")
             _resolve_residual(args, conf, "platoon")
             _resolve_warm_start(args, conf)
+            _resolve_anchor(args, conf)
             try:
                 vt = trainer.VecTrainer(conf, rng="device", auto_reset="platoon", shared_engine=args.engine, fused_update=nofrl,
-                                        train_disturb=args.train_disturb, **_lead_kw(args), **_residual_kw(args), **_warm_kw(args))
+                                        train_disturb=args.train_disturb, **_lead_kw(args), **_residual_kw(args), **_warm_kw(args), **_anchor_kw(args))
             except ValueError as e:
                 if args.train_disturb is None:
                     raise
@@ -994,9 +1072,10 @@ def main(argv=None, conf=None):
             _check_train_leader(args, conf, False)
             _resolve_residual(args, conf, False)
             _resolve_warm_start(args, conf)
+            _resolve_anchor(args, conf)
             try:
                 vt = trainer.VecTrainer(conf, rng=args.rng, auto_reset=False, shared_engine=args.engine, train_disturb=args.train_disturb,
-                                        **_lead_kw(args), **_residual_kw(args), **_warm_kw(args))
+                                        **_lead_kw(args), **_residual_kw(args), **_warm_kw(args), **_anchor_kw(args))
             except ValueError as e:
                 if args.train_disturb is None:
                     raise
@@ -1032,6 +1111,7 @@ def main(argv=None, conf=None):
         _record_train_leader(conf, args)
         _record_residual(conf, args)
         _record_warm(conf, args)
+        _record_anchor(conf, args, vt)
         if args.keep_best is not None:
             _KeepResults(vt, args).write(base, conf, n_save)
         artifacts.config_writer(os.path.join(base, "conf.json"), conf)
@@ -1156,10 +1236,11 @@ def train_seed_batch(args, conf, base, experiments=None):
     _check_train_leader(args, conf, "platoon", hparams=hps)
     _resolve_residual(args, conf, "platoon", hparams=hps)
     _resolve_warm_start(args, conf, hparams=hps)
+    _resolve_anchor(args, conf, hparams=hps)
     try:
         vt = trainer.VecTrainer(conf, rng="device", auto_reset="platoon", shared_engine=args.engine,
                                 fused_update=conf.fed_method == conf.nofrl, seeds=seeds, hparams=hps,
-                                train_disturb=getattr(args, "train_disturb", None), **_lead_kw(args), **_residual_kw(args), **_warm_kw(args))
+                                train_disturb=getattr(args, "train_disturb", None), **_lead_kw(args), **_residual_kw(args), **_warm_kw(args), **_anchor_kw(args))
     except ValueError as e:
         raise SystemExit(f"{flag}: {e}")
     vt.reset_episode()
@@ -1257,6 +1338,7 @@ def train_seed_batch(args, conf, base, experiments=None):
         _record_train_leader(ce, args)
         _record_residual(ce, args)
         _record_warm(ce, args, e)
+        _record_anchor(ce, args, vt, e)
         if suite is not None:
             _write_suite(d, ce, _slice(suite, e), range(1, P + 1), args)
             if baselines is not None:

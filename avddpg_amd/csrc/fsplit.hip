@@ -32,6 +32,7 @@
 #include <type_traits>
 
 #include "fset_common.h"
+#include "anchor.h"
 
 namespace avd {
 namespace fsplit {
@@ -1748,7 +1749,7 @@ static void print_head_stamps(hipStream_t st) {
 template <int S, class... H>
 static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, const float* theta, const float* stats, const float* theta_t,
                const float* stats_t, const float* s, const float* a, const float* r, const float* s2, const float* aw, float gamma,
-               float high, float* grads, float* losses, unsigned char* ws, const Plan& pl, hipStream_t st, H... hp) {
+               float high, float* grads, float* losses, unsigned char* ws, const Plan& pl, hipStream_t st, const AnchorArgs* an, H... hp) {
     PrepArgs pa;
     pa.L = L, pa.S = S, pa.theta = theta, pa.stats = stats, pa.theta_t = theta_t, pa.stats_t = stats_t;
     pa.wap = (unsigned*)(ws + pl.wap), pa.bad = (int*)(ws + pl.bad), pa.smax = (unsigned*)(ws + pl.smax);
@@ -1847,7 +1848,14 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
         SeedArgs sd;
         sd.n_agents = n_agents, sd.n_sets = n_sets, sd.dmu = dmu, sd.tz = F(pl.tz), sd.high = high, sd.g3 = g3, sd.part_m = F(pl.partM[0]),
         sd.part_s = F(pl.partHs[0]);
-        hipLaunchKernelGGL(actor_seed_kernel, grid, block, 0, st, sd);
+        if (an) {  // the anchored seed in actor_seed_kernel's place, then the anchor loss's reducer (one wave per set)
+            AnchorArgs q = *an;
+            q.n_agents = n_agents, q.n_sets = n_sets, q.S = S, q.J = pl.J, q.dmu = dmu, q.tz = sd.tz, q.high = high, q.g3 = g3;
+            q.part_m = sd.part_m, q.part_s = sd.part_s, q.mu = mu, q.s = s, q.aw = aw, q.inv_n = inv_n, q.c = 2.f * an->weight * inv_n;
+            q.bad = bad;
+            launch_anchor_seed(q, pl.grid, st);  // (csrc/anchor.hip)
+        } else
+            hipLaunchKernelGGL(actor_seed_kernel, grid, block, 0, st, sd);
         dw.sm = sma, dx.sm = sma;
         dw.net = net[0], dw.act = nullptr, dw.partG = F(pl.partG[0]), dw.part_m = F(pl.partM[0]);
         hipLaunchKernelGGL((dw_kernel<S, ActorS>), grid, block, 0, st, dw);
@@ -1904,7 +1912,7 @@ template <class... H>
 static int split_entry(int phases, const char* who, const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
                        const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r, const float* s2,
                        const float* agent_weight, float gamma, float high, float* grads, float* losses, void* workspace,
-                       size_t workspace_bytes, void* stream, H... hp) {
+                       size_t workspace_bytes, void* stream, const AnchorArgs* an, H... hp) {
     int rc = fsplit::check_shape(lay, n_agents, n_sets, who);
     if (rc) return rc;
     const bool cr = phases & fsplit::PH_CRITIC;
@@ -1915,9 +1923,9 @@ static int split_entry(int phases, const char* who, const avd_mlp_layout* lay, i
     //  gradient producer keeps them zero)
     if (lay->S == 4)
         return fsplit::run<4>(phases, *lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2, agent_weight, gamma, high, grads,
-                              losses, (unsigned char*)workspace, pl, (hipStream_t)stream, hp...);
+                              losses, (unsigned char*)workspace, pl, (hipStream_t)stream, an, hp...);
     return fsplit::run<3>(phases, *lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2, agent_weight, gamma, high, grads, losses,
-                          (unsigned char*)workspace, pl, (hipStream_t)stream, hp...);
+                          (unsigned char*)workspace, pl, (hipStream_t)stream, an, hp...);
 }
 
 extern "C" int avd_learn_set_split_f16x3(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
@@ -1925,7 +1933,30 @@ extern "C" int avd_learn_set_split_f16x3(const avd_mlp_layout* lay, int n_agents
                                           const float* s2, const float* agent_weight, float gamma, float high, float* grads,
                                           float* losses, void* workspace, size_t workspace_bytes, void* stream) {
     return split_entry(fsplit::PH_BOTH, "avd_learn_set_split_f16x3", lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2,
-                       agent_weight, gamma, high, grads, losses, workspace, workspace_bytes, stream);
+                       agent_weight, gamma, high, grads, losses, workspace, workspace_bytes, stream, nullptr);
+}
+
+// the whole call with the anchored seed (anchor_seed_kernel) and the per-set anchor loss: everything refused here is refused before a HIP call
+extern "C" int avd_learn_set_split_anchor_f16x3(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
+                                                const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
+                                                const float* s2, const float* agent_weight, float gamma, float high, float* grads,
+                                                float* losses, void* workspace, size_t workspace_bytes, const float* gains, int M,
+                                                int model_a, float lo, float hi, float weight, float* anchor_loss, void* stream) {
+    const char* who = "avd_learn_set_split_anchor_f16x3";
+    int rc = fsplit::check_shape(lay, n_agents, n_sets, who);
+    if (rc) return rc;
+    AVD_REQUIRE(gains && anchor_loss, "%s: null gains / anchor_loss", who);
+    AVD_REQUIRE(M >= 1 && n_sets % M == 0, "%s: n_sets=%d M=%d (n_sets must be a multiple of M >= 1)", who, n_sets, M);
+    unsigned wbits;  // (bit tests: this file is built with -fno-honor-nans) sign clear or -0, exponent not all ones
+    memcpy(&wbits, &weight, sizeof wbits);
+    AVD_REQUIRE((wbits & 0x7f800000u) != 0x7f800000u && (!(wbits >> 31) || wbits == 0x80000000u), "%s: weight=%g (must be finite and >= 0)",
+                who, (double)weight);
+    AVD_REQUIRE(lo <= hi, "%s: lo=%g > hi=%g", who, (double)lo, (double)hi);
+    AnchorArgs an{};
+    an.gains = gains, an.M = M, an.model_a = model_a, an.lo = lo, an.hi = hi, an.weight = weight;
+    an.anchor_loss = anchor_loss;
+    return split_entry(fsplit::PH_BOTH, who, lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2, agent_weight, gamma, high,
+                       grads, losses, workspace, workspace_bytes, stream, &an);
 }
 
 // a hyperparameter sweep: the whole call with each weight set's gamma from d_hp (set j: row (j / set_block) % n_groups) in the TD epilogue
@@ -1936,7 +1967,7 @@ extern "C" int avd_learn_set_split_hp_f16x3(const avd_mlp_layout* lay, int n_age
                                             void* stream) {
     AVD_REQUIRE_HP("avd_learn_set_split_hp_f16x3", d_hp, n_groups, set_block, n_sets);
     return split_entry(fsplit::PH_BOTH, "avd_learn_set_split_hp_f16x3", lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2,
-                       agent_weight, 0.f, high, grads, losses, workspace, workspace_bytes, stream, HpRef{d_hp, n_groups, set_block});
+                       agent_weight, 0.f, high, grads, losses, workspace, workspace_bytes, stream, nullptr, HpRef{d_hp, n_groups, set_block});
 }
 
 // deprecated alias (r03's name: the operand pairs were bf16 then; every pair has been fp16 since r04)
@@ -1953,11 +1984,11 @@ extern "C" int avd_learn_set_split_critic(const avd_mlp_layout* lay, int n_agent
                                           const float* s2, const float* agent_weight, float gamma, float high, float* grads,
                                           float* losses, void* workspace, size_t workspace_bytes, void* stream) {
     return split_entry(fsplit::PH_CRITIC, "avd_learn_set_split_critic", lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2,
-                       agent_weight, gamma, high, grads, losses, workspace, workspace_bytes, stream);
+                       agent_weight, gamma, high, grads, losses, workspace, workspace_bytes, stream, nullptr);
 }
 
 extern "C" int avd_learn_set_split_actor(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
                                          const float* s, float high, float* grads, void* workspace, size_t workspace_bytes, void* stream) {
     return split_entry(fsplit::PH_ACTOR, "avd_learn_set_split_actor", lay, n_agents, n_sets, theta, stats, nullptr, nullptr, s, nullptr, nullptr,
-                       nullptr, nullptr, 0.f, high, grads, nullptr, workspace, workspace_bytes, stream);
+                       nullptr, nullptr, 0.f, high, grads, nullptr, workspace, workspace_bytes, stream, nullptr);
 }

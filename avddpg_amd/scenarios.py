@@ -828,6 +828,113 @@ def check_warm_start(spec, conf=None):
     return spec
 
 
+# ---- anchor: a behaviour-cloning term ties the actors to a linear law while they train (tr --anchor; avd_learn_set_split_anchor_f16x3) ----
+
+ANCHOR_NAME = "anchor"
+_ANCHOR_KEYS = GAIN_KEYS + ("weight", "decay")
+
+
+class Anchor(LinearLaw):
+    """A LinearLaw the actor loss is anchored to (TD3+BC's term): the actors minimise -q(s, mu(s)) + weight * (mu(s) - u*(s))^2 with u*
+    the law's clipped action on the sampled state. ``decay`` (a whole number of learner calls, 0 = constant) ramps the weight linearly
+    to 0 at that call. ``source`` records where the gains came from: "given", "tuned" or "searched"; ``pending`` is True for a spec
+    parsed from the word ``tuned`` / ``searched`` whose gains the caller has yet to fill in (with_gains)."""
+
+    def __init__(self, kp=0, kv=0, ka=0, kf=0, table=None, weight=1.0, decay=0, name=ANCHOR_NAME, source="given", pending=False):
+        super().__init__(name, kp, kv, ka, kf, table)
+        self.weight, self.decay, self.source, self.pending = weight, decay, str(source), bool(pending)
+
+    def weight_at(self, call):
+        """The float32 weight of learner call ``call`` (0-based): ``weight``, or with a decay weight * max(0, 1 - call / decay) --
+        computed in float64 and rounded once."""
+        w = float(self.weight)
+        if self.decay:
+            w = w * max(0.0, 1.0 - float(int(call)) / float(int(self.decay)))
+        return float(np.float32(w))
+
+    def record(self):
+        """conf.json's anchor law, a list of pairs like ResidualLaw.record: the gains, the weight, the decay, the table when there is one,
+        the source."""
+        out = [[k, float(getattr(self, k))] for k in GAIN_KEYS] + [["weight", float(self.weight)], ["decay", int(self.decay)]]
+        if self.table is not None:
+            out.append(["table", np.asarray(self.table, dtype=np.float64).tolist()])
+        return out + [["source", self.source]]
+
+    @classmethod
+    def from_record(cls, pairs):
+        """The spec of a conf.json's anchor law (None stays None); an unknown or repeated key is a ValueError."""
+        if pairs is None:
+            return None
+        keys = [k for k, _ in pairs]
+        bad = sorted({k for k in keys if k not in _ANCHOR_KEYS + ("table", "source") or keys.count(k) > 1})
+        if bad:
+            raise ValueError(f"anchor: unknown or repeated key(s) {bad}")
+        d = dict(pairs)
+        return cls(*(d.get(k, 0) for k in GAIN_KEYS), table=d.get("table"), weight=d.get("weight", 1.0), decay=d.get("decay", 0),
+                   source=d.get("source", "given"))
+
+    def with_gains(self, law, source):
+        """This spec's weight and decay around another law's gains (the tuned / searched law)."""
+        return Anchor(law.kp, law.kv, law.ka, law.kf, table=law.table, weight=self.weight, decay=self.decay, source=source)
+
+    def __repr__(self):
+        return "Anchor(" + ", ".join([f"{k}={v!r}" for k, v in self.items()] + [f"weight={self.weight!r}", f"decay={self.decay!r}"]) + ")"
+
+
+def parse_anchor(text):
+    """``kp=2,kv=1[,ka=..,kf=..,weight=..,decay=..]`` -> Anchor. The word ``tuned`` / ``searched`` may stand in place of the gains,
+    followed by the other keys (``tuned,weight=10``): the Anchor then has ``pending`` set and ``source`` that word, and the caller takes
+    the gains --baseline_tune / --baseline_search find (with_gains). An unknown key, a key given twice, a gain beside the word, a value
+    that is no number or an empty text is a ValueError; the values are checked by check_anchor."""
+    text = str(text).strip()
+    kw, word = {}, None
+    parts = [q.strip() for q in text.split(",") if q.strip()]
+    if not parts:
+        raise ValueError(f"anchor {text!r}: no gain given (kp=..,kv=..[,ka=..,kf=..,weight=..,decay=..], or the word {TUNED!r} / "
+                         f"{SEARCHED!r} in place of the gains)")
+    if parts[0] in (TUNED, SEARCHED):
+        word, parts = parts[0], parts[1:]
+    for part in parts:
+        key, eq, val = part.partition("=")
+        key, val = key.strip(), val.strip()
+        if not eq or key not in _ANCHOR_KEYS:
+            raise ValueError(f"anchor: unknown key {key!r} (one of {', '.join(_ANCHOR_KEYS)}, as key=value; the word {TUNED!r} / "
+                             f"{SEARCHED!r} may stand first, in place of the gains)")
+        if word is not None and key in GAIN_KEYS:
+            raise ValueError(f"anchor: {key} given beside the word {word!r} (the word stands in place of the gains)")
+        if key in kw:
+            raise ValueError(f"anchor: {key} given twice")
+        try:
+            kw[key] = float(val)
+        except ValueError:
+            raise ValueError(f"anchor: {key}={val!r} is not a number") from None
+    if "decay" in kw:
+        if not math.isfinite(kw["decay"]) or kw["decay"] != int(kw["decay"]):
+            raise ValueError(f"anchor: decay={kw['decay']!r} is not a whole number")
+        kw["decay"] = int(kw["decay"])
+    if word is not None:
+        return Anchor(source=word, pending=True, **kw)
+    return Anchor(**kw)
+
+
+def check_anchor(spec, conf=None):
+    """The spec, checked. A ValueError for: not an Anchor; check_baselines' rules (a non-finite gain, a table that is not [*, 4]; with
+    ``conf`` a non-zero kf under Model A, a table whose row count is not conf.pl_size, the centralized framework); a weight that is not
+    a finite number >= 0; a decay that is no whole number >= 0."""
+    if not isinstance(spec, Anchor):
+        raise ValueError(f"{spec!r} is not a scenarios.Anchor")
+    check_baselines([spec], conf, reserved=())
+    w = spec.weight
+    if isinstance(w, bool) or not isinstance(w, (int, float, np.integer, np.floating)) or not math.isfinite(w) or not w >= 0:
+        raise ValueError(f"anchor: weight={w!r} must be a finite number >= 0")
+    if float(w) > float(np.finfo(np.float32).max):
+        raise ValueError(f"anchor: weight={w!r} does not fit float32")
+    d = spec.decay
+    if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or d < 0:
+        raise ValueError(f"anchor: decay={d!r} must be a whole number of learner calls >= 0")
+    return spec
+
+
 def parse_gain_grid(text):
     """``kp=lo:hi:n,kv=...`` (keys of GAIN_KEYS; ``key=value`` is the single value) -> float32 [G, 4]: per key np.linspace(lo, hi, n) in
     float64, then cast; a missing key is the single value 0; the product in kp, kv, ka, kf order, the last varying fastest. A

@@ -198,6 +198,34 @@ def check_warm_start(conf, warm_start, rng, world_size=1, hparams=None, residual
     return scenarios.check_warm_start(warm_start, conf)
 
 
+def check_anchor(conf, anchor, shared_engine=None, world_size=1, hparams=None, overlap_allreduce=None, shared_sets=None):
+    """Why a run cannot anchor its actors to this linear law while it trains (VecTrainer(anchor=...)), raised as a ValueError -- or the
+    checked scenarios.Anchor. Called before anything is allocated or launched. The behaviour-cloning term sits in the split set
+    learner's seed launch (avd_learn_set_split_anchor_f16x3): shared_engine='fused3', so shared-set interfrl, on one rank, in the
+    single call (no overlapped exchange), outside any sweep."""
+    from . import scenarios
+
+    if conf.framework == conf.cntrl:
+        raise ValueError("an anchor needs the decentralized framework: a linear law is per vehicle")
+    if shared_engine != "fused3":
+        raise ValueError(f"an anchor needs shared_engine='fused3' (the split set learner holds the anchored seed; the per-agent engines "
+                         f"and the bf16 set learners have none), got shared_engine={shared_engine!r}")
+    can_share = (is_fed_enabled(conf) and conf.fed_method == conf.interfrl and is_gradient_updates_enabled(conf)
+                 and conf.fed_update_delay_steps == 1 and conf.fed_update_count == 1 and conf.fed_cutoff_ratio >= 1.0)
+    if not can_share or (shared_sets is not None and not shared_sets):
+        raise ValueError("an anchor needs shared weight sets: interfrl + gradients with every step federated (the fused3 engine's regime)")
+    if hparams is not None:
+        raise ValueError("an anchor does not combine with a hyperparameter sweep or PBT (hparams=...): the table-driven learn call has no "
+                         "anchored form")
+    if overlap_allreduce:
+        raise ValueError("an anchor does not combine with overlap_allreduce: the two-phase learn call has no anchored form")
+    if int(world_size) > 1:
+        raise ValueError("an anchor runs on one rank: no process group of more than one rank")
+    if getattr(anchor, "pending", False):
+        raise ValueError(f"anchor: the word {anchor.source!r} stands for gains that have not been filled in (Anchor.with_gains)")
+    return scenarios.check_anchor(anchor, conf)
+
+
 def check_actor_hold(actor_hold, hparams=None):
     """Why a run cannot hold its actors still for its first ``actor_hold`` learner calls, raised as a ValueError -- or the count."""
     if isinstance(actor_hold, bool) or not isinstance(actor_hold, (int, np.integer)) or actor_hold < 0:
@@ -234,7 +262,7 @@ class VecTrainer:
     def __init__(self, conf, device=None, rng="device", group=None, shared_sets=None, seed=None, auto_reset=False,
                  pipeline_chunks=1, fused_update=False, shared_engine=None, init_seed=None, fused_step=None,
                  replay_ring=None, overlap_allreduce=None, seeds=None, hparams=None, train_disturb=None, train_leader=None,
-                 residual=None, warm_start=None, actor_hold=0):
+                 residual=None, warm_start=None, actor_hold=0, anchor=None):
         """group: torch.distributed process group whose ranks each hold ``conf.num_platoons`` platoons
         (interfrl gradients are all-reduced over it). auto_reset: end episodes on the device (no host
         sync per step); needs rng='device'. True: the reference's rule -- any terminal platoon (or the step limit) ends
@@ -281,7 +309,13 @@ class VecTrainer:
         handed to the update is 0 for them (AgentGroup.actor_lr), the configuration's afterwards. No kernel changes: w - 0 * x = w keeps
         the actor's bits, and the actor's Adam moments and iteration count keep accumulating under the hold. The critic learns to
         evaluate the policy it was handed; every engine and framework that does not read its step sizes from a sweep table. 0: the
-        configuration's step size is passed as always."""
+        configuration's step size is passed as always.
+        anchor: a scenarios.Anchor the actor loss is tied to while training (TD3+BC's behaviour-cloning term): every learner call runs
+        avd_learn_set_split_anchor_f16x3 with the weight Anchor.weight_at(call) -- also once a decay has brought it to 0, so that
+        anchor_losses() (the last call's mean (mu - u*)^2 per weight set, on the device) stays a diagnostic. With a seed batch every
+        experiment gets the same table (set e * M + m uses row m); with a residual policy the law is the target of the correction.
+        check_anchor says what it needs (shared_engine='fused3', one rank, no sweep, no overlapped exchange). None: nothing is allocated,
+        the un-anchored entry point runs."""
         conf.refresh()
         self.levels = self.manoeuvres = self.lead = None
         self.residual = None
@@ -300,6 +334,13 @@ class VecTrainer:
                 ranks = _td.get_world_size(group)
             self.warm_start = check_warm_start(conf, warm_start, rng, ranks, hparams, residual)
         self.actor_hold = check_actor_hold(actor_hold, hparams)
+        self.anchor = self.anchor_gains = self.anchor_loss = self.anchor_loss_first = self.anchor_weight = None
+        if anchor is not None:
+            ranks = 1
+            if group is not None:
+                import torch.distributed as _td
+                ranks = _td.get_world_size(group)
+            self.anchor = check_anchor(conf, anchor, shared_engine, ranks, hparams, overlap_allreduce, shared_sets)
         self.learner_calls = 0  # steps that passed the replay gate (what actor_hold counts)
         if train_disturb is not None:
             self.levels = check_train_disturb(conf, train_disturb, rng, group, fused_step, hparams)
@@ -467,6 +508,9 @@ class VecTrainer:
                 raise ValueError("a residual policy needs the fused step (fused_step=False has no law in front of the plant)")
             self.res_gains = torch.from_numpy(self.residual.gains(self.L)).to(self.device)
             self.applied = torch.zeros(self.P, self.L, **f32)
+        if self.anchor is not None:  # the gain table, uploaded once; the per-set anchor loss of the last learner call
+            self.anchor_gains = torch.from_numpy(self.anchor.gains(self.L)).to(self.device)
+            self.anchor_loss = torch.zeros(self.Mf, **f32)
         self.fused_update = bool(fused_update)  # nofrl (any framework / widths the learn kernels serve): avd_learn_update_f32
         # fused_update also has the learn kernel evaluate the UPDATED actor on the state the next step acts from
         # (workers/trainer.py:287-289): self.actor_out then already holds the next step's actor outputs unless the states
@@ -709,8 +753,15 @@ class VecTrainer:
                 self._learn_split_overlapped(s, a, r, s2, aw, wsum, carry)
                 self._flag_exchanged = carry is not None
                 return
-            self.agents.learn_set_fused(s, a, r, s2, P * M, grads=self.set_grads, losses=self.set_losses, agent_weight=aw,
-                                        split=self.shared_engine == "fused3")
+            if self.anchor is not None:  # (fused3, checked) the weight of this learner call: learner_calls counts it already
+                self.anchor_weight = self.anchor.weight_at(self.learner_calls - 1)
+                self.agents.learn_set_split_anchor(s, a, r, s2, P * M, self.anchor_gains, self.anchor_weight, self.anchor_loss,
+                                                   grads=self.set_grads, losses=self.set_losses, agent_weight=aw)
+                if self.learner_calls == 1:  # the first learner call's, kept on the device (conf.json's anchor_loss_first)
+                    self.anchor_loss_first = self.anchor_loss.clone()
+            else:
+                self.agents.learn_set_fused(s, a, r, s2, P * M, grads=self.set_grads, losses=self.set_losses, agent_weight=aw,
+                                            split=self.shared_engine == "fused3")
         else:
             if aw_dev is not None:
                 rw = aw_dev.view(P, M).transpose(0, 1).reshape(M, P, 1).expand(M, P, B).reshape(M, P * B).contiguous()
@@ -908,6 +959,13 @@ class VecTrainer:
                     break
             self.update_reward_list(ep)
         return self.all_ep_reward_lists, self.all_avg_reward_lists
+
+    def anchor_losses(self):
+        """The last learner call's anchor loss per weight set, float32 [E * M] on the device: mean over the set's sampled rows of
+        w (mu - u*)^2, not times the weight (zeros before the first learner call)."""
+        if self.anchor is None:
+            raise ValueError("anchor_losses needs VecTrainer(anchor=...)")
+        return self.anchor_loss
 
     def fit_warm_start(self):
         """The warm start's fit (AgentGroup.clone_fit with this trainer's seed or seed table), once, before the first update: the actors

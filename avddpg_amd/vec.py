@@ -747,6 +747,30 @@ class AgentGroup:
         """learn_set_fused with f32-class results (split operands, csrc/fsplit.hip)."""
         return self.learn_set_fused(s, a, r, s2, n_agents, grads=grads, losses=losses, agent_weight=agent_weight, split=True)
 
+    def learn_set_split_anchor(self, s, a, r, s2, n_agents, gains, weight, anchor_loss, grads=None, losses=None, agent_weight=None):
+        """learn_set_split with a behaviour-cloning term in the actor loss (avd_learn_set_split_anchor_f16x3): the actors minimise
+        -mean(w q(s, mu)) + weight * mean(w (mu - u*)^2), u* the clipped linear law of ``gains`` [M, 4] (float32, on the device; set j uses
+        row j % M, the seed-batch layout) on the sampled state. ``anchor_loss`` [n_sets] receives mean(w (mu - u*)^2) per set -- not times
+        ``weight``, and for weight 0 too. The critic block and ``losses`` are learn_set_split's bit for bit."""
+        self._no_hp("learn_set_split_anchor")
+        self._check_agent_major(s, a, r, s2, n_agents, agent_weight)
+        if (gains.dim() != 2 or gains.shape[1] != 4 or gains.dtype != torch.float32 or not gains.is_contiguous() or gains.shape[0] < 1
+                or self.n_sets % gains.shape[0]):
+            raise _hip.AvdError(f"anchor: gains must be contiguous float32 [M, 4] with n_sets={self.n_sets} a multiple of M, got "
+                                f"{tuple(gains.shape)} {gains.dtype}")
+        if anchor_loss.numel() != self.n_sets or anchor_loss.dtype != torch.float32 or not anchor_loss.is_contiguous():
+            raise _hip.AvdError(f"anchor: anchor_loss must be contiguous float32 [{self.n_sets}], got {tuple(anchor_loss.shape)} "
+                                f"{anchor_loss.dtype}")
+        if grads is None:
+            grads = torch.empty(self.n_sets, self.lay.theta_size, dtype=torch.float32, device=self.device)
+        ws = self._workspace("_fsplit_ws", "avd_learn_set_split_workspace", n_agents)
+        c = self.config
+        call("avd_learn_set_split_anchor_f16x3", self._layp, n_agents, self.n_sets, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
+             ptr(self.stats_t), ptr(s), ptr(a), ptr(r), ptr(s2), ptr(agent_weight), c.gamma, self.high, ptr(grads), ptr(losses), ptr(ws),
+             ws.numel(), ptr(gains), int(gains.shape[0]), int(c.model == c.modelA), float(c.action_low), float(c.action_high), float(weight),
+             ptr(anchor_loss), stream_handle())
+        return grads
+
     def _check_agent_major(self, s, a, r, s2, n_agents, agent_weight):
         """The set learners of csrc/fset.hip / fsplit.hip take raw pointers to tightly packed AGENT-major f32 batches
         [n_agents, B, S]: a set-major or strided view (what learn_shared wants) would silently give wrong gradients."""

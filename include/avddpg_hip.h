@@ -561,6 +561,25 @@ int avd_learn_set_split_f16x3(const avd_mlp_layout* lay, int n_agents, int n_set
                                const float* s2, const float* agent_weight, float gamma, float high, float* grads, float* losses,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* avd_learn_set_split_f16x3 with a behaviour-cloning term in the actor loss (TD3+BC's; tr --anchor):
+ *   La' = -mean(w q(s, mu(s))) + weight * mean(w (mu(s) - u*(s))^2),  u* = clip(linear law(gains[j % M], s), lo, hi)
+ * over the P * 64 rows of set j (w: agent_weight's factor of the row's agent, 1 when null). gains [M][4] rows (kp, kv, ka, kf), set j
+ * uses row j % M (the seed-batch layout set = e * M + m of avd_clone_sample_f32); model_a != 0 skips the feed-forward term, as the
+ * evaluators' law does (csrc/eval_common.h linear_law: the same function, float32, no contraction). The chain is the un-anchored
+ * call's with ONE kernel exchanged: in place of the actor's backward seed d mu * high * (1 - tanh(z)^2) runs the anchored seed
+ * with d mu' = d mu + (2 weight / N) w (mu - u*), N = P * 64; one small launch more sums
+ *   anchor_loss[j] = (1 / N) sum w (mu - u*)^2      (NOT times weight; written for weight == 0 too)
+ * in a fixed order (per-wave partials, one wave per set): two calls give the same bits. The critic block of `grads` and both
+ * `losses` are the un-anchored call's bit for bit (losses[j][1] stays the mean of q(s, mu)); with weight == 0 so is the actor block.
+ * Same workspace as avd_learn_set_split_f16x3 (avd_learn_set_split_workspace). Refused on the host before any HIP call: everything
+ * avd_learn_set_split_f16x3 refuses, null gains / anchor_loss, M < 1 or n_sets % M != 0, weight negative or non-finite, lo > hi.
+ * There is no two-phase and no per-set-gamma form of this call. */
+int avd_learn_set_split_anchor_f16x3(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
+                                     const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
+                                     const float* s2, const float* agent_weight, float gamma, float high, float* grads, float* losses,
+                                     void* workspace, size_t workspace_bytes, const float* gains, int M, int model_a, float lo, float hi,
+                                     float weight, float* anchor_loss, void* stream);
+
 /* Deprecated alias of avd_learn_set_split_f16x3 (same arguments, same results). */
 int avd_learn_set_split_bf16x3(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
                                const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
