@@ -548,6 +548,17 @@ def _record_anchor(conf, args, vt, e=0):
     conf.anchor = [["law", args.anchor.record()], ["anchor_loss_first", first], ["anchor_loss_last", last]]
 
 
+def _noise_kw(args):
+    """VecTrainer's target_noise keyword, only where the flag was given."""
+    return {} if getattr(args, "target_noise", None) is None else dict(target_noise=args.target_noise)
+
+
+def _record_noise(conf, args):
+    """conf.json's target_noise (a list of pairs: sigma, clip), only where the flag was given."""
+    if getattr(args, "target_noise", None) is not None:
+        conf.target_noise = args.target_noise.record()
+
+
 def _baselines(conf, args):
     """The run's baseline section, computed once (--residual tuned has already searched the grid)."""
     if getattr(args, "baselines", None) is None:
@@ -780,6 +791,14 @@ def get_cmdl_args(argv, conf):
                          "--actor_hold, --train_disturb, --train_leader, --keep_best and --residual (the target is then a law for the "
                          "correction); not with --sweep / --pbt, a process group of more than one rank or the centralized framework "
                          "(not in the reference CLI)")
+    tr.add_argument("--target_noise", type=str, default=None, metavar="SPEC",
+                    help="target policy smoothing (TD3's): sigma=0.2[,clip=0.5]; the critic's targets evaluate the target critic at "
+                         "clip(mu'(s') + clip(sigma n, -clip, clip), action bounds), n ~ N(0, 1) per sampled row drawn on the device, in one "
+                         "small launch of the split set learner's chain; clip defaults to 2.5 sigma (inf: no noise clip), sigma 0 trains what "
+                         "the run without the flag trains. conf.json records target_noise (sigma, clip). Needs --engine fused3 (shared-set "
+                         "interfrl) and --rng device; combines with --seeds, --anchor, --warm_start, --actor_hold, --residual, "
+                         "--train_disturb, --train_leader and --keep_best; not with --sweep / --pbt, a process group of more than one rank "
+                         "or the centralized framework (not in the reference CLI)")
     tr.add_argument("--actor_hold", type=int, default=None, metavar="N",
                     help="hold the actors still for the first N learner calls (the steps past the replay gate): the actor's step size "
                          "handed to the update is 0 for them, so the critic learns to evaluate the policy it was handed (a --warm_start fit, "
@@ -911,6 +930,21 @@ def get_cmdl_args(argv, conf):
             ap.error("--anchor tuned needs --scenarios and --baseline_tune (the grid the law is searched on)")
         if args.anchor.pending and args.anchor.source == _sc.SEARCHED and (args.scenarios is None or getattr(args, "baseline_search", None) is None):
             ap.error("--anchor searched needs --scenarios and --baseline_search (the space the law is searched in)")
+    if getattr(args, "target_noise", None) is not None:
+        from . import trainer as _tr
+
+        if args.sweep is not None or args.pbt is not None:
+            ap.error("--target_noise does not combine with --sweep / --pbt (the table-driven learn call has no smoothed form)")
+        if args.engine != "fused3":
+            ap.error(f"--target_noise needs --engine fused3 (the split set learner holds the smoothing launch), got --engine {args.engine}")
+        if args.rng != "device":
+            ap.error("--target_noise needs --rng device (the noise is drawn by the device's generator)")
+        if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+            ap.error("--target_noise is not available under a process group of more than one rank")
+        try:  # (what needs the run's configuration is checked below, once it exists)
+            args.target_noise = _tr.check_target_noise(_tr.TargetNoise.parse(args.target_noise))
+        except ValueError as e:
+            ap.error(f"--target_noise: {e}")
     if getattr(args, "actor_hold", None) is not None:
         if args.actor_hold < 1:
             ap.error(f"--actor_hold: N={args.actor_hold} must be >= 1")
@@ -972,6 +1006,13 @@ def get_cmdl_args(argv, conf):
                 _tr.check_anchor(conf, an, args.engine, 1)
             except ValueError as e:
                 ap.error(f"--anchor: {e}")
+        if getattr(args, "target_noise", None) is not None:
+            from . import trainer as _tr
+
+            try:
+                _tr.check_target_noise(args.target_noise, conf, args.engine, args.rng, 1)
+            except ValueError as e:
+                ap.error(f"--target_noise: {e}")
     return args, conf
 
 
@@ -1023,7 +1064,7 @@ def main(argv=None, conf=None):
             _resolve_anchor(args, conf)
             try:
                 vt = trainer.VecTrainer(conf, rng="device", auto_reset="platoon", shared_engine=args.engine, fused_update=nofrl,
-                                        train_disturb=args.train_disturb, **_lead_kw(args), **_residual_kw(args), **_warm_kw(args), **_anchor_kw(args))
+                                        train_disturb=args.train_disturb, **_lead_kw(args), **_residual_kw(args), **_warm_kw(args), **_anchor_kw(args), **_noise_kw(args))
             except ValueError as e:
                 if args.train_disturb is None:
                     raise
@@ -1075,7 +1116,7 @@ def main(argv=None, conf=None):
             _resolve_anchor(args, conf)
             try:
                 vt = trainer.VecTrainer(conf, rng=args.rng, auto_reset=False, shared_engine=args.engine, train_disturb=args.train_disturb,
-                                        **_lead_kw(args), **_residual_kw(args), **_warm_kw(args), **_anchor_kw(args))
+                                        **_lead_kw(args), **_residual_kw(args), **_warm_kw(args), **_anchor_kw(args), **_noise_kw(args))
             except ValueError as e:
                 if args.train_disturb is None:
                     raise
@@ -1112,6 +1153,7 @@ def main(argv=None, conf=None):
         _record_residual(conf, args)
         _record_warm(conf, args)
         _record_anchor(conf, args, vt)
+        _record_noise(conf, args)
         if args.keep_best is not None:
             _KeepResults(vt, args).write(base, conf, n_save)
         artifacts.config_writer(os.path.join(base, "conf.json"), conf)
@@ -1240,7 +1282,7 @@ def train_seed_batch(args, conf, base, experiments=None):
     try:
         vt = trainer.VecTrainer(conf, rng="device", auto_reset="platoon", shared_engine=args.engine,
                                 fused_update=conf.fed_method == conf.nofrl, seeds=seeds, hparams=hps,
-                                train_disturb=getattr(args, "train_disturb", None), **_lead_kw(args), **_residual_kw(args), **_warm_kw(args), **_anchor_kw(args))
+                                train_disturb=getattr(args, "train_disturb", None), **_lead_kw(args), **_residual_kw(args), **_warm_kw(args), **_anchor_kw(args), **_noise_kw(args))
     except ValueError as e:
         raise SystemExit(f"{flag}: {e}")
     vt.reset_episode()
@@ -1339,6 +1381,7 @@ def train_seed_batch(args, conf, base, experiments=None):
         _record_residual(ce, args)
         _record_warm(ce, args, e)
         _record_anchor(ce, args, vt, e)
+        _record_noise(ce, args)
         if suite is not None:
             _write_suite(d, ce, _slice(suite, e), range(1, P + 1), args)
             if baselines is not None:

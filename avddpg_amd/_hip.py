@@ -155,6 +155,9 @@ _PROTOS = {
     "avd_learn_set_split_f16x3": [_LP, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _P, _P, _P, C.c_size_t, _P],
     "avd_learn_set_split_anchor_f16x3": [_LP, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _P, _P, _P, C.c_size_t, _P, _i, _i, _f, _f,
                                          _f, _P, _P],
+    "avd_learn_set_split_smooth_f16x3": [_LP, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _P, _P, _P, C.c_size_t, _P, _i, _i, _f, _f,
+                                         _f, _P, _f, _f, _u64, _u64, _P, _i, _P],
+    "avd_target_smooth_f32": [_i, _i, _i, _P, _f, _f, _f, _f, _u64, _u64, _P, _P],
     "avd_actor_forward_shared_workspace": [_LP, _i, _i, C.POINTER(C.c_size_t)],
     "avd_actor_forward_shared_bf16": [_LP, _i, _i, _P, _P, _P, _f, _P, _P, C.c_size_t, _P],
     "avd_eval_rollout_f32": [_LP, _P, _i, _i, _i, _i, _P, _P, _i, _P, _P, _P, _P, _i, _P, _f, _f, _f, _f, _P, _i, _P, _P, _P, _P,

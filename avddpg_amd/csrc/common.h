@@ -123,6 +123,7 @@ enum PhiloxStream : uint32_t {
     STREAM_TRAIN_LINK = 9,  // training under disturbances: V2V loss, word x
     STREAM_SEARCH = 10,     // gain search: a candidate row's four normals, (counter, index) = (generation, candidate * R + row)
     STREAM_CLONE = 11,      // warm start: a fit row's state words, (counter, index) = (fit step, vehicle index * 64 + row)
+    STREAM_SMOOTH = 12,     // target policy smoothing: four rows' normals, (counter, index) = (learner call, solo agent index * 16 + q)
 };
 
 }  // namespace avd

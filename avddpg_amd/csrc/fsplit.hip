@@ -33,6 +33,7 @@
 
 #include "fset_common.h"
 #include "anchor.h"
+#include "smooth.h"
 
 namespace avd {
 namespace fsplit {
@@ -1749,7 +1750,8 @@ static void print_head_stamps(hipStream_t st) {
 template <int S, class... H>
 static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, const float* theta, const float* stats, const float* theta_t,
                const float* stats_t, const float* s, const float* a, const float* r, const float* s2, const float* aw, float gamma,
-               float high, float* grads, float* losses, unsigned char* ws, const Plan& pl, hipStream_t st, const AnchorArgs* an, H... hp) {
+               float high, float* grads, float* losses, unsigned char* ws, const Plan& pl, hipStream_t st, const AnchorArgs* an,
+               const SmoothArgs* smo, H... hp) {
     PrepArgs pa;
     pa.L = L, pa.S = S, pa.theta = theta, pa.stats = stats, pa.theta_t = theta_t, pa.stats_t = stats_t;
     pa.wap = (unsigned*)(ws + pl.wap), pa.bad = (int*)(ws + pl.bad), pa.smax = (unsigned*)(ws + pl.smax);
@@ -1822,6 +1824,11 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
         hipLaunchKernelGGL(prep_kernel, dim3(H2, 4, n_sets), dim3(320), 0, st, pa);
         // 1-2: targets
         head(head_kernel<S, ActorS, OUT_TANH>, 2, xfs2, nullptr, nullptr, nullptr, a2, nullptr);
+        if (smo) {  // target policy smoothing: a2 in place, between its writer and its only reader (csrc/smooth.hip)
+            SmoothArgs q = *smo;
+            q.n_agents = n_agents, q.a2 = a2;
+            launch_target_smooth(q, st);
+        }
         if constexpr (sizeof...(H) > 0)  // a sweep: each set's gamma (avd_learn_set_split_hp_f16x3)
             head(head_kernel<S, CriticS, OUT_TD, true, H...>, 3, xfs2, a2, r, nullptr, y, nullptr, hp...);
         else
@@ -1912,7 +1919,7 @@ template <class... H>
 static int split_entry(int phases, const char* who, const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
                        const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r, const float* s2,
                        const float* agent_weight, float gamma, float high, float* grads, float* losses, void* workspace,
-                       size_t workspace_bytes, void* stream, const AnchorArgs* an, H... hp) {
+                       size_t workspace_bytes, void* stream, const AnchorArgs* an, const SmoothArgs* smo, H... hp) {
     int rc = fsplit::check_shape(lay, n_agents, n_sets, who);
     if (rc) return rc;
     const bool cr = phases & fsplit::PH_CRITIC;
@@ -1923,9 +1930,9 @@ static int split_entry(int phases, const char* who, const avd_mlp_layout* lay, i
     //  gradient producer keeps them zero)
     if (lay->S == 4)
         return fsplit::run<4>(phases, *lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2, agent_weight, gamma, high, grads,
-                              losses, (unsigned char*)workspace, pl, (hipStream_t)stream, an, hp...);
+                              losses, (unsigned char*)workspace, pl, (hipStream_t)stream, an, smo, hp...);
     return fsplit::run<3>(phases, *lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2, agent_weight, gamma, high, grads, losses,
-                          (unsigned char*)workspace, pl, (hipStream_t)stream, an, hp...);
+                          (unsigned char*)workspace, pl, (hipStream_t)stream, an, smo, hp...);
 }
 
 extern "C" int avd_learn_set_split_f16x3(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
@@ -1933,10 +1940,25 @@ extern "C" int avd_learn_set_split_f16x3(const avd_mlp_layout* lay, int n_agents
                                           const float* s2, const float* agent_weight, float gamma, float high, float* grads,
                                           float* losses, void* workspace, size_t workspace_bytes, void* stream) {
     return split_entry(fsplit::PH_BOTH, "avd_learn_set_split_f16x3", lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2,
-                       agent_weight, gamma, high, grads, losses, workspace, workspace_bytes, stream, nullptr);
+                       agent_weight, gamma, high, grads, losses, workspace, workspace_bytes, stream, nullptr, nullptr);
 }
 
-// the whole call with the anchored seed (anchor_seed_kernel) and the per-set anchor loss: everything refused here is refused before a HIP call
+// the anchor's own arguments, checked (everything refused here is refused before a HIP call) and gathered
+static int anchor_args(const char* who, int n_sets, const float* gains, int M, int model_a, float lo, float hi, float weight, float* anchor_loss,
+                       AnchorArgs& an) {
+    AVD_REQUIRE(gains && anchor_loss, "%s: null gains / anchor_loss", who);
+    AVD_REQUIRE(M >= 1 && n_sets % M == 0, "%s: n_sets=%d M=%d (n_sets must be a multiple of M >= 1)", who, n_sets, M);
+    unsigned wbits;  // (bit tests: this file is built with -fno-honor-nans) sign clear or -0, exponent not all ones
+    memcpy(&wbits, &weight, sizeof wbits);
+    AVD_REQUIRE((wbits & 0x7f800000u) != 0x7f800000u && (!(wbits >> 31) || wbits == 0x80000000u), "%s: weight=%g (must be finite and >= 0)",
+                who, (double)weight);
+    AVD_REQUIRE(lo <= hi, "%s: lo=%g > hi=%g", who, (double)lo, (double)hi);
+    an.gains = gains, an.M = M, an.model_a = model_a, an.lo = lo, an.hi = hi, an.weight = weight;
+    an.anchor_loss = anchor_loss;
+    return AVD_OK;
+}
+
+// the whole call with the anchored seed (anchor_seed_kernel) and the per-set anchor loss
 extern "C" int avd_learn_set_split_anchor_f16x3(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
                                                 const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
                                                 const float* s2, const float* agent_weight, float gamma, float high, float* grads,
@@ -1945,18 +1967,38 @@ extern "C" int avd_learn_set_split_anchor_f16x3(const avd_mlp_layout* lay, int n
     const char* who = "avd_learn_set_split_anchor_f16x3";
     int rc = fsplit::check_shape(lay, n_agents, n_sets, who);
     if (rc) return rc;
-    AVD_REQUIRE(gains && anchor_loss, "%s: null gains / anchor_loss", who);
-    AVD_REQUIRE(M >= 1 && n_sets % M == 0, "%s: n_sets=%d M=%d (n_sets must be a multiple of M >= 1)", who, n_sets, M);
-    unsigned wbits;  // (bit tests: this file is built with -fno-honor-nans) sign clear or -0, exponent not all ones
-    memcpy(&wbits, &weight, sizeof wbits);
-    AVD_REQUIRE((wbits & 0x7f800000u) != 0x7f800000u && (!(wbits >> 31) || wbits == 0x80000000u), "%s: weight=%g (must be finite and >= 0)",
-                who, (double)weight);
-    AVD_REQUIRE(lo <= hi, "%s: lo=%g > hi=%g", who, (double)lo, (double)hi);
     AnchorArgs an{};
-    an.gains = gains, an.M = M, an.model_a = model_a, an.lo = lo, an.hi = hi, an.weight = weight;
-    an.anchor_loss = anchor_loss;
+    rc = anchor_args(who, n_sets, gains, M, model_a, lo, hi, weight, anchor_loss, an);
+    if (rc) return rc;
     return split_entry(fsplit::PH_BOTH, who, lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2, agent_weight, gamma, high,
-                       grads, losses, workspace, workspace_bytes, stream, &an);
+                       grads, losses, workspace, workspace_bytes, stream, &an, nullptr);
+}
+
+// the whole call with target policy smoothing (csrc/smooth.hip) between the target actor's head and the target critic's; gains == null:
+// the un-anchored seed. sigma == 0: no launch, the call IS the un-smoothed one. Everything refused here is refused before a HIP call.
+extern "C" int avd_learn_set_split_smooth_f16x3(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
+                                                const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
+                                                const float* s2, const float* agent_weight, float gamma, float high, float* grads,
+                                                float* losses, void* workspace, size_t workspace_bytes, const float* gains, int M,
+                                                int model_a, float lo, float hi, float weight, float* anchor_loss, float sigma,
+                                                float noise_clip, uint64_t seed, uint64_t counter, const uint64_t* d_seeds, int E,
+                                                void* stream) {
+    const char* who = "avd_learn_set_split_smooth_f16x3";
+    int rc = fsplit::check_shape(lay, n_agents, n_sets, who);
+    if (rc) return rc;
+    AnchorArgs an{};
+    if (gains) {
+        rc = anchor_args(who, n_sets, gains, M, model_a, lo, hi, weight, anchor_loss, an);
+        if (rc) return rc;
+    }
+    SmoothArgs sm{};
+    sm.M = M, sm.E = E, sm.sigma = sigma, sm.clip = noise_clip, sm.lo = lo, sm.hi = hi, sm.seed = seed, sm.counter = counter, sm.seeds = d_seeds;
+    rc = check_smooth(who, sm);  // (csrc/smooth.hip: built without -fno-honor-nans, so its NaN tests are plain comparisons)
+    if (rc) return rc;
+    AVD_REQUIRE(n_sets % ((long)E * M) == 0, "%s: n_sets=%d M=%d E=%d (n_sets must be a multiple of E x M)", who, n_sets, M, E);
+    AVD_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
+    return split_entry(fsplit::PH_BOTH, who, lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2, agent_weight, gamma, high,
+                       grads, losses, workspace, workspace_bytes, stream, gains ? &an : nullptr, sigma == 0.f ? nullptr : &sm);
 }
 
 // a hyperparameter sweep: the whole call with each weight set's gamma from d_hp (set j: row (j / set_block) % n_groups) in the TD epilogue
@@ -1967,7 +2009,8 @@ extern "C" int avd_learn_set_split_hp_f16x3(const avd_mlp_layout* lay, int n_age
                                             void* stream) {
     AVD_REQUIRE_HP("avd_learn_set_split_hp_f16x3", d_hp, n_groups, set_block, n_sets);
     return split_entry(fsplit::PH_BOTH, "avd_learn_set_split_hp_f16x3", lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2,
-                       agent_weight, 0.f, high, grads, losses, workspace, workspace_bytes, stream, nullptr, HpRef{d_hp, n_groups, set_block});
+                       agent_weight, 0.f, high, grads, losses, workspace, workspace_bytes, stream, nullptr, nullptr,
+                       HpRef{d_hp, n_groups, set_block});
 }
 
 // deprecated alias (r03's name: the operand pairs were bf16 then; every pair has been fp16 since r04)
@@ -1984,11 +2027,11 @@ extern "C" int avd_learn_set_split_critic(const avd_mlp_layout* lay, int n_agent
                                           const float* s2, const float* agent_weight, float gamma, float high, float* grads,
                                           float* losses, void* workspace, size_t workspace_bytes, void* stream) {
     return split_entry(fsplit::PH_CRITIC, "avd_learn_set_split_critic", lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2,
-                       agent_weight, gamma, high, grads, losses, workspace, workspace_bytes, stream, nullptr);
+                       agent_weight, gamma, high, grads, losses, workspace, workspace_bytes, stream, nullptr, nullptr);
 }
 
 extern "C" int avd_learn_set_split_actor(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
                                          const float* s, float high, float* grads, void* workspace, size_t workspace_bytes, void* stream) {
     return split_entry(fsplit::PH_ACTOR, "avd_learn_set_split_actor", lay, n_agents, n_sets, theta, stats, nullptr, nullptr, s, nullptr, nullptr,
-                       nullptr, nullptr, 0.f, high, grads, nullptr, workspace, workspace_bytes, stream, nullptr);
+                       nullptr, nullptr, 0.f, high, grads, nullptr, workspace, workspace_bytes, stream, nullptr, nullptr);
 }

@@ -16,6 +16,7 @@ Weight-set regimes (the reference always holds P x M separate agents):
                  gradients through identical Adam states :415-425), so a single copy is exact.
 """
 import logging
+import math
 
 import numpy as np
 import torch
@@ -236,6 +237,101 @@ def check_actor_hold(actor_hold, hparams=None):
     return int(actor_hold)
 
 
+class TargetNoise:
+    """Target policy smoothing (TD3's): the critic's targets evaluate the target critic at
+    clip(mu'(s') + clip(sigma n, -clip, clip), action_low, action_high), n ~ N(0, 1) per sampled row, instead of at mu'(s') alone.
+    ``clip`` defaults to 2.5 sigma, TD3's ratio (0.5 at sigma 0.2); math.inf: no noise clip. Frozen: the fields cannot be reassigned."""
+    __slots__ = ("sigma", "clip")
+
+    def __init__(self, sigma=0.2, clip=None):
+        object.__setattr__(self, "sigma", sigma)
+        if clip is None:  # (sigma 0: any positive clip does, the launch is skipped; an invalid sigma is check_target_noise's to report)
+            ok = isinstance(sigma, (int, float, np.integer, np.floating)) and not isinstance(sigma, bool) and math.isfinite(sigma) and sigma > 0
+            clip = 2.5 * float(sigma) if ok else 1.0
+        object.__setattr__(self, "clip", clip)
+
+    def __setattr__(self, name, value):
+        raise AttributeError(f"TargetNoise is frozen: cannot set {name}")
+
+    def __delattr__(self, name):
+        raise AttributeError(f"TargetNoise is frozen: cannot delete {name}")
+
+    def __eq__(self, other):
+        return isinstance(other, TargetNoise) and (self.sigma, self.clip) == (other.sigma, other.clip)
+
+    def __hash__(self):
+        return hash((self.sigma, self.clip))
+
+    def __repr__(self):
+        return f"TargetNoise(sigma={self.sigma!r}, clip={self.clip!r})"
+
+    def record(self):
+        """conf.json's target_noise, a list of pairs like Anchor.record."""
+        return [["sigma", float(self.sigma)], ["clip", float(self.clip)]]
+
+    @classmethod
+    def parse(cls, text):
+        """``sigma=0.2[,clip=0.5]`` -> TargetNoise. An unknown key, a key given twice, a value that is no number, an empty text or a
+        text without sigma is a ValueError; the values are checked by check_target_noise."""
+        kw = {}
+        parts = [q.strip() for q in str(text).split(",") if q.strip()]
+        for part in parts:
+            key, eq, val = part.partition("=")
+            key, val = key.strip(), val.strip()
+            if not eq or key not in cls.__slots__:
+                raise ValueError(f"target noise: unknown key {key!r} (sigma=..[,clip=..], as key=value)")
+            if key in kw:
+                raise ValueError(f"target noise: {key} given twice")
+            try:
+                kw[key] = float(val)
+            except ValueError:
+                raise ValueError(f"target noise: {key}={val!r} is not a number") from None
+        if "sigma" not in kw:
+            raise ValueError(f"target noise {str(text)!r}: no sigma given (sigma=..[,clip=..])")
+        return cls(**kw)
+
+
+def check_target_noise(target_noise, conf=None, shared_engine="fused3", rng="device", world_size=1, hparams=None, overlap_allreduce=None,
+                       shared_sets=None):
+    """Why a run cannot smooth its target policy with this noise (VecTrainer(target_noise=...)), raised as a ValueError -- or the checked
+    TargetNoise. Called before anything is allocated or launched. The smoothing launch sits in the split set learner's chain
+    (avd_learn_set_split_smooth_f16x3): shared_engine='fused3', so shared-set interfrl, on one rank, in the single call (no overlapped
+    exchange), outside any sweep, with the device's generator. Without ``conf`` the values alone are checked."""
+    tn = target_noise
+    if not isinstance(tn, TargetNoise):
+        raise ValueError(f"{tn!r} is not a trainer.TargetNoise")
+    number = lambda x: isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
+    if not number(tn.sigma) or not math.isfinite(tn.sigma) or not tn.sigma >= 0:
+        raise ValueError(f"target noise: sigma={tn.sigma!r} must be a finite number >= 0")
+    if float(tn.sigma) > float(np.finfo(np.float32).max):
+        raise ValueError(f"target noise: sigma={tn.sigma!r} does not fit float32")
+    if not number(tn.clip) or not tn.clip > 0:  # (a NaN fails the comparison; math.inf: no noise clip)
+        raise ValueError(f"target noise: clip={tn.clip!r} must be a number > 0 (inf: no clip)")
+    if math.isfinite(tn.clip) and float(np.float32(tn.clip)) == 0.0:
+        raise ValueError(f"target noise: clip={tn.clip!r} rounds to 0 in float32")
+    if shared_engine != "fused3":
+        raise ValueError(f"target noise needs shared_engine='fused3' (the split set learner holds the smoothing launch; the per-agent "
+                         f"engines and the bf16 set learners have none), got shared_engine={shared_engine!r}")
+    if rng != "device":
+        raise ValueError(f"target noise needs rng='device' (the noise is drawn by the device's counter-based generator), got rng={rng!r}")
+    if hparams is not None:
+        raise ValueError("target noise does not combine with a hyperparameter sweep or PBT (hparams=...): the table-driven learn call has "
+                         "no smoothed form")
+    if overlap_allreduce:
+        raise ValueError("target noise does not combine with overlap_allreduce: the two-phase learn call has no smoothed form")
+    if int(world_size) > 1:
+        raise ValueError("target noise runs on one rank: no process group of more than one rank")
+    if conf is not None:
+        if conf.framework == conf.cntrl:
+            raise ValueError("target noise needs the decentralized framework (the split set learner's)")
+        can_share = (is_fed_enabled(conf) and conf.fed_method == conf.interfrl and is_gradient_updates_enabled(conf)
+                     and conf.fed_update_delay_steps == 1 and conf.fed_update_count == 1 and conf.fed_cutoff_ratio >= 1.0)
+        if not can_share or (shared_sets is not None and not shared_sets):
+            raise ValueError("target noise needs shared weight sets: interfrl + gradients with every step federated (the fused3 engine's "
+                             "regime)")
+    return tn
+
+
 def check_keep_best(world_size):
     """Why a run cannot keep the best actors seen (VecTrainer.enable_keep_best), raised as a ValueError -- or None. Called before
     anything is allocated or launched."""
@@ -262,7 +358,7 @@ class VecTrainer:
     def __init__(self, conf, device=None, rng="device", group=None, shared_sets=None, seed=None, auto_reset=False,
                  pipeline_chunks=1, fused_update=False, shared_engine=None, init_seed=None, fused_step=None,
                  replay_ring=None, overlap_allreduce=None, seeds=None, hparams=None, train_disturb=None, train_leader=None,
-                 residual=None, warm_start=None, actor_hold=0, anchor=None):
+                 residual=None, warm_start=None, actor_hold=0, anchor=None, target_noise=None):
         """group: torch.distributed process group whose ranks each hold ``conf.num_platoons`` platoons
         (interfrl gradients are all-reduced over it). auto_reset: end episodes on the device (no host
         sync per step); needs rng='device'. True: the reference's rule -- any terminal platoon (or the step limit) ends
@@ -315,7 +411,13 @@ class VecTrainer:
         anchor_losses() (the last call's mean (mu - u*)^2 per weight set, on the device) stays a diagnostic. With a seed batch every
         experiment gets the same table (set e * M + m uses row m); with a residual policy the law is the target of the correction.
         check_anchor says what it needs (shared_engine='fused3', one rank, no sweep, no overlapped exchange). None: nothing is allocated,
-        the un-anchored entry point runs."""
+        the un-anchored entry point runs.
+        target_noise: a TargetNoise -- target policy smoothing (TD3's): every learner call runs avd_learn_set_split_smooth_f16x3, whose
+        critic targets evaluate the target critic at clip(mu'(s') + clip(sigma n, -clip, clip), action_low, action_high). The noise is
+        keyed by the run's seed (under seeds= by each experiment's: experiment e draws what its solo run draws) and the 0-based
+        learner-call count. With anchor= the gains, weight_at(call) and the loss buffer travel in the same call. check_target_noise says
+        what it needs (shared_engine='fused3', rng='device', one rank, no sweep, no overlapped exchange). None: nothing is allocated,
+        today's entry points run."""
         conf.refresh()
         self.levels = self.manoeuvres = self.lead = None
         self.residual = None
@@ -341,6 +443,13 @@ class VecTrainer:
                 import torch.distributed as _td
                 ranks = _td.get_world_size(group)
             self.anchor = check_anchor(conf, anchor, shared_engine, ranks, hparams, overlap_allreduce, shared_sets)
+        self.target_noise = None
+        if target_noise is not None:
+            ranks = 1
+            if group is not None:
+                import torch.distributed as _td
+                ranks = _td.get_world_size(group)
+            self.target_noise = check_target_noise(target_noise, conf, shared_engine, rng, ranks, hparams, overlap_allreduce, shared_sets)
         self.learner_calls = 0  # steps that passed the replay gate (what actor_hold counts)
         if train_disturb is not None:
             self.levels = check_train_disturb(conf, train_disturb, rng, group, fused_step, hparams)
@@ -755,13 +864,19 @@ class VecTrainer:
                 return
             if self.anchor is not None:  # (fused3, checked) the weight of this learner call: learner_calls counts it already
                 self.anchor_weight = self.anchor.weight_at(self.learner_calls - 1)
+            if self.target_noise is not None:  # (fused3, checked) the smoothed call; an anchor's arguments travel in it
+                an = None if self.anchor is None else (self.anchor_gains, self.anchor_weight, self.anchor_loss)
+                self.agents.learn_set_split_smooth(s, a, r, s2, P * M, self.target_noise, self.learner_calls - 1, anchor=an,
+                                                   grads=self.set_grads, losses=self.set_losses, agent_weight=aw, M=self.M, seed=self.seed,
+                                                   d_seeds=None if self.seeds is None else self.env.d_seeds)
+            elif self.anchor is not None:
                 self.agents.learn_set_split_anchor(s, a, r, s2, P * M, self.anchor_gains, self.anchor_weight, self.anchor_loss,
                                                    grads=self.set_grads, losses=self.set_losses, agent_weight=aw)
-                if self.learner_calls == 1:  # the first learner call's, kept on the device (conf.json's anchor_loss_first)
-                    self.anchor_loss_first = self.anchor_loss.clone()
             else:
                 self.agents.learn_set_fused(s, a, r, s2, P * M, grads=self.set_grads, losses=self.set_losses, agent_weight=aw,
                                             split=self.shared_engine == "fused3")
+            if self.anchor is not None and self.learner_calls == 1:  # the first learner call's, kept on the device (anchor_loss_first)
+                self.anchor_loss_first = self.anchor_loss.clone()
         else:
             if aw_dev is not None:
                 rw = aw_dev.view(P, M).transpose(0, 1).reshape(M, P, 1).expand(M, P, B).reshape(M, P * B).contiguous()

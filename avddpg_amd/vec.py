@@ -754,13 +754,7 @@ class AgentGroup:
         ``weight``, and for weight 0 too. The critic block and ``losses`` are learn_set_split's bit for bit."""
         self._no_hp("learn_set_split_anchor")
         self._check_agent_major(s, a, r, s2, n_agents, agent_weight)
-        if (gains.dim() != 2 or gains.shape[1] != 4 or gains.dtype != torch.float32 or not gains.is_contiguous() or gains.shape[0] < 1
-                or self.n_sets % gains.shape[0]):
-            raise _hip.AvdError(f"anchor: gains must be contiguous float32 [M, 4] with n_sets={self.n_sets} a multiple of M, got "
-                                f"{tuple(gains.shape)} {gains.dtype}")
-        if anchor_loss.numel() != self.n_sets or anchor_loss.dtype != torch.float32 or not anchor_loss.is_contiguous():
-            raise _hip.AvdError(f"anchor: anchor_loss must be contiguous float32 [{self.n_sets}], got {tuple(anchor_loss.shape)} "
-                                f"{anchor_loss.dtype}")
+        self._check_anchor_buffers(gains, anchor_loss)
         if grads is None:
             grads = torch.empty(self.n_sets, self.lay.theta_size, dtype=torch.float32, device=self.device)
         ws = self._workspace("_fsplit_ws", "avd_learn_set_split_workspace", n_agents)
@@ -769,6 +763,71 @@ class AgentGroup:
              ptr(self.stats_t), ptr(s), ptr(a), ptr(r), ptr(s2), ptr(agent_weight), c.gamma, self.high, ptr(grads), ptr(losses), ptr(ws),
              ws.numel(), ptr(gains), int(gains.shape[0]), int(c.model == c.modelA), float(c.action_low), float(c.action_high), float(weight),
              ptr(anchor_loss), stream_handle())
+        return grads
+
+    def _check_anchor_buffers(self, gains, anchor_loss):
+        """The anchored calls take raw pointers to the gain table [M, 4] and the per-set anchor loss [n_sets]."""
+        if (gains.dim() != 2 or gains.shape[1] != 4 or gains.dtype != torch.float32 or not gains.is_contiguous() or gains.shape[0] < 1
+                or self.n_sets % gains.shape[0]):
+            raise _hip.AvdError(f"anchor: gains must be contiguous float32 [M, 4] with n_sets={self.n_sets} a multiple of M, got "
+                                f"{tuple(gains.shape)} {gains.dtype}")
+        if anchor_loss.numel() != self.n_sets or anchor_loss.dtype != torch.float32 or not anchor_loss.is_contiguous():
+            raise _hip.AvdError(f"anchor: anchor_loss must be contiguous float32 [{self.n_sets}], got {tuple(anchor_loss.shape)} "
+                                f"{anchor_loss.dtype}")
+
+    def _smooth_key(self, noise, seed, d_seeds, what):
+        """(sigma, clip, seed, d_seeds pointer, E) of a smoothing call: ``noise`` anything with .sigma and .clip; ``d_seeds`` the int64
+        device tensor of vec.seed_table (an experiment batch) or None."""
+        if d_seeds is not None and (d_seeds.dtype != torch.int64 or d_seeds.dim() != 1 or not d_seeds.is_contiguous() or not d_seeds.is_cuda):
+            raise _hip.AvdError(f"{what}: d_seeds must be vec.seed_table's contiguous int64 device tensor, got {tuple(d_seeds.shape)} "
+                                f"{d_seeds.dtype}")
+        E = 1 if d_seeds is None else int(d_seeds.numel())
+        key = int(self.config.random_seed if seed is None else seed) if d_seeds is None else 0
+        return float(noise.sigma), float(noise.clip), key, ptr(d_seeds), E
+
+    def target_smooth(self, a2, noise, counter, M=None, seed=None, d_seeds=None):
+        """Target policy smoothing alone (avd_target_smooth_f32), in place on ``a2`` [n_agents, 64] float32 (agent-major, agent v of weight
+        set v % (E * M)): a2 <- clip(a2 + clip(sigma n, -clip, clip), action_low, action_high) with the normals keyed by (seed or
+        d_seeds[e], counter, the agent's index in its experiment's solo run). ``noise``: a trainer.TargetNoise (anything with .sigma and
+        .clip); M: vehicles per platoon (default n_sets // E). What learn_set_split_smooth applies to its target actions. Returns a2."""
+        if a2.dim() != 2 or a2.shape[1] != 64 or a2.dtype != torch.float32 or not a2.is_contiguous() or not a2.is_cuda:
+            raise _hip.AvdError(f"target_smooth: a2 must be a contiguous float32 [n_agents, 64] device tensor, got {tuple(a2.shape)} {a2.dtype}")
+        sigma, clip, key, seeds, E = self._smooth_key(noise, seed, d_seeds, "target_smooth")
+        c = self.config
+        call("avd_target_smooth_f32", int(a2.shape[0]), int(self.n_sets // E if M is None else M), E, ptr(a2), sigma, clip,
+             float(c.action_low), float(c.action_high), key, int(counter), seeds, stream_handle())
+        return a2
+
+    def learn_set_split_smooth(self, s, a, r, s2, n_agents, noise, counter, anchor=None, grads=None, losses=None, agent_weight=None, M=None,
+                               seed=None, d_seeds=None):
+        """learn_set_split with target policy smoothing (avd_learn_set_split_smooth_f16x3): the critic's targets are
+        r + gamma Q'(s2, clip(mu'(s2) + clip(sigma n, -clip, clip), action_low, action_high)), the noise target_smooth's for this
+        ``counter`` (the caller's learner-call count), ``seed`` (default: the configuration's) or ``d_seeds`` (vec.seed_table's device
+        tensor: E experiments, set j of experiment (j // M) % E) and M (vehicles per platoon, default n_sets // E). ``noise``: a
+        trainer.TargetNoise; sigma 0 is the un-smoothed call bit for bit. ``anchor``: None, or (gains [M, 4], weight, anchor_loss [n_sets])
+        as learn_set_split_anchor takes them -- the anchored seed then runs in the same call. The actor block of the gradients and
+        losses[:, 1] do not depend on the noise."""
+        self._no_hp("learn_set_split_smooth")
+        self._check_agent_major(s, a, r, s2, n_agents, agent_weight)
+        sigma, clip, key, seeds, E = self._smooth_key(noise, seed, d_seeds, "learn_set_split_smooth")
+        gains = weight = anchor_loss = None
+        if anchor is not None:
+            gains, weight, anchor_loss = anchor
+            self._check_anchor_buffers(gains, anchor_loss)
+            if M is None:
+                M = int(gains.shape[0])
+            elif int(M) != int(gains.shape[0]):
+                raise _hip.AvdError(f"learn_set_split_smooth: M={M} but the anchor's table has {gains.shape[0]} rows (one M serves both)")
+        if M is None:
+            M = self.n_sets // E
+        if grads is None:
+            grads = torch.empty(self.n_sets, self.lay.theta_size, dtype=torch.float32, device=self.device)
+        ws = self._workspace("_fsplit_ws", "avd_learn_set_split_workspace", n_agents)
+        c = self.config
+        call("avd_learn_set_split_smooth_f16x3", self._layp, n_agents, self.n_sets, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
+             ptr(self.stats_t), ptr(s), ptr(a), ptr(r), ptr(s2), ptr(agent_weight), c.gamma, self.high, ptr(grads), ptr(losses), ptr(ws),
+             ws.numel(), ptr(gains), int(M), int(c.model == c.modelA), float(c.action_low), float(c.action_high),
+             0.0 if weight is None else float(weight), ptr(anchor_loss), sigma, clip, key, int(counter), seeds, E, stream_handle())
         return grads
 
     def _check_agent_major(self, s, a, r, s2, n_agents, agent_weight):

@@ -580,6 +580,43 @@ int avd_learn_set_split_anchor_f16x3(const avd_mlp_layout* lay, int n_agents, in
                                      void* workspace, size_t workspace_bytes, const float* gains, int M, int model_a, float lo, float hi,
                                      float weight, float* anchor_loss, void* stream);
 
+/* Target policy smoothing (TD3's; tr --target_noise), the kernel alone on a caller's buffer: a2 [n_agents][64] float32, 16-byte
+ * aligned, the target actions mu'(s2) in the split set learner's agent-major layout, updated IN PLACE:
+ *   a2'[v][4q + k] = min(max(a2[v][4q + k] + min(max(sigma * n_k, -noise_clip), noise_clip), lo), hi)      q = 0 .. 15, k = 0 .. 3
+ *   w = philox(d_seeds ? d_seeds[e] : seed, counter, vs * 16 + q, stream 12);  (n_0, n_1) = box_muller(w.x, w.y) (cos, sin branch),
+ *   (n_2, n_3) = box_muller(w.z, w.w)
+ * float32 without contraction. Agent v belongs to weight set v % (E * M): vehicle m = v % M of experiment e = (v / M) % E, platoon
+ * p = v / (E * M); vs = p * M + m is its index in the experiment's solo run, so experiment e of a seed batch draws what its solo
+ * run draws (E = 1 and d_seeds = NULL without a seed table). noise_clip = +inf: no noise clip. A NaN in a2 stays a NaN (the outer
+ * clip is written as two comparisons). One thread per four rows (one 16-byte load and store), no LDS, no atomics: two calls with the
+ * same arguments give the same bits. It exists so that the draws can be checked without a learner around them.
+ * Refused on the host before any HIP call (AVD_E_INVALID): null or misaligned a2, n_agents < 1 or > 2^24, M or E < 1, n_agents not a
+ * multiple of E * M, E > 1 without d_seeds, sigma negative or non-finite, noise_clip NaN or <= 0, lo > hi. */
+int avd_target_smooth_f32(int n_agents, int M, int E, float* a2, float sigma, float noise_clip, float lo, float hi, uint64_t seed,
+                          uint64_t counter, const uint64_t* d_seeds, void* stream);
+
+/* avd_learn_set_split_anchor_f16x3 with target policy smoothing: the critic is regressed onto
+ *   y = r + gamma * Q'(s2, clip(mu'(s2) + clip(sigma n, -noise_clip, noise_clip), lo, hi))
+ * The chain is the same with ONE launch more: avd_target_smooth_f32's kernel on the workspace's target actions, between the target
+ * actor's head (their writer) and the target critic's (their only reader), with n_agents, M, E, lo, hi, seed, counter and d_seeds as
+ * there (counter: the caller's learner-call count). None of the chain's own kernels changes. Only y changes, and through it the critic
+ * block of `grads` and losses[j][0]: the actor block and losses[j][1] are the un-smoothed call's bit for bit.
+ * gains == NULL selects the un-anchored seed: anchor_loss may then be NULL, model_a and weight are unread, and the call is
+ * avd_learn_set_split_f16x3 with the smoothing launch; otherwise the anchored seed and the anchor loss run exactly as in
+ * avd_learn_set_split_anchor_f16x3. sigma == 0 skips the launch on the host: the call is then avd_learn_set_split_f16x3's
+ * (gains == NULL) or avd_learn_set_split_anchor_f16x3's, bit for bit. A non-finite input stays loud: the heads raise the chain's flag
+ * from their own accumulators before the smoothing runs, and the slab and the losses come out all NaN.
+ * Refused on the host before any HIP call: everything avd_learn_set_split_f16x3 refuses; with gains, everything
+ * avd_learn_set_split_anchor_f16x3 refuses; M or E < 1, n_sets not a multiple of E * M, E > 1 without d_seeds, sigma negative or
+ * non-finite, noise_clip NaN or <= 0, lo > hi, a workspace that is not 16-byte aligned.
+ * There is no two-phase and no per-set-gamma form of this call. */
+int avd_learn_set_split_smooth_f16x3(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
+                                     const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
+                                     const float* s2, const float* agent_weight, float gamma, float high, float* grads, float* losses,
+                                     void* workspace, size_t workspace_bytes, const float* gains, int M, int model_a, float lo, float hi,
+                                     float weight, float* anchor_loss, float sigma, float noise_clip, uint64_t seed, uint64_t counter,
+                                     const uint64_t* d_seeds, int E, void* stream);
+
 /* Deprecated alias of avd_learn_set_split_f16x3 (same arguments, same results). */
 int avd_learn_set_split_bf16x3(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
                                const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
