@@ -527,18 +527,26 @@ struct HeadArgs {
 
 // HP (OUT_TD of avd_learn_set_split_hp_f16x3): the TD epilogue's gamma is the workgroup's weight set's, row (set / block) % n_groups of
 // the sweep table; nothing else differs from the scalar instantiation.
+//
+// The kernel's body is a device function over ONE raw, 16-byte aligned LDS buffer from which it carves its arrays (r15): the
+// stand-alone kernel below declares the buffer and calls it, forward_kernel calls four of them in a row on the same buffer. A body
+// never returns early: a workgroup without tiles falls through to its end like every other (the next phase's barrier expects it).
+template <class NET, int MODE>
+constexpr int head_lds_bytes() {
+    return 2 * H2 * NET::LD * (int)sizeof(f16) + 2 * H2 * (int)sizeof(float) + (MODE == HEAD_BOTH ? 48 : 4) * (int)sizeof(unsigned);
+}
 template <int S, class NET, int MODE, bool HP = false, class... H>
-__global__ __launch_bounds__(NT) void head_kernel(const HeadArgs p, H... hp) {
+__device__ __forceinline__ void head_body(const HeadArgs& p, unsigned char* lds, const int tid, H... hp) {
     constexpr int K = NET::K, NKS = NET::NKS, NFT = NET::NFT, LD = NET::LD;  // LD/2 = 4 (mod 8) dwords: conflict-free b128
     constexpr int NTH = NT;  // 8 waves: two per SIMD at <= 256 registers
     constexpr bool BOTH = (MODE == HEAD_BOTH);
     // (T1 = sum_rows g3 relu(z2) is not accumulated here: finalize derives it from dw_kernel's partials, FinArgs::t1_from_g)
     static_assert(!BOTH || NET::critic, "HEAD_BOTH is a critic mode");
-    __shared__ __attribute__((aligned(16))) f16 wimg[2][H2 * LD];
-    __shared__ __attribute__((aligned(16))) float b2s[H2];
-    __shared__ __attribute__((aligned(16))) float c3s[H2];
-    __shared__ __attribute__((aligned(16))) unsigned waps[BOTH ? 48 : 4];
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5, q = w >> 1, rh = w & 1;
+    f16(*wimg)[H2 * LD] = (f16(*)[H2 * LD]) lds;                       // [2][H2 * LD]
+    float* b2s = (float*)(lds + 2 * H2 * LD * sizeof(f16));            // [H2]
+    float* c3s = b2s + H2;                                             // [H2]
+    unsigned* waps = (unsigned*)(c3s + H2);                            // [BOTH ? 48 : 4]
+    const int w = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5, q = w >> 1, rh = w & 1;
     const int set = blockIdx.x % p.n_sets, j0 = blockIdx.x / p.n_sets, J = gridDim.x / p.n_sets, P = p.n_agents / p.n_sets;
 #ifdef AVD_STAMP
     unsigned long long hacc[4] = {0, 0, 0, 0}, hlast = __builtin_amdgcn_s_memtime();
@@ -921,6 +929,11 @@ __global__ __launch_bounds__(NT) void head_kernel(const HeadArgs p, H... hp) {
         }
     }
 }
+template <int S, class NET, int MODE, bool HP = false, class... H>
+__global__ __launch_bounds__(NT) void head_kernel(const HeadArgs p, H... hp) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[head_lds_bytes<NET, MODE>()];
+    head_body<S, NET, MODE, HP, H...>(p, lds, threadIdx.x, hp...);
+}
 
 // ---- the actor's backward seed (r04: what is left of r03's HEAD_ACTOR launch) --------------------------------------------------
 // g3[row] = d mu[row] * high * (1 - tanh(z)^2) (workers/trainer.py:502-506 through agent/model.py:34-36), from the d q / d mu the
@@ -931,8 +944,8 @@ struct SeedArgs {
     float high;
     float *g3, *part_m, *part_s;
 };
-__global__ __launch_bounds__(NT) void actor_seed_kernel(const SeedArgs p) {
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+__device__ __forceinline__ void seed_body(const SeedArgs& p, const int tid) {
+    const int w = tid >> 6, lane = tid & 63;
     const int set = blockIdx.x % p.n_sets, j0 = blockIdx.x / p.n_sets, J = gridDim.x / p.n_sets, P = p.n_agents / p.n_sets;
     float gmax = 0.f, D = 0.f;
     for (int pi = j0 + w * J; pi < P; pi += 8 * J) {  // wave w: tiles j0 + w J, + 8 J, .. of the workgroup's set; lane = row
@@ -949,6 +962,7 @@ __global__ __launch_bounds__(NT) void actor_seed_kernel(const SeedArgs p) {
         p.part_s[((long)blockIdx.x * 8 + w) * 2] = D, p.part_s[((long)blockIdx.x * 8 + w) * 2 + 1] = 0.f;
     }
 }
+__global__ __launch_bounds__(NT) void actor_seed_kernel(const SeedArgs p) { seed_body(p, threadIdx.x); }
 
 // ---- the row factor's scale --------------------------------------------------------------------------------------------------
 // dw and dx carry |g3[row]| inside fp16 operands; g3 is 2 (q - y) / N or d mu * high * (1 - t^2): anything from 1e-12 to 1e-3. The
@@ -956,8 +970,7 @@ __global__ __launch_bounds__(NT) void actor_seed_kernel(const SeedArgs p) {
 // 2^kg with max |g3| 2^kg in [0.5, 1) (exact scaling; max() is order-independent: every workgroup gets the same bits) and
 // divides it out of its partial sums at the end. With |g3| 2^kg < 1 an operand |g3| 2^kg S1 P1 stays below the S1 P1 the heads
 // have already watched for fp16 overflow. Block-cooperative (one barrier); red: 8 floats of LDS.
-__device__ __forceinline__ float set_gscale(const float* part_m, int set, int n_sets, int J, float* red) {
-    const int tid = threadIdx.x;
+__device__ __forceinline__ float set_gscale(const float* part_m, int set, int n_sets, int J, float* red, const int tid) {
     float m = 0.f;
     for (int i = tid; i < J * 8; i += NT) m = fmaxf(m, part_m[((long)(i >> 3) * n_sets + set) * 8 + (i & 7)]);
 #pragma unroll
@@ -1008,15 +1021,17 @@ struct DwArgs {
 // (r04: was a bf16 pair, 2^-17 per row -- in a noise-dominated sum that IS the relative error of the result) and used against
 // all four column tiles: 48 VALU per 17 MFMAs. The sm tile goes through LDS (row stride 320 B: conflict-free ds_read_b64_tr_b16), fetched
 // TWO tiles ahead; the |g3|-scaled input fragments are built once per tile by 128 threads and shared through LDS.
+constexpr int DW_LDZ = 160;
+constexpr int DW_LDS_BYTES = 2 * TILE * DW_LDZ * (int)sizeof(f16) + 2 * 2 * TILE * 2 * 16 + 8 * (int)sizeof(float);
 template <int S, class NET>
-__global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
-    constexpr int KG = NET::KG, LDZ = 160;
+__device__ __forceinline__ void dw_body(const DwArgs& p, unsigned char* lds, const int tid) {
+    constexpr int KG = NET::KG, LDZ = DW_LDZ;
     constexpr int XC = NET::critic ? 2 : 1;  // column tiles of a wave's extra piece
-    __shared__ __attribute__((aligned(16))) f16 smimg[2][TILE * LDZ];  // (40 KB: reused for the extra pieces' partial sums)
-    __shared__ __attribute__((aligned(16))) f16x8 fq[2][TILE * 2];      // scaled input fragments [row][lane half] of the states
-    __shared__ __attribute__((aligned(16))) f16x8 fa[2][TILE * 2];      // ... of the action (critic)
-    __shared__ float gred[8];
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
+    f16(*smimg)[TILE * LDZ] = (f16(*)[TILE * LDZ]) lds;                                   // [2][TILE * LDZ] (40 KB: reused for the extra pieces' partial sums)
+    f16x8(*fq)[TILE * 2] = (f16x8(*)[TILE * 2])(lds + 2 * TILE * LDZ * sizeof(f16));     // [2][TILE * 2] scaled input fragments [row][lane half] of the states
+    f16x8(*fa)[TILE * 2] = fq + 2;                                                        // [2][TILE * 2] ... of the action (critic)
+    float* gred = (float*)(fa + 2);                                                       // [8]
+    const int w = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
     const int set = blockIdx.x % p.n_sets, j0 = blockIdx.x / p.n_sets, J = gridDim.x / p.n_sets, P = p.n_agents / p.n_sets;
     float gsc;  // 2^kg: set_gscale, below -- behind the requests for everything that does not depend on it
     const f16x8* wf1 = p.net.wf1h + (long)set * NGT_MAX * 64 + lane;
@@ -1186,7 +1201,7 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
     if (j0 + J < P) fetch_m(j0 + J, mb, gb);
     // (r14) the weight fragments and the first two tiles' operands are in flight while set_gscale loads, reduces and meets its
     // barrier: one round trip to memory in front of the tile loop, not two in a row
-    gsc = set_gscale(p.part_m, set, p.n_sets, J, gred);
+    gsc = set_gscale(p.part_m, set, p.n_sets, J, gred, tid);
     stage_m(0, ma, ga), stage_x(j0, 0);
     __syncthreads();
 #ifdef AVD_STAMP
@@ -1249,6 +1264,11 @@ __global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
         }
     }
 }
+template <int S, class NET>
+__global__ __launch_bounds__(NT) void dw_kernel(const DwArgs p) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[DW_LDS_BYTES];
+    dw_body<S, NET>(p, lds, threadIdx.x);
+}
 
 // ---- dx: dC = |g3| (sm . W2c^T), BN/ReLU backward of the first layer and its parameter sums -----------------------------------
 struct DxArgs {
@@ -1280,17 +1300,19 @@ struct DxArgs {
 // wait for the four waves that carry a unit, the unit is a serial chain -- LDS reads, 16 dependent MFMAs, ~150 VALU -- that no
 // other wave of the workgroup can overlap, and its 20 persistent registers came back as scratch reloads in the tile loop. They
 // stay in dxa_kernel.)
+constexpr int DX_LDZ = 136;
+constexpr int DX_LDS_BYTES = 2 * TILE * DX_LDZ * (int)sizeof(f16) + 3 * 2 * 32 * 32 * (int)sizeof(f16) + 3 * TILE * (int)sizeof(float) + 8 * (int)sizeof(float);
 template <int S, class NET>
-__global__ __launch_bounds__(NT) void dx_kernel(const DxArgs p) {
-    constexpr int KP = NET::KP, LDZ = 136;  // 272-byte rows: conflict-free b128 row reads
+__device__ __forceinline__ void dx_body(const DxArgs& p, unsigned char* lds, const int tid) {
+    constexpr int KP = NET::KP, LDZ = DX_LDZ;  // 272-byte rows: conflict-free b128 row reads
     constexpr float VSH = 1.f / 32.f;
     // sm images: two buffers (read by the dC products only, all before the barrier that ends their tile); input images and row
     // factors: three (the previous tile's row half 1 is still read after the barrier that publishes the next one: see the loop)
-    __shared__ __attribute__((aligned(16))) f16 smimg[2][TILE * LDZ];
-    __shared__ __attribute__((aligned(16))) f16 xt[3][2][32 * 32];  // per slot, per row half: [k column][row]
-    __shared__ __attribute__((aligned(16))) float g3s[3][TILE];
-    __shared__ float gred[8];
-    const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, r = lane & 31, h = lane >> 5, ft = w;
+    f16(*smimg)[TILE * LDZ] = (f16(*)[TILE * LDZ]) lds;                                       // [2][TILE * LDZ]
+    f16(*xt)[2][32 * 32] = (f16(*)[2][32 * 32])(lds + 2 * TILE * LDZ * sizeof(f16));         // [3][2][32 * 32] per slot, per row half: [k column][row]
+    float(*g3s)[TILE] = (float(*)[TILE])(xt + 3);                                             // [3][TILE]
+    float* gred = (float*)(g3s + 3);                                                          // [8]
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, r = lane & 31, h = lane >> 5, ft = w;
     const int set = blockIdx.x % p.n_sets, j0 = blockIdx.x / p.n_sets, J = gridDim.x / p.n_sets, P = p.n_agents / p.n_sets;
     const f32x16 zero16 = {};
     f16x8 wch[8], wcl[8];
@@ -1483,7 +1505,7 @@ __global__ __launch_bounds__(NT) void dx_kernel(const DxArgs p) {
         fetch(n1), fetch_x(n1);
     }
     {
-        const float gsc = set_gscale(p.part_m, set, p.n_sets, J, gred);  // 2^kg (its barrier: also the zero / ones fill above before the first stage_x)
+        const float gsc = set_gscale(p.part_m, set, p.n_sets, J, gred, tid);  // 2^kg (its barrier: also the zero / ones fill above before the first stage_x)
         gv = gsc * VSH, vs = gsc * swc * VSH;
     }
     if (j0 < P) {
@@ -1519,6 +1541,11 @@ __global__ __launch_bounds__(NT) void dx_kernel(const DxArgs p) {
         for (int k = 0; k < 16; ++k) pv[(long)acc_row(k, h) * 16] = V[k] * ivs;
     }
 }
+template <int S, class NET>
+__global__ __launch_bounds__(NT) void dx_kernel(const DxArgs p) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[DX_LDS_BYTES];
+    dx_body<S, NET>(p, lds, threadIdx.x);
+}
 
 // ---- dxa: the critic's ACTION feature tiles (48 features = tiles 8, 9) of dC and their parameter sums ----------------------
 // A quarter of dx_kernel's matrix work per tile. Every wave is on its own: wave w = (rh, ft, par) takes row half rh of feature tile
@@ -1533,15 +1560,16 @@ __global__ __launch_bounds__(NT) void dx_kernel(const DxArgs p) {
 // first-layer MFMA, a [k][row] LDS image per wave, four more MFMAs and their operand splits per unit): p1 = relu(a wa + ba) as
 // one fma + max -- the relu mask from an exact f32 pre-activation --, dWa = sum (dC mask) a, dba = sum (dC mask). The two
 // parities and the two row halves are combined once, at the end, in a fixed order.
+constexpr int DXA_LDS_BYTES = (8 * 2 * 2 * 32 + 8 * 64 * 2 + 8) * (int)sizeof(float);
 template <int S>
-__global__ __launch_bounds__(NT) void dxa_kernel(const DxArgs p) {
+__device__ __forceinline__ void dxa_body(const DxArgs& p, unsigned char* lds, const int tid) {
     typedef CriticS NET;
     constexpr int KP = NET::KP;
     constexpr float VSH = 1.f / 32.f;
-    __shared__ __attribute__((aligned(16))) float ga[8][2][2][32];  // per wave, per buffer: |g3| gv and a of its 32 rows
-    __shared__ float comb[8][64][2];
-    __shared__ float gred[8];
-    const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, r = lane & 31, h = lane >> 5;
+    float(*ga)[2][2][32] = (float(*)[2][2][32]) lds;     // [8][2][2][32] per wave, per buffer: |g3| gv and a of its 32 rows
+    float(*comb)[64][2] = (float(*)[64][2])(ga + 8);     // [8][64][2]
+    float* gred = (float*)(comb + 8);                    // [8]
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, r = lane & 31, h = lane >> 5;
     const int rh = w & 1, ftl = (w >> 1) & 1, par = w >> 2;
     const int set = blockIdx.x % p.n_sets, j0 = blockIdx.x / p.n_sets, J = gridDim.x / p.n_sets, P = p.n_agents / p.n_sets;
     const f32x16 zero16 = {};
@@ -1603,7 +1631,7 @@ __global__ __launch_bounds__(NT) void dxa_kernel(const DxArgs p) {
     if (par < ntile) DXA_FETCH(par, mA, gA, aA);
     if (par + 2 < ntile) DXA_FETCH(par + 2, mB, gB, aB);
     // (r14) the row factor's scale LAST: the resident fragments and both prefetched units are in flight under its loads and barrier
-    const float gsc = set_gscale(p.part_m, set, p.n_sets, J, gred);
+    const float gsc = set_gscale(p.part_m, set, p.n_sets, J, gred, tid);
     const float gv = gsc * VSH, vs = gsc * swc * VSH;  // the scaled domain of dx_kernel (nothing here needs it for range: one scale for both kernels)
     for (int k = par; k < ntile; k += 4) {
         DXA_PUT(0, gA, aA);
@@ -1639,11 +1667,87 @@ __global__ __launch_bounds__(NT) void dxa_kernel(const DxArgs p) {
         for (int c = 0; c < 9; ++c) pv[c] = c == 0 ? t[0] * ivs : (c == 8 ? t[1] * ivs : 0.f);
     }
 }
+template <int S>
+__global__ __launch_bounds__(NT) void dxa_kernel(const DxArgs p) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[DXA_LDS_BYTES];
+    dxa_body<S>(p, lds, threadIdx.x);
+}
+
+// ---- the fused launches (r15): the forward chain in one launch, the backward chain in one ---------------------------------------
+// Every persistent kernel above runs the same grid, and workgroup b (set b % n_sets, j0 = b / n_sets) owns the same tiles j0, j0 + J, ..
+// of its set in every one of them; the heads even share the static wave-pair map. What a kernel reads of an earlier one's output it
+// reads from ITS OWN workgroup's tiles -- with two exceptions: the row factor's scale (set_gscale: part_m of every workgroup of the
+// set) and the weight images of prep_kernel. So between OUT_TANH, OUT_TD, OUT_TANH_SAVE, HEAD_BOTH and the actor's seed, and between
+// the five backward kernels (which do not depend on one another at all), a launch boundary orders nothing that a workgroup barrier
+// does not: the bodies run back to back in one launch, and a workgroup that ends a phase early starts the next at once instead of
+// idling until the slowest workgroup of the grid has drained. No workgroup ever waits for another: nothing here can hang.
+// The seam between two phases is __syncthreads(): it frees the LDS buffer for the next phase's arrays, and it is HIP's guarantee that
+// the global stores of the workgroup's waves in front of it (a2, y, mu, dmu, tz rows; the seed reads rows of OTHER waves of the
+// workgroup) are seen by its loads behind it -- all of a workgroup's waves share one CU's L1, so no wider scope is involved; an
+// agent-scope release / acquire pair would write back the XCD's L2 and invalidate the L1 at every seam for nothing. Every load of a
+// phase, the one-unit-ahead fetch_in included, is issued behind the seam: the bodies are the stand-alone kernels' instruction for
+// instruction, their per-wave arithmetic, tile maps and partial-sum grouping with them -- same bits.
+__device__ __forceinline__ void phase_seam() {
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();
+    __builtin_amdgcn_sched_barrier(0);
+}
+// The thread index of one phase: the same number behind an optimisation barrier, so that what a phase derives from it -- lane offsets,
+// addresses -- is computed in that phase. As one value for the whole launch the compiler shared such registers between the phases and
+// kept them alive across the tile loops in between: 256 registers and spills around the loops (the phases' live ranges are disjoint).
+__device__ __forceinline__ int phase_tid() {
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    __builtin_assume(t >= 0 && t < NT);
+    return t;
+}
+struct FwdArgs {
+    HeadArgs tanh_t, td, tanh_save, both;  // target actor -> a2, target critic -> y, actor -> mu (+ masks, tanh z), critic(s, a) and critic(s, mu)
+    SeedArgs seed;                         // writes the actor's g3 into a buffer of its own (Plan::g3a): the critic's is still to be read
+};
+struct BwdArgs {
+    DwArgs dw_c;
+    DxArgs dx_c, dxa;
+    DwArgs dw_a;
+    DxArgs dx_a;
+};
+constexpr int FWD_LDS_BYTES = head_lds_bytes<CriticS, HEAD_BOTH>();
+static_assert(FWD_LDS_BYTES >= head_lds_bytes<ActorS, OUT_TANH_SAVE>() && FWD_LDS_BYTES >= head_lds_bytes<CriticS, OUT_TD>(), "the largest phase");
+constexpr int BWD_LDS_BYTES = DW_LDS_BYTES > DX_LDS_BYTES ? DW_LDS_BYTES : DX_LDS_BYTES;
+static_assert(BWD_LDS_BYTES >= DXA_LDS_BYTES, "the largest phase");
+template <int S>
+__global__ __launch_bounds__(NT) void forward_kernel(const FwdArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[FWD_LDS_BYTES];
+    head_body<S, ActorS, OUT_TANH>(a.tanh_t, lds, phase_tid());
+    phase_seam();
+    head_body<S, CriticS, OUT_TD>(a.td, lds, phase_tid());
+    phase_seam();
+    head_body<S, ActorS, OUT_TANH_SAVE>(a.tanh_save, lds, phase_tid());
+    phase_seam();
+    head_body<S, CriticS, HEAD_BOTH>(a.both, lds, phase_tid());
+    phase_seam();
+    seed_body(a.seed, phase_tid());
+}
+// (each phase carries its own set_gscale -- the critic's part_m, the actor's: both complete at the launch boundary in front -- and its
+//  own partial outputs; no data flows from one phase to the next)
+template <int S>
+__global__ __launch_bounds__(NT) void backward_kernel(const BwdArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[BWD_LDS_BYTES];
+    dw_body<S, CriticS>(a.dw_c, lds, phase_tid());
+    phase_seam();
+    dx_body<S, CriticS>(a.dx_c, lds, phase_tid());
+    phase_seam();
+    dxa_body<S>(a.dxa, lds, phase_tid());
+    phase_seam();
+    dw_body<S, ActorS>(a.dw_a, lds, phase_tid());
+    phase_seam();
+    dx_body<S, ActorS>(a.dx_a, lds, phase_tid());
+}
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 struct Plan {
     int grid, J;
-    size_t Whi[4], Wlo[4], Wchi[2], Wclo[2], wf1h[4], vec[4], wap, a2, y, mu, dmu, g3, sm, sma, tz, t1p, s2raw, xfs, xfs2, partHs[3], partM[2],
+    size_t Whi[4], Wlo[4], Wchi[2], Wclo[2], wf1h[4], vec[4], wap, a2, y, mu, dmu, g3, g3a, sm, sma, tz, t1p, s2raw, xfs, xfs2, partHs[3], partM[2],
         partV[2], partG[2], bad, smax, fflag, total;
     int n_prep1, n_pack, n_fflag;  // front_kernel: blocks of the prep1 role, of the pack role per input; front flag words
 };
@@ -1671,6 +1775,7 @@ static Plan make_plan(int n_agents, int n_sets) {
     pl.wap = take(4 * (size_t)n_sets * 48);
     const size_t rows = (size_t)n_agents * TILE;
     pl.a2 = take(4 * rows), pl.y = take(4 * rows), pl.mu = take(4 * rows), pl.dmu = take(4 * rows), pl.g3 = take(4 * rows);
+    pl.g3a = take(4 * rows);  // the actor's row factor (its seed runs in the forward launch, before the critic's backward pass has read g3)
     pl.sm = take(16 * rows);   // the critic's relu masks, one bit per element (HEAD_BOTH)
     pl.sma = take(16 * rows);  // the actor's (OUT_TANH_SAVE: written before the critic's are used)
     pl.tz = take(4 * rows);
@@ -1710,11 +1815,13 @@ static int check_shape(const avd_mlp_layout* L, int n_agents, int n_sets, const 
 //   ACTOR : actor gradients from the d mu the critic phase left in the workspace, finalize of the actor block
 // so that a multi-GPU caller can put the critic block's all-reduce on a side stream while the actor phase still runs
 // (avddpg_amd/trainer.py; workers/trainer.py:400-431 averages the two gradient lists independently).
-// Fifteen launches and no other stream operation in the single call (r09; r08 issued 21: two memsets -- three fills -- and 18 launches):
+// Fifteen launches and no other stream operation in the single call as r09 left it (seven since r15, below; r08 issued 21: two memsets --
+// three fills -- and 18 launches):
 //   front_kernel (scale | prep1 | slab and *bad zeroing | pack_x, roles by block range: ~30 us where the five operations it replaces
 //   took 54), prep_kernel, the four heads, dw / dx / dxa of the critic, actor_seed, dw / dx of the actor, then finalize in three
-//   (fset.hip launch_finalize: column items; W2 rows | feature items; t1 -- 41 us where four launches took 48). Every cross-block
-//   dependence is a launch boundary; the workspace and the slab may hold anything when a call begins (tests/test_gpu_fsplit_glue.py).
+//   (fset.hip launch_finalize: column items; W2 rows | feature items; t1 -- 41 us where four launches took 48). Until r15 every
+//   dependence was a launch boundary (r15, below: only the cross-WORKGROUP ones need one); the workspace and the slab may hold anything when
+//   a call begins (tests/test_gpu_fsplit_glue.py).
 //   Same box, 400-learn rounds alternated: 1785.5-1786.5 -> 1754.6-1757.0 us per learn (profiles/r09_glue_ab_learn_time.txt).
 //   r14: what a workgroup of the ten persistent kernels does in front of its first tile. The heads filled their LDS weight image in a
 //   rolled loop of load, wait, store -- 16 (actor) / 19 (critic) dependent round trips per thread, all workgroups of a set on the same
@@ -1725,7 +1832,28 @@ static int check_shape(const avd_mlp_layout* L, int n_agents, int n_sets, const 
 //   (r14_startup_static.txt). Heads' start-up 12.4-16.9 k -> 6.6-8.0 k cycles, 2.6-4.1 % -> 1.3-2.2 % of the kernel (r14_startup_stamps.txt);
 //   same box, 400-learn rounds alternated: 1775.7-1780.6 -> 1727.4-1731.0 us per learn (r14_startup_ab_learn_time.txt).
 //   Not done: finalize in TWO launches -- finalize_w2 is not independent of the column items (it adds sh1 * db2 read back from the
-//   slab), so the column items keep a launch of their own; the actor seed folded into HEAD_BOTH (7 us and a boundary: not tried).
+//   slab), so the column items keep a launch of their own.
+//   r15: seven launches in the plain single call. Who reads what of whom, in the chain between prep and finalize:
+//       consumer                      reads                         produced by                    scope
+//       OUT_TD                        a2 rows                       OUT_TANH                       same workgroup, same tiles (same wave)
+//       HEAD_BOTH                     mu, y rows                    OUT_TANH_SAVE, OUT_TD          same workgroup (same wave)
+//       actor seed                    dmu, tz rows                  HEAD_BOTH, OUT_TANH_SAVE       same workgroup (other waves)
+//       dw / dx / dxa (both nets)     sm, g3 rows of their tiles    heads / seed                   same workgroup
+//       dw / dx / dxa                 part_m of the whole set       every workgroup of the set     SET-WIDE  (set_gscale)
+//       finalize_*                    all partials                  every workgroup                SET-WIDE
+//       heads                         weight images, tables         prep_kernel                    GLOBAL
+//   dw<Critic>, dx<Critic>, dxa, dw<Actor>, dx<Actor> do not depend on one another. Three points need a device-wide boundary -- after
+//   prep, after the last writer of part_m, before finalize -- where the chain had eleven. The eight others are now workgroup barriers
+//   inside forward_kernel (four heads + the seed) and backward_kernel (five phases): above, "the fused launches". The seed runs before the
+//   critic's backward pass now and writes the actor's row factor into a buffer of its own (Plan::g3a; the two-phase calls use it too).
+//   What a boundary costs cannot be read from a kernel trace: the profiler's start stamp of a dispatch IS the end stamp of the one before
+//   (every gap 0.00 us, profiles/r15_launch_boundaries_parent.txt) -- drain, end-of-kernel cache work, dispatch and start-up are all
+//   inside the durations. The A/B is the measurement: same box, 400-learn rounds alternated, 1803.5-1805.0 -> 1771.0-1777.4 us per learn
+//   (-29.2 us = -1.6 %: 3.6 us per boundary removed; profiles/r15_fused_launches_ab_learn_time.txt), same bits
+//   (r15_fused_launches_bit_identity.txt, tests/test_gpu_fsplit_fused_launches.py against the two-phase calls, which keep the stand-alone
+//   launches), 236 / 224 registers, no scratch, LDS of the largest phase, every tile loop the stand-alone kernel's instructions
+//   (r15_fused_launches_static.txt). The seams are workgroup barriers, not the agent-scope release / acquire pairs first planned: no
+//   dependence crosses a workgroup, and an agent-scope pair costs more per seam (L2 write-back, L1 invalidate) than the boundary it replaces.
 enum Phase { PH_CRITIC = 1, PH_ACTOR = 2, PH_BOTH = 3 };
 #ifdef AVD_STAMP
 // Diagnostic build with -DAVD_STAMP: the heads' s_memtime stamps (head_kernel: HSTAMP; workgroup 16, per wave the cycles of 0 unit start,
@@ -1773,7 +1901,7 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
     f16x8 *xfs = (f16x8*)(ws + pl.xfs), *xfs2 = (f16x8*)(ws + pl.xfs2);
     int* bad = (int*)(ws + pl.bad);
     float *a2 = (float*)(ws + pl.a2), *y = (float*)(ws + pl.y), *mu = (float*)(ws + pl.mu), *dmu = (float*)(ws + pl.dmu);
-    float* g3 = (float*)(ws + pl.g3);
+    float *g3 = (float*)(ws + pl.g3), *g3a = (float*)(ws + pl.g3a);  // the critic's row factor, the actor's
     unsigned *sm = (unsigned*)(ws + pl.sm), *sma = (unsigned*)(ws + pl.sma);
     auto F = [&](size_t off) { return (float*)(ws + off); };
     const dim3 grid(pl.grid), block(NT);
@@ -1781,13 +1909,16 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
     h.n_agents = n_agents, h.n_sets = n_sets, h.gamma = gamma, h.high = high, h.inv_n = inv_n, h.aw = aw, h.sm = sm, h.g3 = g3, h.dmu = dmu;
     h.act2 = nullptr, h.part_s2 = nullptr, h.stamp = nullptr, h.bad = bad, h.part_m = nullptr, h.tz = F(pl.tz), h.abl = 0;
     if (const char* e = AVD_DIAG_ENV("FSPLIT_ABL")) h.abl = atoi(e);
-    auto head = [&](auto kern, int ni, const f16x8* x, const float* act, const float* rr, const float* yin, float* out, float* part_s,
-                    auto... extra) {
+    auto head_args = [&](int ni, const f16x8* x, const float* act, const float* rr, const float* yin, float* out, float* part_s) {
         h.net = net[ni], h.xf = x, h.act = act, h.r = rr, h.yin = yin, h.out = out, h.part_s = part_s;
 #ifdef AVD_STAMP
         h.stamp = head_stamps() + 128 * ni;  // one region per head launch (net index): read back below
 #endif
-        hipLaunchKernelGGL(kern, grid, block, 0, st, h, extra...);
+        return h;
+    };
+    auto head = [&](auto kern, int ni, const f16x8* x, const float* act, const float* rr, const float* yin, float* out, float* part_s,
+                    auto... extra) {
+        hipLaunchKernelGGL(kern, grid, block, 0, st, head_args(ni, x, act, rr, yin, out, part_s), extra...);
     };
     DwArgs dw;
     dw.n_agents = n_agents, dw.n_sets = n_sets, dw.sm = sm, dw.g3 = g3, dw.x = s, dw.stamp = nullptr, dw.abl = 0;
@@ -1810,6 +1941,18 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
         fa.partH[i] = nullptr, fa.partHs[i] = F(pl.partHs[i]), fa.partU[i] = nullptr, fa.partV[i] = F(pl.partV[i]),
         fa.partG[i] = F(pl.partG[i]), fa.c3[i] = F(pl.vec[i]);
     fa.t1_from_g[0] = fa.t1_from_g[1] = 1, fa.t1p = F(pl.t1p), fa.s2raw = F(pl.s2raw);  // T1 of both nets: from the weight-gradient partials
+    // r15: the plain single call runs its ten persistent kernels and the seed as TWO launches (forward_kernel, backward_kernel: 7
+    // launches per call where there were 15). Every other form keeps the stand-alone launches: a phase alone, the smoothed call (a
+    // launch of its own sits between OUT_TANH and OUT_TD), the anchored call (its own seed launch), a sweep (OUT_TD's HP instantiation), the
+    // stamped diagnostic build -- and, in the diagnostic build, AVD_FSPLIT_UNFUSED=1 for A/B runs of the two forms of one library.
+    bool fused = phases == PH_BOTH && !an && !smo && sizeof...(H) == 0;
+#ifdef AVD_STAMP
+    fused = false;
+#endif
+    if (AVD_DIAG_ENV("FSPLIT_UNFUSED")) fused = false;
+    SeedArgs sd;
+    sd.n_agents = n_agents, sd.n_sets = n_sets, sd.dmu = dmu, sd.tz = F(pl.tz), sd.high = high, sd.g3 = g3a, sd.part_m = F(pl.partM[0]),
+    sd.part_s = F(pl.partHs[0]);
     if (phases & PH_CRITIC) {
         // (r05, measured and not kept: the preparation chain -- three small dependent launches over 1.5 MB of weights, ~30 us -- on a side
         //  stream beside the input packing, forked and joined by events: 1969-1978 us per learn against 1957-1961 serial on the same
@@ -1822,6 +1965,34 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
         fr.n_zero = (int)((fr.n_grads + ZERO_PER_BLOCK - 1) / ZERO_PER_BLOCK);
         hipLaunchKernelGGL(front_kernel<S>, dim3((unsigned)(fr.n_scale + fr.n_prep1 + fr.n_zero + 2 * fr.n_pack)), dim3(256), 0, st, fr);
         hipLaunchKernelGGL(prep_kernel, dim3(H2, 4, n_sets), dim3(320), 0, st, pa);
+    }
+    if (fused) {
+        FwdArgs fw;
+        fw.tanh_t = head_args(2, xfs2, nullptr, nullptr, nullptr, a2, nullptr);
+        fw.td = head_args(3, xfs2, a2, r, nullptr, y, nullptr);
+        h.sm = sma;
+        fw.tanh_save = head_args(0, xfs, nullptr, nullptr, nullptr, mu, nullptr);
+        h.sm = sm;
+        h.act2 = mu, h.part_s2 = F(pl.partHs[2]), h.part_m = F(pl.partM[1]);
+        fw.both = head_args(1, xfs, a, nullptr, y, nullptr, F(pl.partHs[1]));
+        fw.seed = sd;
+        hipLaunchKernelGGL(forward_kernel<S>, grid, block, 0, st, fw);
+        BwdArgs bw;
+        dw.net = net[1], dw.act = a, dw.partG = F(pl.partG[1]), dw.part_m = F(pl.partM[1]);
+        bw.dw_c = dw;
+        dx.net = net[1], dx.partV = F(pl.partV[1]), dx.act = a, dx.part_m = F(pl.partM[1]);
+        bw.dx_c = dx;
+        dx.L_cWa = L.cWa, dx.L_cba = L.cba;
+        bw.dxa = dx;
+        dw.sm = sma, dw.g3 = g3a, dw.net = net[0], dw.act = nullptr, dw.partG = F(pl.partG[0]), dw.part_m = F(pl.partM[0]);
+        bw.dw_a = dw;
+        dx.sm = sma, dx.g3 = g3a, dx.net = net[0], dx.partV = F(pl.partV[0]), dx.act = nullptr, dx.part_m = F(pl.partM[0]), dx.L_cWa = dx.L_cba = 0;
+        bw.dx_a = dx;
+        hipLaunchKernelGGL(backward_kernel<S>, grid, block, 0, st, bw);
+        launch_finalize(fa, st, 0, 2);
+        return check_launch("avd_learn_set_split");
+    }
+    if (phases & PH_CRITIC) {
         // 1-2: targets
         head(head_kernel<S, ActorS, OUT_TANH>, 2, xfs2, nullptr, nullptr, nullptr, a2, nullptr);
         if (smo) {  // target policy smoothing: a2 in place, between its writer and its only reader (csrc/smooth.hip)
@@ -1851,19 +2022,17 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
         if (phases == PH_CRITIC) launch_finalize(fa, st, 1, 1);
     }
     if (phases & PH_ACTOR) {
-        // 9-11: actor gradients: the seed from d mu and the stored tanh(z), then dw / dx on the stored (unsigned) masks
-        SeedArgs sd;
-        sd.n_agents = n_agents, sd.n_sets = n_sets, sd.dmu = dmu, sd.tz = F(pl.tz), sd.high = high, sd.g3 = g3, sd.part_m = F(pl.partM[0]),
-        sd.part_s = F(pl.partHs[0]);
+        // 9-11: actor gradients: the seed from d mu and the stored tanh(z) (into g3a, as in the fused launches), then dw / dx on the stored
+        // (unsigned) masks
         if (an) {  // the anchored seed in actor_seed_kernel's place, then the anchor loss's reducer (one wave per set)
             AnchorArgs q = *an;
-            q.n_agents = n_agents, q.n_sets = n_sets, q.S = S, q.J = pl.J, q.dmu = dmu, q.tz = sd.tz, q.high = high, q.g3 = g3;
+            q.n_agents = n_agents, q.n_sets = n_sets, q.S = S, q.J = pl.J, q.dmu = dmu, q.tz = sd.tz, q.high = high, q.g3 = g3a;
             q.part_m = sd.part_m, q.part_s = sd.part_s, q.mu = mu, q.s = s, q.aw = aw, q.inv_n = inv_n, q.c = 2.f * an->weight * inv_n;
             q.bad = bad;
             launch_anchor_seed(q, pl.grid, st);  // (csrc/anchor.hip)
         } else
             hipLaunchKernelGGL(actor_seed_kernel, grid, block, 0, st, sd);
-        dw.sm = sma, dx.sm = sma;
+        dw.sm = sma, dx.sm = sma, dw.g3 = g3a, dx.g3 = g3a;
         dw.net = net[0], dw.act = nullptr, dw.partG = F(pl.partG[0]), dw.part_m = F(pl.partM[0]);
         hipLaunchKernelGGL((dw_kernel<S, ActorS>), grid, block, 0, st, dw);
         dx.net = net[0], dx.partV = F(pl.partV[0]), dx.act = nullptr, dx.part_m = F(pl.partM[0]), dx.L_cWa = dx.L_cba = 0;
