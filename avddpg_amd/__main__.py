@@ -559,6 +559,17 @@ def _record_noise(conf, args):
         conf.target_noise = args.target_noise.record()
 
 
+def _delay_kw(args):
+    """VecTrainer's policy_delay keyword, only where the flag was given."""
+    return {} if getattr(args, "policy_delay", None) is None else dict(policy_delay=args.policy_delay)
+
+
+def _record_delay(conf, args):
+    """conf.json's policy_delay (the delay, an int), only where the flag was given."""
+    if getattr(args, "policy_delay", None) is not None:
+        conf.policy_delay = int(args.policy_delay)
+
+
 def _baselines(conf, args):
     """The run's baseline section, computed once (--residual tuned has already searched the grid)."""
     if getattr(args, "baselines", None) is None:
@@ -799,6 +810,14 @@ def get_cmdl_args(argv, conf):
                          "interfrl) and --rng device; combines with --seeds, --anchor, --warm_start, --actor_hold, --residual, "
                          "--train_disturb, --train_leader and --keep_best; not with --sweep / --pbt, a process group of more than one rank "
                          "or the centralized framework (not in the reference CLI)")
+    tr.add_argument("--policy_delay", type=str, default=None, metavar="D",
+                    help="delayed policy updates (TD3's): the actors and every target network move on every D-th learner call only (call "
+                         "k, 0-based, iff (k + 1) %% D == 0); on the others the critic alone takes its Adam step, from a TD-only learn call "
+                         "that computes nothing of the actor's half of the chain, and the actors keep an Adam count of their own. D = 1 "
+                         "trains what the run without the flag trains. conf.json records policy_delay. Needs --engine fused3 (shared-set "
+                         "interfrl) and --rng device; combines with --seeds, --anchor (acts on policy calls), --target_noise, --warm_start, "
+                         "--actor_hold, --residual, --train_disturb, --train_leader and --keep_best; not with --sweep / --pbt, a process "
+                         "group of more than one rank or the centralized framework (not in the reference CLI)")
     tr.add_argument("--actor_hold", type=int, default=None, metavar="N",
                     help="hold the actors still for the first N learner calls (the steps past the replay gate): the actor's step size "
                          "handed to the update is 0 for them, so the critic learns to evaluate the policy it was handed (a --warm_start fit, "
@@ -945,6 +964,26 @@ def get_cmdl_args(argv, conf):
             args.target_noise = _tr.check_target_noise(_tr.TargetNoise.parse(args.target_noise))
         except ValueError as e:
             ap.error(f"--target_noise: {e}")
+    if getattr(args, "policy_delay", None) is not None:
+        from . import trainer as _tr
+
+        if args.sweep is not None or args.pbt is not None:
+            ap.error("--policy_delay does not combine with --sweep / --pbt (the experiment copy and the table-driven update know one Adam "
+                     "count per weight set)")
+        if args.engine != "fused3":
+            ap.error(f"--policy_delay needs --engine fused3 (the split set learner holds the TD-only call), got --engine {args.engine}")
+        if args.rng != "device":
+            ap.error("--policy_delay needs --rng device (the fused3 engine's device-side run)")
+        if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+            ap.error("--policy_delay is not available under a process group of more than one rank")
+        try:  # (what needs the run's configuration is checked below, once it exists)
+            try:
+                d = int(args.policy_delay)
+            except ValueError:
+                raise ValueError(f"policy delay: D={args.policy_delay!r} must be a whole number >= 1") from None
+            args.policy_delay = _tr.check_policy_delay(d)
+        except ValueError as e:
+            ap.error(f"--policy_delay: {e}")
     if getattr(args, "actor_hold", None) is not None:
         if args.actor_hold < 1:
             ap.error(f"--actor_hold: N={args.actor_hold} must be >= 1")
@@ -1013,6 +1052,13 @@ def get_cmdl_args(argv, conf):
                 _tr.check_target_noise(args.target_noise, conf, args.engine, args.rng, 1)
             except ValueError as e:
                 ap.error(f"--target_noise: {e}")
+        if getattr(args, "policy_delay", None) is not None:
+            from . import trainer as _tr
+
+            try:
+                _tr.check_policy_delay(args.policy_delay, conf, args.engine, args.rng, 1, steps=conf.total_time_steps)
+            except ValueError as e:
+                ap.error(f"--policy_delay: {e}")
     return args, conf
 
 
@@ -1064,7 +1110,7 @@ def main(argv=None, conf=None):
             _resolve_anchor(args, conf)
             try:
                 vt = trainer.VecTrainer(conf, rng="device", auto_reset="platoon", shared_engine=args.engine, fused_update=nofrl,
-                                        train_disturb=args.train_disturb, **_lead_kw(args), **_residual_kw(args), **_warm_kw(args), **_anchor_kw(args), **_noise_kw(args))
+                                        train_disturb=args.train_disturb, **_lead_kw(args), **_residual_kw(args), **_warm_kw(args), **_anchor_kw(args), **_noise_kw(args), **_delay_kw(args))
             except ValueError as e:
                 if args.train_disturb is None:
                     raise
@@ -1116,7 +1162,7 @@ def main(argv=None, conf=None):
             _resolve_anchor(args, conf)
             try:
                 vt = trainer.VecTrainer(conf, rng=args.rng, auto_reset=False, shared_engine=args.engine, train_disturb=args.train_disturb,
-                                        **_lead_kw(args), **_residual_kw(args), **_warm_kw(args), **_anchor_kw(args), **_noise_kw(args))
+                                        **_lead_kw(args), **_residual_kw(args), **_warm_kw(args), **_anchor_kw(args), **_noise_kw(args), **_delay_kw(args))
             except ValueError as e:
                 if args.train_disturb is None:
                     raise
@@ -1154,6 +1200,7 @@ def main(argv=None, conf=None):
         _record_warm(conf, args)
         _record_anchor(conf, args, vt)
         _record_noise(conf, args)
+        _record_delay(conf, args)
         if args.keep_best is not None:
             _KeepResults(vt, args).write(base, conf, n_save)
         artifacts.config_writer(os.path.join(base, "conf.json"), conf)
@@ -1282,7 +1329,7 @@ def train_seed_batch(args, conf, base, experiments=None):
     try:
         vt = trainer.VecTrainer(conf, rng="device", auto_reset="platoon", shared_engine=args.engine,
                                 fused_update=conf.fed_method == conf.nofrl, seeds=seeds, hparams=hps,
-                                train_disturb=getattr(args, "train_disturb", None), **_lead_kw(args), **_residual_kw(args), **_warm_kw(args), **_anchor_kw(args), **_noise_kw(args))
+                                train_disturb=getattr(args, "train_disturb", None), **_lead_kw(args), **_residual_kw(args), **_warm_kw(args), **_anchor_kw(args), **_noise_kw(args), **_delay_kw(args))
     except ValueError as e:
         raise SystemExit(f"{flag}: {e}")
     vt.reset_episode()
@@ -1382,6 +1429,7 @@ def train_seed_batch(args, conf, base, experiments=None):
         _record_warm(ce, args, e)
         _record_anchor(ce, args, vt, e)
         _record_noise(ce, args)
+        _record_delay(ce, args)
         if suite is not None:
             _write_suite(d, ce, _slice(suite, e), range(1, P + 1), args)
             if baselines is not None:

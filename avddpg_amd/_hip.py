@@ -135,6 +135,7 @@ _PROTOS = {
     "avd_learn_update_plan": [_LP, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "avd_adam_polyak_f32": [_LP, _i, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _d, _P],
     "avd_adam_polyak_guarded_f32": [_LP, _i, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _d, _P, _P],
+    "avd_adam_polyak_delayed_f32": [_LP, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _f, _f, _d, _P, _P],
     "avd_polyak_f32": [_i64, _P, _P, _d, _P],
     "avd_fed_sum_f32": [_i, _i, _i, _i, _i, _P, _P, _P, _P, _P],
     "avd_fed_finalize_f32": [_i, _i, _P, _f, _P, _P],
@@ -157,6 +158,8 @@ _PROTOS = {
                                          _f, _P, _P],
     "avd_learn_set_split_smooth_f16x3": [_LP, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _P, _P, _P, C.c_size_t, _P, _i, _i, _f, _f,
                                          _f, _P, _f, _f, _u64, _u64, _P, _i, _P],
+    "avd_learn_set_split_td_f16x3": [_LP, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _f, _f, _P, _P, _P, C.c_size_t, _f, _f, _f, _f, _u64,
+                                     _u64, _P, _i, _i, _P],
     "avd_target_smooth_f32": [_i, _i, _i, _P, _f, _f, _f, _f, _u64, _u64, _P, _P],
     "avd_actor_forward_shared_workspace": [_LP, _i, _i, C.POINTER(C.c_size_t)],
     "avd_actor_forward_shared_bf16": [_LP, _i, _i, _P, _P, _P, _f, _P, _P, C.c_size_t, _P],

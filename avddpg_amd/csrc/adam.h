@@ -35,13 +35,22 @@ __device__ __forceinline__ AdamAlphas adam_alphas(float actor_lr, float critic_l
 struct AdamElem {
     float w, wt, m, v;
 };
-__device__ __forceinline__ AdamElem adam_polyak_step(float w_in, float wt, float m, float v, float g, float alpha, float tau,
-                                                     float omt) {
+// The Adam half alone: (pre-update weight, moments, gradient) -> (updated weight, moments); wt is not touched. What a skipped call of
+// the delayed update (optim.hip: adam_polyak_delayed_kernel<false>) applies to the critic block, whose target follows only on policy
+// calls -- and the first three statements of every other update: adam_polyak_step below goes through it.
+__device__ __forceinline__ AdamElem adam_step(float w_in, float wt, float m, float v, float g, float alpha) {
 #pragma clang fp contract(off)
     AdamElem o;
     o.m = m + (g - m) * (1.0f - ADAM_B1);
     o.v = v + (g * g - v) * (1.0f - ADAM_B2);
     o.w = w_in - (o.m * alpha) / (sqrtf(o.v) + ADAM_EPS);
+    o.wt = wt;
+    return o;
+}
+__device__ __forceinline__ AdamElem adam_polyak_step(float w_in, float wt, float m, float v, float g, float alpha, float tau,
+                                                     float omt) {
+#pragma clang fp contract(off)
+    AdamElem o = adam_step(w_in, wt, m, v, g, alpha);
     o.wt = o.w * tau + wt * omt;  // update_target on the freshly updated weight
     return o;
 }

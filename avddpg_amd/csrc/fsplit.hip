@@ -479,8 +479,9 @@ __global__ __launch_bounds__(256) void front_kernel(const FrontArgs a) {
 }
 
 // ---- head: first layer -> second-layer GEMM (three MFMAs per product) -> output layer [-> its backward] -------------------
-// (2..4 were r03's HEAD_CRITIC / HEAD_CONST / HEAD_ACTOR: two-launch critic heads and the second actor forward, gone in r04)
-enum HeadMode { OUT_TANH = 0, OUT_TD = 1, HEAD_BOTH = 5, OUT_TANH_SAVE = 6 };
+// (2..4 were r03's HEAD_CRITIC / HEAD_CONST / HEAD_ACTOR: two-launch critic heads and the second actor forward, gone in r04; today's
+//  HEAD_CRITIC, 7, is HEAD_BOTH cut off behind its branch A: the TD-only call's critic head)
+enum HeadMode { OUT_TANH = 0, OUT_TD = 1, HEAD_BOTH = 5, OUT_TANH_SAVE = 6, HEAD_CRITIC = 7 };
 struct HeadArgs {
     unsigned long long* stamp;  // diagnostic build (-DAVD_STAMP) only: [8 waves][8] accumulated s_memtime deltas of workgroup 16
     NetP net;
@@ -489,7 +490,7 @@ struct HeadArgs {
     const float* act;  // [n_agents][64] the critic's action input (a, a' or mu)
     const float* act2; // HEAD_BOTH: mu (act = a)
     const float* r;    // OUT_TD: rewards [n_agents][64]
-    const float* yin;  // HEAD_BOTH: TD targets
+    const float* yin;  // HEAD_BOTH, HEAD_CRITIC: TD targets
     const float* aw;   // per-agent factor on the loss seeds (weighted federated mean) or NULL
     float* out;        // OUT_*: per-row result
     unsigned* sm;      // HEAD_BOTH, OUT_TANH_SAVE: the relu mask [z2 > 0], one bit per element, [n_agents][64][4 words] (16 B per row;
@@ -499,7 +500,7 @@ struct HeadArgs {
     float* g3;         // HEAD_BOTH: the row factor of dZ2 [n_agents][64]
     float* dmu;        // HEAD_BOTH: dLa/dmu per row [n_agents][64]
     float* part_s;     // HEAD_*: [grid][8 waves][2] sums of the seeds and of the loss terms
-    float* part_s2;    // HEAD_BOTH: the same sums of the critic(s, mu) branch (the actor loss)
+    float* part_s2;    // HEAD_BOTH: the same sums of the critic(s, mu) branch (the actor loss); HEAD_CRITIC: zeros
     float* part_m;     // backward modes: [grid][8 waves] max |g3| over the wave's rows (dw / dx scale their fp16 operands by it)
     float* tz;         // OUT_TANH_SAVE: tanh(z) per row [n_agents][64] (the actor's backward seed needs 1 - t^2: actor_seed_kernel)
     float gamma, high, inv_n;
@@ -517,6 +518,10 @@ struct HeadArgs {
 // first-layer tiles and 192 of their 228 second-layer MFMAs per 32 rows are the SAME work -- one pass over the state tiles, then
 // three sweeps over the action k-steps on the one accumulator set: A (input a: TD seed, signed masks), B1 (input mu, by
 // linearity), B2 (the action gradient through M).
+// HEAD_CRITIC (avd_learn_set_split_td_f16x3: a call on which the actor does not move) is HEAD_BOTH up to and including branch A --
+// the state tiles, the A sweep, g3, the masks, the loss sums -- and then the next tile: no mu input, no wap table, no B sweeps, no
+// dmu; its part_s2 is zeros, so that finalize's actor-loss sum is defined. What it shares with HEAD_BOTH it computes the same way:
+// same bits in g3, the masks and the partial sums.
 // (r04, tried: the forward-only modes with 64 rows per wave -- both row halves against every weight fragment pair, six MFMAs per
 // two LDS reads instead of three, 128 accumulator registers: OUT_TANH 190.9 us against 190, OUT_TD 220.8 against 223 on the same
 // box. Halving the LDS bytes per MFMA buys nothing: the heads are not LDS-bound. Not kept.)
@@ -540,8 +545,9 @@ __device__ __forceinline__ void head_body(const HeadArgs& p, unsigned char* lds,
     constexpr int K = NET::K, NKS = NET::NKS, NFT = NET::NFT, LD = NET::LD;  // LD/2 = 4 (mod 8) dwords: conflict-free b128
     constexpr int NTH = NT;  // 8 waves: two per SIMD at <= 256 registers
     constexpr bool BOTH = (MODE == HEAD_BOTH);
+    constexpr bool BA = BOTH || MODE == HEAD_CRITIC;  // the modes that run branch A (the critic loss and its backward seed)
     // (T1 = sum_rows g3 relu(z2) is not accumulated here: finalize derives it from dw_kernel's partials, FinArgs::t1_from_g)
-    static_assert(!BOTH || NET::critic, "HEAD_BOTH is a critic mode");
+    static_assert(!BA || NET::critic, "HEAD_BOTH and HEAD_CRITIC are critic modes");
     f16(*wimg)[H2 * LD] = (f16(*)[H2 * LD]) lds;                       // [2][H2 * LD]
     float* b2s = (float*)(lds + 2 * H2 * LD * sizeof(f16));            // [H2]
     float* c3s = b2s + H2;                                             // [H2]
@@ -569,8 +575,8 @@ __device__ __forceinline__ void head_body(const HeadArgs& p, unsigned char* lds,
         if (NET::critic) na = p.act[ri];
         if (BOTH) nb = p.act2[ri];
         if (MODE == OUT_TD) ny = p.r[ri];
-        if (BOTH) ny = p.yin[ri];
-        if (BOTH && p.aw) nw = p.aw[agent];
+        if (BA) ny = p.yin[ri];
+        if (BA && p.aw) nw = p.aw[agent];
     };
     // The two waves of a SIMD (w and w + 4) are arbitrated oldest first: with equal shares, waves 0..3 ran 12.0 k cycles per unit
     // and waves 4..7 20.4 k until the old ones were done, then finished alone at 61 % of the matrix pipe (s_memtime stamps, r03;
@@ -629,7 +635,7 @@ __device__ __forceinline__ void head_body(const HeadArgs& p, unsigned char* lds,
     const f16* whi0 = &wimg[0][r * LD + 8 * h];  // + 32 t LD + 16 ks
     const f16* wlo0 = &wimg[1][r * LD + 8 * h];
     // the sequence of feature tiles of a unit: tiles 0 .. NFT - 1; HEAD_BOTH: + the action tiles 8, 9 once more (input mu)
-    constexpr int NSEQ = BOTH ? 8 : NFT;  // HEAD_BOTH: the state tiles; the action tiles are streamed per column tile below
+    constexpr int NSEQ = BA ? 8 : NFT;  // HEAD_BOTH, HEAD_CRITIC: the state tiles; the action tiles are streamed per column tile below
     HSTAMP(3);  // image fill, tables, first fetch (from the kernel's first instruction)
     for (int ui = 0; k < ntile; ++ui, k = next_tile(k, pos), pos = pos + 1 == cnt ? 0 : pos + 1) {
         const int agent = (j0 + k * J) * p.n_sets + set;
@@ -743,7 +749,7 @@ __device__ __forceinline__ void head_body(const HeadArgs& p, unsigned char* lds,
 #pragma unroll
                 for (int th = 0; th < 2; ++th) {
                     const int g = 2 * ks + th;
-                    if (g + 1 < 2 * (BOTH ? 16 : NKS)) read_group(g + 1, wg[(g + 1) & 1]);
+                    if (g + 1 < 2 * (BA ? 16 : NKS)) read_group(g + 1, wg[(g + 1) & 1]);
 #pragma unroll
                     for (int tt = 0; tt < 2; ++tt) {
                         const int t = 2 * th + tt;
@@ -773,7 +779,7 @@ __device__ __forceinline__ void head_body(const HeadArgs& p, unsigned char* lds,
         HSTAMP(0);  // unit start: inputs, bias
         static_for<0, NSEQ>([&](auto si_c) { tile(si_c, acc); });
         HSTAMP(1);  // the feature tiles
-        if constexpr (BOTH) {
+        if constexpr (BA) {
             // acc = the state part of z2 (+ bias); the action part is 3 k-steps. Three sweeps of 36 MFMAs over the four column
             // tiles, all on the ONE set of accumulators (acc + T1 + M never coexist: <= 256 registers, two waves per SIMD):
             //   A : acc += W2T[:, action] . f(a)             -> z, TD seed, masks, T1 (acc left as z2, not relu'd)
@@ -824,6 +830,7 @@ __device__ __forceinline__ void head_body(const HeadArgs& p, unsigned char* lds,
                 mask_store(mb, p.sm + ri * 4);
             }
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (!BOTH) continue;  // HEAD_CRITIC: the critic loss alone -- on to the next tile
             // ---- branch B: critic(s, mu) -> the actor loss -mean(q) and its gradient w.r.t. the action (:501-504)
             f16x8 mh[3], ml[3];
 #pragma unroll
@@ -912,7 +919,7 @@ __device__ __forceinline__ void head_body(const HeadArgs& p, unsigned char* lds,
         for (int i = 0; i < 4; ++i) p.stamp[w * 8 + i] = hacc[i];
 #endif
     if (watch >= 0x7f800000u) atomicOr(p.bad, 1);
-    if (BOTH) {
+    if (BA) {  // (HEAD_CRITIC: Dacc2 = Lacc2 = 0)
         // one partial per wave: sums over the 32 row lanes of each half (fixed shuffle tree), one writer per half
 #pragma unroll
         for (int o = 1; o < 32; o <<= 1) {
@@ -1854,7 +1861,7 @@ static int check_shape(const avd_mlp_layout* L, int n_agents, int n_sets, const 
 //   launches), 236 / 224 registers, no scratch, LDS of the largest phase, every tile loop the stand-alone kernel's instructions
 //   (r15_fused_launches_static.txt). The seams are workgroup barriers, not the agent-scope release / acquire pairs first planned: no
 //   dependence crosses a workgroup, and an agent-scope pair costs more per seam (L2 write-back, L1 invalidate) than the boundary it replaces.
-enum Phase { PH_CRITIC = 1, PH_ACTOR = 2, PH_BOTH = 3 };
+enum Phase { PH_CRITIC = 1, PH_ACTOR = 2, PH_BOTH = 3, PH_TD = 4 };  // PH_TD: the TD-only call (alone, never or'ed with the others)
 #ifdef AVD_STAMP
 // Diagnostic build with -DAVD_STAMP: the heads' s_memtime stamps (head_kernel: HSTAMP; workgroup 16, per wave the cycles of 0 unit start,
 // 1 feature tiles, 2 epilogue, 3 start-up) land in host-visible memory, one region of 128 words per net, and AVD_FSPLIT_STAMPS=1 prints
@@ -1953,7 +1960,7 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
     SeedArgs sd;
     sd.n_agents = n_agents, sd.n_sets = n_sets, sd.dmu = dmu, sd.tz = F(pl.tz), sd.high = high, sd.g3 = g3a, sd.part_m = F(pl.partM[0]),
     sd.part_s = F(pl.partHs[0]);
-    if (phases & PH_CRITIC) {
+    if (phases & (PH_CRITIC | PH_TD)) {
         // (r05, measured and not kept: the preparation chain -- three small dependent launches over 1.5 MB of weights, ~30 us -- on a side
         //  stream beside the input packing, forked and joined by events: 1969-1978 us per learn against 1957-1961 serial on the same
         //  box; the fork / join costs more than the overlap of two sub-30-us stages returns. r09: the same overlap without a fork --
@@ -1992,7 +1999,11 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
         launch_finalize(fa, st, 0, 2);
         return check_launch("avd_learn_set_split");
     }
-    if (phases & PH_CRITIC) {
+    // The TD-only call (avd_learn_set_split_td_f16x3) is the critic phase without what only the actor phase reads: no mu pass
+    // (OUT_TANH_SAVE), and the critic head in its loss-only mode (HEAD_CRITIC: no B sweeps, no d mu). dxa stays: the action layer's
+    // parameter sums are the critic's own gradients. One launch sequence serves both.
+    const bool td = phases == PH_TD;
+    if (phases & (PH_CRITIC | PH_TD)) {
         // 1-2: targets
         head(head_kernel<S, ActorS, OUT_TANH>, 2, xfs2, nullptr, nullptr, nullptr, a2, nullptr);
         if (smo) {  // target policy smoothing: a2 in place, between its writer and its only reader (csrc/smooth.hip)
@@ -2005,12 +2016,17 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
         else
             head(head_kernel<S, CriticS, OUT_TD>, 3, xfs2, a2, r, nullptr, y, nullptr);
         // 3: mu -- and the actor's relu masks + tanh(z) for its backward pass (no second actor forward: r03's HEAD_ACTOR)
-        h.sm = sma;
-        head(head_kernel<S, ActorS, OUT_TANH_SAVE>, 0, xfs, nullptr, nullptr, nullptr, mu, nullptr);
-        h.sm = sm;
-        // 4-7: critic loss and gradients; critic(s, mu) and the action gradient ride in the same launch (HEAD_BOTH)
-        h.act2 = mu, h.part_s2 = F(pl.partHs[2]), h.part_m = F(pl.partM[1]);
-        head(head_kernel<S, CriticS, HEAD_BOTH>, 1, xfs, a, nullptr, y, nullptr, F(pl.partHs[1]));
+        if (!td) {
+            h.sm = sma;
+            head(head_kernel<S, ActorS, OUT_TANH_SAVE>, 0, xfs, nullptr, nullptr, nullptr, mu, nullptr);
+            h.sm = sm;
+        }
+        // 4-7: critic loss and gradients; critic(s, mu) and the action gradient ride in the same launch (HEAD_BOTH; TD-only: neither)
+        h.act2 = td ? nullptr : mu, h.part_s2 = F(pl.partHs[2]), h.part_m = F(pl.partM[1]);
+        if (td)
+            head(head_kernel<S, CriticS, HEAD_CRITIC>, 1, xfs, a, nullptr, y, nullptr, F(pl.partHs[1]));
+        else
+            head(head_kernel<S, CriticS, HEAD_BOTH>, 1, xfs, a, nullptr, y, nullptr, F(pl.partHs[1]));
         dw.net = net[1], dw.act = a, dw.partG = F(pl.partG[1]), dw.part_m = F(pl.partM[1]);
         hipLaunchKernelGGL((dw_kernel<S, CriticS>), grid, block, 0, st, dw);
         dx.net = net[1], dx.partV = F(pl.partV[1]), dx.act = a, dx.part_m = F(pl.partM[1]);
@@ -2019,7 +2035,8 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
         hipLaunchKernelGGL((dxa_kernel<S>), grid, block, 0, st, dx);
         // 8: the critic block of the slab (+ both losses: the actor loss is the mean of q(s, mu), summed by HEAD_BOTH) -- when the
         // caller asked for this phase alone; the single call finalizes both blocks together at its end (three launches, not six)
-        if (phases == PH_CRITIC) launch_finalize(fa, st, 1, 1);
+        // (TD-only: the actor block stays the zeros of the front launch)
+        if (phases == PH_CRITIC || td) launch_finalize(fa, st, 1, 1);
     }
     if (phases & PH_ACTOR) {
         // 9-11: actor gradients: the seed from d mu and the stored tanh(z) (into g3a, as in the fused launches), then dw / dx on the stored
@@ -2067,6 +2084,13 @@ constexpr long MFMA_PER_TILE = 2 * (200 + 238 + 200 + 314)            /* four he
                                + 2 * 8 * (32 + 2 + 8)                 /* dx critic, actor */
                                + 4 * 16;                              /* dxa */
 static_assert(MFMA_PER_TILE == 3296, "update DESIGN.md 3.4 and the count above together");
+// The TD-only call (avd_learn_set_split_td_f16x3): OUT_TANH, OUT_TD and HEAD_CRITIC = the state part 8 + 192 and branch A 2 + 36 = 238;
+// the critic's dw, dx and dxa. (Without dxa, whose 64 are the critic's action-layer sums: 2032.)
+constexpr long MFMA_PER_TILE_TD = 2 * (200 + 238 + 238)               /* three head launches */
+                                  + 8 * (2 + 32 + 1 + 2 * 2 * 2)      /* dw critic */
+                                  + 8 * (32 + 2 + 8)                  /* dx critic */
+                                  + 4 * 16;                           /* dxa */
+static_assert(MFMA_PER_TILE_TD == 2096 && MFMA_PER_TILE_TD - 4 * 16 == 2032, "update DESIGN.md 3.4 and the count above together");
 }}
 extern "C" int avd_learn_set_split_mfma_count(const avd_mlp_layout* lay, int n_agents, int n_sets, unsigned long long* mfma_32x32x16) {
     int rc = fsplit::check_shape(lay, n_agents, n_sets, "avd_learn_set_split_mfma_count");
@@ -2091,7 +2115,7 @@ static int split_entry(int phases, const char* who, const avd_mlp_layout* lay, i
                        size_t workspace_bytes, void* stream, const AnchorArgs* an, const SmoothArgs* smo, H... hp) {
     int rc = fsplit::check_shape(lay, n_agents, n_sets, who);
     if (rc) return rc;
-    const bool cr = phases & fsplit::PH_CRITIC;
+    const bool cr = phases & (fsplit::PH_CRITIC | fsplit::PH_TD);
     AVD_REQUIRE(theta && stats && s && grads && workspace && (!cr || (theta_t && stats_t && a && r && s2)), "%s: null pointer", who);
     const fsplit::Plan pl = fsplit::make_plan(n_agents, n_sets);
     AVD_REQUIRE(workspace_bytes >= pl.total, "%s: workspace %zu B < %zu B", who, workspace_bytes, pl.total);
@@ -2197,6 +2221,26 @@ extern "C" int avd_learn_set_split_critic(const avd_mlp_layout* lay, int n_agent
                                           float* losses, void* workspace, size_t workspace_bytes, void* stream) {
     return split_entry(fsplit::PH_CRITIC, "avd_learn_set_split_critic", lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2,
                        agent_weight, gamma, high, grads, losses, workspace, workspace_bytes, stream, nullptr, nullptr);
+}
+
+// The TD-only call: the critic block and the critic loss, nothing of the actor's half of the chain (fsplit::run, PH_TD). The smoothing
+// arguments as in avd_learn_set_split_smooth_f16x3; sigma == 0: no smoothing launch. Everything refused here is refused before a HIP call.
+extern "C" int avd_learn_set_split_td_f16x3(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
+                                            const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
+                                            const float* s2, const float* agent_weight, float gamma, float high, float* grads,
+                                            float* losses, void* workspace, size_t workspace_bytes, float sigma, float noise_clip, float lo,
+                                            float hi, uint64_t seed, uint64_t counter, const uint64_t* d_seeds, int E, int M, void* stream) {
+    const char* who = "avd_learn_set_split_td_f16x3";
+    int rc = fsplit::check_shape(lay, n_agents, n_sets, who);
+    if (rc) return rc;
+    SmoothArgs sm{};
+    sm.M = M, sm.E = E, sm.sigma = sigma, sm.clip = noise_clip, sm.lo = lo, sm.hi = hi, sm.seed = seed, sm.counter = counter, sm.seeds = d_seeds;
+    rc = check_smooth(who, sm);
+    if (rc) return rc;
+    AVD_REQUIRE(n_sets % ((long)E * M) == 0, "%s: n_sets=%d M=%d E=%d (n_sets must be a multiple of E x M)", who, n_sets, M, E);
+    AVD_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
+    return split_entry(fsplit::PH_TD, who, lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2, agent_weight, gamma, high, grads,
+                       losses, workspace, workspace_bytes, stream, nullptr, sigma == 0.f ? nullptr : &sm);
 }
 
 extern "C" int avd_learn_set_split_actor(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,

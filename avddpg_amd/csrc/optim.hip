@@ -35,6 +35,10 @@ __device__ __forceinline__ bool slab_is_nan(const float* g, int actor_size) {
     const unsigned a = __float_as_uint(g[0]) & 0x7fffffffu, c = __float_as_uint(g[actor_size]) & 0x7fffffffu;
     return a >= 0x7f800000u || c >= 0x7f800000u;
 }
+// the same test of ONE head, for the delayed update below, whose two kinds of call look at different heads. (slab_is_nan written as
+// two calls of it compiles to other instructions in the four existing kernels -- float compares in place of the integer ones -- so it
+// keeps its own text.)
+__device__ __forceinline__ bool head_not_finite(float x) { return (__float_as_uint(x) & 0x7fffffffu) >= 0x7f800000u; }
 
 // grid: (blocks over theta_size/4, n_sets). GUARD: avd_adam_polyak_guarded_f32 -- a set with a NaN gradient slab takes no step at all
 // (weights, moments, targets untouched), its Adam iteration count (already advanced by the caller) is put back and *skipped counts it.
@@ -395,6 +399,68 @@ template __global__ void avd::adam_polyak_kernel<true>(int, int, float4*, float4
 template __global__ void avd::adam_polyak_kernel<false>(int, int, float4*, float4*, float4*, float4*, const float4*, int32_t*, float, float,
                                                          float, float, int32_t*);
 
+// ---- the delayed update (TD3's delayed policy updates; avd_adam_polyak_delayed_f32) ---------------------------------------------
+// Behind the instantiations above, so that every kernel in front keeps its place and its text in the code object.
+// grid: (blocks over the float4 groups the call covers, n_sets); always guarded. step[set] is the critic block's Adam count,
+// actor_step[set] the actor block's own.
+//   POLICY : the whole slab, adam_polyak_kernel<true>'s loop with the actor block's step size from actor_step[set]: with
+//            actor_step == step the same bits. The guard looks at both heads and puts back both counts.
+//   !POLICY: a skipped call. The critic block's float4 groups only, adam_step without the target half: theta_t, the actor block of
+//            every array (its gradients included: they may hold anything) and actor_step are neither read nor written. The guard
+//            looks at the critic block's head alone.
+namespace avd {
+template <bool POLICY>
+__global__ __launch_bounds__(256) void adam_polyak_delayed_kernel(int theta_size, int actor_size, float4* __restrict__ theta,
+                                                                  float4* __restrict__ theta_t, float4* __restrict__ m,
+                                                                  float4* __restrict__ v, const float4* __restrict__ grads,
+                                                                  int32_t* __restrict__ step, int32_t* __restrict__ actor_step,
+                                                                  float actor_lr, float critic_lr, float tau, float omt,
+                                                                  int32_t* __restrict__ skipped) {
+    const int set = blockIdx.y;
+    const int t = step[set];
+    const float* gs = (const float*)grads + (long)set * theta_size;
+    if (head_not_finite(gs[actor_size]) || (POLICY && head_not_finite(gs[0]))) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) {  // (every thread of the set returns here: nobody uses the counts)
+            step[set] = t - 1;
+            if (POLICY) actor_step[set] = actor_step[set] - 1;
+            if (skipped) atomicAdd(skipped, 1);
+        }
+        return;
+    }
+    const int n4 = theta_size / 4, a4 = actor_size / 4;  // blocks are 4-float aligned
+    const long base = (long)set * n4;
+    const float alpha_c = adam_bias(t).alpha(critic_lr);
+    if constexpr (POLICY) {
+        const float alpha_a = adam_bias(actor_step[set]).alpha(actor_lr);
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
+            const float alpha = i < a4 ? alpha_a : alpha_c;
+            float4 w = theta[base + i], wt = theta_t[base + i], mm = m[base + i], vv = v[base + i];
+            const float4 g = grads[base + i];
+            adam_polyak_step4(w, wt, mm, vv, &g.x, alpha, tau, omt);
+            theta[base + i] = w;
+            theta_t[base + i] = wt;
+            m[base + i] = mm;
+            v[base + i] = vv;
+        }
+    } else {
+        for (int i = a4 + blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
+            float4 w = theta[base + i], mm = m[base + i], vv = v[base + i];
+            const float4 g = grads[base + i];
+            float *wp = &w.x, *mp = &mm.x, *vp = &vv.x;
+            const float* gp = &g.x;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const AdamElem o = adam_step(wp[k], 0.f, mp[k], vp[k], gp[k], alpha_c);
+                wp[k] = o.w, mp[k] = o.m, vp[k] = o.v;
+            }
+            theta[base + i] = w;
+            m[base + i] = mm;
+            v[base + i] = vv;
+        }
+    }
+}
+}  // namespace avd
+
 // The four avd_adam_polyak_*_f32 entries: Adam + Polyak of n_sets whole slabs, then the BN moving statistics' soft update (they take
 // part in it too: ddpgagent.py:44-53 iterates .weights). GUARD: sets with a NaN gradient slab are left alone and counted in *skipped.
 // hp = one HpRef: each set's step sizes and tau from row (set / set_block) % n_groups of the sweep table (the scalars are unused);
@@ -569,4 +635,39 @@ extern "C" int avd_adam_polyak_intra_f32(const avd_mlp_layout* lay, int P, int M
     hipLaunchKernelGGL(polyak_intra_kernel, dim3((unsigned)((lay->stats_size + 255) / 256), (unsigned)(P * M)), dim3(256), 0,
                        (hipStream_t)stream, lay->stats_size, M, lead_skip ? 1 : 0, stats, stats_t, tauf, omt);
     return check_launch("avd_adam_polyak_intra_f32");
+}
+
+// policy != 0: Adam + Polyak of both blocks, then the BN statistics' soft update of the sets that stepped (polyak_guarded_kernel's
+// guard is this call's: either head). policy == 0: one launch over the critic blocks, no target of any kind moves.
+extern "C" int avd_adam_polyak_delayed_f32(const avd_mlp_layout* lay, int n_sets, float* theta, float* stats, float* theta_t,
+                                           float* stats_t, float* m, float* v, const float* grads, int32_t* step, int32_t* actor_step,
+                                           int policy, float actor_lr, float critic_lr, double tau, int32_t* skipped, void* stream) {
+    const char* who = "avd_adam_polyak_delayed_f32";
+    AVD_REQUIRE(lay && n_sets > 0 && n_sets <= 65535, "%s: n_sets=%d", who, n_sets);
+    AVD_REQUIRE(theta && stats && theta_t && stats_t && m && v && grads && step && actor_step, "%s: null pointer", who);
+    AVD_REQUIRE(lay->theta_size % 4 == 0 && lay->actor_size % 4 == 0 && lay->stats_size % 4 == 0, "%s: layout not 4-float aligned", who);
+    AVD_REQUIRE(lay->actor_size > 0 && lay->actor_size < lay->theta_size && lay->stats_size > 0, "%s: layout without an actor or a critic block",
+                who);
+    AVD_REQUIRE(actor_lr >= 0.f && actor_lr <= 3.4028235e38f && critic_lr >= 0.f && critic_lr <= 3.4028235e38f,  // (a NaN fails both)
+                "%s: actor_lr=%g critic_lr=%g (must be finite and >= 0)",
+                who, (double)actor_lr, (double)critic_lr);
+    AVD_REQUIRE(tau > 0.0 && tau <= 1.0, "%s: tau=%g (must be in (0, 1])", who, tau);
+    const float tauf = (float)tau, omt = (float)(1.0 - tau);
+    const int n4 = (policy ? lay->theta_size : lay->theta_size - lay->actor_size) / 4;
+    int gx = (n4 + 255) / 256;
+    if (n_sets >= 256 && gx > 8) gx = 8;  // many sets: fewer, longer-lived blocks per set (as adam_polyak_launch)
+    if (!policy) {
+        hipLaunchKernelGGL(adam_polyak_delayed_kernel<false>, dim3(gx, n_sets), dim3(256), 0, (hipStream_t)stream, lay->theta_size,
+                           lay->actor_size, (float4*)theta, (float4*)theta_t, (float4*)m, (float4*)v, (const float4*)grads, step, actor_step,
+                           actor_lr, critic_lr, tauf, omt, skipped);
+        return check_launch(who);
+    }
+    hipLaunchKernelGGL(adam_polyak_delayed_kernel<true>, dim3(gx, n_sets), dim3(256), 0, (hipStream_t)stream, lay->theta_size, lay->actor_size,
+                       (float4*)theta, (float4*)theta_t, (float4*)m, (float4*)v, (const float4*)grads, step, actor_step, actor_lr, critic_lr,
+                       tauf, omt, skipped);
+    int rc = check_launch(who);
+    if (rc) return rc;
+    hipLaunchKernelGGL((polyak_guarded_kernel<true>), dim3((unsigned)((lay->stats_size + 255) / 256), n_sets), dim3(256), 0, (hipStream_t)stream,
+                       lay->stats_size, stats, stats_t, tauf, omt, grads, lay->theta_size, lay->actor_size);
+    return check_launch(who);
 }

@@ -332,6 +332,55 @@ def check_target_noise(target_noise, conf=None, shared_engine="fused3", rng="dev
     return tn
 
 
+def is_policy_call(call, policy_delay):
+    """Whether learner call ``call`` (0-based) of a run with this delay moves the actors and the targets: every policy_delay-th call,
+    the policy_delay-th first (TD3's delayed policy updates). No delay (None): every call."""
+    return policy_delay is None or (int(call) + 1) % int(policy_delay) == 0
+
+
+def check_policy_delay(policy_delay, conf=None, shared_engine="fused3", rng="device", world_size=1, hparams=None, overlap_allreduce=None,
+                       shared_sets=None, steps=None):
+    """Why a run cannot delay its policy updates by ``policy_delay`` (VecTrainer(policy_delay=...)), raised as a ValueError -- or the
+    checked delay, an int >= 1. Called before anything is allocated or launched. The skipped calls run the split set learner's TD-only
+    call and the update with the actor's own Adam count (avd_learn_set_split_td_f16x3, avd_adam_polyak_delayed_f32): shared_engine=
+    'fused3', so shared-set interfrl, on one rank, in the single call, outside any sweep, with the device's generator. ``steps``: the
+    run's step count where the caller knows it -- a delay at or above it, or (with ``conf``) above the steps - batch_size learner calls
+    the run makes past the replay gate, would never move the actors. Without ``conf`` the value
+    alone is checked."""
+    d = policy_delay
+    if isinstance(d, bool) or not isinstance(d, (int, np.integer)):
+        raise ValueError(f"policy delay: policy_delay={d!r} must be a whole number >= 1")
+    if d < 1:
+        raise ValueError(f"policy delay: policy_delay={d!r} must be >= 1")
+    if steps is not None and d >= int(steps):
+        raise ValueError(f"policy delay: policy_delay={d} is not below the run's {int(steps)} steps: the actors would never move")
+    if steps is not None and conf is not None and d > int(steps) - int(conf.batch_size):
+        # (the replay gate: the first learner call is the step after batch_size rows are in, so a run makes steps - batch_size calls)
+        raise ValueError(f"policy delay: policy_delay={d} is above the {max(0, int(steps) - int(conf.batch_size))} learner calls that "
+                         f"{int(steps)} steps make past the replay gate ({int(conf.batch_size)} rows): the actors would never move")
+    if shared_engine != "fused3":
+        raise ValueError(f"policy delay needs shared_engine='fused3' (the split set learner holds the TD-only call; the per-agent engines "
+                         f"and the bf16 set learners have none), got shared_engine={shared_engine!r}")
+    if rng != "device":
+        raise ValueError(f"policy delay needs rng='device' (the fused3 engine's device-side run), got rng={rng!r}")
+    if hparams is not None:
+        raise ValueError("policy delay does not combine with a hyperparameter sweep or PBT (hparams=...): the experiment copy and the "
+                         "table-driven update know one Adam count per weight set")
+    if overlap_allreduce:
+        raise ValueError("policy delay does not combine with overlap_allreduce: the two-phase learn call has no TD-only form")
+    if int(world_size) > 1:
+        raise ValueError("policy delay runs on one rank: no process group of more than one rank")
+    if conf is not None:
+        if conf.framework == conf.cntrl:
+            raise ValueError("policy delay needs the decentralized framework (the split set learner's)")
+        can_share = (is_fed_enabled(conf) and conf.fed_method == conf.interfrl and is_gradient_updates_enabled(conf)
+                     and conf.fed_update_delay_steps == 1 and conf.fed_update_count == 1 and conf.fed_cutoff_ratio >= 1.0)
+        if not can_share or (shared_sets is not None and not shared_sets):
+            raise ValueError("policy delay needs shared weight sets: interfrl + gradients with every step federated (the fused3 engine's "
+                             "regime)")
+    return int(d)
+
+
 def check_keep_best(world_size):
     """Why a run cannot keep the best actors seen (VecTrainer.enable_keep_best), raised as a ValueError -- or None. Called before
     anything is allocated or launched."""
@@ -358,7 +407,7 @@ class VecTrainer:
     def __init__(self, conf, device=None, rng="device", group=None, shared_sets=None, seed=None, auto_reset=False,
                  pipeline_chunks=1, fused_update=False, shared_engine=None, init_seed=None, fused_step=None,
                  replay_ring=None, overlap_allreduce=None, seeds=None, hparams=None, train_disturb=None, train_leader=None,
-                 residual=None, warm_start=None, actor_hold=0, anchor=None, target_noise=None):
+                 residual=None, warm_start=None, actor_hold=0, anchor=None, target_noise=None, policy_delay=None):
         """group: torch.distributed process group whose ranks each hold ``conf.num_platoons`` platoons
         (interfrl gradients are all-reduced over it). auto_reset: end episodes on the device (no host
         sync per step); needs rng='device'. True: the reference's rule -- any terminal platoon (or the step limit) ends
@@ -417,7 +466,15 @@ class VecTrainer:
         keyed by the run's seed (under seeds= by each experiment's: experiment e draws what its solo run draws) and the 0-based
         learner-call count. With anchor= the gains, weight_at(call) and the loss buffer travel in the same call. check_target_noise says
         what it needs (shared_engine='fused3', rng='device', one rank, no sweep, no overlapped exchange). None: nothing is allocated,
-        today's entry points run."""
+        today's entry points run.
+        policy_delay: d >= 1 -- TD3's delayed policy updates: learner call k (0-based) is a POLICY call iff (k + 1) % d == 0
+        (is_policy_call). A policy call runs the learn call of the run (plain, anchored or smoothed) and AgentGroup.apply_delayed(policy=
+        True): both nets step, every target follows. Every other call runs the TD-only call (AgentGroup.learn_set_split_td, with the
+        run's target_noise) and apply_delayed(policy=False): the critic alone steps, no target moves, nothing of the actor is computed,
+        read or written. The critic's Adam count is agents.step, the actors' own agents.actor_step. The smoothing counter and the
+        anchor's weight ramp go on counting learner calls; the anchor acts on policy calls only; actor_hold passes step size 0 on the
+        policy calls inside the hold. d = 1 trains bit for bit what None trains, through the new update entry. check_policy_delay says
+        what it needs (as target_noise). None: nothing is allocated, today's entry points run."""
         conf.refresh()
         self.levels = self.manoeuvres = self.lead = None
         self.residual = None
@@ -450,6 +507,14 @@ class VecTrainer:
                 import torch.distributed as _td
                 ranks = _td.get_world_size(group)
             self.target_noise = check_target_noise(target_noise, conf, shared_engine, rng, ranks, hparams, overlap_allreduce, shared_sets)
+        self.policy_delay = None
+        if policy_delay is not None:
+            ranks = 1
+            if group is not None:
+                import torch.distributed as _td
+                ranks = _td.get_world_size(group)
+            self.policy_delay = check_policy_delay(policy_delay, conf, shared_engine, rng, ranks, hparams, overlap_allreduce, shared_sets)
+        self.policy_call = True  # whether the last learner call moved the actors and the targets (always, without a delay)
         self.learner_calls = 0  # steps that passed the replay gate (what actor_hold counts)
         if train_disturb is not None:
             self.levels = check_train_disturb(conf, train_disturb, rng, group, fused_step, hparams)
@@ -503,6 +568,8 @@ class VecTrainer:
         self.agents = vec.AgentGroup(self.Mf if self.shared else n_agents, self.S, self.A, conf, self.device,
                                      seed=None if self.seeds else (conf.random_seed if init_seed is None else init_seed),
                                      hidd_mult=self.env.hidden_multiplier, seeds=self.seeds, seed_block=self.M)
+        if self.policy_delay is not None:  # the actors' own Adam count
+            self.agents.enable_policy_delay()
         self.d_hp = None
         if self.hp_rows is not None:  # the sweep's table: agent / set j of the batch is experiment (j // M) % E
             self.d_hp = vec.hparams_table(self.hp_rows, conf.ou_dt, self.device)
@@ -832,6 +899,9 @@ class VecTrainer:
             self._timed("learn", self._learn_batched, s, a, r, s2, self._fed_weights(ep, on_device="device"))
             # the 16-bit set learners answer a non-finite input / an fp16 overflow with an all-NaN slab: the guarded update then
             # leaves that weight set untouched and counts the event (nonfinite_updates()) instead of poisoning it for good
+            if self.policy_delay is not None:  # (fused3, checked) the critic alone on a skipped call; always guarded
+                self._timed("update", self.agents.apply_delayed, self.set_grads, self.policy_call)
+                return
             self._timed("update", self.agents.apply, self.set_grads, guarded=self.shared_engine in ("fused", "fused3"))
             return
         self._timed("learn", self.agents.learn, s, a, r, s2, self.set_mod, grads=self.grads, losses=self.losses)
@@ -864,7 +934,12 @@ class VecTrainer:
                 return
             if self.anchor is not None:  # (fused3, checked) the weight of this learner call: learner_calls counts it already
                 self.anchor_weight = self.anchor.weight_at(self.learner_calls - 1)
-            if self.target_noise is not None:  # (fused3, checked) the smoothed call; an anchor's arguments travel in it
+            self.policy_call = is_policy_call(self.learner_calls - 1, self.policy_delay)
+            if not self.policy_call:  # (fused3, checked) a skipped call of a delayed-policy run: the critic's gradients alone
+                self.agents.learn_set_split_td(s, a, r, s2, P * M, noise=self.target_noise, counter=self.learner_calls - 1,
+                                               grads=self.set_grads, losses=self.set_losses, agent_weight=aw, M=self.M, seed=self.seed,
+                                               d_seeds=None if self.seeds is None else self.env.d_seeds)
+            elif self.target_noise is not None:  # (fused3, checked) the smoothed call; an anchor's arguments travel in it
                 an = None if self.anchor is None else (self.anchor_gains, self.anchor_weight, self.anchor_loss)
                 self.agents.learn_set_split_smooth(s, a, r, s2, P * M, self.target_noise, self.learner_calls - 1, anchor=an,
                                                    grads=self.set_grads, losses=self.set_losses, agent_weight=aw, M=self.M, seed=self.seed,
@@ -875,7 +950,7 @@ class VecTrainer:
             else:
                 self.agents.learn_set_fused(s, a, r, s2, P * M, grads=self.set_grads, losses=self.set_losses, agent_weight=aw,
                                             split=self.shared_engine == "fused3")
-            if self.anchor is not None and self.learner_calls == 1:  # the first learner call's, kept on the device (anchor_loss_first)
+            if self.anchor is not None and self.learner_calls == (self.policy_delay or 1):  # the first (policy) call's, kept on the device
                 self.anchor_loss_first = self.anchor_loss.clone()
         else:
             if aw_dev is not None:
@@ -1076,8 +1151,9 @@ class VecTrainer:
         return self.all_ep_reward_lists, self.all_avg_reward_lists
 
     def anchor_losses(self):
-        """The last learner call's anchor loss per weight set, float32 [E * M] on the device: mean over the set's sampled rows of
-        w (mu - u*)^2, not times the weight (zeros before the first learner call)."""
+        """The last learner call's anchor loss per weight set -- under policy_delay the last POLICY call's: the skipped calls run no
+        anchored seed --, float32 [E * M] on the device: mean over the set's sampled rows of w (mu - u*)^2, not times the weight (zeros
+        before the first such call)."""
         if self.anchor is None:
             raise ValueError("anchor_losses needs VecTrainer(anchor=...)")
         return self.anchor_loss

@@ -878,6 +878,56 @@ class AgentGroup:
             call("avd_adam_polyak_guarded_f32" if guarded else "avd_adam_polyak_f32", *args, self.actor_lr, c.critic_lr, float(c.tau), *skipped,
                  stream_handle())
 
+    actor_step = None  # int32 [n_sets], the actor block's own Adam count: only a delayed-policy run has one (enable_policy_delay)
+
+    def enable_policy_delay(self):
+        """Give the group the actor block's own Adam count (``actor_step``, int32 [n_sets], zeros): what apply_delayed steps the actors
+        by while ``step`` goes on counting the critic's updates. Nothing else allocates it."""
+        self._no_hp("enable_policy_delay")
+        if self.actor_step is None:
+            self.actor_step = torch.zeros(self.n_sets, dtype=torch.int32, device=self.device)
+        return self.actor_step
+
+    def apply_delayed(self, grads, policy):
+        """apply(guarded=True) under TD3's delayed policy updates (avd_adam_polyak_delayed_f32). policy false, a skipped call: the
+        critic block takes its Adam step and ``step`` advances; no target moves (theta_t, stats_t) and nothing of the actor block is
+        read or written -- its part of ``grads`` may hold anything. policy true: both blocks step, the critic at ``step``, the actor
+        at ``actor_step`` (both advance), then the soft update of everything. A set with a non-finite gradient block takes no step,
+        has its counts put back and is counted in ``self.nonfinite_skipped``."""
+        self._no_hp("apply_delayed")
+        self.enable_policy_delay()
+        c = self.config
+        self.step += 1
+        if policy:
+            self.actor_step += 1
+        if getattr(self, "nonfinite_skipped", None) is None:
+            self.nonfinite_skipped = torch.zeros(1, dtype=torch.int32, device=self.device)
+        call("avd_adam_polyak_delayed_f32", self._layp, self.n_sets, ptr(self.theta), ptr(self.stats), ptr(self.theta_t), ptr(self.stats_t),
+             ptr(self.m), ptr(self.v), ptr(grads), ptr(self.step), ptr(self.actor_step), 1 if policy else 0, self.actor_lr, c.critic_lr,
+             float(c.tau), ptr(self.nonfinite_skipped), stream_handle())
+
+    def learn_set_split_td(self, s, a, r, s2, n_agents, noise=None, counter=0, grads=None, losses=None, agent_weight=None, M=None, seed=None,
+                           d_seeds=None):
+        """The TD-only call of the split set learner (avd_learn_set_split_td_f16x3), for the calls on which the actors do not move: the
+        critic block of the gradients and losses[:, 0] are learn_set_split's bit for bit -- with ``noise`` (a trainer.TargetNoise), the
+        smoothed call's for the same ``counter``, ``seed`` / ``d_seeds`` and M -- while nothing of the actor's half of the chain runs:
+        the actor block is all zero and losses[:, 1] is 0."""
+        self._no_hp("learn_set_split_td")
+        self._check_agent_major(s, a, r, s2, n_agents, agent_weight)
+        sigma, clip, key, seeds, E = 0.0, float("inf"), 0, None, 1
+        if noise is not None:
+            sigma, clip, key, seeds, E = self._smooth_key(noise, seed, d_seeds, "learn_set_split_td")
+        if M is None:
+            M = self.n_sets // E
+        if grads is None:
+            grads = torch.empty(self.n_sets, self.lay.theta_size, dtype=torch.float32, device=self.device)
+        ws = self._workspace("_fsplit_ws", "avd_learn_set_split_workspace", n_agents)
+        c = self.config
+        call("avd_learn_set_split_td_f16x3", self._layp, n_agents, self.n_sets, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
+             ptr(self.stats_t), ptr(s), ptr(a), ptr(r), ptr(s2), ptr(agent_weight), c.gamma, self.high, ptr(grads), ptr(losses), ptr(ws),
+             ws.numel(), sigma, clip, float(c.action_low), float(c.action_high), key, int(counter), seeds, E, int(M), stream_handle())
+        return grads
+
     def apply_intra(self, grads, P, M, weights=None, lead_skip=False, lo=0, hi=None, stream=None, advance=True):
         """intrafrl + gradients (workers/trainer.py:417-431) for platoons [lo, hi): every agent of a platoon steps with the (weighted)
         mean of the platoon's M gradient rows, averaged where it is consumed (avd_adam_polyak_intra_f32: one pass over the slab;

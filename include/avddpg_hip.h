@@ -258,6 +258,25 @@ int avd_adam_polyak_guarded_f32(const avd_mlp_layout* lay, int n_sets, float* th
                                 float* m, float* v, const float* grads, int32_t* step, float actor_lr, float critic_lr, double tau,
                                 int32_t* skipped, void* stream);
 
+/* avd_adam_polyak_guarded_f32 with TD3's delayed policy updates (tr --policy_delay): the two blocks of a set count their Adam
+ * iterations apart -- step[set] is the CRITIC block's count, actor_step [n_sets] (device int32) the ACTOR block's -- and `policy`
+ * (by value; nothing is read back) says which kind of call this is. Both counts are advanced by the caller BEFORE a call that uses them.
+ *   policy == 0, a skipped call: the critic block takes its Adam step at iteration step[set]. NO target moves -- not the critic's,
+ *     not the actor's, not the BN statistics' (stats_t): targets follow only on policy calls. The actor block is neither read nor
+ *     written: weights, moments, target and its part of `grads`, which may hold anything (NaN included). The launch covers the
+ *     critic block's float4 groups only; actor_step is not read.
+ *   policy != 0, a policy call: the critic block steps at step[set], the actor block at actor_step[set], then the soft update of both
+ *     blocks and of the statistics. Element arithmetic and step sizes are avd_adam_polyak_guarded_f32's: with actor_step == step
+ *     every output bit is that call's (tested).
+ * Always guarded: a non-finite head of the critic block -- on a policy call also of the actor block -- leaves the set untouched, puts
+ * back step[set] (on a policy call actor_step[set] too) by one and increments *skipped (optional). On a skipped call the actor block's
+ * head is not looked at.
+ * Refused on the host before any launch (AVD_E_INVALID): a null pointer (skipped excepted), n_sets < 1 or > 65535, a layout whose
+ * blocks are not 4-float aligned or that lacks one of them, a negative or non-finite step size, tau outside (0, 1]. */
+int avd_adam_polyak_delayed_f32(const avd_mlp_layout* lay, int n_sets, float* theta, float* stats, float* theta_t, float* stats_t,
+                                float* m, float* v, const float* grads, int32_t* step, int32_t* actor_step, int policy, float actor_lr,
+                                float critic_lr, double tau, int32_t* skipped, void* stream);
+
 /* Fused form of avd_learn_f32 + avd_adam_polyak_f32 for one weight set per agent (reference nofrl:
  * workers/trainer.py:325-356 learn, apply_gradients x2, update_target per agent): Adam and the soft update are
  * applied where each gradient is produced, so no gradient slab is written or read back.
@@ -616,6 +635,26 @@ int avd_learn_set_split_smooth_f16x3(const avd_mlp_layout* lay, int n_agents, in
                                      void* workspace, size_t workspace_bytes, const float* gains, int M, int model_a, float lo, float hi,
                                      float weight, float* anchor_loss, float sigma, float noise_clip, uint64_t seed, uint64_t counter,
                                      const uint64_t* d_seeds, int E, void* stream);
+
+/* The TD-only learn call of the split set learner, for the calls of a delayed-policy run on which the actor does not move
+ * (avd_adam_polyak_delayed_f32 with policy == 0): the critic block of `grads` and the critic loss, and nothing of the actor's half of
+ * the chain -- no actor forward, no critic(s, mu), no action gradient, no actor backward pass. The chain: front, prep, the target
+ * actor's head, the smoothing launch of avd_learn_set_split_smooth_f16x3 (sigma, noise_clip, lo, hi, seed, counter, d_seeds, E, M as
+ * there; sigma == 0: no launch), the target critic's head, the critic head in its loss-only mode (HEAD_BOTH up to and including its
+ * branch A), the critic's three backward kernels (dw, dx and dxa: the action layer's parameter sums are the critic's own) and the
+ * critic block's finalize.
+ *   grads : the critic block of every set is avd_learn_set_split_critic's bit for bit (smoothed: the critic block of
+ *           avd_learn_set_split_smooth_f16x3 with the same key and counter); the actor block is all zero;
+ *   losses: [n_sets][2], losses[j][0] the critic loss as there; losses[j][1] compares equal to 0 (finalize negates the zero sum: the
+ *           sign bit is set, the value is -0.0f).
+ * A non-finite input stays loud: an all-NaN critic block. Workspace: avd_learn_set_split_workspace's; it and the slab may hold
+ * anything at entry. Refused on the host before any HIP call: everything avd_learn_set_split_critic refuses and everything the
+ * smoothing arguments are refused for in avd_learn_set_split_smooth_f16x3. There is no anchored and no per-set-gamma form. */
+int avd_learn_set_split_td_f16x3(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
+                                 const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
+                                 const float* s2, const float* agent_weight, float gamma, float high, float* grads, float* losses,
+                                 void* workspace, size_t workspace_bytes, float sigma, float noise_clip, float lo, float hi, uint64_t seed,
+                                 uint64_t counter, const uint64_t* d_seeds, int E, int M, void* stream);
 
 /* Deprecated alias of avd_learn_set_split_f16x3 (same arguments, same results). */
 int avd_learn_set_split_bf16x3(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
