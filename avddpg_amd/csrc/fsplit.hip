@@ -1862,6 +1862,22 @@ static int check_shape(const avd_mlp_layout* L, int n_agents, int n_sets, const 
 //   (r15_fused_launches_static.txt). The seams are workgroup barriers, not the agent-scope release / acquire pairs first planned: no
 //   dependence crosses a workgroup, and an agent-scope pair costs more per seam (L2 write-back, L1 invalidate) than the boundary it replaces.
 enum Phase { PH_CRITIC = 1, PH_ACTOR = 2, PH_BOTH = 3, PH_TD = 4 };  // PH_TD: the TD-only call (alone, never or'ed with the others)
+// What an entry point of the split learner asks for ("host side"). Every avd_learn_set_split_* wrapper makes one
+// (AVD_SPLIT_CALL), attaches its variant's parts and hands it to split_run: the one place with the checks, the plan and the dispatch on S.
+struct SplitCall {
+    int phases;       // a Phase
+    const char* who;  // the entry point, for messages
+    const avd_mlp_layout* lay;
+    int n_agents, n_sets;
+    const float *theta, *stats, *theta_t, *stats_t, *s, *a, *r, *s2, *aw;  // (the actor phase alone: theta, stats and s only)
+    float gamma, high, *grads, *losses;
+    unsigned char* ws;
+    size_t ws_bytes;
+    hipStream_t st;
+    const AnchorArgs* an;   // the anchored seed's own arguments, or null: actor_seed_kernel
+    const SmoothArgs* smo;  // target policy smoothing's, or null; sigma 0: checked like any other, and no launch
+    const HpRef* hp;        // a sweep's table (each set's gamma in OUT_TD's epilogue), or null: gamma
+};
 #ifdef AVD_STAMP
 // Diagnostic build with -DAVD_STAMP: the heads' s_memtime stamps (head_kernel: HSTAMP; workgroup 16, per wave the cycles of 0 unit start,
 // 1 feature tiles, 2 epilogue, 3 start-up) land in host-visible memory, one region of 128 words per net, and AVD_FSPLIT_STAMPS=1 prints
@@ -1882,13 +1898,18 @@ static void print_head_stamps(hipStream_t st) {
         }
 }
 #endif
-template <int S, class... H>
-static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, const float* theta, const float* stats, const float* theta_t,
-               const float* stats_t, const float* s, const float* a, const float* r, const float* s2, const float* aw, float gamma,
-               float high, float* grads, float* losses, unsigned char* ws, const Plan& pl, hipStream_t st, const AnchorArgs* an,
-               const SmoothArgs* smo, H... hp) {
+// One call, checked and planned (split_run). Every kernel-argument record of the chain is built ONCE, each by its own function from the
+// call and the plan (FwdArgs: the heads' and the seed's, BwdArgs: dw's and dx's), and then issued in one of two forms: FwdArgs and BwdArgs
+// whole (two launches), or member by member with the variants' launches between. Same records, so the same bits.
+template <int S>
+static int run(const SplitCall& c, const Plan& pl) {
+    const avd_mlp_layout& L = *c.lay;
+    const int n_agents = c.n_agents, n_sets = c.n_sets;
+    const float *theta = c.theta, *theta_t = c.theta_t, *s = c.s, *a = c.a;
+    unsigned char* const ws = c.ws;
+    const hipStream_t st = c.st;
     PrepArgs pa;
-    pa.L = L, pa.S = S, pa.theta = theta, pa.stats = stats, pa.theta_t = theta_t, pa.stats_t = stats_t;
+    pa.L = L, pa.S = S, pa.theta = theta, pa.stats = c.stats, pa.theta_t = theta_t, pa.stats_t = c.stats_t;
     pa.wap = (unsigned*)(ws + pl.wap), pa.bad = (int*)(ws + pl.bad), pa.smax = (unsigned*)(ws + pl.smax);
     pa.fflag = (unsigned*)(ws + pl.fflag), pa.n_fflag = pl.n_fflag;
     NetP net[4];
@@ -1899,11 +1920,9 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
         pa.Wchi[i] = i < 2 ? (f16*)(ws + pl.Wchi[i]) : nullptr, pa.Wclo[i] = i < 2 ? (f16*)(ws + pl.Wclo[i]) : nullptr;
         NetP& n = net[i];
         n.th = (target ? theta_t : theta) + (critic ? L.actor_size : 0), n.th_stride = L.theta_size;
-        n.Whi = pa.Whi[i], n.Wlo = pa.Wlo[i], n.Wchi = pa.Wchi[i], n.Wclo = pa.Wclo[i], n.wf1h = pa.wf1h[i], n.vec = pa.vec[i];
-        n.wap = pa.wap;
+        n.Whi = pa.Whi[i], n.Wlo = pa.Wlo[i], n.Wchi = pa.Wchi[i], n.Wclo = pa.Wclo[i], n.wf1h = pa.wf1h[i], n.vec = pa.vec[i], n.wap = pa.wap;
     }
-    const int P = n_agents / n_sets;
-    const float inv_n = 1.0f / ((float)P * TILE);
+    const float inv_n = 1.0f / ((float)(n_agents / n_sets) * TILE);
     const long nrows = (long)n_agents * TILE;
     f16x8 *xfs = (f16x8*)(ws + pl.xfs), *xfs2 = (f16x8*)(ws + pl.xfs2);
     int* bad = (int*)(ws + pl.bad);
@@ -1912,37 +1931,52 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
     unsigned *sm = (unsigned*)(ws + pl.sm), *sma = (unsigned*)(ws + pl.sma);
     auto F = [&](size_t off) { return (float*)(ws + off); };
     const dim3 grid(pl.grid), block(NT);
-    HeadArgs h;
-    h.n_agents = n_agents, h.n_sets = n_sets, h.gamma = gamma, h.high = high, h.inv_n = inv_n, h.aw = aw, h.sm = sm, h.g3 = g3, h.dmu = dmu;
-    h.act2 = nullptr, h.part_s2 = nullptr, h.stamp = nullptr, h.bad = bad, h.part_m = nullptr, h.tz = F(pl.tz), h.abl = 0;
-    if (const char* e = AVD_DIAG_ENV("FSPLIT_ABL")) h.abl = atoi(e);
-    auto head_args = [&](int ni, const f16x8* x, const float* act, const float* rr, const float* yin, float* out, float* part_s) {
-        h.net = net[ni], h.xf = x, h.act = act, h.r = rr, h.yin = yin, h.out = out, h.part_s = part_s;
+    const bool td = c.phases == PH_TD;
+    const int abl = AVD_DIAG_ENV("FSPLIT_ABL") ? atoi(AVD_DIAG_ENV("FSPLIT_ABL")) : 0;
+    static unsigned long long* d_stamp = nullptr;  // dw / dx: the stamped diagnostic build only
+#ifdef AVD_STAMP
+    if (!d_stamp) (void)hipMalloc(&d_stamp, 128 * 8);
+#endif
+    // the head of net ni: its input rows, what rides with them, its per-row result and the masks it writes (the modes that write any)
+    const auto head_args = [&](int ni, const f16x8* x, const float* act, const float* rr, const float* yin, float* out, unsigned* masks) {
+        HeadArgs h;
+        h.net = net[ni], h.n_agents = n_agents, h.n_sets = n_sets, h.xf = x, h.act = act, h.act2 = nullptr, h.r = rr, h.yin = yin, h.aw = c.aw;
+        h.out = out, h.sm = masks, h.g3 = g3, h.dmu = dmu, h.part_s = h.part_s2 = h.part_m = nullptr, h.tz = F(pl.tz);
+        h.gamma = c.gamma, h.high = c.high, h.inv_n = inv_n, h.bad = bad, h.abl = abl, h.stamp = nullptr;
 #ifdef AVD_STAMP
         h.stamp = head_stamps() + 128 * ni;  // one region per head launch (net index): read back below
 #endif
         return h;
     };
-    auto head = [&](auto kern, int ni, const f16x8* x, const float* act, const float* rr, const float* yin, float* out, float* part_s,
-                    auto... extra) {
-        hipLaunchKernelGGL(kern, grid, block, 0, st, head_args(ni, x, act, rr, yin, out, part_s), extra...);
+    FwdArgs fw;
+    fw.tanh_t = head_args(2, xfs2, nullptr, nullptr, nullptr, a2, sm);
+    fw.td = head_args(3, xfs2, a2, c.r, nullptr, y, sm);
+    fw.tanh_save = head_args(0, xfs, nullptr, nullptr, nullptr, mu, sma);  // (the actor's masks: written before the critic's are used)
+    fw.both = head_args(1, xfs, a, nullptr, y, nullptr, sm);
+    // critic(s, a) and critic(s, mu) in one head (HEAD_BOTH); the TD-only call's HEAD_CRITIC has no mu input
+    fw.both.act2 = td ? nullptr : mu, fw.both.part_s = F(pl.partHs[1]), fw.both.part_s2 = F(pl.partHs[2]), fw.both.part_m = F(pl.partM[1]);
+    SeedArgs& sd = fw.seed;
+    sd.n_agents = n_agents, sd.n_sets = n_sets, sd.dmu = dmu, sd.tz = F(pl.tz), sd.high = c.high, sd.g3 = g3a, sd.part_m = F(pl.partM[0]),
+    sd.part_s = F(pl.partHs[0]);
+    // the backward kernels of net ni (1 critic, 0 actor) on that net's masks and row factor: the partials are the net's own
+    const auto dw_args = [&](int ni, const float* act, const unsigned* masks, const float* row) {
+        DwArgs d;
+        d.net = net[ni], d.n_agents = n_agents, d.n_sets = n_sets, d.x = s, d.act = act, d.g3 = row, d.part_m = F(pl.partM[ni]), d.sm = masks;
+        d.partG = F(pl.partG[ni]), d.abl = abl, d.stamp = d_stamp;
+        return d;
     };
-    DwArgs dw;
-    dw.n_agents = n_agents, dw.n_sets = n_sets, dw.sm = sm, dw.g3 = g3, dw.x = s, dw.stamp = nullptr, dw.abl = 0;
-    if (const char* e = AVD_DIAG_ENV("FSPLIT_ABL")) dw.abl = atoi(e);
-#ifdef AVD_STAMP
-    static unsigned long long* d_stamp = nullptr;
-    if (!d_stamp) (void)hipMalloc(&d_stamp, 128 * 8);
-    dw.stamp = d_stamp;
-#endif
-    DxArgs dx;
-    dx.n_agents = n_agents, dx.n_sets = n_sets, dx.sm = sm, dx.g3 = g3, dx.xfh = xfs, dx.stamp = nullptr, dx.L_cWa = dx.L_cba = 0;
-    dx.abl = dw.abl;
-#ifdef AVD_STAMP
-    dx.stamp = d_stamp;
-#endif
+    const auto dx_args = [&](int ni, const float* act, const unsigned* masks, const float* row, bool action_layer) {
+        DxArgs d;
+        d.net = net[ni], d.n_agents = n_agents, d.n_sets = n_sets, d.xfh = xfs, d.act = act, d.g3 = row, d.part_m = F(pl.partM[ni]), d.sm = masks;
+        d.L_cWa = action_layer ? L.cWa : 0, d.L_cba = action_layer ? L.cba : 0;  // (dxa_kernel alone reads them)
+        d.partV = F(pl.partV[ni]), d.abl = abl, d.stamp = d_stamp;
+        return d;
+    };
+    BwdArgs bw;
+    bw.dw_c = dw_args(1, a, sm, g3), bw.dx_c = dx_args(1, a, sm, g3, false), bw.dxa = dx_args(1, a, sm, g3, true);
+    bw.dw_a = dw_args(0, nullptr, sma, g3a), bw.dx_a = dx_args(0, nullptr, sma, g3a, false);
     FinArgs fa;
-    fa.L = L, fa.n_sets = n_sets, fa.J = pl.J, fa.S = S, fa.nrh = 1, fa.theta = theta, fa.stats = stats, fa.grads = grads, fa.losses = losses;
+    fa.L = L, fa.n_sets = n_sets, fa.J = pl.J, fa.S = S, fa.nrh = 1, fa.theta = theta, fa.stats = c.stats, fa.grads = c.grads, fa.losses = c.losses;
     fa.inv_n = inv_n, fa.partLa = F(pl.partHs[2]), fa.bad = bad;
     for (int i = 0; i < 2; ++i)
         fa.partH[i] = nullptr, fa.partHs[i] = F(pl.partHs[i]), fa.partU[i] = nullptr, fa.partV[i] = F(pl.partV[i]),
@@ -1952,111 +1986,73 @@ static int run(int phases, const avd_mlp_layout& L, int n_agents, int n_sets, co
     // launches per call where there were 15). Every other form keeps the stand-alone launches: a phase alone, the smoothed call (a
     // launch of its own sits between OUT_TANH and OUT_TD), the anchored call (its own seed launch), a sweep (OUT_TD's HP instantiation), the
     // stamped diagnostic build -- and, in the diagnostic build, AVD_FSPLIT_UNFUSED=1 for A/B runs of the two forms of one library.
-    bool fused = phases == PH_BOTH && !an && !smo && sizeof...(H) == 0;
+    const bool smooth = c.smo && c.smo->sigma != 0.f;  // sigma 0: no launch, the call IS the un-smoothed one
+    bool fused = c.phases == PH_BOTH && !c.an && !smooth && !c.hp;
 #ifdef AVD_STAMP
     fused = false;
 #endif
     if (AVD_DIAG_ENV("FSPLIT_UNFUSED")) fused = false;
-    SeedArgs sd;
-    sd.n_agents = n_agents, sd.n_sets = n_sets, sd.dmu = dmu, sd.tz = F(pl.tz), sd.high = high, sd.g3 = g3a, sd.part_m = F(pl.partM[0]),
-    sd.part_s = F(pl.partHs[0]);
-    if (phases & (PH_CRITIC | PH_TD)) {
+    if (c.phases & (PH_CRITIC | PH_TD)) {
         // (r05, measured and not kept: the preparation chain -- three small dependent launches over 1.5 MB of weights, ~30 us -- on a side
         //  stream beside the input packing, forked and joined by events: 1969-1978 us per learn against 1957-1961 serial on the same
         //  box; the fork / join costs more than the overlap of two sub-30-us stages returns. r09: the same overlap without a fork --
         //  the independent pieces are roles of ONE launch, front_kernel, which also does what two memsets did)
         FrontArgs fr;
-        fr.pa = pa, fr.grads = grads, fr.n_grads = (long)n_sets * L.theta_size, fr.n_sets = n_sets;
-        fr.pk.x[0] = s, fr.pk.extra[0] = a, fr.pk.outh[0] = xfs, fr.pk.x[1] = s2, fr.pk.extra[1] = r, fr.pk.outh[1] = xfs2, fr.pk.rows = nrows;
+        fr.pa = pa, fr.grads = c.grads, fr.n_grads = (long)n_sets * L.theta_size, fr.n_sets = n_sets;
+        fr.pk.x[0] = s, fr.pk.extra[0] = a, fr.pk.outh[0] = xfs, fr.pk.x[1] = c.s2, fr.pk.extra[1] = c.r, fr.pk.outh[1] = xfs2, fr.pk.rows = nrows;
         fr.n_scale = 4 * n_sets * SCALE_SLICES, fr.n_prep1 = pl.n_prep1, fr.n_pack = pl.n_pack;
         fr.n_zero = (int)((fr.n_grads + ZERO_PER_BLOCK - 1) / ZERO_PER_BLOCK);
         hipLaunchKernelGGL(front_kernel<S>, dim3((unsigned)(fr.n_scale + fr.n_prep1 + fr.n_zero + 2 * fr.n_pack)), dim3(256), 0, st, fr);
         hipLaunchKernelGGL(prep_kernel, dim3(H2, 4, n_sets), dim3(320), 0, st, pa);
     }
+    const auto launch = [&](auto kern, const auto&... args) { hipLaunchKernelGGL(kern, grid, block, 0, st, args...); };
     if (fused) {
-        FwdArgs fw;
-        fw.tanh_t = head_args(2, xfs2, nullptr, nullptr, nullptr, a2, nullptr);
-        fw.td = head_args(3, xfs2, a2, r, nullptr, y, nullptr);
-        h.sm = sma;
-        fw.tanh_save = head_args(0, xfs, nullptr, nullptr, nullptr, mu, nullptr);
-        h.sm = sm;
-        h.act2 = mu, h.part_s2 = F(pl.partHs[2]), h.part_m = F(pl.partM[1]);
-        fw.both = head_args(1, xfs, a, nullptr, y, nullptr, F(pl.partHs[1]));
-        fw.seed = sd;
-        hipLaunchKernelGGL(forward_kernel<S>, grid, block, 0, st, fw);
-        BwdArgs bw;
-        dw.net = net[1], dw.act = a, dw.partG = F(pl.partG[1]), dw.part_m = F(pl.partM[1]);
-        bw.dw_c = dw;
-        dx.net = net[1], dx.partV = F(pl.partV[1]), dx.act = a, dx.part_m = F(pl.partM[1]);
-        bw.dx_c = dx;
-        dx.L_cWa = L.cWa, dx.L_cba = L.cba;
-        bw.dxa = dx;
-        dw.sm = sma, dw.g3 = g3a, dw.net = net[0], dw.act = nullptr, dw.partG = F(pl.partG[0]), dw.part_m = F(pl.partM[0]);
-        bw.dw_a = dw;
-        dx.sm = sma, dx.g3 = g3a, dx.net = net[0], dx.partV = F(pl.partV[0]), dx.act = nullptr, dx.part_m = F(pl.partM[0]), dx.L_cWa = dx.L_cba = 0;
-        bw.dx_a = dx;
-        hipLaunchKernelGGL(backward_kernel<S>, grid, block, 0, st, bw);
+        launch(forward_kernel<S>, fw);
+        launch(backward_kernel<S>, bw);
         launch_finalize(fa, st, 0, 2);
         return check_launch("avd_learn_set_split");
     }
     // The TD-only call (avd_learn_set_split_td_f16x3) is the critic phase without what only the actor phase reads: no mu pass
     // (OUT_TANH_SAVE), and the critic head in its loss-only mode (HEAD_CRITIC: no B sweeps, no d mu). dxa stays: the action layer's
     // parameter sums are the critic's own gradients. One launch sequence serves both.
-    const bool td = phases == PH_TD;
-    if (phases & (PH_CRITIC | PH_TD)) {
+    if (c.phases & (PH_CRITIC | PH_TD)) {
         // 1-2: targets
-        head(head_kernel<S, ActorS, OUT_TANH>, 2, xfs2, nullptr, nullptr, nullptr, a2, nullptr);
-        if (smo) {  // target policy smoothing: a2 in place, between its writer and its only reader (csrc/smooth.hip)
-            SmoothArgs q = *smo;
+        launch(head_kernel<S, ActorS, OUT_TANH>, fw.tanh_t);
+        if (smooth) {  // target policy smoothing: a2 in place, between its writer and its only reader (csrc/smooth.hip)
+            SmoothArgs q = *c.smo;
             q.n_agents = n_agents, q.a2 = a2;
             launch_target_smooth(q, st);
         }
-        if constexpr (sizeof...(H) > 0)  // a sweep: each set's gamma (avd_learn_set_split_hp_f16x3)
-            head(head_kernel<S, CriticS, OUT_TD, true, H...>, 3, xfs2, a2, r, nullptr, y, nullptr, hp...);
-        else
-            head(head_kernel<S, CriticS, OUT_TD>, 3, xfs2, a2, r, nullptr, y, nullptr);
+        if (c.hp) launch(head_kernel<S, CriticS, OUT_TD, true, HpRef>, fw.td, *c.hp);  // a sweep: each set's gamma (avd_learn_set_split_hp_f16x3)
+        else launch(head_kernel<S, CriticS, OUT_TD>, fw.td);
         // 3: mu -- and the actor's relu masks + tanh(z) for its backward pass (no second actor forward: r03's HEAD_ACTOR)
-        if (!td) {
-            h.sm = sma;
-            head(head_kernel<S, ActorS, OUT_TANH_SAVE>, 0, xfs, nullptr, nullptr, nullptr, mu, nullptr);
-            h.sm = sm;
-        }
+        if (!td) launch(head_kernel<S, ActorS, OUT_TANH_SAVE>, fw.tanh_save);
         // 4-7: critic loss and gradients; critic(s, mu) and the action gradient ride in the same launch (HEAD_BOTH; TD-only: neither)
-        h.act2 = td ? nullptr : mu, h.part_s2 = F(pl.partHs[2]), h.part_m = F(pl.partM[1]);
-        if (td)
-            head(head_kernel<S, CriticS, HEAD_CRITIC>, 1, xfs, a, nullptr, y, nullptr, F(pl.partHs[1]));
-        else
-            head(head_kernel<S, CriticS, HEAD_BOTH>, 1, xfs, a, nullptr, y, nullptr, F(pl.partHs[1]));
-        dw.net = net[1], dw.act = a, dw.partG = F(pl.partG[1]), dw.part_m = F(pl.partM[1]);
-        hipLaunchKernelGGL((dw_kernel<S, CriticS>), grid, block, 0, st, dw);
-        dx.net = net[1], dx.partV = F(pl.partV[1]), dx.act = a, dx.part_m = F(pl.partM[1]);
-        hipLaunchKernelGGL((dx_kernel<S, CriticS>), grid, block, 0, st, dx);
-        dx.L_cWa = L.cWa, dx.L_cba = L.cba;
-        hipLaunchKernelGGL((dxa_kernel<S>), grid, block, 0, st, dx);
+        if (td) launch(head_kernel<S, CriticS, HEAD_CRITIC>, fw.both);
+        else launch(head_kernel<S, CriticS, HEAD_BOTH>, fw.both);
+        launch(dw_kernel<S, CriticS>, bw.dw_c);
+        launch(dx_kernel<S, CriticS>, bw.dx_c);
+        launch(dxa_kernel<S>, bw.dxa);
         // 8: the critic block of the slab (+ both losses: the actor loss is the mean of q(s, mu), summed by HEAD_BOTH) -- when the
         // caller asked for this phase alone; the single call finalizes both blocks together at its end (three launches, not six)
         // (TD-only: the actor block stays the zeros of the front launch)
-        if (phases == PH_CRITIC || td) launch_finalize(fa, st, 1, 1);
+        if (c.phases == PH_CRITIC || td) launch_finalize(fa, st, 1, 1);
     }
-    if (phases & PH_ACTOR) {
+    if (c.phases & PH_ACTOR) {
         // 9-11: actor gradients: the seed from d mu and the stored tanh(z) (into g3a, as in the fused launches), then dw / dx on the stored
         // (unsigned) masks
-        if (an) {  // the anchored seed in actor_seed_kernel's place, then the anchor loss's reducer (one wave per set)
-            AnchorArgs q = *an;
-            q.n_agents = n_agents, q.n_sets = n_sets, q.S = S, q.J = pl.J, q.dmu = dmu, q.tz = sd.tz, q.high = high, q.g3 = g3a;
-            q.part_m = sd.part_m, q.part_s = sd.part_s, q.mu = mu, q.s = s, q.aw = aw, q.inv_n = inv_n, q.c = 2.f * an->weight * inv_n;
+        if (c.an) {  // the anchored seed in actor_seed_kernel's place, then the anchor loss's reducer (one wave per set)
+            AnchorArgs q = *c.an;
+            q.n_agents = n_agents, q.n_sets = n_sets, q.S = S, q.J = pl.J, q.dmu = dmu, q.tz = sd.tz, q.high = c.high, q.g3 = g3a;
+            q.part_m = sd.part_m, q.part_s = sd.part_s, q.mu = mu, q.s = s, q.aw = c.aw, q.inv_n = inv_n, q.c = 2.f * c.an->weight * inv_n;
             q.bad = bad;
             launch_anchor_seed(q, pl.grid, st);  // (csrc/anchor.hip)
         } else
-            hipLaunchKernelGGL(actor_seed_kernel, grid, block, 0, st, sd);
-        dw.sm = sma, dx.sm = sma, dw.g3 = g3a, dx.g3 = g3a;
-        dw.net = net[0], dw.act = nullptr, dw.partG = F(pl.partG[0]), dw.part_m = F(pl.partM[0]);
-        hipLaunchKernelGGL((dw_kernel<S, ActorS>), grid, block, 0, st, dw);
-        dx.net = net[0], dx.partV = F(pl.partV[0]), dx.act = nullptr, dx.part_m = F(pl.partM[0]), dx.L_cWa = dx.L_cba = 0;
-        hipLaunchKernelGGL((dx_kernel<S, ActorS>), grid, block, 0, st, dx);
+            launch(actor_seed_kernel, sd);
+        launch(dw_kernel<S, ActorS>, bw.dw_a);
+        launch(dx_kernel<S, ActorS>, bw.dx_a);
         // 12: the actor block of the slab (the single call: both blocks)
-        if (phases == PH_ACTOR) launch_finalize(fa, st, 0, 1);
-        else launch_finalize(fa, st, 0, 2);
+        launch_finalize(fa, st, 0, c.phases == PH_ACTOR ? 1 : 2);
     }
 #ifdef AVD_STAMP
     if (AVD_DIAG_ENV("FSPLIT_STAMPS")) print_head_stamps(st);
@@ -2108,47 +2104,67 @@ extern "C" int avd_learn_set_split_workspace(const avd_mlp_layout* lay, int n_ag
     return AVD_OK;
 }
 
-template <class... H>
-static int split_entry(int phases, const char* who, const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
-                       const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r, const float* s2,
-                       const float* agent_weight, float gamma, float high, float* grads, float* losses, void* workspace,
-                       size_t workspace_bytes, void* stream, const AnchorArgs* an, const SmoothArgs* smo, H... hp) {
-    int rc = fsplit::check_shape(lay, n_agents, n_sets, who);
+// StepCall's counterpart (csrc/env.hip): SplitCall c of the wrapper it stands in, from the parameter names that the signatures share.
+// gamma_: the entry's gamma, or the sweep's 0 (its kernel reads each set's own).
+#define AVD_SPLIT_CALL(c, phases_, who_, gamma_)                                                                                           \
+    fsplit::SplitCall c = {};                                                                                                                \
+    c.phases = phases_, c.who = who_, c.lay = lay, c.n_agents = n_agents, c.n_sets = n_sets, c.theta = theta, c.stats = stats;               \
+    c.theta_t = theta_t, c.stats_t = stats_t, c.s = s, c.a = a, c.r = r, c.s2 = s2, c.aw = agent_weight, c.gamma = gamma_, c.high = high;    \
+    c.grads = grads, c.losses = losses, c.ws = (unsigned char*)workspace, c.ws_bytes = workspace_bytes, c.st = (hipStream_t)stream
+
+// The parts of a call, as the wrappers gather them from their arguments (anchor_args, smooth_args) and as split_run checks them once the
+// shape has passed: the refusals keep their order -- shape, anchor, smoothing, null pointers, workspace size -- all before a HIP call.
+static AnchorArgs anchor_args(const float* gains, int M, int model_a, float lo, float hi, float weight, float* anchor_loss) {
+    AnchorArgs an{};
+    an.gains = gains, an.M = M, an.model_a = model_a, an.lo = lo, an.hi = hi, an.weight = weight, an.anchor_loss = anchor_loss;
+    return an;
+}
+static int check_anchor_args(const char* who, int n_sets, const AnchorArgs& an) {
+    AVD_REQUIRE(an.gains && an.anchor_loss, "%s: null gains / anchor_loss", who);
+    AVD_REQUIRE(an.M >= 1 && n_sets % an.M == 0, "%s: n_sets=%d M=%d (n_sets must be a multiple of M >= 1)", who, n_sets, an.M);
+    unsigned wbits;  // (bit tests: this file is built with -fno-honor-nans) sign clear or -0, exponent not all ones
+    memcpy(&wbits, &an.weight, sizeof wbits);
+    AVD_REQUIRE((wbits & 0x7f800000u) != 0x7f800000u && (!(wbits >> 31) || wbits == 0x80000000u), "%s: weight=%g (must be finite and >= 0)",
+                who, (double)an.weight);
+    AVD_REQUIRE(an.lo <= an.hi, "%s: lo=%g > hi=%g", who, (double)an.lo, (double)an.hi);
+    return AVD_OK;
+}
+// what the smoothed and the TD-only entries share: the smoothing arguments, checked for sigma 0 too (no launch then: fsplit::run) --
+// the 16-byte workspace check with them, for those two entries alone
+static SmoothArgs smooth_args(int M, int E, float sigma, float clip, float lo, float hi, uint64_t seed, uint64_t counter, const uint64_t* seeds) {
+    SmoothArgs sm{};
+    sm.M = M, sm.E = E, sm.sigma = sigma, sm.clip = clip, sm.lo = lo, sm.hi = hi, sm.seed = seed, sm.counter = counter, sm.seeds = seeds;
+    return sm;
+}
+static int check_smooth_args(const fsplit::SplitCall& c) {
+    const SmoothArgs& sm = *c.smo;
+    if (const int rc = check_smooth(c.who, sm)) return rc;  // (csrc/smooth.hip: built without -fno-honor-nans: plain NaN comparisons)
+    AVD_REQUIRE(c.n_sets % ((long)sm.E * sm.M) == 0, "%s: n_sets=%d M=%d E=%d (n_sets must be a multiple of E x M)", c.who, c.n_sets, sm.M, sm.E);
+    AVD_REQUIRE(((uintptr_t)c.ws & 15) == 0, "%s: the workspace must be 16-byte aligned", c.who);
+    return AVD_OK;
+}
+
+// Every check of a call, once and in one order; then the plan, and the chain for the layout's S
+static int split_run(const fsplit::SplitCall& c) {
+    int rc = fsplit::check_shape(c.lay, c.n_agents, c.n_sets, c.who);
+    if (!rc && c.an) rc = check_anchor_args(c.who, c.n_sets, *c.an);
+    if (!rc && c.smo) rc = check_smooth_args(c);
     if (rc) return rc;
-    const bool cr = phases & (fsplit::PH_CRITIC | fsplit::PH_TD);
-    AVD_REQUIRE(theta && stats && s && grads && workspace && (!cr || (theta_t && stats_t && a && r && s2)), "%s: null pointer", who);
-    const fsplit::Plan pl = fsplit::make_plan(n_agents, n_sets);
-    AVD_REQUIRE(workspace_bytes >= pl.total, "%s: workspace %zu B < %zu B", who, workspace_bytes, pl.total);
+    const bool cr = c.phases & (fsplit::PH_CRITIC | fsplit::PH_TD);
+    AVD_REQUIRE(c.theta && c.stats && c.s && c.grads && c.ws && (!cr || (c.theta_t && c.stats_t && c.a && c.r && c.s2)), "%s: null pointer", c.who);
+    const fsplit::Plan pl = fsplit::make_plan(c.n_agents, c.n_sets);
+    AVD_REQUIRE(c.ws_bytes >= pl.total, "%s: workspace %zu B < %zu B", c.who, c.ws_bytes, pl.total);
     // (padding floats of the slab are never written by finalize: the critic phase's front launch zeroes the slab, like every other
     //  gradient producer keeps them zero)
-    if (lay->S == 4)
-        return fsplit::run<4>(phases, *lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2, agent_weight, gamma, high, grads,
-                              losses, (unsigned char*)workspace, pl, (hipStream_t)stream, an, smo, hp...);
-    return fsplit::run<3>(phases, *lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2, agent_weight, gamma, high, grads, losses,
-                          (unsigned char*)workspace, pl, (hipStream_t)stream, an, smo, hp...);
+    return c.lay->S == 4 ? fsplit::run<4>(c, pl) : fsplit::run<3>(c, pl);
 }
 
 extern "C" int avd_learn_set_split_f16x3(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
                                           const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
                                           const float* s2, const float* agent_weight, float gamma, float high, float* grads,
                                           float* losses, void* workspace, size_t workspace_bytes, void* stream) {
-    return split_entry(fsplit::PH_BOTH, "avd_learn_set_split_f16x3", lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2,
-                       agent_weight, gamma, high, grads, losses, workspace, workspace_bytes, stream, nullptr, nullptr);
-}
-
-// the anchor's own arguments, checked (everything refused here is refused before a HIP call) and gathered
-static int anchor_args(const char* who, int n_sets, const float* gains, int M, int model_a, float lo, float hi, float weight, float* anchor_loss,
-                       AnchorArgs& an) {
-    AVD_REQUIRE(gains && anchor_loss, "%s: null gains / anchor_loss", who);
-    AVD_REQUIRE(M >= 1 && n_sets % M == 0, "%s: n_sets=%d M=%d (n_sets must be a multiple of M >= 1)", who, n_sets, M);
-    unsigned wbits;  // (bit tests: this file is built with -fno-honor-nans) sign clear or -0, exponent not all ones
-    memcpy(&wbits, &weight, sizeof wbits);
-    AVD_REQUIRE((wbits & 0x7f800000u) != 0x7f800000u && (!(wbits >> 31) || wbits == 0x80000000u), "%s: weight=%g (must be finite and >= 0)",
-                who, (double)weight);
-    AVD_REQUIRE(lo <= hi, "%s: lo=%g > hi=%g", who, (double)lo, (double)hi);
-    an.gains = gains, an.M = M, an.model_a = model_a, an.lo = lo, an.hi = hi, an.weight = weight;
-    an.anchor_loss = anchor_loss;
-    return AVD_OK;
+    AVD_SPLIT_CALL(c, fsplit::PH_BOTH, "avd_learn_set_split_f16x3", gamma);
+    return split_run(c);
 }
 
 // the whole call with the anchored seed (anchor_seed_kernel) and the per-set anchor loss
@@ -2157,18 +2173,14 @@ extern "C" int avd_learn_set_split_anchor_f16x3(const avd_mlp_layout* lay, int n
                                                 const float* s2, const float* agent_weight, float gamma, float high, float* grads,
                                                 float* losses, void* workspace, size_t workspace_bytes, const float* gains, int M,
                                                 int model_a, float lo, float hi, float weight, float* anchor_loss, void* stream) {
-    const char* who = "avd_learn_set_split_anchor_f16x3";
-    int rc = fsplit::check_shape(lay, n_agents, n_sets, who);
-    if (rc) return rc;
-    AnchorArgs an{};
-    rc = anchor_args(who, n_sets, gains, M, model_a, lo, hi, weight, anchor_loss, an);
-    if (rc) return rc;
-    return split_entry(fsplit::PH_BOTH, who, lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2, agent_weight, gamma, high,
-                       grads, losses, workspace, workspace_bytes, stream, &an, nullptr);
+    AVD_SPLIT_CALL(c, fsplit::PH_BOTH, "avd_learn_set_split_anchor_f16x3", gamma);
+    const AnchorArgs an = anchor_args(gains, M, model_a, lo, hi, weight, anchor_loss);
+    c.an = &an;
+    return split_run(c);
 }
 
 // the whole call with target policy smoothing (csrc/smooth.hip) between the target actor's head and the target critic's; gains == null:
-// the un-anchored seed. sigma == 0: no launch, the call IS the un-smoothed one. Everything refused here is refused before a HIP call.
+// the un-anchored seed. sigma == 0: no launch, the call IS the un-smoothed one.
 extern "C" int avd_learn_set_split_smooth_f16x3(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
                                                 const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
                                                 const float* s2, const float* agent_weight, float gamma, float high, float* grads,
@@ -2176,22 +2188,11 @@ extern "C" int avd_learn_set_split_smooth_f16x3(const avd_mlp_layout* lay, int n
                                                 int model_a, float lo, float hi, float weight, float* anchor_loss, float sigma,
                                                 float noise_clip, uint64_t seed, uint64_t counter, const uint64_t* d_seeds, int E,
                                                 void* stream) {
-    const char* who = "avd_learn_set_split_smooth_f16x3";
-    int rc = fsplit::check_shape(lay, n_agents, n_sets, who);
-    if (rc) return rc;
-    AnchorArgs an{};
-    if (gains) {
-        rc = anchor_args(who, n_sets, gains, M, model_a, lo, hi, weight, anchor_loss, an);
-        if (rc) return rc;
-    }
-    SmoothArgs sm{};
-    sm.M = M, sm.E = E, sm.sigma = sigma, sm.clip = noise_clip, sm.lo = lo, sm.hi = hi, sm.seed = seed, sm.counter = counter, sm.seeds = d_seeds;
-    rc = check_smooth(who, sm);  // (csrc/smooth.hip: built without -fno-honor-nans, so its NaN tests are plain comparisons)
-    if (rc) return rc;
-    AVD_REQUIRE(n_sets % ((long)E * M) == 0, "%s: n_sets=%d M=%d E=%d (n_sets must be a multiple of E x M)", who, n_sets, M, E);
-    AVD_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
-    return split_entry(fsplit::PH_BOTH, who, lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2, agent_weight, gamma, high,
-                       grads, losses, workspace, workspace_bytes, stream, gains ? &an : nullptr, sigma == 0.f ? nullptr : &sm);
+    AVD_SPLIT_CALL(c, fsplit::PH_BOTH, "avd_learn_set_split_smooth_f16x3", gamma);
+    const AnchorArgs an = anchor_args(gains, M, model_a, lo, hi, weight, anchor_loss);
+    const SmoothArgs sm = smooth_args(M, E, sigma, noise_clip, lo, hi, seed, counter, d_seeds);
+    c.an = gains ? &an : nullptr, c.smo = &sm;
+    return split_run(c);
 }
 
 // a hyperparameter sweep: the whole call with each weight set's gamma from d_hp (set j: row (j / set_block) % n_groups) in the TD epilogue
@@ -2201,9 +2202,10 @@ extern "C" int avd_learn_set_split_hp_f16x3(const avd_mlp_layout* lay, int n_age
                                             void* workspace, size_t workspace_bytes, const avd_hparams* d_hp, int n_groups, int set_block,
                                             void* stream) {
     AVD_REQUIRE_HP("avd_learn_set_split_hp_f16x3", d_hp, n_groups, set_block, n_sets);
-    return split_entry(fsplit::PH_BOTH, "avd_learn_set_split_hp_f16x3", lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2,
-                       agent_weight, 0.f, high, grads, losses, workspace, workspace_bytes, stream, nullptr, nullptr,
-                       HpRef{d_hp, n_groups, set_block});
+    AVD_SPLIT_CALL(c, fsplit::PH_BOTH, "avd_learn_set_split_hp_f16x3", 0.f);
+    const HpRef hp{d_hp, n_groups, set_block};
+    c.hp = &hp;
+    return split_run(c);
 }
 
 // deprecated alias (r03's name: the operand pairs were bf16 then; every pair has been fp16 since r04)
@@ -2219,32 +2221,27 @@ extern "C" int avd_learn_set_split_critic(const avd_mlp_layout* lay, int n_agent
                                           const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
                                           const float* s2, const float* agent_weight, float gamma, float high, float* grads,
                                           float* losses, void* workspace, size_t workspace_bytes, void* stream) {
-    return split_entry(fsplit::PH_CRITIC, "avd_learn_set_split_critic", lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2,
-                       agent_weight, gamma, high, grads, losses, workspace, workspace_bytes, stream, nullptr, nullptr);
+    AVD_SPLIT_CALL(c, fsplit::PH_CRITIC, "avd_learn_set_split_critic", gamma);
+    return split_run(c);
 }
 
 // The TD-only call: the critic block and the critic loss, nothing of the actor's half of the chain (fsplit::run, PH_TD). The smoothing
-// arguments as in avd_learn_set_split_smooth_f16x3; sigma == 0: no smoothing launch. Everything refused here is refused before a HIP call.
+// arguments as in avd_learn_set_split_smooth_f16x3; sigma == 0: no smoothing launch.
 extern "C" int avd_learn_set_split_td_f16x3(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
                                             const float* theta_t, const float* stats_t, const float* s, const float* a, const float* r,
                                             const float* s2, const float* agent_weight, float gamma, float high, float* grads,
                                             float* losses, void* workspace, size_t workspace_bytes, float sigma, float noise_clip, float lo,
                                             float hi, uint64_t seed, uint64_t counter, const uint64_t* d_seeds, int E, int M, void* stream) {
-    const char* who = "avd_learn_set_split_td_f16x3";
-    int rc = fsplit::check_shape(lay, n_agents, n_sets, who);
-    if (rc) return rc;
-    SmoothArgs sm{};
-    sm.M = M, sm.E = E, sm.sigma = sigma, sm.clip = noise_clip, sm.lo = lo, sm.hi = hi, sm.seed = seed, sm.counter = counter, sm.seeds = d_seeds;
-    rc = check_smooth(who, sm);
-    if (rc) return rc;
-    AVD_REQUIRE(n_sets % ((long)E * M) == 0, "%s: n_sets=%d M=%d E=%d (n_sets must be a multiple of E x M)", who, n_sets, M, E);
-    AVD_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
-    return split_entry(fsplit::PH_TD, who, lay, n_agents, n_sets, theta, stats, theta_t, stats_t, s, a, r, s2, agent_weight, gamma, high, grads,
-                       losses, workspace, workspace_bytes, stream, nullptr, sigma == 0.f ? nullptr : &sm);
+    AVD_SPLIT_CALL(c, fsplit::PH_TD, "avd_learn_set_split_td_f16x3", gamma);
+    const SmoothArgs sm = smooth_args(M, E, sigma, noise_clip, lo, hi, seed, counter, d_seeds);
+    c.smo = &sm;
+    return split_run(c);
 }
 
 extern "C" int avd_learn_set_split_actor(const avd_mlp_layout* lay, int n_agents, int n_sets, const float* theta, const float* stats,
                                          const float* s, float high, float* grads, void* workspace, size_t workspace_bytes, void* stream) {
-    return split_entry(fsplit::PH_ACTOR, "avd_learn_set_split_actor", lay, n_agents, n_sets, theta, stats, nullptr, nullptr, s, nullptr, nullptr,
-                       nullptr, nullptr, 0.f, high, grads, nullptr, workspace, workspace_bytes, stream, nullptr, nullptr);
+    const float *theta_t = nullptr, *stats_t = nullptr, *a = nullptr, *r = nullptr, *s2 = nullptr, *agent_weight = nullptr;  // (takes none of
+    float* losses = nullptr;  // these: it reads the online weights, the states and what the critic phase left in the workspace)
+    AVD_SPLIT_CALL(c, fsplit::PH_ACTOR, "avd_learn_set_split_actor", 0.f);
+    return split_run(c);
 }

@@ -36,6 +36,13 @@ def is_gradient_updates_enabled(conf):
     return conf.aggregation_method == conf.gradients
 
 
+def can_share_sets(conf):
+    """Whether the agents of a run may share one weight set per vehicle slot: interfrl + gradients with every step federated -- the
+    only regime in which every platoon's agent m holds the same weights after every step (the set learners' regime)."""
+    return (is_fed_enabled(conf) and conf.fed_method == conf.interfrl and is_gradient_updates_enabled(conf)
+            and conf.fed_update_delay_steps == 1 and conf.fed_update_count == 1 and conf.fed_cutoff_ratio >= 1.0)
+
+
 def is_model_weight_updates_enabled(conf):
     return conf.aggregation_method == conf.weights
 
@@ -211,9 +218,7 @@ def check_anchor(conf, anchor, shared_engine=None, world_size=1, hparams=None, o
     if shared_engine != "fused3":
         raise ValueError(f"an anchor needs shared_engine='fused3' (the split set learner holds the anchored seed; the per-agent engines "
                          f"and the bf16 set learners have none), got shared_engine={shared_engine!r}")
-    can_share = (is_fed_enabled(conf) and conf.fed_method == conf.interfrl and is_gradient_updates_enabled(conf)
-                 and conf.fed_update_delay_steps == 1 and conf.fed_update_count == 1 and conf.fed_cutoff_ratio >= 1.0)
-    if not can_share or (shared_sets is not None and not shared_sets):
+    if not can_share_sets(conf) or (shared_sets is not None and not shared_sets):
         raise ValueError("an anchor needs shared weight sets: interfrl + gradients with every step federated (the fused3 engine's regime)")
     if hparams is not None:
         raise ValueError("an anchor does not combine with a hyperparameter sweep or PBT (hparams=...): the table-driven learn call has no "
@@ -324,9 +329,7 @@ def check_target_noise(target_noise, conf=None, shared_engine="fused3", rng="dev
     if conf is not None:
         if conf.framework == conf.cntrl:
             raise ValueError("target noise needs the decentralized framework (the split set learner's)")
-        can_share = (is_fed_enabled(conf) and conf.fed_method == conf.interfrl and is_gradient_updates_enabled(conf)
-                     and conf.fed_update_delay_steps == 1 and conf.fed_update_count == 1 and conf.fed_cutoff_ratio >= 1.0)
-        if not can_share or (shared_sets is not None and not shared_sets):
+        if not can_share_sets(conf) or (shared_sets is not None and not shared_sets):
             raise ValueError("target noise needs shared weight sets: interfrl + gradients with every step federated (the fused3 engine's "
                              "regime)")
     return tn
@@ -373,9 +376,7 @@ def check_policy_delay(policy_delay, conf=None, shared_engine="fused3", rng="dev
     if conf is not None:
         if conf.framework == conf.cntrl:
             raise ValueError("policy delay needs the decentralized framework (the split set learner's)")
-        can_share = (is_fed_enabled(conf) and conf.fed_method == conf.interfrl and is_gradient_updates_enabled(conf)
-                     and conf.fed_update_delay_steps == 1 and conf.fed_update_count == 1 and conf.fed_cutoff_ratio >= 1.0)
-        if not can_share or (shared_sets is not None and not shared_sets):
+        if not can_share_sets(conf) or (shared_sets is not None and not shared_sets):
             raise ValueError("policy delay needs shared weight sets: interfrl + gradients with every step federated (the fused3 engine's "
                              "regime)")
     return int(d)
@@ -476,44 +477,30 @@ class VecTrainer:
         policy calls inside the hold. d = 1 trains bit for bit what None trains, through the new update entry. check_policy_delay says
         what it needs (as target_noise). None: nothing is allocated, today's entry points run."""
         conf.refresh()
+        def ranks():  # of `group`; asked for where a check needs them, so that a group refused before that is never asked
+            if group is None:
+                return 1
+            import torch.distributed as _td
+            return _td.get_world_size(group)
+
         self.levels = self.manoeuvres = self.lead = None
         self.residual = None
         if residual is not None:
-            ranks = 1
-            if group is not None:
-                import torch.distributed as _td
-                ranks = _td.get_world_size(group)
-            self.residual = check_residual(conf, residual, rng, ranks, fused_step, hparams)
+            self.residual = check_residual(conf, residual, rng, ranks(), fused_step, hparams)
         self.res_gains = self.applied = None
         self.warm_start = self.warm_start_losses = None
         if warm_start is not None:
-            ranks = 1
-            if group is not None:
-                import torch.distributed as _td
-                ranks = _td.get_world_size(group)
-            self.warm_start = check_warm_start(conf, warm_start, rng, ranks, hparams, residual)
+            self.warm_start = check_warm_start(conf, warm_start, rng, ranks(), hparams, residual)
         self.actor_hold = check_actor_hold(actor_hold, hparams)
         self.anchor = self.anchor_gains = self.anchor_loss = self.anchor_loss_first = self.anchor_weight = None
         if anchor is not None:
-            ranks = 1
-            if group is not None:
-                import torch.distributed as _td
-                ranks = _td.get_world_size(group)
-            self.anchor = check_anchor(conf, anchor, shared_engine, ranks, hparams, overlap_allreduce, shared_sets)
+            self.anchor = check_anchor(conf, anchor, shared_engine, ranks(), hparams, overlap_allreduce, shared_sets)
         self.target_noise = None
         if target_noise is not None:
-            ranks = 1
-            if group is not None:
-                import torch.distributed as _td
-                ranks = _td.get_world_size(group)
-            self.target_noise = check_target_noise(target_noise, conf, shared_engine, rng, ranks, hparams, overlap_allreduce, shared_sets)
+            self.target_noise = check_target_noise(target_noise, conf, shared_engine, rng, ranks(), hparams, overlap_allreduce, shared_sets)
         self.policy_delay = None
         if policy_delay is not None:
-            ranks = 1
-            if group is not None:
-                import torch.distributed as _td
-                ranks = _td.get_world_size(group)
-            self.policy_delay = check_policy_delay(policy_delay, conf, shared_engine, rng, ranks, hparams, overlap_allreduce, shared_sets)
+            self.policy_delay = check_policy_delay(policy_delay, conf, shared_engine, rng, ranks(), hparams, overlap_allreduce, shared_sets)
         self.policy_call = True  # whether the last learner call moved the actors and the targets (always, without a delay)
         self.learner_calls = 0  # steps that passed the replay gate (what actor_hold counts)
         if train_disturb is not None:
@@ -555,9 +542,7 @@ class VecTrainer:
         self.n_agents = n_agents
         self.ou = vec.VecOUNoise(n_agents, conf, self.device, rng=rng, seed=seed or 0, seeds=self.seeds, distinct_seeds=distinct)
         fed = is_fed_enabled(conf)
-        can_share = (fed and conf.fed_method == conf.interfrl and is_gradient_updates_enabled(conf)
-                     and conf.fed_update_delay_steps == 1 and conf.fed_update_count == 1
-                     and conf.fed_cutoff_ratio >= 1.0)
+        can_share = can_share_sets(conf)
         self.shared = can_share if shared_sets is None else bool(shared_sets)
         if self.shared and not can_share:
             raise ValueError("shared weight sets are only exact for interfrl+gradients with every step federated")
@@ -663,12 +648,8 @@ class VecTrainer:
         # this step's any-terminal flag has already travelled with it
         self._xbuf = None
         self._flag_exchanged = False
-        ws = 1
-        if group is not None:
-            import torch.distributed as _td
-            ws = _td.get_world_size(group)
-        self._equal_shards = abs(self.total_platoons - self.P * ws) < 0.5
-        self.world_size = ws
+        self.world_size = ranks()
+        self._equal_shards = abs(self.total_platoons - self.P * self.world_size) < 0.5
         self._keep = None  # retention of the best actors seen (enable_keep_best); None: nothing allocated, no entry point called
         self._step_parity = 0
         self._added = False

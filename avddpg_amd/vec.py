@@ -718,29 +718,44 @@ class AgentGroup:
         Returns the mean gradient per set [n_sets, theta_size]."""
         if self.hp is not None and not (split and phase is None):
             self._no_hp("learn_set_fused (bf16 operands, or a phase of the split call)")
+        if split:
+            if phase not in (None, "critic", "actor"):
+                raise _hip.AvdError(f"phase={phase!r}")
+            entry, tail = "avd_learn_set_split_" + (phase or "f16x3"), tuple
+            if self.hp is not None:  # a sweep: each set's gamma from the table (avd_learn_set_split_hp_f16x3)
+                tbl, E, blk = self.hp
+                entry, tail = "avd_learn_set_split_hp_f16x3", lambda: (ptr(tbl), E, blk)
+            return self._split_learn(entry, (s, a, r, s2, n_agents, agent_weight), grads, losses, tail=tail)
         self._check_agent_major(s, a, r, s2, n_agents, agent_weight)
         if grads is None:
             grads = torch.empty(self.n_sets, self.lay.theta_size, dtype=torch.float32, device=self.device)
-        wsf, fn, attr = (("avd_learn_set_split_workspace", "avd_learn_set_split_f16x3", "_fsplit_ws") if split else
-                         ("avd_learn_set_fused_workspace", "avd_learn_set_fused_bf16", "_fset_ws"))
-        ws = self._workspace(attr, wsf, n_agents)
-        if phase is not None and not split:
+        ws = self._workspace("_fset_ws", "avd_learn_set_fused_workspace", n_agents)
+        if phase is not None:
             raise _hip.AvdError("phase= needs split=True (csrc/fsplit.hip)")
-        if phase == "actor":
-            call("avd_learn_set_split_actor", self._layp, n_agents, self.n_sets, ptr(self.theta), ptr(self.stats), ptr(s), self.high,
-                 ptr(grads), ptr(ws), ws.numel(), stream_handle())
-            return grads
-        if phase not in (None, "critic"):
-            raise _hip.AvdError(f"phase={phase!r}")
-        if self.hp is not None:  # a sweep: each set's gamma from the table (avd_learn_set_split_hp_f16x3)
-            tbl, E, blk = self.hp
-            call("avd_learn_set_split_hp_f16x3", self._layp, n_agents, self.n_sets, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
-                 ptr(self.stats_t), ptr(s), ptr(a), ptr(r), ptr(s2), ptr(agent_weight), self.high, ptr(grads), ptr(losses), ptr(ws),
-                 ws.numel(), ptr(tbl), E, blk, stream_handle())
-            return grads
-        call("avd_learn_set_split_critic" if phase == "critic" else fn, self._layp, n_agents, self.n_sets, ptr(self.theta), ptr(self.stats),
-             ptr(self.theta_t), ptr(self.stats_t), ptr(s), ptr(a), ptr(r), ptr(s2), ptr(agent_weight), self.config.gamma, self.high,
-             ptr(grads), ptr(losses), ptr(ws), ws.numel(), stream_handle())
+        call("avd_learn_set_fused_bf16", self._layp, n_agents, self.n_sets, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
+             ptr(self.stats_t), ptr(s), ptr(a), ptr(r), ptr(s2), ptr(agent_weight), self.config.gamma, self.high, ptr(grads), ptr(losses),
+             ptr(ws), ws.numel(), stream_handle())
+        return grads
+
+    def _split_learn(self, entry, batch, grads, losses, what=None, tail=tuple):
+        """What every method of the split set learner (csrc/fsplit.hip) does around its library call. ``batch``: (s, a, r, s2, n_agents,
+        agent_weight). ``what``: the method's name where a sweep has no form of it. ``tail``: makes the entry's own arguments behind the
+        common ones, raising for those it refuses (the anchor's buffers, the seed table), once the batch has passed. Returns ``grads``."""
+        s, a, r, s2, n_agents, agent_weight = batch
+        if what is not None:
+            self._no_hp(what)
+        self._check_agent_major(s, a, r, s2, n_agents, agent_weight)
+        tail = tail()
+        if grads is None:
+            grads = torch.empty(self.n_sets, self.lay.theta_size, dtype=torch.float32, device=self.device)
+        ws = self._workspace("_fsplit_ws", "avd_learn_set_split_workspace", n_agents)
+        if entry.endswith("_actor"):  # the actor phase reads the states alone, and what the critic phase left in `ws`
+            args = (ptr(s), self.high, ptr(grads))
+        else:
+            gamma = () if entry.endswith("_hp_f16x3") else (self.config.gamma,)  # (a sweep reads each set's from its table)
+            args = (ptr(self.theta_t), ptr(self.stats_t), ptr(s), ptr(a), ptr(r), ptr(s2), ptr(agent_weight), *gamma, self.high, ptr(grads),
+                    ptr(losses))
+        call(entry, self._layp, n_agents, self.n_sets, ptr(self.theta), ptr(self.stats), *args, ptr(ws), ws.numel(), *tail, stream_handle())
         return grads
 
     def learn_set_split(self, s, a, r, s2, n_agents, grads=None, losses=None, agent_weight=None):
@@ -752,18 +767,13 @@ class AgentGroup:
         -mean(w q(s, mu)) + weight * mean(w (mu - u*)^2), u* the clipped linear law of ``gains`` [M, 4] (float32, on the device; set j uses
         row j % M, the seed-batch layout) on the sampled state. ``anchor_loss`` [n_sets] receives mean(w (mu - u*)^2) per set -- not times
         ``weight``, and for weight 0 too. The critic block and ``losses`` are learn_set_split's bit for bit."""
-        self._no_hp("learn_set_split_anchor")
-        self._check_agent_major(s, a, r, s2, n_agents, agent_weight)
-        self._check_anchor_buffers(gains, anchor_loss)
-        if grads is None:
-            grads = torch.empty(self.n_sets, self.lay.theta_size, dtype=torch.float32, device=self.device)
-        ws = self._workspace("_fsplit_ws", "avd_learn_set_split_workspace", n_agents)
-        c = self.config
-        call("avd_learn_set_split_anchor_f16x3", self._layp, n_agents, self.n_sets, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
-             ptr(self.stats_t), ptr(s), ptr(a), ptr(r), ptr(s2), ptr(agent_weight), c.gamma, self.high, ptr(grads), ptr(losses), ptr(ws),
-             ws.numel(), ptr(gains), int(gains.shape[0]), int(c.model == c.modelA), float(c.action_low), float(c.action_high), float(weight),
-             ptr(anchor_loss), stream_handle())
-        return grads
+        def tail():
+            self._check_anchor_buffers(gains, anchor_loss)
+            c = self.config
+            return (ptr(gains), int(gains.shape[0]), int(c.model == c.modelA), float(c.action_low), float(c.action_high), float(weight),
+                    ptr(anchor_loss))
+        return self._split_learn("avd_learn_set_split_anchor_f16x3", (s, a, r, s2, n_agents, agent_weight), grads, losses,
+                                 "learn_set_split_anchor", tail)
 
     def _check_anchor_buffers(self, gains, anchor_loss):
         """The anchored calls take raw pointers to the gain table [M, 4] and the per-set anchor loss [n_sets]."""
@@ -807,28 +817,24 @@ class AgentGroup:
         trainer.TargetNoise; sigma 0 is the un-smoothed call bit for bit. ``anchor``: None, or (gains [M, 4], weight, anchor_loss [n_sets])
         as learn_set_split_anchor takes them -- the anchored seed then runs in the same call. The actor block of the gradients and
         losses[:, 1] do not depend on the noise."""
-        self._no_hp("learn_set_split_smooth")
-        self._check_agent_major(s, a, r, s2, n_agents, agent_weight)
-        sigma, clip, key, seeds, E = self._smooth_key(noise, seed, d_seeds, "learn_set_split_smooth")
-        gains = weight = anchor_loss = None
-        if anchor is not None:
-            gains, weight, anchor_loss = anchor
-            self._check_anchor_buffers(gains, anchor_loss)
-            if M is None:
-                M = int(gains.shape[0])
-            elif int(M) != int(gains.shape[0]):
-                raise _hip.AvdError(f"learn_set_split_smooth: M={M} but the anchor's table has {gains.shape[0]} rows (one M serves both)")
-        if M is None:
-            M = self.n_sets // E
-        if grads is None:
-            grads = torch.empty(self.n_sets, self.lay.theta_size, dtype=torch.float32, device=self.device)
-        ws = self._workspace("_fsplit_ws", "avd_learn_set_split_workspace", n_agents)
-        c = self.config
-        call("avd_learn_set_split_smooth_f16x3", self._layp, n_agents, self.n_sets, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
-             ptr(self.stats_t), ptr(s), ptr(a), ptr(r), ptr(s2), ptr(agent_weight), c.gamma, self.high, ptr(grads), ptr(losses), ptr(ws),
-             ws.numel(), ptr(gains), int(M), int(c.model == c.modelA), float(c.action_low), float(c.action_high),
-             0.0 if weight is None else float(weight), ptr(anchor_loss), sigma, clip, key, int(counter), seeds, E, stream_handle())
-        return grads
+        def tail():
+            sigma, clip, key, seeds, E = self._smooth_key(noise, seed, d_seeds, "learn_set_split_smooth")
+            gains = weight = anchor_loss = None
+            m = M
+            if anchor is not None:
+                gains, weight, anchor_loss = anchor
+                self._check_anchor_buffers(gains, anchor_loss)
+                if m is None:
+                    m = int(gains.shape[0])
+                elif int(m) != int(gains.shape[0]):
+                    raise _hip.AvdError(f"learn_set_split_smooth: M={m} but the anchor's table has {gains.shape[0]} rows (one M serves both)")
+            if m is None:
+                m = self.n_sets // E
+            c = self.config
+            return (ptr(gains), int(m), int(c.model == c.modelA), float(c.action_low), float(c.action_high),
+                    0.0 if weight is None else float(weight), ptr(anchor_loss), sigma, clip, key, int(counter), seeds, E)
+        return self._split_learn("avd_learn_set_split_smooth_f16x3", (s, a, r, s2, n_agents, agent_weight), grads, losses,
+                                 "learn_set_split_smooth", tail)
 
     def _check_agent_major(self, s, a, r, s2, n_agents, agent_weight):
         """The set learners of csrc/fset.hip / fsplit.hip take raw pointers to tightly packed AGENT-major f32 batches
@@ -912,21 +918,14 @@ class AgentGroup:
         critic block of the gradients and losses[:, 0] are learn_set_split's bit for bit -- with ``noise`` (a trainer.TargetNoise), the
         smoothed call's for the same ``counter``, ``seed`` / ``d_seeds`` and M -- while nothing of the actor's half of the chain runs:
         the actor block is all zero and losses[:, 1] is 0."""
-        self._no_hp("learn_set_split_td")
-        self._check_agent_major(s, a, r, s2, n_agents, agent_weight)
-        sigma, clip, key, seeds, E = 0.0, float("inf"), 0, None, 1
-        if noise is not None:
-            sigma, clip, key, seeds, E = self._smooth_key(noise, seed, d_seeds, "learn_set_split_td")
-        if M is None:
-            M = self.n_sets // E
-        if grads is None:
-            grads = torch.empty(self.n_sets, self.lay.theta_size, dtype=torch.float32, device=self.device)
-        ws = self._workspace("_fsplit_ws", "avd_learn_set_split_workspace", n_agents)
-        c = self.config
-        call("avd_learn_set_split_td_f16x3", self._layp, n_agents, self.n_sets, ptr(self.theta), ptr(self.stats), ptr(self.theta_t),
-             ptr(self.stats_t), ptr(s), ptr(a), ptr(r), ptr(s2), ptr(agent_weight), c.gamma, self.high, ptr(grads), ptr(losses), ptr(ws),
-             ws.numel(), sigma, clip, float(c.action_low), float(c.action_high), key, int(counter), seeds, E, int(M), stream_handle())
-        return grads
+        def tail():
+            sigma, clip, key, seeds, E = 0.0, float("inf"), 0, None, 1
+            if noise is not None:
+                sigma, clip, key, seeds, E = self._smooth_key(noise, seed, d_seeds, "learn_set_split_td")
+            c = self.config
+            return (sigma, clip, float(c.action_low), float(c.action_high), key, int(counter), seeds, E, int(self.n_sets // E if M is None else M))
+        return self._split_learn("avd_learn_set_split_td_f16x3", (s, a, r, s2, n_agents, agent_weight), grads, losses, "learn_set_split_td",
+                                 tail)
 
     def apply_intra(self, grads, P, M, weights=None, lead_skip=False, lo=0, hi=None, stream=None, advance=True):
         """intrafrl + gradients (workers/trainer.py:417-431) for platoons [lo, hi): every agent of a platoon steps with the (weighted)
